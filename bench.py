@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- MCRAW frame-decode throughput on MI355X (one process per GPU).
 
-    python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -13,10 +13,19 @@ frames that are already resident in HBM.  Workload = BASELINE.json config 3:
 data path (weak scaling: every rank decodes its own frames); torch.distributed
 only carries the barriers and the max of the per-rank times.
 
-Timed region: W warm-up steps, then rounds of exactly K steps, each round
-bracketed by barrier + synchronise; as many rounds as it takes to cover 0.5 s
-(motioncam_decoder_amd/benchlib.py).  `ms_per_step` is the median round / K,
-the spread is reported beside it.
+Timed region: half a second of untimed steps (the clocks), W warm-up steps,
+then exactly K steps bracketed by barrier + synchronise, with no events in the
+stream; `ms_per_step` is their time / K (the max over ranks).  That is all a
+plain run measures.  With --full the timed region is rounds of exactly K
+steps, each bracketed the same way, as many as it takes to cover 0.5 s
+(motioncam_decoder_amd/benchlib.py), every eighth k7_tiles launch between two
+event records; `ms_per_step` is then the median round / K, the spread is
+reported beside it, and the other legs (roofline, verification, host buffers,
+other workloads, CPU baseline) follow.
+
+--dump-outputs DIR writes what the last timed step decoded (rank 0's frames:
+seeded samples of every frame and a checksum of each whole frame, float .npy
+files); the inputs are seeded, the same in every run with the same arguments.
 
 Prints ONE JSON line on rank 0 (see the keys at the bottom).
 """
@@ -50,8 +59,15 @@ def parse():
     ap.add_argument("--config", type=int, default=3, choices=(3, 5),
                     help="BASELINE.json config: 3 = 240 x 3840x2160 per GPU (the metric's workload), 5 = 120 x 7680x4320 per GPU")
     ap.add_argument("--frames", type=int, default=None, help="frames per GPU per step (default: the config's)")
-    ap.add_argument("--min-seconds", type=float, default=0.5, help="timed rounds cover at least this long")
-    ap.add_argument("--no-pcie", action="store_true", help="skip the host-buffer (PCIe-inclusive) legs")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: timed rounds with their spread, the roofline and per-kernel figures, "
+                         "verification and frame checksums, the HBM calibration, the other distribution, the host-buffer, "
+                         "pool, legacy, rotating-output, config 5, config 4 and post-stage legs and the CPU baseline (a plain "
+                         "run times exactly --steps steps, once, and prints the headline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one decoded (rank 0's frames) as float .npy files to DIR")
+    ap.add_argument("--min-seconds", type=float, default=0.5, help="--full: timed rounds cover at least this long")
+    ap.add_argument("--no-pcie", action="store_true", help="--full: skip the host-buffer (PCIe-inclusive) legs")
     ap.add_argument("--dist-backend", default="nccl", help="process-group backend (nccl = RCCL; gloo for rehearsals)")
     ap.add_argument("--all-on-device0", action="store_true",
                     help="rehearsal of the multi-rank path on a one-GPU box: every rank decodes on cuda:0 (use with --dist-backend gloo)")
@@ -68,10 +84,12 @@ def parse():
                          "buffers each, so that the chain-resolve kernels of one batch run beside the HBM-bound unpack "
                          "kernel of the previous one (2 streams: +4 %% throughput, but the overlapped unpack launches "
                          "each get 4-5 %% longer, so the default stays 1)")
-    ap.add_argument("--no-also", action="store_true", help="skip the second (other distribution) measurement")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU work per cpu_baseline pass (all threads, then one thread)")
+    ap.add_argument("--no-also", action="store_true", help="--full: skip the second (other distribution) measurement")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: CPU work per cpu_baseline pass (all threads, then one thread)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     cw, ch, cf = {3: (3840, 2160, 240), 5: (7680, 4320, 120)}[a.config]
     a.width = a.width or cw
     a.height = a.height or ch
@@ -148,10 +166,12 @@ class Workload:
         if os.environ.get("MCRAW_BENCH_DEBUG"):
             print("buffers: in %#x (%d B) out %#x (%d B)" % (self.t_in.data_ptr(), self.t_in.numel(), self.t_out.data_ptr(), self.t_out.numel()),
                   file=sys.stderr, flush=True)
-        orc = L.oracle()
-        used = [orc.mcraw_oracle_len_used7(L._ptr(p[1]), p[1].size) for p in self.pairs]
-        assert all(u > 0 for u in used)
-        self.in_bytes = sum(used[i % d] for i in range(self.frames))      # algorithmic input bytes / step
+        self.in_bytes = None
+        if args.full:  # (the roofline figures' byte count, from the oracle: nothing a plain run reports needs it)
+            orc = L.oracle()
+            used = [orc.mcraw_oracle_len_used7(L._ptr(p[1]), p[1].size) for p in self.pairs]
+            assert all(u > 0 for u in used)
+            self.in_bytes = sum(used[i % d] for i in range(self.frames))  # algorithmic input bytes / step
         self.out_bytes = self.frames * self.out_stride                    # algorithmic output bytes / step
         self.pixels = self.frames * self.w * self.h
         self.bpp = 8.0 * sum(lens) / (d * self.w * self.h)
@@ -188,9 +208,27 @@ def frame_checksums(torch, comm, wl, nglobal):
     return vals, hashlib.sha1(struct.pack("<%dI" % len(vals), *vals)).hexdigest()[:16]
 
 
+def dump_outputs(torch, wl, steps, out_dir, samples=32768, budget=48 << 20):
+    """--dump-outputs: what the last timed step decoded -- this rank's frames, the uint16 mosaics a caller receives -- as
+    out_dir/decoded_sample.npy, float32 [frames, n]: every frame's samples at the same n positions (seeded: the same in every
+    run), n <= `samples` and the file <= `budget` bytes; and out_dir/frame_checksums.npy, float64 [frames]: the 32-bit
+    position-weighted checksum of every whole frame (buffer_checksum), so that a difference outside the sample shows too."""
+    os.makedirs(out_dir, exist_ok=True)
+    t = wl.t_outs[(steps - 1) % len(wl.t_outs)]  # (step i writes buffer set i % streams)
+    npx = wl.w * wl.h
+    n = max(1, min(npx, samples, budget // (4 * wl.frames)))
+    pos = np.sort(np.random.default_rng(0).choice(npx, size=n, replace=False))
+    px = t.view(torch.int16).view(wl.frames, npx)[:, torch.from_numpy(pos).to(t.device)].to(torch.int32) & 0xFFFF
+    np.save(os.path.join(out_dir, "decoded_sample.npy"), px.cpu().numpy().astype(np.float32))
+    sums = [buffer_checksum(torch, t[i * wl.out_stride:(i + 1) * wl.out_stride]) for i in range(wl.frames)]
+    np.save(os.path.join(out_dir, "frame_checksums.npy"), np.array(sums, dtype=np.float64))
+
+
 def run_timed(torch, comm, ctx, M, wl, args):
-    """Warm-up, the timed rounds, then k7_side's time (untimed).  Returns (round times [s, max over ranks], {k7_side ms, the
-    XCD mapping, this rank's own ms per step}, (k7_tiles ms summed over the sampled launches of the timed rounds, launches), ok)."""
+    """Warm-up and the timed steps.  A plain run: exactly `steps` timed steps, no events in the stream; returns ([their time,
+    s, max over ranks], None, None, None).  --full: the timed rounds, then k7_side's time (untimed); returns (round times [s, max
+    over ranks], {k7_side ms, the XCD mapping, this rank's own ms per step}, (k7_tiles ms summed over the sampled launches of the
+    timed rounds, launches), ok)."""
     from motioncam_decoder_amd import benchlib
     steps, warmup = args.steps, args.warmup
     nset = len(wl.desc_sets)
@@ -202,22 +240,29 @@ def run_timed(torch, comm, ctx, M, wl, args):
     written, status = ctx.decode_batch(wl.descs, mem=M.MEM_DEVICE, stream=streams[0].cuda_stream, want_status=True)
     assert all(s == 0 for s in status), "decode failed: %s" % [hex(s) for s in status if s][:4]
     assert all(wr == wl.w * wl.h for wr in written)
-    ok = wl.verify(torch, sorted({0, wl.frames // 2, wl.frames - 1}))
+    ok = wl.verify(torch, sorted({0, wl.frames // 2, wl.frames - 1})) if args.full else None
     for _ in range(6):  # (the library times its XCD mapping of k7_tiles on the first launches on a new set of buffers)
         ctx.decode_batch(wl.descs, mem=M.MEM_DEVICE, stream=streams[0].cuda_stream, want_status=False)
     torch.cuda.synchronize()
     for t in wl.t_outs:
         t.zero_()
+
+    def step(i):
+        ctx.decode_batch(wl.desc_sets[i % nset], mem=M.MEM_DEVICE, stream=streams[i % nset].cuda_stream, want_status=False)
+
+    if not args.full:
+        # the GPU at its working clocks before the warm-up proper: untimed steps for half a second, in bursts of eight (in a
+        # --full run the first round of K steps, which sizes the rounds, plays that part)
+        t0 = time.perf_counter()
+        while time.perf_counter() - t0 < 0.5:
+            for i in range(8):
+                step(i)
+            torch.cuda.synchronize()
+        return [benchlib.timed_steps(step, torch.cuda.synchronize, comm, steps, max(0, warmup - 1))], None, None, None
     # timed: only the roofline kernel carries events, and only every eighth launch of it (a bracket is two event
     # records in the stream, several microseconds; the sampled launches give the same average duration)
     ctx.profile(only=("k7_tiles",), every=8)
     ctx.kernel_ms("k7_tiles", reset=True)
-    counted = [0]
-
-    def step(i):
-        ctx.decode_batch(wl.desc_sets[i % nset], mem=M.MEM_DEVICE, stream=streams[i % nset].cuda_stream, want_status=False)
-        counted[0] += 1
-
     own = []
     times = benchlib.timed_rounds(step, torch.cuda.synchronize, comm, steps, max(0, warmup - 1), args.min_seconds, own=own)
     st = ctx.synchronize(wl.frames)
@@ -675,7 +720,7 @@ def legacy_leg(torch, ctx, M, L, dev, n=32, w=4000, h=3000, nbits=12, sigma=12.0
 def config5_leg(torch, ctx, M, L, dev, n=120, w=7680, h=4320, nbits=12, sigma=12.0, reps=8, distinct=4):
     """One rank's share of BASELINE config 5 (120 frames of 7680x4320, 12-bit, type 7, resident in HBM): the step against the HBM
     peak, and its two kernels -- an 8K frame's side streams are four times as long as a UHD frame's, and k7_side follows a chain.
-    Not the bench line; `python bench.py --config 5` times the same workload with rounds and spread."""
+    Not the bench line; `python bench.py --config 5 --full` times the same workload with rounds and spread."""
     def one(seed):
         img = L.synth_image(w, h, nbits, 1, sigma, seed)
         return img, L.encode7(img)
@@ -839,24 +884,65 @@ def stub_main(args):
     assert len(mine) == args.frames
     per_step = 0.002 * (1 + rank)  # the slower rank sets the job's time
     own = []
-    times = benchlib.timed_rounds(lambda i: time.sleep(per_step), lambda: None, comm, args.steps, args.warmup, args.min_seconds, own=own)
-    ok = bool(comm.min([1.0])[0] > 0.5)
-    per_rank = {"ms_per_step": [round(v, 4) for v in comm.gather(1e3 * sorted(own)[len(own) // 2] / args.steps)]} if world > 1 else None
+    calls = [0]
+
+    def step(i):
+        time.sleep(per_step)
+        calls[0] += 1
+
+    if args.full:
+        times = benchlib.timed_rounds(step, lambda: None, comm, args.steps, args.warmup, args.min_seconds, own=own)
+    else:
+        times = [benchlib.timed_steps(step, lambda: None, comm, args.steps, args.warmup)]
+    calls = [int(v) for v in comm.gather(calls[0])]  # (every rank's steps, warm-up included)
+    if args.full:
+        ok = bool(comm.min([1.0])[0] > 0.5)
+        per_rank = {"ms_per_step": [round(v, 4) for v in comm.gather(1e3 * sorted(own)[len(own) // 2] / args.steps)]} if world > 1 else None
     if comm.rank == 0:
         st = benchlib.round_stats(times, args.steps)
         pixels = world * args.frames * args.width * args.height
-        print(json.dumps({"metric": METRIC, "value": round(pixels / (st["median"] * 1e-3) / 1e6, 1), "unit": "MPixels/s",
-                          "n_gpus": world, "ranks_seen": ranks_seen, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(st["median"], 4),
-                          "ms_per_step_min": round(st["min"], 4), "ms_per_step_max": round(st["max"], 4), "rounds": st["rounds"],
-                          "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u16",
-                          "data": "stub: no decode (CPU rehearsal of the multi-rank protocol)", "bit_exact": ok, "per_rank": per_rank,
-                          "config": {"workload": "stub", "frames_per_gpu": args.frames}}), flush=True)
+        out = {"metric": METRIC, "value": round(pixels / (st["median"] * 1e-3) / 1e6, 1), "unit": "MPixels/s",
+               "n_gpus": world, "ranks_seen": ranks_seen, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(st["median"], 4),
+               "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u16",
+               "full": bool(args.full), "data": "stub: no decode (CPU rehearsal of the multi-rank protocol)", "steps_run": calls,
+               "config": {"workload": "stub", "frames_per_gpu": args.frames}}
+        if args.full:
+            out.update({"ms_per_step_min": round(st["min"], 4), "ms_per_step_max": round(st["max"], 4), "rounds": st["rounds"],
+                        "bit_exact": ok, "per_rank": per_rank})
+        print(json.dumps(out), flush=True)
     if comm.dist:
         dist_mod.barrier()
         dist_mod.destroy_process_group()
 
 
 METRIC = "MPixels/s unpacked + achieved HBM GB/s %peak, 4K 12-bit, 1/2/4/8 GPUs"
+
+
+def headline(args, world, ranks_seen, wl, st, numa):
+    """The keys of the result line that a plain run prints (--full adds the rest): the rate from the timed steps' ms per step."""
+    wname = "%dx%d %d-bit type-7 x %d frames/GPU, %s" % (args.width, args.height, args.nbits, args.frames,
+                                                         "Nat (smooth field + noise sigma %g)" % args.sigma if args.dist == "nat" else "U (uniform)")
+    return {
+        "metric": METRIC,
+        "value": round(world * wl.pixels / (st["median"] * 1e-3) / 1e6, 1),
+        "unit": "MPixels/s",
+        "n_gpus": world,
+        "ranks_seen": ranks_seen,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(st["median"], 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u16",
+        "full": bool(args.full),
+        "data": "synthetic: %d seeded distinct frames per rank (own encoder), replicated to %d frames at distinct "
+                "HBM addresses; inputs resident in HBM before the timed region" % (len(wl.pairs), args.frames),
+        "frames_per_s": round(world * args.frames / (st["median"] * 1e-3), 1),
+        "config": {"workload": wname, "baseline_config": args.config, "frames_per_gpu": args.frames, "width": args.width,
+                   "height": args.height, "bits": args.nbits, "encoding": 7, "input_bpp": round(wl.bpp, 2),
+                   "sharding": "frame index, no collective", "streams": args.streams, "numa": numa},
+    }
 
 
 def visible_gpus():
@@ -941,22 +1027,36 @@ def main():
     L = synth_lib()
     if ctx is None:
         ctx = M.Context(local)
-    ctx.profile(True)
+    if args.full:
+        ctx.profile(True)
     ranks_seen = int(round(comm.sum([1.0])[0]))  # every rank that takes part says so: the line's n_gpus is counted, not assumed
     if ranks_seen != args.gpus:
         print("bench.py: %d rank(s) took part, --gpus %d" % (ranks_seen, args.gpus), file=sys.stderr)
         return 2
 
-    dists = [args.dist] + ([] if args.no_also else [("u" if args.dist == "nat" else "nat")])  # (at every N: a SCALE line is as complete as the N = 1 line)
+    also = [] if args.no_also or not args.full else [("u" if args.dist == "nat" else "nat")]
+    dists = [args.dist] + also  # (at every N: a SCALE line is as complete as the N = 1 line)
     results = {}
-    calib = box_calibration(torch, dev) if rank == 0 else None
+    calib = box_calibration(torch, dev) if rank == 0 and args.full else None
     for d in dists:
         # weak scaling: the job is world * frames frames, frame i decoded by rank i % world
         wl = Workload(torch, M, L, dev, args, d, shard.shard_frames(world * args.frames, rank, world))
         times, kms, tiles, ok = run_timed(torch, comm, ctx, M, wl, args)
-        results[d] = dict(wl=wl, times=times, kms=kms, tiles=tiles, ok=bool(comm.min([1.0 if ok else 0.0])[0] > 0.5))
+        if args.dump_outputs and d == args.dist and rank == 0:  # (before any other leg writes to the output buffers)
+            dump_outputs(torch, wl, args.steps, args.dump_outputs)
+        results[d] = dict(wl=wl, times=times, kms=kms, tiles=tiles,
+                          ok=bool(comm.min([1.0 if ok else 0.0])[0] > 0.5) if args.full else None)
 
     wl = results[args.dist]["wl"]
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline(args, world, ranks_seen, wl, benchlib.round_stats(results[args.dist]["times"], args.steps),
+                                      numa)), flush=True)
+        ctx.close()
+        if use_dist:
+            dist_mod.barrier()
+            dist_mod.destroy_process_group()
+        return 0
     extra = {}
     sums, digest = frame_checksums(torch, comm, wl, args.frames)
     # which GPU every rank decoded on (PCI bus of its device), gathered like the checksums
@@ -1032,30 +1132,15 @@ def main():
             }
 
         s = summarize(results[args.dist])
-        wname = "%dx%d %d-bit type-7 x %d frames/GPU, %s" % (args.width, args.height, args.nbits, args.frames,
-                                                             "Nat (smooth field + noise sigma %g)" % args.sigma if args.dist == "nat" else "U (uniform)")
         key = "%dx%d_%dbit_%d_%s" % (args.width, args.height, args.nbits, args.frames, args.dist)
         traffic, traffic_src = traffic_from_profile(key, s["bytes_per_launch"])
         prof_ms, prof_path = profile_launch_ms(args.dist) if (args.width, args.height, args.frames, args.nbits) == (3840, 2160, 240, 12) else (None, None)
-        out = {
-            "metric": METRIC,
-            "value": round(s["mpix_s"], 1),
-            "unit": "MPixels/s",
-            "n_gpus": world,
-            "ranks_seen": ranks_seen,
+        out = headline(args, world, ranks_seen, wl, s["st"], numa)
+        out.update({
             "devices": devices_seen,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(s["st"]["median"], 4),
             "ms_per_step_min": round(s["st"]["min"], 4),
             "ms_per_step_max": round(s["st"]["max"], 4),
             "rounds": s["st"]["rounds"],
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u16",
-            "data": "synthetic: %d seeded distinct frames per rank (own encoder), replicated to %d frames at distinct "
-                    "HBM addresses; inputs resident in HBM before the timed region" % (len(wl.pairs), args.frames),
             "bit_exact": results[args.dist]["ok"],
             "frame_checksums": {"frames": len(sums), "digest": digest, "first": sums[:4],
                                 "note": "32-bit checksums of the decoded global frames 0..%d of the job (frame g = image g mod %d, decoded by "
@@ -1064,10 +1149,6 @@ def main():
             "distinct_devices": len(set(devices_seen)),
             "bit_exact_scope": "sanity flag: sampled output frames of the timed buffers equal the images the encoder was given; "
                                "parity against the oracle / reference is what tests/ -m gpu checks",
-            "frames_per_s": round(world * args.frames / (s["st"]["median"] * 1e-3), 1),
-            "config": {"workload": wname, "baseline_config": args.config, "frames_per_gpu": args.frames, "width": args.width,
-                       "height": args.height, "bits": args.nbits, "encoding": 7, "input_bpp": round(s["bpp"], 2),
-                       "sharding": "frame index, no collective", "streams": args.streams, "numa": numa},
             "roofline": {"bound": "hbm", "kernel": "k7_tiles", "achieved": round(s["achieved_gbs"], 1), "peak": HBM_PEAK_GBS,
                          "unit": "GB/s", "frac": round(s["achieved_gbs"] / HBM_PEAK_GBS, 4),
                          # the whole step (every launch of the path) against the same peak: what a caller sees
@@ -1088,7 +1169,7 @@ def main():
             "kernels_ms_per_step": {"k7_tiles": round(s["tiles_ms_per_launch"], 4), "k7_side": round(s["kms"]["k7_side"], 4)},
             "kernels_ms_per_step_note": "k7_tiles: every 8th launch of the timed rounds between two event records (= roofline.avg_launch_ms); "
                                         "k7_side: every launch of six untimed steps behind them; the rest of ms_per_step is two kernel boundaries",
-        }
+        })
         if world > 1:
             out["per_rank"] = per_rank
         calib_after = box_calibration(torch, dev)

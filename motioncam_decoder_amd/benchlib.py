@@ -1,8 +1,8 @@
 """Measurement plumbing shared by bench.py and its CPU test (tests/test_bench_dist_gloo.py).
 
-Nothing here decodes anything: process placement (NUMA), the timed-region protocol
-(warm-up, rounds of exactly K steps between barrier + synchronise, max over ranks),
-and small statistics.  bench.py passes the step function; the gloo test passes a stub.
+Nothing here decodes anything: process placement (NUMA), the timed-region protocols
+(warm-up, then exactly K steps -- a plain run -- or rounds of exactly K steps -- --full --,
+between barrier + synchronise, max over ranks), and small statistics.  bench.py passes the step function; the gloo test passes a stub.
 """
 import glob
 import math
@@ -151,6 +151,23 @@ class Comm:
         """Every rank's `value` (a number), by rank: one all-reduce of a one-hot vector."""
         w, r = self.world, self.rank
         return self.sum([float(value) if i == r else 0.0 for i in range(w)])
+
+
+def timed_steps(step, sync, comm, steps, warmup):
+    """A plain bench.py run: `warmup` untimed steps, then EXACTLY `steps` timed steps, bracketed by barrier + sync on both
+    sides.  Returns their time in seconds, the MAX over ranks."""
+    for i in range(warmup):
+        step(i)
+    sync()
+    comm.barrier()
+    sync()
+    t0 = time.perf_counter()
+    for i in range(steps):
+        step(i)
+    sync()
+    t = time.perf_counter() - t0
+    comm.barrier()
+    return comm.max([t])[0]
 
 
 def timed_rounds(step, sync, comm, steps, warmup, min_seconds=0.5, max_rounds=200, own=None):

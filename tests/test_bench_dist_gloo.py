@@ -26,7 +26,7 @@ def _free_port():
 def test_bench_protocol_world2_gloo():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--stub-decode", "--min-seconds", "0.1", "--frames", "5"]
+           "--stub-decode", "--min-seconds", "0.1", "--frames", "5", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=280, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -43,6 +43,27 @@ def test_bench_protocol_world2_gloo():
     # every rank's own time beside the max over ranks: the stub's rank 1 takes twice as long per step as its rank 0
     own = d["per_rank"]["ms_per_step"]
     assert len(own) == 2 and 1.9 <= own[0] < own[1] <= d["ms_per_step"] + 0.5 and own[1] > 3.9
+
+
+@pytest.mark.timeout(300)
+def test_bench_plain_run_times_exactly_the_steps_asked_for_gloo():
+    """A plain run (no --full): `--warmup` untimed steps, then exactly `--steps` timed steps, once, on every rank; the line
+    holds the headline alone."""
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "7", "--warmup", "2",
+           "--stub-decode", "--frames", "5"]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=280, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == 2 and d["steps"] == 7 and d["warmup"] == 2 and d["full"] is False
+    assert d["steps_run"] == [2 + 7, 2 + 7]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert not {"rounds", "ms_per_step_min", "ms_per_step_max", "per_rank", "bit_exact"} & set(d)
+    assert 3.9 <= d["ms_per_step"] < 60.0  # the slower rank (4 ms per step) sets the time
+    assert abs(d["value"] - 2 * 5 * 3840 * 2160 / (d["ms_per_step"] * 1e-3) / 1e6) < 1.0
 
 
 @pytest.mark.timeout(300)
@@ -83,6 +104,9 @@ def test_timed_rounds_single_process():
     assert len(calls) == 2 + 4 + 4            # warm-up, the sizing round, one timed round
     st = benchlib.round_stats([0.004, 0.008, 0.006], 2)
     assert st == {"median": 3.0, "min": 2.0, "max": 4.0, "rounds": 3}
+    calls = []
+    t = benchlib.timed_steps(lambda i: calls.append(i), lambda: None, comm, steps=4, warmup=2)
+    assert calls == [0, 1, 0, 1, 2, 3] and t >= 0.0  # warm-up, then exactly the timed steps
 
 
 def test_numa_helpers_do_not_need_a_gpu():

@@ -161,7 +161,7 @@ def test_bench_multi_rank_path_on_one_gpu(tmp_path):
     # `bench.py --gpus 2` starts its two ranks itself (a child process: torch.distributed.run); the line says how many took part
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
            "--frames", "24", "--distinct", "4", "--min-seconds", "0.05", "--dist-backend", "gloo", "--all-on-device0",
-           "--cpu-seconds", "0.2"]
+           "--cpu-seconds", "0.2", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -174,7 +174,7 @@ def test_bench_multi_rank_path_on_one_gpu(tmp_path):
     assert d["roofline"]["step_frac"] > 0 and d["roofline"]["frac"] > 0
     # the job's first 24 frames decode to the same pixels whether one rank holds them all or two share them
     r1 = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--frames", "24",
-                         "--distinct", "4", "--min-seconds", "0.02", "--no-pcie", "--no-cpu", "--no-also"], capture_output=True, text=True,
+                         "--distinct", "4", "--min-seconds", "0.02", "--no-pcie", "--no-cpu", "--no-also", "--full"], capture_output=True, text=True,
                         timeout=600, cwd=root, env=env)
     assert r1.returncode == 0, r1.stderr[-3000:]
     d1 = json.loads([ln for ln in r1.stdout.splitlines() if ln.startswith("{")][0])
@@ -182,6 +182,46 @@ def test_bench_multi_rank_path_on_one_gpu(tmp_path):
     assert d1["frame_checksums"]["frames"] == 24 and d1["frame_checksums"] == d["frame_checksums"]
     p = d["pcie_inclusive"]
     assert p["bit_exact"] is True and p["frames_per_rank"] == 24 and abs(p["frames_per_s"] - 2 * p["frames_per_s_per_rank"]) < 1.0
+
+
+def test_bench_plain_run_and_its_dumped_outputs(tmp_path):
+    """`bench.py` without --full: the headline alone, from exactly --steps timed steps; --dump-outputs writes what the last
+    timed step decoded -- the same arrays as a --full run's, equal to the encoder's images at the sampled positions, and
+    whose per-frame checksums are the ones the --full line reports."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    base = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--frames", "24",
+            "--distinct", "4"]
+    lines = {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--min-seconds", "0.02", "--no-pcie", "--no-cpu", "--no-also"])):
+        r = subprocess.run(base + extra + ["--dump-outputs", str(tmp_path / mode)], capture_output=True, text=True, timeout=600,
+                           cwd=root, env=env)
+        assert r.returncode == 0, r.stderr[-3000:]
+        ls = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(ls) == 1, r.stdout
+        lines[mode] = json.loads(ls[0])
+    d = lines["plain"]
+    assert d["full"] is False and d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1
+    assert d["unit"] == "MPixels/s" and d["higher_is_better"] is True and d["dtype"] == "u16" and d["ms_per_step"] > 0
+    assert abs(d["value"] / (24 * 3840 * 2160 / (d["ms_per_step"] * 1e-3) / 1e6) - 1.0) < 2e-3  # (ms_per_step is rounded)
+    assert not {"roofline", "rounds", "bit_exact", "frame_checksums", "also_u", "cpu_baseline"} & set(d)
+    assert lines["full"]["full"] is True and lines["full"]["bit_exact"] is True
+    sample = np.load(str(tmp_path / "plain" / "decoded_sample.npy"))
+    sums = np.load(str(tmp_path / "plain" / "frame_checksums.npy"))
+    assert sample.dtype == np.float32 and sample.shape == (24, 32768) and sums.dtype == np.float64 and sums.shape == (24,)
+    assert np.array_equal(sample, np.load(str(tmp_path / "full" / "decoded_sample.npy")))
+    assert np.array_equal(sums, np.load(str(tmp_path / "full" / "frame_checksums.npy")))
+    assert [int(v) for v in sums[:4]] == lines["full"]["frame_checksums"]["first"]
+    # the sampled positions: seeded, the same in every frame; local frame i is image i mod 4 (seed 3000 + i mod 4, config 3)
+    pos = np.sort(np.random.default_rng(0).choice(3840 * 2160, size=32768, replace=False))
+    for i in range(4):
+        img = L.synth_image(3840, 2160, 12, 1, 12.0, 3000 + i)
+        for f in (i, i + 4, i + 20):
+            assert np.array_equal(sample[f], img.reshape(-1)[pos].astype(np.float32)), f
 
 
 def test_xcd_mapping_is_measured_per_buffer_set_and_kept(gpu_ctx):

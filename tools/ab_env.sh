@@ -4,7 +4,7 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 for i in $(seq 1 ${AB_N:-2}); do for e in ${AB_ENVS:-X=0}; do
   ( IFS=';'; for kv in $e; do export "$kv"; done; unset IFS
-    python3 $R/bench.py --steps 20 --warmup 3 --no-cpu --no-also --no-pcie ${AB_ARGS:-} 2>/tmp/err.txt | grep "^{" > /tmp/line.json )
+    python3 $R/bench.py --full --steps 20 --warmup 3 --no-cpu --no-also --no-pcie ${AB_ARGS:-} 2>/tmp/err.txt | grep "^{" > /tmp/line.json )
   python3 - "$e" <<'PY'
 import json, sys
 try:

@@ -4,7 +4,7 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 for i in $(seq 1 ${AB_N:-3}); do for v in "$@"; do
   if [ $v = cur ]; then unset MCRAW_LIB_PATH; else export MCRAW_LIB_PATH=$R/motioncam_decoder_amd/lib/libmcraw_hip_$v.so; fi
-  python3 $R/bench.py --steps 20 --warmup 3 --no-cpu --no-pcie ${AB_ARGS:-} 2>/tmp/err.txt | grep "^{" > /tmp/line.json
+  python3 $R/bench.py --full --steps 20 --warmup 3 --no-cpu --no-pcie ${AB_ARGS:-} 2>/tmp/err.txt | grep "^{" > /tmp/line.json
   python3 - "$v" <<'PY'
 import json, sys
 try:

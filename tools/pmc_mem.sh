@@ -1,7 +1,7 @@
 #!/bin/bash
 # memory-side counters of k7_tiles (diagnostic): gpurun -- 'bash tools/pmc_mem.sh'
 R=${GRAFT_REPO_ROOT:-$(pwd)}; cd /tmp; export TMPDIR=/tmp
-A="--steps 3 --warmup 1 --no-cpu --no-also"
+A="--full --steps 3 --warmup 1 --no-cpu --no-also"
 rocprofv3 --kernel-trace --output-format csv --pmc TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum TCC_EA0_WRREQ_STALL_sum TCC_EA0_RDREQ_sum -d $R/gpurun_out/pmc_m1 -- python3 $R/bench.py $A > /dev/null 2>&1
 rocprofv3 --kernel-trace --output-format csv --pmc TCC_EA0_RDREQ_32B_sum TCC_HIT_sum TCC_MISS_sum TCC_TAG_STALL_sum -d $R/gpurun_out/pmc_m2 -- python3 $R/bench.py $A > /dev/null 2>&1
 rocprofv3 --kernel-trace --output-format csv --pmc TCC_WRITE_sum TCC_READ_sum TCC_TOO_MANY_EA_WRREQS_STALL_sum TCC_EA0_WRREQ_DRAM_CREDIT_STALL_sum -d $R/gpurun_out/pmc_m3 -- python3 $R/bench.py $A > /dev/null 2>&1

@@ -3,7 +3,7 @@
 # different lengths (MCRAW_XCD_CHUNK: 0 = the grid in eight parts, 1 = plain blockIdx order)
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 for i in $(seq 1 ${N:-4}); do for C in ${CHUNKS:-0 1 64 2048}; do
-  MCRAW_XCD_CHUNK=$C python3 $R/bench.py --steps 10 --warmup 2 --no-cpu --no-also --no-pcie 2>/dev/null | grep "^{" > /tmp/line.json
+  MCRAW_XCD_CHUNK=$C python3 $R/bench.py --full --steps 10 --warmup 2 --no-cpu --no-also --no-pcie 2>/dev/null | grep "^{" > /tmp/line.json
   python3 - <<PY
 import json
 d = json.load(open("/tmp/line.json"))
