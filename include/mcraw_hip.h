@@ -120,6 +120,40 @@ uint64_t mcraw_ctx_last_serial(mcraw_ctx *ctx);
 int mcraw_ctx_batch_status(mcraw_ctx *ctx, uint64_t serial, int32_t *status, int nframes);
 int32_t mcraw_ctx_errors(mcraw_ctx *ctx, int reset);
 
+/* ---- encoder: uint16 mosaics -> type-7 frame buffers ---------------------
+ *
+ * The bytes are exactly those of the project's canonical type-7 writer (the
+ * test synthesiser's mcraw_synth_encode7 with no forced classes and flags 0):
+ * 16-byte header {encW, encH, bits offset, refs offset}, the payload blocks in
+ * tile order at their natural class, then the bits stream and the refs stream
+ * (entry counts rounded up to 64, padded entries 0).  No CPU fallback: without
+ * a device these calls fail. */
+typedef struct mcraw_enc_frame {
+    const uint16_t *in;  /* row-major mosaic, width*height uint16, 2-byte aligned          */
+    int32_t width, height;
+    uint8_t *out;        /* any byte alignment                                             */
+    size_t out_capacity; /* bytes; must be >= mcraw_encode_bound7(width, height)            */
+    uint64_t *len_out;   /* optional, same memory space as out: bytes written, stream order */
+} mcraw_enc_frame;
+/* Exact worst case of an encoded frame: 16 + 128 nblk + 2 (4 + 130 ceil(nblk / 64)) with
+ * nblk = ceil64(width) * ceil4(height) / 64.  Host only, no device needed; 0 for width or height < 1. */
+size_t mcraw_encode_bound7(int width, int height);
+/* Encode `nframes` mosaics; the conventions of mcraw_decode_batch: with MCRAW_MEM_DEVICE the work is
+ * enqueued on `stream` (NULL: the context's stream) and the call synchronises only when `written` or
+ * `status` is requested (len_out gives the sizes in stream order without a synchronisation);
+ * MCRAW_MEM_HOST uploads, encodes and downloads the written bytes before it returns.
+ *   written[i] : bytes written for frame i (0 on failure), or NULL
+ *   status[i]  : MCRAW_E_ARGS (width or height < 1, width*height >= 2^31, a bound >= 2^32, a NULL or odd
+ *                pointer), MCRAW_E_CAPACITY (out_capacity below the bound: nothing is written),
+ *                MCRAW_E_DEVICE, or 0
+ * Encode batches do not touch the decode side's state: they take no serial number and leave
+ * mcraw_ctx_last_serial / mcraw_ctx_batch_status / mcraw_ctx_errors as they are.
+ * Returns 0, or a negative value when the batch could not be submitted. */
+int mcraw_encode_batch(mcraw_ctx *ctx, const mcraw_enc_frame *frames, int nframes, int mem, void *stream,
+                       size_t *written, int32_t *status);
+/* Single frame, host pointers, on the process-wide default context (beside mcraw_decode7): returns the
+ * bytes written, or 0 on failure. */
+size_t mcraw_encode7(uint8_t *output, size_t capacity, const uint16_t *input, int width, int height);
 /* ---- several GPUs of one node (device pool) --------------------------------------------------
  *
  * The reference walks a clip frame by frame on one thread (example.cpp:187-195 over
@@ -193,7 +227,9 @@ uint32_t mcraw_tile_order(uint32_t b, uint32_t n, uint32_t runs);
 #define MCRAW_K7_TILES   3 /* tile decode (the roofline kernel)   */
                            /* ids 4 and 5 are retired (former legacy map / resolve kernels) */
 #define MCRAW_K6_DECODE  6 /* legacy: the whole decode (one launch) */
-#define MCRAW_K_COUNT    7
+#define MCRAW_K7E_PAYLOAD 7 /* encoder: payload of every frame (mcraw_encode_batch) */
+#define MCRAW_K7E_SIDE   8 /* encoder: side streams, header, byte count           */
+#define MCRAW_K_COUNT    9
 
 /* hipEvent bracketing of kernel launches on the launch stream: 0 = off, 1 = every
  * kernel, MCRAW_PROFILE_ONLY(id) [| MCRAW_PROFILE_ONLY(id2) ...] = those kernels only

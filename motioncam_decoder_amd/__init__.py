@@ -11,8 +11,8 @@ present, every decode call raises.
 import ctypes as C
 import os
 
-__all__ = ["lib_path", "load", "Context", "Pool", "Frame", "McrawError", "TYPE_LEGACY", "TYPE_BLOCK",
-           "MEM_DEVICE", "MEM_HOST", "KERNELS", "ABI_SYMBOLS"]
+__all__ = ["lib_path", "load", "Context", "Pool", "Frame", "EncFrame", "McrawError", "TYPE_LEGACY", "TYPE_BLOCK",
+           "MEM_DEVICE", "MEM_HOST", "KERNELS", "ENC_KERNELS", "ABI_SYMBOLS", "encode_bound7"]
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 
@@ -25,6 +25,7 @@ MEM_HOST = 1
 E_ARGS, E_HEADER, E_TRUNCATED, E_SIDESTREAM, E_CAPACITY, E_DEVICE = 0x1, 0x2, 0x4, 0x8, 0x10, 0x100
 
 KERNELS = {"k7_side": 0, "k7_tiles": 3, "k6_decode": 6}
+ENC_KERNELS = {"k7e_payload": 7, "k7e_side": 8}  # the encoder's launches (mcraw_encode_batch)
 
 # every symbol include/mcraw_hip.h declares
 ABI_SYMBOLS = [
@@ -36,6 +37,7 @@ ABI_SYMBOLS = [
     "mcraw_pool_host_alloc", "mcraw_pool_decode_batch", "mcraw_pool_decode_batch_async", "mcraw_pool_ticket_wait",
     "mcraw_pool_decode_batch_device", "mcraw_ctx_xcd_runs", "mcraw_pool_synchronize", "mcraw_tile_order",
     "mcraw_ctx_last_serial", "mcraw_ctx_batch_status", "mcraw_ctx_errors", "mcraw_ctx_side_parts", "mcraw_ctx_host_way",
+    "mcraw_encode_bound7", "mcraw_encode_batch", "mcraw_encode7",
 ]
 
 POST_BLACK, POST_PACK12, POST_PACK10, POST_PACK14 = 1, 2, 4, 8
@@ -55,6 +57,12 @@ class Frame(C.Structure):
     """struct mcraw_frame (include/mcraw_hip.h)."""
     _fields_ = [("in_", C.c_void_p), ("len", C.c_size_t), ("width", C.c_int32), ("height", C.c_int32),
                 ("type", C.c_int32), ("reserved", C.c_int32), ("out", C.c_void_p), ("out_capacity", C.c_size_t)]
+
+
+class EncFrame(C.Structure):
+    """struct mcraw_enc_frame (include/mcraw_hip.h)."""
+    _fields_ = [("in_", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("out", C.c_void_p),
+                ("out_capacity", C.c_size_t), ("len_out", C.c_void_p)]
 
 
 def lib_path():
@@ -167,8 +175,20 @@ def load():
     lib.mcraw_pool_decode_batch_async.argtypes = [C.c_void_p, C.POINTER(Frame), C.c_int, C.POINTER(C.c_void_p)]
     lib.mcraw_pool_ticket_wait.restype = C.c_int
     lib.mcraw_pool_ticket_wait.argtypes = [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]
+    lib.mcraw_encode_bound7.restype = C.c_size_t
+    lib.mcraw_encode_bound7.argtypes = [C.c_int, C.c_int]
+    lib.mcraw_encode_batch.restype = C.c_int
+    lib.mcraw_encode_batch.argtypes = [C.c_void_p, C.POINTER(EncFrame), C.c_int, C.c_int, C.c_void_p,
+                                       C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]
+    lib.mcraw_encode7.restype = C.c_size_t
+    lib.mcraw_encode7.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int]
     _lib = lib
     return lib
+
+
+def encode_bound7(w, h):
+    """Exact worst-case size in bytes of a type-7 frame of w x h samples (host only, no GPU needed)."""
+    return int(load().mcraw_encode_bound7(int(w), int(h)))
 
 
 class Pool:
@@ -323,6 +343,32 @@ class Context:
             return list(written), list(status)
         return None
 
+    @staticmethod
+    def make_enc_frames(descs):
+        """descs: iterable of (in_ptr, width, height, out_ptr, out_capacity[, len_out_ptr])."""
+        descs = list(descs)
+        arr = (EncFrame * len(descs))()
+        for i, d in enumerate(descs):
+            inp, w, h, outp, cap = d[:5]
+            arr[i] = EncFrame(inp, w, h, outp, cap, d[5] if len(d) > 5 else None)
+        return arr
+
+    def encode_batch(self, frames, mem=MEM_DEVICE, stream=None, want_status=True):
+        """frames: ctypes array from make_enc_frames.  Returns (written bytes, status) lists when
+        want_status (synchronises), else None (asynchronous on `stream`; len_out gives the sizes)."""
+        n = len(frames)
+        if want_status:
+            written = (C.c_size_t * max(n, 1))()
+            status = (C.c_int32 * max(n, 1))()
+            rc = self._lib.mcraw_encode_batch(self._h, frames, n, mem, stream, written, status)
+        else:
+            rc = self._lib.mcraw_encode_batch(self._h, frames, n, mem, stream, None, None)
+        if rc != 0:
+            raise McrawError("mcraw_encode_batch failed (%d): %s" % (rc, self._lib.mcraw_last_error().decode()))
+        if want_status:
+            return list(written)[:n], list(status)[:n]
+        return None
+
     def decode_batch_async(self, frames):
         """Host-memory batch, queued: returns a ticket for wait()."""
         t = C.c_void_p()
@@ -396,7 +442,7 @@ class Context:
         if only:
             mode = 0
             for name in only:
-                mode |= 2 << KERNELS[name]
+                mode |= 2 << (KERNELS[name] if name in KERNELS else ENC_KERNELS[name])
         else:
             mode = 1 if enable else 0
         self._lib.mcraw_ctx_profile(self._h, mode)
@@ -404,7 +450,8 @@ class Context:
     def kernel_ms(self, name, reset=False):
         ms = C.c_double()
         n = C.c_int()
-        rc = self._lib.mcraw_ctx_kernel_ms(self._h, KERNELS[name], C.byref(ms), C.byref(n), 1 if reset else 0)
+        kid = KERNELS[name] if name in KERNELS else ENC_KERNELS[name]
+        rc = self._lib.mcraw_ctx_kernel_ms(self._h, kid, C.byref(ms), C.byref(n), 1 if reset else 0)
         if rc != 0:
             raise McrawError("mcraw_ctx_kernel_ms failed (%d)" % rc)
         return ms.value, n.value

@@ -204,6 +204,7 @@ void mcraw_ctx_destroy(mcraw_ctx *c)
         if (s.decoded) (void)hipEventDestroy(s.decoded);
         if (s.stream) (void)hipStreamDestroy(s.stream);
     };
+    enc_release(c->enc);
     for (Slot &s : c->slots)
         release(s);
     for (Slot &s : c->dslots)
@@ -440,6 +441,24 @@ size_t mcraw_decode7(uint16_t *output, int width, int height, const uint8_t *inp
 size_t mcraw_decode6(uint16_t *output, int width, int height, const uint8_t *input, size_t len)
 {
     return decode_one(MCRAW_TYPE_LEGACY, output, width, height, input, len);
+}
+
+size_t mcraw_encode7(uint8_t *output, size_t capacity, const uint16_t *input, int width, int height)
+{
+    mcraw_ctx *c = default_ctx();
+    if (!c)
+        return 0;
+    mcraw_enc_frame f{};
+    f.in = input;
+    f.width = width;
+    f.height = height;
+    f.out = output;
+    f.out_capacity = capacity;
+    size_t written = 0;
+    int32_t status = 0;
+    if (mcraw_encode_batch(c, &f, 1, MCRAW_MEM_HOST, nullptr, &written, &status) != 0 || status != 0)
+        return 0;
+    return written;
 }
 
 int mcraw_ctx_set_post(mcraw_ctx *c, const mcraw_post *post)

@@ -29,6 +29,8 @@ namespace mcraw {
 void launch_k7(const Work7 &W, uint32_t stage, hipStream_t st);
 void launch_k6_decode(const Plan6 *plans, const uint32_t *wg_tab, uint32_t stage0, uint32_t nwg, const Look6 &look,
                       uint32_t *tickets, uint32_t epoch, int nframes, uint32_t smax, const Post &post, hipStream_t st);
+struct EncState; // the encoder's arena of a context (mcraw_encode7.hip)
+void enc_release(EncState *e);
 } // namespace mcraw
 
 struct mcraw_ticket;
@@ -250,6 +252,7 @@ struct mcraw_ctx {
     uint64_t serial = 0;
     std::deque<std::pair<uint64_t, std::vector<int32_t>>> settled;
     int32_t sticky = 0;
+    mcraw::EncState *enc = nullptr; // encode batches (mcraw_encode_batch): workspace of their own, grown on first use
     std::mutex mu;
 };
 

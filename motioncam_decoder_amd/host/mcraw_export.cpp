@@ -2,9 +2,13 @@
 //
 //   mcraw_export <file.mcraw> [-n frames] [-o outdir] [--single [--reuse]] [--no-write] [--black] [--bits 10|12|14|auto] [--pinned]
 //   mcraw_export <file.mcraw> --remux <out.mcraw> [-n frames] [--sorted-index] [--audio-inline] [--no-audio-index]
+//   mcraw_export <file.mcraw> --transcode <out.mcraw> [-n frames] [--sorted-index] [--audio-inline] [--no-audio-index]
 //
 // --remux copies the first N frames (compressed as they are), their metadata and the audio into a new container
 // written by motioncam::Writer (host only, no GPU): a trim / repair tool, and the round trip of the build's own writer.
+// --transcode writes the same container with every frame (type 6 or 7) decoded on the GPU and encoded again on the GPU
+// as type 7 (mcraw_encode_batch), its metadata copied with "compressionType" 7: upgrades a legacy clip once, so that
+// every later decode of it runs at the type-7 rate.
 //
 // Writes outdir/frame_%06d.u16 (width*height uint16 LE, row-major Bayer mosaic) for the
 // first N frames (by timestamp) and outdir/audio.s16 (interleaved PCM), and prints one line
@@ -21,6 +25,7 @@
 
 #include "mcraw_hip.h" // mcraw_host_alloc / mcraw_host_free for --pinned
 
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -58,13 +63,78 @@ static bool writeFile(const std::string &path, const void *data, size_t size)
     return ok;
 }
 
+// --transcode: batches of frames decoded on the GPU (Decoder::loadFrames), encoded on the GPU (mcraw_encode_batch), written
+// with the container metadata and the audio exactly as --remux writes them.
+static int transcodeClip(motioncam::Decoder &decoder, const std::vector<motioncam::Timestamp> &frames, const std::string &path,
+                         const motioncam::Writer::Options &wopt)
+{
+    mcraw_ctx *ctx = nullptr;
+    if (mcraw_ctx_create(-1, &ctx) != 0) {
+        std::cerr << "Error: " << mcraw_last_error() << std::endl;
+        return 1;
+    }
+    struct Ctx {
+        mcraw_ctx *c;
+        ~Ctx() { mcraw_ctx_destroy(c); }
+    } guard{ctx};
+    std::vector<motioncam::AudioChunk> chunks;
+    decoder.loadAudio(chunks);
+    motioncam::Writer writer(path, decoder.getContainerMetadata(), wopt);
+    constexpr size_t BATCH = 16;
+    size_t bytes_in = 0, bytes_out = 0, a = 0;
+    std::vector<uint8_t> payload;
+    for (size_t first = 0; first < frames.size(); first += BATCH) {
+        const std::vector<motioncam::Timestamp> part(frames.begin() + static_cast<long>(first),
+                                                     frames.begin() + static_cast<long>(std::min(frames.size(), first + BATCH)));
+        std::vector<std::vector<uint8_t>> data;
+        std::vector<nlohmann::json> meta;
+        decoder.loadFrames(part, data, meta);
+        std::vector<std::vector<uint8_t>> enc(part.size());
+        std::vector<mcraw_enc_frame> ef(part.size());
+        for (size_t i = 0; i < part.size(); i++) {
+            const int w = meta[i]["width"], h = meta[i]["height"];
+            enc[i].resize(mcraw_encode_bound7(w, h));
+            ef[i] = mcraw_enc_frame{reinterpret_cast<const uint16_t *>(data[i].data()), w, h, enc[i].data(), enc[i].size(), nullptr};
+        }
+        std::vector<size_t> written(part.size(), 0);
+        std::vector<int32_t> status(part.size(), 0);
+        if (mcraw_encode_batch(ctx, ef.data(), static_cast<int>(part.size()), MCRAW_MEM_HOST, nullptr, written.data(),
+                               status.data()) != 0) {
+            std::cerr << "Error: " << mcraw_last_error() << std::endl;
+            return 1;
+        }
+        for (size_t i = 0; i < part.size(); i++) {
+            if (status[i] != 0 || written[i] == 0) {
+                std::cerr << "Error: frame " << first + i << " could not be encoded (status " << status[i] << ")" << std::endl;
+                return 1;
+            }
+            nlohmann::json m;
+            decoder.loadFramePayload(part[i], payload, m); // (the frame's own metadata as stored, and the bytes it had)
+            bytes_in += payload.size();
+            m["compressionType"] = 7;
+            writer.addFrame(part[i], enc[i].data(), written[i], m);
+            bytes_out += written[i];
+            const size_t k = first + i;
+            for (; !wopt.audioBehindFrames && a < chunks.size() && a * frames.size() < (k + 1) * chunks.size(); a++)
+                writer.addAudio(chunks[a].first, chunks[a].second.data(), chunks[a].second.size());
+        }
+    }
+    for (; a < chunks.size(); a++)
+        writer.addAudio(chunks[a].first, chunks[a].second.data(), chunks[a].second.size());
+    writer.finish();
+    std::cout << "transcoded " << frames.size() << " frames (" << bytes_in << " payload bytes in, " << bytes_out
+              << " payload bytes out, type 7), " << chunks.size() << " audio chunks -> " << path << std::endl;
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     if (argc < 2) {
-        std::cerr << "Usage: mcraw_export <input file> [-n frames] [-o outdir] [--single]" << std::endl;
+        std::cerr << "Usage: mcraw_export <input file> [-n frames] [-o outdir] [--single] [--remux <out.mcraw>] "
+                     "[--transcode <out.mcraw>]" << std::endl;
         return 2;
     }
-    std::string input = argv[1], outdir = ".", remux;
+    std::string input = argv[1], outdir = ".", remux, transcode;
     motioncam::Writer::Options wopt;
     long limit = -1;
     bool single = false, nowrite = false, pinned = false, reuse = false;
@@ -76,6 +146,8 @@ int main(int argc, char **argv)
             outdir = argv[++i];
         else if (!std::strcmp(argv[i], "--remux") && i + 1 < argc)
             remux = argv[++i];
+        else if (!std::strcmp(argv[i], "--transcode") && i + 1 < argc)
+            transcode = argv[++i];
         else if (!std::strcmp(argv[i], "--sorted-index"))
             wopt.indexInArrivalOrder = false;
         else if (!std::strcmp(argv[i], "--audio-inline"))
@@ -109,6 +181,8 @@ int main(int argc, char **argv)
         if (limit >= 0 && static_cast<size_t>(limit) < frames.size())
             frames.resize(static_cast<size_t>(limit));
 
+        if (!transcode.empty())
+            return transcodeClip(decoder, frames, transcode, wopt);
         if (!remux.empty()) {
             std::vector<motioncam::AudioChunk> chunks;
             decoder.loadAudio(chunks);
