@@ -165,6 +165,7 @@ size_t mcraw_encode7(uint8_t *output, size_t capacity, const uint16_t *input, in
 typedef struct mcraw_pool mcraw_pool;
 typedef struct mcraw_pool_ticket mcraw_pool_ticket;
 struct mcraw_post;
+struct mcraw_float_out;
 
 /* The partition rule, usable without a GPU: which member decodes frame `index` (index mod ndevices;
  * -1 on bad arguments), and how many of `nframes` frames member `member` gets. */
@@ -181,6 +182,7 @@ int mcraw_pool_device(const mcraw_pool *pool, int member);    /* its HIP device 
 int mcraw_pool_numa_cpus(const mcraw_pool *pool, int member); /* CPUs its host thread is bound to (0: not bound) */
 mcraw_ctx *mcraw_pool_ctx(mcraw_pool *pool, int member);      /* for the measurement calls below */
 int mcraw_pool_set_post(mcraw_pool *pool, const struct mcraw_post *post);
+int mcraw_pool_set_float_out(mcraw_pool *pool, const struct mcraw_float_out *f); /* every member: mcraw_ctx_set_float_out */
 /* Pinned host memory allocated by the member's own (NUMA-bound) thread: local to its GPU.  Free with mcraw_host_free. */
 void *mcraw_pool_host_alloc(mcraw_pool *pool, int member, size_t bytes);
 /* One batch over all members; the asynchronous form returns when every member has queued its share.
@@ -283,6 +285,40 @@ typedef struct mcraw_post {
     uint16_t black[4];
 } mcraw_post;
 int mcraw_ctx_set_post(mcraw_ctx *ctx, const mcraw_post *post);
+
+/* The other kind of fused stage: normalised float samples, for a model's input (raw denoising, raw-to-RGB networks).
+ * A context has ONE stage: mcraw_ctx_set_float_out replaces any mcraw_ctx_set_post stage, and mcraw_ctx_set_post (NULL
+ * included) replaces a float stage.  It applies to every batch submitted afterwards, in every mode (device and host
+ * memory, tickets, pools, mixed type-6 / type-7 batches); NULL restores the plain uint16 mosaic.  Per sample, at CFA
+ * position p = (row & 1) * 2 + (col & 1), bit-exact:
+ *   inv[p] = 1.0f / (white - (float)black[p])                  (host, IEEE f32 division)
+ *   v      = (float)((int)sample - (int)black[p]) * inv[p]      (the difference is exact; one f32 multiply, RNE; no FMA)
+ *   v      = CLIP ? min(max(v, 0.0f), 1.0f) : v                 (negatives are kept without CLIP)
+ *   out    = v as f32, or rounded to nearest even into f16 (overflow: +inf) / bf16
+ * Layouts: MCRAW_LAYOUT_MOSAIC = width x height row-major, like the uint16 output (any width); MCRAW_LAYOUT_PLANES = four
+ * planes of (height/2) x (width/2), plane-major, position (r, c) to plane plane[p], row r/2, column c/2 (width and height
+ * must be even, else the frame gets MCRAW_E_ARGS and nothing is written).  `out_capacity` still counts uint16 units (2
+ * bytes): f32 needs 2 * width * height, f16 / bf16 width * height (mosaic rows: as far as the rows are written); less gives
+ * MCRAW_E_CAPACITY and nothing is written.  `written` counts samples.  `out` must be 2-byte aligned (f16 / bf16) or
+ * 4-byte aligned (f32: else MCRAW_E_ARGS); the vector-store path takes 16-byte aligned outputs (8-byte for f16 / bf16
+ * planes) and width % 8 == 0.  Rows the frame header does not provide are left untouched.
+ * Rejected (returns < 0, mcraw_last_error says why): an unknown dtype, layout or flag; white <= black[p] for some p;
+ * a white that is not finite; a plane map that is not a permutation of 0..3. */
+#define MCRAW_FLOAT_F32     1
+#define MCRAW_FLOAT_F16     2
+#define MCRAW_FLOAT_BF16    3
+#define MCRAW_LAYOUT_MOSAIC 0  /* width x height, row-major, like the uint16 output            */
+#define MCRAW_LAYOUT_PLANES 1  /* 4 planes of (height/2) x (width/2), plane-major               */
+#define MCRAW_FLOAT_CLIP    1u /* flags: clamp to [0, 1] after normalising                      */
+typedef struct mcraw_float_out {
+    uint32_t dtype;    /* MCRAW_FLOAT_*                                                        */
+    uint32_t layout;   /* MCRAW_LAYOUT_*                                                       */
+    uint32_t flags;    /* MCRAW_FLOAT_CLIP or 0                                                */
+    uint16_t black[4]; /* by CFA position p = (row & 1) * 2 + (col & 1), as mcraw_post         */
+    float white;       /* container "whiteLevel"; must be > every black[p]                     */
+    uint8_t plane[4];  /* PLANES: output plane of CFA position p; a permutation of 0..3         */
+} mcraw_float_out;
+int mcraw_ctx_set_float_out(mcraw_ctx *ctx, const mcraw_float_out *f);
 
 /* ---- environment ------------------------------------------------------------------------------
  * Read when a context (or pool) is created, never afterwards:

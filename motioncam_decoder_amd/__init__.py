@@ -11,8 +11,8 @@ present, every decode call raises.
 import ctypes as C
 import os
 
-__all__ = ["lib_path", "load", "Context", "Pool", "Frame", "EncFrame", "McrawError", "TYPE_LEGACY", "TYPE_BLOCK",
-           "MEM_DEVICE", "MEM_HOST", "KERNELS", "ENC_KERNELS", "ABI_SYMBOLS", "encode_bound7"]
+__all__ = ["lib_path", "load", "Context", "Pool", "Frame", "EncFrame", "FloatOut", "McrawError", "TYPE_LEGACY", "TYPE_BLOCK",
+           "MEM_DEVICE", "MEM_HOST", "KERNELS", "ENC_KERNELS", "ABI_SYMBOLS", "encode_bound7", "cfa_planes"]
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 
@@ -37,7 +37,7 @@ ABI_SYMBOLS = [
     "mcraw_pool_host_alloc", "mcraw_pool_decode_batch", "mcraw_pool_decode_batch_async", "mcraw_pool_ticket_wait",
     "mcraw_pool_decode_batch_device", "mcraw_ctx_xcd_runs", "mcraw_pool_synchronize", "mcraw_tile_order",
     "mcraw_ctx_last_serial", "mcraw_ctx_batch_status", "mcraw_ctx_errors", "mcraw_ctx_side_parts", "mcraw_ctx_host_way",
-    "mcraw_encode_bound7", "mcraw_encode_batch", "mcraw_encode7",
+    "mcraw_encode_bound7", "mcraw_encode_batch", "mcraw_encode7", "mcraw_ctx_set_float_out", "mcraw_pool_set_float_out",
 ]
 
 POST_BLACK, POST_PACK12, POST_PACK10, POST_PACK14 = 1, 2, 4, 8
@@ -51,6 +51,65 @@ class Post(C.Structure):
 
 class McrawError(RuntimeError):
     pass
+
+
+# normalised float output (mcraw_ctx_set_float_out)
+FLOAT_F32, FLOAT_F16, FLOAT_BF16 = 1, 2, 3
+LAYOUT_MOSAIC, LAYOUT_PLANES = 0, 1
+FLOAT_CLIP = 1
+_FLOAT_CODES = {"f32": FLOAT_F32, "f16": FLOAT_F16, "bf16": FLOAT_BF16,
+                "float32": FLOAT_F32, "float16": FLOAT_F16, "bfloat16": FLOAT_BF16}
+_LAYOUTS = {"mosaic": LAYOUT_MOSAIC, "planes": LAYOUT_PLANES}
+# plane of CFA position p = (row & 1) * 2 + (col & 1) that puts R, G (R row), G (B row), B in planes 0..3
+_CFA_PLANES = {"rggb": [0, 1, 2, 3], "bggr": [3, 2, 1, 0], "grbg": [1, 0, 3, 2], "gbrg": [2, 3, 0, 1]}
+
+
+class FloatOut(C.Structure):
+    """struct mcraw_float_out (include/mcraw_hip.h)."""
+    _fields_ = [("dtype", C.c_uint32), ("layout", C.c_uint32), ("flags", C.c_uint32), ("black", C.c_uint16 * 4),
+                ("white", C.c_float), ("plane", C.c_uint8 * 4)]
+
+
+def cfa_planes(arrangement):
+    """The ``plane`` map of set_float_out / decode_tensor that puts R, G (on the R row), G (on the B row), B in planes
+    0..3, from the container's ``sensorArrangment`` ("rggb", "bggr", "grbg" or "gbrg")."""
+    key = str(arrangement).strip().lower()
+    if key not in _CFA_PLANES:
+        raise ValueError("unknown sensorArrangment %r (rggb, bggr, grbg or gbrg)" % (arrangement,))
+    return list(_CFA_PLANES[key])
+
+
+def _float_code(dtype):
+    """MCRAW_FLOAT_* of a torch dtype or of "f32" / "f16" / "bf16" (torch is not needed for the strings)."""
+    if isinstance(dtype, str):
+        code = _FLOAT_CODES.get(dtype.lower())
+    else:
+        code = _FLOAT_CODES.get(str(dtype).replace("torch.", ""))
+    if code is None:
+        raise ValueError("float output dtype must be torch.float32 / float16 / bfloat16 or 'f32' / 'f16' / 'bf16', not %r" % (dtype,))
+    return code
+
+
+def float_out(dtype, white, layout="planes", black=(0, 0, 0, 0), clip=False, plane=None):
+    """The FloatOut struct of these arguments (plane: None = identity)."""
+    if layout not in _LAYOUTS:
+        raise ValueError("layout must be 'planes' or 'mosaic', not %r" % (layout,))
+    f = FloatOut()
+    f.dtype = _float_code(dtype)
+    f.layout = _LAYOUTS[layout]
+    f.flags = FLOAT_CLIP if clip else 0
+    black = list(black)
+    if len(black) != 4:
+        raise ValueError("black: four levels, by CFA position (row & 1) * 2 + (col & 1)")
+    for i in range(4):
+        f.black[i] = int(black[i])
+    f.white = float(white)
+    plane = [0, 1, 2, 3] if plane is None else list(plane)
+    if len(plane) != 4:
+        raise ValueError("plane: four plane indices, by CFA position")
+    for i in range(4):
+        f.plane[i] = int(plane[i])
+    return f
 
 
 class Frame(C.Structure):
@@ -180,6 +239,10 @@ def load():
     lib.mcraw_encode_batch.restype = C.c_int
     lib.mcraw_encode_batch.argtypes = [C.c_void_p, C.POINTER(EncFrame), C.c_int, C.c_int, C.c_void_p,
                                        C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]
+    lib.mcraw_ctx_set_float_out.restype = C.c_int
+    lib.mcraw_ctx_set_float_out.argtypes = [C.c_void_p, C.POINTER(FloatOut)]
+    lib.mcraw_pool_set_float_out.restype = C.c_int
+    lib.mcraw_pool_set_float_out.argtypes = [C.c_void_p, C.POINTER(FloatOut)]
     lib.mcraw_encode7.restype = C.c_size_t
     lib.mcraw_encode7.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int]
     _lib = lib
@@ -243,6 +306,13 @@ class Pool:
         if rc != 0:  # (a rejected stage must not decode plain mosaics silently)
             raise McrawError("mcraw_pool_set_post failed (%d): %s" % (rc, self._lib.mcraw_last_error().decode()))
 
+    def set_float_out(self, dtype, white, layout="planes", black=(0, 0, 0, 0), clip=False, plane=None):
+        """Normalised float output on every member (Context.set_float_out); set_post() goes back to uint16 mosaics."""
+        f = float_out(dtype, white, layout, black, clip, plane)
+        rc = self._lib.mcraw_pool_set_float_out(self._h, C.byref(f))
+        if rc != 0:
+            raise McrawError("mcraw_pool_set_float_out failed (%d): %s" % (rc, self._lib.mcraw_pool_last_error().decode()))
+
     def decode_batch_device(self, frames, want_status=True):
         """frames: ctypes array from Context.make_frames whose in / out pointers live in the HBM of the GPU that decodes
         the frame: frame i on ``devices()[i % size]``.  Returns (written, status); with want_status=False the members
@@ -302,6 +372,8 @@ class Context:
         if rc != 0 or not h.value:
             raise McrawError("mcraw_ctx_create failed (%d): %s" % (rc, self._lib.mcraw_last_error().decode()))
         self._h = h
+        self._device = device
+        self._stage = None  # the stage last set: None (plain mosaic), ("post", kwargs) or ("float", kwargs)
 
     def xcd_runs(self):
         """The XCD mapping the library chose for the current large resident batches (mcraw_ctx_xcd_runs)."""
@@ -435,6 +507,90 @@ class Context:
             rc = self._lib.mcraw_ctx_set_post(self._h, C.byref(p))
         if rc != 0:
             raise McrawError("mcraw_ctx_set_post failed (%d): %s" % (rc, self._lib.mcraw_last_error().decode()))
+        self._stage = ("post", dict(black=black, pack12=pack12, bits=bits)) if (black is not None or nb != 16) else None
+
+    def set_float_out(self, dtype, white, layout="planes", black=(0, 0, 0, 0), clip=False, plane=None):
+        """Normalised float output for the batches to come, in place of the uint16 mosaic (and of any set_post stage):
+        (sample - black[p]) / (white - black[p]) as torch.float32 / float16 / bfloat16 (or "f32" / "f16" / "bf16"),
+        clamped to [0, 1] with clip; layout "mosaic" (width x height) or "planes" (4 planes of height/2 x width/2,
+        CFA position p to plane[p]; cfa_planes() gives R, G, G, B).  set_post() goes back to the uint16 mosaic."""
+        f = float_out(dtype, white, layout, black, clip, plane)
+        rc = self._lib.mcraw_ctx_set_float_out(self._h, C.byref(f))
+        if rc != 0:
+            raise McrawError("mcraw_ctx_set_float_out failed (%d): %s" % (rc, self._lib.mcraw_last_error().decode()))
+        self._stage = ("float", dict(dtype=dtype, white=white, layout=layout, black=tuple(black), clip=clip, plane=plane))
+
+    def _restore_stage(self, stage):
+        if stage is None:
+            self.set_post()
+        elif stage[0] == "post":
+            self.set_post(**stage[1])
+        else:
+            self.set_float_out(**stage[1])
+
+    def _torch_device(self, torch):
+        if self._device >= 0:
+            return torch.device("cuda", self._device)
+        env = os.environ.get("MCRAW_DEVICE")
+        return torch.device("cuda", int(env)) if env else torch.device("cuda", torch.cuda.current_device())
+
+    def decode_tensor(self, inputs, width, height, type, *, dtype, white, layout="planes", black=(0, 0, 0, 0), clip=False,
+                      plane=None, out=None, check=True):
+        """Decode frames of one geometry that are resident in HBM straight into a normalised float tensor on the
+        context's device: (N, 4, height/2, width/2) for layout "planes", (N, height, width) for "mosaic".
+
+        inputs: uint8 CUDA tensors, or (device pointer, length) pairs.  The batch is enqueued on
+        torch.cuda.current_stream(), so torch work queued behind it on that stream sees the result.  check=True
+        synchronises and raises McrawError naming the frames that failed; check=False returns at once.  The stage the
+        context had before the call is restored afterwards."""
+        import torch
+        width, height, n = int(width), int(height), len(inputs)
+        if layout not in _LAYOUTS:
+            raise ValueError("layout must be 'planes' or 'mosaic', not %r" % (layout,))
+        if width <= 0 or height <= 0 or (layout == "planes" and (width % 2 or height % 2)):
+            raise ValueError("decode_tensor: %dx%d frames (the planes layout needs an even width and height)" % (width, height))
+        tdtype = {FLOAT_F32: torch.float32, FLOAT_F16: torch.float16, FLOAT_BF16: torch.bfloat16}[_float_code(dtype)]
+        dev = self._torch_device(torch)
+        shape = (n, 4, height // 2, width // 2) if layout == "planes" else (n, height, width)
+        if out is None:
+            out = torch.empty(shape, dtype=tdtype, device=dev)
+        elif tuple(out.shape) != shape or out.dtype != tdtype or out.device != dev or not out.is_contiguous():
+            raise ValueError("decode_tensor: out must be a contiguous %s tensor of shape %s on %s" % (tdtype, shape, dev))
+        frame_bytes = width * height * out.element_size()
+        descs = []
+        for x in inputs:
+            if isinstance(x, torch.Tensor):
+                if x.dtype != torch.uint8 or x.device != dev or not x.is_contiguous():
+                    raise ValueError("decode_tensor: inputs must be contiguous uint8 tensors on %s" % dev)
+                ptr, ln = x.data_ptr(), x.numel()
+            else:
+                ptr, ln = int(x[0]), int(x[1])
+            descs.append((ptr, ln, width, height, int(type), out.data_ptr() + len(descs) * frame_bytes, frame_bytes // 2))
+        if n == 0:
+            return out
+        cur = torch.cuda.current_stream(dev)
+        # (torch's default stream is the null stream, which the library reads as "the context's own": such a batch runs on a
+        # side stream of this context's that waits for the current stream and is waited for by it -- still no host sync)
+        run = cur
+        if not cur.cuda_stream:
+            if getattr(self, "_side", None) is None:
+                self._side = torch.cuda.Stream(dev)
+            run = self._side
+            run.wait_stream(cur)
+        prev = self._stage
+        self.set_float_out(dtype, white, layout, black, clip, plane)
+        try:
+            res = self.decode_batch(self.make_frames(descs), mem=MEM_DEVICE, stream=C.c_void_p(run.cuda_stream), want_status=check)
+        finally:
+            self._restore_stage(prev)
+            if run is not cur:
+                cur.wait_stream(run)
+        if check:
+            bad = [(i, st) for i, st in enumerate(res[1]) if st != 0]
+            if bad:
+                raise McrawError("decode_tensor: %d of %d frames failed: %s" % (
+                    len(bad), n, ", ".join("frame %d status 0x%x" % b for b in bad[:16])))
+        return out
 
     def profile(self, enable=True, only=None, every=1):
         """Bracket kernel launches with events: all kernels, or just the names in `only`; every `every`-th launch."""

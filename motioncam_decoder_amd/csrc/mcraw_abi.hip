@@ -2,6 +2,8 @@
 // slots (pinned upload buffer + HBM arena + completion event).  The work behind them: mcraw_host.h.
 #include "mcraw_host.h"
 
+#include <cmath>
+
 using namespace mcraw;
 
 std::atomic<int> g_ctx_on_device[64];
@@ -278,7 +280,7 @@ int mcraw_decode_batch_async(mcraw_ctx *c, const mcraw_frame *frames, int nframe
     t->got_status.assign(static_cast<size_t>(nframes), 0);
     constexpr int TRIAL_TICKETS = 12;
     way_from_env(c);
-    const size_t total = host_bytes(frames, nframes);
+    const size_t total = host_bytes(frames, nframes, c->post.mode);
     int way;
     if (total > PIECE_BYTES) { // a large batch as a ticket: compared like the synchronous ones, its time runs until it is waited for
         way = big_way(c, total, &t->big_trial);
@@ -488,6 +490,68 @@ int mcraw_ctx_set_post(mcraw_ctx *c, const mcraw_post *post)
         p.mode |= POST_PACK10;
     if (post->flags & MCRAW_POST_PACK14)
         p.mode |= POST_PACK14;
+    c->post = p;
+    return 0;
+}
+
+// The float stage as the kernels take it (Post), or false with g_err set.
+static bool float_stage(const mcraw_float_out *f, Post *out)
+{
+    static const uint32_t modes[4] = {0u, POST_F32, POST_F16, POST_BF16};
+    if (f->dtype < MCRAW_FLOAT_F32 || f->dtype > MCRAW_FLOAT_BF16) {
+        g_err = "mcraw: unknown float-output dtype";
+        return false;
+    }
+    if (f->layout != MCRAW_LAYOUT_MOSAIC && f->layout != MCRAW_LAYOUT_PLANES) {
+        g_err = "mcraw: unknown float-output layout";
+        return false;
+    }
+    if ((f->flags & ~MCRAW_FLOAT_CLIP) != 0u) {
+        g_err = "mcraw: unknown float-output flags";
+        return false;
+    }
+    if (!std::isfinite(f->white)) {
+        g_err = "mcraw: float-output white level is not finite";
+        return false;
+    }
+    Post p{0, 0, 0};
+    uint32_t seen = 0;
+    for (int k = 0; k < 4; k++) {
+        if (!(f->white > static_cast<float>(f->black[k]))) {
+            g_err = "mcraw: float-output white level must exceed every black level";
+            return false;
+        }
+        if (f->layout == MCRAW_LAYOUT_PLANES) {
+            if (f->plane[k] > 3u || (seen & (1u << f->plane[k]))) {
+                g_err = "mcraw: float-output plane map is not a permutation of 0..3";
+                return false;
+            }
+            seen |= 1u << f->plane[k];
+            p.plane4 |= static_cast<uint32_t>(f->plane[k]) << (8 * k);
+        }
+        // (a volatile divisor: one IEEE f32 division on the host, whatever the compiler's floating-point flags)
+        const volatile float den = f->white - static_cast<float>(f->black[k]);
+        p.inv[k] = 1.0f / den;
+    }
+    p.mode = modes[f->dtype] | (f->layout == MCRAW_LAYOUT_PLANES ? POST_PLANES : 0u);
+    p.black01 = static_cast<uint32_t>(f->black[0]) | (static_cast<uint32_t>(f->black[1]) << 16);
+    p.black23 = static_cast<uint32_t>(f->black[2]) | (static_cast<uint32_t>(f->black[3]) << 16);
+    if (f->flags & MCRAW_FLOAT_CLIP)
+        p.mode |= POST_CLIP;
+    *out = p;
+    return true;
+}
+
+int mcraw_ctx_set_float_out(mcraw_ctx *c, const mcraw_float_out *f)
+{
+    if (!c) {
+        g_err = "mcraw: NULL context";
+        return -1;
+    }
+    Post p{0, 0, 0};
+    if (f && !float_stage(f, &p))
+        return -1;
+    std::lock_guard<std::mutex> lk(c->mu);
     c->post = p;
     return 0;
 }

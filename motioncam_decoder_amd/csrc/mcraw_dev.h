@@ -269,6 +269,11 @@ __device__ __forceinline__ void store_stream12(void *dst, mcraw_u32x3 v)
 {
     asm volatile("global_store_dwordx3 %0, %1, off " MCRAW_STORE_POLICY "\n\ts_nop 1" ::"v"(dst), "v"(v) : "memory");
 }
+typedef uint32_t mcraw_u32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void store_stream8(void *dst, mcraw_u32x2 v)
+{
+    asm volatile("global_store_dwordx2 %0, %1, off " MCRAW_STORE_POLICY ::"v"(dst), "v"(v) : "memory");
+}
 
 // Bytes [0, nb) of the dwords o[] to dst, the last one masked by `last` (the cropped end of a strip row).
 __device__ __forceinline__ void post_store_bytes(uint8_t *dst, const uint32_t *o, uint32_t nb, uint32_t last, uint32_t maxb)
@@ -370,6 +375,133 @@ __device__ __forceinline__ void post_store8(uint16_t *out, const Post &post, uin
             if (i < n)
                 gptr<uint16_t>(dst)[i] = static_cast<uint16_t>(p[i >> 1] >> (16u * (i & 1u)));
     }
+}
+
+// ---- float rows (mcraw_ctx_set_float_out) --------------------------------------------------------
+//
+// 8 samples of row y from column x on (x % 8 == 0; the first `n` exist), as the dwords (even | odd << 16) the decode kernels
+// hand over.  Sample s at CFA position p = (y & 1) * 2 + (column & 1):
+//   v = (float)((int)s - (int)black[p]) * inv[p]    (the difference is exact; ONE rounding, in the multiply: no FMA can form)
+//   v = min(max(v, 0), 1) with POST_CLIP                (v_med3_f32; a wave-uniform branch)
+// stored as f32, or rounded to nearest even into f16 (v_cvt_f16_f32; overflow to +-inf) / bf16 (v_cvt_pk_bf16_f32).
+// MOSAIC: 8 consecutive elements of row y (one 16-byte store for f16 / bf16, two for f32).  PLANES: the 4 even-column
+// samples go to plane plane4[(y & 1) * 2], the 4 odd-column ones to plane4[(y & 1) * 2 + 1], both to row y / 2, column
+// x / 2 (8 + 8 bytes for f16 / bf16, 16 + 16 for f32); `pstride` samples per plane.  `quick`: the pieces are on their
+// natural grid (post_fast_align and width % 8 == 0).  PK: PK_F32 / PK_F16 / PK_BF16, one kernel instance each.
+template <int PK>
+__device__ __forceinline__ uint32_t float_bits16(float v)
+{
+    if (PK == PK_F16)
+        return __builtin_bit_cast(uint16_t, static_cast<_Float16>(v));
+    return __builtin_bit_cast(uint16_t, static_cast<__bf16>(v));
+}
+
+// `inv`: post.inv, which a caller may hold in vector registers (k6_decode: its scalar registers are taken).
+template <bool NT, int PK>
+__device__ __forceinline__ void float_store8(uint16_t *out, const Post &post, const float inv[4], uint32_t width, uint32_t pstride,
+                                             uint32_t y, uint32_t x, const uint32_t p[4], uint32_t n, bool quick)
+{
+    static_assert(PK == PK_F32 || PK == PK_F16 || PK == PK_BF16, "float row formats");
+    constexpr uint32_t ES = PK == PK_F32 ? 4u : 2u;
+    const bool odd_row = (y & 1u) != 0u;
+    const uint32_t bl = odd_row ? post.black23 : post.black01;
+    const int b0 = static_cast<int>(bl & 0xffffu), b1 = static_cast<int>(bl >> 16);
+    const float i0 = odd_row ? inv[2] : inv[0], i1 = odd_row ? inv[3] : inv[1];
+    float v[8];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        v[2 * i] = static_cast<float>(static_cast<int>(p[i] & 0xffffu) - b0) * i0;
+        v[2 * i + 1] = static_cast<float>(static_cast<int>(p[i] >> 16) - b1) * i1;
+    }
+    if (post.mode & POST_CLIP) {
+#pragma unroll
+        for (int i = 0; i < 8; i++)
+            v[i] = __builtin_amdgcn_fmed3f(v[i], 0.0f, 1.0f);
+    }
+    // the 8 output elements as dwords, in mosaic order (f32: one per dword; f16 / bf16: even | odd << 16)
+    uint32_t e[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++)
+        e[i] = ES == 4u ? __builtin_bit_cast(uint32_t, v[i]) : 0u;
+    if (ES == 2u) {
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+            e[i] = float_bits16<PK>(v[2 * i]) | (float_bits16<PK>(v[2 * i + 1]) << 16);
+    }
+    uint8_t *const base = reinterpret_cast<uint8_t *>(out);
+    if (!(post.mode & POST_PLANES)) {
+        uint8_t *dst = base + (static_cast<size_t>(y) * width + x) * ES;
+        if (n == 8u) {
+#pragma unroll
+            for (uint32_t h = 0; h < ES / 2u; h++) { // 16-byte pieces
+                const mcraw_u32x4 w = {e[4 * h], e[4 * h + 1], e[4 * h + 2], e[4 * h + 3]};
+                if (quick && NT)
+                    store_stream16(dst + 16u * h, w);
+                else if (quick)
+                    *gptr<mcraw_u32x4>(dst + 16u * h) = w;
+                else { // rows off the 16-byte grid: still one (unaligned) 16-byte store
+                    typedef uint32_t u32x4_u __attribute__((ext_vector_type(4), aligned(2)));
+                    const u32x4_u wu = {w[0], w[1], w[2], w[3]};
+                    *gptr<u32x4_u>(dst + 16u * h) = wu;
+                }
+            }
+        } else { // the cropped end of a row: element stores
+#pragma unroll
+            for (uint32_t i = 0; i < 8u; i++)
+                if (i < n) {
+                    if (ES == 4u)
+                        gptr<uint32_t>(dst)[i] = e[i];
+                    else
+                        gptr<uint16_t>(dst)[i] = static_cast<uint16_t>(e[i >> 1] >> (16u * (i & 1u)));
+                }
+        }
+        return;
+    }
+    const uint32_t sh = odd_row ? 16u : 0u;
+    const size_t prow = static_cast<size_t>(y >> 1) * (width >> 1) + (x >> 1);
+    uint8_t *const de = base + (static_cast<size_t>((post.plane4 >> sh) & 3u) * pstride + prow) * ES;
+    uint8_t *const dodd = base + (static_cast<size_t>((post.plane4 >> (sh + 8u)) & 3u) * pstride + prow) * ES;
+    if (n == 8u) {
+        if (ES == 4u) {
+            const mcraw_u32x4 we = {e[0], e[2], e[4], e[6]}, wo = {e[1], e[3], e[5], e[7]};
+            if (quick && NT) {
+                store_stream16(de, we);
+                store_stream16(dodd, wo);
+            } else if (quick) {
+                *gptr<mcraw_u32x4>(de) = we;
+                *gptr<mcraw_u32x4>(dodd) = wo;
+            } else {
+                typedef uint32_t u32x4_u __attribute__((ext_vector_type(4), aligned(4)));
+                *gptr<u32x4_u>(de) = u32x4_u{we[0], we[1], we[2], we[3]};
+                *gptr<u32x4_u>(dodd) = u32x4_u{wo[0], wo[1], wo[2], wo[3]};
+            }
+        } else {
+            // even halves of e[0..3] -> plane of the even columns, odd halves -> the other one
+            const mcraw_u32x2 we = {__builtin_amdgcn_perm(e[1], e[0], 0x05040100u), __builtin_amdgcn_perm(e[3], e[2], 0x05040100u)};
+            const mcraw_u32x2 wo = {__builtin_amdgcn_perm(e[1], e[0], 0x07060302u), __builtin_amdgcn_perm(e[3], e[2], 0x07060302u)};
+            if (quick && NT) {
+                store_stream8(de, we);
+                store_stream8(dodd, wo);
+            } else if (quick) {
+                *gptr<mcraw_u32x2>(de) = we;
+                *gptr<mcraw_u32x2>(dodd) = wo;
+            } else {
+                typedef uint32_t u32x2_u __attribute__((ext_vector_type(2), aligned(2)));
+                *gptr<u32x2_u>(de) = u32x2_u{we[0], we[1]};
+                *gptr<u32x2_u>(dodd) = u32x2_u{wo[0], wo[1]};
+            }
+        }
+        return;
+    }
+#pragma unroll
+    for (uint32_t i = 0; i < 8u; i++) // the cropped end of a row (n even: PLANES needs an even width)
+        if (i < n) {
+            uint8_t *d = (i & 1u) ? dodd : de;
+            if (ES == 4u)
+                gptr<uint32_t>(d)[i >> 1] = e[i];
+            else
+                gptr<uint16_t>(d)[i >> 1] = static_cast<uint16_t>(e[i >> 1] >> (16u * (i & 1u)));
+        }
 }
 
 // 10- and 14-bit strip rows, the interior of a frame (round 5).  A lane's 8 samples are 10 / 14 bytes; stored as 8 + 2 / 12 + 2

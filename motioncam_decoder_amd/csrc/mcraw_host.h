@@ -357,7 +357,16 @@ int host_submit(mcraw_ticket *t);
 int host_finish(mcraw_ticket *t, size_t *written, int32_t *status_out);
 void forget_ticket(mcraw_ticket *t);
 int land_piece(std::vector<std::unique_ptr<mcraw_ticket>> &pieces, std::vector<int> &piece_first, size_t *written, int32_t *status_out);
-size_t host_bytes(const mcraw_frame *frames, int n);
+size_t host_bytes(const mcraw_frame *frames, int n, uint32_t mode);
+// Device bytes the kernels may write for a frame of the stage `mode` (a whole frame, whatever the caller's capacity): the
+// uint16 mosaic's or the stage's own output size (post_out_bytes), whichever is larger; 0 for a frame without a size.
+inline size_t frame_out_full(const mcraw_frame &f, uint32_t mode)
+{
+    if (f.width <= 0 || f.height <= 0)
+        return 0;
+    const uint32_t w = static_cast<uint32_t>(f.width), h = static_cast<uint32_t>(f.height);
+    return std::max(static_cast<size_t>(w) * h * 2, post_out_bytes(w, h, h, mode));
+}
 void way_from_env(mcraw_ctx *c);
 int big_way(mcraw_ctx *c, size_t total, bool *trial);
 void big_way_result(mcraw_ctx *c, int way, size_t total, double seconds);

@@ -89,10 +89,11 @@ int host_submit_part(mcraw_ticket *t, int first, int count)
             in_off[i] = dev;
         }
         io = rin.back().dev + rin.back().bytes;
-        out_len[i] = std::min(f.out_capacity * 2, static_cast<size_t>(f.height) * post_row_bytes(static_cast<uint32_t>(f.width), c->post.mode));
+        out_len[i] = std::min(f.out_capacity * 2, post_out_bytes(static_cast<uint32_t>(f.width), static_cast<uint32_t>(f.height),
+                                                                static_cast<uint32_t>(f.height), c->post.mode));
         // the kernels may write a whole frame even when the caller's capacity is smaller (that frame then
         // fails with MCRAW_E_CAPACITY before any kernel runs): reserve the full size on the device
-        const size_t full = std::max(out_len[i], static_cast<size_t>(f.width) * f.height * 2);
+        const size_t full = std::max(out_len[i], frame_out_full(f, c->post.mode));
         const uintptr_t ao = reinterpret_cast<uintptr_t>(f.out);
         if (lay_ok && ao == lay_host_end)
             out_off[i] = lay_dev_end; // adjacent in host memory: adjacent in the staging too
@@ -238,7 +239,7 @@ int host_submit(mcraw_ticket *t)
         int count = 0, n7 = 0;
         while (first + count < n) {
             const mcraw_frame &f = frames[first + count];
-            const size_t fb = frame_args_ok(f, f.in, f.out) ? f.len + static_cast<size_t>(f.width) * f.height * 2 : 0;
+            const size_t fb = frame_args_ok(f, f.in, f.out) ? f.len + frame_out_full(f, c->post.mode) : 0;
             const size_t g = groups_of(first + count);
             const size_t gm = std::max(gmax, g);
             if (count > 0 && (bytes + fb > SUB_BYTES || gm * WS_PER_GROUP * static_cast<size_t>(n7 + (g ? 1 : 0)) > WS_BUDGET))
@@ -389,11 +390,11 @@ int land_piece(std::vector<std::unique_ptr<mcraw_ticket>> &pieces, std::vector<i
 // fetched).  Streams of short tickets decide for themselves (mcraw_decode_batch_async: sending won wherever it was
 // measured).  MCRAW_SHORT_WAY=0|1 decides both beforehand.
 
-size_t host_bytes(const mcraw_frame *frames, int n)
+size_t host_bytes(const mcraw_frame *frames, int n, uint32_t mode)
 {
     size_t total = 0;
     for (int i = 0; i < n; i++)
-        total += static_cast<size_t>(frames[i].len) + (frames[i].width > 0 && frames[i].height > 0 ? static_cast<size_t>(frames[i].width) * frames[i].height * 2 : 0);
+        total += static_cast<size_t>(frames[i].len) + frame_out_full(frames[i], mode);
     return total;
 }
 
@@ -464,7 +465,7 @@ int deal_host(mcraw_ctx *c, const mcraw_frame *frames, int n, size_t *written, i
         int count = 0;
         while (first + count < n) {
             const mcraw_frame &f = frames[first + count];
-            const size_t fb = static_cast<size_t>(f.len) + (f.width > 0 && f.height > 0 ? static_cast<size_t>(f.width) * f.height * 2 : 0);
+            const size_t fb = static_cast<size_t>(f.len) + frame_out_full(f, c->post.mode);
             if (count > 0 && bytes + fb > piece)
                 break;
             bytes += fb;
@@ -499,7 +500,7 @@ int decode_host(mcraw_ctx *c, const mcraw_frame *frames, int n, size_t *written,
 {
     std::vector<std::unique_ptr<mcraw_ticket>> pieces;
     std::vector<int> piece_first;
-    const size_t total = host_bytes(frames, n);
+    const size_t total = host_bytes(frames, n, c->post.mode);
     bool trial = false;
     way_from_env(c);
     const int way = total > PIECE_BYTES ? big_way(c, total, &trial) : std::max(0, c->send_home_tickets);

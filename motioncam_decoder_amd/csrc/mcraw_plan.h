@@ -23,27 +23,75 @@ constexpr int ITEM_SPAN = ITEM_BLOCKS * 128; // largest payload span of one item
 constexpr int SPAN_MAX = 64 * 128; // largest payload span of one group (all raw-16)
 
 // Optional stage fused behind the decode (what a DNG writer does next with the mosaic,
-// example.cpp:80-92): black-level subtraction and 12-bit strip packing.  Batch-wide, passed by value.
+// example.cpp:80-92): black-level subtraction and 12-bit strip packing -- or, as the other kind of stage, normalised
+// float rows for a model's input.  Batch-wide, passed by value.
 struct Post {
     uint32_t mode;             // POST_* bits; 0 = plain uint16 mosaic (the reference's output)
     uint32_t black01, black23; // black levels of CFA positions (row & 1, col & 1): (0,0) | (0,1) << 16 and (1,0) | (1,1) << 16
+    // float rows (POST_F32 / F16 / BF16): v = (float)((int)sample - (int)black[p]) * inv[p], clamped to [0, 1] with POST_CLIP
+    uint32_t plane4;           // POST_PLANES: output plane of CFA position p in byte p (a permutation of 0..3)
+    uint32_t pad[3];
+    float inv[4];              // 1 / (white - black[p]), rounded once, on the host
 };
 constexpr uint32_t POST_BLACK = 1;  // sample = max(sample - black[row & 1][col & 1], 0)
 constexpr uint32_t POST_PACK12 = 2; // rows of min(sample, 4095) packed MSB-first, 3 bytes per 2 samples (TIFF/DNG BitsPerSample 12)
 constexpr uint32_t POST_PACK10 = 4; // ... min(sample, 1023), 5 bytes per 4 samples (BitsPerSample 10)
 constexpr uint32_t POST_PACK14 = 8; // ... min(sample, 16383), 7 bytes per 4 samples (BitsPerSample 14)
 constexpr uint32_t POST_PACKED = POST_PACK12 | POST_PACK10 | POST_PACK14;
+// Normalised float output (mcraw_ctx_set_float_out), never combined with the bits above.  Internal values: the public
+// mcraw_post flags are checked against their own list.
+constexpr uint32_t POST_F32 = 0x100;    // IEEE binary32 samples
+constexpr uint32_t POST_F16 = 0x200;    // binary16, rounded to nearest even from the f32 value (overflow: +-inf)
+constexpr uint32_t POST_BF16 = 0x400;   // bfloat16, rounded to nearest even from the f32 value
+constexpr uint32_t POST_PLANES = 0x800; // four planes of (height/2) x (width/2), plane-major, instead of mosaic rows
+constexpr uint32_t POST_CLIP = 0x1000;  // float values clamped to [0, 1]
+constexpr uint32_t POST_FLOAT = POST_F32 | POST_F16 | POST_BF16;
 
-// Bits per sample of an output row.
+// Bits per sample of an output row of uint16 samples or a strip (the kernels' strip addressing).
 __host__ __device__ inline uint32_t post_bits(uint32_t mode)
 {
     return (mode & POST_PACK12) ? 12u : (mode & POST_PACK10) ? 10u : (mode & POST_PACK14) ? 14u : 16u;
 }
 
-// Bytes of one output row of `width` samples.
+// Bits of one output sample, the float types included.
+__host__ __device__ inline uint32_t post_sample_bits(uint32_t mode)
+{
+    return (mode & POST_F32) ? 32u : post_bits(mode);
+}
+
+// Which kernel instance writes the rows: the bits of a strip or of the uint16 mosaic (16), or one of the float types.
+constexpr int PK_F32 = 32, PK_F16 = 33, PK_BF16 = 34;
+__host__ __device__ inline int post_kind(uint32_t mode)
+{
+    return (mode & POST_F32) ? PK_F32 : (mode & POST_F16) ? PK_F16 : (mode & POST_BF16) ? PK_BF16 : static_cast<int>(post_bits(mode));
+}
+
+// Bytes of one output row of `width` samples of a uint16 mosaic or strip (post_out_bytes: of any output).
 __host__ __device__ inline uint32_t post_row_bytes(uint32_t width, uint32_t mode)
 {
     return (width * post_bits(mode) + 7u) >> 3;
+}
+
+// Bytes of a frame's output when `rows` of its `height` rows are written: the four planes are laid out for the whole
+// height (plane stride (height/2) * (width/2) samples), mosaic rows and strips only as far as they are written.  Every
+// place that sizes an output goes through this.
+__host__ __device__ inline size_t post_out_bytes(uint32_t width, uint32_t height, uint32_t rows, uint32_t mode)
+{
+    if (mode & POST_PLANES)
+        return static_cast<size_t>(height / 2u) * (width / 2u) * 4u * (post_sample_bits(mode) / 8u);
+    if (mode & POST_FLOAT)
+        return static_cast<size_t>(rows) * width * (post_sample_bits(mode) / 8u);
+    return static_cast<size_t>(rows) * post_row_bytes(width, mode);
+}
+
+// The alignment of `out` that the vector-store path of a frame needs (with width % 8 == 0): 16-byte pieces of uint16 and
+// float rows, 8-byte plane pieces of f16 / bf16, 12-byte pieces of a 12-bit strip (dword aligned), 10- and 14-bit strips as
+// 2-byte aligned pieces.
+__host__ __device__ inline uint32_t post_fast_align(uint32_t mode)
+{
+    if (mode & POST_FLOAT)
+        return ((mode & POST_PLANES) && !(mode & POST_F32)) ? 8u : 16u;
+    return (mode & POST_PACK12) ? 4u : (mode & POST_PACKED) ? 2u : 16u;
 }
 
 // Per-frame plan of the current ("type 7") encoding, written by the host into PINNED HOST memory
@@ -58,7 +106,7 @@ struct Plan7 {
     int32_t height;      // output rows the caller has room for; rows kept = min(height, encH)
     uint32_t ngroups;    // decode groups (side-stream records) the workspace and the k7_tiles grid provide for
     uint32_t fast_store; // 1: out 16-B aligned and width % 8 == 0
-    uint32_t pad;
+    uint32_t pstride;    // POST_PLANES: samples per output plane, (height/2) * (width/2)
 };
 
 // What k7_tiles needs to know about a frame, in HBM: written by k7_side (the workgroup of the bits
@@ -78,7 +126,7 @@ struct Frame7 {
     // k7_tiles adds to an offset: part_len[q] for every q with part_item[q] <= item.
     uint32_t part_item[3]; // first decode item of parts 1..3 of the bits stream (0xFFFFFFFF: no such part, or it had nothing to do)
     uint32_t part_len[3];  // payload bytes of parts 0..2 (part 0: up to the end of its last item, the 16-byte header included)
-    uint32_t pad;
+    uint32_t pstride;      // Plan7::pstride
 };
 constexpr int MAX_SPLIT7 = 4; // parts per side stream, at most
 

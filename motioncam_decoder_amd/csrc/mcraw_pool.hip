@@ -351,6 +351,22 @@ int mcraw_pool_set_post(mcraw_pool *p, const mcraw_post *post)
     return rc;
 }
 
+int mcraw_pool_set_float_out(mcraw_pool *p, const mcraw_float_out *f)
+{
+    if (!p) {
+        g_pool_err = "mcraw: NULL pool";
+        return -1;
+    }
+    std::lock_guard<std::mutex> lk(p->mu); // (as mcraw_pool_set_post: all members of one batch get the same stage)
+    int rc = 0;
+    for (Member *m : p->members)
+        if (int r = mcraw_ctx_set_float_out(m->ctx, f))
+            rc = r;
+    if (rc)
+        g_pool_err = mcraw_last_error();
+    return rc;
+}
+
 void *mcraw_pool_host_alloc(mcraw_pool *p, int member, size_t bytes)
 {
     if (!p || member < 0 || member >= static_cast<int>(p->members.size()))

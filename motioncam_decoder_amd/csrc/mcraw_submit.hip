@@ -24,9 +24,15 @@ int submit(mcraw_ctx *c, Slot &s, const mcraw_frame *frames, int n, const std::v
             continue;
         }
         const uint32_t pmode = c->post.mode;
-        // vector stores: 16-byte rows pieces of uint16, or 12-byte pieces of a 12-bit strip (dword aligned)
-        // (10- and 14-bit strips go out as 2-byte aligned pieces: any uint16 pointer will do)
-        const uintptr_t oalign = (pmode & POST_PACK12) ? 4 : (pmode & POST_PACKED) ? 2 : 16;
+        // float rows: f32 elements need a 4-byte aligned `out`; the four planes need an even width and height
+        if (((pmode & POST_F32) && reinterpret_cast<uintptr_t>(out) % 4 != 0) ||
+            ((pmode & POST_PLANES) && ((f.width & 1) || (f.height & 1)))) {
+            status[i] = MCRAW_E_ARGS;
+            continue;
+        }
+        // vector stores (post_fast_align): 16-byte pieces of uint16 or float rows, 8-byte plane pieces of f16 / bf16, 12-byte
+        // pieces of a 12-bit strip (dword aligned); 10- and 14-bit strips go out as 2-byte aligned pieces
+        const uintptr_t oalign = post_fast_align(pmode);
         const bool fast = (reinterpret_cast<uintptr_t>(out) % oalign == 0) && (f.width % 8 == 0);
         if (f.type == MCRAW_TYPE_BLOCK) {
             Plan7 p{};
@@ -47,11 +53,12 @@ int submit(mcraw_ctx *c, Slot &s, const mcraw_frame *frames, int n, const std::v
                 continue;
             }
             const uint32_t rows = std::min<uint32_t>(static_cast<uint32_t>(f.height), encH);
-            if (f.out_capacity * 2 < static_cast<size_t>(rows) * post_row_bytes(static_cast<uint32_t>(f.width), pmode)) {
+            if (f.out_capacity * 2 < post_out_bytes(static_cast<uint32_t>(f.width), static_cast<uint32_t>(f.height), rows, pmode)) {
                 status[i] = MCRAW_E_CAPACITY;
                 continue;
             }
             p.height = f.height;
+            p.pstride = (static_cast<uint32_t>(f.height) / 2u) * (static_cast<uint32_t>(f.width) / 2u);
             p.ngroups = (4 * (encW / 64) * (encH / 4) + GROUP_BLOCKS - 1) / GROUP_BLOCKS;
             p.fast_store = fast ? 1u : 0u;
             B.p7.push_back(p);
@@ -63,7 +70,8 @@ int submit(mcraw_ctx *c, Slot &s, const mcraw_frame *frames, int n, const std::v
             p.len = static_cast<uint32_t>(f.len);
             p.width = f.width;
             p.height = f.height;
-            if (f.out_capacity * 2 < static_cast<size_t>(f.height) * post_row_bytes(static_cast<uint32_t>(f.width), pmode)) {
+            if (f.out_capacity * 2 < post_out_bytes(static_cast<uint32_t>(f.width), static_cast<uint32_t>(f.height),
+                                                    static_cast<uint32_t>(f.height), pmode)) {
                 status[i] = MCRAW_E_CAPACITY;
                 continue;
             }

@@ -247,7 +247,7 @@ __device__ uint32_t g_k6_prof[K6_PROF_WG][K6_PROF_N];
 //    they are one: the lanes behind that boundary are verified from there (the segment then says its exit phase at once),
 //    the ones in front of it wait for the segment in front to say at which phase it ends.  A stream whose chains never
 //    meet publishes the map entry phase -> exit phase instead, and its segments resolve in wave fronts of 64.
-template <int POST> // 0 = the plain mosaic, else bits per sample of the post stage's rows
+template <int POST> // 0 = the plain mosaic, else post_kind: bits per sample of the post stage's rows, or PK_F*
 __global__ __launch_bounds__(DEC_T) void k6_decode(const Plan6 *__restrict__ plans, const uint32_t *__restrict__ wg_tab,
                                                    uint32_t stage0, const Look6 look, uint32_t *__restrict__ tickets,
                                                    uint32_t epoch, uint32_t nframes, uint32_t smax, const Post post)
@@ -314,6 +314,11 @@ __global__ __launch_bounds__(DEC_T) void k6_decode(const Plan6 *__restrict__ pla
     // the workgroup's last barrier, on every wave's way from the record lists to its first store (worth 1 % at most: they hit the scalar cache).
     uint32_t width = static_cast<uint32_t>(P->width), fast_store = P->fast_store, ppr = P->recs_per_row >> 1;
     uint16_t *out = P->out;
+    const uint32_t pstride = POST >= PK_F32 ? (static_cast<uint32_t>(P->height) >> 1) * (width >> 1) : 0u; // (float planes)
+    // (float rows: the four factors in vector registers -- held in scalar ones they cost the instance a workgroup per CU)
+    float finv[4] = {post.inv[0], post.inv[1], post.inv[2], post.inv[3]};
+    if constexpr (POST >= PK_F32)
+        asm volatile("" : "+v"(finv[0]), "+v"(finv[1]), "+v"(finv[2]), "+v"(finv[3]));
     // row arithmetic without per-lane division: pairs per row `ppr`; a round spans < 2 rows when
     // ppr >= 512, otherwise n / ppr for n < 1024 is exact as (n * ceil(2^20 / ppr)) >> 20
     const bool widerow = ppr >= 512u;
@@ -1013,7 +1018,11 @@ __global__ __launch_bounds__(DEC_T) void k6_decode(const Plan6 *__restrict__ pla
 #pragma unroll
             for (int j = 0; j < 4; j++)
                 o[j] = __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2, va[j] | (vb[j] << 16)) + refs);
-            if (POST) { // black levels / 12-bit strip rows (mcraw_dev.h); padded columns are cropped
+            if constexpr (POST >= PK_F32) { // normalised float rows or planes (mcraw_dev.h); padded columns are cropped
+                if (x < width)
+                    float_store8<true, POST>(out, post, finv, width, pstride, y0 + dy, x, o, min(8u, width - x), fast);
+                continue;
+            } else if (POST) { // black levels / 12-bit strip rows (mcraw_dev.h); padded columns are cropped
                 if (x < width)
                     post_store8<true, POST>(out, post, width, y0 + dy, x, o, min(8u, width - x), fast);
                 continue;
@@ -1174,7 +1183,10 @@ void launch_k6_decode(const Plan6 *plans, const uint32_t *wg_tab, uint32_t stage
 #endif
         return;
     }
-    switch (post_bits(post.mode)) { // one kernel instance per row format
+    switch (post_kind(post.mode)) { // one kernel instance per row format
+    case PK_F32: hipLaunchKernelGGL(k6_decode<PK_F32>, grid, block, 0, st, plans, wg_tab, stage0, look, tickets, epoch, nf, smax, post); break;
+    case PK_F16: hipLaunchKernelGGL(k6_decode<PK_F16>, grid, block, 0, st, plans, wg_tab, stage0, look, tickets, epoch, nf, smax, post); break;
+    case PK_BF16: hipLaunchKernelGGL(k6_decode<PK_BF16>, grid, block, 0, st, plans, wg_tab, stage0, look, tickets, epoch, nf, smax, post); break;
     case 12: hipLaunchKernelGGL(k6_decode<12>, grid, block, 0, st, plans, wg_tab, stage0, look, tickets, epoch, nf, smax, post); break;
     case 10: hipLaunchKernelGGL(k6_decode<10>, grid, block, 0, st, plans, wg_tab, stage0, look, tickets, epoch, nf, smax, post); break;
     case 14: hipLaunchKernelGGL(k6_decode<14>, grid, block, 0, st, plans, wg_tab, stage0, look, tickets, epoch, nf, smax, post); break;

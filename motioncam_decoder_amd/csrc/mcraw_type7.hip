@@ -352,7 +352,7 @@ __global__ __launch_bounds__(SIDE_T) __attribute__((amdgpu_waves_per_eu(4, 4))) 
         FR->nblk = err ? 0u : nblk; // a frame rejected here is not touched by k7_tiles
         FR->fast_store = P->fast_store;
         FR->encH = encH;
-        FR->pad = 0u;
+        FR->pstride = P->pstride;
         for (uint32_t q = err ? 0u : nsb - 1u; q < 3u; q++) {
             FR->part_item[q] = 0xFFFFFFFFu;
             FR->part_len[q] = 0u;
@@ -1084,6 +1084,7 @@ struct ItemS {
     uint16_t *out;
     size_t meta;         // index of the group's first entry in W.bits / W.refs
     uint32_t lean;       // (strip rows) no sample of the item can reach 2^bits, black levels are off its references
+    uint32_t pstride;    // (float planes) samples per output plane
 };
 
 __device__ __forceinline__ ItemS item_scalars(const Work7 &W, uint32_t item, uint32_t first_frame, uint32_t class_groups)
@@ -1143,18 +1144,22 @@ __device__ __forceinline__ ItemS item_scalars(const Work7 &W, uint32_t item, uin
     I.out = F->out;
     I.meta = static_cast<size_t>(f) * W.Rmax * 64u + static_cast<size_t>(g) * ITEM_BLOCKS;
     I.lean = 0u;
+    I.pstride = F->pstride;
     return I;
 }
 
 // Store 8 consecutive pixels (16 B) of row y starting at column x, cropped to `width`
 // (RawData.cpp:598-608 copies `width` pixels of the coded row).
-template <bool NT = false, int POST = 0> // POST: 0 = the plain mosaic, else bits per sample of the post stage's rows
+template <bool NT = false, int POST = 0> // POST: 0 = the plain mosaic, else post_kind: bits per sample of the post stage's rows, or PK_F*
 __device__ __forceinline__ void store_px8(const ItemS &I, const Post &post, uint32_t y, uint32_t x, uint32_t p[4])
 {
     const uint32_t width = static_cast<uint32_t>(I.width);
     if (y >= static_cast<uint32_t>(I.rows) || x >= width)
         return;
-    if (POST) { // black levels / 12-bit strip rows (mcraw_dev.h)
+    if constexpr (POST >= PK_F32) { // normalised float rows or planes (mcraw_dev.h)
+        float_store8<NT, POST>(I.out, post, post.inv, width, I.pstride, y, x, p, min(8u, width - x), I.fast != 0u);
+        return;
+    } else if (POST) { // black levels / 12-bit strip rows (mcraw_dev.h)
         post_store8<NT, POST>(I.out, post, width, y, x, p, min(8u, width - x), I.fast != 0u, POST != 16 && I.lean != 0u);
         return;
     }
@@ -1307,7 +1312,7 @@ __global__ __launch_bounds__(256) void k7_tiles(const Work7 W, uint32_t total, u
         b = W.bits[I.meta + lane];
         r = W.refs[I.meta + lane];
     }
-    if (POST == 12 || POST == 10 || POST == 14) {
+    if constexpr (POST == 12 || POST == 10 || POST == 14) {
         // strip rows (round 4: 12 bits; round 5: 10 and 14 too): a block is one colour plane of its tile (block k of a tile: row parity k >> 1, column parity
         // k & 1, RawData.cpp:581-593), so its black level is ONE value and can come off its reference -- if the reference is not
         // below it --, and no sample of the block can reach 2^POST when reference - black + (2^storage width - 1) does not: then
@@ -1392,7 +1397,10 @@ void launch_k7(const Work7 &W, uint32_t stage, hipStream_t st)
                 continue;
             const dim3 grid((total + 3) / 4);
             if (W.post.mode != 0u) { // one kernel instance per row format
-                switch (post_bits(W.post.mode)) {
+                switch (post_kind(W.post.mode)) {
+                case PK_F32: hipLaunchKernelGGL((k7_tiles<0, true, PK_F32>), grid, dim3(256), 0, st, W, total, first, groups); break;
+                case PK_F16: hipLaunchKernelGGL((k7_tiles<0, true, PK_F16>), grid, dim3(256), 0, st, W, total, first, groups); break;
+                case PK_BF16: hipLaunchKernelGGL((k7_tiles<0, true, PK_BF16>), grid, dim3(256), 0, st, W, total, first, groups); break;
                 case 12: hipLaunchKernelGGL((k7_tiles<0, true, 12>), grid, dim3(256), 0, st, W, total, first, groups); break;
                 case 10: hipLaunchKernelGGL((k7_tiles<0, true, 10>), grid, dim3(256), 0, st, W, total, first, groups); break;
                 case 14: hipLaunchKernelGGL((k7_tiles<0, true, 14>), grid, dim3(256), 0, st, W, total, first, groups); break;
