@@ -231,7 +231,9 @@ uint32_t mcraw_tile_order(uint32_t b, uint32_t n, uint32_t runs);
 #define MCRAW_K6_DECODE  6 /* legacy: the whole decode (one launch) */
 #define MCRAW_K7E_PAYLOAD 7 /* encoder: payload of every frame (mcraw_encode_batch) */
 #define MCRAW_K7E_SIDE   8 /* encoder: side streams, header, byte count           */
-#define MCRAW_K_COUNT    9
+#define MCRAW_KRGB_MHC   9 /* demosaic, full resolution (mcraw_demosaic_batch)     */
+#define MCRAW_KRGB_BIN2 10 /* demosaic, 2x2 binning                                */
+#define MCRAW_K_COUNT   11
 
 /* hipEvent bracketing of kernel launches on the launch stream: 0 = off, 1 = every
  * kernel, MCRAW_PROFILE_ONLY(id) [| MCRAW_PROFILE_ONLY(id2) ...] = those kernels only
@@ -319,6 +321,61 @@ typedef struct mcraw_float_out {
     uint8_t plane[4];  /* PLANES: output plane of CFA position p; a permutation of 0..3         */
 } mcraw_float_out;
 int mcraw_ctx_set_float_out(mcraw_ctx *ctx, const mcraw_float_out *f);
+
+/* ---- uint16 mosaics -> planar linear RGB ------------------------------------------------------------------------
+ *
+ * Demosaics `n` uint16 mosaics that are resident in HBM into (n, 3, Ho, Wo) planar RGB at `out`: contiguous, frames back to
+ * back, channel-major per frame (R, G, B planes), row-major planes.  `in_pitch` and `in_frame_stride` count uint16 elements.
+ *   MCRAW_RGB_MHC   Ho = height, Wo = width: Malvar-He-Cutler 5x5 gradient-corrected bilinear interpolation
+ *   MCRAW_RGB_BIN2  Ho = height / 2, Wo = width / 2: one output pixel per 2x2 CFA quad, R = r, G = mean(g1, g2), B = b
+ * Bit-exact arithmetic, at CFA position p = (y & 1) * 2 + (x & 1):
+ *   d(y, x) = (int)s(y, x) - (int)black[p]   (int32; MHC reads outside the frame are reflected 101-style: -k -> k,
+ *                                             H-1+k -> H-1-k, the same for columns, which keeps the CFA parity)
+ *   integer estimates E_c, in units of 1/16 (MHC) or 1/2 (BIN2), C = d at the pixel:
+ *     MHC native channel            16 C
+ *     G at R or B                   8 C + 4 (4 axial neighbours at distance 1) - 2 (4 axial at distance 2)
+ *     R or B at G, colour left/right  10 C + 8 (d[y][x-1] + d[y][x+1]) - 2 (d[y][x-2] + d[y][x+2]) - 2 (4 diagonals)
+ *                                   + (d[y-2][x] + d[y+2][x]);  colour above/below: the transpose
+ *     R at B, B at R                12 C + 4 (4 diagonals) - 3 (4 axial at distance 2)
+ *     BIN2                          E_R = 2 d(r), E_G = d(g1) + d(g2), E_B = 2 d(b)
+ *   (|E_c| <= 28 * 65535 < 2^24: (float)E_c is exact)
+ *   host, f32: inv = 1.0f / (white - 0.25f * (float)(black[0] + black[1] + black[2] + black[3]));
+ *              k[c] = (gain[c] * inv) * (MHC ? 0.0625f : 0.5f)
+ *   device, f32, every product and sum rounded on its own (no FMA):
+ *              v_c = (float)E_c * k[c];  o_i = (m[3i] v_0 + m[3i+1] v_1) + m[3i+2] v_2
+ *   o_i clamped to [0, 1] with MCRAW_FLOAT_CLIP, then stored as f32, f16 (RNE, overflow to inf) or bf16 (RNE), as
+ *   mcraw_ctx_set_float_out does.
+ * `colors` is host memory: ncolors == 1 applies to every frame, ncolors == n gives one per frame.  The values travel with
+ * the launches, so batches queued back to back (on one stream or several) never see each other's colours.
+ * `stream`: a hipStream_t, NULL = the context's own stream; the call queues the work and returns without synchronising.
+ * It takes no decode serial and leaves the decode slots, mcraw_ctx_errors, mcraw_ctx_last_serial and the context's
+ * stage (set_post / set_float_out) alone.  n == 0 is a no-op.
+ * Rejected (returns < 0, mcraw_last_error says why, nothing is written): an odd width or height, or one below 4 or above
+ * 65536; in_pitch < width; n > 1 and in_frame_stride < (height - 1) * in_pitch + width; an unknown algo, dtype, cfa or
+ * flag; a white that is not finite or not above 0.25 * (sum of black); a non-finite gain or matrix entry; ncolors not 1
+ * or n; out_bytes < n * 3 * Ho * Wo * element size; a NULL or odd `in`; a NULL `out` or one not aligned to the element
+ * size.  Kernels: MCRAW_KRGB_MHC / MCRAW_KRGB_BIN2 (mcraw_ctx_kernel_ms). */
+#define MCRAW_RGB_MHC  1
+#define MCRAW_RGB_BIN2 2
+#define MCRAW_CFA_RGGB 0
+#define MCRAW_CFA_BGGR 1
+#define MCRAW_CFA_GRBG 2
+#define MCRAW_CFA_GBRG 3
+typedef struct mcraw_rgb {
+    uint32_t algo;     /* MCRAW_RGB_MHC or MCRAW_RGB_BIN2                                    */
+    uint32_t dtype;    /* MCRAW_FLOAT_F32 / _F16 / _BF16                                      */
+    uint32_t flags;    /* MCRAW_FLOAT_CLIP or 0                                               */
+    uint32_t cfa;      /* MCRAW_CFA_* (the container's sensorArrangment)                      */
+    uint16_t black[4]; /* by CFA position p = (y & 1) * 2 + (x & 1)                           */
+    float white;       /* container "whiteLevel"                                              */
+} mcraw_rgb;
+typedef struct mcraw_rgb_color {
+    float gain[3]; /* white balance, R G B (1 / asShotNeutral)                                */
+    float m[9];    /* row-major 3x3, out = m . v                                              */
+} mcraw_rgb_color;
+int mcraw_demosaic_batch(mcraw_ctx *ctx, const mcraw_rgb *p, const mcraw_rgb_color *colors, int ncolors,
+                         const uint16_t *in, size_t in_pitch, size_t in_frame_stride, int width, int height, int n,
+                         void *out, size_t out_bytes, void *stream);
 
 /* ---- environment ------------------------------------------------------------------------------
  * Read when a context (or pool) is created, never afterwards:

@@ -12,7 +12,8 @@ import ctypes as C
 import os
 
 __all__ = ["lib_path", "load", "Context", "Pool", "Frame", "EncFrame", "FloatOut", "McrawError", "TYPE_LEGACY", "TYPE_BLOCK",
-           "MEM_DEVICE", "MEM_HOST", "KERNELS", "ENC_KERNELS", "ABI_SYMBOLS", "encode_bound7", "cfa_planes"]
+           "MEM_DEVICE", "MEM_HOST", "KERNELS", "ENC_KERNELS", "ABI_SYMBOLS", "encode_bound7", "cfa_planes",
+           "RgbParams", "RgbColor", "RGB_KERNELS", "rgb_color"]
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 
@@ -26,6 +27,7 @@ E_ARGS, E_HEADER, E_TRUNCATED, E_SIDESTREAM, E_CAPACITY, E_DEVICE = 0x1, 0x2, 0x
 
 KERNELS = {"k7_side": 0, "k7_tiles": 3, "k6_decode": 6}
 ENC_KERNELS = {"k7e_payload": 7, "k7e_side": 8}  # the encoder's launches (mcraw_encode_batch)
+RGB_KERNELS = {"krgb_mhc": 9, "krgb_bin2": 10}  # the demosaic's launches (mcraw_demosaic_batch)
 
 # every symbol include/mcraw_hip.h declares
 ABI_SYMBOLS = [
@@ -38,6 +40,7 @@ ABI_SYMBOLS = [
     "mcraw_pool_decode_batch_device", "mcraw_ctx_xcd_runs", "mcraw_pool_synchronize", "mcraw_tile_order",
     "mcraw_ctx_last_serial", "mcraw_ctx_batch_status", "mcraw_ctx_errors", "mcraw_ctx_side_parts", "mcraw_ctx_host_way",
     "mcraw_encode_bound7", "mcraw_encode_batch", "mcraw_encode7", "mcraw_ctx_set_float_out", "mcraw_pool_set_float_out",
+    "mcraw_demosaic_batch",
 ]
 
 POST_BLACK, POST_PACK12, POST_PACK10, POST_PACK14 = 1, 2, 4, 8
@@ -110,6 +113,66 @@ def float_out(dtype, white, layout="planes", black=(0, 0, 0, 0), clip=False, pla
     for i in range(4):
         f.plane[i] = int(plane[i])
     return f
+
+
+# demosaic to planar linear RGB (mcraw_demosaic_batch)
+RGB_MHC, RGB_BIN2 = 1, 2
+_RGB_ALGOS = {"mhc": RGB_MHC, "bin2": RGB_BIN2}
+_CFA_CODES = {"rggb": 0, "bggr": 1, "grbg": 2, "gbrg": 3}
+
+
+class RgbParams(C.Structure):
+    """struct mcraw_rgb (include/mcraw_hip.h)."""
+    _fields_ = [("algo", C.c_uint32), ("dtype", C.c_uint32), ("flags", C.c_uint32), ("cfa", C.c_uint32),
+                ("black", C.c_uint16 * 4), ("white", C.c_float)]
+
+
+class RgbColor(C.Structure):
+    """struct mcraw_rgb_color (include/mcraw_hip.h): white-balance gains and a row-major 3x3 matrix, out = m . v."""
+    _fields_ = [("gain", C.c_float * 3), ("m", C.c_float * 9)]
+
+
+def _xyz_d50_to_srgb():
+    """Linear sRGB (D65) from XYZ (D50): Bradford adaptation D50 -> D65, then the inverse of the sRGB primaries' matrix."""
+    import numpy as np
+    d50 = np.array([0.96422, 1.0, 0.82521])
+    d65 = np.array([0.95047, 1.0, 1.08883])
+    xy = np.array([[0.64, 0.33], [0.30, 0.60], [0.15, 0.06]])
+    prim = np.stack([xy[:, 0] / xy[:, 1], np.ones(3), (1 - xy[:, 0] - xy[:, 1]) / xy[:, 1]])  # columns: XYZ of R, G, B
+    rgb_to_xyz = prim * np.linalg.solve(prim, d65)[None, :]
+    brad = np.array([[0.8951, 0.2664, -0.1614], [-0.7502, 1.7135, 0.0367], [0.0389, -0.0685, 1.0296]])
+    adapt = np.linalg.inv(brad) @ np.diag((brad @ d65) / (brad @ d50)) @ brad
+    return np.linalg.inv(rgb_to_xyz) @ adapt
+
+
+def rgb_color(container_meta, frame_meta=None, space="srgb"):
+    """(gain[3], m[3][3]) as float32 for Context.demosaic / decode_rgb, from the clip's metadata, computed in float64 and
+    rounded once.  gain = 1 / asShotNeutral of the frame (ones without frame metadata).  space: "camera" (identity: white-
+    balanced camera RGB), "xyz" (forwardMatrix1: white-balanced camera RGB to XYZ D50) or "srgb" (linear sRGB, D65: the
+    Bradford-adapted XYZ(D50) -> sRGB matrix times forwardMatrix1).  The DNG calibration illuminant 1 of these clips is D65;
+    interpolating between forwardMatrix1 and forwardMatrix2 by colour temperature is not done.  A missing or all-zero
+    forwardMatrix1 raises ValueError (for "xyz" and "srgb")."""
+    import numpy as np
+    if space not in ("camera", "xyz", "srgb"):
+        raise ValueError("space must be 'camera', 'xyz' or 'srgb', not %r" % (space,))
+    if frame_meta is not None and frame_meta.get("asShotNeutral") is not None:
+        neutral = np.asarray(frame_meta["asShotNeutral"], dtype=np.float64).ravel()
+        if neutral.size != 3 or not np.all(np.isfinite(neutral)) or np.any(neutral <= 0):
+            raise ValueError("asShotNeutral must be three positive numbers, not %r" % (frame_meta["asShotNeutral"],))
+        gain = 1.0 / neutral
+    else:
+        gain = np.ones(3)
+    if space == "camera":
+        m = np.eye(3)
+    else:
+        fm = container_meta.get("forwardMatrix1") if container_meta is not None else None
+        fm = None if fm is None else np.asarray(fm, dtype=np.float64).ravel()
+        if fm is None or fm.size != 9 or not np.any(fm) or not np.all(np.isfinite(fm)):
+            raise ValueError("the container has no usable forwardMatrix1 (nine numbers, not all zero)")
+        m = fm.reshape(3, 3)
+        if space == "srgb":
+            m = _xyz_d50_to_srgb() @ m
+    return gain.astype(np.float32), m.astype(np.float32)
 
 
 class Frame(C.Structure):
@@ -243,10 +306,20 @@ def load():
     lib.mcraw_ctx_set_float_out.argtypes = [C.c_void_p, C.POINTER(FloatOut)]
     lib.mcraw_pool_set_float_out.restype = C.c_int
     lib.mcraw_pool_set_float_out.argtypes = [C.c_void_p, C.POINTER(FloatOut)]
+    lib.mcraw_demosaic_batch.restype = C.c_int
+    lib.mcraw_demosaic_batch.argtypes = [C.c_void_p, C.POINTER(RgbParams), C.POINTER(RgbColor), C.c_int, C.c_void_p, C.c_size_t,
+                                         C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.mcraw_encode7.restype = C.c_size_t
     lib.mcraw_encode7.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int]
     _lib = lib
     return lib
+
+
+def _kernel_id(name):
+    for table in (KERNELS, ENC_KERNELS, RGB_KERNELS):
+        if name in table:
+            return table[name]
+    raise KeyError(name)
 
 
 def encode_bound7(w, h):
@@ -592,13 +665,138 @@ class Context:
                     len(bad), n, ", ".join("frame %d status 0x%x" % b for b in bad[:16])))
         return out
 
+    def _run_stream(self, torch, dev):
+        """(current stream, stream to run on): torch's default stream is the null stream, which the library reads as "the
+        context's own", so work for it runs on a side stream of this context's that waits for the current stream (the
+        caller then makes the current stream wait for it: still no host sync)."""
+        cur = torch.cuda.current_stream(dev)
+        if cur.cuda_stream:
+            return cur, cur
+        if getattr(self, "_side", None) is None:
+            self._side = torch.cuda.Stream(dev)
+        self._side.wait_stream(cur)
+        return cur, self._side
+
+    def demosaic(self, mosaic, *, algo="mhc", dtype, white, black=(0, 0, 0, 0), cfa="rggb", gain=None, matrix=None,
+                 clip=False, out=None, check=True):
+        """uint16 mosaics resident on the context's device -> planar linear RGB, (N, 3, H, W) for algo "mhc" (Malvar-He-
+        Cutler) or (N, 3, H/2, W/2) for "bin2" (one pixel per 2x2 quad), as torch.float32 / float16 / bfloat16 ("f32" /
+        "f16" / "bf16").  mosaic: a CUDA uint16 tensor (N, H, W) or (H, W) whose rows are contiguous (rows and frames may
+        be strided); the result of an (H, W) mosaic is (3, Ho, Wo).  black: four levels by CFA position (y & 1) * 2 +
+        (x & 1); cfa: the container's sensorArrangment; gain (3,) or (N, 3) and matrix (3, 3) or (N, 3, 3): white balance
+        and colour matrix for all frames or per frame (rgb_color gives them); clip: clamp to [0, 1].  Queued on
+        torch.cuda.current_stream(); nothing synchronises.  `check` is accepted for symmetry with decode_rgb (the
+        arguments are always checked; there are no per-frame statuses)."""
+        import torch
+        import numpy as np
+        if algo not in _RGB_ALGOS:
+            raise ValueError("algo must be 'mhc' or 'bin2', not %r" % (algo,))
+        key = str(cfa).strip().lower()
+        if key not in _CFA_CODES:
+            raise ValueError("unknown cfa %r (rggb, bggr, grbg or gbrg)" % (cfa,))
+        code = _float_code(dtype)
+        tdtype = {FLOAT_F32: torch.float32, FLOAT_F16: torch.float16, FLOAT_BF16: torch.bfloat16}[code]
+        dev = self._torch_device(torch)
+        if not isinstance(mosaic, torch.Tensor) or mosaic.dtype != torch.uint16 or mosaic.device != dev or mosaic.dim() not in (2, 3):
+            raise ValueError("demosaic: mosaic must be a uint16 tensor (N, H, W) or (H, W) on %s" % dev)
+        single = mosaic.dim() == 2
+        mos = mosaic.unsqueeze(0) if single else mosaic
+        n, h, w = (int(v) for v in mos.shape)
+        if n and h > 1 and mos.stride(2) != 1:
+            raise ValueError("demosaic: the rows of the mosaic must be contiguous")
+        ho, wo = (h, w) if algo == "mhc" else (h // 2, w // 2)
+        shape = (n, 3, ho, wo)
+        want = shape[1:] if single else shape
+        if out is None:
+            out = torch.empty(want, dtype=tdtype, device=dev)
+        elif tuple(out.shape) != tuple(want) or out.dtype != tdtype or out.device != dev or not out.is_contiguous():
+            raise ValueError("demosaic: out must be a contiguous %s tensor of shape %s on %s" % (tdtype, tuple(want), dev))
+        if n == 0:
+            return out
+        gain = np.ones(3, np.float32) if gain is None else np.asarray(gain, dtype=np.float32)
+        matrix = np.eye(3, dtype=np.float32) if matrix is None else np.asarray(matrix, dtype=np.float32)
+        per = gain.ndim == 2 or matrix.ndim == 3
+        if gain.shape not in ((3,), (n, 3)) or matrix.shape not in ((3, 3), (n, 3, 3)):
+            raise ValueError("demosaic: gain (3,) or (N, 3), matrix (3, 3) or (N, 3, 3)")
+        nc = n if per else 1
+        gains = np.broadcast_to(gain, (nc, 3)) if gain.ndim == 1 else gain
+        mats = np.broadcast_to(matrix, (nc, 3, 3)) if matrix.ndim == 2 else matrix
+        cols = (RgbColor * nc)()
+        for i in range(nc):
+            for c in range(3):
+                cols[i].gain[c] = float(gains[i, c])
+            for j in range(9):
+                cols[i].m[j] = float(mats[i].ravel()[j])
+        prm = RgbParams()
+        prm.algo, prm.dtype, prm.flags, prm.cfa = _RGB_ALGOS[algo], code, FLOAT_CLIP if clip else 0, _CFA_CODES[key]
+        black = list(black)
+        if len(black) != 4:
+            raise ValueError("black: four levels, by CFA position (y & 1) * 2 + (x & 1)")
+        for i in range(4):
+            prm.black[i] = int(black[i])
+        prm.white = float(white)
+        pitch = int(mos.stride(1)) if h > 1 else w
+        fstride = int(mos.stride(0)) if n > 1 else pitch * h
+        cur, run = self._run_stream(torch, dev)
+        try:
+            rc = self._lib.mcraw_demosaic_batch(self._h, C.byref(prm), cols, nc, C.c_void_p(mos.data_ptr()), pitch, fstride, w, h,
+                                                n, C.c_void_p(out.data_ptr()), out.numel() * out.element_size(),
+                                                C.c_void_p(run.cuda_stream))
+        finally:
+            if run is not cur:
+                mos.record_stream(run)
+                out.record_stream(run)
+                cur.wait_stream(run)
+        if rc != 0:
+            raise McrawError("mcraw_demosaic_batch failed (%d): %s" % (rc, self._lib.mcraw_last_error().decode()))
+        return out
+
+    def decode_rgb(self, inputs, width, height, type, *, algo="mhc", dtype, white, black=(0, 0, 0, 0), cfa="rggb",
+                   gain=None, matrix=None, clip=False, out=None, check=True):
+        """Decode frames of one geometry that are resident in HBM and demosaic them (demosaic()): (N, 3, H, W) for "mhc",
+        (N, 3, H/2, W/2) for "bin2".  inputs: uint8 CUDA tensors, or (device pointer, length) pairs.  The plain uint16
+        mosaics go to a scratch tensor of torch's caching allocator; both steps are queued on torch.cuda.current_stream().
+        check=True synchronises after the decode and raises McrawError naming the frames that failed; check=False returns
+        at once.  The stage the context had before the call is restored afterwards."""
+        import torch
+        width, height, n = int(width), int(height), len(inputs)
+        dev = self._torch_device(torch)
+        scratch = torch.empty((n, height, width), dtype=torch.uint16, device=dev)
+        descs = []
+        for i, x in enumerate(inputs):
+            if isinstance(x, torch.Tensor):
+                if x.dtype != torch.uint8 or x.device != dev or not x.is_contiguous():
+                    raise ValueError("decode_rgb: inputs must be contiguous uint8 tensors on %s" % dev)
+                ptr, ln = x.data_ptr(), x.numel()
+            else:
+                ptr, ln = int(x[0]), int(x[1])
+            descs.append((ptr, ln, width, height, int(type), scratch.data_ptr() + i * width * height * 2, width * height))
+        if n:
+            cur, run = self._run_stream(torch, dev)
+            prev = self._stage
+            self.set_post()
+            try:
+                res = self.decode_batch(self.make_frames(descs), mem=MEM_DEVICE, stream=C.c_void_p(run.cuda_stream), want_status=check)
+            finally:
+                self._restore_stage(prev)
+                if run is not cur:
+                    scratch.record_stream(run)
+                    cur.wait_stream(run)
+            if check:
+                bad = [(i, st) for i, st in enumerate(res[1]) if st != 0]
+                if bad:
+                    raise McrawError("decode_rgb: %d of %d frames failed: %s" % (
+                        len(bad), n, ", ".join("frame %d status 0x%x" % b for b in bad[:16])))
+        return self.demosaic(scratch, algo=algo, dtype=dtype, white=white, black=black, cfa=cfa, gain=gain, matrix=matrix,
+                             clip=clip, out=out, check=check)
+
     def profile(self, enable=True, only=None, every=1):
         """Bracket kernel launches with events: all kernels, or just the names in `only`; every `every`-th launch."""
         self._lib.mcraw_ctx_profile_every(self._h, max(1, int(every)))
         if only:
             mode = 0
             for name in only:
-                mode |= 2 << (KERNELS[name] if name in KERNELS else ENC_KERNELS[name])
+                mode |= 2 << _kernel_id(name)
         else:
             mode = 1 if enable else 0
         self._lib.mcraw_ctx_profile(self._h, mode)
@@ -606,7 +804,7 @@ class Context:
     def kernel_ms(self, name, reset=False):
         ms = C.c_double()
         n = C.c_int()
-        kid = KERNELS[name] if name in KERNELS else ENC_KERNELS[name]
+        kid = _kernel_id(name)
         rc = self._lib.mcraw_ctx_kernel_ms(self._h, kid, C.byref(ms), C.byref(n), 1 if reset else 0)
         if rc != 0:
             raise McrawError("mcraw_ctx_kernel_ms failed (%d)" % rc)
