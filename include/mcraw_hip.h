@@ -377,6 +377,38 @@ int mcraw_demosaic_batch(mcraw_ctx *ctx, const mcraw_rgb *p, const mcraw_rgb_col
                          const uint16_t *in, size_t in_pitch, size_t in_frame_stride, int width, int height, int n,
                          void *out, size_t out_bytes, void *stream);
 
+/* ---- uint16 mosaics -> display-ready uint8 / uint16 RGB through a transfer-curve LUT ------------------------------
+ *
+ * The demosaic and colour arithmetic of mcraw_demosaic_batch, bit for bit, up to o_i; then, per output sample (f32, no FMA):
+ *   c   = (o_i > 0.0f) ? fminf(o_i, 1.0f) : 0.0f      always clamped; NaN -> 0
+ *   i   = (uint32_t) rintf(c * (float)(L - 1))        one f32 multiply (RNE), round half to even; 0 <= i <= L - 1
+ *   out = U8 ? (uint8_t)(lut[i] & 0xFF) : lut[i]
+ * Layouts: MCRAW_DISP_CHW = (n, 3, Ho, Wo) as mcraw_demosaic_batch; MCRAW_DISP_HWC = (n, Ho, Wo, 3), interleaved R G B.
+ * `p->dtype` and `p->flags` must be 0 (`d` decides the output type; the clamp is unconditional); everything else in `p`
+ * and `colors` means what it means for mcraw_demosaic_batch, whose argument rules hold here as well.
+ * The LUT (L = 1 << lut_log2 uint16 entries) is the caller's DEVICE memory, read by the queued kernels in stream order and
+ * never copied into or cached by the context: two calls with the same pointer and new contents in between each see their
+ * own.  The call takes no decode serial and leaves the decode slots, mcraw_ctx_errors and the context's stage alone.
+ * Rejected besides (returns < 0, mcraw_last_error says why, nothing is written): a NULL `d`; a NULL or not 16-byte aligned
+ * `lut`; lut_log2 outside 8 .. 16; an unknown dtype or layout; a non-zero `reserved`; a non-zero p->dtype or p->flags;
+ * out_bytes < n * 3 * Ho * Wo * (1 or 2); an `out` not aligned to its element size.
+ * Kernels: MCRAW_KRGB_MHC / MCRAW_KRGB_BIN2 (mcraw_ctx_kernel_ms). */
+#define MCRAW_DISP_U8   1
+#define MCRAW_DISP_U16  2
+#define MCRAW_DISP_CHW  0   /* (n, 3, Ho, Wo), as mcraw_demosaic_batch            */
+#define MCRAW_DISP_HWC  1   /* (n, Ho, Wo, 3), interleaved R G B                   */
+typedef struct mcraw_display {
+    uint32_t dtype;        /* MCRAW_DISP_U8 / MCRAW_DISP_U16                        */
+    uint32_t layout;       /* MCRAW_DISP_CHW / MCRAW_DISP_HWC                       */
+    uint32_t lut_log2;     /* 8 .. 16: the LUT has L = 1 << lut_log2 entries        */
+    uint32_t reserved;     /* must be 0                                             */
+    const uint16_t *lut;   /* DEVICE memory, 16-byte aligned, read in stream order  */
+} mcraw_display;           /* sizeof 24, lut at offset 16                           */
+int mcraw_demosaic_display_batch(mcraw_ctx *ctx, const mcraw_rgb *p, const mcraw_display *d,
+                                 const mcraw_rgb_color *colors, int ncolors, const uint16_t *in, size_t in_pitch,
+                                 size_t in_frame_stride, int width, int height, int n, void *out, size_t out_bytes,
+                                 void *stream);
+
 /* ---- environment ------------------------------------------------------------------------------
  * Read when a context (or pool) is created, never afterwards:
  *   MCRAW_DEVICE=n, MCRAW_DEVICES=all|0,1,5   default device of the five-argument entry points / members of a default pool

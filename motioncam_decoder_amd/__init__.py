@@ -13,7 +13,8 @@ import os
 
 __all__ = ["lib_path", "load", "Context", "Pool", "Frame", "EncFrame", "FloatOut", "McrawError", "TYPE_LEGACY", "TYPE_BLOCK",
            "MEM_DEVICE", "MEM_HOST", "KERNELS", "ENC_KERNELS", "ABI_SYMBOLS", "encode_bound7", "cfa_planes",
-           "RgbParams", "RgbColor", "RGB_KERNELS", "rgb_color"]
+           "RgbParams", "RgbColor", "RGB_KERNELS", "rgb_color", "Display", "transfer_lut", "DISP_U8", "DISP_U16",
+           "DISP_CHW", "DISP_HWC"]
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 
@@ -40,7 +41,7 @@ ABI_SYMBOLS = [
     "mcraw_pool_decode_batch_device", "mcraw_ctx_xcd_runs", "mcraw_pool_synchronize", "mcraw_tile_order",
     "mcraw_ctx_last_serial", "mcraw_ctx_batch_status", "mcraw_ctx_errors", "mcraw_ctx_side_parts", "mcraw_ctx_host_way",
     "mcraw_encode_bound7", "mcraw_encode_batch", "mcraw_encode7", "mcraw_ctx_set_float_out", "mcraw_pool_set_float_out",
-    "mcraw_demosaic_batch",
+    "mcraw_demosaic_batch", "mcraw_demosaic_display_batch",
 ]
 
 POST_BLACK, POST_PACK12, POST_PACK10, POST_PACK14 = 1, 2, 4, 8
@@ -130,6 +131,91 @@ class RgbParams(C.Structure):
 class RgbColor(C.Structure):
     """struct mcraw_rgb_color (include/mcraw_hip.h): white-balance gains and a row-major 3x3 matrix, out = m . v."""
     _fields_ = [("gain", C.c_float * 3), ("m", C.c_float * 9)]
+
+
+# display-ready integer RGB through a transfer-curve LUT (mcraw_demosaic_display_batch)
+DISP_U8, DISP_U16 = 1, 2
+DISP_CHW, DISP_HWC = 0, 1
+_DISP_LAYOUTS = {"chw": DISP_CHW, "hwc": DISP_HWC}
+
+
+class Display(C.Structure):
+    """struct mcraw_display (include/mcraw_hip.h): output dtype, layout and the device LUT of L = 1 << lut_log2 entries."""
+    _fields_ = [("dtype", C.c_uint32), ("layout", C.c_uint32), ("lut_log2", C.c_uint32), ("reserved", C.c_uint32),
+                ("lut", C.c_void_p)]
+
+
+def _srgb_oetf(x):
+    import numpy as np
+    return np.where(x <= 0.0031308, 12.92 * x, 1.055 * np.power(x, 1.0 / 2.4) - 0.055)
+
+
+def _bt709_oetf(x):
+    import numpy as np
+    return np.where(x < 0.018, 4.5 * x, 1.099 * np.power(x, 0.45) - 0.099)
+
+
+def transfer_lut(curve="srgb", size=4096, bits=8):
+    """uint16 numpy array of `size` entries: code[k] = rint(f(k / (size - 1)) * (2**bits - 1)), f evaluated in float64 and
+    clamped to [0, 1].  curve: "linear", "srgb" (IEC 61966-2-1), "bt709" (4.5 x below 0.018, else 1.099 x^0.45 - 0.099), a
+    number g for x ** (1 / g), or a callable on [0, 1] (numpy array in, array out).  size: a power of two, 256 .. 65536;
+    bits: 8, 10, 12 or 16."""
+    import numpy as np
+    size, bits = int(size), int(bits)
+    if size < 256 or size > 65536 or size & (size - 1):
+        raise ValueError("transfer_lut: size must be a power of two, 256 .. 65536, not %d" % size)
+    if bits not in (8, 10, 12, 16):
+        raise ValueError("transfer_lut: bits must be 8, 10, 12 or 16, not %d" % bits)
+    x = np.arange(size, dtype=np.float64) / float(size - 1)
+    if callable(curve):
+        f = curve
+    elif isinstance(curve, str):
+        f = {"linear": lambda v: v, "srgb": _srgb_oetf, "bt709": _bt709_oetf}.get(curve.lower())
+        if f is None:
+            raise ValueError("transfer_lut: unknown curve %r (linear, srgb, bt709, a gamma or a callable)" % (curve,))
+    elif isinstance(curve, (int, float)) and not isinstance(curve, bool):
+        g = float(curve)
+        if not (g > 0.0) or g == float("inf"):
+            raise ValueError("transfer_lut: the gamma must be finite and positive, not %r" % (curve,))
+        f = lambda v: np.power(v, 1.0 / g)
+    else:
+        raise ValueError("transfer_lut: curve must be a name, a number or a callable, not %r" % (curve,))
+    y = np.asarray(f(x), dtype=np.float64)
+    if y.shape != x.shape or not np.isfinite(y).all():
+        raise ValueError("transfer_lut: the curve must give one finite value per input")
+    return np.rint(np.clip(y, 0.0, 1.0) * float((1 << bits) - 1)).astype(np.uint16)
+
+
+def _rgb_colors(gain, matrix, n, fn):
+    """(RgbColor array, ncolors) of gain (3,) / (N, 3) and matrix (3, 3) / (N, 3, 3): one set, or one per frame."""
+    import numpy as np
+    gain = np.ones(3, np.float32) if gain is None else np.asarray(gain, dtype=np.float32)
+    matrix = np.eye(3, dtype=np.float32) if matrix is None else np.asarray(matrix, dtype=np.float32)
+    per = gain.ndim == 2 or matrix.ndim == 3
+    if gain.shape not in ((3,), (n, 3)) or matrix.shape not in ((3, 3), (n, 3, 3)):
+        raise ValueError("%s: gain (3,) or (N, 3), matrix (3, 3) or (N, 3, 3)" % fn)
+    nc = n if per else 1
+    gains = np.broadcast_to(gain, (nc, 3)) if gain.ndim == 1 else gain
+    mats = np.broadcast_to(matrix, (nc, 3, 3)) if matrix.ndim == 2 else matrix
+    cols = (RgbColor * nc)()
+    for i in range(nc):
+        for c in range(3):
+            cols[i].gain[c] = float(gains[i, c])
+        for j in range(9):
+            cols[i].m[j] = float(mats[i].ravel()[j])
+    return cols, nc
+
+
+def _rgb_params(algo, dtype_code, flags, cfa_key, white, black):
+    prm = RgbParams()
+    prm.algo, prm.dtype, prm.flags, prm.cfa = _RGB_ALGOS[algo], dtype_code, flags, _CFA_CODES[cfa_key]
+    black = list(black)
+    if len(black) != 4:
+        raise ValueError("black: four levels, by CFA position (y & 1) * 2 + (x & 1)")
+    for i in range(4):
+        prm.black[i] = int(black[i])
+    prm.white = float(white)
+    return prm
 
 
 def _xyz_d50_to_srgb():
@@ -309,6 +395,10 @@ def load():
     lib.mcraw_demosaic_batch.restype = C.c_int
     lib.mcraw_demosaic_batch.argtypes = [C.c_void_p, C.POINTER(RgbParams), C.POINTER(RgbColor), C.c_int, C.c_void_p, C.c_size_t,
                                          C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.mcraw_demosaic_display_batch.restype = C.c_int
+    lib.mcraw_demosaic_display_batch.argtypes = [C.c_void_p, C.POINTER(RgbParams), C.POINTER(Display), C.POINTER(RgbColor),
+                                                 C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int,
+                                                 C.c_void_p, C.c_size_t, C.c_void_p]
     lib.mcraw_encode7.restype = C.c_size_t
     lib.mcraw_encode7.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int]
     _lib = lib
@@ -688,7 +778,6 @@ class Context:
         torch.cuda.current_stream(); nothing synchronises.  `check` is accepted for symmetry with decode_rgb (the
         arguments are always checked; there are no per-frame statuses)."""
         import torch
-        import numpy as np
         if algo not in _RGB_ALGOS:
             raise ValueError("algo must be 'mhc' or 'bin2', not %r" % (algo,))
         key = str(cfa).strip().lower()
@@ -713,28 +802,8 @@ class Context:
             raise ValueError("demosaic: out must be a contiguous %s tensor of shape %s on %s" % (tdtype, tuple(want), dev))
         if n == 0:
             return out
-        gain = np.ones(3, np.float32) if gain is None else np.asarray(gain, dtype=np.float32)
-        matrix = np.eye(3, dtype=np.float32) if matrix is None else np.asarray(matrix, dtype=np.float32)
-        per = gain.ndim == 2 or matrix.ndim == 3
-        if gain.shape not in ((3,), (n, 3)) or matrix.shape not in ((3, 3), (n, 3, 3)):
-            raise ValueError("demosaic: gain (3,) or (N, 3), matrix (3, 3) or (N, 3, 3)")
-        nc = n if per else 1
-        gains = np.broadcast_to(gain, (nc, 3)) if gain.ndim == 1 else gain
-        mats = np.broadcast_to(matrix, (nc, 3, 3)) if matrix.ndim == 2 else matrix
-        cols = (RgbColor * nc)()
-        for i in range(nc):
-            for c in range(3):
-                cols[i].gain[c] = float(gains[i, c])
-            for j in range(9):
-                cols[i].m[j] = float(mats[i].ravel()[j])
-        prm = RgbParams()
-        prm.algo, prm.dtype, prm.flags, prm.cfa = _RGB_ALGOS[algo], code, FLOAT_CLIP if clip else 0, _CFA_CODES[key]
-        black = list(black)
-        if len(black) != 4:
-            raise ValueError("black: four levels, by CFA position (y & 1) * 2 + (x & 1)")
-        for i in range(4):
-            prm.black[i] = int(black[i])
-        prm.white = float(white)
+        cols, nc = _rgb_colors(gain, matrix, n, "demosaic")
+        prm = _rgb_params(algo, code, FLOAT_CLIP if clip else 0, key, white, black)
         pitch = int(mos.stride(1)) if h > 1 else w
         fstride = int(mos.stride(0)) if n > 1 else pitch * h
         cur, run = self._run_stream(torch, dev)
@@ -751,13 +820,9 @@ class Context:
             raise McrawError("mcraw_demosaic_batch failed (%d): %s" % (rc, self._lib.mcraw_last_error().decode()))
         return out
 
-    def decode_rgb(self, inputs, width, height, type, *, algo="mhc", dtype, white, black=(0, 0, 0, 0), cfa="rggb",
-                   gain=None, matrix=None, clip=False, out=None, check=True):
-        """Decode frames of one geometry that are resident in HBM and demosaic them (demosaic()): (N, 3, H, W) for "mhc",
-        (N, 3, H/2, W/2) for "bin2".  inputs: uint8 CUDA tensors, or (device pointer, length) pairs.  The plain uint16
-        mosaics go to a scratch tensor of torch's caching allocator; both steps are queued on torch.cuda.current_stream().
-        check=True synchronises after the decode and raises McrawError naming the frames that failed; check=False returns
-        at once.  The stage the context had before the call is restored afterwards."""
+    def _decode_scratch(self, inputs, width, height, type, check, fn):
+        """The plain uint16 mosaics of frames resident in HBM, decoded into a scratch tensor on the current stream (for
+        decode_rgb / decode_display; the stage is restored afterwards)."""
         import torch
         width, height, n = int(width), int(height), len(inputs)
         dev = self._torch_device(torch)
@@ -766,7 +831,7 @@ class Context:
         for i, x in enumerate(inputs):
             if isinstance(x, torch.Tensor):
                 if x.dtype != torch.uint8 or x.device != dev or not x.is_contiguous():
-                    raise ValueError("decode_rgb: inputs must be contiguous uint8 tensors on %s" % dev)
+                    raise ValueError("%s: inputs must be contiguous uint8 tensors on %s" % (fn, dev))
                 ptr, ln = x.data_ptr(), x.numel()
             else:
                 ptr, ln = int(x[0]), int(x[1])
@@ -785,10 +850,124 @@ class Context:
             if check:
                 bad = [(i, st) for i, st in enumerate(res[1]) if st != 0]
                 if bad:
-                    raise McrawError("decode_rgb: %d of %d frames failed: %s" % (
-                        len(bad), n, ", ".join("frame %d status 0x%x" % b for b in bad[:16])))
+                    raise McrawError("%s: %d of %d frames failed: %s" % (
+                        fn, len(bad), n, ", ".join("frame %d status 0x%x" % b for b in bad[:16])))
+        return scratch
+
+    def decode_rgb(self, inputs, width, height, type, *, algo="mhc", dtype, white, black=(0, 0, 0, 0), cfa="rggb",
+                   gain=None, matrix=None, clip=False, out=None, check=True):
+        """Decode frames of one geometry that are resident in HBM and demosaic them (demosaic()): (N, 3, H, W) for "mhc",
+        (N, 3, H/2, W/2) for "bin2".  inputs: uint8 CUDA tensors, or (device pointer, length) pairs.  The plain uint16
+        mosaics go to a scratch tensor of torch's caching allocator; both steps are queued on torch.cuda.current_stream().
+        check=True synchronises after the decode and raises McrawError naming the frames that failed; check=False returns
+        at once.  The stage the context had before the call is restored afterwards."""
+        scratch = self._decode_scratch(inputs, width, height, type, check, "decode_rgb")
         return self.demosaic(scratch, algo=algo, dtype=dtype, white=white, black=black, cfa=cfa, gain=gain, matrix=matrix,
                              clip=clip, out=out, check=check)
+
+    def _display_lut(self, torch, dev, transfer, lut_size, bits):
+        """(device LUT tensor, caller-owned?) for demosaic_display: a ready 1-D uint16 LUT (CUDA tensor on `dev`, or a
+        host array, uploaded), or the built-in curve of transfer_lut, built once per (curve, size, bits, device)."""
+        import numpy as np
+        if isinstance(transfer, torch.Tensor):
+            if transfer.device != dev or transfer.dim() != 1 or transfer.dtype not in (torch.uint16, torch.int16) \
+                    or not transfer.is_contiguous():
+                raise ValueError("demosaic_display: a LUT tensor must be a contiguous 1-D uint16 tensor on %s" % dev)
+            lut, own = transfer.view(torch.uint16), True
+        elif isinstance(transfer, np.ndarray):
+            if transfer.ndim != 1 or transfer.dtype != np.uint16:
+                raise ValueError("demosaic_display: a LUT array must be 1-D uint16")
+            lut, own = torch.from_numpy(np.ascontiguousarray(transfer).view(np.int16)).to(dev).view(torch.uint16), True
+        else:
+            key = (transfer if isinstance(transfer, str) else float(transfer) if not callable(transfer) else None,
+                   int(lut_size), int(bits), str(dev))
+            cache = self.__dict__.setdefault("_luts", {})
+            lut = cache.get(key) if key[0] is not None else None
+            if lut is None:
+                host = transfer_lut(transfer, lut_size, bits)
+                lut = torch.from_numpy(host.view(np.int16)).to(dev).view(torch.uint16)
+                if key[0] is not None:
+                    cache[key] = lut
+            own = False
+        L = int(lut.numel())
+        if L < 256 or L > 65536 or L & (L - 1):
+            raise ValueError("demosaic_display: the LUT length must be a power of two, 256 .. 65536, not %d" % L)
+        return lut, own
+
+    def demosaic_display(self, mosaic, *, algo="mhc", white, black=(0, 0, 0, 0), cfa="rggb", gain=None, matrix=None,
+                         transfer="srgb", lut_size=4096, dtype=None, layout="hwc", bits=None, out=None, check=True):
+        """uint16 mosaics resident on the context's device -> display-ready integer RGB: the demosaic and colours of
+        demosaic(), then clamp to [0, 1], index a transfer-curve LUT of L entries at rint(c * (L - 1)) and store the entry
+        (its low byte for uint8).  dtype: torch.uint8 (default) or torch.uint16; layout "hwc" gives (N, Ho, Wo, 3), "chw"
+        (N, 3, Ho, Wo) (an (H, W) mosaic drops N).  transfer: "srgb", "bt709", "linear", a gamma g (x ** (1/g)), a callable
+        on [0, 1] -- built by transfer_lut(transfer, lut_size, bits), bits 8 for uint8 and 16 for uint16 unless given --
+        or a ready 1-D uint16 LUT (host array or CUDA tensor) whose length is a power of two, 256 .. 65536.  Queued on
+        torch.cuda.current_stream(); nothing synchronises, and a caller's LUT is read when the kernels run (in stream
+        order).  `check` is accepted for symmetry with decode_display."""
+        import torch
+        if algo not in _RGB_ALGOS:
+            raise ValueError("algo must be 'mhc' or 'bin2', not %r" % (algo,))
+        key = str(cfa).strip().lower()
+        if key not in _CFA_CODES:
+            raise ValueError("unknown cfa %r (rggb, bggr, grbg or gbrg)" % (cfa,))
+        dtype = torch.uint8 if dtype is None else dtype
+        dcode = {torch.uint8: DISP_U8, torch.uint16: DISP_U16, "u8": DISP_U8, "u16": DISP_U16}.get(dtype)
+        if dcode is None:
+            raise ValueError("demosaic_display: dtype must be torch.uint8 or torch.uint16, not %r" % (dtype,))
+        tdtype = torch.uint8 if dcode == DISP_U8 else torch.uint16
+        if layout not in _DISP_LAYOUTS:
+            raise ValueError("demosaic_display: layout must be 'hwc' or 'chw', not %r" % (layout,))
+        dev = self._torch_device(torch)
+        if not isinstance(mosaic, torch.Tensor) or mosaic.dtype != torch.uint16 or mosaic.device != dev or mosaic.dim() not in (2, 3):
+            raise ValueError("demosaic_display: mosaic must be a uint16 tensor (N, H, W) or (H, W) on %s" % dev)
+        single = mosaic.dim() == 2
+        mos = mosaic.unsqueeze(0) if single else mosaic
+        n, h, w = (int(v) for v in mos.shape)
+        if n and h > 1 and mos.stride(2) != 1:
+            raise ValueError("demosaic_display: the rows of the mosaic must be contiguous")
+        ho, wo = (h, w) if algo == "mhc" else (h // 2, w // 2)
+        shape = (n, ho, wo, 3) if layout == "hwc" else (n, 3, ho, wo)
+        want = shape[1:] if single else shape
+        if out is None:
+            out = torch.empty(want, dtype=tdtype, device=dev)
+        elif tuple(out.shape) != tuple(want) or out.dtype != tdtype or out.device != dev or not out.is_contiguous():
+            raise ValueError("demosaic_display: out must be a contiguous %s tensor of shape %s on %s" % (tdtype, tuple(want), dev))
+        if n == 0:
+            return out
+        lut, own = self._display_lut(torch, dev, transfer, lut_size, (8 if dcode == DISP_U8 else 16) if bits is None else bits)
+        cols, nc = _rgb_colors(gain, matrix, n, "demosaic_display")
+        prm = _rgb_params(algo, 0, 0, key, white, black)
+        d = Display()
+        d.dtype, d.layout, d.lut_log2, d.reserved = dcode, _DISP_LAYOUTS[layout], int(lut.numel()).bit_length() - 1, 0
+        d.lut = lut.data_ptr()
+        pitch = int(mos.stride(1)) if h > 1 else w
+        fstride = int(mos.stride(0)) if n > 1 else pitch * h
+        cur, run = self._run_stream(torch, dev)
+        try:
+            rc = self._lib.mcraw_demosaic_display_batch(self._h, C.byref(prm), C.byref(d), cols, nc, C.c_void_p(mos.data_ptr()),
+                                                        pitch, fstride, w, h, n, C.c_void_p(out.data_ptr()),
+                                                        out.numel() * out.element_size(), C.c_void_p(run.cuda_stream))
+        finally:
+            if run is not cur:
+                mos.record_stream(run)
+                out.record_stream(run)
+                if own:
+                    lut.record_stream(run)
+                cur.wait_stream(run)
+        if rc != 0:
+            raise McrawError("mcraw_demosaic_display_batch failed (%d): %s" % (rc, self._lib.mcraw_last_error().decode()))
+        return out
+
+    def decode_display(self, inputs, width, height, type, *, algo="mhc", white, black=(0, 0, 0, 0), cfa="rggb", gain=None,
+                       matrix=None, transfer="srgb", lut_size=4096, dtype=None, layout="hwc", bits=None, out=None, check=True):
+        """Decode frames of one geometry that are resident in HBM and turn them into display-ready RGB
+        (demosaic_display()), as decode_rgb does: the plain uint16 mosaics go to a scratch tensor, both steps are queued on
+        torch.cuda.current_stream(), check=True synchronises after the decode and raises McrawError naming the frames that
+        failed, and the context's stage is restored afterwards."""
+        scratch = self._decode_scratch(inputs, width, height, type, check, "decode_display")
+        return self.demosaic_display(scratch, algo=algo, white=white, black=black, cfa=cfa, gain=gain, matrix=matrix,
+                                     transfer=transfer, lut_size=lut_size, dtype=dtype, layout=layout, bits=bits, out=out,
+                                     check=check)
 
     def profile(self, enable=True, only=None, every=1):
         """Bracket kernel launches with events: all kernels, or just the names in `only`; every `every`-th launch."""

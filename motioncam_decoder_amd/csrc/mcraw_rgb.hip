@@ -6,6 +6,11 @@
 // Both write (N, 3, Ho, Wo), channel-major per frame.  The arithmetic is the contract of include/mcraw_hip.h; the
 // numpy statement of it is tests/_rgb_ref.py.  One instance per (dtype, CFA): the CFA decides at compile time which
 // filter every lane slot runs.  CLIP is a wave-uniform run-time flag (v_med3_f32 under a uniform branch).
+//
+// The display kinds (PK_DISP8 / PK_DISP16, mcraw_demosaic_display_batch) share the integer estimates and the colour stage,
+// then clamp, index a transfer-curve LUT and store uint8 / uint16, (N, 3, Ho, Wo) or (N, Ho, Wo, 3): layout and where the
+// LUT is read from (LDS or global) are wave-uniform run-time flags.  Their grids are persistent (a grid-stride loop over
+// tiles), so that each workgroup stages the LUT in LDS once; tests/_display_ref.py states the stage in numpy.
 #include <cmath>
 
 #include "mcraw_dev.h"
@@ -33,6 +38,12 @@ struct RgbArgs {
     uint32_t clip, percol;
     int32_t black[4];
     RgbCol col[RGB_MAXF];
+    // display kinds only (behind the float kinds' fields, which keep their offsets)
+    const uint16_t *lut; // the transfer-curve LUT (caller's device memory, 16-byte aligned)
+    uint32_t lutn;       // LUT entries L (a power of two, 256 .. 65536)
+    uint32_t lutg;       // the LUT is read from global memory (L > DISP_LDS_MAX) rather than staged in LDS
+    uint32_t hwc;        // (n, Ho, Wo, 3) rather than (n, 3, Ho, Wo)
+    uint32_t units, nf;  // tiles (MHC) or workgroups' items (BIN2) per frame; frames in this launch
 };
 
 constexpr uint32_t RGB_T = 256;             // threads per workgroup
@@ -41,6 +52,12 @@ constexpr uint32_t MHC_TH = 32;             // tile rows: 8 row pairs x 2 passes
 constexpr uint32_t MHC_LW = MHC_TW + 16;    // LDS row: 8 columns either side (2 used), so that chunks stay on the 8-grid
 constexpr uint32_t MHC_LH = MHC_TH + 4;     // 2 halo rows above and below
 constexpr uint32_t MHC_CH = MHC_LW / 8u;    // 16-byte chunks per LDS row
+
+// display output kinds (beside PK_F32 / PK_F16 / PK_BF16 of mcraw_plan.h)
+constexpr int PK_DISP8 = 48, PK_DISP16 = 49;
+constexpr uint32_t DISP_LDS_MAX = 4096; // LUTs up to this many entries (8 KiB) are staged in LDS
+constexpr bool is_disp(int pk) { return pk == PK_DISP8 || pk == PK_DISP16; }
+constexpr uint32_t out_es(int pk) { return pk == PK_F32 ? 4u : pk == PK_DISP8 ? 1u : 2u; }
 
 static __device__ __forceinline__ int reflect101(int i, int n)
 {
@@ -61,13 +78,11 @@ __device__ __forceinline__ uint32_t bits16(float v)
 // E (3 channels x 8 pixels of one row) -> o_i = (m[3i] v0 + m[3i+1] v1) + m[3i+2] v2, v_c = (float)E_c * k[c], every
 // product and sum rounded on its own (no FMA), optional clamp, stored as 8 consecutive elements of row y, column x, of each
 // plane.  `n`: elements of the 8 that exist.
-template <int PK>
-__device__ __forceinline__ void rgb_store8(const RgbArgs &A, const RgbCol &col, uint8_t *frame_out, uint32_t y, uint32_t x,
-                                           uint32_t n, const int (&E)[3][8])
+// The colour stage every output kind shares: o_i = (m[3i] v0 + m[3i+1] v1) + m[3i+2] v2, v_c = (float)E_c * k[c].
+__device__ __forceinline__ void rgb_color8(const RgbCol &col, const int (&E)[3][8], float (&o)[3][8])
 {
 #pragma clang fp contract(off)
-    constexpr uint32_t ES = PK == PK_F32 ? 4u : 2u;
-    float v[3][8], o[3][8];
+    float v[3][8];
 #pragma unroll
     for (int c = 0; c < 3; c++)
 #pragma unroll
@@ -80,6 +95,16 @@ __device__ __forceinline__ void rgb_store8(const RgbArgs &A, const RgbCol &col, 
             const float a = col.m[3 * r] * v[0][i], b = col.m[3 * r + 1] * v[1][i], c = col.m[3 * r + 2] * v[2][i];
             o[r][i] = (a + b) + c;
         }
+}
+
+template <int PK>
+__device__ __forceinline__ void rgb_store8(const RgbArgs &A, const RgbCol &col, uint8_t *frame_out, uint32_t y, uint32_t x,
+                                           uint32_t n, const int (&E)[3][8])
+{
+#pragma clang fp contract(off)
+    constexpr uint32_t ES = PK == PK_F32 ? 4u : 2u;
+    float o[3][8];
+    rgb_color8(col, E, o);
     if (A.clip) {
 #pragma unroll
         for (int r = 0; r < 3; r++)
@@ -126,140 +151,301 @@ __device__ __forceinline__ void rgb_store8(const RgbArgs &A, const RgbCol &col, 
     }
 }
 
+// The display stage: the colour stage, then per sample c = o > 0 ? min(o, 1) : 0 (NaN -> 0), i = rint(c * (L - 1)) (one
+// f32 multiply, RNE), q = lut[i] (the low byte for uint8).  The LUT is read from LDS (s_lut, staged by the kernel) or,
+// for L > DISP_LDS_MAX, from global memory through L1 / L2.  Stores, plain (each instruction covers only part of the
+// lines it touches in HWC):
+//   CHW  u8: 8 B per plane (8-byte aligned); u16: 16 B per plane (16-byte aligned)
+//   HWC  u8: 24 B per lane as 16 + 8 B, in whichever order keeps the 16-byte store 16-byte aligned (8-byte aligned rows);
+//        u16: 48 B per lane as three 16-byte stores (16-byte aligned rows)
+//   element stores for a cropped row end and for rows off those grids
+template <int PK>
+__device__ __forceinline__ void disp_store8(const RgbArgs &A, const RgbCol &col, const uint16_t *s_lut, uint8_t *frame_out,
+                                            uint32_t y, uint32_t x, uint32_t n, const int (&E)[3][8])
+{
+#pragma clang fp contract(off)
+    constexpr uint32_t ES = out_es(PK);
+    float o[3][8];
+    rgb_color8(col, E, o);
+    const float lf = static_cast<float>(A.lutn - 1u);
+    uint32_t q[3][8];
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            const float c = o[r][i] > 0.0f ? fminf(o[r][i], 1.0f) : 0.0f;
+            q[r][i] = static_cast<uint32_t>(rintf(c * lf));
+        }
+    if (A.lutg) {
+#pragma unroll
+        for (int r = 0; r < 3; r++)
+#pragma unroll
+            for (int i = 0; i < 8; i++)
+                q[r][i] = gptr<const uint16_t>(A.lut)[q[r][i]];
+    } else {
+#pragma unroll
+        for (int r = 0; r < 3; r++)
+#pragma unroll
+            for (int i = 0; i < 8; i++)
+                q[r][i] = s_lut[q[r][i]];
+    }
+    if (ES == 1u) {
+#pragma unroll
+        for (int r = 0; r < 3; r++)
+#pragma unroll
+            for (int i = 0; i < 8; i++)
+                q[r][i] &= 0xffu;
+    }
+    const bool full = n == 8u;
+    if (A.hwc) {
+        uint8_t *dst = frame_out + (static_cast<size_t>(y) * A.Wo + x) * 3u * ES;
+        const uintptr_t a = reinterpret_cast<uintptr_t>(dst);
+        if (ES == 1u) {
+            uint32_t w[6] = {0, 0, 0, 0, 0, 0}; // byte j: pixel j / 3, channel j % 3
+#pragma unroll
+            for (int j = 0; j < 24; j++)
+                w[j >> 2] |= q[j % 3][j / 3] << (8 * (j & 3));
+            if (full && (a & 7u) == 0u) {
+                if ((a & 8u) == 0u) {
+                    *gptr<mcraw_u32x4>(dst) = mcraw_u32x4{w[0], w[1], w[2], w[3]};
+                    *gptr<mcraw_u32x2>(dst + 16) = mcraw_u32x2{w[4], w[5]};
+                } else {
+                    *gptr<mcraw_u32x2>(dst) = mcraw_u32x2{w[0], w[1]};
+                    *gptr<mcraw_u32x4>(dst + 8) = mcraw_u32x4{w[2], w[3], w[4], w[5]};
+                }
+            } else {
+#pragma unroll
+                for (uint32_t i = 0; i < 8u; i++)
+                    if (i < n) {
+#pragma unroll
+                        for (uint32_t c = 0; c < 3u; c++)
+                            gptr<uint8_t>(dst)[3u * i + c] = static_cast<uint8_t>(q[c][i]);
+                    }
+            }
+        } else {
+            uint32_t w[12]; // uint16 j: pixel j / 3, channel j % 3
+#pragma unroll
+            for (int k = 0; k < 12; k++)
+                w[k] = q[(2 * k) % 3][(2 * k) / 3] | (q[(2 * k + 1) % 3][(2 * k + 1) / 3] << 16);
+            if (full && (a & 15u) == 0u) {
+#pragma unroll
+                for (int h = 0; h < 3; h++)
+                    *gptr<mcraw_u32x4>(dst + 16 * h) = mcraw_u32x4{w[4 * h], w[4 * h + 1], w[4 * h + 2], w[4 * h + 3]};
+            } else {
+#pragma unroll
+                for (uint32_t i = 0; i < 8u; i++)
+                    if (i < n) {
+#pragma unroll
+                        for (uint32_t c = 0; c < 3u; c++)
+                            gptr<uint16_t>(dst)[3u * i + c] = static_cast<uint16_t>(q[c][i]);
+                    }
+            }
+        }
+        return;
+    }
+    const size_t plane = static_cast<size_t>(A.Ho) * A.Wo;
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+        uint8_t *dst = frame_out + (r * plane + static_cast<size_t>(y) * A.Wo + x) * ES;
+        const uintptr_t a = reinterpret_cast<uintptr_t>(dst);
+        if (ES == 1u) {
+            const uint32_t w0 = q[r][0] | (q[r][1] << 8) | (q[r][2] << 16) | (q[r][3] << 24);
+            const uint32_t w1 = q[r][4] | (q[r][5] << 8) | (q[r][6] << 16) | (q[r][7] << 24);
+            if (full && (a & 7u) == 0u) {
+                *gptr<mcraw_u32x2>(dst) = mcraw_u32x2{w0, w1};
+            } else {
+#pragma unroll
+                for (uint32_t i = 0; i < 8u; i++)
+                    if (i < n)
+                        gptr<uint8_t>(dst)[i] = static_cast<uint8_t>(q[r][i]);
+            }
+        } else {
+            if (full && (a & 15u) == 0u) {
+                *gptr<mcraw_u32x4>(dst) = mcraw_u32x4{q[r][0] | (q[r][1] << 16), q[r][2] | (q[r][3] << 16),
+                                                      q[r][4] | (q[r][5] << 16), q[r][6] | (q[r][7] << 16)};
+            } else {
+#pragma unroll
+                for (uint32_t i = 0; i < 8u; i++)
+                    if (i < n)
+                        gptr<uint16_t>(dst)[i] = static_cast<uint16_t>(q[r][i]);
+            }
+        }
+    }
+}
+
+// A display kernel's workgroup stages an LDS-sized LUT once, before its first tile (the caller syncs).
+__device__ __forceinline__ void stage_lut(const RgbArgs &A, uint16_t *s_lut)
+{
+    if (A.lutg)
+        return;
+    for (uint32_t i = threadIdx.x; i < A.lutn / 8u; i += RGB_T)
+        *reinterpret_cast<mcraw_u32x4 *>(&s_lut[8u * i]) = gptr<const mcraw_u32x4>(A.lut)[i];
+}
+
 // ---- MHC --------------------------------------------------------------------------------------------------------------
 //
 // A workgroup owns a tile of 256 columns x 32 rows of one frame.  It stages the tile and a 2-pixel halo (reflected at the
 // frame edges) in LDS as raw samples, 16-byte chunks on the frame's 8-column grid.  Lane (lx, ly) then makes 8 columns of
 // row pairs ly and ly + 8: four CFA quads, so every filter choice is fixed per lane slot by the CFA (template S: the RGGB
 // role of CFA position p is p ^ S).  The halo rows are read again by the tiles above and below (L2 / Infinity Cache).
+// Float kinds: one tile per workgroup (blockIdx.x: tile, blockIdx.y: frame).  Display kinds: a persistent grid whose
+// workgroups stage the LUT in LDS once and then take units t = blockIdx.x, + gridDim.x, ... (A.units tiles per frame, of
+// the launch's A.nf frames); the loop runs once for the float kinds.
 template <int PK, int S>
 __global__ void __launch_bounds__(RGB_T) krgb_mhc(const RgbArgs A)
 {
+    constexpr bool DISP = is_disp(PK);
     __shared__ __attribute__((aligned(16))) uint16_t s_t[MHC_LH * MHC_LW];
-    const uint32_t f = blockIdx.y, tx = blockIdx.x % A.tilesX, ty = blockIdx.x / A.tilesX;
-    const int W = static_cast<int>(A.W), H = static_cast<int>(A.H);
-    const int x0 = static_cast<int>(tx * MHC_TW), y0 = static_cast<int>(ty * MHC_TH);
-    const uint16_t *in = A.in + static_cast<size_t>(f) * A.fstride;
-    for (uint32_t i = threadIdx.x; i < MHC_LH * MHC_CH; i += RGB_T) {
-        const uint32_t r = i / MHC_CH, q = i % MHC_CH;
-        const uint16_t *row = in + static_cast<size_t>(reflect101(y0 - 2 + static_cast<int>(r), H)) * A.pitch;
-        const int xs = x0 - 8 + 8 * static_cast<int>(q);
-        mcraw_u32x4 v;
-        if (A.invec && xs >= 0 && xs + 8 <= W) {
-            v = *gptr<const mcraw_u32x4>(row + xs);
-        } else {
-            uint32_t u[8];
-#pragma unroll
-            for (int e = 0; e < 8; e++)
-                u[e] = gptr<const uint16_t>(row)[reflect101(xs + e, W)];
-            v = mcraw_u32x4{u[0] | (u[1] << 16), u[2] | (u[3] << 16), u[4] | (u[5] << 16), u[6] | (u[7] << 16)};
+    __shared__ __attribute__((aligned(16))) uint16_t s_lut[DISP ? DISP_LDS_MAX : 8u];
+    uint32_t t = blockIdx.x;
+    if constexpr (DISP)
+        stage_lut(A, s_lut);
+    do {
+        if constexpr (DISP)
+            __syncthreads(); // the LUT is staged; the previous tile's LDS reads are done
+        const uint32_t f = DISP ? t / A.units : blockIdx.y, u = DISP ? t % A.units : blockIdx.x;
+        const uint32_t tx = u % A.tilesX, ty = u / A.tilesX;
+        const int W = static_cast<int>(A.W), H = static_cast<int>(A.H);
+        const int x0 = static_cast<int>(tx * MHC_TW), y0 = static_cast<int>(ty * MHC_TH);
+        const uint16_t *in = A.in + static_cast<size_t>(f) * A.fstride;
+        for (uint32_t i = threadIdx.x; i < MHC_LH * MHC_CH; i += RGB_T) {
+            const uint32_t r = i / MHC_CH, q = i % MHC_CH;
+            const uint16_t *row = in + static_cast<size_t>(reflect101(y0 - 2 + static_cast<int>(r), H)) * A.pitch;
+            const int xs = x0 - 8 + 8 * static_cast<int>(q);
+            mcraw_u32x4 v;
+            if (A.invec && xs >= 0 && xs + 8 <= W) {
+                v = *gptr<const mcraw_u32x4>(row + xs);
+            } else {
+                uint32_t u[8];
+    #pragma unroll
+                for (int e = 0; e < 8; e++)
+                    u[e] = gptr<const uint16_t>(row)[reflect101(xs + e, W)];
+                v = mcraw_u32x4{u[0] | (u[1] << 16), u[2] | (u[3] << 16), u[4] | (u[5] << 16), u[6] | (u[7] << 16)};
+            }
+            *reinterpret_cast<mcraw_u32x4 *>(&s_t[r * MHC_LW + 8u * q]) = v;
         }
-        *reinterpret_cast<mcraw_u32x4 *>(&s_t[r * MHC_LW + 8u * q]) = v;
-    }
-    __syncthreads();
-    const uint32_t lx = threadIdx.x & 31u, ly = threadIdx.x >> 5;
-    const uint32_t x = static_cast<uint32_t>(x0) + 8u * lx;
-    if (x >= A.W)
-        return;
-    const uint32_t n = min(8u, A.W - x);
-    const RgbCol &col = A.col[A.percol ? f : 0u];
-    uint8_t *fout = A.out + static_cast<size_t>(f) * 3u * A.Ho * A.Wo * (PK == PK_F32 ? 4u : 2u);
-#pragma unroll 1
-    for (uint32_t pass = 0; pass < MHC_TH / 16u; pass++) {
-        const uint32_t rp = ly + 8u * pass, y = static_cast<uint32_t>(y0) + 2u * rp;
-        if (y >= A.H)
-            break;
-        // window: rows y-2 .. y+3, columns x-2 .. x+9, black subtracted: d[r][j] at image (y - 2 + r, x - 2 + j)
-        int d[6][12];
-#pragma unroll
-        for (int r = 0; r < 6; r++) {
-            const uint16_t *lrow = &s_t[(2u * rp + static_cast<uint32_t>(r)) * MHC_LW + 8u * lx];
-            const mcraw_u32x4 c0 = *reinterpret_cast<const mcraw_u32x4 *>(lrow);
-            const mcraw_u32x4 c1 = *reinterpret_cast<const mcraw_u32x4 *>(lrow + 8);
-            const uint32_t c2 = *reinterpret_cast<const uint32_t *>(lrow + 16);
-            const uint32_t w[6] = {c0[3], c1[0], c1[1], c1[2], c1[3], c2};
-#pragma unroll
-            for (int j = 0; j < 12; j++)
-                d[r][j] = static_cast<int>((w[j >> 1] >> (16u * (j & 1))) & 0xffffu) - A.black[(r & 1) * 2 + (j & 1)];
-        }
-#pragma unroll
-        for (int a = 0; a < 2; a++) {
-            int E[3][8];
-#pragma unroll
-            for (int b = 0; b < 8; b++) {
-                const int R = a + 2, J = b + 2;
-                const int C = d[R][J];
-                const int n1 = d[R - 1][J], s1 = d[R + 1][J], w1 = d[R][J - 1], e1 = d[R][J + 1];
-                const int v2 = d[R - 2][J] + d[R + 2][J], h2 = d[R][J - 2] + d[R][J + 2];
-                const int dg = (d[R - 1][J - 1] + d[R - 1][J + 1]) + (d[R + 1][J - 1] + d[R + 1][J + 1]);
-                const int role = (a * 2 + (b & 1)) ^ S;
-                const int nat = 16 * C;
-                if (role == 0 || role == 3) { // R or B site
-                    const int g = 8 * C + 4 * ((n1 + s1) + (w1 + e1)) - 2 * (v2 + h2);
-                    const int o = 12 * C + 4 * dg - 3 * (v2 + h2);
-                    E[0][b] = role == 0 ? nat : o;
-                    E[1][b] = g;
-                    E[2][b] = role == 0 ? o : nat;
-                } else { // G site: role 1 has R left / right, role 2 has B left / right
-                    const int hz = 10 * C + 8 * (w1 + e1) - 2 * h2 - 2 * dg + v2;
-                    const int vt = 10 * C + 8 * (n1 + s1) - 2 * v2 - 2 * dg + h2;
-                    E[0][b] = role == 1 ? hz : vt;
-                    E[1][b] = nat;
-                    E[2][b] = role == 1 ? vt : hz;
+        __syncthreads();
+        const uint32_t lx = threadIdx.x & 31u, ly = threadIdx.x >> 5;
+        const uint32_t x = static_cast<uint32_t>(x0) + 8u * lx;
+        if (x >= A.W)
+            continue;
+        const uint32_t n = min(8u, A.W - x);
+        const RgbCol &col = A.col[A.percol ? f : 0u];
+        uint8_t *fout = A.out + static_cast<size_t>(f) * 3u * A.Ho * A.Wo * out_es(PK);
+    #pragma unroll 1
+        for (uint32_t pass = 0; pass < MHC_TH / 16u; pass++) {
+            const uint32_t rp = ly + 8u * pass, y = static_cast<uint32_t>(y0) + 2u * rp;
+            if (y >= A.H)
+                break;
+            // window: rows y-2 .. y+3, columns x-2 .. x+9, black subtracted: d[r][j] at image (y - 2 + r, x - 2 + j)
+            int d[6][12];
+    #pragma unroll
+            for (int r = 0; r < 6; r++) {
+                const uint16_t *lrow = &s_t[(2u * rp + static_cast<uint32_t>(r)) * MHC_LW + 8u * lx];
+                const mcraw_u32x4 c0 = *reinterpret_cast<const mcraw_u32x4 *>(lrow);
+                const mcraw_u32x4 c1 = *reinterpret_cast<const mcraw_u32x4 *>(lrow + 8);
+                const uint32_t c2 = *reinterpret_cast<const uint32_t *>(lrow + 16);
+                const uint32_t w[6] = {c0[3], c1[0], c1[1], c1[2], c1[3], c2};
+    #pragma unroll
+                for (int j = 0; j < 12; j++)
+                    d[r][j] = static_cast<int>((w[j >> 1] >> (16u * (j & 1))) & 0xffffu) - A.black[(r & 1) * 2 + (j & 1)];
+            }
+    #pragma unroll
+            for (int a = 0; a < 2; a++) {
+                int E[3][8];
+    #pragma unroll
+                for (int b = 0; b < 8; b++) {
+                    const int R = a + 2, J = b + 2;
+                    const int C = d[R][J];
+                    const int n1 = d[R - 1][J], s1 = d[R + 1][J], w1 = d[R][J - 1], e1 = d[R][J + 1];
+                    const int v2 = d[R - 2][J] + d[R + 2][J], h2 = d[R][J - 2] + d[R][J + 2];
+                    const int dg = (d[R - 1][J - 1] + d[R - 1][J + 1]) + (d[R + 1][J - 1] + d[R + 1][J + 1]);
+                    const int role = (a * 2 + (b & 1)) ^ S;
+                    const int nat = 16 * C;
+                    if (role == 0 || role == 3) { // R or B site
+                        const int g = 8 * C + 4 * ((n1 + s1) + (w1 + e1)) - 2 * (v2 + h2);
+                        const int o = 12 * C + 4 * dg - 3 * (v2 + h2);
+                        E[0][b] = role == 0 ? nat : o;
+                        E[1][b] = g;
+                        E[2][b] = role == 0 ? o : nat;
+                    } else { // G site: role 1 has R left / right, role 2 has B left / right
+                        const int hz = 10 * C + 8 * (w1 + e1) - 2 * h2 - 2 * dg + v2;
+                        const int vt = 10 * C + 8 * (n1 + s1) - 2 * v2 - 2 * dg + h2;
+                        E[0][b] = role == 1 ? hz : vt;
+                        E[1][b] = nat;
+                        E[2][b] = role == 1 ? vt : hz;
+                    }
+                }
+                if (y + static_cast<uint32_t>(a) < A.H) {
+                    if constexpr (is_disp(PK))
+                        disp_store8<PK>(A, col, s_lut, fout, y + static_cast<uint32_t>(a), x, n, E);
+                    else
+                        rgb_store8<PK>(A, col, fout, y + static_cast<uint32_t>(a), x, n, E);
                 }
             }
-            if (y + static_cast<uint32_t>(a) < A.H)
-                rgb_store8<PK>(A, col, fout, y + static_cast<uint32_t>(a), x, n, E);
         }
-    }
+    } while (DISP && (t += gridDim.x) < A.units * A.nf);
 }
 
 // ---- BIN2 -------------------------------------------------------------------------------------------------------------
 //
 // Lane = 8 consecutive output columns of one output row: 16 input columns of two input rows (two 16-byte loads per row
 // where the rows allow it).
+// Float kinds: item blockIdx.x * RGB_T + lane of frame blockIdx.y.  Display kinds: persistent, as krgb_mhc.
 template <int PK, int S>
 __global__ void __launch_bounds__(RGB_T) krgb_bin2(const RgbArgs A)
 {
-    const uint32_t f = blockIdx.y, item = blockIdx.x * RGB_T + threadIdx.x;
-    const uint32_t yo = item / A.tilesX, xo = 8u * (item % A.tilesX);
-    if (yo >= A.Ho)
-        return;
-    const uint32_t n = min(8u, A.Wo - xo);
-    const uint16_t *row0 = A.in + static_cast<size_t>(f) * A.fstride + static_cast<size_t>(2u * yo) * A.pitch + 2u * xo;
-    const uint16_t *row1 = row0 + A.pitch;
-    uint32_t u[2][8]; // (even column | odd column << 16) of quad i, rows 0 and 1
-    if (A.invec && n == 8u) {
-        const mcraw_u32x4 a0 = gptr<const mcraw_u32x4>(row0)[0], a1 = gptr<const mcraw_u32x4>(row0)[1];
-        const mcraw_u32x4 b0 = gptr<const mcraw_u32x4>(row1)[0], b1 = gptr<const mcraw_u32x4>(row1)[1];
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            u[0][i] = a0[i];
-            u[0][4 + i] = a1[i];
-            u[1][i] = b0[i];
-            u[1][4 + i] = b1[i];
-        }
-    } else {
-#pragma unroll
-        for (uint32_t i = 0; i < 8u; i++) {
-            const uint32_t k = i < n ? 2u * i : 0u;
-            u[0][i] = gptr<const uint16_t>(row0)[k] | (static_cast<uint32_t>(gptr<const uint16_t>(row0)[k + 1]) << 16);
-            u[1][i] = gptr<const uint16_t>(row1)[k] | (static_cast<uint32_t>(gptr<const uint16_t>(row1)[k + 1]) << 16);
-        }
+    constexpr bool DISP = is_disp(PK);
+    __shared__ __attribute__((aligned(16))) uint16_t s_lut[DISP ? DISP_LDS_MAX : 8u];
+    uint32_t t = blockIdx.x;
+    if constexpr (DISP) {
+        stage_lut(A, s_lut);
+        __syncthreads();
     }
-    int E[3][8];
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        int q[4];
-#pragma unroll
-        for (int p = 0; p < 4; p++)
-            q[p] = static_cast<int>((u[p >> 1][i] >> (16u * (p & 1))) & 0xffffu) - A.black[p];
-        E[0][i] = 2 * q[0 ^ S];
-        E[1][i] = q[1 ^ S] + q[2 ^ S];
-        E[2][i] = 2 * q[3 ^ S];
-    }
-    uint8_t *fout = A.out + static_cast<size_t>(f) * 3u * A.Ho * A.Wo * (PK == PK_F32 ? 4u : 2u);
-    rgb_store8<PK>(A, A.col[A.percol ? f : 0u], fout, yo, xo, n, E);
+    do {
+        const uint32_t f = DISP ? t / A.units : blockIdx.y, item = (DISP ? t % A.units : blockIdx.x) * RGB_T + threadIdx.x;
+        const uint32_t yo = item / A.tilesX, xo = 8u * (item % A.tilesX);
+        if (yo >= A.Ho)
+            continue;
+        const uint32_t n = min(8u, A.Wo - xo);
+        const uint16_t *row0 = A.in + static_cast<size_t>(f) * A.fstride + static_cast<size_t>(2u * yo) * A.pitch + 2u * xo;
+        const uint16_t *row1 = row0 + A.pitch;
+        uint32_t u[2][8]; // (even column | odd column << 16) of quad i, rows 0 and 1
+        if (A.invec && n == 8u) {
+            const mcraw_u32x4 a0 = gptr<const mcraw_u32x4>(row0)[0], a1 = gptr<const mcraw_u32x4>(row0)[1];
+            const mcraw_u32x4 b0 = gptr<const mcraw_u32x4>(row1)[0], b1 = gptr<const mcraw_u32x4>(row1)[1];
+    #pragma unroll
+            for (int i = 0; i < 4; i++) {
+                u[0][i] = a0[i];
+                u[0][4 + i] = a1[i];
+                u[1][i] = b0[i];
+                u[1][4 + i] = b1[i];
+            }
+        } else {
+    #pragma unroll
+            for (uint32_t i = 0; i < 8u; i++) {
+                const uint32_t k = i < n ? 2u * i : 0u;
+                u[0][i] = gptr<const uint16_t>(row0)[k] | (static_cast<uint32_t>(gptr<const uint16_t>(row0)[k + 1]) << 16);
+                u[1][i] = gptr<const uint16_t>(row1)[k] | (static_cast<uint32_t>(gptr<const uint16_t>(row1)[k + 1]) << 16);
+            }
+        }
+        int E[3][8];
+    #pragma unroll
+        for (int i = 0; i < 8; i++) {
+            int q[4];
+    #pragma unroll
+            for (int p = 0; p < 4; p++)
+                q[p] = static_cast<int>((u[p >> 1][i] >> (16u * (p & 1))) & 0xffffu) - A.black[p];
+            E[0][i] = 2 * q[0 ^ S];
+            E[1][i] = q[1 ^ S] + q[2 ^ S];
+            E[2][i] = 2 * q[3 ^ S];
+        }
+        uint8_t *fout = A.out + static_cast<size_t>(f) * 3u * A.Ho * A.Wo * out_es(PK);
+        if constexpr (is_disp(PK))
+            disp_store8<PK>(A, A.col[A.percol ? f : 0u], s_lut, fout, yo, xo, n, E);
+        else
+            rgb_store8<PK>(A, A.col[A.percol ? f : 0u], fout, yo, xo, n, E);
+    } while (DISP && (t += gridDim.x) < A.units * A.nf);
 }
 
 typedef void (*RgbKernel)(const RgbArgs);
@@ -272,9 +458,9 @@ static RgbKernel pick_kernel(uint32_t algo, int s)
     return algo == MCRAW_RGB_MHC ? mhc[s] : bin2[s];
 }
 
-static int reject(const char *why)
+static int reject(const char *fn, const char *why)
 {
-    g_err = std::string("mcraw_demosaic_batch: ") + why;
+    g_err = std::string(fn) + ": " + why;
     return -1;
 }
 
@@ -286,50 +472,80 @@ static bool finite_all(const float *v, int n)
     return true;
 }
 
-} // namespace mcraw
+// Workgroups of a persistent display grid: what the device holds at once (compute units x resident workgroups of the
+// instance), found once per (device, kernel).
+static uint32_t resident_groups(int device, RgbKernel k)
+{
+    static std::mutex mu;
+    static std::vector<std::pair<std::pair<int, RgbKernel>, uint32_t>> seen;
+    std::lock_guard<std::mutex> lk(mu);
+    for (const auto &e : seen)
+        if (e.first.first == device && e.first.second == k)
+            return e.second;
+    int cus = 0, per = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0)
+        cus = 256;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, reinterpret_cast<const void *>(k), RGB_T, 0) != hipSuccess || per <= 0)
+        per = 2;
+    const uint32_t g = static_cast<uint32_t>(cus) * static_cast<uint32_t>(per);
+    seen.push_back({{device, k}, g});
+    return g;
+}
 
-using namespace mcraw;
-
-extern "C" {
-
-int mcraw_demosaic_batch(mcraw_ctx *c, const mcraw_rgb *p, const mcraw_rgb_color *colors, int ncolors, const uint16_t *in,
-                         size_t in_pitch, size_t in_frame_stride, int width, int height, int n, void *out, size_t out_bytes,
-                         void *stream)
+// Both entry points: the checks of mcraw_demosaic_batch, those of the display stage when `d` is given, then the launches.
+static int demosaic_launch(const char *fn, mcraw_ctx *c, const mcraw_rgb *p, const mcraw_display *d,
+                           const mcraw_rgb_color *colors, int ncolors, const uint16_t *in, size_t in_pitch,
+                           size_t in_frame_stride, int width, int height, int n, void *out, size_t out_bytes, void *stream)
 {
     if (!c || !p || n < 0)
-        return reject("bad arguments");
+        return reject(fn, "bad arguments");
     if (n == 0)
         return 0;
     if (width < 4 || height < 4 || (width & 1) || (height & 1) || width > 65536 || height > 65536)
-        return reject("width and height must be even, 4 .. 65536");
+        return reject(fn, "width and height must be even, 4 .. 65536");
     if (in_pitch < static_cast<size_t>(width))
-        return reject("in_pitch below width");
+        return reject(fn, "in_pitch below width");
     if (n > 1 && in_frame_stride < (static_cast<size_t>(height) - 1u) * in_pitch + static_cast<size_t>(width))
-        return reject("in_frame_stride too small for the frames not to overlap");
+        return reject(fn, "in_frame_stride too small for the frames not to overlap");
     if (p->algo != MCRAW_RGB_MHC && p->algo != MCRAW_RGB_BIN2)
-        return reject("unknown algo");
-    if (p->dtype != MCRAW_FLOAT_F32 && p->dtype != MCRAW_FLOAT_F16 && p->dtype != MCRAW_FLOAT_BF16)
-        return reject("unknown dtype");
+        return reject(fn, "unknown algo");
+    if (d) {
+        if (p->dtype != 0u || p->flags != 0u)
+            return reject(fn, "p->dtype and p->flags must be 0 (the display stage decides the output)");
+        if (d->dtype != MCRAW_DISP_U8 && d->dtype != MCRAW_DISP_U16)
+            return reject(fn, "unknown display dtype");
+        if (d->layout != MCRAW_DISP_CHW && d->layout != MCRAW_DISP_HWC)
+            return reject(fn, "unknown display layout");
+        if (d->reserved != 0u)
+            return reject(fn, "reserved must be 0");
+        if (d->lut_log2 < 8u || d->lut_log2 > 16u)
+            return reject(fn, "lut_log2 must be 8 .. 16");
+        if (!d->lut || (reinterpret_cast<uintptr_t>(d->lut) & 15u))
+            return reject(fn, "lut missing or not 16-byte aligned");
+    } else {
+        if (p->dtype != MCRAW_FLOAT_F32 && p->dtype != MCRAW_FLOAT_F16 && p->dtype != MCRAW_FLOAT_BF16)
+            return reject(fn, "unknown dtype");
+    }
     if (p->cfa > MCRAW_CFA_GBRG)
-        return reject("unknown cfa");
+        return reject(fn, "unknown cfa");
     if (p->flags & ~MCRAW_FLOAT_CLIP)
-        return reject("unknown flag");
+        return reject(fn, "unknown flag");
     const float bsum = static_cast<float>(static_cast<int>(p->black[0]) + p->black[1] + p->black[2] + p->black[3]);
     if (!std::isfinite(p->white) || !(p->white > 0.25f * bsum))
-        return reject("white must be finite and above the mean black level");
+        return reject(fn, "white must be finite and above the mean black level");
     if (!colors || (ncolors != 1 && ncolors != n))
-        return reject("ncolors must be 1 or n");
+        return reject(fn, "ncolors must be 1 or n");
     for (int i = 0; i < ncolors; i++)
         if (!finite_all(colors[i].gain, 3) || !finite_all(colors[i].m, 9))
-            return reject("non-finite gain or matrix entry");
+            return reject(fn, "non-finite gain or matrix entry");
     const bool mhc = p->algo == MCRAW_RGB_MHC;
-    const size_t es = p->dtype == MCRAW_FLOAT_F32 ? 4u : 2u;
+    const size_t es = d ? (d->dtype == MCRAW_DISP_U8 ? 1u : 2u) : p->dtype == MCRAW_FLOAT_F32 ? 4u : 2u;
     const size_t Wo = mhc ? static_cast<size_t>(width) : static_cast<size_t>(width) / 2u;
     const size_t Ho = mhc ? static_cast<size_t>(height) : static_cast<size_t>(height) / 2u;
     if (out_bytes / es / 3u / Ho / Wo < static_cast<size_t>(n))
-        return reject("out_bytes below n * 3 * Ho * Wo * element size");
+        return reject(fn, "out_bytes below n * 3 * Ho * Wo * element size");
     if (!in || !out || (reinterpret_cast<uintptr_t>(in) & 1u) || (reinterpret_cast<uintptr_t>(out) & (es - 1u)))
-        return reject("in / out missing or not aligned to their element size");
+        return reject(fn, "in / out missing or not aligned to their element size");
 
     std::lock_guard<std::mutex> lk(c->mu);
     HIP_TRY(hipSetDevice(c->device));
@@ -345,7 +561,8 @@ int mcraw_demosaic_batch(mcraw_ctx *c, const mcraw_rgb *p, const mcraw_rgb_color
     }
     static const int shift_of[4] = {0, 3, 1, 2}; // MCRAW_CFA_* -> role shift: RGGB 0, BGGR 3, GRBG 1, GBRG 2
     const int s = shift_of[p->cfa];
-    RgbKernel k = p->dtype == MCRAW_FLOAT_F32 ? pick_kernel<PK_F32>(p->algo, s)
+    RgbKernel k = d ? (d->dtype == MCRAW_DISP_U8 ? pick_kernel<PK_DISP8>(p->algo, s) : pick_kernel<PK_DISP16>(p->algo, s))
+                  : p->dtype == MCRAW_FLOAT_F32 ? pick_kernel<PK_F32>(p->algo, s)
                   : p->dtype == MCRAW_FLOAT_F16 ? pick_kernel<PK_F16>(p->algo, s)
                                                 : pick_kernel<PK_BF16>(p->algo, s);
     RgbArgs A{};
@@ -358,6 +575,12 @@ int mcraw_demosaic_batch(mcraw_ctx *c, const mcraw_rgb *p, const mcraw_rgb_color
     A.invec = (reinterpret_cast<uintptr_t>(in) & 15u) == 0u && in_pitch % 8u == 0u && (n == 1 || in_frame_stride % 8u == 0u);
     A.clip = (p->flags & MCRAW_FLOAT_CLIP) ? 1u : 0u;
     A.percol = ncolors > 1 ? 1u : 0u;
+    if (d) {
+        A.lut = d->lut;
+        A.lutn = 1u << d->lut_log2;
+        A.lutg = A.lutn > DISP_LDS_MAX ? 1u : 0u;
+        A.hwc = d->layout == MCRAW_DISP_HWC ? 1u : 0u;
+    }
     for (int i = 0; i < 4; i++)
         A.black[i] = p->black[i];
     uint32_t blocks;
@@ -368,6 +591,8 @@ int mcraw_demosaic_batch(mcraw_ctx *c, const mcraw_rgb *p, const mcraw_rgb_color
         A.tilesX = static_cast<uint32_t>((Wo + 7u) / 8u);
         blocks = static_cast<uint32_t>((static_cast<size_t>(A.tilesX) * Ho + RGB_T - 1u) / RGB_T);
     }
+    A.units = blocks;
+    const uint32_t resident = d ? resident_groups(c->device, k) : 0u;
     const int kid = mhc ? MCRAW_KRGB_MHC : MCRAW_KRGB_BIN2;
     const int piece = A.percol ? RGB_MAXF : 65535;
     const size_t out_frame = 3u * Ho * Wo * es;
@@ -375,13 +600,41 @@ int mcraw_demosaic_batch(mcraw_ctx *c, const mcraw_rgb *p, const mcraw_rgb_color
         const int nf = std::min(piece, n - f0);
         A.in = in + static_cast<size_t>(f0) * in_frame_stride;
         A.out = static_cast<uint8_t *>(out) + static_cast<size_t>(f0) * out_frame;
+        A.nf = static_cast<uint32_t>(nf);
         for (int i = 0; i < (A.percol ? nf : 1); i++)
             A.col[i] = cols[static_cast<size_t>(A.percol ? f0 + i : 0)];
+        // display kinds: a persistent grid of at most what the device holds at once, over blocks x nf units of work
+        const dim3 grid = d ? dim3(static_cast<uint32_t>(std::min<uint64_t>(static_cast<uint64_t>(blocks) * nf, resident)))
+                            : dim3(blocks, static_cast<uint32_t>(nf));
         KTimer kt(c, kid, st);
-        hipLaunchKernelGGL(k, dim3(blocks, static_cast<uint32_t>(nf)), dim3(RGB_T), 0, st, A);
+        hipLaunchKernelGGL(k, grid, dim3(RGB_T), 0, st, A);
         HIP_TRY(hipGetLastError());
     }
     return 0;
+}
+
+} // namespace mcraw
+
+using namespace mcraw;
+
+extern "C" {
+
+int mcraw_demosaic_batch(mcraw_ctx *c, const mcraw_rgb *p, const mcraw_rgb_color *colors, int ncolors, const uint16_t *in,
+                         size_t in_pitch, size_t in_frame_stride, int width, int height, int n, void *out, size_t out_bytes,
+                         void *stream)
+{
+    return demosaic_launch("mcraw_demosaic_batch", c, p, nullptr, colors, ncolors, in, in_pitch, in_frame_stride, width, height,
+                           n, out, out_bytes, stream);
+}
+
+int mcraw_demosaic_display_batch(mcraw_ctx *c, const mcraw_rgb *p, const mcraw_display *d, const mcraw_rgb_color *colors,
+                                 int ncolors, const uint16_t *in, size_t in_pitch, size_t in_frame_stride, int width, int height,
+                                 int n, void *out, size_t out_bytes, void *stream)
+{
+    if (!d)
+        return reject("mcraw_demosaic_display_batch", "bad arguments");
+    return demosaic_launch("mcraw_demosaic_display_batch", c, p, d, colors, ncolors, in, in_pitch, in_frame_stride, width,
+                           height, n, out, out_bytes, stream);
 }
 
 } // extern "C"
