@@ -212,21 +212,7 @@ void mcraw_ctx_destroy(mcraw_ctx *c)
     for (Slot &s : c->dslots)
         release(s);
     release(c->rslot);
-    for (KStat &k : c->kstat)
-        for (auto &p : k.pending) {
-            (void)hipEventDestroy(p.first);
-            (void)hipEventDestroy(p.second);
-        }
-    for (auto &t : c->tunes)
-        for (auto &p : t.pending) {
-            (void)hipEventDestroy(p.a);
-            (void)hipEventDestroy(p.b);
-        }
-    for (auto &t : c->side_tunes)
-        for (auto &p : t.pending) {
-            (void)hipEventDestroy(p.a);
-            (void)hipEventDestroy(p.b);
-        }
+    tune_release(c);
     for (hipEvent_t e : c->event_pool)
         (void)hipEventDestroy(e);
     if (c->stream)
@@ -278,27 +264,9 @@ int mcraw_decode_batch_async(mcraw_ctx *c, const mcraw_frame *frames, int nframe
     t->composite = true;
     t->got_written.assign(static_cast<size_t>(nframes), 0);
     t->got_status.assign(static_cast<size_t>(nframes), 0);
-    constexpr int TRIAL_TICKETS = 12;
-    way_from_env(c);
-    const size_t total = host_bytes(frames, nframes, c->post.mode);
-    int way;
-    if (total > PIECE_BYTES) { // a large batch as a ticket: compared like the synchronous ones, its time runs until it is waited for
-        way = big_way(c, total, &t->big_trial);
-        t->trial_bytes = total;
-        t->t_queued = std::chrono::steady_clock::now();
-    } else if (c->send_home_tickets >= 0) {
-        way = c->send_home_tickets;
-    } else if (nframes > 0 && alone_on_device(c) && c->tt.queued < TRIAL_TICKETS) {
-        way = t->trial_way = c->tt.way; // (undecided: this ticket belongs to the row under way)
-        t->trial_bytes = total;
-        c->tt.queued++;
-    } else {
-        way = 0;
-    }
-    t->way = way;
+    const int way = ticket_way(c, t, nframes, host_bytes(frames, nframes, c->post.mode));
     if (int rc = deal_host(c, frames, nframes, t->got_written.data(), t->got_status.data(), t->pieces, t->piece_first, false, way)) {
-        if (t->trial_way >= 0 && c->tt.queued > 0)
-            c->tt.queued--; // (a ticket that never flew lands nowhere: its place in the trial row is free again)
+        ticket_never_flew(c, t);
         delete t;
         return rc;
     }
@@ -320,28 +288,7 @@ int mcraw_ticket_wait(mcraw_ticket *t, size_t *written, int32_t *status)
             if (rc == 0)
                 rc = r;
         }
-        if (t->big_trial && rc == 0)
-            big_way_result(c, t->way, t->trial_bytes, std::chrono::duration<double>(std::chrono::steady_clock::now() - t->t_queued).count());
-        if (t->trial_way >= 0 && c->send_home_tickets < 0 && t->trial_way == c->tt.way) { // a ticket of the trial row under way has landed
-            constexpr int TRIAL_TICKETS = 12;
-            mcraw_ctx::TicketTrial &tt = c->tt;
-            const auto now = std::chrono::steady_clock::now();
-            if (tt.landed++ == 0)
-                tt.t_first = now; // (the row's clock starts with its first landing; that ticket's bytes are not counted)
-            else
-                tt.bytes += t->trial_bytes;
-            if (tt.landed == TRIAL_TICKETS) {
-                tt.rate[tt.way] = tt.bytes / std::max(1e-9, std::chrono::duration<double>(now - tt.t_first).count());
-                if (tt.way == 0) {
-                    tt = mcraw_ctx::TicketTrial{1, 0, 0, 0, now, {tt.rate[0], 0.0}};
-                } else {
-                    c->send_home_tickets = tt.rate[1] > tt.rate[0] * 1.03 ? 1 : 0;
-                    if (c->env_trace)
-                        std::fprintf(stderr, "[mcraw] host-memory pipeline (tickets): status words fetched %.1f GB/s, sent home %.1f GB/s: %s from here on\n",
-                                     tt.rate[0] / 1e9, tt.rate[1] / 1e9, c->send_home_tickets ? "sent" : "fetched");
-                }
-            }
-        }
+        ticket_landed(c, t, rc);
         const size_t n = t->got_status.size();
         for (size_t i = 0; i < n; i++) {
             if (written)
@@ -590,7 +537,8 @@ int mcraw_ctx_xcd_runs(mcraw_ctx *c)
     if (!c)
         return -2;
     std::lock_guard<std::mutex> lk(c->mu);
-    return c->tune_last >= 0 && c->tunes[c->tune_last].decided >= 0 ? static_cast<int>(TUNE_CHUNKS[c->tunes[c->tune_last].decided]) : -1;
+    const int *cd = tune_decided(c->xcd);
+    return cd ? cd[0] : -1;
 }
 
 int mcraw_ctx_side_parts(mcraw_ctx *c)
@@ -598,10 +546,8 @@ int mcraw_ctx_side_parts(mcraw_ctx *c)
     if (!c)
         return -2;
     std::lock_guard<std::mutex> lk(c->mu);
-    if (c->side_last < 0 || c->side_tunes[c->side_last].decided < 0)
-        return -1;
-    const mcraw_ctx::SideTune &t = c->side_tunes[c->side_last];
-    return t.cand[t.decided][0] * 16 + t.cand[t.decided][1];
+    const int *cd = tune_decided(c->side);
+    return cd ? cd[0] * 16 + cd[1] : -1;
 }
 
 int mcraw_ctx_host_way(mcraw_ctx *c)
@@ -609,7 +555,7 @@ int mcraw_ctx_host_way(mcraw_ctx *c)
     if (!c)
         return -1;
     std::lock_guard<std::mutex> lk(c->mu);
-    return c->send_home;
+    return host_way(c, false);
 }
 
 int mcraw_ctx_profile_every(mcraw_ctx *c, int n)

@@ -2,7 +2,8 @@
 // the host-memory pipeline, and the functions the units call in each other.
 //   mcraw_abi.hip      the extern "C" entry points, context life cycle
 //   mcraw_submit.hip   one batch: plan (geometry, workspace carving, launch order), table upload, kernel launches
-//   mcraw_tune.hip     the context's run-time measurements (XCD mapping of k7_tiles, parts per side stream)
+//   mcraw_tune.hip     the context's run-time measurements: the races of single launches (XCD mapping of k7_tiles, parts per side
+//                      stream; their rule, free of HIP: mcraw_race.h) and the host-memory pipeline's trials (status words fetched or sent)
 //   mcraw_device.hip   batches whose buffers are in HBM: slots, statuses, second plans
 //   mcraw_hostmem.hip  batches whose buffers are in host memory: the three-lane pipeline, tickets
 // Replaces the per-frame dispatch of lib/Decoder.cpp:216-234 with batched submits.  There is no CPU decode fallback in any of them.
@@ -23,6 +24,7 @@
 
 #include "../../include/mcraw_hip.h"
 #include "mcraw_plan.h"
+#include "mcraw_race.h"
 
 
 namespace mcraw {
@@ -121,6 +123,43 @@ struct KStat {
     int launches = 0;
 };
 
+// A launch parameter chosen by measurement (mcraw_tune.hip; the rule: mcraw_race.h).  The choice is made PER GEOMETRY, not per
+// buffer: a few geometries at a time have an entry with a race of their own and the event pairs of its timed launches under way.
+struct Tuner {
+    struct Entry {
+        int key_n = 0; // what the choice was made for: frames, groups, row format (another kernel instance, other rows)
+        uint32_t key_R = 0, key_mode = 0;
+        int cand[Race::MAXC][2] = {{1, 1}}; // what the candidates stand for: an XCD chunk; parts per bits / refs stream
+        Race race;
+        struct Pending { // a timed launch under way
+            hipEvent_t a, b;
+            int cand;
+        };
+        std::vector<Pending> pending;
+        unsigned long long used = 0; // (least recently used entry is replaced)
+        explicit Entry(float margin) : race(margin) {}
+    } entries[4];
+    unsigned long long clock = 0;
+    Entry *last = nullptr; // of the last batch that asked (mcraw_ctx_xcd_runs, mcraw_ctx_side_parts)
+    explicit Tuner(float m) : entries{Entry(m), Entry(m), Entry(m), Entry(m)} {}
+};
+
+// Host-memory pipeline: do the status words go home behind their kernels (1) or are they fetched when the batch is waited for
+// (0)?  Decided by measurement (mcraw_tune.hip owns every field), or by MCRAW_SHORT_WAY=0|1; until then: fetched.
+struct HostWay {
+    int send_home = -1;         // ... a large batch in one synchronous call
+    int send_home_tickets = -1; // ... a stream of tickets
+    double trial_rate[2] = {0.0, 0.0}; // bytes per second of the two trial batches (fetched, sent)
+    int big_seen = 0;                  // large batches so far (the first one is not compared)
+    int sent_trials = 0;               // ... that sent (the first of them is not compared either)
+    struct TicketTrial { // the row of short tickets under way (ticket_way, ticket_landed)
+        int way = 0, queued = 0, landed = 0;
+        size_t bytes = 0;
+        std::chrono::steady_clock::time_point t_first;
+        double rate[2] = {0.0, 0.0};
+    } tt;
+};
+
 
 } // namespace mcraw
 
@@ -138,7 +177,7 @@ struct mcraw_ticket {
     bool small = false; // a few sub-batches only: scheduled the short way (host_submit)
     bool send = false;  // ... and its status words go home behind their kernels (send_status)
     int want_send = -1; // (deal_host: what this piece is to do; -1: what the context has decided)
-    int trial_way = -1; // a ticket of the context's trial rows (mcraw_decode_batch_async): which row
+    int trial_way = -1; // a ticket of the context's trial rows (ticket_way): which row
     size_t trial_bytes = 0;
     bool big_trial = false; // a large batch whose way is being compared (big_way)
     int way = 0;
@@ -159,21 +198,7 @@ extern std::atomic<int> g_ctx_on_device[64];
 struct mcraw_ctx {
     uint64_t part_seq = 0;
     bool counted = false; // in g_ctx_on_device
-    // Host-memory pipeline: do the status words go home behind their kernels (1) or are they fetched when the batch is waited for
-    // (0)?  Decided by measurement on the first large batch (deal_host), or by MCRAW_SHORT_WAY=0|1; until then: fetched.
-    int send_home = -1;         // ... a large batch in one synchronous call
-    int send_home_tickets = -1; // ... a stream of tickets
-    double trial_rate[2] = {0.0, 0.0}; // bytes per second of the two trial batches (fetched, sent)
-    int big_seen = 0;                  // large batches so far (the first one is not compared)
-    int sent_trials = 0;               // ... that sent (the first of them is not compared either)
-    // ... and for a caller that streams short tickets instead (the facade's chunks): TRIAL_TICKETS in a row fetch, the next
-    // TRIAL_TICKETS send, the rate between the first and the last landing of each row is compared
-    struct TicketTrial {
-        int way = 0, queued = 0, landed = 0;
-        size_t bytes = 0;
-        std::chrono::steady_clock::time_point t_first;
-        double rate[2] = {0.0, 0.0};
-    } tt;
+    HostWay way;
 #ifdef MCRAW_TIMELINE
     hipEvent_t tl0 = nullptr; // the timeline's zero: recorded on the upload stream in front of the first sub-batch
     std::chrono::steady_clock::time_point tl_host0;
@@ -199,49 +224,13 @@ struct mcraw_ctx {
     Post post{0, 0, 0};   // fused post-decode stage of the batches to come (mcraw_ctx_set_post)
     KStat kstat[MCRAW_K_COUNT];
     std::vector<hipEvent_t> event_pool;
-    // How k7_tiles' workgroups are dealt to the XCDs (Work7::xcd_chunk), chosen by measurement for large resident batches:
-    // which of the candidates is faster depends on where the caller's buffers lie in physical memory (see submit()).  The
-    // choice is made PER GEOMETRY (frames, groups), not per buffer: the first launches of a geometry try each candidate twice
-    // between events and the faster one stays; afterwards one launch in 64 is timed -- the chosen candidate and the other one
-    // in turn --, and the choice moves when the other one has become the faster (a caller whose buffers change is never
-    // left measuring, and one whose buffers moved to a place where the other mapping wins gets there).
-    struct Tune {
-        static constexpr int NC = 2;
-        int key_n = 0;       // what the choice was made for: frames, groups, row format (another kernel instance, other rows)
-        uint32_t key_R = 0, key_mode = 0;
-        int issued[NC] = {0, 0}, done[NC] = {0, 0};
-        float best[NC] = {0.f, 0.f}; // first samples: the minimum; afterwards a moving average
-        int decided = -1;
-        unsigned long long launches = 0; // tunable launches since the decision
-        struct Pending {
-            hipEvent_t a, b;
-            int cand;
-        };
-        std::vector<Pending> pending;
-        unsigned long long used = 0; // (least recently used entry is replaced)
-    } tunes[4]; // a few geometries at a time
+    // How k7_tiles' workgroups are dealt to the XCDs (Work7::xcd_chunk), chosen by measurement for large resident batches: which
+    // of the candidates is faster depends on where the caller's buffers lie in physical memory (see submit()).
+    Tuner xcd{0.99f};
     // How many workgroups ("parts") resolve a long side stream of a small resident batch (Work7::nsplit[bits, refs]): which of
     // the two streams is the slow one is a matter of content -- the bits stream of coded frames (short runs of equally long
-    // records), the refs stream of noise --, and the chip holds 512 workgroups of k7_side at a time.  Chosen like the XCD mapping:
-    // the first launches of a geometry try each candidate twice between events, the fastest stays, one launch in 64 re-checks.
-    struct SideTune {
-        static constexpr int MAXC = 8;
-        int key_n = 0;
-        uint32_t key_R = 0;
-        int nc = 0, cand[MAXC][2] = {{1, 1}};
-        int issued[MAXC] = {0}, done[MAXC] = {0};
-        float best[MAXC] = {0.f};
-        int decided = -1;
-        unsigned long long launches = 0, used = 0;
-        struct Pending {
-            hipEvent_t a, b;
-            int cand;
-        };
-        std::vector<Pending> pending;
-    } side_tunes[4];
-    int side_last = -1;
-    unsigned long long tune_clock = 0;
-    int tune_last = -1; // entry of the last tunable batch (mcraw_ctx_xcd_runs)
+    // records), the refs stream of noise --, and the chip holds 512 workgroups of k7_side at a time.
+    Tuner side{0.97f};
     // last device-memory batch, for mcraw_ctx_synchronize
     int last_slot = -1;
     int last_n = 0;
@@ -261,6 +250,18 @@ namespace mcraw {
 
 int ensure(Buf &b, size_t bytes, bool pinned);
 hipEvent_t get_event(mcraw_ctx *c);
+
+// Brackets one launch that a race wants timed (cand >= 0: tune_xcd / tune_side said so; else nothing happens) with events on the
+// launch stream and files them with the race's entry.  A batch that fails before its launch loses the sample and says so.
+struct TuneTimer {
+    mcraw_ctx *c = nullptr;
+    Tuner::Entry *e = nullptr;
+    int cand = -1;
+    hipStream_t st = nullptr;
+    hipEvent_t a = nullptr, b = nullptr;
+    void begin(hipStream_t st_), end();
+    ~TuneTimer() { end(); }
+};
 
 struct KTimer { // brackets one launch with events on the launch stream
     mcraw_ctx *c;
@@ -313,11 +314,19 @@ struct Layout { // byte offsets inside the slot arena / upload image
     size_t total = 0;
 };
 
-constexpr uint32_t TUNE_CHUNKS[mcraw_ctx::Tune::NC] = {128u, 0u};
-
 // ---- mcraw_tune.hip
-int tune_pick(mcraw_ctx *c, int n7, uint32_t R, uint32_t mode);
-int side_pick(mcraw_ctx *c, int n7, uint32_t R);
+// What the next launch of this geometry runs with (k7_tiles' XCD chunk; k7_side's parts per stream); `tm` is to bracket that launch.
+uint32_t tune_xcd(mcraw_ctx *c, int n7, uint32_t R, uint32_t mode, TuneTimer &tm);
+void tune_side(mcraw_ctx *c, int n7, uint32_t R, int nsplit[2], TuneTimer &tm);
+const int *tune_decided(const Tuner &t); // the candidate the tuner's last geometry has decided for (Tuner::Entry::cand), or null
+void tune_release(mcraw_ctx *c);         // a context that goes away: every event of a measurement under way back into event_pool
+void way_from_env(mcraw_ctx *c);
+int host_way(const mcraw_ctx *c, bool tickets); // what is decided for large batches / streams of tickets (-1: nothing yet)
+int big_way(mcraw_ctx *c, size_t total, bool *trial);
+void big_way_result(mcraw_ctx *c, int way, size_t total, double seconds);
+int ticket_way(mcraw_ctx *c, mcraw_ticket *t, int nframes, size_t total); // the way of a new ticket (noted in it, with its trial row)
+void ticket_never_flew(mcraw_ctx *c, const mcraw_ticket *t);
+void ticket_landed(mcraw_ctx *c, const mcraw_ticket *t, int rc);
 // ---- mcraw_submit.hip
 int submit(mcraw_ctx *c, Slot &s, const mcraw_frame *frames, int n, const std::vector<Geom7> *geom_override,
            const uint8_t *const *dev_in, uint16_t *const *dev_out, hipStream_t st, size_t *status_off);
@@ -367,9 +376,6 @@ inline size_t frame_out_full(const mcraw_frame &f, uint32_t mode)
     const uint32_t w = static_cast<uint32_t>(f.width), h = static_cast<uint32_t>(f.height);
     return std::max(static_cast<size_t>(w) * h * 2, post_out_bytes(w, h, h, mode));
 }
-void way_from_env(mcraw_ctx *c);
-int big_way(mcraw_ctx *c, size_t total, bool *trial);
-void big_way_result(mcraw_ctx *c, int way, size_t total, double seconds);
 int deal_host(mcraw_ctx *c, const mcraw_frame *frames, int n, size_t *written, int32_t *status_out,
               std::vector<std::unique_ptr<mcraw_ticket>> &pieces, std::vector<int> &piece_first, bool finish, int way);
 int decode_host(mcraw_ctx *c, const mcraw_frame *frames, int n, size_t *written, int32_t *status_out);

@@ -259,8 +259,8 @@ int host_submit(mcraw_ticket *t)
     // way -- statuses fetched when the batch is waited for, which queues that fetch behind everything submitted since and so
     // lets the ring run empty now and then -- keeps 2 700-2 900.  So: batches of up to SHORT_PARTS sub-batches are scheduled the
     // short way (queued only when at most ONE other batch still has downloads under way; larger batches are dealt out as such
-    // by deal_host), and whether their status words are sent home is the caller's word (`want_send`: big_way / the ticket rows
-    // of mcraw_decode_batch_async measure what is faster in this process).
+    // by deal_host), and whether their status words are sent home is the caller's word (`want_send`: big_way / ticket_way
+    // measure what is faster in this process).
     constexpr int SHORT_PARTS = 6;
     {
         int parts = 0;
@@ -380,77 +380,12 @@ int land_piece(std::vector<std::unique_ptr<mcraw_ticket>> &pieces, std::vector<i
     return r;
 }
 
-// Status words home behind their kernels (1), or fetched at the wait (0)?  In a process whose first GPU work was this context
-// sending is 10 % faster for a large batch (2 960 against 2 680 UHD frames/s); behind one torch operation -- HIP hands a process four
-// hardware queues per stream priority, and which of the context's streams share one depends on what existed before -- the small
-// kernel that writes home makes sub-batch k + 1's upload wait for sub-batch k's download there (1 600 against 2 570).  Neither a
-// probe on dummy buffers nor the first pieces of a batch show that (it sets in later), so whole batches are compared: of the
-// batches of ten pieces or more the first one fetches and only warms the slots up, the second fetches, the third and the fourth
-// send (the fourth is the one compared), and the faster way is the context's for large batches from then on (until then:
-// fetched).  Streams of short tickets decide for themselves (mcraw_decode_batch_async: sending won wherever it was
-// measured).  MCRAW_SHORT_WAY=0|1 decides both beforehand.
-
 size_t host_bytes(const mcraw_frame *frames, int n, uint32_t mode)
 {
     size_t total = 0;
     for (int i = 0; i < n; i++)
         total += static_cast<size_t>(frames[i].len) + frame_out_full(frames[i], mode);
     return total;
-}
-
-void way_from_env(mcraw_ctx *c)
-{
-    if (c->env_short_way >= 0 && c->send_home < 0)
-        c->send_home = c->send_home_tickets = c->env_short_way;
-    // (a context that shares its device does not compare -- the others' traffic is in its times --: it takes what a context of
-    // this device found, if one has)
-    if (c->send_home < 0 && !alone_on_device(c) && c->device >= 0 && c->device < 64) {
-        std::lock_guard<std::mutex> lk(g_gate[c->device].mu);
-        if (g_gate[c->device].way >= 0)
-            c->send_home = c->send_home_tickets = g_gate[c->device].way;
-    }
-}
-
-// The way of a batch of more than one piece; *trial: it is one of the two that are compared (big_way_result when it is over).
-int big_way(mcraw_ctx *c, size_t total, bool *trial)
-{
-    way_from_env(c);
-    *trial = c->send_home < 0 && alone_on_device(c) && total / PIECE_BYTES >= 10;
-    if (c->send_home >= 0)
-        return c->send_home;
-    if (*trial && c->big_seen++ == 0) {
-        *trial = false; // (the context's first large batch pays for the slots' buffers: fetched, and not compared)
-        // ... and what the other way needs is made now, so that its trial batch does not pay for it: the slots' pinned status
-        // buffers, the first launch of the kernel that writes into them
-        for (Slot &x : c->slots)
-            if (ensure(x.status_host, 4096, true) != 0)
-                break;
-        if (c->slots[0].status_host.p) {
-            warm_send_status(c->slots[0].stream);
-            (void)hipStreamSynchronize(c->slots[0].stream);
-        }
-        (void)hipGetLastError();
-    }
-    return *trial && c->trial_rate[0] != 0.0 ? 1 : 0;
-}
-
-void big_way_result(mcraw_ctx *c, int way, size_t total, double seconds)
-{
-    if (c->send_home >= 0 || seconds <= 0)
-        return;
-    if (way == 1 && c->sent_trials++ == 0)
-        return; // (the first batch that sends is its way's warm-up, as the context's first batch was the other's)
-    c->trial_rate[way] = total / seconds;
-    if (way == 1) {
-        c->send_home = c->trial_rate[1] > c->trial_rate[0] * 1.03 ? 1 : 0;
-        if (c->device >= 0 && c->device < 64) {
-            std::lock_guard<std::mutex> lk(g_gate[c->device].mu);
-            g_gate[c->device].way = c->send_home;
-        }
-        if (c->env_trace)
-            std::fprintf(stderr, "[mcraw] host-memory pipeline: status words fetched %.1f GB/s, sent home %.1f GB/s: %s from here on\n",
-                         c->trial_rate[0] / 1e9, c->trial_rate[1] / 1e9, c->send_home ? "sent" : "fetched");
-    }
 }
 
 int deal_host(mcraw_ctx *c, const mcraw_frame *frames, int n, size_t *written, int32_t *status_out,
@@ -503,7 +438,7 @@ int decode_host(mcraw_ctx *c, const mcraw_frame *frames, int n, size_t *written,
     const size_t total = host_bytes(frames, n, c->post.mode);
     bool trial = false;
     way_from_env(c);
-    const int way = total > PIECE_BYTES ? big_way(c, total, &trial) : std::max(0, c->send_home_tickets);
+    const int way = total > PIECE_BYTES ? big_way(c, total, &trial) : std::max(0, host_way(c, true));
     const auto t0 = std::chrono::steady_clock::now();
     const int rc = deal_host(c, frames, n, written, status_out, pieces, piece_first, true, way);
     if (trial && rc == 0)

@@ -134,21 +134,17 @@ int submit(mcraw_ctx *c, Slot &s, const mcraw_frame *frames, int n, const std::v
     // count over its own pieces and a hand-off: measured (tools/side_split.py, tools/side_warm2.sh), 16 x 12 MP frames
     // 160 -> 85 us with four parts per stream (14-bit noise 205 -> 162), 120 x 8K 270 -> 208 us with two, UHD frames (streams
     // of two to eight pieces) lose.  Which stream needs the parts is a matter of content, so resident batches measure
-    // (side_pick); host-memory batches and re-planned frames take two or four per stream.  MCRAW_SIDE_SPLIT=b,r pins the
+    // (tune_side); host-memory batches and re-planned frames take two or four per stream.  MCRAW_SIDE_SPLIT=b,r pins the
     // numbers (tests run the type-7 suites with 2,2 and 4,4).
     int nsplit[2] = {1, 1};
-    int side_cand = -1;
+    TuneTimer side_timer, xcd_timer;
     {
         uint32_t rmax = 0;
         for (const Plan7 &p : B.p7)
             rmax = std::max(rmax, p.ngroups);
         const bool longstreams = rmax >= 2900u && n7 * 4 <= 1024;
         if (longstreams && !dev_in && !geom_override && !c->env_side_split[0]) {
-            side_cand = side_pick(c, n7, rmax);
-            const mcraw_ctx::SideTune &t = c->side_tunes[c->side_last];
-            const int k = side_cand >= 0 ? side_cand : std::max(t.decided, 0);
-            nsplit[0] = t.cand[k][0];
-            nsplit[1] = t.cand[k][1];
+            tune_side(c, n7, rmax, nsplit, side_timer);
         } else if (longstreams && n7 * 8 <= 512)
             nsplit[0] = nsplit[1] = 4;
         else if (longstreams && n7 * 4 <= 512)
@@ -277,43 +273,26 @@ int submit(mcraw_ctx *c, Slot &s, const mcraw_frame *frames, int n, const std::v
         // the other, from box to box and -- for the eight parts -- from one process to the next on one box: the streams
         // meet on memory channels or not, as the physical pages of the caller's buffers fall (runs of 8 MiB are the slow
         // case every time).  So large resident batches measure: the first launches of a geometry take turns between
-        // events, the faster candidate stays, and one launch in 64 re-checks it (tune_pick).  MCRAW_XCD_CHUNK pins the
+        // events, the faster candidate stays, and one launch in 64 re-checks it (tune_xcd).  MCRAW_XCD_CHUNK pins the
         // choice (0: eight parts, 1: blockIdx order, n: runs of n).
         const int xcd_env = c->env_xcd_chunk;
         const bool tunable = xcd_env < 0 && !dev_in && !geom_override && n7 >= 32;
-        int tune_cand = -1;
-        uint32_t xcd_chunk = xcd_env >= 0 ? static_cast<uint32_t>(xcd_env) : 128u;
-        if (tunable) {
-            tune_cand = tune_pick(c, n7, static_cast<uint32_t>(Rmax), c->post.mode);
-            xcd_chunk = TUNE_CHUNKS[tune_cand >= 0 ? tune_cand : std::max(c->tunes[c->tune_last].decided, 0)];
-        }
-        W.xcd_chunk = xcd_chunk;
+        W.xcd_chunk = xcd_env >= 0 ? static_cast<uint32_t>(xcd_env) : 128u;
+        if (tunable)
+            W.xcd_chunk = tune_xcd(c, n7, static_cast<uint32_t>(Rmax), c->post.mode, xcd_timer);
         W.nclasses = nclasses;
         for (uint32_t k = 0; k <= nclasses; k++)
             W.class_first[k] = class_first[k];
         for (uint32_t k = 0; k < nclasses; k++)
             W.class_groups[k] = class_groups[k];
         for (uint32_t stage : {MCRAW_K7_SIDE, MCRAW_K7_TILES}) {
-            hipEvent_t ta = nullptr, tb = nullptr;
-            const bool time_side = stage == MCRAW_K7_SIDE && side_cand >= 0;
-            hipStream_t kst = st;
-            if ((stage == MCRAW_K7_TILES && tune_cand >= 0) || time_side) {
-                ta = get_event(c);
-                tb = get_event(c);
-                if (ta && tb)
-                    (void)hipEventRecord(ta, kst);
-            }
+            TuneTimer &tm = stage == MCRAW_K7_SIDE ? side_timer : xcd_timer;
+            tm.begin(st);
             {
-                KTimer t(c, static_cast<int>(stage), kst);
-                launch_k7(W, stage, kst);
+                KTimer t(c, static_cast<int>(stage), st);
+                launch_k7(W, stage, st);
             }
-            if (ta && tb) {
-                (void)hipEventRecord(tb, kst);
-                if (time_side)
-                    c->side_tunes[c->side_last].pending.push_back({ta, tb, side_cand});
-                else
-                    c->tunes[c->tune_last].pending.push_back({ta, tb, tune_cand});
-            }
+            tm.end();
         }
     }
     if (n6) {
