@@ -409,6 +409,45 @@ int mcraw_demosaic_display_batch(mcraw_ctx *ctx, const mcraw_rgb *p, const mcraw
                                  size_t in_frame_stride, int width, int height, int n, void *out, size_t out_bytes,
                                  void *stream);
 
+/* ---- uint16 mosaics -> video-ready Y'CbCr 4:2:0: NV12 (8 bit) / P010 (10 bit) --------------------------------------
+ *
+ * Everything up to the LUT lookup is mcraw_demosaic_display_batch, bit for bit: the integer estimates, the colour stage,
+ * the clamp, i = rint(c * (L - 1)) and the LUT rules (the caller's DEVICE memory, 16-byte aligned, L = 1 << lut_log2 uint16
+ * entries, read in stream order, never copied or cached).  Then, in integers (int32 sums, `>>` arithmetic: floor):
+ *   P_c = lut[i_c] & ((1 << in_bits) - 1)                                   c = R', G', B'
+ *   Y   = clamp(((cy . P + (1 << (sh - 1))) >> sh) + y_off, 0, top)         per output pixel; top = 2^bits - 1
+ *   S_c = sum of P_c over the 2x2 block of output pixels (rows 2j, 2j + 1; columns 2k, 2k + 1)
+ *   Cb  = clamp(((cb . S + (1 << (sh + 1))) >> (sh + 2)) + c_off, 0, top)   per 2x2 block
+ *   Cr  = clamp(((cr . S + (1 << (sh + 1))) >> (sh + 2)) + c_off, 0, top)
+ * The box average puts the chroma sample at the centre of its 2x2 block (JPEG / MPEG-1 siting), not on the left column.
+ * Formats: MCRAW_YUV_NV12: bits = 8, uint8 samples; MCRAW_YUV_P010: bits = 10, uint16 samples holding code << 6.
+ * Output per frame, frames back to back: the Y plane, Ho x Wo samples, row-major; directly behind it Ho / 2 rows of Wo / 2
+ * interleaved (Cb, Cr) pairs: Ho * Wo * 3 / 2 samples, what `-f rawvideo -pix_fmt nv12` / `p010le` reads.  Ho, Wo as for
+ * mcraw_demosaic_batch.  `p`, `colors`, `in` follow mcraw_demosaic_display_batch's rules (p->dtype and p->flags 0).
+ * Rejected besides (returns < 0, mcraw_last_error says why, nothing is written): a NULL `y`; an unknown format; a non-zero
+ * `reserved`; a NULL or not 16-byte aligned `lut`; lut_log2 outside 8 .. 16; in_bits outside 8 .. 16; sh outside 1 .. 24;
+ * y_off or c_off outside 0 .. top; an odd Ho or Wo (BIN2: a width or height that is no multiple of 4); out_bytes <
+ * n * Ho * Wo * 3 / 2 * sample size; an `out` not aligned to the sample size; and, for any of cy, cb, cr,
+ *   4 * (2^in_bits - 1) * (|c0| + |c1| + |c2|) + 2^(sh + 1) >= 2^31.
+ * With that rule and the mask on P_c no LUT content can make an int32 sum wrap.
+ * The call queues on `stream` and returns; it takes no decode serial and leaves the decode slots, mcraw_ctx_errors and the
+ * context's stage alone.  n == 0 is a no-op.  Kernels: MCRAW_KRGB_MHC / MCRAW_KRGB_BIN2 (mcraw_ctx_kernel_ms). */
+#define MCRAW_YUV_NV12  1
+#define MCRAW_YUV_P010  2
+typedef struct mcraw_yuv {
+    uint32_t format;       /* MCRAW_YUV_NV12 / MCRAW_YUV_P010                       */
+    uint32_t lut_log2;     /* 8 .. 16: the LUT has L = 1 << lut_log2 entries        */
+    uint32_t in_bits;      /* 8 .. 16: bits of a LUT entry that are used            */
+    uint32_t sh;           /* 1 .. 24: binary point of the coefficients             */
+    int32_t y_off, c_off;  /* 0 .. top                                              */
+    int32_t cy[3], cb[3], cr[3]; /* rows of the matrix, times 2^sh                  */
+    uint32_t reserved;     /* must be 0                                             */
+    const uint16_t *lut;   /* DEVICE memory, 16-byte aligned, read in stream order  */
+} mcraw_yuv;               /* sizeof 72; y_off 16, c_off 20, cy 24, cb 36, cr 48, reserved 60, lut 64 */
+int mcraw_demosaic_yuv_batch(mcraw_ctx *ctx, const mcraw_rgb *p, const mcraw_yuv *y, const mcraw_rgb_color *colors,
+                             int ncolors, const uint16_t *in, size_t in_pitch, size_t in_frame_stride, int width,
+                             int height, int n, void *out, size_t out_bytes, void *stream);
+
 /* ---- environment ------------------------------------------------------------------------------
  * Read when a context (or pool) is created, never afterwards:
  *   MCRAW_DEVICE=n, MCRAW_DEVICES=all|0,1,5   default device of the five-argument entry points / members of a default pool

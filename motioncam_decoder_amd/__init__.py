@@ -9,12 +9,13 @@ There is no CPU decode path here: if the HIP library is missing or no GPU is
 present, every decode call raises.
 """
 import ctypes as C
+import functools
 import os
 
 __all__ = ["lib_path", "load", "Context", "Pool", "Frame", "EncFrame", "FloatOut", "McrawError", "TYPE_LEGACY", "TYPE_BLOCK",
            "MEM_DEVICE", "MEM_HOST", "KERNELS", "ENC_KERNELS", "ABI_SYMBOLS", "encode_bound7", "cfa_planes",
            "RgbParams", "RgbColor", "RGB_KERNELS", "rgb_color", "Display", "transfer_lut", "DISP_U8", "DISP_U16",
-           "DISP_CHW", "DISP_HWC"]
+           "DISP_CHW", "DISP_HWC", "Yuv", "YUV_NV12", "YUV_P010", "yuv_matrix", "yuv_planes"]
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 
@@ -41,7 +42,7 @@ ABI_SYMBOLS = [
     "mcraw_pool_decode_batch_device", "mcraw_ctx_xcd_runs", "mcraw_pool_synchronize", "mcraw_tile_order",
     "mcraw_ctx_last_serial", "mcraw_ctx_batch_status", "mcraw_ctx_errors", "mcraw_ctx_side_parts", "mcraw_ctx_host_way",
     "mcraw_encode_bound7", "mcraw_encode_batch", "mcraw_encode7", "mcraw_ctx_set_float_out", "mcraw_pool_set_float_out",
-    "mcraw_demosaic_batch", "mcraw_demosaic_display_batch",
+    "mcraw_demosaic_batch", "mcraw_demosaic_display_batch", "mcraw_demosaic_yuv_batch",
 ]
 
 POST_BLACK, POST_PACK12, POST_PACK10, POST_PACK14 = 1, 2, 4, 8
@@ -143,6 +144,79 @@ class Display(C.Structure):
     """struct mcraw_display (include/mcraw_hip.h): output dtype, layout and the device LUT of L = 1 << lut_log2 entries."""
     _fields_ = [("dtype", C.c_uint32), ("layout", C.c_uint32), ("lut_log2", C.c_uint32), ("reserved", C.c_uint32),
                 ("lut", C.c_void_p)]
+
+
+# video-ready Y'CbCr 4:2:0 (mcraw_demosaic_yuv_batch)
+YUV_NV12, YUV_P010 = 1, 2
+_YUV_FORMATS = {"nv12": (YUV_NV12, 8, 12), "p010": (YUV_P010, 10, 16)}  # code, bits, default in_bits
+_YUV_KR_KB = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722), "bt2020": (0.2627, 0.0593)}
+_YUV_SH = tuple(range(24, 0, -1))  # candidates for sh, largest first
+
+
+class Yuv(C.Structure):
+    """struct mcraw_yuv (include/mcraw_hip.h): format, the device LUT and the integer matrix behind it."""
+    _fields_ = [("format", C.c_uint32), ("lut_log2", C.c_uint32), ("in_bits", C.c_uint32), ("sh", C.c_uint32),
+                ("y_off", C.c_int32), ("c_off", C.c_int32), ("cy", C.c_int32 * 3), ("cb", C.c_int32 * 3),
+                ("cr", C.c_int32 * 3), ("reserved", C.c_uint32), ("lut", C.c_void_p)]
+
+
+def _yuv_rule_ok(rows, sh, in_bits):
+    """The overflow rule of mcraw_demosaic_yuv_batch: no int32 sum can wrap."""
+    return all(4 * ((1 << in_bits) - 1) * sum(abs(int(c)) for c in r) + (1 << (sh + 1)) < (1 << 31) for r in rows)
+
+
+def yuv_matrix(standard="bt709", range="limited", bits=8, in_bits=8):
+    """(cy, cb, cr, sh, y_off, c_off) as Python ints for mcraw_demosaic_yuv_batch: the R'G'B' -> Y'CbCr matrix of
+    `standard` ("bt601", "bt709", "bt2020") for LUT entries of `in_bits` (8 .. 16) bits and codes of `bits` (8 or 10) bits,
+    range "limited" (luma 16 .. 235, chroma 16 .. 240, times 2^(bits - 8)) or "full" (0 .. 2^bits - 1, chroma centred on
+    2^(bits - 1)).  sh is the largest the overflow rule admits; the coefficients are the scaled ones rounded to nearest,
+    then the G entry of each row is corrected so that sum(cb) == sum(cr) == 0 and sum(cy) == rint(luma_span * 2^sh /
+    (2^in_bits - 1)): greys are exactly neutral, and black and white land exactly on the ends of the range."""
+    key = standard.lower() if isinstance(standard, str) else None
+    if key not in _YUV_KR_KB:
+        raise ValueError("yuv_matrix: standard must be 'bt601', 'bt709' or 'bt2020', not %r" % (standard,))
+    if range not in ("limited", "full"):
+        raise ValueError("yuv_matrix: range must be 'limited' or 'full', not %r" % (range,))
+    if isinstance(bits, bool) or bits not in (8, 10):
+        raise ValueError("yuv_matrix: bits must be 8 or 10, not %r" % (bits,))
+    if isinstance(in_bits, bool) or in_bits not in (8, 9, 10, 11, 12, 13, 14, 15, 16):
+        raise ValueError("yuv_matrix: in_bits must be 8 .. 16, not %r" % (in_bits,))
+    return _yuv_matrix(key, range == "limited", int(bits), int(in_bits))
+
+
+@functools.lru_cache(maxsize=None)
+def _yuv_matrix(key, limited, bits, in_bits):
+    """yuv_matrix behind its argument checks, in exact rational arithmetic (once per combination: demosaic_yuv asks on
+    every call)."""
+    from fractions import Fraction as F
+    kr, kb = (F(str(v)) for v in _YUV_KR_KB[key])
+    kg = 1 - kr - kb
+    if limited:
+        luma, chroma, y_off, c_off = 219 << (bits - 8), 224 << (bits - 8), 16 << (bits - 8), 128 << (bits - 8)
+    else:
+        luma, chroma, y_off, c_off = (1 << bits) - 1, (1 << bits) - 1, 0, 1 << (bits - 1)
+    top_in = (1 << in_bits) - 1
+    fy = [k * luma / top_in for k in (kr, kg, kb)]
+    fcb = [k * chroma / (2 * (1 - kb)) / top_in for k in (-kr, -kg, 1 - kb)]
+    fcr = [k * chroma / (2 * (1 - kr)) / top_in for k in (1 - kr, -kg, -kb)]
+    rint = lambda v: int(round(v))  # (Fraction: exact, ties to even)
+    for sh in _YUV_SH:
+        cy, cb, cr = ([rint(v * (1 << sh)) for v in row] for row in (fy, fcb, fcr))
+        cy[1] = rint(F(luma << sh, top_in)) - cy[0] - cy[2]
+        cb[1] = -(cb[0] + cb[2])
+        cr[1] = -(cr[0] + cr[2])
+        if _yuv_rule_ok((cy, cb, cr), sh, in_bits):
+            return tuple(cy), tuple(cb), tuple(cr), sh, y_off, c_off
+    raise ValueError("yuv_matrix: no sh satisfies the overflow rule")  # (not reachable for the arguments accepted above)
+
+
+def yuv_planes(t, Ho):
+    """(Y, CbCr) as views of a demosaic_yuv / decode_yuv result (N, Ho * 3 // 2, Wo): Y (N, Ho, Wo) and the interleaved
+    chroma (N, Ho / 2, Wo / 2, 2), [..., 0] = Cb, [..., 1] = Cr (a result without N gives planes without N)."""
+    Ho = int(Ho)
+    if t.shape[-2] != Ho * 3 // 2 or Ho % 2 or t.shape[-1] % 2:
+        raise ValueError("yuv_planes: %s is no (.., Ho * 3 // 2, Wo) result for Ho = %d" % (tuple(t.shape), Ho))
+    return t[..., :Ho, :], t[..., Ho:, :].reshape(tuple(t.shape[:-2]) + (Ho // 2, t.shape[-1] // 2, 2))
 
 
 def _srgb_oetf(x):
@@ -399,6 +473,10 @@ def load():
     lib.mcraw_demosaic_display_batch.argtypes = [C.c_void_p, C.POINTER(RgbParams), C.POINTER(Display), C.POINTER(RgbColor),
                                                  C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int,
                                                  C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.mcraw_demosaic_yuv_batch.restype = C.c_int
+    lib.mcraw_demosaic_yuv_batch.argtypes = [C.c_void_p, C.POINTER(RgbParams), C.POINTER(Yuv), C.POINTER(RgbColor), C.c_int,
+                                             C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                             C.c_size_t, C.c_void_p]
     lib.mcraw_encode7.restype = C.c_size_t
     lib.mcraw_encode7.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int]
     _lib = lib
@@ -968,6 +1046,85 @@ class Context:
         return self.demosaic_display(scratch, algo=algo, white=white, black=black, cfa=cfa, gain=gain, matrix=matrix,
                                      transfer=transfer, lut_size=lut_size, dtype=dtype, layout=layout, bits=bits, out=out,
                                      check=check)
+
+    def demosaic_yuv(self, mosaic, *, algo="mhc", white, black=(0, 0, 0, 0), cfa="rggb", gain=None, matrix=None, fmt="nv12",
+                     standard="bt709", range="limited", transfer="bt709", lut_size=4096, in_bits=None, out=None, check=True):
+        """uint16 mosaics resident on the context's device -> video-ready Y'CbCr 4:2:0: the demosaic, colours, clamp and
+        transfer-curve LUT of demosaic_display(), then the integer matrix of yuv_matrix(standard, range) and a 2x2 box
+        average for the chroma (sited at the block's centre).  fmt "nv12": torch.uint8; "p010": torch.uint16 holding
+        10-bit codes << 6.  Result (N, Ho * 3 // 2, Wo) (an (H, W) mosaic drops N): per frame the Y plane (Ho rows), then
+        Ho / 2 rows of interleaved (Cb, Cr) -- the bytes ffmpeg reads as -f rawvideo -pix_fmt nv12 / p010le; yuv_planes()
+        gives the two as views.  Ho and Wo must be even (bin2: H and W multiples of 4).  transfer: as demosaic_display; a
+        built-in curve is transfer_lut(transfer, lut_size, in_bits), in_bits defaulting to 12 (nv12) or 16 (p010); a ready
+        LUT may hold entries of any in_bits 8 .. 16 (higher bits are masked off).  Queued on torch.cuda.current_stream();
+        nothing synchronises.  `check` is accepted for symmetry with decode_yuv."""
+        import torch
+        if algo not in _RGB_ALGOS:
+            raise ValueError("algo must be 'mhc' or 'bin2', not %r" % (algo,))
+        key = str(cfa).strip().lower()
+        if key not in _CFA_CODES:
+            raise ValueError("unknown cfa %r (rggb, bggr, grbg or gbrg)" % (cfa,))
+        if fmt not in _YUV_FORMATS:
+            raise ValueError("demosaic_yuv: fmt must be 'nv12' or 'p010', not %r" % (fmt,))
+        fcode, bits, default_in = _YUV_FORMATS[fmt]
+        in_bits = default_in if in_bits is None else in_bits
+        cy, cb, cr, sh, y_off, c_off = yuv_matrix(standard, range, bits, in_bits)
+        tdtype = torch.uint8 if fcode == YUV_NV12 else torch.uint16
+        dev = self._torch_device(torch)
+        if not isinstance(mosaic, torch.Tensor) or mosaic.dtype != torch.uint16 or mosaic.device != dev or mosaic.dim() not in (2, 3):
+            raise ValueError("demosaic_yuv: mosaic must be a uint16 tensor (N, H, W) or (H, W) on %s" % dev)
+        single = mosaic.dim() == 2
+        mos = mosaic.unsqueeze(0) if single else mosaic
+        n, h, w = (int(v) for v in mos.shape)
+        if n and h > 1 and mos.stride(2) != 1:
+            raise ValueError("demosaic_yuv: the rows of the mosaic must be contiguous")
+        ho, wo = (h, w) if algo == "mhc" else (h // 2, w // 2)
+        shape = (n, ho * 3 // 2, wo)
+        want = shape[1:] if single else shape
+        if out is None:
+            out = torch.empty(want, dtype=tdtype, device=dev)
+        elif tuple(out.shape) != tuple(want) or out.dtype != tdtype or out.device != dev or not out.is_contiguous():
+            raise ValueError("demosaic_yuv: out must be a contiguous %s tensor of shape %s on %s" % (tdtype, tuple(want), dev))
+        if n == 0:
+            return out
+        lut, own = self._display_lut(torch, dev, transfer, lut_size, in_bits)
+        cols, nc = _rgb_colors(gain, matrix, n, "demosaic_yuv")
+        prm = _rgb_params(algo, 0, 0, key, white, black)
+        y = Yuv()
+        y.format, y.lut_log2, y.in_bits, y.sh, y.y_off, y.c_off = fcode, int(lut.numel()).bit_length() - 1, in_bits, sh, y_off, c_off
+        for i in (0, 1, 2):
+            y.cy[i], y.cb[i], y.cr[i] = cy[i], cb[i], cr[i]
+        y.reserved = 0
+        y.lut = lut.data_ptr()
+        pitch = int(mos.stride(1)) if h > 1 else w
+        fstride = int(mos.stride(0)) if n > 1 else pitch * h
+        cur, run = self._run_stream(torch, dev)
+        try:
+            rc = self._lib.mcraw_demosaic_yuv_batch(self._h, C.byref(prm), C.byref(y), cols, nc, C.c_void_p(mos.data_ptr()), pitch,
+                                                    fstride, w, h, n, C.c_void_p(out.data_ptr()),
+                                                    out.numel() * out.element_size(), C.c_void_p(run.cuda_stream))
+        finally:
+            if run is not cur:
+                mos.record_stream(run)
+                out.record_stream(run)
+                if own:
+                    lut.record_stream(run)
+                cur.wait_stream(run)
+        if rc != 0:
+            raise McrawError("mcraw_demosaic_yuv_batch failed (%d): %s" % (rc, self._lib.mcraw_last_error().decode()))
+        return out
+
+    def decode_yuv(self, inputs, width, height, type, *, algo="mhc", white, black=(0, 0, 0, 0), cfa="rggb", gain=None,
+                   matrix=None, fmt="nv12", standard="bt709", range="limited", transfer="bt709", lut_size=4096, in_bits=None,
+                   out=None, check=True):
+        """Decode frames of one geometry that are resident in HBM and turn them into NV12 / P010 (demosaic_yuv()), as
+        decode_display does: the plain uint16 mosaics go to a scratch tensor, both steps are queued on
+        torch.cuda.current_stream(), check=True synchronises after the decode and raises McrawError naming the frames that
+        failed, and the context's stage is restored afterwards."""
+        scratch = self._decode_scratch(inputs, width, height, type, check, "decode_yuv")
+        return self.demosaic_yuv(scratch, algo=algo, white=white, black=black, cfa=cfa, gain=gain, matrix=matrix, fmt=fmt,
+                                 standard=standard, range=range, transfer=transfer, lut_size=lut_size, in_bits=in_bits, out=out,
+                                 check=check)
 
     def profile(self, enable=True, only=None, every=1):
         """Bracket kernel launches with events: all kernels, or just the names in `only`; every `every`-th launch."""

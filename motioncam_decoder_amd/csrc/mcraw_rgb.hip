@@ -11,7 +11,13 @@
 // then clamp, index a transfer-curve LUT and store uint8 / uint16, (N, 3, Ho, Wo) or (N, Ho, Wo, 3): layout and where the
 // LUT is read from (LDS or global) are wave-uniform run-time flags.  Their grids are persistent (a grid-stride loop over
 // tiles), so that each workgroup stages the LUT in LDS once; tests/_display_ref.py states the stage in numpy.
+//
+// The YUV kinds (PK_NV12 / PK_P010, mcraw_demosaic_yuv_batch) run the display stage up to the LUT entry, then an integer
+// 3x3 matrix: a luma sample per pixel and, from the sums over each 2x2 block of output pixels, one (Cb, Cr) pair (4:2:0,
+// chroma at the block's centre).  A lane owns whole 2x2 blocks (8 columns of a row pair), so nothing is exchanged.
+// tests/_yuv_ref.py states the stage in numpy.
 #include <cmath>
+#include <cstdlib>
 
 #include "mcraw_dev.h"
 #include "mcraw_host.h"
@@ -44,6 +50,10 @@ struct RgbArgs {
     uint32_t lutg;       // the LUT is read from global memory (L > DISP_LDS_MAX) rather than staged in LDS
     uint32_t hwc;        // (n, Ho, Wo, 3) rather than (n, 3, Ho, Wo)
     uint32_t units, nf;  // tiles (MHC) or workgroups' items (BIN2) per frame; frames in this launch
+    // YUV kinds only (behind everything else)
+    int32_t ycf[9];      // cy, cb, cr
+    uint32_t ymask, ysh; // (1 << in_bits) - 1; sh
+    int32_t yoff, coff;
 };
 
 constexpr uint32_t RGB_T = 256;             // threads per workgroup
@@ -57,7 +67,11 @@ constexpr uint32_t MHC_CH = MHC_LW / 8u;    // 16-byte chunks per LDS row
 constexpr int PK_DISP8 = 48, PK_DISP16 = 49;
 constexpr uint32_t DISP_LDS_MAX = 4096; // LUTs up to this many entries (8 KiB) are staged in LDS
 constexpr bool is_disp(int pk) { return pk == PK_DISP8 || pk == PK_DISP16; }
-constexpr uint32_t out_es(int pk) { return pk == PK_F32 ? 4u : pk == PK_DISP8 ? 1u : 2u; }
+// Y'CbCr 4:2:0 output kinds: a Y plane, then interleaved (Cb, Cr) rows; uint8, or uint16 holding a 10-bit code << 6
+constexpr int PK_NV12 = 50, PK_P010 = 51;
+constexpr bool is_yuv(int pk) { return pk == PK_NV12 || pk == PK_P010; }
+constexpr bool has_lut(int pk) { return is_disp(pk) || is_yuv(pk); } // persistent grid, LUT staged per workgroup
+constexpr uint32_t out_es(int pk) { return pk == PK_F32 ? 4u : (pk == PK_DISP8 || pk == PK_NV12) ? 1u : 2u; }
 
 static __device__ __forceinline__ int reflect101(int i, int n)
 {
@@ -159,16 +173,14 @@ __device__ __forceinline__ void rgb_store8(const RgbArgs &A, const RgbCol &col, 
 //   HWC  u8: 24 B per lane as 16 + 8 B, in whichever order keeps the 16-byte store 16-byte aligned (8-byte aligned rows);
 //        u16: 48 B per lane as three 16-byte stores (16-byte aligned rows)
 //   element stores for a cropped row end and for rows off those grids
-template <int PK>
-__device__ __forceinline__ void disp_store8(const RgbArgs &A, const RgbCol &col, const uint16_t *s_lut, uint8_t *frame_out,
-                                            uint32_t y, uint32_t x, uint32_t n, const int (&E)[3][8])
+// (disp_lookup8: everything up to the LUT entry q, which the YUV kinds share)
+__device__ __forceinline__ void disp_lookup8(const RgbArgs &A, const RgbCol &col, const uint16_t *s_lut, const int (&E)[3][8],
+                                             uint32_t (&q)[3][8])
 {
 #pragma clang fp contract(off)
-    constexpr uint32_t ES = out_es(PK);
     float o[3][8];
     rgb_color8(col, E, o);
     const float lf = static_cast<float>(A.lutn - 1u);
-    uint32_t q[3][8];
 #pragma unroll
     for (int r = 0; r < 3; r++)
 #pragma unroll
@@ -189,6 +201,15 @@ __device__ __forceinline__ void disp_store8(const RgbArgs &A, const RgbCol &col,
             for (int i = 0; i < 8; i++)
                 q[r][i] = s_lut[q[r][i]];
     }
+}
+
+template <int PK>
+__device__ __forceinline__ void disp_store8(const RgbArgs &A, const RgbCol &col, const uint16_t *s_lut, uint8_t *frame_out,
+                                            uint32_t y, uint32_t x, uint32_t n, const int (&E)[3][8])
+{
+    constexpr uint32_t ES = out_es(PK);
+    uint32_t q[3][8];
+    disp_lookup8(A, col, s_lut, E, q);
     if (ES == 1u) {
 #pragma unroll
         for (int r = 0; r < 3; r++)
@@ -273,6 +294,80 @@ __device__ __forceinline__ void disp_store8(const RgbArgs &A, const RgbCol &col,
     }
 }
 
+// 8 consecutive samples (n of them exist) of one row of a YUV plane: one 8-byte (uint8) or 16-byte (uint16) store on
+// natural alignment, element stores for a cropped row end or an address off that grid.
+template <uint32_t ES>
+__device__ __forceinline__ void yuv_store8(uint8_t *dst, uint32_t n, const uint32_t (&v)[8])
+{
+    const uintptr_t a = reinterpret_cast<uintptr_t>(dst);
+    if (ES == 1u) {
+        if (n == 8u && (a & 7u) == 0u) {
+            *gptr<mcraw_u32x2>(dst) = mcraw_u32x2{v[0] | (v[1] << 8) | (v[2] << 16) | (v[3] << 24),
+                                                  v[4] | (v[5] << 8) | (v[6] << 16) | (v[7] << 24)};
+        } else {
+#pragma unroll
+            for (uint32_t i = 0; i < 8u; i++)
+                if (i < n)
+                    gptr<uint8_t>(dst)[i] = static_cast<uint8_t>(v[i]);
+        }
+    } else {
+        if (n == 8u && (a & 15u) == 0u) {
+            *gptr<mcraw_u32x4>(dst) = mcraw_u32x4{v[0] | (v[1] << 16), v[2] | (v[3] << 16), v[4] | (v[5] << 16), v[6] | (v[7] << 16)};
+        } else {
+#pragma unroll
+            for (uint32_t i = 0; i < 8u; i++)
+                if (i < n)
+                    gptr<uint16_t>(dst)[i] = static_cast<uint16_t>(v[i]);
+        }
+    }
+}
+
+// The YUV stage of row `a` (0 or 1) of a row pair: the display stage up to the LUT entry, P = entry & mask, then
+//   Y = clamp(((cy . P + (1 << (sh - 1))) >> sh) + y_off, 0, top), stored at once;
+// S (the sums of P over the lane's four 2x2 blocks) takes the row, and behind row 1
+//   Cb, Cr = clamp(((c . S + (1 << (sh + 1))) >> (sh + 2)) + c_off, 0, top), stored as four (Cb, Cr) pairs.
+// The host's overflow rule keeps every coefficient below 2^22 in magnitude and every sum inside int32; P < 2^16 and
+// S < 2^18: the products are exact as 24-bit multiplies (v_mad_i32_i24, full rate; v_mul_lo_u32 is quarter rate).
+template <int PK>
+__device__ __forceinline__ void yuv_row8(const RgbArgs &A, const RgbCol &col, const uint16_t *s_lut, uint8_t *frame_out,
+                                         uint32_t y, uint32_t x, uint32_t n, int a, const int (&E)[3][8], int (&S)[3][4])
+{
+    constexpr uint32_t ES = out_es(PK);
+    constexpr int TOP = PK == PK_NV12 ? 255 : 1023, SHL = PK == PK_NV12 ? 0 : 6;
+    uint32_t q[3][8];
+    disp_lookup8(A, col, s_lut, E, q);
+    int P[3][8];
+#pragma unroll
+    for (int c = 0; c < 3; c++)
+#pragma unroll
+        for (int i = 0; i < 8; i++)
+            P[c][i] = static_cast<int>(q[c][i] & A.ymask);
+    const int rnd = 1 << (A.ysh - 1u);
+    uint32_t v[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        const int s = __mul24(A.ycf[0], P[0][i]) + __mul24(A.ycf[1], P[1][i]) + __mul24(A.ycf[2], P[2][i]) + rnd;
+        v[i] = static_cast<uint32_t>(min(max((s >> A.ysh) + A.yoff, 0), TOP)) << SHL;
+    }
+    yuv_store8<ES>(frame_out + (static_cast<size_t>(y) * A.Wo + x) * ES, n, v);
+#pragma unroll
+    for (int c = 0; c < 3; c++)
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            S[c][k] += P[c][2 * k] + P[c][2 * k + 1];
+    if (a == 0)
+        return;
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+#pragma unroll
+        for (int r = 1; r < 3; r++) {
+            const int s = __mul24(A.ycf[3 * r], S[0][k]) + __mul24(A.ycf[3 * r + 1], S[1][k]) + __mul24(A.ycf[3 * r + 2], S[2][k]) +
+                          4 * rnd;
+            v[2 * k + r - 1] = static_cast<uint32_t>(min(max((s >> (A.ysh + 2u)) + A.coff, 0), TOP)) << SHL;
+        }
+    yuv_store8<ES>(frame_out + ((static_cast<size_t>(A.Ho) + (y >> 1)) * A.Wo + x) * ES, n, v);
+}
+
 // A display kernel's workgroup stages an LDS-sized LUT once, before its first tile (the caller syncs).
 __device__ __forceinline__ void stage_lut(const RgbArgs &A, uint16_t *s_lut)
 {
@@ -288,13 +383,13 @@ __device__ __forceinline__ void stage_lut(const RgbArgs &A, uint16_t *s_lut)
 // frame edges) in LDS as raw samples, 16-byte chunks on the frame's 8-column grid.  Lane (lx, ly) then makes 8 columns of
 // row pairs ly and ly + 8: four CFA quads, so every filter choice is fixed per lane slot by the CFA (template S: the RGGB
 // role of CFA position p is p ^ S).  The halo rows are read again by the tiles above and below (L2 / Infinity Cache).
-// Float kinds: one tile per workgroup (blockIdx.x: tile, blockIdx.y: frame).  Display kinds: a persistent grid whose
+// Float kinds: one tile per workgroup (blockIdx.x: tile, blockIdx.y: frame).  Display and YUV kinds: a persistent grid whose
 // workgroups stage the LUT in LDS once and then take units t = blockIdx.x, + gridDim.x, ... (A.units tiles per frame, of
 // the launch's A.nf frames); the loop runs once for the float kinds.
 template <int PK, int S>
 __global__ void __launch_bounds__(RGB_T) krgb_mhc(const RgbArgs A)
 {
-    constexpr bool DISP = is_disp(PK);
+    constexpr bool DISP = has_lut(PK);
     __shared__ __attribute__((aligned(16))) uint16_t s_t[MHC_LH * MHC_LW];
     __shared__ __attribute__((aligned(16))) uint16_t s_lut[DISP ? DISP_LDS_MAX : 8u];
     uint32_t t = blockIdx.x;
@@ -331,7 +426,7 @@ __global__ void __launch_bounds__(RGB_T) krgb_mhc(const RgbArgs A)
             continue;
         const uint32_t n = min(8u, A.W - x);
         const RgbCol &col = A.col[A.percol ? f : 0u];
-        uint8_t *fout = A.out + static_cast<size_t>(f) * 3u * A.Ho * A.Wo * out_es(PK);
+        uint8_t *fout = A.out + static_cast<size_t>(f) * 3u * A.Ho * A.Wo * out_es(PK) / (is_yuv(PK) ? 2u : 1u);
     #pragma unroll 1
         for (uint32_t pass = 0; pass < MHC_TH / 16u; pass++) {
             const uint32_t rp = ly + 8u * pass, y = static_cast<uint32_t>(y0) + 2u * rp;
@@ -350,6 +445,7 @@ __global__ void __launch_bounds__(RGB_T) krgb_mhc(const RgbArgs A)
                 for (int j = 0; j < 12; j++)
                     d[r][j] = static_cast<int>((w[j >> 1] >> (16u * (j & 1))) & 0xffffu) - A.black[(r & 1) * 2 + (j & 1)];
             }
+            int SUM[3][4] = {}; // YUV kinds: the sums of P over the lane's four 2x2 blocks
     #pragma unroll
             for (int a = 0; a < 2; a++) {
                 int E[3][8];
@@ -377,7 +473,9 @@ __global__ void __launch_bounds__(RGB_T) krgb_mhc(const RgbArgs A)
                     }
                 }
                 if (y + static_cast<uint32_t>(a) < A.H) {
-                    if constexpr (is_disp(PK))
+                    if constexpr (is_yuv(PK)) // (H is even: a row pair always has both rows)
+                        yuv_row8<PK>(A, col, s_lut, fout, y + static_cast<uint32_t>(a), x, n, a, E, SUM);
+                    else if constexpr (is_disp(PK))
                         disp_store8<PK>(A, col, s_lut, fout, y + static_cast<uint32_t>(a), x, n, E);
                     else
                         rgb_store8<PK>(A, col, fout, y + static_cast<uint32_t>(a), x, n, E);
@@ -448,6 +546,65 @@ __global__ void __launch_bounds__(RGB_T) krgb_bin2(const RgbArgs A)
     } while (DISP && (t += gridDim.x) < A.units * A.nf);
 }
 
+// The YUV kinds of BIN2: 4:2:0 needs two output rows, so a lane takes 8 output columns of an output row PAIR (four input
+// rows), which holds its four 2x2 blocks.  A kernel of its own: the float and display instances of krgb_bin2 keep their
+// code and registers.  Persistent, as the display kinds; A.units counts groups of 256 such items per frame.
+template <int PK, int S>
+__global__ void __launch_bounds__(RGB_T) krgb_bin2y(const RgbArgs A)
+{
+    static_assert(is_yuv(PK), "the YUV kinds only");
+    constexpr uint32_t ROWS = 2u; // output rows per item
+    __shared__ __attribute__((aligned(16))) uint16_t s_lut[DISP_LDS_MAX];
+    uint32_t t = blockIdx.x;
+    stage_lut(A, s_lut);
+    __syncthreads();
+    do {
+        const uint32_t f = t / A.units, item = (t % A.units) * RGB_T + threadIdx.x;
+        const uint32_t yo = item / A.tilesX * ROWS, xo = 8u * (item % A.tilesX);
+        if (yo >= A.Ho)
+            continue;
+        const uint32_t n = min(8u, A.Wo - xo);
+        int SUM[3][4] = {}; // the sums of P over the lane's four 2x2 blocks
+    #pragma unroll
+        for (uint32_t a = 0; a < ROWS; a++) {
+            const uint16_t *row0 = A.in + static_cast<size_t>(f) * A.fstride + static_cast<size_t>(2u * (yo + a)) * A.pitch + 2u * xo;
+            const uint16_t *row1 = row0 + A.pitch;
+            uint32_t u[2][8]; // (even column | odd column << 16) of quad i, rows 0 and 1
+            if (A.invec && n == 8u) {
+                const mcraw_u32x4 a0 = gptr<const mcraw_u32x4>(row0)[0], a1 = gptr<const mcraw_u32x4>(row0)[1];
+                const mcraw_u32x4 b0 = gptr<const mcraw_u32x4>(row1)[0], b1 = gptr<const mcraw_u32x4>(row1)[1];
+    #pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    u[0][i] = a0[i];
+                    u[0][4 + i] = a1[i];
+                    u[1][i] = b0[i];
+                    u[1][4 + i] = b1[i];
+                }
+            } else {
+    #pragma unroll
+                for (uint32_t i = 0; i < 8u; i++) {
+                    const uint32_t k = i < n ? 2u * i : 0u;
+                    u[0][i] = gptr<const uint16_t>(row0)[k] | (static_cast<uint32_t>(gptr<const uint16_t>(row0)[k + 1]) << 16);
+                    u[1][i] = gptr<const uint16_t>(row1)[k] | (static_cast<uint32_t>(gptr<const uint16_t>(row1)[k + 1]) << 16);
+                }
+            }
+            int E[3][8];
+    #pragma unroll
+            for (int i = 0; i < 8; i++) {
+                int q[4];
+    #pragma unroll
+                for (int p = 0; p < 4; p++)
+                    q[p] = static_cast<int>((u[p >> 1][i] >> (16u * (p & 1))) & 0xffffu) - A.black[p];
+                E[0][i] = 2 * q[0 ^ S];
+                E[1][i] = q[1 ^ S] + q[2 ^ S];
+                E[2][i] = 2 * q[3 ^ S];
+            }
+            uint8_t *fout = A.out + static_cast<size_t>(f) * 3u * A.Ho * A.Wo * out_es(PK) / ROWS;
+            yuv_row8<PK>(A, A.col[A.percol ? f : 0u], s_lut, fout, yo + a, xo, n, static_cast<int>(a), E, SUM);
+        }
+    } while ((t += gridDim.x) < A.units * A.nf);
+}
+
 typedef void (*RgbKernel)(const RgbArgs);
 
 template <int PK>
@@ -455,6 +612,14 @@ static RgbKernel pick_kernel(uint32_t algo, int s)
 {
     static const RgbKernel mhc[4] = {krgb_mhc<PK, 0>, krgb_mhc<PK, 1>, krgb_mhc<PK, 2>, krgb_mhc<PK, 3>};
     static const RgbKernel bin2[4] = {krgb_bin2<PK, 0>, krgb_bin2<PK, 1>, krgb_bin2<PK, 2>, krgb_bin2<PK, 3>};
+    return algo == MCRAW_RGB_MHC ? mhc[s] : bin2[s];
+}
+
+template <int PK>
+static RgbKernel pick_yuv_kernel(uint32_t algo, int s)
+{
+    static const RgbKernel mhc[4] = {krgb_mhc<PK, 0>, krgb_mhc<PK, 1>, krgb_mhc<PK, 2>, krgb_mhc<PK, 3>};
+    static const RgbKernel bin2[4] = {krgb_bin2y<PK, 0>, krgb_bin2y<PK, 1>, krgb_bin2y<PK, 2>, krgb_bin2y<PK, 3>};
     return algo == MCRAW_RGB_MHC ? mhc[s] : bin2[s];
 }
 
@@ -492,8 +657,9 @@ static uint32_t resident_groups(int device, RgbKernel k)
     return g;
 }
 
-// Both entry points: the checks of mcraw_demosaic_batch, those of the display stage when `d` is given, then the launches.
-static int demosaic_launch(const char *fn, mcraw_ctx *c, const mcraw_rgb *p, const mcraw_display *d,
+// The three entry points: the checks of mcraw_demosaic_batch, those of the display stage when `d` is given or of the YUV
+// stage when `yv` is (never both), then the launches.
+static int demosaic_launch(const char *fn, mcraw_ctx *c, const mcraw_rgb *p, const mcraw_display *d, const mcraw_yuv *yv,
                            const mcraw_rgb_color *colors, int ncolors, const uint16_t *in, size_t in_pitch,
                            size_t in_frame_stride, int width, int height, int n, void *out, size_t out_bytes, void *stream)
 {
@@ -509,19 +675,43 @@ static int demosaic_launch(const char *fn, mcraw_ctx *c, const mcraw_rgb *p, con
         return reject(fn, "in_frame_stride too small for the frames not to overlap");
     if (p->algo != MCRAW_RGB_MHC && p->algo != MCRAW_RGB_BIN2)
         return reject(fn, "unknown algo");
-    if (d) {
+    const uint16_t *lut = d ? d->lut : yv ? yv->lut : nullptr;
+    const uint32_t lut_log2 = d ? d->lut_log2 : yv ? yv->lut_log2 : 0u;
+    if (d || yv) {
         if (p->dtype != 0u || p->flags != 0u)
-            return reject(fn, "p->dtype and p->flags must be 0 (the display stage decides the output)");
+            return reject(fn, "p->dtype and p->flags must be 0 (the display / YUV stage decides the output)");
+        if (lut_log2 < 8u || lut_log2 > 16u)
+            return reject(fn, "lut_log2 must be 8 .. 16");
+        if (!lut || (reinterpret_cast<uintptr_t>(lut) & 15u))
+            return reject(fn, "lut missing or not 16-byte aligned");
+    }
+    if (d) {
         if (d->dtype != MCRAW_DISP_U8 && d->dtype != MCRAW_DISP_U16)
             return reject(fn, "unknown display dtype");
         if (d->layout != MCRAW_DISP_CHW && d->layout != MCRAW_DISP_HWC)
             return reject(fn, "unknown display layout");
         if (d->reserved != 0u)
             return reject(fn, "reserved must be 0");
-        if (d->lut_log2 < 8u || d->lut_log2 > 16u)
-            return reject(fn, "lut_log2 must be 8 .. 16");
-        if (!d->lut || (reinterpret_cast<uintptr_t>(d->lut) & 15u))
-            return reject(fn, "lut missing or not 16-byte aligned");
+    } else if (yv) {
+        if (yv->format != MCRAW_YUV_NV12 && yv->format != MCRAW_YUV_P010)
+            return reject(fn, "unknown YUV format");
+        if (yv->reserved != 0u)
+            return reject(fn, "reserved must be 0");
+        if (yv->in_bits < 8u || yv->in_bits > 16u)
+            return reject(fn, "in_bits must be 8 .. 16");
+        if (yv->sh < 1u || yv->sh > 24u)
+            return reject(fn, "sh must be 1 .. 24");
+        const int32_t top = yv->format == MCRAW_YUV_NV12 ? 255 : 1023;
+        if (yv->y_off < 0 || yv->y_off > top || yv->c_off < 0 || yv->c_off > top)
+            return reject(fn, "y_off and c_off must be 0 .. 2^bits - 1");
+        // no int32 sum can wrap: 4 * (2^in_bits - 1) * (|c0| + |c1| + |c2|) + 2^(sh + 1) < 2^31 for every row
+        const int32_t *rows[3] = {yv->cy, yv->cb, yv->cr};
+        for (const int32_t *r : rows) {
+            const int64_t mag = std::llabs(static_cast<int64_t>(r[0])) + std::llabs(static_cast<int64_t>(r[1])) +
+                                std::llabs(static_cast<int64_t>(r[2]));
+            if (4 * ((int64_t{1} << yv->in_bits) - 1) * mag + (int64_t{1} << (yv->sh + 1u)) >= (int64_t{1} << 31))
+                return reject(fn, "coefficients could overflow int32: 4 * (2^in_bits - 1) * (|c0| + |c1| + |c2|) + 2^(sh + 1) >= 2^31");
+        }
     } else {
         if (p->dtype != MCRAW_FLOAT_F32 && p->dtype != MCRAW_FLOAT_F16 && p->dtype != MCRAW_FLOAT_BF16)
             return reject(fn, "unknown dtype");
@@ -539,11 +729,16 @@ static int demosaic_launch(const char *fn, mcraw_ctx *c, const mcraw_rgb *p, con
         if (!finite_all(colors[i].gain, 3) || !finite_all(colors[i].m, 9))
             return reject(fn, "non-finite gain or matrix entry");
     const bool mhc = p->algo == MCRAW_RGB_MHC;
-    const size_t es = d ? (d->dtype == MCRAW_DISP_U8 ? 1u : 2u) : p->dtype == MCRAW_FLOAT_F32 ? 4u : 2u;
+    const size_t es = d ? (d->dtype == MCRAW_DISP_U8 ? 1u : 2u) : yv ? (yv->format == MCRAW_YUV_NV12 ? 1u : 2u)
+                                                                      : p->dtype == MCRAW_FLOAT_F32 ? 4u : 2u;
     const size_t Wo = mhc ? static_cast<size_t>(width) : static_cast<size_t>(width) / 2u;
     const size_t Ho = mhc ? static_cast<size_t>(height) : static_cast<size_t>(height) / 2u;
-    if (out_bytes / es / 3u / Ho / Wo < static_cast<size_t>(n))
-        return reject(fn, "out_bytes below n * 3 * Ho * Wo * element size");
+    if (yv && ((Ho | Wo) & 1u))
+        return reject(fn, "4:2:0 needs an even Ho and Wo (BIN2: width and height multiples of 4)");
+    // samples per frame: 3 planes, or a Y plane and half of one for the (Cb, Cr) rows
+    const size_t frame_samples = yv ? Ho * Wo / 2u * 3u : 3u * Ho * Wo;
+    if (out_bytes / es / frame_samples < static_cast<size_t>(n))
+        return reject(fn, yv ? "out_bytes below n * Ho * Wo * 3 / 2 * sample size" : "out_bytes below n * 3 * Ho * Wo * element size");
     if (!in || !out || (reinterpret_cast<uintptr_t>(in) & 1u) || (reinterpret_cast<uintptr_t>(out) & (es - 1u)))
         return reject(fn, "in / out missing or not aligned to their element size");
 
@@ -561,7 +756,8 @@ static int demosaic_launch(const char *fn, mcraw_ctx *c, const mcraw_rgb *p, con
     }
     static const int shift_of[4] = {0, 3, 1, 2}; // MCRAW_CFA_* -> role shift: RGGB 0, BGGR 3, GRBG 1, GBRG 2
     const int s = shift_of[p->cfa];
-    RgbKernel k = d ? (d->dtype == MCRAW_DISP_U8 ? pick_kernel<PK_DISP8>(p->algo, s) : pick_kernel<PK_DISP16>(p->algo, s))
+    RgbKernel k = yv ? (yv->format == MCRAW_YUV_NV12 ? pick_yuv_kernel<PK_NV12>(p->algo, s) : pick_yuv_kernel<PK_P010>(p->algo, s))
+                  : d ? (d->dtype == MCRAW_DISP_U8 ? pick_kernel<PK_DISP8>(p->algo, s) : pick_kernel<PK_DISP16>(p->algo, s))
                   : p->dtype == MCRAW_FLOAT_F32 ? pick_kernel<PK_F32>(p->algo, s)
                   : p->dtype == MCRAW_FLOAT_F16 ? pick_kernel<PK_F16>(p->algo, s)
                                                 : pick_kernel<PK_BF16>(p->algo, s);
@@ -575,11 +771,22 @@ static int demosaic_launch(const char *fn, mcraw_ctx *c, const mcraw_rgb *p, con
     A.invec = (reinterpret_cast<uintptr_t>(in) & 15u) == 0u && in_pitch % 8u == 0u && (n == 1 || in_frame_stride % 8u == 0u);
     A.clip = (p->flags & MCRAW_FLOAT_CLIP) ? 1u : 0u;
     A.percol = ncolors > 1 ? 1u : 0u;
-    if (d) {
-        A.lut = d->lut;
-        A.lutn = 1u << d->lut_log2;
+    if (d || yv) {
+        A.lut = lut;
+        A.lutn = 1u << lut_log2;
         A.lutg = A.lutn > DISP_LDS_MAX ? 1u : 0u;
-        A.hwc = d->layout == MCRAW_DISP_HWC ? 1u : 0u;
+        A.hwc = d && d->layout == MCRAW_DISP_HWC ? 1u : 0u;
+    }
+    if (yv) {
+        for (int i = 0; i < 3; i++) {
+            A.ycf[i] = yv->cy[i];
+            A.ycf[3 + i] = yv->cb[i];
+            A.ycf[6 + i] = yv->cr[i];
+        }
+        A.ymask = (1u << yv->in_bits) - 1u;
+        A.ysh = yv->sh;
+        A.yoff = yv->y_off;
+        A.coff = yv->c_off;
     }
     for (int i = 0; i < 4; i++)
         A.black[i] = p->black[i];
@@ -589,13 +796,15 @@ static int demosaic_launch(const char *fn, mcraw_ctx *c, const mcraw_rgb *p, con
         blocks = A.tilesX * static_cast<uint32_t>((height + MHC_TH - 1) / MHC_TH);
     } else {
         A.tilesX = static_cast<uint32_t>((Wo + 7u) / 8u);
-        blocks = static_cast<uint32_t>((static_cast<size_t>(A.tilesX) * Ho + RGB_T - 1u) / RGB_T);
+        // items: 8 output columns of an output row (YUV kinds: of an output row pair)
+        blocks = static_cast<uint32_t>((static_cast<size_t>(A.tilesX) * (yv ? Ho / 2u : Ho) + RGB_T - 1u) / RGB_T);
     }
     A.units = blocks;
-    const uint32_t resident = d ? resident_groups(c->device, k) : 0u;
+    const bool persistent = d || yv;
+    const uint32_t resident = persistent ? resident_groups(c->device, k) : 0u;
     const int kid = mhc ? MCRAW_KRGB_MHC : MCRAW_KRGB_BIN2;
     const int piece = A.percol ? RGB_MAXF : 65535;
-    const size_t out_frame = 3u * Ho * Wo * es;
+    const size_t out_frame = frame_samples * es;
     for (int f0 = 0; f0 < n; f0 += piece) {
         const int nf = std::min(piece, n - f0);
         A.in = in + static_cast<size_t>(f0) * in_frame_stride;
@@ -603,8 +812,8 @@ static int demosaic_launch(const char *fn, mcraw_ctx *c, const mcraw_rgb *p, con
         A.nf = static_cast<uint32_t>(nf);
         for (int i = 0; i < (A.percol ? nf : 1); i++)
             A.col[i] = cols[static_cast<size_t>(A.percol ? f0 + i : 0)];
-        // display kinds: a persistent grid of at most what the device holds at once, over blocks x nf units of work
-        const dim3 grid = d ? dim3(static_cast<uint32_t>(std::min<uint64_t>(static_cast<uint64_t>(blocks) * nf, resident)))
+        // display and YUV kinds: a persistent grid of at most what the device holds at once, over blocks x nf units of work
+        const dim3 grid = persistent ? dim3(static_cast<uint32_t>(std::min<uint64_t>(static_cast<uint64_t>(blocks) * nf, resident)))
                             : dim3(blocks, static_cast<uint32_t>(nf));
         KTimer kt(c, kid, st);
         hipLaunchKernelGGL(k, grid, dim3(RGB_T), 0, st, A);
@@ -623,7 +832,7 @@ int mcraw_demosaic_batch(mcraw_ctx *c, const mcraw_rgb *p, const mcraw_rgb_color
                          size_t in_pitch, size_t in_frame_stride, int width, int height, int n, void *out, size_t out_bytes,
                          void *stream)
 {
-    return demosaic_launch("mcraw_demosaic_batch", c, p, nullptr, colors, ncolors, in, in_pitch, in_frame_stride, width, height,
+    return demosaic_launch("mcraw_demosaic_batch", c, p, nullptr, nullptr, colors, ncolors, in, in_pitch, in_frame_stride, width, height,
                            n, out, out_bytes, stream);
 }
 
@@ -633,7 +842,17 @@ int mcraw_demosaic_display_batch(mcraw_ctx *c, const mcraw_rgb *p, const mcraw_d
 {
     if (!d)
         return reject("mcraw_demosaic_display_batch", "bad arguments");
-    return demosaic_launch("mcraw_demosaic_display_batch", c, p, d, colors, ncolors, in, in_pitch, in_frame_stride, width,
+    return demosaic_launch("mcraw_demosaic_display_batch", c, p, d, nullptr, colors, ncolors, in, in_pitch, in_frame_stride,
+                           width, height, n, out, out_bytes, stream);
+}
+
+int mcraw_demosaic_yuv_batch(mcraw_ctx *c, const mcraw_rgb *p, const mcraw_yuv *y, const mcraw_rgb_color *colors, int ncolors,
+                             const uint16_t *in, size_t in_pitch, size_t in_frame_stride, int width, int height, int n,
+                             void *out, size_t out_bytes, void *stream)
+{
+    if (!y)
+        return reject("mcraw_demosaic_yuv_batch", "bad arguments");
+    return demosaic_launch("mcraw_demosaic_yuv_batch", c, p, nullptr, y, colors, ncolors, in, in_pitch, in_frame_stride, width,
                            height, n, out, out_bytes, stream);
 }
 

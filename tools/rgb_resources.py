@@ -1,0 +1,65 @@
+#!/usr/bin/env python3
+"""Resource report of the demosaic kernels (csrc/mcraw_rgb.hip): compiles the file for gfx950 with
+-Rpass-analysis=kernel-resource-usage (no GPU needed) and prints one line per instance in the format of
+profiles/rgb_resources.txt / display_resources.txt / yuv_resources.txt.
+
+    python tools/rgb_resources.py            # every instance
+    python tools/rgb_resources.py --check    # the figures in the three committed files must equal the compiler's; exit 1 if not
+"""
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from motioncam_decoder_amd import build as B
+
+KINDS = {32: "f32", 33: "f16", 34: "bf16", 48: "u8", 49: "u16", 50: "nv12", 51: "p010"}
+FILES = ("rgb_resources.txt", "display_resources.txt", "yuv_resources.txt")
+
+
+def report():
+    src = os.path.join(B.CSRC, "mcraw_rgb.hip")
+    with tempfile.TemporaryDirectory() as d:
+        cmd = [B.HIPCC] + B.HIP_FLAGS + ["--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c", "-o",
+                                         os.path.join(d, "x.o"), src]
+        err = subprocess.run(cmd, check=True, stderr=subprocess.PIPE, text=True).stderr
+    rows, cur = {}, None
+    for line in err.splitlines():
+        m = re.search(r"Function Name: _ZN5mcraw\d+(krgb_mhc|krgb_bin2)y?ILi(\d+)ELi(\d)EEEv", line)
+        if m:
+            cur = "%s<%s,S=%s>" % (m.group(1), KINDS[int(m.group(2))], m.group(3))
+            rows[cur] = {}
+            continue
+        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
+        if m and cur:
+            rows[cur][m.group(1).strip()] = int(m.group(2))
+    out = {}
+    for k, v in rows.items():
+        out[k] = "%-24s %6d %5d %8d %12d %7d" % (k, v["VGPRs"], v["TotalSGPRs"], v["ScratchSize"], v["Occupancy"], v["LDS Size"])
+    return out
+
+
+def main():
+    rep = report()
+    if "--check" not in sys.argv:
+        for line in rep.values():
+            print(line)
+        return 0
+    bad, seen = 0, 0
+    for f in FILES:
+        for line in open(os.path.join(ROOT, "profiles", f)) if os.path.exists(os.path.join(ROOT, "profiles", f)) else ():
+            if not line.startswith("krgb_"):
+                continue
+            seen += 1
+            if rep.get(line.split()[0], "").split() != line.split():  # (the files differ in column spacing)
+                bad += 1
+                print("%s: committed  %s\n%s  compiler   %s" % (f, line.rstrip("\n"), " " * len(f), rep.get(line.split()[0])))
+    print("%d committed lines, %d differ, %d instances compiled" % (seen, bad, len(rep)))
+    return 1 if bad or seen != len(rep) else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
