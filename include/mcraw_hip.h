@@ -448,6 +448,49 @@ int mcraw_demosaic_yuv_batch(mcraw_ctx *ctx, const mcraw_rgb *p, const mcraw_yuv
                              int ncolors, const uint16_t *in, size_t in_pitch, size_t in_frame_stride, int width,
                              int height, int n, void *out, size_t out_bytes, void *stream);
 
+/* ---- uint16 mosaics -> uint16 mosaics with a lens-shading gain map applied ----------------------------------------
+ *
+ * Multiplies what `n` uint16 mosaics of width x height hold above their black level by a per-pixel gain that is bilinearly
+ * interpolated from a small map, and writes mosaics of the same black level: the stage in front of a demosaic that takes
+ * the vignetting and its colour cast out (Android's LensShadingMap, a DNG GainMap opcode).  Pitches and frame strides count
+ * uint16 elements.  A map has four planes of map_h x map_w uint16 entries in Q3.12 (4096 is a gain of 1.0), indexed by CFA
+ * position p = (y & 1) * 2 + (x & 1) like black[4] (the call never needs the CFA).  Bit 15 of an entry is ignored:
+ * g = entry & 0x7FFF, so gains stay below 8 and no map content can make a sum wrap.  Map point (j, i) sits on pixel
+ * (j * (H - 1) / (map_h - 1), i * (W - 1) / (map_w - 1)): the corner points sit on the corner pixels.  Bit-exact, in integers:
+ *   host:   sx = W > 1 ? floor((map_w - 1) * 2^24 / (W - 1)) : 0        sy likewise from map_h, H
+ *   pixel:  ux = x * sx;  i0 = ux >> 24;  fx = (ux >> 12) & 4095;  i1 = min(i0 + 1, map_w - 1)
+ *           uy = y * sy;  j0 = uy >> 24;  fy = (uy >> 12) & 4095;  j1 = min(j0 + 1, map_h - 1)
+ *           V0 = (g[p][j0][i0] * (4096 - fy) + g[p][j1][i0] * fy + 2048) >> 12        vertical first
+ *           V1 = (g[p][j0][i1] * (4096 - fy) + g[p][j1][i1] * fy + 2048) >> 12
+ *           G  = (V0 * (4096 - fx) + V1 * fx + 2048) >> 12                            0 <= G <= 32767
+ *           d  = (int)s - (int)black[p]
+ *           c  = black[p] + ((d * G + 2048) >> 12)                                   arithmetic shift: floor
+ *           out = (uint16) min(max(c, 0), top)
+ * The order is fixed, vertical then horizontal, because each stage rounds.  map_w, map_h <= 64 gives ux < 2^30;
+ * |d * G| + 2048 <= 65535 * 32767 + 2048 < 2^31; every factor fits in 24 bits.  An all-4096 map returns the input (below
+ * `top`) bit for bit.
+ * The map is the caller's DEVICE memory, read by the queued kernel in stream order and never copied into or cached by the
+ * context: two calls with the same pointer and new contents in between each see their own.  nmaps == 1 applies one map to
+ * every frame, nmaps == n gives one per frame, back to back.
+ * In place is allowed: out == in with the same pitch and (n > 1) the same frame stride; each pixel reads only itself.
+ * `stream`: a hipStream_t, NULL = the context's own stream; the call queues the work and returns without synchronising.
+ * It takes no decode serial and leaves the decode slots, mcraw_ctx_errors, mcraw_ctx_last_serial and the context's stage
+ * alone.  n == 0 is a no-op.  The launch has no id in mcraw_ctx_kernel_ms (time it with stream events).
+ * Rejected (returns < 0, mcraw_last_error says why, nothing is written): a NULL `s`, `in`, `out` or `map`; an odd `in` or
+ * `out` address; a `map` that is not 16-byte aligned; width or height outside 1 .. 65536 (odd sizes are fine); a pitch
+ * below width; n > 1 and a frame stride below (height - 1) * pitch + width; map_w or map_h outside 1 .. 64; nmaps not 1 or
+ * n; top outside 1 .. 65535; a non-zero `reserved`; input and output extents that overlap other than in place. */
+typedef struct mcraw_shade {
+    uint32_t map_w, map_h;   /* 1 .. 64 each                                                  */
+    uint32_t nmaps;          /* 1: one map for the batch; n: one per frame, back to back      */
+    uint32_t top;            /* 1 .. 65535: the output saturates here                         */
+    uint16_t black[4];       /* by CFA position                                               */
+    uint32_t reserved[2];    /* must be 0                                                     */
+    const uint16_t *map;     /* DEVICE memory, 16-byte aligned: (nmaps, 4, map_h, map_w)      */
+} mcraw_shade;               /* sizeof 40; black 16, reserved 24, map 32                      */
+int mcraw_shade_batch(mcraw_ctx *ctx, const mcraw_shade *s, const uint16_t *in, size_t in_pitch, size_t in_frame_stride,
+                      int width, int height, int n, uint16_t *out, size_t out_pitch, size_t out_frame_stride, void *stream);
+
 /* ---- environment ------------------------------------------------------------------------------
  * Read when a context (or pool) is created, never afterwards:
  *   MCRAW_DEVICE=n, MCRAW_DEVICES=all|0,1,5   default device of the five-argument entry points / members of a default pool

@@ -15,7 +15,8 @@ import os
 __all__ = ["lib_path", "load", "Context", "Pool", "Frame", "EncFrame", "FloatOut", "McrawError", "TYPE_LEGACY", "TYPE_BLOCK",
            "MEM_DEVICE", "MEM_HOST", "KERNELS", "ENC_KERNELS", "ABI_SYMBOLS", "encode_bound7", "cfa_planes",
            "RgbParams", "RgbColor", "RGB_KERNELS", "rgb_color", "Display", "transfer_lut", "DISP_U8", "DISP_U16",
-           "DISP_CHW", "DISP_HWC", "Yuv", "YUV_NV12", "YUV_P010", "yuv_matrix", "yuv_planes"]
+           "DISP_CHW", "DISP_HWC", "Yuv", "YUV_NV12", "YUV_P010", "yuv_matrix", "yuv_planes", "Shade", "gain_map",
+           "shading_map"]
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 
@@ -42,7 +43,7 @@ ABI_SYMBOLS = [
     "mcraw_pool_decode_batch_device", "mcraw_ctx_xcd_runs", "mcraw_pool_synchronize", "mcraw_tile_order",
     "mcraw_ctx_last_serial", "mcraw_ctx_batch_status", "mcraw_ctx_errors", "mcraw_ctx_side_parts", "mcraw_ctx_host_way",
     "mcraw_encode_bound7", "mcraw_encode_batch", "mcraw_encode7", "mcraw_ctx_set_float_out", "mcraw_pool_set_float_out",
-    "mcraw_demosaic_batch", "mcraw_demosaic_display_batch", "mcraw_demosaic_yuv_batch",
+    "mcraw_demosaic_batch", "mcraw_demosaic_display_batch", "mcraw_demosaic_yuv_batch", "mcraw_shade_batch",
 ]
 
 POST_BLACK, POST_PACK12, POST_PACK10, POST_PACK14 = 1, 2, 4, 8
@@ -158,6 +159,69 @@ class Yuv(C.Structure):
     _fields_ = [("format", C.c_uint32), ("lut_log2", C.c_uint32), ("in_bits", C.c_uint32), ("sh", C.c_uint32),
                 ("y_off", C.c_int32), ("c_off", C.c_int32), ("cy", C.c_int32 * 3), ("cb", C.c_int32 * 3),
                 ("cr", C.c_int32 * 3), ("reserved", C.c_uint32), ("lut", C.c_void_p)]
+
+
+# lens-shading gain maps on mosaics (mcraw_shade_batch)
+class Shade(C.Structure):
+    """struct mcraw_shade (include/mcraw_hip.h): the device gain map (nmaps, 4, map_h, map_w) in Q3.12 by CFA position, the
+    black levels the gain pivots on and the level the output saturates at."""
+    _fields_ = [("map_w", C.c_uint32), ("map_h", C.c_uint32), ("nmaps", C.c_uint32), ("top", C.c_uint32),
+                ("black", C.c_uint16 * 4), ("reserved", C.c_uint32 * 2), ("map", C.c_void_p)]
+
+
+def gain_map(gains, cfa="rggb", order="rggb"):
+    """The uint16 Q3.12 gain map of Context.shade / shading= from float gains (4, gh, gw) or (N, 4, gh, gw): entries
+    rint(g * 4096), planes in CFA-position order p = (y & 1) * 2 + (x & 1) for the sensor arrangement `cfa`.  order "rggb":
+    the planes of `gains` are R, G (red row), G (blue row), B and are permuted as cfa_planes(cfa) says; order "cfa": they are
+    in CFA-position order already.  Raises ValueError on a non-finite or negative gain, or one that rounds above 32767
+    (gains stay below 8)."""
+    import numpy as np
+    perm = cfa_planes(cfa)
+    if order not in ("rggb", "cfa"):
+        raise ValueError("order must be 'rggb' or 'cfa', not %r" % (order,))
+    g = np.asarray(gains, dtype=np.float64)
+    if g.ndim not in (3, 4) or g.shape[-3] != 4 or g.shape[-1] < 1 or g.shape[-2] < 1:
+        raise ValueError("gain_map: gains must be (4, gh, gw) or (N, 4, gh, gw), not %r" % (g.shape,))
+    if not np.all(np.isfinite(g)):
+        raise ValueError("gain_map: non-finite gain")
+    if np.any(g < 0):
+        raise ValueError("gain_map: negative gain")
+    q = np.rint(g * 4096.0)
+    if np.any(q > 32767):
+        raise ValueError("gain_map: a gain rounds above 32767 / 4096 (gains must stay below 8)")
+    if order == "rggb":
+        q = q[..., perm, :, :]
+    return np.ascontiguousarray(q.astype(np.uint16))
+
+
+def shading_map(frame_meta, cfa="rggb"):
+    """The gain map (gain_map) of a frame's metadata, or None when it carries none: reads `lensShadingMap` -- four planes in
+    Android's LensShadingMap order [R, G_even, G_odd, B], taken as R, G (red row), G (blue row), B, each a flat list of
+    lensShadingMapHeight * lensShadingMapWidth gains in row-major order or a list of rows -- with `lensShadingMapWidth` /
+    `lensShadingMapHeight`.
+    UNVERIFIED: the key names and the layout are written from memory of the recorder's files; the reference reads none of
+    these keys and no real clip was at hand.  All of the parsing is in this function: a clip that differs needs a change
+    here only (or build the map with gain_map)."""
+    import numpy as np
+    if frame_meta is None or frame_meta.get("lensShadingMap") is None:
+        return None
+    planes = frame_meta["lensShadingMap"]
+    if len(planes) != 4:
+        raise ValueError("lensShadingMap must hold four planes, not %d" % len(planes))
+    gw, gh = frame_meta.get("lensShadingMapWidth"), frame_meta.get("lensShadingMapHeight")
+    out = []
+    for pl in planes:
+        a = np.asarray(pl, dtype=np.float64)
+        if a.ndim == 1:
+            if gw is None or gh is None or int(gw) * int(gh) != a.size:
+                raise ValueError("lensShadingMap: a flat plane needs lensShadingMapWidth * lensShadingMapHeight == its length")
+            a = a.reshape(int(gh), int(gw))
+        elif a.ndim != 2 or (gw is not None and int(gw) != a.shape[1]) or (gh is not None and int(gh) != a.shape[0]):
+            raise ValueError("lensShadingMap: a plane must be a flat list or lensShadingMapHeight rows of lensShadingMapWidth gains")
+        out.append(a)
+    if any(a.shape != out[0].shape for a in out):
+        raise ValueError("lensShadingMap: the four planes differ in size")
+    return gain_map(np.stack(out), cfa)
 
 
 def _yuv_rule_ok(rows, sh, in_bits):
@@ -477,6 +541,9 @@ def load():
     lib.mcraw_demosaic_yuv_batch.argtypes = [C.c_void_p, C.POINTER(RgbParams), C.POINTER(Yuv), C.POINTER(RgbColor), C.c_int,
                                              C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                              C.c_size_t, C.c_void_p]
+    lib.mcraw_shade_batch.restype = C.c_int
+    lib.mcraw_shade_batch.argtypes = [C.c_void_p, C.POINTER(Shade), C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int,
+                                      C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
     lib.mcraw_encode7.restype = C.c_size_t
     lib.mcraw_encode7.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int]
     _lib = lib
@@ -845,8 +912,76 @@ class Context:
         self._side.wait_stream(cur)
         return cur, self._side
 
+    def _shading_tensor(self, torch, dev, shading, n, fn):
+        """The device gain map of `shading` (a CUDA uint16 tensor, or a host array from gain_map, uploaded on the current
+        stream) as (tensor, maps, gh, gw)."""
+        import numpy as np
+        if isinstance(shading, np.ndarray):
+            if shading.dtype != np.uint16:
+                raise ValueError("%s: a shading array must be uint16 (gain_map makes one)" % fn)
+            shading = torch.from_numpy(np.ascontiguousarray(shading).view(np.int16)).to(dev).view(torch.uint16)
+        if not isinstance(shading, torch.Tensor) or shading.dtype != torch.uint16 or shading.device != dev \
+                or shading.dim() not in (3, 4) or not shading.is_contiguous():
+            raise ValueError("%s: shading must be a contiguous uint16 tensor (4, gh, gw) or (N, 4, gh, gw) on %s" % (fn, dev))
+        maps = int(shading.shape[0]) if shading.dim() == 4 else 1
+        if int(shading.shape[-3]) != 4 or maps not in (1, n):
+            raise ValueError("%s: shading must hold four planes, for all frames or for each of the %d" % (fn, n))
+        return shading, maps, int(shading.shape[-2]), int(shading.shape[-1])
+
+    def shade(self, mosaic, shading, *, black=(0, 0, 0, 0), top=65535, out=None):
+        """Apply a lens-shading gain map to uint16 mosaics resident on the context's device (mcraw_shade_batch): what a
+        sample holds above its black level is multiplied by the gain that the map gives for its place, bilinearly
+        interpolated per CFA position in integers, and the result saturates at `top`; the black level of the output is the
+        black level of the input, so everything that takes a mosaic takes the result with the parameters it would take
+        anyway.  mosaic: (N, H, W) or (H, W), rows contiguous (rows and frames may be strided), odd sizes are fine.
+        shading: a uint16 Q3.12 map (4, gh, gw) for all frames or (N, 4, gh, gw) per frame, gh, gw <= 64, planes by CFA
+        position (gain_map / shading_map make one): a CUDA tensor, read when the kernel runs (in stream order), or a host
+        array, uploaded on the current stream.  out: None (a new contiguous tensor), a uint16 tensor of the mosaic's
+        shape, or the mosaic itself (in place).  Queued on torch.cuda.current_stream(); nothing synchronises."""
+        import torch
+        dev = self._torch_device(torch)
+        if not isinstance(mosaic, torch.Tensor) or mosaic.dtype != torch.uint16 or mosaic.device != dev or mosaic.dim() not in (2, 3):
+            raise ValueError("shade: mosaic must be a uint16 tensor (N, H, W) or (H, W) on %s" % dev)
+        if out is None:
+            out = torch.empty(tuple(mosaic.shape), dtype=torch.uint16, device=dev)
+        elif not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(mosaic.shape) or out.dtype != torch.uint16 or out.device != dev:
+            raise ValueError("shade: out must be a uint16 tensor of shape %s on %s" % (tuple(mosaic.shape), dev))
+        mos, dst = (mosaic.unsqueeze(0), out.unsqueeze(0)) if mosaic.dim() == 2 else (mosaic, out)
+        n, h, w = (int(v) for v in mos.shape)
+        if n == 0 or h == 0 or w == 0:
+            return out
+        if w > 1 and (mos.stride(2) != 1 or dst.stride(2) != 1):
+            raise ValueError("shade: the rows of the mosaic and of out must be contiguous")
+        shading, maps, gh, gw = self._shading_tensor(torch, dev, shading, n, "shade")
+        black = list(black)
+        if len(black) != 4:
+            raise ValueError("black: four levels, by CFA position (row & 1) * 2 + (col & 1)")
+        s = Shade()
+        s.map_w, s.map_h, s.nmaps, s.top = gw, gh, maps, int(top)
+        for i in range(4):
+            s.black[i] = int(black[i])
+        s.reserved[0] = s.reserved[1] = 0
+        s.map = shading.data_ptr()
+        ip = int(mos.stride(1)) if h > 1 else w
+        op = int(dst.stride(1)) if h > 1 else w
+        ifs = int(mos.stride(0)) if n > 1 else ip * h
+        ofs = int(dst.stride(0)) if n > 1 else op * h
+        cur, run = self._run_stream(torch, dev)
+        try:
+            rc = self._lib.mcraw_shade_batch(self._h, C.byref(s), C.c_void_p(mos.data_ptr()), ip, ifs, w, h, n,
+                                             C.c_void_p(dst.data_ptr()), op, ofs, C.c_void_p(run.cuda_stream))
+        finally:
+            if run is not cur:
+                mos.record_stream(run)
+                dst.record_stream(run)
+                shading.record_stream(run)
+                cur.wait_stream(run)
+        if rc != 0:
+            raise McrawError("mcraw_shade_batch failed (%d): %s" % (rc, self._lib.mcraw_last_error().decode()))
+        return out
+
     def demosaic(self, mosaic, *, algo="mhc", dtype, white, black=(0, 0, 0, 0), cfa="rggb", gain=None, matrix=None,
-                 clip=False, out=None, check=True):
+                 clip=False, out=None, check=True, shading=None):
         """uint16 mosaics resident on the context's device -> planar linear RGB, (N, 3, H, W) for algo "mhc" (Malvar-He-
         Cutler) or (N, 3, H/2, W/2) for "bin2" (one pixel per 2x2 quad), as torch.float32 / float16 / bfloat16 ("f32" /
         "f16" / "bf16").  mosaic: a CUDA uint16 tensor (N, H, W) or (H, W) whose rows are contiguous (rows and frames may
@@ -854,7 +989,9 @@ class Context:
         (x & 1); cfa: the container's sensorArrangment; gain (3,) or (N, 3) and matrix (3, 3) or (N, 3, 3): white balance
         and colour matrix for all frames or per frame (rgb_color gives them); clip: clamp to [0, 1].  Queued on
         torch.cuda.current_stream(); nothing synchronises.  `check` is accepted for symmetry with decode_rgb (the
-        arguments are always checked; there are no per-frame statuses)."""
+        arguments are always checked; there are no per-frame statuses).  shading: a lens-shading gain map as shade() takes
+        it, applied in front of the demosaic with this call's black levels and top 65535, into a scratch tensor (the
+        caller's mosaic is left as it is); None: no such stage."""
         import torch
         if algo not in _RGB_ALGOS:
             raise ValueError("algo must be 'mhc' or 'bin2', not %r" % (algo,))
@@ -868,6 +1005,8 @@ class Context:
             raise ValueError("demosaic: mosaic must be a uint16 tensor (N, H, W) or (H, W) on %s" % dev)
         single = mosaic.dim() == 2
         mos = mosaic.unsqueeze(0) if single else mosaic
+        if shading is not None and mos.numel():  # into a scratch tensor: the caller's mosaic stays as it is
+            mos = self.shade(mos, shading, black=black)
         n, h, w = (int(v) for v in mos.shape)
         if n and h > 1 and mos.stride(2) != 1:
             raise ValueError("demosaic: the rows of the mosaic must be contiguous")
@@ -933,13 +1072,16 @@ class Context:
         return scratch
 
     def decode_rgb(self, inputs, width, height, type, *, algo="mhc", dtype, white, black=(0, 0, 0, 0), cfa="rggb",
-                   gain=None, matrix=None, clip=False, out=None, check=True):
+                   gain=None, matrix=None, clip=False, out=None, check=True, shading=None):
         """Decode frames of one geometry that are resident in HBM and demosaic them (demosaic()): (N, 3, H, W) for "mhc",
         (N, 3, H/2, W/2) for "bin2".  inputs: uint8 CUDA tensors, or (device pointer, length) pairs.  The plain uint16
         mosaics go to a scratch tensor of torch's caching allocator; both steps are queued on torch.cuda.current_stream().
         check=True synchronises after the decode and raises McrawError naming the frames that failed; check=False returns
-        at once.  The stage the context had before the call is restored afterwards."""
+        at once.  The stage the context had before the call is restored afterwards.  shading: a lens-shading gain map
+        (shade()), applied to the scratch mosaics in place before the demosaic."""
         scratch = self._decode_scratch(inputs, width, height, type, check, "decode_rgb")
+        if shading is not None:
+            self.shade(scratch, shading, black=black, out=scratch)
         return self.demosaic(scratch, algo=algo, dtype=dtype, white=white, black=black, cfa=cfa, gain=gain, matrix=matrix,
                              clip=clip, out=out, check=check)
 
@@ -973,7 +1115,7 @@ class Context:
         return lut, own
 
     def demosaic_display(self, mosaic, *, algo="mhc", white, black=(0, 0, 0, 0), cfa="rggb", gain=None, matrix=None,
-                         transfer="srgb", lut_size=4096, dtype=None, layout="hwc", bits=None, out=None, check=True):
+                         transfer="srgb", lut_size=4096, dtype=None, layout="hwc", bits=None, out=None, check=True, shading=None):
         """uint16 mosaics resident on the context's device -> display-ready integer RGB: the demosaic and colours of
         demosaic(), then clamp to [0, 1], index a transfer-curve LUT of L entries at rint(c * (L - 1)) and store the entry
         (its low byte for uint8).  dtype: torch.uint8 (default) or torch.uint16; layout "hwc" gives (N, Ho, Wo, 3), "chw"
@@ -981,7 +1123,7 @@ class Context:
         on [0, 1] -- built by transfer_lut(transfer, lut_size, bits), bits 8 for uint8 and 16 for uint16 unless given --
         or a ready 1-D uint16 LUT (host array or CUDA tensor) whose length is a power of two, 256 .. 65536.  Queued on
         torch.cuda.current_stream(); nothing synchronises, and a caller's LUT is read when the kernels run (in stream
-        order).  `check` is accepted for symmetry with decode_display."""
+        order).  `check` is accepted for symmetry with decode_display.  shading: as demosaic()."""
         import torch
         if algo not in _RGB_ALGOS:
             raise ValueError("algo must be 'mhc' or 'bin2', not %r" % (algo,))
@@ -1000,6 +1142,8 @@ class Context:
             raise ValueError("demosaic_display: mosaic must be a uint16 tensor (N, H, W) or (H, W) on %s" % dev)
         single = mosaic.dim() == 2
         mos = mosaic.unsqueeze(0) if single else mosaic
+        if shading is not None and mos.numel():  # into a scratch tensor: the caller's mosaic stays as it is
+            mos = self.shade(mos, shading, black=black)
         n, h, w = (int(v) for v in mos.shape)
         if n and h > 1 and mos.stride(2) != 1:
             raise ValueError("demosaic_display: the rows of the mosaic must be contiguous")
@@ -1037,18 +1181,20 @@ class Context:
         return out
 
     def decode_display(self, inputs, width, height, type, *, algo="mhc", white, black=(0, 0, 0, 0), cfa="rggb", gain=None,
-                       matrix=None, transfer="srgb", lut_size=4096, dtype=None, layout="hwc", bits=None, out=None, check=True):
+                       matrix=None, transfer="srgb", lut_size=4096, dtype=None, layout="hwc", bits=None, out=None, check=True, shading=None):
         """Decode frames of one geometry that are resident in HBM and turn them into display-ready RGB
         (demosaic_display()), as decode_rgb does: the plain uint16 mosaics go to a scratch tensor, both steps are queued on
         torch.cuda.current_stream(), check=True synchronises after the decode and raises McrawError naming the frames that
-        failed, and the context's stage is restored afterwards."""
+        failed, and the context's stage is restored afterwards.  shading: as decode_rgb()."""
         scratch = self._decode_scratch(inputs, width, height, type, check, "decode_display")
+        if shading is not None:
+            self.shade(scratch, shading, black=black, out=scratch)
         return self.demosaic_display(scratch, algo=algo, white=white, black=black, cfa=cfa, gain=gain, matrix=matrix,
                                      transfer=transfer, lut_size=lut_size, dtype=dtype, layout=layout, bits=bits, out=out,
                                      check=check)
 
     def demosaic_yuv(self, mosaic, *, algo="mhc", white, black=(0, 0, 0, 0), cfa="rggb", gain=None, matrix=None, fmt="nv12",
-                     standard="bt709", range="limited", transfer="bt709", lut_size=4096, in_bits=None, out=None, check=True):
+                     standard="bt709", range="limited", transfer="bt709", lut_size=4096, in_bits=None, out=None, check=True, shading=None):
         """uint16 mosaics resident on the context's device -> video-ready Y'CbCr 4:2:0: the demosaic, colours, clamp and
         transfer-curve LUT of demosaic_display(), then the integer matrix of yuv_matrix(standard, range) and a 2x2 box
         average for the chroma (sited at the block's centre).  fmt "nv12": torch.uint8; "p010": torch.uint16 holding
@@ -1057,7 +1203,7 @@ class Context:
         gives the two as views.  Ho and Wo must be even (bin2: H and W multiples of 4).  transfer: as demosaic_display; a
         built-in curve is transfer_lut(transfer, lut_size, in_bits), in_bits defaulting to 12 (nv12) or 16 (p010); a ready
         LUT may hold entries of any in_bits 8 .. 16 (higher bits are masked off).  Queued on torch.cuda.current_stream();
-        nothing synchronises.  `check` is accepted for symmetry with decode_yuv."""
+        nothing synchronises.  `check` is accepted for symmetry with decode_yuv.  shading: as demosaic()."""
         import torch
         if algo not in _RGB_ALGOS:
             raise ValueError("algo must be 'mhc' or 'bin2', not %r" % (algo,))
@@ -1075,6 +1221,8 @@ class Context:
             raise ValueError("demosaic_yuv: mosaic must be a uint16 tensor (N, H, W) or (H, W) on %s" % dev)
         single = mosaic.dim() == 2
         mos = mosaic.unsqueeze(0) if single else mosaic
+        if shading is not None and mos.numel():  # into a scratch tensor: the caller's mosaic stays as it is
+            mos = self.shade(mos, shading, black=black)
         n, h, w = (int(v) for v in mos.shape)
         if n and h > 1 and mos.stride(2) != 1:
             raise ValueError("demosaic_yuv: the rows of the mosaic must be contiguous")
@@ -1116,12 +1264,14 @@ class Context:
 
     def decode_yuv(self, inputs, width, height, type, *, algo="mhc", white, black=(0, 0, 0, 0), cfa="rggb", gain=None,
                    matrix=None, fmt="nv12", standard="bt709", range="limited", transfer="bt709", lut_size=4096, in_bits=None,
-                   out=None, check=True):
+                   out=None, check=True, shading=None):
         """Decode frames of one geometry that are resident in HBM and turn them into NV12 / P010 (demosaic_yuv()), as
         decode_display does: the plain uint16 mosaics go to a scratch tensor, both steps are queued on
         torch.cuda.current_stream(), check=True synchronises after the decode and raises McrawError naming the frames that
-        failed, and the context's stage is restored afterwards."""
+        failed, and the context's stage is restored afterwards.  shading: as decode_rgb()."""
         scratch = self._decode_scratch(inputs, width, height, type, check, "decode_yuv")
+        if shading is not None:
+            self.shade(scratch, shading, black=black, out=scratch)
         return self.demosaic_yuv(scratch, algo=algo, white=white, black=black, cfa=cfa, gain=gain, matrix=matrix, fmt=fmt,
                                  standard=standard, range=range, transfer=transfer, lut_size=lut_size, in_bits=in_bits, out=out,
                                  check=check)

@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
-"""Resource report of the demosaic kernels (csrc/mcraw_rgb.hip): compiles the file for gfx950 with
--Rpass-analysis=kernel-resource-usage (no GPU needed) and prints one line per instance in the format of
-profiles/rgb_resources.txt / display_resources.txt / yuv_resources.txt.
+"""Resource report of the demosaic kernels (csrc/mcraw_rgb.hip) and of the lens-shading kernel (csrc/mcraw_shade.hip):
+compiles the files for gfx950 with -Rpass-analysis=kernel-resource-usage (no GPU needed) and prints one line per instance in
+the format of profiles/rgb_resources.txt / display_resources.txt / yuv_resources.txt / shade_resources.txt.
 
     python tools/rgb_resources.py            # every instance
-    python tools/rgb_resources.py --check    # the figures in the three committed files must equal the compiler's; exit 1 if not
+    python tools/rgb_resources.py --check    # the figures in the four committed files must equal the compiler's; exit 1 if not
 """
 import os
 import re
@@ -18,19 +18,28 @@ from motioncam_decoder_amd import build as B
 
 KINDS = {32: "f32", 33: "f16", 34: "bf16", 48: "u8", 49: "u16", 50: "nv12", 51: "p010"}
 FILES = ("rgb_resources.txt", "display_resources.txt", "yuv_resources.txt")
+SHADE_FILE = "shade_resources.txt"
+RGB_NAME = r"Function Name: _ZN5mcraw\d+(krgb_mhc|krgb_bin2)y?ILi(\d+)ELi(\d)EEEv"
+SHADE_NAME = r"Function Name: _ZN5mcraw\d+(kshade)ILb([01])EEEv"  # kshade<NT>: `sc1 nt` streaming stores or plain ones
 
 
-def report():
-    src = os.path.join(B.CSRC, "mcraw_rgb.hip")
+def _label(m):
+    if m.group(1) == "kshade":
+        return "kshade<%s>" % ("stream" if m.group(2) == "1" else "plain")
+    return "%s<%s,S=%s>" % (m.group(1), KINDS[int(m.group(2))], m.group(3))
+
+
+def report(source="mcraw_rgb.hip", name=RGB_NAME):
+    src = os.path.join(B.CSRC, source)
     with tempfile.TemporaryDirectory() as d:
         cmd = [B.HIPCC] + B.HIP_FLAGS + ["--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c", "-o",
                                          os.path.join(d, "x.o"), src]
         err = subprocess.run(cmd, check=True, stderr=subprocess.PIPE, text=True).stderr
     rows, cur = {}, None
     for line in err.splitlines():
-        m = re.search(r"Function Name: _ZN5mcraw\d+(krgb_mhc|krgb_bin2)y?ILi(\d+)ELi(\d)EEEv", line)
+        m = re.search(name, line)
         if m:
-            cur = "%s<%s,S=%s>" % (m.group(1), KINDS[int(m.group(2))], m.group(3))
+            cur = _label(m)
             rows[cur] = {}
             continue
         m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
@@ -42,16 +51,11 @@ def report():
     return out
 
 
-def main():
-    rep = report()
-    if "--check" not in sys.argv:
-        for line in rep.values():
-            print(line)
-        return 0
+def _check(files, rep, prefix):
     bad, seen = 0, 0
-    for f in FILES:
+    for f in files:
         for line in open(os.path.join(ROOT, "profiles", f)) if os.path.exists(os.path.join(ROOT, "profiles", f)) else ():
-            if not line.startswith("krgb_"):
+            if not line.startswith(prefix):
                 continue
             seen += 1
             if rep.get(line.split()[0], "").split() != line.split():  # (the files differ in column spacing)
@@ -59,6 +63,15 @@ def main():
                 print("%s: committed  %s\n%s  compiler   %s" % (f, line.rstrip("\n"), " " * len(f), rep.get(line.split()[0])))
     print("%d committed lines, %d differ, %d instances compiled" % (seen, bad, len(rep)))
     return 1 if bad or seen != len(rep) else 0
+
+
+def main():
+    rep, shade = report(), report("mcraw_shade.hip", SHADE_NAME)
+    if "--check" not in sys.argv:
+        for line in list(rep.values()) + list(shade.values()):
+            print(line)
+        return 0
+    return _check(FILES, rep, "krgb_") | _check((SHADE_FILE,), shade, "kshade")
 
 
 if __name__ == "__main__":
