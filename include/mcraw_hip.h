@@ -491,6 +491,51 @@ typedef struct mcraw_shade {
 int mcraw_shade_batch(mcraw_ctx *ctx, const mcraw_shade *s, const uint16_t *in, size_t in_pitch, size_t in_frame_stride,
                       int width, int height, int n, uint16_t *out, size_t out_pitch, size_t out_frame_stride, void *stream);
 
+/* ---- uint16 mosaics -> per-frame statistics by CFA position ----------------------------------------------------------
+ *
+ * Counts what `n` uint16 mosaics of width x height hold inside one window, per frame and per CFA position
+ * p = (y & 1) * 2 + (x & 1): what measures the `white`, `black` and `gain` the other stages take, a clip's exposure, its
+ * clipping.  Pitches and frame strides count uint16 elements.  Everything is an integer, so the result does not depend on
+ * the order of the additions: it is bit-exact.  With B = 1 << bins_log2, for frame f and every pixel (y, x) with
+ * y0 <= y < y0 + h and x0 <= x < x0 + w (frame coordinates: a window at an odd offset keeps the frame's CFA positions),
+ * v = in[f * in_frame_stride + y * in_pitch + x]:
+ *   hist[p][min(v >> shift, B - 1)] += 1            the last bin takes everything above it
+ *   cnt[p]  += 1
+ *   nsat[p] += 1          if v >= sat[p]             (sat[p] = 0: every sample is saturated)
+ *   sum[p]  += v          otherwise                  the unsaturated samples only
+ *   min[p] = min(min[p], v),  max[p] = max(max[p], v)    over all samples of the window, saturated ones included
+ * A CFA position without a sample in the window (a window one pixel wide or high) keeps min = 65535 and max = 0.
+ * The record of one frame, records back to back in `out` (8-byte aligned):
+ *   uint32 hist[4][B];  uint32 cnt[4], nsat[4], min[4], max[4];  uint64 sum[4]        16 * B + 96 bytes
+ * With width, height <= 65536 a CFA position has at most 2^30 samples: no uint32 counter can wrap, and sum < 2^46.
+ * Without MCRAW_STATS_ACCUMULATE the call initialises the n records itself, on the stream (the caller never clears `out`;
+ * a second call into the same `out` gives the same bytes).  With it the call adds to the records that are there and takes
+ * min / max against them: a clip's histogram over several batches, a frame's over several windows.  The uint32 counters
+ * then wrap modulo 2^32 (sum modulo 2^64) once the caller's total passes them.
+ * `in` may sit at any 2-byte alignment with any pitch (16-byte loads where base, pitch and stride allow it).  Only the
+ * window's samples are read.
+ * `stream`: a hipStream_t, NULL = the context's own stream; the call queues the work and returns without synchronising.
+ * It takes no decode serial and leaves the decode slots, mcraw_ctx_errors, mcraw_ctx_last_serial and the context's stage
+ * alone.  n == 0 is a no-op; n may exceed 65535.  The launches have no id in mcraw_ctx_kernel_ms (time them with stream
+ * events).
+ * Rejected (returns < 0, mcraw_last_error says why, starting with "mcraw_stats_batch: ", nothing is written): a NULL `s`, `in`
+ * or `out`; an odd `in` address; an `out` that is not 8-byte aligned; width or height outside 1 .. 65536; a pitch below
+ * width; n > 1 and a frame stride below (height - 1) * pitch + width; bins_log2 outside 6 .. 12; shift above 15; w or h of 0;
+ * a window that leaves the frame (x0 + w > width or y0 + h > height, computed without overflow); an unknown flag; a non-zero
+ * `reserved`; out_bytes < n * mcraw_stats_record_bytes(bins_log2); an `out` range that overlaps the input's extent. */
+#define MCRAW_STATS_ACCUMULATE 1u   /* flags: add to the records already at `out` instead of initialising them */
+typedef struct mcraw_stats {
+    uint32_t bins_log2;      /* 6 .. 12: B = 1 << bins_log2 bins per CFA position                 */
+    uint32_t shift;          /* 0 .. 15: bin of sample s = min(s >> shift, B - 1)                 */
+    uint32_t x0, y0, w, h;   /* the window counted, in frame pixels; w, h >= 1                    */
+    uint16_t sat[4];         /* by CFA position: s >= sat[p] counts as saturated                  */
+    uint32_t flags;          /* MCRAW_STATS_ACCUMULATE or 0                                       */
+    uint32_t reserved;       /* must be 0                                                         */
+} mcraw_stats;               /* sizeof 40; x0 8, sat 24, flags 32, reserved 36                    */
+size_t mcraw_stats_record_bytes(uint32_t bins_log2);   /* 16 * B + 96; 0 for a bins_log2 outside 6 .. 12 */
+int mcraw_stats_batch(mcraw_ctx *ctx, const mcraw_stats *s, const uint16_t *in, size_t in_pitch, size_t in_frame_stride,
+                      int width, int height, int n, void *out, size_t out_bytes, void *stream);
+
 /* ---- environment ------------------------------------------------------------------------------
  * Read when a context (or pool) is created, never afterwards:
  *   MCRAW_DEVICE=n, MCRAW_DEVICES=all|0,1,5   default device of the five-argument entry points / members of a default pool

@@ -16,7 +16,8 @@ __all__ = ["lib_path", "load", "Context", "Pool", "Frame", "EncFrame", "FloatOut
            "MEM_DEVICE", "MEM_HOST", "KERNELS", "ENC_KERNELS", "ABI_SYMBOLS", "encode_bound7", "cfa_planes",
            "RgbParams", "RgbColor", "RGB_KERNELS", "rgb_color", "Display", "transfer_lut", "DISP_U8", "DISP_U16",
            "DISP_CHW", "DISP_HWC", "Yuv", "YUV_NV12", "YUV_P010", "yuv_matrix", "yuv_planes", "Shade", "gain_map",
-           "shading_map"]
+           "shading_map", "Stats", "STATS_ACCUMULATE", "FrameStats", "stats_white_balance", "stats_percentile",
+           "stats_clipped"]
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 
@@ -44,6 +45,7 @@ ABI_SYMBOLS = [
     "mcraw_ctx_last_serial", "mcraw_ctx_batch_status", "mcraw_ctx_errors", "mcraw_ctx_side_parts", "mcraw_ctx_host_way",
     "mcraw_encode_bound7", "mcraw_encode_batch", "mcraw_encode7", "mcraw_ctx_set_float_out", "mcraw_pool_set_float_out",
     "mcraw_demosaic_batch", "mcraw_demosaic_display_batch", "mcraw_demosaic_yuv_batch", "mcraw_shade_batch",
+    "mcraw_stats_batch", "mcraw_stats_record_bytes",
 ]
 
 POST_BLACK, POST_PACK12, POST_PACK10, POST_PACK14 = 1, 2, 4, 8
@@ -222,6 +224,120 @@ def shading_map(frame_meta, cfa="rggb"):
     if any(a.shape != out[0].shape for a in out):
         raise ValueError("lensShadingMap: the four planes differ in size")
     return gain_map(np.stack(out), cfa)
+
+
+# per-frame statistics of mosaics (mcraw_stats_batch)
+STATS_ACCUMULATE = 1
+
+
+class Stats(C.Structure):
+    """struct mcraw_stats (include/mcraw_hip.h): bins, shift, the window, the saturation levels by CFA position, flags."""
+    _fields_ = [("bins_log2", C.c_uint32), ("shift", C.c_uint32), ("x0", C.c_uint32), ("y0", C.c_uint32), ("w", C.c_uint32),
+                ("h", C.c_uint32), ("sat", C.c_uint16 * 4), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class FrameStats:
+    """What Context.stats returns: `raw`, the (N, record_bytes) uint8 tensor of mcraw_stats_batch's records ((record_bytes,)
+    for an (H, W) mosaic), and exact views into it, by CFA position p = (y & 1) * 2 + (x & 1): hist (N, 4, bins) int32;
+    cnt, nsat, min, max (N, 4) int32; sum (N, 4) int64 (the unsaturated samples only); bins and shift as given.  The signed
+    views are exact because a frame of at most 65536 x 65536 has at most 2^30 samples per position; records that were
+    accumulated into (accumulate=True) can pass 2^31, and their int32 views then show negative numbers: reinterpret them as
+    unsigned.  The views are device tensors: reading them synchronises like any other tensor."""
+
+    def __init__(self, raw, bins, shift):
+        import torch
+        self.raw, self.bins, self.shift = raw, int(bins), int(shift)
+        nb = 16 * self.bins
+        lead = tuple(raw.shape[:-1])
+        words = raw[..., :nb + 64].view(torch.int32)
+        self.hist = words[..., :4 * self.bins].unflatten(-1, (4, self.bins))
+        small = words[..., 4 * self.bins:]
+        self.cnt, self.nsat, self.min, self.max = (small[..., 4 * i:4 * i + 4] for i in range(4))
+        self.sum = raw[..., nb + 64:nb + 96].view(torch.int64)
+        assert tuple(self.sum.shape) == lead + (4,)
+
+    def cpu(self):
+        """The fields as numpy arrays on the host (a dict with hist, cnt, nsat, min, max, sum, bins, shift): what the
+        stats_* helpers take."""
+        d = {k: getattr(self, k).cpu().numpy() for k in ("hist", "cnt", "nsat", "min", "max", "sum")}
+        d["bins"], d["shift"] = self.bins, self.shift
+        return d
+
+
+def _stats_arrays(st):
+    """(fields as numpy arrays with a leading frame axis, whether that axis was added) of a FrameStats or of a mapping /
+    object that holds its arrays on the CPU."""
+    import numpy as np
+    if isinstance(st, FrameStats):
+        st = st.cpu()
+    get = st.__getitem__ if isinstance(st, dict) else (lambda k: getattr(st, k))
+    d = {k: np.asarray(get(k)).astype(np.int64) for k in ("hist", "cnt", "nsat", "sum")}
+    d["shift"] = int(get("shift"))
+    single = d["cnt"].ndim == 1
+    if single:
+        d = {k: (v[None] if k != "shift" else v) for k, v in d.items()}
+    return d, single
+
+
+def stats_white_balance(st, black=(0, 0, 0, 0), cfa="rggb"):
+    """Grey-world white-balance gains (N, 3) float64, R, G, B with G = 1, from a FrameStats (or its arrays on the CPU): usable
+    as gain= of the demosaic methods.  The mean of a CFA position is sum / (cnt - nsat) - black (the unsaturated samples
+    only; black by CFA position, as everywhere); the two green positions are pooled by their counts; gain = mean G / mean
+    of the channel.  A channel without an unsaturated sample, or with a mean <= 0, gets gain 1 (and so do both others when
+    that channel is G).  A (4,)-shaped record gives (3,)."""
+    import numpy as np
+    d, single = _stats_arrays(st)
+    plane = cfa_planes(cfa)  # plane[p]: 0 R, 1 G (R row), 2 G (B row), 3 B
+    black = np.asarray(black, dtype=np.float64).ravel()
+    if black.size != 4:
+        raise ValueError("black: four levels, by CFA position (row & 1) * 2 + (col & 1)")
+    good = (d["cnt"] - d["nsat"]).astype(np.float64)  # (N, 4) by position
+    above = d["sum"].astype(np.float64) - good * black[None, :]  # sum of (v - black) over the unsaturated samples
+    n = good.shape[0]
+    tot, num = np.zeros((n, 3)), np.zeros((n, 3))
+    for p in range(4):
+        ch = (0, 1, 1, 2)[plane[p]]
+        tot[:, ch] += good[:, p]
+        num[:, ch] += above[:, p]
+    mean = np.where(tot > 0, num / np.maximum(tot, 1.0), 0.0)
+    gains = np.ones((n, 3))
+    ok = mean > 0
+    for ch in (0, 2):
+        use = ok[:, ch] & ok[:, 1]
+        gains[use, ch] = mean[use, 1] / mean[use, ch]
+    return gains[0] if single else gains
+
+
+def stats_percentile(st, q, pool=True):
+    """The level below which the fraction q (0 .. 1) of the samples lies, from the histogram: the smallest bin b whose
+    cumulative count reaches ceil(q * total) (bin 0 for q = 0), returned as that bin's upper edge
+    min(((b + 1) << shift) - 1, 65535).  q * total is computed exactly (q may be a fractions.Fraction).  Per frame, (N,)
+    int64, over the four CFA positions pooled, or (N, 4) per position with pool=False; usable as white=, or to match
+    exposures."""
+    import numpy as np
+    from fractions import Fraction
+    if not 0 <= q <= 1:
+        raise ValueError("q must be in 0 .. 1")
+    d, single = _stats_arrays(st)
+    hist = d["hist"].sum(axis=1, keepdims=True) if pool else d["hist"]  # (N, 1 or 4, B)
+    cum = np.cumsum(hist, axis=-1)
+    total = cum[..., -1]
+    fq = Fraction(q)
+    need = np.array([-((-fq.numerator * int(t)) // fq.denominator) for t in total.ravel()],
+                    dtype=np.int64).reshape(total.shape)  # ceil(q * total) in integers
+    b = (cum < need[..., None]).sum(axis=-1)  # the first bin that reaches it; B when none does
+    edge = np.minimum(((np.minimum(b, hist.shape[-1] - 1) + 1) << d["shift"]) - 1, 65535)
+    if pool:
+        edge = edge[:, 0]
+    return edge[0] if single else edge
+
+
+def stats_clipped(st):
+    """nsat / cnt per frame and CFA position, (N, 4) float64 (0 where a position has no sample)."""
+    import numpy as np
+    d, single = _stats_arrays(st)
+    r = d["nsat"] / np.maximum(d["cnt"], 1)
+    return r[0] if single else r
 
 
 def _yuv_rule_ok(rows, sh, in_bits):
@@ -544,6 +660,11 @@ def load():
     lib.mcraw_shade_batch.restype = C.c_int
     lib.mcraw_shade_batch.argtypes = [C.c_void_p, C.POINTER(Shade), C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int,
                                       C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
+    lib.mcraw_stats_record_bytes.restype = C.c_size_t
+    lib.mcraw_stats_record_bytes.argtypes = [C.c_uint32]
+    lib.mcraw_stats_batch.restype = C.c_int
+    lib.mcraw_stats_batch.argtypes = [C.c_void_p, C.POINTER(Stats), C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int,
+                                      C.c_void_p, C.c_size_t, C.c_void_p]
     lib.mcraw_encode7.restype = C.c_size_t
     lib.mcraw_encode7.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int]
     _lib = lib
@@ -979,6 +1100,84 @@ class Context:
         if rc != 0:
             raise McrawError("mcraw_shade_batch failed (%d): %s" % (rc, self._lib.mcraw_last_error().decode()))
         return out
+
+    def stats(self, mosaic, *, bins=256, shift=None, sat=65535, roi=None, out=None, accumulate=False):
+        """Per-frame statistics of uint16 mosaics resident on the context's device (mcraw_stats_batch), by CFA position
+        p = (y & 1) * 2 + (x & 1): a histogram of `bins` (64 .. 4096, a power of two) bins with bin = min(v >> shift,
+        bins - 1), the sample count, the count of saturated samples (v >= sat), the sum of the unsaturated ones, min and
+        max.  mosaic: (N, H, W) or (H, W), rows contiguous (rows and frames may be strided), odd sizes are fine.
+        shift=None: the smallest shift with (max(sat) >> shift) < bins, so every unsaturated level has a bin of its own
+        scale.  sat: one level or four, by CFA position.  roi=(y0, x0, h, w): the window counted, in frame pixels (a window
+        at an odd offset keeps the frame's CFA positions); None: the whole frame.  Returns a FrameStats over a new
+        (N, record_bytes) uint8 tensor, or over `out` (a contiguous uint8 tensor of that shape, 8-byte aligned), which the
+        call initialises itself.  accumulate=True adds to the records already in `out` instead (a clip over several batches,
+        a frame over several windows): counters then wrap modulo 2^32 and FrameStats' int32 views are exact only below 2^31.
+        An (H, W) mosaic drops N.  Queued on torch.cuda.current_stream(); nothing synchronises."""
+        import torch
+        dev = self._torch_device(torch)
+        if not isinstance(mosaic, torch.Tensor) or mosaic.dtype != torch.uint16 or mosaic.device != dev or mosaic.dim() not in (2, 3):
+            raise ValueError("stats: mosaic must be a uint16 tensor (N, H, W) or (H, W) on %s" % dev)
+        bins = int(bins)
+        if bins < 64 or bins > 4096 or bins & (bins - 1):
+            raise ValueError("stats: bins must be a power of two in 64 .. 4096, not %r" % (bins,))
+        sat = [int(sat)] * 4 if not hasattr(sat, "__len__") else [int(v) for v in sat]
+        if len(sat) != 4 or any(v < 0 or v > 65535 for v in sat):
+            raise ValueError("sat: one level or four, by CFA position (row & 1) * 2 + (col & 1), each 0 .. 65535")
+        if shift is None:
+            shift = 0
+            while (max(sat) >> shift) >= bins:
+                shift += 1
+        single = mosaic.dim() == 2
+        mos = mosaic.unsqueeze(0) if single else mosaic
+        n, h, w = (int(v) for v in mos.shape)
+        if h == 0 or w == 0:
+            raise ValueError("stats: empty frames have no statistics")
+        if w > 1 and mos.stride(2) != 1:
+            raise ValueError("stats: the rows of the mosaic must be contiguous")
+        y0, x0, rh, rw = (0, 0, h, w) if roi is None else (int(v) for v in roi)
+        if min(y0, x0) < 0 or rh < 1 or rw < 1 or y0 + rh > h or x0 + rw > w:
+            raise ValueError("stats: roi (y0, x0, h, w) = %r leaves the %d x %d frame" % (roi, h, w))
+        rec = 16 * bins + 96
+        want = (rec,) if single else (n, rec)
+        if out is None:
+            if accumulate:
+                raise ValueError("stats: accumulate=True needs the records to add to (out=)")
+            out = torch.empty(want, dtype=torch.uint8, device=dev)
+        elif not isinstance(out, torch.Tensor) or tuple(out.shape) != want or out.dtype != torch.uint8 or out.device != dev \
+                or not out.is_contiguous():
+            raise ValueError("stats: out must be a contiguous uint8 tensor of shape %s on %s" % (want, dev))
+        res = FrameStats(out, bins, shift)
+        if n == 0:
+            return res
+        s = Stats()
+        s.bins_log2, s.shift, s.x0, s.y0, s.w, s.h = bins.bit_length() - 1, int(shift), x0, y0, rw, rh
+        for i in range(4):
+            s.sat[i] = sat[i]
+        s.flags, s.reserved = (STATS_ACCUMULATE if accumulate else 0), 0
+        pitch = int(mos.stride(1)) if h > 1 else w
+        fstride = int(mos.stride(0)) if n > 1 else pitch * h
+        cur, run = self._run_stream(torch, dev)
+        try:
+            rc = self._lib.mcraw_stats_batch(self._h, C.byref(s), C.c_void_p(mos.data_ptr()), pitch, fstride, w, h, n,
+                                             C.c_void_p(out.data_ptr()), n * rec, C.c_void_p(run.cuda_stream))
+        finally:
+            if run is not cur:
+                mos.record_stream(run)
+                out.record_stream(run)
+                cur.wait_stream(run)
+        if rc != 0:
+            raise McrawError("mcraw_stats_batch failed (%d): %s" % (rc, self._lib.mcraw_last_error().decode()))
+        return res
+
+    def decode_stats(self, inputs, width, height, type, *, bins=256, shift=None, sat=65535, roi=None, out=None,
+                     accumulate=False, check=True):
+        """Decode frames of one geometry that are resident in HBM and count them (stats()): the plain uint16 mosaics go to a
+        scratch tensor of torch's caching allocator, both steps are queued on torch.cuda.current_stream().  inputs: uint8
+        CUDA tensors, or (device pointer, length) pairs.  check=True synchronises after the decode and raises McrawError
+        naming the frames that failed; check=False returns at once.  The stage the context had before the call is restored
+        afterwards.  Returns the FrameStats of the (N, H, W) batch."""
+        scratch = self._decode_scratch(inputs, width, height, type, check, "decode_stats")
+        return self.stats(scratch, bins=bins, shift=shift, sat=sat, roi=roi, out=out, accumulate=accumulate)
 
     def demosaic(self, mosaic, *, algo="mhc", dtype, white, black=(0, 0, 0, 0), cfa="rggb", gain=None, matrix=None,
                  clip=False, out=None, check=True, shading=None):

@@ -7,6 +7,7 @@
 //   mcraw_device.hip   batches whose buffers are in HBM: slots, statuses, second plans
 //   mcraw_hostmem.hip  batches whose buffers are in host memory: the three-lane pipeline, tickets
 //   mcraw_shade.hip    mcraw_shade_batch: its kernel, checks and launch (it shares the context's mutex, device and stream only)
+//   mcraw_stats.hip    mcraw_stats_batch: its kernels, checks and launches (likewise)
 // Replaces the per-frame dispatch of lib/Decoder.cpp:216-234 with batched submits.  There is no CPU decode fallback in any of them.
 #pragma once
 #include <hip/hip_runtime.h>
