@@ -93,8 +93,24 @@ def build_variant(out, flags=()):
     return out
 
 
-# The -D builds that tests/ links on the GPU box (tests/test_gpu_split.py, test_gpu_segw.py, test_gpu_lookback_fault.py).
-TEST_VARIANTS = (["-DMCRAW_FORCE_SEGW"], ["-DMCRAW_INJECT_MUTE7"], ["-DMCRAW_INJECT_LOST"])
+# k6_decode with one of its rare paths forced and every path counted (tests/test_gpu_k6_paths.py; the switches: csrc/mcraw_type6.hip).
+# Every name below occurs in mcraw_type6.hip alone, so a variant compiles that one source.
+K6_PATH_VARIANTS = {
+    "census": ["-DMCRAW_PATHS6"],
+    "polls0": ["-DMCRAW_PATHS6", "-DMCRAW_SCALAR_POLLS6=0"],
+    "polls1": ["-DMCRAW_PATHS6", "-DMCRAW_SCALAR_POLLS6=1"],
+    "slowprefix": ["-DMCRAW_PATHS6", "-DMCRAW_INJECT_SLOWPREFIX6"],
+    "careful": ["-DMCRAW_PATHS6", "-DMCRAW_FORCE_CAREFUL6"],
+    "latefront": ["-DMCRAW_PATHS6", "-DMCRAW_FORCE_LATEFRONT6"],
+    "nofront": ["-DMCRAW_PATHS6", "-DMCRAW_FORCE_NOFRONT6"],
+    "nolean": ["-DMCRAW_PATHS6", "-DMCRAW_FORCE_NOLEAN6"],
+    "pairmode": ["-DMCRAW_PATHS6", "-DMCRAW_FORCE_PAIRMODE6"],
+    "warm64": ["-DMCRAW_PATHS6", "-DMCRAW_WARM6=64"],
+    "poison": ["-DMCRAW_PATHS6", "-DMCRAW_POISON_FRONT6"],
+}
+
+# The -D builds that tests/ links on the GPU box (tests/test_gpu_split.py, test_gpu_segw.py, test_gpu_lookback_fault.py, test_gpu_k6_paths.py).
+TEST_VARIANTS = (["-DMCRAW_FORCE_SEGW"], ["-DMCRAW_INJECT_MUTE7"], ["-DMCRAW_INJECT_LOST"]) + tuple(K6_PATH_VARIANTS.values())
 
 
 def prebuild_test_variants():

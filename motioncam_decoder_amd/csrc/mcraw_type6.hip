@@ -227,6 +227,55 @@ __device__ uint32_t g_k6_prof[K6_PROF_WG][K6_PROF_N];
 #define K6_COUNT(slot, v)
 #endif
 
+// ---- test builds (tests/test_gpu_k6_paths.py; none of this is in the product library) --------------------------------
+// Which of its paths a segment takes is decided by its content and, for the look-back, by timing.  Every switch below
+// picks among paths that are valid for every input, so a build with any of them decodes every stream as the product does:
+//   MCRAW_SCALAR_POLLS6=n     scalar look-back polls before the vector loop takes over (0: vector polls alone; 1: one window, then hand-over)
+//   MCRAW_WARM6=64            (above) walkers start almost cold: the repair rounds carry the load
+//   MCRAW_FORCE_CAREFUL6      the careful walk (counts only) in every workgroup
+//   MCRAW_FORCE_LATEFRONT6    the sure entry accepts its chains' agreement no earlier than quarter 2: every segment with a
+//                             predecessor is entered through what that one publishes (EX_PHASE; a partly filled or never-agreeing segment: the map)
+//   MCRAW_FORCE_NOFRONT6      ... never: every full segment publishes its map (EX_MAP, hm), successors compose maps
+//   MCRAW_FORCE_NOLEAN6       no wave is on the lean path: every list is built by its own wave, in rounds
+//   MCRAW_FORCE_PAIRMODE6     one list entry per record pair, whatever the number of records
+//   MCRAW_INJECT_SLOWPREFIX6  a few microseconds between a segment's look-back and its prefix word: successors find aggregates
+//                             without prefixes, their look-backs run window by window to the frame's front
+//   MCRAW_POISON_FRONT6       the staged front is overwritten once the chain is resolved, before any list is written: a stale front
+//                             byte read as a list entry, or a read of the front behind the resolve, changes pixels
+//   MCRAW_PATHS6              the path census below
+#ifndef MCRAW_SCALAR_POLLS6
+#define MCRAW_SCALAR_POLLS6 32
+#endif
+#if defined(MCRAW_FORCE_NOFRONT6)
+#define K6_FRONT_OK(kb) false
+#elif defined(MCRAW_FORCE_LATEFRONT6)
+#define K6_FRONT_OK(kb) ((kb) >= 2u)
+#else
+#define K6_FRONT_OK(kb) true
+#endif
+#ifdef MCRAW_PATHS6
+// How many segments, look-backs, lists and unpacking waves went which way, summed over the launches since the last reset
+// (mcraw_diag_k6_paths; one lane per workgroup or wave counts).  The front kinds and the look-backs count segments that have a predecessor.
+enum Path6 {
+    P6_SEGMENTS, P6_CAREFUL, P6_REPAIRED,          // segments resolved; ... by the careful walk; ... whose walkers took more than one round
+    P6_FRONT0, P6_LATEFRONT, P6_NOFRONT, P6_MAPS,  // the sure entry's chains are one at the segment's start / inside it / never; maps published
+    P6_LB_SCALAR, P6_LB_VECTOR, P6_LB_HANDED,      // look-backs resolved by scalar polls alone / by the vector loop entered with a sum of 0 / ... with a
+                                                   // sum above 0.  (LB_VECTOR is not "no scalar window succeeded": windows over predecessors without records sum to 0 too)
+    P6_NOTED, P6_COOP, P6_NONCOOP,                 // segments whose lists come from the notes / a cooperative walk / every wave's own walk
+    P6_WAVES, P6_WAVES_PAIR, P6_WAVES_MULTI,       // live unpacking waves; ... in the layout by pairs; ... with more than one round
+    P6_LOST,                                       // segments that gave up waiting
+    P6_N
+};
+__device__ unsigned long long g_k6_paths[P6_N];
+#define K6_PATH(cond, slot)                                                                                            \
+    do {                                                                                                               \
+        if (cond)                                                                                                      \
+            atomicAdd(&g_k6_paths[slot], 1ull);                                                                        \
+    } while (0)
+#else
+#define K6_PATH(cond, slot)
+#endif
+
 // A workgroup works on ONE frame (the launch interleaves the frames: a segment's predecessors then started long before
 // it) and takes its segment -- DEC_CH chunks -- from the frame's ticket counter: the segments it may have to wait on were all taken by
 // workgroups that are running or done, whatever order the hardware starts workgroups in.  (One counter per frame,
@@ -399,7 +448,12 @@ __global__ __launch_bounds__(DEC_T) void k6_decode(const Plan6 *__restrict__ pla
         if (K6_ABL == 4)
             return;
         // (wave-uniform: which walk loop this workgroup runs)
+#ifdef MCRAW_FORCE_CAREFUL6
+        const bool careful = true;
+        (void)near_end;
+#else
         const bool careful = near_end || __ballot(lane < NROUND * (DEC_T / 64u) && s_flat[lane < NROUND * (DEC_T / 64u) ? lane : 0u] != 0ull) != 0ull;
+#endif
         constexpr uint32_t CLAMP = FRONT6 + OWN + SLACK - 2u; // (free-running walks stay inside the stage)
 
         // ---- the sure entry (wave RESOLVER - 1): the 17 chains that can cross into the staged front -- every chain starts a record
@@ -430,7 +484,7 @@ __global__ __launch_bounds__(DEC_T) void k6_decode(const Plan6 *__restrict__ pla
                     }
                     const unsigned long long am = __ballot(alive && ph != DEAD);
                     const uint32_t ph0 = am ? wave_lane(ph, static_cast<uint32_t>(__builtin_ctzll(am))) : DEAD;
-                    if (kb < 4u * cnt && __ballot(alive && ph != DEAD && ph != ph0) == 0ull) {
+                    if (kb < 4u * cnt && K6_FRONT_OK(kb) && __ballot(alive && ph != DEAD && ph != ph0) == 0ull) {
                         fr = (kb << 8) | ph0;
                         break;
                     }
@@ -589,6 +643,7 @@ __global__ __launch_bounds__(DEC_T) void k6_decode(const Plan6 *__restrict__ pla
                                 look_put(look.hm + 3u * lme + lane, epoch, hw);
                             if (lane == 0)
                                 look_put(look.ex + lme, epoch, EX_MAP << 30);
+                            K6_PATH(lane == 0u, P6_MAPS);
                         }
                         // The nearest segment in front whose exit is known -- it has resolved and published its records, or said a
                         // phase above --, and from there through the maps of the segments in between (64 segments per poll; the
@@ -656,6 +711,17 @@ __global__ __launch_bounds__(DEC_T) void k6_decode(const Plan6 *__restrict__ pla
                     break;
             }
             K6_COUNT(25, rounds);
+#ifdef MCRAW_PATHS6
+            if (lane == 0u) {
+                const uint32_t kind = s_front >> 8; // (what the sure entry said: `from` has moved on)
+                K6_PATH(true, P6_SEGMENTS);
+                K6_PATH(careful, P6_CAREFUL);
+                K6_PATH(rounds > 1u, P6_REPAIRED);
+                K6_PATH(seg && kind == 0u, P6_FRONT0);
+                K6_PATH(seg && kind != 0u && kind != NOFRONT, P6_LATEFRONT);
+                K6_PATH(seg && kind == NOFRONT, P6_NOFRONT);
+            }
+#endif
         }
     }
 
@@ -683,6 +749,12 @@ __global__ __launch_bounds__(DEC_T) void k6_decode(const Plan6 *__restrict__ pla
         g.N = g.live ? g.R1 - g.R0 : 0u;
         g.lean = g.live && inner && g.N <= ROWS_CAP && c0 * CHUNK6 + STAGE < len;
         g.pairmode = g.N + NOTES6 > ROWS_CAP / 2u; // (the layout by records: as long as the notes' stores stay inside the list)
+#ifdef MCRAW_FORCE_NOLEAN6
+        g.lean = false;
+#endif
+#ifdef MCRAW_FORCE_PAIRMODE6
+        g.pairmode = true;
+#endif
         return g;
     };
     auto range_of = [&](uint32_t w) { return range_from(w, ent_of(w * ROWS_CH), ent_of(w * ROWS_CH + ROWS_CH)); };
@@ -732,7 +804,7 @@ __global__ __launch_bounds__(DEC_T) void k6_decode(const Plan6 *__restrict__ pla
             // relied on; what it does not find after SCALAR_POLLS6 polls is asked for by vector loads at device scope as before
             // (measured: a frame whose segments run on all eight XCDs resolves by scalar polls alone -- the fallback is there
             // because nothing documents that it must).  Windows that reach in front of the frame's first segment go the vector way too.
-            constexpr uint32_t SCALAR_POLLS6 = 32;
+            constexpr uint32_t SCALAR_POLLS6 = MCRAW_SCALAR_POLLS6;
             constexpr int SW = 8; // segments per scalar poll: ONE s_load_dwordx16 (two of them for sixteen segments: 2.5 % slower, and
                                   // 26 instead of 15 MB of polls per 380 MB of stream; four segments by s_load_dwordx8: the same as eight)
             typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
@@ -767,6 +839,9 @@ __global__ __launch_bounds__(DEC_T) void k6_decode(const Plan6 *__restrict__ pla
                 }
                 jn -= SW;
             }
+            K6_PATH(lane == 0u && prefixed, P6_LB_SCALAR);
+            K6_PATH(lane == 0u && !prefixed && !lost && base == 0u, P6_LB_VECTOR);
+            K6_PATH(lane == 0u && !prefixed && !lost && base != 0u, P6_LB_HANDED); // (the scalar windows' sum and `jn` go on into the vector loop)
             while (!lost && !prefixed && K6_ABL != 32 && K6_ABL != 33) {
                 const int32_t k = jn - static_cast<int32_t>(lane);
                 w = RES_AGG << 30; // segments "before the frame": nothing, and never reached (segment 0 has a prefix)
@@ -797,11 +872,17 @@ __global__ __launch_bounds__(DEC_T) void k6_decode(const Plan6 *__restrict__ pla
         if (lost) { // (a predecessor never published: fail the frame rather than wait for ever)
             if (lane == 0)
                 atomicOr(P->status, MCRAW_E_DEVICE);
+            K6_PATH(lane == 0u, P6_LOST);
             qp = DEAD;
         }
         // entries carry the record index in 24 bits: a stream with more records than that (the frame itself has
         // fewer, the host checks) saturates instead of wrapping back into the frame
         const uint32_t endn = min(base + total, 0xFFFFFFu);
+#ifdef MCRAW_INJECT_SLOWPREFIX6 // (a delay, not a withheld word: ~13 us behind the aggregate; segment 0 has no aggregate and is what every look-back ends at)
+        if (seg)
+            for (int d = 0; d < 4; d++)
+                __builtin_amdgcn_s_sleep(127);
+#endif
 #ifdef MCRAW_INJECT_LOST
         if (lane == 0 && !(f == 0u && seg == 3u))
 #else
@@ -850,6 +931,16 @@ __global__ __launch_bounds__(DEC_T) void k6_decode(const Plan6 *__restrict__ pla
         // (a list by pairs holds every second note: up to ROWS_CAP - NOTES6 records per wave; round 6 -- until then the notes served
         // the layout by records only, and a wave of more than 512 records was listed by a second walk along the chain: 12 % of the kernel)
         const bool noted = coop && notes_ok && __ballot(rg.N + NOTES6 > (rg.pairmode ? ROWS_CAP : ROWS_CAP / 2u)) == 0ull;
+#ifdef MCRAW_POISON_FRONT6
+        // This wave is past the barrier behind the sure entry, whose wave waits at the one below: the front has been read for the last
+        // time.  All of it -- list 0's place and the rest -- now holds 0x0FFE: as a list entry a position inside the wave's stage that
+        // is no record of its range, as stream bytes a chain of raw records.
+        *reinterpret_cast<uint4 *>(s_stage + lane * 16u) = make_uint4(0x0FFE0FFEu, 0x0FFE0FFEu, 0x0FFE0FFEu, 0x0FFE0FFEu);
+        static_assert(FRONT6 == 64u * 16u, "one 16-byte store per lane covers the front");
+#endif
+        K6_PATH(lane == 0u && noted, P6_NOTED);
+        K6_PATH(lane == 0u && coop && !noted, P6_COOP);
+        K6_PATH(lane == 0u && !coop, P6_NONCOOP);
         if (K6_ABL != 3 && noted) {
             const int32_t slot0 = static_cast<int32_t>(qi - rg.R0); // -1: an odd first record belongs to the previous wave's
             uint16_t *lp = pos_of(uw) + slot0;                        // last pair, never listed
@@ -1081,6 +1172,8 @@ __global__ __launch_bounds__(DEC_T) void k6_decode(const Plan6 *__restrict__ pla
 
     if (coop) {
         K6_STAMP(4, 0);
+        K6_PATH(lane == 0u, P6_WAVES); // (every wave of a cooperative segment is live)
+        K6_PATH(lane == 0u && pairmode, P6_WAVES_PAIR);
         unpack_round(wave, R0, R1, pairmode, 0u, 2u * (R1 - R0));
         K6_STAMP(5, 0);
 #ifdef MCRAW_DIAG
@@ -1098,6 +1191,9 @@ __global__ __launch_bounds__(DEC_T) void k6_decode(const Plan6 *__restrict__ pla
     }
     if (!live)
         return;
+    K6_PATH(lane == 0u, P6_WAVES);
+    K6_PATH(lane == 0u, P6_WAVES_PAIR); // (the general path lists by pairs)
+    K6_PATH(lane == 0u && N > ROWS_CAP, P6_WAVES_MULTI);
     const uint8_t *bytes = s_own + wave * (ROWS_CH * CHUNK6);
     // The lists of the general path: one lane per QUARTER chunk walks from where the chain enters its quarter (s_ent4: sixteen
     // walks side by side per wave -- round 6; until then one lane per chunk: a wave of 2-byte records cost 64 steps a round).
@@ -1161,6 +1257,24 @@ extern "C" void mcraw_diag_k6_prof(uint32_t *out, int nwg, int reset)
         (void)hipGetSymbolAddress(&p, HIP_SYMBOL(g_k6_prof));
         (void)hipMemset(p, 0, sizeof(g_k6_prof));
     }
+}
+#endif
+
+#ifdef MCRAW_PATHS6
+// The census, in the order of Path6 (up to n counters; returns how many there are); `reset`: and start it over.
+extern "C" int mcraw_diag_k6_paths(uint64_t *out, int n, int reset)
+{
+    (void)hipDeviceSynchronize();
+    n = n < 0 ? 0 : n < static_cast<int>(P6_N) ? n : static_cast<int>(P6_N);
+    if (out && n)
+        (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_k6_paths), sizeof(uint64_t) * static_cast<size_t>(n));
+    if (reset) {
+        void *p = nullptr;
+        (void)hipGetSymbolAddress(&p, HIP_SYMBOL(g_k6_paths));
+        (void)hipMemset(p, 0, sizeof(g_k6_paths));
+        (void)hipDeviceSynchronize(); // (the contexts' streams do not wait for the null stream)
+    }
+    return static_cast<int>(P6_N);
 }
 #endif
 

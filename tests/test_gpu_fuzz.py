@@ -6,24 +6,9 @@ import numpy as np
 import pytest
 
 import _libs as L
+from _legacy_corpus import mutants as _mutants  # (the mutator: shared with the corpus of test_gpu_k6_paths.py)
 
 pytestmark = pytest.mark.gpu
-
-
-def _mutants(buf, rng, n, hot=()):
-    out = []
-    for i in range(n):
-        b = buf.copy()
-        k = int(rng.integers(1, 4))
-        for _ in range(k):
-            if hot and rng.random() < 0.5:
-                lo, hi = hot[int(rng.integers(0, len(hot)))]
-                pos = int(rng.integers(lo, min(hi, b.size)))
-            else:
-                pos = int(rng.integers(0, b.size))
-            b[pos] = rng.integers(0, 256)
-        out.append(b)
-    return out
 
 
 def _compare(ctx, typ, w, h, bufs, decode):

@@ -5,6 +5,7 @@ bar is memcmp equality, including the return value."""
 import numpy as np
 import pytest
 
+import _legacy_corpus as K
 import _libs as L
 import motioncam_decoder_amd as M
 
@@ -209,9 +210,8 @@ def test_legacy_frames_of_one_record_size_each_over_several_segments(gpu_ctx):
         nb = nib if nib <= 10 else 16
         w = 1024 + 32 * nib
         h = max(96, int(6 * 16384 / (2 + 2 * nb) * 16 / w) + 1 + nib) # at least six segments of 16 KiB
-        img = rng.integers(0, 1 << max(nb, 1), size=(h, w), dtype=np.uint16) if nb else np.full((h, w), 321, np.uint16)
-        nrec = ((w + 31) // 32) * 2 * h
-        buf = L.encode6(img, np.full(nrec, nib, np.uint8))
+        img, mb = K.one_size_frame(rng, nib, w, h)
+        buf = L.encode6(img, mb)
         ret, out = L.oracle_decode6(buf, w, h)
         assert ret == w * h and np.array_equal(out, img)
         items.append((6, w, h, buf))
@@ -227,14 +227,8 @@ def test_legacy_frames_of_mixed_record_sizes_around_the_list_thresholds(gpu_ctx)
     rng = np.random.default_rng(606)
     for nibs, w in (((4, 5, 6), 1504), ((3, 4, 5), 1280), ((2, 3), 1056), ((1, 2, 3), 2016), ((0, 1, 2), 992), ((0, 5), 1600), ((2, 12), 1184)):
         h = 260
-        rpr = w // 32 * 2                                           # records per row (w is a multiple of 32)
-        nrec = rpr * h
-        run = rng.integers(1, 400, size=nrec)                      # sizes change in runs of 1 .. 400 records
-        idx = np.repeat(np.arange(nrec), run)[:nrec] % len(nibs)
-        nib = np.asarray(nibs, np.int64)[rng.permutation(len(nibs))][idx].reshape(h, w // 32, 2)
-        # record (y, g, p) holds the samples of columns 32 g + 2 i + p: residuals of nib[y, g, p] bits above a common reference
-        bits = np.repeat(nib, 16, axis=1).reshape(h, w // 32, 16, 2).reshape(h, w)
-        img = (100 + (rng.random((h, w)) * (1 << bits)).astype(np.int64)).astype(np.uint16)
+        nrec = w // 32 * 2 * h                                      # (w is a multiple of 32)
+        img = K.mixed_size_image(rng, nibs, w, h)                   # sizes change in runs of 1 .. 400 records
         buf = L.encode6(img)
         ret, out = L.oracle_decode6(buf, w, h)
         assert ret == w * h and np.array_equal(out, img)
@@ -252,9 +246,7 @@ def test_flat_and_textured_bands_mix_dense_and_sparse_chunks(gpu_ctx):
     rng = np.random.default_rng(77)
     items, expect = [], []
     for (w, h, band) in ((2048, 192, 24), (1024, 1536, 512), (1000, 150, 10)):
-        img = rng.integers(0, 4096, size=(h, w), dtype=np.uint16)
-        for y0 in range(0, h, 2 * band):
-            img[y0:y0 + band] = 517
+        img = K.banded_image(rng, w, h, band)
         for typ, enc, dec in ((7, L.encode7, L.oracle_decode7), (6, L.encode6, L.oracle_decode6)):
             buf = enc(img)
             ret, out = dec(buf, w, h)
@@ -395,7 +387,7 @@ def test_legacy_streams_whose_chunk_maps_are_never_unanimous(gpu_ctx):
     # payload bytes that read as headers of the same record size: the constant 0xBFFF is coded with the reference 0xFFF
     # and raw residuals 0xB000, so every even byte of the stream -- the headers' 0xFF and the payload's 0xB0 -- has a
     # nibble >= 11 = "raw record, 34 bytes"
-    img2 = np.full((h, w), 0xBFFF, np.uint16)
+    img2 = K.never_unanimous_image(w, h)
     buf2 = L.encode6(img2)
     assert all((int(b) >> 4) >= 11 for b in buf2[0:4096:2])
     ret2, out2 = L.oracle_decode6(buf2, w, h)
@@ -412,7 +404,7 @@ def test_legacy_stream_cut_inside_a_late_segment(gpu_ctx):
     w, h = 1920, 540
     img = L.natural_image_np(w, h, 12, 12.0, 31)
     good = L.encode6(img)
-    cut = good[: (good.size * 2 // 3) | 1].copy()
+    cut = K.cut_inside_late_segment(good)
     ret, _ = L.oracle_decode6(cut, w, h)
     assert ret == 0
     written, status, outs = decode_batch_device(gpu_ctx, [(6, w, h, good), (6, w, h, cut), (6, w, h, good)])
