@@ -536,6 +536,66 @@ size_t mcraw_stats_record_bytes(uint32_t bins_log2);   /* 16 * B + 96; 0 for a b
 int mcraw_stats_batch(mcraw_ctx *ctx, const mcraw_stats *s, const uint16_t *in, size_t in_pitch, size_t in_frame_stride,
                       int width, int height, int n, void *out, size_t out_bytes, void *stream);
 
+/* ---- uint16 mosaics -> uint16 mosaics with the defective pixels taken out ------------------------------------------------
+ *
+ * Finds hot, dead and stuck pixels in `n` uint16 mosaics of width x height and replaces them, and replaces the pixels of an
+ * optional static list: a DNG FixBadPixelsConstant / FixBadPixelsList, Android's hotPixelMap.  The output is a mosaic of the
+ * same black level, so everything that takes a mosaic takes the result.  Pitches and frame strides count uint16 elements.
+ * black[4] and abs_thr[4] are indexed by CFA position p = (y & 1) * 2 + (x & 1) (the call never needs the CFA).  Integers
+ * only: bit-exact.
+ * Neighbours.  All neighbours lie on the pixel's own lattice, at distance 2: the same colour for every Bayer arrangement.
+ * For d in {-2, +2} the neighbour coordinate of c is c' = c + d; if that is outside [0, size), c' = c - d; if that is outside
+ * too, c' = c -- for rows and columns independently.  The eight neighbours as (dy, dx), in this order: NW (-2,-2), N (-2,0),
+ * NE (-2,2), W (0,-2), E (0,2), SW (2,-2), S (2,0), SE (2,2).  Duplicates that the reflection makes count with their
+ * multiplicity.  With height <= 2 (width <= 2) the centre stands in for its vertical (horizontal) neighbours.  The
+ * centre is then among its own neighbours and the dynamic detector finds nothing: defined behaviour, not an error.
+ * Dynamic detection, for every pixel, from the values of `in` only (v: the pixel):
+ *   Hk = the rank-th largest of the eight neighbour values, Lk = the rank-th smallest              rank: 1 or 2
+ *   thr(m) = abs_thr[p] + ((max(m - black[p], 0) * rel_thr) >> 8)       rel_thr in Q8, 0 .. 65535; everything below 2^32
+ *   hot:   MCRAW_FIXPIX_HOT  is set, v > Hk and v - Hk > thr(Hk)
+ *   cold:  MCRAW_FIXPIX_COLD is set, v < Lk and Lk - v > thr(Lk)
+ * rank 2 lets two adjacent defects of one colour both be found; a line one pixel wide is kept at either rank.
+ * Replacement of a hot or cold pixel: of the four opposite pairs in the order (W,E), (N,S), (NW,SE), (NE,SW) the one with the
+ * smallest |a - b|, the first such pair on a tie: out = (a + b + 1) >> 1.  Every other pixel is copied.
+ * counts: NULL, or 4-byte aligned DEVICE memory for n records of uint32 hot[4], cold[4] (32 bytes each, indexed by p), which
+ * the call initialises itself on the stream: the pixels that the dynamic detector flagged, except those that the search below
+ * finds in the list.
+ * list: DEVICE memory, 4-byte aligned, of nlist <= 1 << 20 entries y << 16 | x, for every frame of the batch; read by the
+ * queued kernels in stream order and never copied into or cached by the context (two calls with the same pointer and new
+ * contents in between each see their own).  Entries with x >= width or y >= height are skipped.  A listed pixel is replaced
+ * unconditionally, after and over the dynamic result, from the values of `in`: by the rule above among the pairs of which
+ * NEITHER member is listed; if there is no such pair, the dynamic pass's result for the pixel stands.  "Listed" is what
+ * this search finds, for the kernels and for the reference alike:
+ *   lo = 0, hi = nlist;  while (lo < hi) { mid = (lo + hi) >> 1;  list[mid] < key ? lo = mid + 1 : hi = mid; }
+ *   member = lo < nlist && list[lo] == key
+ * so an ascending list means what it says, and a list that is not ascending still has one defined result.  The dynamic
+ * detector does not consult the list.
+ * There is no in-place form: every pixel reads its neighbours.  `in` and `out` may sit at any 2-byte alignment with any pitch
+ * (16-byte accesses where base, pitch and stride allow it).
+ * `stream`: a hipStream_t, NULL = the context's own stream; the call queues the work and returns without synchronising.
+ * It takes no decode serial and leaves the decode slots, mcraw_ctx_errors, mcraw_ctx_last_serial and the context's stage
+ * alone.  n == 0 is a no-op.  The launches have no id in mcraw_ctx_kernel_ms (time them with stream events).
+ * Rejected (returns < 0, mcraw_last_error says why, starting with "mcraw_fixpix_batch: ", nothing is written): a NULL `f`, `in`
+ * or `out`; an odd `in` or `out` address; width or height outside 1 .. 65536; a pitch below width; n > 1 and a frame stride
+ * below (height - 1) * pitch + width; rank not 1 or 2; rel_thr > 65535; an unknown flag; nlist > 0 with a NULL or misaligned
+ * `list`; nlist > 1 << 20; a misaligned `counts`; a non-zero `reserved`; input and output extents that overlap at all; a
+ * `counts` range that overlaps the input's or the output's extent. */
+#define MCRAW_FIXPIX_HOT 1u    /* flags: replace pixels far above their neighbours */
+#define MCRAW_FIXPIX_COLD 2u   /* flags: replace pixels far below their neighbours */
+typedef struct mcraw_fixpix {
+    uint32_t flags;          /* MCRAW_FIXPIX_HOT | MCRAW_FIXPIX_COLD, or 0 (the list alone)       */
+    uint32_t rank;           /* 1 or 2: the neighbour a pixel is compared with                    */
+    uint32_t rel_thr;        /* 0 .. 65535, Q8: the part of the threshold that grows with level   */
+    uint32_t nlist;          /* 0 .. 1 << 20 entries of `list`                                    */
+    uint16_t black[4];       /* by CFA position                                                   */
+    uint16_t abs_thr[4];     /* by CFA position                                                   */
+    const uint32_t *list;    /* DEVICE memory, 4-byte aligned: y << 16 | x; NULL with nlist 0     */
+    uint32_t *counts;        /* DEVICE memory, 4-byte aligned: n x (hot[4], cold[4]); or NULL     */
+    uint32_t reserved[2];    /* must be 0                                                         */
+} mcraw_fixpix;              /* sizeof 56; rank 4, rel_thr 8, nlist 12, black 16, abs_thr 24, list 32, counts 40, reserved 48 */
+int mcraw_fixpix_batch(mcraw_ctx *ctx, const mcraw_fixpix *f, const uint16_t *in, size_t in_pitch, size_t in_frame_stride,
+                       int width, int height, int n, uint16_t *out, size_t out_pitch, size_t out_frame_stride, void *stream);
+
 /* ---- environment ------------------------------------------------------------------------------
  * Read when a context (or pool) is created, never afterwards:
  *   MCRAW_DEVICE=n, MCRAW_DEVICES=all|0,1,5   default device of the five-argument entry points / members of a default pool

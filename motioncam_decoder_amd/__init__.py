@@ -17,7 +17,7 @@ __all__ = ["lib_path", "load", "Context", "Pool", "Frame", "EncFrame", "FloatOut
            "RgbParams", "RgbColor", "RGB_KERNELS", "rgb_color", "Display", "transfer_lut", "DISP_U8", "DISP_U16",
            "DISP_CHW", "DISP_HWC", "Yuv", "YUV_NV12", "YUV_P010", "yuv_matrix", "yuv_planes", "Shade", "gain_map",
            "shading_map", "Stats", "STATS_ACCUMULATE", "FrameStats", "stats_white_balance", "stats_percentile",
-           "stats_clipped"]
+           "stats_clipped", "FixPix", "FIXPIX_HOT", "FIXPIX_COLD", "pack_pixels"]
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 
@@ -45,7 +45,7 @@ ABI_SYMBOLS = [
     "mcraw_ctx_last_serial", "mcraw_ctx_batch_status", "mcraw_ctx_errors", "mcraw_ctx_side_parts", "mcraw_ctx_host_way",
     "mcraw_encode_bound7", "mcraw_encode_batch", "mcraw_encode7", "mcraw_ctx_set_float_out", "mcraw_pool_set_float_out",
     "mcraw_demosaic_batch", "mcraw_demosaic_display_batch", "mcraw_demosaic_yuv_batch", "mcraw_shade_batch",
-    "mcraw_stats_batch", "mcraw_stats_record_bytes",
+    "mcraw_stats_batch", "mcraw_stats_record_bytes", "mcraw_fixpix_batch",
 ]
 
 POST_BLACK, POST_PACK12, POST_PACK10, POST_PACK14 = 1, 2, 4, 8
@@ -338,6 +338,42 @@ def stats_clipped(st):
     d, single = _stats_arrays(st)
     r = d["nsat"] / np.maximum(d["cnt"], 1)
     return r[0] if single else r
+
+
+# defective pixels of mosaics (mcraw_fixpix_batch)
+FIXPIX_HOT, FIXPIX_COLD = 1, 2
+FIXPIX_MAX_LIST = 1 << 20
+
+
+class FixPix(C.Structure):
+    """struct mcraw_fixpix (include/mcraw_hip.h): flags, rank, the thresholds and black levels by CFA position, the device
+    list of packed pixels and the device records of the counts."""
+    _fields_ = [("flags", C.c_uint32), ("rank", C.c_uint32), ("rel_thr", C.c_uint32), ("nlist", C.c_uint32),
+                ("black", C.c_uint16 * 4), ("abs_thr", C.c_uint16 * 4), ("list", C.c_void_p), ("counts", C.c_void_p),
+                ("reserved", C.c_uint32 * 2)]
+
+
+def pack_pixels(xy):
+    """The static list of Context.fix_pixels / defects= from pixel coordinates: an integer array (K, 2) of (x, y) -> the
+    uint32 entries y << 16 | x, ascending and without duplicates (what mcraw_fixpix_batch's search expects).  K = 0 gives an
+    empty list.  Raises ValueError on another shape, a non-integer dtype, a coordinate outside 0 .. 65535, or more than
+    1 << 20 distinct pixels.  (Android's hotPixelMap is such a list of (x, y); under which key a .mcraw file carries it is
+    UNVERIFIED -- the reference reads no such key and no real clip was at hand -- so no helper here guesses it.)"""
+    import numpy as np
+    a = np.asarray(xy)
+    if a.ndim != 2 or a.shape[1] != 2:
+        if a.size == 0:
+            return np.zeros(0, np.uint32)
+        raise ValueError("pack_pixels: pixels must be (K, 2) of (x, y), not %r" % (a.shape,))
+    if a.dtype.kind not in "iu":
+        raise ValueError("pack_pixels: pixel coordinates must be integers, not %s" % a.dtype)
+    if a.size and (int(a.min()) < 0 or int(a.max()) > 65535):
+        raise ValueError("pack_pixels: a coordinate outside 0 .. 65535")
+    a = a.astype(np.uint32)
+    packed = np.unique((a[:, 1] << np.uint32(16)) | a[:, 0])  # ascending, duplicates gone
+    if packed.size > FIXPIX_MAX_LIST:
+        raise ValueError("pack_pixels: more than %d pixels" % FIXPIX_MAX_LIST)
+    return np.ascontiguousarray(packed, dtype=np.uint32)
 
 
 def _yuv_rule_ok(rows, sh, in_bits):
@@ -665,6 +701,9 @@ def load():
     lib.mcraw_stats_batch.restype = C.c_int
     lib.mcraw_stats_batch.argtypes = [C.c_void_p, C.POINTER(Stats), C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int,
                                       C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.mcraw_fixpix_batch.restype = C.c_int
+    lib.mcraw_fixpix_batch.argtypes = [C.c_void_p, C.POINTER(FixPix), C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int,
+                                       C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
     lib.mcraw_encode7.restype = C.c_size_t
     lib.mcraw_encode7.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int]
     _lib = lib
@@ -1101,6 +1140,101 @@ class Context:
             raise McrawError("mcraw_shade_batch failed (%d): %s" % (rc, self._lib.mcraw_last_error().decode()))
         return out
 
+    def fix_pixels(self, mosaic, *, black=(0, 0, 0, 0), abs_thr, rel_thr=0.0, rank=2, hot=True, cold=True, pixels=None,
+                   counts=False, out=None):
+        """Take the defective pixels out of uint16 mosaics resident on the context's device (mcraw_fixpix_batch).  A pixel
+        is compared with the rank-th largest (hot) / smallest (cold) of its eight neighbours of the same colour (distance
+        2, reflected at the edges) and replaced when it is beyond it by more than abs_thr + rel_thr * (that neighbour
+        above black); the replacement is the mean of the opposite pair that differs least.  The black level of the output
+        is that of the input.  mosaic: (N, H, W) or (H, W), rows contiguous (rows and frames may be strided), odd sizes are
+        fine.  black, abs_thr: one level or four, by CFA position (row & 1) * 2 + (col & 1), integers 0 .. 65535 (a
+        fractional level raises ValueError, also one that defects= forwards from the enclosing call's black=).  rel_thr: a float,
+        kept as rint(rel_thr * 256) in 0 .. 65535.  rank: 1 or 2 (2 finds two adjacent defects of one colour).  pixels: a
+        static list that is replaced unconditionally, in every frame, from neighbours that are not listed: an (K, 2)
+        integer array of (x, y) (packed by pack_pixels and uploaded on the current stream) or a 1-D uint32 / int32 CUDA
+        tensor of packed entries y << 16 | x, taken as it is and read when the kernels run (in stream order).  hot=False,
+        cold=False leaves the list alone at work.  out: None (a new contiguous tensor) or a uint16 tensor of the mosaic's
+        shape that does not overlap it (there is no in-place form).  counts=True also returns an int32 tensor (N, 2, 4)
+        ((2, 4) for an (H, W) mosaic): per frame the hot and the cold pixels the detector flagged, by CFA position, listed
+        pixels left out.  Queued on torch.cuda.current_stream(); nothing synchronises."""
+        import numpy as np
+        import torch
+        dev = self._torch_device(torch)
+        if not isinstance(mosaic, torch.Tensor) or mosaic.dtype != torch.uint16 or mosaic.device != dev or mosaic.dim() not in (2, 3):
+            raise ValueError("fix_pixels: mosaic must be a uint16 tensor (N, H, W) or (H, W) on %s" % dev)
+        four = lambda v: [v] * 4 if not hasattr(v, "__len__") else list(v)
+        black, abs_thr = four(black), four(abs_thr)
+        if len(black) != 4 or len(abs_thr) != 4 or any(v != int(v) or v < 0 or v > 65535 for v in black + abs_thr):
+            raise ValueError("fix_pixels: black and abs_thr are one level or four, by CFA position (row & 1) * 2 + (col & 1), "
+                             "each an integer 0 .. 65535 (the stage works on integers: a fractional level is not rounded for you)")
+        black, abs_thr = [int(v) for v in black], [int(v) for v in abs_thr]
+        rel = float(rel_thr)
+        if not np.isfinite(rel) or np.rint(rel * 256.0) < 0 or np.rint(rel * 256.0) > 65535:
+            raise ValueError("fix_pixels: rel_thr * 256 must round into 0 .. 65535, not %r" % (rel_thr,))
+        if rank not in (1, 2):
+            raise ValueError("fix_pixels: rank must be 1 or 2, not %r" % (rank,))
+        single = mosaic.dim() == 2
+        if out is None:
+            out = torch.empty(tuple(mosaic.shape), dtype=torch.uint16, device=dev)
+        elif not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(mosaic.shape) or out.dtype != torch.uint16 or out.device != dev:
+            raise ValueError("fix_pixels: out must be a uint16 tensor of shape %s on %s" % (tuple(mosaic.shape), dev))
+        mos, dst = (mosaic.unsqueeze(0), out.unsqueeze(0)) if single else (mosaic, out)
+        n, h, w = (int(v) for v in mos.shape)
+        cnt = torch.empty((n, 2, 4), dtype=torch.int32, device=dev) if counts else None  # (the call initialises the records)
+        res = (out, cnt[0] if single else cnt) if counts else out
+        if n == 0 or h == 0 or w == 0:
+            if counts:
+                cnt.zero_()
+            return res
+        if w > 1 and (mos.stride(2) != 1 or dst.stride(2) != 1):
+            raise ValueError("fix_pixels: the rows of the mosaic and of out must be contiguous")
+        lst = None
+        if pixels is not None:
+            if isinstance(pixels, torch.Tensor):
+                if pixels.device != dev or pixels.dim() != 1 or pixels.dtype not in (torch.uint32, torch.int32) or not pixels.is_contiguous():
+                    raise ValueError("fix_pixels: a pixels tensor must be a contiguous 1-D uint32 tensor of y << 16 | x on %s" % dev)
+                lst = pixels
+            else:
+                lst = torch.from_numpy(pack_pixels(pixels).view(np.int32)).to(dev)
+            if int(lst.numel()) > FIXPIX_MAX_LIST:
+                raise ValueError("fix_pixels: more than %d listed pixels" % FIXPIX_MAX_LIST)
+        s = FixPix()
+        s.flags = (FIXPIX_HOT if hot else 0) | (FIXPIX_COLD if cold else 0)
+        s.rank, s.rel_thr = int(rank), int(np.rint(rel * 256.0))
+        s.nlist = int(lst.numel()) if lst is not None else 0
+        for i in range(4):
+            s.black[i], s.abs_thr[i] = black[i], abs_thr[i]
+        s.list = lst.data_ptr() if s.nlist else None
+        s.counts = cnt.data_ptr() if counts else None
+        s.reserved[0] = s.reserved[1] = 0
+        ip = int(mos.stride(1)) if h > 1 else w
+        op = int(dst.stride(1)) if h > 1 else w
+        ifs = int(mos.stride(0)) if n > 1 else ip * h
+        ofs = int(dst.stride(0)) if n > 1 else op * h
+        cur, run = self._run_stream(torch, dev)
+        try:
+            rc = self._lib.mcraw_fixpix_batch(self._h, C.byref(s), C.c_void_p(mos.data_ptr()), ip, ifs, w, h, n,
+                                              C.c_void_p(dst.data_ptr()), op, ofs, C.c_void_p(run.cuda_stream))
+        finally:
+            if run is not cur:
+                mos.record_stream(run)
+                dst.record_stream(run)
+                if lst is not None:
+                    lst.record_stream(run)
+                if cnt is not None:
+                    cnt.record_stream(run)
+                cur.wait_stream(run)
+        if rc != 0:
+            raise McrawError("mcraw_fixpix_batch failed (%d): %s" % (rc, self._lib.mcraw_last_error().decode()))
+        return res
+
+    def _fix_defects(self, mos, defects, black, fn):
+        """defects= of the demosaic / decode methods: fix_pixels() with these keyword arguments (black: the call's own
+        unless given) into a scratch tensor of the caching allocator."""
+        if not isinstance(defects, dict) or "counts" in defects or "out" in defects:
+            raise ValueError("%s: defects must be a dict of fix_pixels' keyword arguments (without counts and out)" % fn)
+        return self.fix_pixels(mos, **{"black": black, **defects})
+
     def stats(self, mosaic, *, bins=256, shift=None, sat=65535, roi=None, out=None, accumulate=False):
         """Per-frame statistics of uint16 mosaics resident on the context's device (mcraw_stats_batch), by CFA position
         p = (y & 1) * 2 + (x & 1): a histogram of `bins` (64 .. 4096, a power of two) bins with bin = min(v >> shift,
@@ -1180,7 +1314,7 @@ class Context:
         return self.stats(scratch, bins=bins, shift=shift, sat=sat, roi=roi, out=out, accumulate=accumulate)
 
     def demosaic(self, mosaic, *, algo="mhc", dtype, white, black=(0, 0, 0, 0), cfa="rggb", gain=None, matrix=None,
-                 clip=False, out=None, check=True, shading=None):
+                 clip=False, out=None, check=True, shading=None, defects=None):
         """uint16 mosaics resident on the context's device -> planar linear RGB, (N, 3, H, W) for algo "mhc" (Malvar-He-
         Cutler) or (N, 3, H/2, W/2) for "bin2" (one pixel per 2x2 quad), as torch.float32 / float16 / bfloat16 ("f32" /
         "f16" / "bf16").  mosaic: a CUDA uint16 tensor (N, H, W) or (H, W) whose rows are contiguous (rows and frames may
@@ -1190,7 +1324,9 @@ class Context:
         torch.cuda.current_stream(); nothing synchronises.  `check` is accepted for symmetry with decode_rgb (the
         arguments are always checked; there are no per-frame statuses).  shading: a lens-shading gain map as shade() takes
         it, applied in front of the demosaic with this call's black levels and top 65535, into a scratch tensor (the
-        caller's mosaic is left as it is); None: no such stage."""
+        caller's mosaic is left as it is); None: no such stage.  defects: a dict of fix_pixels()' keyword arguments (black
+        defaults to this call's): the defective pixels are taken out first, into a scratch tensor, in front of shading=
+        (gains change the differences between neighbours); None: no such stage."""
         import torch
         if algo not in _RGB_ALGOS:
             raise ValueError("algo must be 'mhc' or 'bin2', not %r" % (algo,))
@@ -1204,6 +1340,8 @@ class Context:
             raise ValueError("demosaic: mosaic must be a uint16 tensor (N, H, W) or (H, W) on %s" % dev)
         single = mosaic.dim() == 2
         mos = mosaic.unsqueeze(0) if single else mosaic
+        if defects is not None and mos.numel():  # into a scratch tensor, in front of the gains
+            mos = self._fix_defects(mos, defects, black, "demosaic")
         if shading is not None and mos.numel():  # into a scratch tensor: the caller's mosaic stays as it is
             mos = self.shade(mos, shading, black=black)
         n, h, w = (int(v) for v in mos.shape)
@@ -1271,14 +1409,17 @@ class Context:
         return scratch
 
     def decode_rgb(self, inputs, width, height, type, *, algo="mhc", dtype, white, black=(0, 0, 0, 0), cfa="rggb",
-                   gain=None, matrix=None, clip=False, out=None, check=True, shading=None):
+                   gain=None, matrix=None, clip=False, out=None, check=True, shading=None, defects=None):
         """Decode frames of one geometry that are resident in HBM and demosaic them (demosaic()): (N, 3, H, W) for "mhc",
         (N, 3, H/2, W/2) for "bin2".  inputs: uint8 CUDA tensors, or (device pointer, length) pairs.  The plain uint16
         mosaics go to a scratch tensor of torch's caching allocator; both steps are queued on torch.cuda.current_stream().
         check=True synchronises after the decode and raises McrawError naming the frames that failed; check=False returns
         at once.  The stage the context had before the call is restored afterwards.  shading: a lens-shading gain map
-        (shade()), applied to the scratch mosaics in place before the demosaic."""
+        (shade()), applied to the scratch mosaics in place before the demosaic.  defects: a dict of fix_pixels()' keyword
+        arguments (black defaults to this call's), applied in front of shading= into a second scratch tensor."""
         scratch = self._decode_scratch(inputs, width, height, type, check, "decode_rgb")
+        if defects is not None and scratch.numel():
+            scratch = self._fix_defects(scratch, defects, black, "decode_rgb")
         if shading is not None:
             self.shade(scratch, shading, black=black, out=scratch)
         return self.demosaic(scratch, algo=algo, dtype=dtype, white=white, black=black, cfa=cfa, gain=gain, matrix=matrix,
@@ -1314,7 +1455,8 @@ class Context:
         return lut, own
 
     def demosaic_display(self, mosaic, *, algo="mhc", white, black=(0, 0, 0, 0), cfa="rggb", gain=None, matrix=None,
-                         transfer="srgb", lut_size=4096, dtype=None, layout="hwc", bits=None, out=None, check=True, shading=None):
+                         transfer="srgb", lut_size=4096, dtype=None, layout="hwc", bits=None, out=None, check=True, shading=None,
+                         defects=None):
         """uint16 mosaics resident on the context's device -> display-ready integer RGB: the demosaic and colours of
         demosaic(), then clamp to [0, 1], index a transfer-curve LUT of L entries at rint(c * (L - 1)) and store the entry
         (its low byte for uint8).  dtype: torch.uint8 (default) or torch.uint16; layout "hwc" gives (N, Ho, Wo, 3), "chw"
@@ -1322,7 +1464,7 @@ class Context:
         on [0, 1] -- built by transfer_lut(transfer, lut_size, bits), bits 8 for uint8 and 16 for uint16 unless given --
         or a ready 1-D uint16 LUT (host array or CUDA tensor) whose length is a power of two, 256 .. 65536.  Queued on
         torch.cuda.current_stream(); nothing synchronises, and a caller's LUT is read when the kernels run (in stream
-        order).  `check` is accepted for symmetry with decode_display.  shading: as demosaic()."""
+        order).  `check` is accepted for symmetry with decode_display.  shading, defects: as demosaic()."""
         import torch
         if algo not in _RGB_ALGOS:
             raise ValueError("algo must be 'mhc' or 'bin2', not %r" % (algo,))
@@ -1341,6 +1483,8 @@ class Context:
             raise ValueError("demosaic_display: mosaic must be a uint16 tensor (N, H, W) or (H, W) on %s" % dev)
         single = mosaic.dim() == 2
         mos = mosaic.unsqueeze(0) if single else mosaic
+        if defects is not None and mos.numel():  # into a scratch tensor, in front of the gains
+            mos = self._fix_defects(mos, defects, black, "demosaic_display")
         if shading is not None and mos.numel():  # into a scratch tensor: the caller's mosaic stays as it is
             mos = self.shade(mos, shading, black=black)
         n, h, w = (int(v) for v in mos.shape)
@@ -1380,12 +1524,15 @@ class Context:
         return out
 
     def decode_display(self, inputs, width, height, type, *, algo="mhc", white, black=(0, 0, 0, 0), cfa="rggb", gain=None,
-                       matrix=None, transfer="srgb", lut_size=4096, dtype=None, layout="hwc", bits=None, out=None, check=True, shading=None):
+                       matrix=None, transfer="srgb", lut_size=4096, dtype=None, layout="hwc", bits=None, out=None, check=True, shading=None,
+                       defects=None):
         """Decode frames of one geometry that are resident in HBM and turn them into display-ready RGB
         (demosaic_display()), as decode_rgb does: the plain uint16 mosaics go to a scratch tensor, both steps are queued on
         torch.cuda.current_stream(), check=True synchronises after the decode and raises McrawError naming the frames that
-        failed, and the context's stage is restored afterwards.  shading: as decode_rgb()."""
+        failed, and the context's stage is restored afterwards.  shading, defects: as decode_rgb()."""
         scratch = self._decode_scratch(inputs, width, height, type, check, "decode_display")
+        if defects is not None and scratch.numel():
+            scratch = self._fix_defects(scratch, defects, black, "decode_display")
         if shading is not None:
             self.shade(scratch, shading, black=black, out=scratch)
         return self.demosaic_display(scratch, algo=algo, white=white, black=black, cfa=cfa, gain=gain, matrix=matrix,
@@ -1393,7 +1540,8 @@ class Context:
                                      check=check)
 
     def demosaic_yuv(self, mosaic, *, algo="mhc", white, black=(0, 0, 0, 0), cfa="rggb", gain=None, matrix=None, fmt="nv12",
-                     standard="bt709", range="limited", transfer="bt709", lut_size=4096, in_bits=None, out=None, check=True, shading=None):
+                     standard="bt709", range="limited", transfer="bt709", lut_size=4096, in_bits=None, out=None, check=True, shading=None,
+                     defects=None):
         """uint16 mosaics resident on the context's device -> video-ready Y'CbCr 4:2:0: the demosaic, colours, clamp and
         transfer-curve LUT of demosaic_display(), then the integer matrix of yuv_matrix(standard, range) and a 2x2 box
         average for the chroma (sited at the block's centre).  fmt "nv12": torch.uint8; "p010": torch.uint16 holding
@@ -1402,7 +1550,7 @@ class Context:
         gives the two as views.  Ho and Wo must be even (bin2: H and W multiples of 4).  transfer: as demosaic_display; a
         built-in curve is transfer_lut(transfer, lut_size, in_bits), in_bits defaulting to 12 (nv12) or 16 (p010); a ready
         LUT may hold entries of any in_bits 8 .. 16 (higher bits are masked off).  Queued on torch.cuda.current_stream();
-        nothing synchronises.  `check` is accepted for symmetry with decode_yuv.  shading: as demosaic()."""
+        nothing synchronises.  `check` is accepted for symmetry with decode_yuv.  shading, defects: as demosaic()."""
         import torch
         if algo not in _RGB_ALGOS:
             raise ValueError("algo must be 'mhc' or 'bin2', not %r" % (algo,))
@@ -1420,6 +1568,8 @@ class Context:
             raise ValueError("demosaic_yuv: mosaic must be a uint16 tensor (N, H, W) or (H, W) on %s" % dev)
         single = mosaic.dim() == 2
         mos = mosaic.unsqueeze(0) if single else mosaic
+        if defects is not None and mos.numel():  # into a scratch tensor, in front of the gains
+            mos = self._fix_defects(mos, defects, black, "demosaic_yuv")
         if shading is not None and mos.numel():  # into a scratch tensor: the caller's mosaic stays as it is
             mos = self.shade(mos, shading, black=black)
         n, h, w = (int(v) for v in mos.shape)
@@ -1463,12 +1613,14 @@ class Context:
 
     def decode_yuv(self, inputs, width, height, type, *, algo="mhc", white, black=(0, 0, 0, 0), cfa="rggb", gain=None,
                    matrix=None, fmt="nv12", standard="bt709", range="limited", transfer="bt709", lut_size=4096, in_bits=None,
-                   out=None, check=True, shading=None):
+                   out=None, check=True, shading=None, defects=None):
         """Decode frames of one geometry that are resident in HBM and turn them into NV12 / P010 (demosaic_yuv()), as
         decode_display does: the plain uint16 mosaics go to a scratch tensor, both steps are queued on
         torch.cuda.current_stream(), check=True synchronises after the decode and raises McrawError naming the frames that
-        failed, and the context's stage is restored afterwards.  shading: as decode_rgb()."""
+        failed, and the context's stage is restored afterwards.  shading, defects: as decode_rgb()."""
         scratch = self._decode_scratch(inputs, width, height, type, check, "decode_yuv")
+        if defects is not None and scratch.numel():
+            scratch = self._fix_defects(scratch, defects, black, "decode_yuv")
         if shading is not None:
             self.shade(scratch, shading, black=black, out=scratch)
         return self.demosaic_yuv(scratch, algo=algo, white=white, black=black, cfa=cfa, gain=gain, matrix=matrix, fmt=fmt,

@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
-"""Resource report of the demosaic kernels (csrc/mcraw_rgb.hip), of the lens-shading kernel (csrc/mcraw_shade.hip) and of
-the statistics kernels (csrc/mcraw_stats.hip): compiles the files for gfx950 with -Rpass-analysis=kernel-resource-usage (no GPU
-needed) and prints one line per instance in the format of profiles/rgb_resources.txt / display_resources.txt /
-yuv_resources.txt / shade_resources.txt / stats_resources.txt.
+"""Resource report of the demosaic kernels (csrc/mcraw_rgb.hip), of the lens-shading kernel (csrc/mcraw_shade.hip), of the
+statistics kernels (csrc/mcraw_stats.hip) and of the defective-pixel kernels (csrc/mcraw_fixpix.hip): compiles the files for
+gfx950 with -Rpass-analysis=kernel-resource-usage (no GPU needed) and prints one line per instance in the format of
+profiles/rgb_resources.txt / display_resources.txt / yuv_resources.txt / shade_resources.txt / stats_resources.txt /
+fixpix_resources.txt.
 
     python tools/rgb_resources.py            # every instance
-    python tools/rgb_resources.py --check    # the figures in the five committed files must equal the compiler's; exit 1 if not
+    python tools/rgb_resources.py --check    # the figures in the six committed files must equal the compiler's; exit 1 if not
 """
 import os
 import re
@@ -23,6 +24,8 @@ SHADE_FILE = "shade_resources.txt"
 RGB_NAME = r"Function Name: _ZN5mcraw\d+(krgb_mhc|krgb_bin2)y?ILi(\d+)ELi(\d)EEEv"
 STATS_FILE = "stats_resources.txt"
 STATS_NAME = r"Function Name: _ZN5mcraw\d+(kstats_init|kstats)(?:ILi(\d+)EEEv|E)"  # kstats<bins_log2>, and the kernel that empties the records
+FIXPIX_FILE = "fixpix_resources.txt"
+FIXPIX_NAME = r"Function Name: _ZN5mcraw\d+(kfixpix_init|kfixpix_list|kfixpix)(?:ILb([01])EEEv|E)"  # kfixpix<NT>, the list pass, the counts' init
 SHADE_NAME = r"Function Name: _ZN5mcraw\d+(kshade)ILb([01])EEEv"  # kshade<NT>: `sc1 nt` streaming stores or plain ones
 
 
@@ -31,6 +34,10 @@ def _label(m):
         return "kstats_init"
     if m.group(1) == "kstats":
         return "kstats<B=%d>" % (1 << int(m.group(2)))
+    if m.group(1) in ("kfixpix_init", "kfixpix_list"):
+        return m.group(1)
+    if m.group(1) == "kfixpix":
+        return "kfixpix<%s>" % ("stream" if m.group(2) == "1" else "plain")
     if m.group(1) == "kshade":
         return "kshade<%s>" % ("stream" if m.group(2) == "1" else "plain")
     return "%s<%s,S=%s>" % (m.group(1), KINDS[int(m.group(2))], m.group(3))
@@ -74,11 +81,13 @@ def _check(files, rep, prefix):
 
 def main():
     rep, shade, stats = report(), report("mcraw_shade.hip", SHADE_NAME), report("mcraw_stats.hip", STATS_NAME)
+    fixpix = report("mcraw_fixpix.hip", FIXPIX_NAME)
     if "--check" not in sys.argv:
-        for line in list(rep.values()) + list(shade.values()) + list(stats.values()):
+        for line in list(rep.values()) + list(shade.values()) + list(stats.values()) + list(fixpix.values()):
             print(line)
         return 0
-    return _check(FILES, rep, "krgb_") | _check((SHADE_FILE,), shade, "kshade") | _check((STATS_FILE,), stats, "kstats")
+    return _check(FILES, rep, "krgb_") | _check((SHADE_FILE,), shade, "kshade") | _check((STATS_FILE,), stats, "kstats") | \
+        _check((FIXPIX_FILE,), fixpix, "kfixpix")
 
 
 if __name__ == "__main__":
