@@ -596,6 +596,55 @@ typedef struct mcraw_fixpix {
 int mcraw_fixpix_batch(mcraw_ctx *ctx, const mcraw_fixpix *f, const uint16_t *in, size_t in_pitch, size_t in_frame_stride,
                        int width, int height, int n, uint16_t *out, size_t out_pitch, size_t out_frame_stride, void *stream);
 
+/* ---- uint16 mosaics -> denoised uint16 mosaics ----------------------------------------------------------------------------
+ *
+ * Noise-adaptive smoothing of `n` uint16 mosaics of width x height on the raw sensor values, where the noise follows
+ * variance = S * signal + O per CFA position (Android's noiseProfile, DNG's NoiseProfile): in front of the lens-shading
+ * gains, the demosaic and the transfer curve, which make that model position-dependent, correlated and non-linear.  The
+ * output is a mosaic of the same black level, so everything that takes a mosaic takes the result.  Pitches and frame strides
+ * count uint16 elements.  Integers only: bit-exact.
+ * Neighbours.  All neighbours lie on the pixel's own lattice (the same colour for every Bayer arrangement; the call never
+ * needs the CFA): the offsets (dy, dx) run over {-2R .. 2R step 2}^2 without (0, 0), R = radius: 8 neighbours at radius 1,
+ * 24 at radius 2.  For each axis independently and d in {-4, -2, +2, +4} the neighbour coordinate of c is c' = c + d; if that
+ * is outside [0, size), c' = c - d; if that is outside too, c' = c (the rule of the defective-pixel stage, extended to
+ * distance 4).  Duplicates that the reflection makes count with their multiplicity, so frames of width or height 1 .. 8
+ * are defined, not rejected.
+ * Per pixel of value c at CFA position p = (y & 1) * 2 + (x & 1), in frame f, with L = 1 << lut_log2 and the table
+ * t = (nluts == 1 ? 0 : f):
+ *   r   = lut[t][p][min(c >> shift, L - 1)]              uint16: 4096 / (the cut-off in DN) at the pixel's level
+ *   for every neighbour value a:
+ *       x = min((|a - c| * r) >> 8, 16)                  |a - c| * r <= 65535 * 65535 < 2^32
+ *       w = 256 - x * x                                  0 .. 256: 1 - (difference / cut-off)^2 in Q8
+ *   num = 256 * c + sum(w * a)                           <= 6400 * 65535 < 2^29
+ *   den = 256     + sum(w)                               256 .. 6400
+ *   m   = (num + (den >> 1)) / den                       unsigned integer division (floor)
+ *   out = c + (((m - c) * amount + 128) >> 8)            signed, arithmetic shift (floor); amount 256 gives m
+ * out lies between c and m, so there is no clamp.  A table of all 65535 is the identity (any |a - c| >= 1 gives x = 16), a
+ * table of all 0 is the reflected box mean, and a flat frame comes back bit for bit.
+ * lut: the caller's DEVICE memory, 16-byte aligned, (nluts, 4, L) uint16; read by the queued kernel in stream order and never
+ * copied into or cached by the context (two calls with the same pointer and new contents in between each see their own).
+ * There is no in-place form: every pixel reads its neighbours.  `in` and `out` may sit at any 2-byte alignment with any pitch
+ * (16-byte accesses where base, pitch and stride allow it).
+ * `stream`: a hipStream_t, NULL = the context's own stream; the call queues the work and returns without synchronising.
+ * It takes no decode serial and leaves the decode slots, mcraw_ctx_errors, mcraw_ctx_last_serial and the context's stage
+ * alone.  n == 0 is a no-op.  The launches have no id in mcraw_ctx_kernel_ms (time them with stream events).
+ * Rejected (returns < 0, mcraw_last_error says why, starting with "mcraw_denoise_batch: ", nothing is written): a NULL `d`,
+ * `in`, `out` or `lut`; an odd `in` or `out` address; a `lut` that is not 16-byte aligned; width or height outside
+ * 1 .. 65536; a pitch below width; n > 1 and a frame stride below (height - 1) * pitch + width; radius not 1 or 2; amount
+ * outside 1 .. 256; lut_log2 outside 6 .. 10; shift above 15; nluts not 1 or n; a non-zero `reserved`; input and output
+ * extents that overlap at all. */
+typedef struct mcraw_denoise {
+    uint32_t radius;       /* 1: the 8 neighbours at distance 2;  2: the 24 at distances 2 and 4        */
+    uint32_t amount;       /* 1 .. 256: how much of the correction is applied, 256 = all                */
+    uint32_t lut_log2;     /* 6 .. 10: L = 1 << lut_log2 entries per CFA position                       */
+    uint32_t shift;        /* 0 .. 15: entry of a pixel of value c = min(c >> shift, L - 1)             */
+    uint32_t nluts;        /* 1: one table for the batch;  n: one per frame, back to back               */
+    uint32_t reserved[3];  /* must be 0                                                                 */
+    const uint16_t *lut;   /* DEVICE memory, 16-byte aligned: (nluts, 4, L)                             */
+} mcraw_denoise;           /* sizeof 40; amount 4, lut_log2 8, shift 12, nluts 16, reserved 20, lut 32  */
+int mcraw_denoise_batch(mcraw_ctx *ctx, const mcraw_denoise *d, const uint16_t *in, size_t in_pitch, size_t in_frame_stride,
+                        int width, int height, int n, uint16_t *out, size_t out_pitch, size_t out_frame_stride, void *stream);
+
 /* ---- environment ------------------------------------------------------------------------------
  * Read when a context (or pool) is created, never afterwards:
  *   MCRAW_DEVICE=n, MCRAW_DEVICES=all|0,1,5   default device of the five-argument entry points / members of a default pool

@@ -17,7 +17,7 @@ __all__ = ["lib_path", "load", "Context", "Pool", "Frame", "EncFrame", "FloatOut
            "RgbParams", "RgbColor", "RGB_KERNELS", "rgb_color", "Display", "transfer_lut", "DISP_U8", "DISP_U16",
            "DISP_CHW", "DISP_HWC", "Yuv", "YUV_NV12", "YUV_P010", "yuv_matrix", "yuv_planes", "Shade", "gain_map",
            "shading_map", "Stats", "STATS_ACCUMULATE", "FrameStats", "stats_white_balance", "stats_percentile",
-           "stats_clipped", "FixPix", "FIXPIX_HOT", "FIXPIX_COLD", "pack_pixels"]
+           "stats_clipped", "FixPix", "FIXPIX_HOT", "FIXPIX_COLD", "pack_pixels", "Denoise", "noise_lut"]
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 
@@ -45,7 +45,7 @@ ABI_SYMBOLS = [
     "mcraw_ctx_last_serial", "mcraw_ctx_batch_status", "mcraw_ctx_errors", "mcraw_ctx_side_parts", "mcraw_ctx_host_way",
     "mcraw_encode_bound7", "mcraw_encode_batch", "mcraw_encode7", "mcraw_ctx_set_float_out", "mcraw_pool_set_float_out",
     "mcraw_demosaic_batch", "mcraw_demosaic_display_batch", "mcraw_demosaic_yuv_batch", "mcraw_shade_batch",
-    "mcraw_stats_batch", "mcraw_stats_record_bytes", "mcraw_fixpix_batch",
+    "mcraw_stats_batch", "mcraw_stats_record_bytes", "mcraw_fixpix_batch", "mcraw_denoise_batch",
 ]
 
 POST_BLACK, POST_PACK12, POST_PACK10, POST_PACK14 = 1, 2, 4, 8
@@ -376,6 +376,59 @@ def pack_pixels(xy):
     return np.ascontiguousarray(packed, dtype=np.uint32)
 
 
+# noise-adaptive denoising of mosaics (mcraw_denoise_batch)
+class Denoise(C.Structure):
+    """struct mcraw_denoise (include/mcraw_hip.h): radius, amount in Q8, the table's size and shift, how many tables, and the
+    device table (nluts, 4, L) of uint16."""
+    _fields_ = [("radius", C.c_uint32), ("amount", C.c_uint32), ("lut_log2", C.c_uint32), ("shift", C.c_uint32),
+                ("nluts", C.c_uint32), ("reserved", C.c_uint32 * 3), ("lut", C.c_void_p)]
+
+
+def noise_lut(S, O, black, white, strength=3.0, entries=256, top=None):
+    """The table of Context.denoise / denoise= from a noise profile: variance = S * x + O on values x normalised to [0, 1],
+    the form in which Android's noiseProfile and DNG's NoiseProfile state it.  S, O, black: scalars or four values by CFA
+    position (row & 1) * 2 + (col & 1); white: the white level; top: the largest value the table has to tell apart (white
+    unless given).  Returns (lut, shift): shift is the smallest one with (top >> shift) < entries, lut is uint16 (4,
+    entries); entry i of position p, in float64, with m = (i << shift) + (1 << shift) / 2 and R = white - black[p]:
+    var = S[p] * R * max(m - black[p], 0) + O[p] * R * R in DN^2, entry = clip(rint(4096 / (strength * sqrt(var))), 1,
+    65535), and 65535 where var is 0 -- the weight of a neighbour reaches 0 at `strength` standard deviations.  Raises
+    ValueError for entries that is not a power of two in 64 .. 1024, white <= black, a negative S or O, or strength <= 0."""
+    import numpy as np
+
+    def four(v, name):
+        a = np.asarray(v, dtype=np.float64)
+        if a.ndim == 0:
+            a = np.full(4, float(a))
+        if a.shape != (4,) or not np.isfinite(a).all():
+            raise ValueError("noise_lut: %s is one finite value or four, by CFA position" % name)
+        return a
+
+    S, O, black = four(S, "S"), four(O, "O"), four(black, "black")
+    entries = int(entries)
+    if entries not in (64, 128, 256, 512, 1024):
+        raise ValueError("noise_lut: entries must be a power of two in 64 .. 1024, not %r" % (entries,))
+    white = float(white)
+    if not np.isfinite(white) or (white <= black).any():
+        raise ValueError("noise_lut: white must be above every black level")
+    if (S < 0).any() or (O < 0).any():
+        raise ValueError("noise_lut: S and O must not be negative")
+    strength = float(strength)
+    if not strength > 0 or not np.isfinite(strength):
+        raise ValueError("noise_lut: strength must be above 0, not %r" % (strength,))
+    top = int(white if top is None else top)
+    if top < 0 or top > 65535:
+        raise ValueError("noise_lut: top must be 0 .. 65535")
+    shift = 0
+    while (top >> shift) >= entries:
+        shift += 1
+    m = (np.arange(entries, dtype=np.float64) * (1 << shift) + (1 << shift) / 2.0)[None, :]
+    R = (white - black)[:, None]
+    var = S[:, None] * R * np.maximum(m - black[:, None], 0.0) + O[:, None] * R * R
+    with np.errstate(divide="ignore"):
+        e = np.where(var > 0, np.clip(np.rint(4096.0 / (strength * np.sqrt(var))), 1, 65535), 65535)
+    return np.ascontiguousarray(e, dtype=np.uint16), shift
+
+
 def _yuv_rule_ok(rows, sh, in_bits):
     """The overflow rule of mcraw_demosaic_yuv_batch: no int32 sum can wrap."""
     return all(4 * ((1 << in_bits) - 1) * sum(abs(int(c)) for c in r) + (1 << (sh + 1)) < (1 << 31) for r in rows)
@@ -704,6 +757,9 @@ def load():
     lib.mcraw_fixpix_batch.restype = C.c_int
     lib.mcraw_fixpix_batch.argtypes = [C.c_void_p, C.POINTER(FixPix), C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int,
                                        C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
+    lib.mcraw_denoise_batch.restype = C.c_int
+    lib.mcraw_denoise_batch.argtypes = [C.c_void_p, C.POINTER(Denoise), C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int,
+                                        C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
     lib.mcraw_encode7.restype = C.c_size_t
     lib.mcraw_encode7.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int]
     _lib = lib
@@ -1235,6 +1291,80 @@ class Context:
             raise ValueError("%s: defects must be a dict of fix_pixels' keyword arguments (without counts and out)" % fn)
         return self.fix_pixels(mos, **{"black": black, **defects})
 
+    def denoise(self, mosaic, lut, shift, radius=2, amount=1.0, out=None):
+        """Noise-adaptive smoothing of uint16 mosaics resident on the context's device (mcraw_denoise_batch): every pixel
+        becomes the weighted mean of itself and its 8 (radius 1) or 24 (radius 2) neighbours of the same colour (distances
+        2 and 4, reflected at the edges); a neighbour's weight is 1 - (difference / cut-off)^2, 0 beyond the cut-off, and
+        the cut-off at the pixel's level and CFA position is what the table says (noise_lut makes one from a noise
+        profile).  The black level of the output is that of the input.  mosaic: (N, H, W) or (H, W), rows contiguous (rows
+        and frames may be strided), odd sizes are fine.  lut: uint16 (4, L) for all frames or (N, 4, L) per frame, L a
+        power of two in 64 .. 1024, planes by CFA position (row & 1) * 2 + (col & 1): a CUDA tensor, read when the kernel
+        runs (in stream order), or a host array, uploaded on the current stream.  shift: 0 .. 15, a pixel of value c uses
+        entry min(c >> shift, L - 1).  amount: how much of the correction is applied, a float kept as rint(amount * 256) in
+        1 .. 256.  out: None (a new contiguous tensor) or a uint16 tensor of the mosaic's shape that does not overlap it
+        (there is no in-place form).  Queued on torch.cuda.current_stream(); nothing synchronises."""
+        import numpy as np
+        import torch
+        dev = self._torch_device(torch)
+        if not isinstance(mosaic, torch.Tensor) or mosaic.dtype != torch.uint16 or mosaic.device != dev or mosaic.dim() not in (2, 3):
+            raise ValueError("denoise: mosaic must be a uint16 tensor (N, H, W) or (H, W) on %s" % dev)
+        if radius not in (1, 2):
+            raise ValueError("denoise: radius must be 1 or 2, not %r" % (radius,))
+        amt = float(amount)
+        if not np.isfinite(amt) or np.rint(amt * 256.0) < 1 or np.rint(amt * 256.0) > 256:
+            raise ValueError("denoise: amount * 256 must round into 1 .. 256, not %r" % (amount,))
+        if shift != int(shift) or not 0 <= int(shift) <= 15:
+            raise ValueError("denoise: shift must be an integer 0 .. 15, not %r" % (shift,))
+        if out is None:
+            out = torch.empty(tuple(mosaic.shape), dtype=torch.uint16, device=dev)
+        elif not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(mosaic.shape) or out.dtype != torch.uint16 or out.device != dev:
+            raise ValueError("denoise: out must be a uint16 tensor of shape %s on %s" % (tuple(mosaic.shape), dev))
+        mos, dst = (mosaic.unsqueeze(0), out.unsqueeze(0)) if mosaic.dim() == 2 else (mosaic, out)
+        n, h, w = (int(v) for v in mos.shape)
+        if isinstance(lut, np.ndarray):
+            if lut.dtype != np.uint16:
+                raise ValueError("denoise: a lut array must be uint16 (noise_lut makes one)")
+            lut = torch.from_numpy(np.ascontiguousarray(lut).view(np.int16)).to(dev).view(torch.uint16)
+        if not isinstance(lut, torch.Tensor) or lut.dtype != torch.uint16 or lut.device != dev or lut.dim() not in (2, 3) \
+                or not lut.is_contiguous():
+            raise ValueError("denoise: lut must be a contiguous uint16 tensor (4, L) or (N, 4, L) on %s" % dev)
+        nluts, L = (int(lut.shape[0]) if lut.dim() == 3 else 1), int(lut.shape[-1])
+        if int(lut.shape[-2]) != 4 or L not in (64, 128, 256, 512, 1024) or (lut.dim() == 3 and nluts != n):
+            raise ValueError("denoise: lut must hold four planes of 64 .. 1024 (a power of two) entries, for all frames or for "
+                             "each of the %d" % n)
+        if n == 0 or h == 0 or w == 0:
+            return out
+        if w > 1 and (mos.stride(2) != 1 or dst.stride(2) != 1):
+            raise ValueError("denoise: the rows of the mosaic and of out must be contiguous")
+        s = Denoise()
+        s.radius, s.amount, s.lut_log2, s.shift, s.nluts = int(radius), int(np.rint(amt * 256.0)), L.bit_length() - 1, int(shift), nluts
+        s.reserved[0] = s.reserved[1] = s.reserved[2] = 0
+        s.lut = lut.data_ptr()
+        ip = int(mos.stride(1)) if h > 1 else w
+        op = int(dst.stride(1)) if h > 1 else w
+        ifs = int(mos.stride(0)) if n > 1 else ip * h
+        ofs = int(dst.stride(0)) if n > 1 else op * h
+        cur, run = self._run_stream(torch, dev)
+        try:
+            rc = self._lib.mcraw_denoise_batch(self._h, C.byref(s), C.c_void_p(mos.data_ptr()), ip, ifs, w, h, n,
+                                               C.c_void_p(dst.data_ptr()), op, ofs, C.c_void_p(run.cuda_stream))
+        finally:
+            if run is not cur:
+                mos.record_stream(run)
+                dst.record_stream(run)
+                lut.record_stream(run)
+                cur.wait_stream(run)
+        if rc != 0:
+            raise McrawError("mcraw_denoise_batch failed (%d): %s" % (rc, self._lib.mcraw_last_error().decode()))
+        return out
+
+    def _denoise_stage(self, mos, denoise, fn):
+        """denoise= of the demosaic / decode methods: denoise() with these keyword arguments into a scratch tensor of the
+        caching allocator."""
+        if not isinstance(denoise, dict) or "out" in denoise or "mosaic" in denoise:
+            raise ValueError("%s: denoise must be a dict of denoise()'s keyword arguments (without out)" % fn)
+        return self.denoise(mos, **denoise)
+
     def stats(self, mosaic, *, bins=256, shift=None, sat=65535, roi=None, out=None, accumulate=False):
         """Per-frame statistics of uint16 mosaics resident on the context's device (mcraw_stats_batch), by CFA position
         p = (y & 1) * 2 + (x & 1): a histogram of `bins` (64 .. 4096, a power of two) bins with bin = min(v >> shift,
@@ -1314,7 +1444,7 @@ class Context:
         return self.stats(scratch, bins=bins, shift=shift, sat=sat, roi=roi, out=out, accumulate=accumulate)
 
     def demosaic(self, mosaic, *, algo="mhc", dtype, white, black=(0, 0, 0, 0), cfa="rggb", gain=None, matrix=None,
-                 clip=False, out=None, check=True, shading=None, defects=None):
+                 clip=False, out=None, check=True, shading=None, defects=None, denoise=None):
         """uint16 mosaics resident on the context's device -> planar linear RGB, (N, 3, H, W) for algo "mhc" (Malvar-He-
         Cutler) or (N, 3, H/2, W/2) for "bin2" (one pixel per 2x2 quad), as torch.float32 / float16 / bfloat16 ("f32" /
         "f16" / "bf16").  mosaic: a CUDA uint16 tensor (N, H, W) or (H, W) whose rows are contiguous (rows and frames may
@@ -1326,7 +1456,9 @@ class Context:
         it, applied in front of the demosaic with this call's black levels and top 65535, into a scratch tensor (the
         caller's mosaic is left as it is); None: no such stage.  defects: a dict of fix_pixels()' keyword arguments (black
         defaults to this call's): the defective pixels are taken out first, into a scratch tensor, in front of shading=
-        (gains change the differences between neighbours); None: no such stage."""
+        (gains change the differences between neighbours); None: no such stage.  denoise: a dict of denoise()'s
+        keyword arguments (lut, shift, radius, amount), applied behind defects= and in front of shading=, into a scratch
+        tensor: the noise model holds for the sensor's values, not for the shaded ones; None: no such stage."""
         import torch
         if algo not in _RGB_ALGOS:
             raise ValueError("algo must be 'mhc' or 'bin2', not %r" % (algo,))
@@ -1342,6 +1474,8 @@ class Context:
         mos = mosaic.unsqueeze(0) if single else mosaic
         if defects is not None and mos.numel():  # into a scratch tensor, in front of the gains
             mos = self._fix_defects(mos, defects, black, "demosaic")
+        if denoise is not None and mos.numel():  # on the sensor's values: behind the defects, in front of the gains
+            mos = self._denoise_stage(mos, denoise, "demosaic")
         if shading is not None and mos.numel():  # into a scratch tensor: the caller's mosaic stays as it is
             mos = self.shade(mos, shading, black=black)
         n, h, w = (int(v) for v in mos.shape)
@@ -1409,17 +1543,20 @@ class Context:
         return scratch
 
     def decode_rgb(self, inputs, width, height, type, *, algo="mhc", dtype, white, black=(0, 0, 0, 0), cfa="rggb",
-                   gain=None, matrix=None, clip=False, out=None, check=True, shading=None, defects=None):
+                   gain=None, matrix=None, clip=False, out=None, check=True, shading=None, defects=None, denoise=None):
         """Decode frames of one geometry that are resident in HBM and demosaic them (demosaic()): (N, 3, H, W) for "mhc",
         (N, 3, H/2, W/2) for "bin2".  inputs: uint8 CUDA tensors, or (device pointer, length) pairs.  The plain uint16
         mosaics go to a scratch tensor of torch's caching allocator; both steps are queued on torch.cuda.current_stream().
         check=True synchronises after the decode and raises McrawError naming the frames that failed; check=False returns
         at once.  The stage the context had before the call is restored afterwards.  shading: a lens-shading gain map
         (shade()), applied to the scratch mosaics in place before the demosaic.  defects: a dict of fix_pixels()' keyword
-        arguments (black defaults to this call's), applied in front of shading= into a second scratch tensor."""
+        arguments (black defaults to this call's), applied in front of shading= into a second scratch tensor.  denoise: a
+        dict of denoise()'s keyword arguments, applied behind defects= and in front of shading=."""
         scratch = self._decode_scratch(inputs, width, height, type, check, "decode_rgb")
         if defects is not None and scratch.numel():
             scratch = self._fix_defects(scratch, defects, black, "decode_rgb")
+        if denoise is not None and scratch.numel():
+            scratch = self._denoise_stage(scratch, denoise, "decode_rgb")
         if shading is not None:
             self.shade(scratch, shading, black=black, out=scratch)
         return self.demosaic(scratch, algo=algo, dtype=dtype, white=white, black=black, cfa=cfa, gain=gain, matrix=matrix,
@@ -1456,7 +1593,7 @@ class Context:
 
     def demosaic_display(self, mosaic, *, algo="mhc", white, black=(0, 0, 0, 0), cfa="rggb", gain=None, matrix=None,
                          transfer="srgb", lut_size=4096, dtype=None, layout="hwc", bits=None, out=None, check=True, shading=None,
-                         defects=None):
+                         defects=None, denoise=None):
         """uint16 mosaics resident on the context's device -> display-ready integer RGB: the demosaic and colours of
         demosaic(), then clamp to [0, 1], index a transfer-curve LUT of L entries at rint(c * (L - 1)) and store the entry
         (its low byte for uint8).  dtype: torch.uint8 (default) or torch.uint16; layout "hwc" gives (N, Ho, Wo, 3), "chw"
@@ -1464,7 +1601,7 @@ class Context:
         on [0, 1] -- built by transfer_lut(transfer, lut_size, bits), bits 8 for uint8 and 16 for uint16 unless given --
         or a ready 1-D uint16 LUT (host array or CUDA tensor) whose length is a power of two, 256 .. 65536.  Queued on
         torch.cuda.current_stream(); nothing synchronises, and a caller's LUT is read when the kernels run (in stream
-        order).  `check` is accepted for symmetry with decode_display.  shading, defects: as demosaic()."""
+        order).  `check` is accepted for symmetry with decode_display.  shading, defects, denoise: as demosaic()."""
         import torch
         if algo not in _RGB_ALGOS:
             raise ValueError("algo must be 'mhc' or 'bin2', not %r" % (algo,))
@@ -1485,6 +1622,8 @@ class Context:
         mos = mosaic.unsqueeze(0) if single else mosaic
         if defects is not None and mos.numel():  # into a scratch tensor, in front of the gains
             mos = self._fix_defects(mos, defects, black, "demosaic_display")
+        if denoise is not None and mos.numel():  # on the sensor's values: behind the defects, in front of the gains
+            mos = self._denoise_stage(mos, denoise, "demosaic_display")
         if shading is not None and mos.numel():  # into a scratch tensor: the caller's mosaic stays as it is
             mos = self.shade(mos, shading, black=black)
         n, h, w = (int(v) for v in mos.shape)
@@ -1525,14 +1664,16 @@ class Context:
 
     def decode_display(self, inputs, width, height, type, *, algo="mhc", white, black=(0, 0, 0, 0), cfa="rggb", gain=None,
                        matrix=None, transfer="srgb", lut_size=4096, dtype=None, layout="hwc", bits=None, out=None, check=True, shading=None,
-                       defects=None):
+                       defects=None, denoise=None):
         """Decode frames of one geometry that are resident in HBM and turn them into display-ready RGB
         (demosaic_display()), as decode_rgb does: the plain uint16 mosaics go to a scratch tensor, both steps are queued on
         torch.cuda.current_stream(), check=True synchronises after the decode and raises McrawError naming the frames that
-        failed, and the context's stage is restored afterwards.  shading, defects: as decode_rgb()."""
+        failed, and the context's stage is restored afterwards.  shading, defects, denoise: as decode_rgb()."""
         scratch = self._decode_scratch(inputs, width, height, type, check, "decode_display")
         if defects is not None and scratch.numel():
             scratch = self._fix_defects(scratch, defects, black, "decode_display")
+        if denoise is not None and scratch.numel():
+            scratch = self._denoise_stage(scratch, denoise, "decode_display")
         if shading is not None:
             self.shade(scratch, shading, black=black, out=scratch)
         return self.demosaic_display(scratch, algo=algo, white=white, black=black, cfa=cfa, gain=gain, matrix=matrix,
@@ -1541,7 +1682,7 @@ class Context:
 
     def demosaic_yuv(self, mosaic, *, algo="mhc", white, black=(0, 0, 0, 0), cfa="rggb", gain=None, matrix=None, fmt="nv12",
                      standard="bt709", range="limited", transfer="bt709", lut_size=4096, in_bits=None, out=None, check=True, shading=None,
-                     defects=None):
+                     defects=None, denoise=None):
         """uint16 mosaics resident on the context's device -> video-ready Y'CbCr 4:2:0: the demosaic, colours, clamp and
         transfer-curve LUT of demosaic_display(), then the integer matrix of yuv_matrix(standard, range) and a 2x2 box
         average for the chroma (sited at the block's centre).  fmt "nv12": torch.uint8; "p010": torch.uint16 holding
@@ -1550,7 +1691,7 @@ class Context:
         gives the two as views.  Ho and Wo must be even (bin2: H and W multiples of 4).  transfer: as demosaic_display; a
         built-in curve is transfer_lut(transfer, lut_size, in_bits), in_bits defaulting to 12 (nv12) or 16 (p010); a ready
         LUT may hold entries of any in_bits 8 .. 16 (higher bits are masked off).  Queued on torch.cuda.current_stream();
-        nothing synchronises.  `check` is accepted for symmetry with decode_yuv.  shading, defects: as demosaic()."""
+        nothing synchronises.  `check` is accepted for symmetry with decode_yuv.  shading, defects, denoise: as demosaic()."""
         import torch
         if algo not in _RGB_ALGOS:
             raise ValueError("algo must be 'mhc' or 'bin2', not %r" % (algo,))
@@ -1570,6 +1711,8 @@ class Context:
         mos = mosaic.unsqueeze(0) if single else mosaic
         if defects is not None and mos.numel():  # into a scratch tensor, in front of the gains
             mos = self._fix_defects(mos, defects, black, "demosaic_yuv")
+        if denoise is not None and mos.numel():  # on the sensor's values: behind the defects, in front of the gains
+            mos = self._denoise_stage(mos, denoise, "demosaic_yuv")
         if shading is not None and mos.numel():  # into a scratch tensor: the caller's mosaic stays as it is
             mos = self.shade(mos, shading, black=black)
         n, h, w = (int(v) for v in mos.shape)
@@ -1613,14 +1756,16 @@ class Context:
 
     def decode_yuv(self, inputs, width, height, type, *, algo="mhc", white, black=(0, 0, 0, 0), cfa="rggb", gain=None,
                    matrix=None, fmt="nv12", standard="bt709", range="limited", transfer="bt709", lut_size=4096, in_bits=None,
-                   out=None, check=True, shading=None, defects=None):
+                   out=None, check=True, shading=None, defects=None, denoise=None):
         """Decode frames of one geometry that are resident in HBM and turn them into NV12 / P010 (demosaic_yuv()), as
         decode_display does: the plain uint16 mosaics go to a scratch tensor, both steps are queued on
         torch.cuda.current_stream(), check=True synchronises after the decode and raises McrawError naming the frames that
-        failed, and the context's stage is restored afterwards.  shading, defects: as decode_rgb()."""
+        failed, and the context's stage is restored afterwards.  shading, defects, denoise: as decode_rgb()."""
         scratch = self._decode_scratch(inputs, width, height, type, check, "decode_yuv")
         if defects is not None and scratch.numel():
             scratch = self._fix_defects(scratch, defects, black, "decode_yuv")
+        if denoise is not None and scratch.numel():
+            scratch = self._denoise_stage(scratch, denoise, "decode_yuv")
         if shading is not None:
             self.shade(scratch, shading, black=black, out=scratch)
         return self.demosaic_yuv(scratch, algo=algo, white=white, black=black, cfa=cfa, gain=gain, matrix=matrix, fmt=fmt,

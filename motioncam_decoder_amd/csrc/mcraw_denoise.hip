@@ -1,0 +1,386 @@
+// mcraw_denoise.hip -- gfx950 kernel for uint16 mosaics resident in HBM -> noise-adaptively smoothed uint16 mosaics
+// (mcraw_denoise_batch).  The contract (integers only, bit-exact) is in include/mcraw_hip.h; DESIGN.md 19 has the design.
+//
+// kdenoise<RADIUS, NT>: a workgroup owns a tile of DN_TW columns x DN_TH rows of one frame and stages it with a halo of
+// 2 * RADIUS rows and columns in LDS as raw samples, 16-byte chunks on the frame's 8-column grid (kfixpix's staging), and
+// the frame's table behind it.  The halo holds what the contract's reflection names for the pixel at distance 2 (the two
+// coordinates next to the frame) or 4 (the two beyond); the pixels 2 and 3 from an edge, whose distance-4 neighbour falls on
+// a coordinate that belongs to the distance-2 reader, take their opposite distance-4 neighbour instead, which the rule
+// makes the same sample.  Lane (lx, ly) makes 8 columns of rows ly, ly + 8, ...: for each of the 2R + 1 LDS
+// rows it reads 8 + 4R samples and accumulates, for all 8 pixels, q = x * x, q * a and a over the 2R + 1 columns.  The
+// centre counts as a neighbour of itself (x = 0, weight 256): that is the contract's 256 * c and 256.  |a - c| runs packed
+// on the dwords as they lie in memory; every product has a factor below 2^24.
+#include "mcraw_dev.h"
+#include "mcraw_host.h"
+
+namespace mcraw {
+
+constexpr int DN_T = 256;        // threads per workgroup
+constexpr uint32_t DN_LX = 32u;  // lanes across a tile: 8 columns each
+constexpr uint32_t DN_LY = DN_T / DN_LX;
+constexpr uint32_t DN_TW = 8u * DN_LX;
+// Tile rows: 32 re-reads 40/32 of the rows at radius 2 (21.3 KB of LDS), 16 re-reads 24/16 (12.8 KB).
+// -DMCRAW_DENOISE_TH=16 builds the other one; tools/bench_denoise.py --alt-lib runs two builds side by side.
+#ifndef MCRAW_DENOISE_TH
+#define MCRAW_DENOISE_TH 32
+#endif
+constexpr uint32_t DN_TH = MCRAW_DENOISE_TH;
+static_assert(DN_TH == 16u || DN_TH == 32u, "the lanes' rows are DN_LY apart: the tile is a multiple of it");
+constexpr uint32_t DN_LW = DN_TW + 16u; // LDS row: 8 columns either side (2 * RADIUS used), so that chunks stay on the 8-grid
+constexpr uint32_t DN_CH = DN_LW / 8u;  // 16-byte chunks per LDS row
+
+// Which stores the full aligned pieces of the output rows use: `sc1 nt` streaming stores (store_stream16) or plain ones.
+// -DMCRAW_DENOISE_FLIP_STORES builds the other one.
+#ifdef MCRAW_DENOISE_FLIP_STORES
+constexpr bool DN_NT = false;
+#else
+constexpr bool DN_NT = true;
+#endif
+
+struct DnArgs {
+    const uint16_t *in;
+    uint16_t *out;
+    const uint16_t *lut; // the launch's first table
+    size_t ipitch, ifstride, opitch, ofstride;
+    uint32_t W, H, tilesX;
+    uint32_t amount, L, shift, perframe;
+    uint32_t invec, outvec; // every 8-column piece of `in` / `out` lies on the 16-byte grid
+};
+
+// The frame coordinate whose sample the halo coordinate h stands for.  h in {-2, -1} is read at distance 2 by c = h + 2, h in
+// {-4, -3} at distance 4 by c = h + 4 (and mirrored on the high side): the contract's c - d, or c itself where that leaves
+// the frame too.  (h in {-2, -1} is also where c = 2, 3 would look at distance 4: those pixels do not, see dn_swap.)
+// Coordinates no output reads are clamped.
+__device__ __forceinline__ int dn_halo(int h, int n)
+{
+    if (h < -2)
+        h = h + 8 < n ? h + 8 : h + 4;
+    else if (h < 0)
+        h = h + 4 < n ? h + 4 : h + 2;
+    else if (h >= n + 2)
+        h = h - 8 >= 0 ? h - 8 : h - 4;
+    else if (h >= n)
+        h = h - 4 >= 0 ? h - 4 : h - 2;
+    return min(max(h, 0), n - 1);
+}
+
+// Which way a pixel at coordinate c looks for its neighbours at distance 4.  c - 4 in {-2, -1} and c + 4 in {n, n + 1} are
+// halo coordinates that hold the distance-2 reader's sample.  For such a c the contract's rule gives the neighbours at -4
+// and at +4 the same coordinate (c - 4 is outside, so -4 means c + 4 or c, and +4 means c + 4 or, c - 4 being outside, c;
+// likewise on the high side), so the pixel reads the other side: bit 0 = take +4 for -4, bit 1 = take -4 for +4, both = the
+// pixel itself for both (n = 6, 7).
+__device__ __forceinline__ uint32_t dn_swap(int c, int n)
+{
+    return ((c & ~1) == 2 ? 1u : 0u) | (static_cast<uint32_t>(c + 4 - n) < 2u ? 2u : 0u);
+}
+
+// Two uint16 per dword, both halves at once (v_pk_max_u16, v_pk_min_u16, v_pk_sub_u16).
+typedef unsigned short dn_u16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t dn_pkabsdiff(uint32_t a, uint32_t b)
+{
+    const dn_u16x2 x = __builtin_bit_cast(dn_u16x2, a), y = __builtin_bit_cast(dn_u16x2, b);
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(x, y) - __builtin_elementwise_min(x, y));
+}
+
+__device__ __forceinline__ uint32_t dn_half(uint32_t w, uint32_t h)
+{
+    return h ? w >> 16 : w & 0xFFFFu;
+}
+
+// v_mul_u32_u24: both factors below 2^24
+__device__ __forceinline__ uint32_t dn_mul24(uint32_t a, uint32_t b)
+{
+    return static_cast<uint32_t>(__umul24(a, b));
+}
+
+// (num + (den >> 1)) / den, exactly.  n < 2^30 and den in 256 .. 6400; the quotient is at most 65536 (a weighted mean of
+// uint16 values plus the rounding half).  In float: n rounds with a relative error of 2^-24, den is exact, v_rcp_f32 is
+// good to 1 ulp (2^-23) and the product rounds once more: the estimate is off by less than 65536 * 2^-21 = 1 / 32, so its
+// integer part is the quotient or one beside it, and one step either way by the sign of the remainder makes it exact.
+__device__ __forceinline__ uint32_t dn_div(uint32_t n, uint32_t den)
+{
+    uint32_t q = static_cast<uint32_t>(static_cast<float>(n) * __builtin_amdgcn_rcpf(static_cast<float>(den)));
+    const int32_t r = static_cast<int32_t>(n - dn_mul24(q, den)); // q <= 65537, den < 2^13: exact
+    q = r < 0 ? q - 1u : q;
+    q = r >= static_cast<int32_t>(den) ? q + 1u : q;
+    return q;
+}
+
+template <bool NT>
+__device__ __forceinline__ void dn_store8(uint16_t *dst, uint32_t n, bool vec, const uint32_t p[4])
+{
+    if (n == 8u) {
+        if (vec) {
+            const mcraw_u32x4 v = {p[0], p[1], p[2], p[3]};
+            if (NT)
+                store_stream16(dst, v);
+            else
+                *gptr<mcraw_u32x4>(dst) = v;
+        } else { // rows off the 16-byte grid: one unaligned 16-byte store
+            typedef uint32_t u32x4_u __attribute__((ext_vector_type(4), aligned(2)));
+            const u32x4_u v = {p[0], p[1], p[2], p[3]};
+            *gptr<u32x4_u>(dst) = v;
+        }
+        return;
+    }
+#pragma unroll
+    for (uint32_t i = 0; i < 8u; i++) // the cropped end of a row: element stores
+        if (i < n)
+            gptr<uint16_t>(dst)[i] = static_cast<uint16_t>(p[i >> 1] >> (16u * (i & 1u)));
+}
+
+template <int RADIUS, bool NT>
+__global__ void __launch_bounds__(DN_T) kdenoise(const DnArgs A)
+{
+    constexpr int HALO = 2 * RADIUS;
+    constexpr uint32_t NP = 2u * RADIUS + 1u;       // neighbours per axis, the centre among them
+    constexpr uint32_t NW = 4u + 2u * RADIUS;       // dwords of an LDS row that a lane reads: columns x - HALO .. x + 7 + HALO
+    constexpr uint32_t LH = DN_TH + 2u * HALO;
+    __shared__ __attribute__((aligned(16))) uint16_t s_t[LH * DN_LW];          // the tile and its halo
+    extern __shared__ __attribute__((aligned(16))) uint16_t dn_lut[];          // the frame's table: 4 * L entries (the launch sizes it)
+    const uint32_t tile = blockIdx.x, f = blockIdx.y;
+    const uint32_t ty = tile / A.tilesX, tx = tile - ty * A.tilesX;
+    const int W = static_cast<int>(A.W), H = static_cast<int>(A.H);
+    const int x0 = static_cast<int>(tx * DN_TW), y0 = static_cast<int>(ty * DN_TH);
+    const uint16_t *in = A.in + static_cast<size_t>(f) * A.ifstride;
+    {
+        const uint16_t *lut = A.lut + (A.perframe ? static_cast<size_t>(f) * 4u * A.L : 0u);
+        for (uint32_t i = threadIdx.x; i < A.L / 2u; i += DN_T) // 4 * L * 2 bytes in 16-byte chunks (L >= 64)
+            *reinterpret_cast<mcraw_u32x4 *>(&dn_lut[8u * i]) = *gptr<const mcraw_u32x4>(lut + 8u * i);
+    }
+    for (uint32_t i = threadIdx.x; i < LH * DN_CH; i += DN_T) {
+        const uint32_t r = i / DN_CH, q = i % DN_CH;
+        const int yy = y0 - HALO + static_cast<int>(r), xs = x0 - 8 + 8 * static_cast<int>(q);
+        if (yy >= H + HALO || xs >= W + HALO) // no output of the frame reads it
+            continue;
+        const uint16_t *row = in + static_cast<size_t>(dn_halo(yy, H)) * A.ipitch;
+        mcraw_u32x4 v;
+        if (q != 0u && q != DN_CH - 1u && xs + 8 <= W) { // (xs >= 0 here) a full piece of the row
+            if (A.invec) {
+                v = *gptr<const mcraw_u32x4>(row + xs);
+            } else { // rows off the 16-byte grid: one unaligned 16-byte load
+                typedef uint32_t u32x4_u __attribute__((ext_vector_type(4), aligned(2)));
+                const u32x4_u t = *gptr<const u32x4_u>(row + xs);
+                v = mcraw_u32x4{t[0], t[1], t[2], t[3]};
+            }
+        } else { // the halo columns (the last HALO of the first chunk, the first HALO of the last) and a cropped row end:
+                 // element loads through the reflection
+            const int e0 = q == 0u ? 8 - HALO : 0, e1 = q == DN_CH - 1u ? HALO : 8;
+            uint32_t u[8];
+#pragma unroll
+            for (int e = 0; e < 8; e++)
+                u[e] = (e >= e0 && e < e1 && xs + e < W + HALO) ? gptr<const uint16_t>(row)[dn_halo(xs + e, W)] : 0u;
+            v = mcraw_u32x4{u[0] | (u[1] << 16), u[2] | (u[3] << 16), u[4] | (u[5] << 16), u[6] | (u[7] << 16)};
+        }
+        *reinterpret_cast<mcraw_u32x4 *>(&s_t[r * DN_LW + 8u * q]) = v;
+    }
+    __syncthreads();
+    const uint32_t lx = threadIdx.x % DN_LX, ly = threadIdx.x / DN_LX;
+    const uint32_t x = static_cast<uint32_t>(x0) + 8u * lx;
+    const uint32_t n = x < A.W ? min(8u, A.W - x) : 0u;
+    if (n == 0u)
+        return;
+    // the lane's rows all have the parity of ly (y0 and DN_LY are even): two of the table's four planes
+    const uint16_t *plane[2] = {dn_lut + (2u * (ly & 1u)) * A.L, dn_lut + (2u * (ly & 1u) + 1u) * A.L};
+    // radius 2: the halves of the lane's dwords whose distance-4 neighbours along the row are taken from the other side
+    uint32_t mlo[4] = {0u, 0u, 0u, 0u}, mhi[4] = {0u, 0u, 0u, 0u};
+    bool edgex = false;
+    if (RADIUS == 2) {
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; k++)
+#pragma unroll
+            for (uint32_t h = 0; h < 2u; h++) {
+                const uint32_t s = dn_swap(static_cast<int>(x + 2u * k + h), W);
+                mlo[k] |= (s & 1u) ? 0xFFFFu << (16u * h) : 0u;
+                mhi[k] |= (s & 2u) ? 0xFFFFu << (16u * h) : 0u;
+                edgex = edgex || s != 0u;
+            }
+    }
+    uint16_t *fout = A.out + static_cast<size_t>(f) * A.ofstride + x;
+    const uint32_t lmax = A.L - 1u;
+#pragma unroll 1
+    for (uint32_t rr = ly; rr < DN_TH; rr += DN_LY) {
+        const uint32_t y = static_cast<uint32_t>(y0) + rr;
+        if (y >= A.H)
+            break;
+        const uint32_t sy = RADIUS == 2 ? dn_swap(static_cast<int>(y), H) : 0u;
+        const uint16_t *lane = &s_t[(rr + HALO) * DN_LW + 8u * lx + 8u - HALO]; // the pixel row, column x - HALO
+        uint32_t c[4], rv[8];
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; k++) {
+            c[k] = *reinterpret_cast<const uint32_t *>(lane + HALO + 2u * k);
+#pragma unroll
+            for (uint32_t h = 0; h < 2u; h++)
+                rv[2u * k + h] = plane[h][min(dn_half(c[k], h) >> A.shift, lmax)];
+        }
+        uint32_t sq[8], sqa[8], sa[8];
+#pragma unroll
+        for (uint32_t p = 0; p < 8u; p++)
+            sq[p] = sqa[p] = sa[p] = 0u;
+#pragma unroll 1
+        for (uint32_t j = 0; j < NP; j++) {
+            int dy = 2 * (static_cast<int>(j) - RADIUS);
+            if (RADIUS == 2) { // the row at distance 4 that the halo cannot serve: the opposite one, or the pixel's own
+                if (j == 0u && (sy & 1u))
+                    dy = (sy & 2u) ? 0 : 4;
+                if (j == NP - 1u && (sy & 2u))
+                    dy = (sy & 1u) ? 0 : -4;
+            }
+            const uint16_t *lrow = lane + dy * static_cast<int>(DN_LW);
+            uint32_t w[NW]; // w[i]: columns x - HALO + 2i, x - HALO + 2i + 1
+            if (RADIUS == 2) {
+                const mcraw_u32x2 a0 = *reinterpret_cast<const mcraw_u32x2 *>(lrow);
+                const mcraw_u32x4 a1 = *reinterpret_cast<const mcraw_u32x4 *>(lrow + 4);
+                const mcraw_u32x2 a2 = *reinterpret_cast<const mcraw_u32x2 *>(lrow + 12);
+                const uint32_t t[8] = {a0[0], a0[1], a1[0], a1[1], a1[2], a1[3], a2[0], a2[1]};
+#pragma unroll
+                for (uint32_t i = 0; i < NW; i++)
+                    w[i] = t[i];
+            } else {
+                const uint32_t a0 = *reinterpret_cast<const uint32_t *>(lrow);
+                const mcraw_u32x4 a1 = *reinterpret_cast<const mcraw_u32x4 *>(lrow + 2);
+                const uint32_t a2 = *reinterpret_cast<const uint32_t *>(lrow + 10);
+                const uint32_t t[6] = {a0, a1[0], a1[1], a1[2], a1[3], a2};
+#pragma unroll
+                for (uint32_t i = 0; i < NW; i++)
+                    w[i] = t[i];
+            }
+            uint32_t far[2][4]; // radius 2: the neighbours at -4 and +4 along the row
+            if (RADIUS == 2) {
+#pragma unroll
+                for (uint32_t k = 0; k < 4u; k++)
+                    far[0][k] = w[k], far[1][k] = w[k + 4u];
+                if (edgex) {
+#pragma unroll
+                    for (uint32_t k = 0; k < 4u; k++) {
+                        const uint32_t both = mlo[k] & mhi[k], own = w[k + 2u];
+                        far[0][k] = (w[k] & ~mlo[k]) | (w[k + 4u] & mlo[k] & ~both) | (own & both);
+                        far[1][k] = (w[k + 4u] & ~mhi[k]) | (w[k] & mhi[k] & ~both) | (own & both);
+                    }
+                }
+            }
+#pragma unroll
+            for (uint32_t k = 0; k < 4u; k++) {
+#pragma unroll
+                for (uint32_t i = 0; i < NP; i++) {
+                    const uint32_t a2 = (RADIUS == 2 && i == 0u) ? far[0][k] : (RADIUS == 2 && i == NP - 1u) ? far[1][k] : w[k + i];
+                    const uint32_t d2 = dn_pkabsdiff(a2, c[k]);
+#pragma unroll
+                    for (uint32_t h = 0; h < 2u; h++) {
+                        const uint32_t p = 2u * k + h, a = dn_half(a2, h);
+                        const uint32_t t = dn_mul24(dn_half(d2, h), rv[p]) >> 8, xx = t < 16u ? t : 16u;
+                        const uint32_t q = dn_mul24(xx, xx);
+                        sq[p] += q;
+                        sqa[p] += dn_mul24(q, a);
+                        sa[p] += a;
+                    }
+                }
+            }
+        }
+        uint32_t o[4];
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; k++) {
+            uint32_t res[2];
+#pragma unroll
+            for (uint32_t h = 0; h < 2u; h++) {
+                const uint32_t p = 2u * k + h;
+                // sum(w) = 256 * NP * NP - sum(q), sum(w * a) = 256 * sum(a) - sum(q * a), the centre (q = 0) among them
+                const uint32_t den = 256u * NP * NP - sq[p], num = 256u * sa[p] - sqa[p];
+                const int32_t cv = static_cast<int32_t>(dn_half(c[k], h));
+                const int32_t m = static_cast<int32_t>(dn_div(num + (den >> 1), den));
+                res[h] = static_cast<uint32_t>(cv + (((m - cv) * static_cast<int32_t>(A.amount) + 128) >> 8));
+            }
+            o[k] = res[0] | (res[1] << 16);
+        }
+        dn_store8<NT>(fout + static_cast<size_t>(y) * A.opitch, n, A.outvec != 0u, o);
+    }
+}
+
+static int denoise_reject(const char *why)
+{
+    g_err = std::string("mcraw_denoise_batch: ") + why;
+    return -1;
+}
+
+template <int RADIUS>
+static void denoise_launch(const DnArgs &A, uint32_t tilesY, uint32_t nf, hipStream_t st)
+{
+    hipLaunchKernelGGL((DN_NT ? kdenoise<RADIUS, true> : kdenoise<RADIUS, false>), dim3(A.tilesX * tilesY, nf), dim3(DN_T), static_cast<size_t>(A.L) * 8u, st, A);
+}
+
+} // namespace mcraw
+
+using namespace mcraw;
+
+extern "C" int mcraw_denoise_batch(mcraw_ctx *c, const mcraw_denoise *d, const uint16_t *in, size_t in_pitch, size_t in_frame_stride,
+                                   int width, int height, int n, uint16_t *out, size_t out_pitch, size_t out_frame_stride,
+                                   void *stream)
+{
+    if (!c || !d || n < 0)
+        return denoise_reject("bad arguments");
+    if (n == 0)
+        return 0;
+    if (!in || !out)
+        return denoise_reject("in or out missing");
+    if ((reinterpret_cast<uintptr_t>(in) & 1u) || (reinterpret_cast<uintptr_t>(out) & 1u))
+        return denoise_reject("in / out not aligned to uint16");
+    if (width < 1 || height < 1 || width > 65536 || height > 65536)
+        return denoise_reject("width and height must be 1 .. 65536");
+    const size_t W = static_cast<size_t>(width), H = static_cast<size_t>(height);
+    if (in_pitch < W || out_pitch < W)
+        return denoise_reject("pitch below width");
+    if (n > 1 && (in_frame_stride < (H - 1u) * in_pitch + W || out_frame_stride < (H - 1u) * out_pitch + W))
+        return denoise_reject("frame stride too small for the frames not to overlap");
+    if (d->radius != 1u && d->radius != 2u)
+        return denoise_reject("radius must be 1 or 2");
+    if (d->amount < 1u || d->amount > 256u)
+        return denoise_reject("amount must be 1 .. 256");
+    if (d->lut_log2 < 6u || d->lut_log2 > 10u)
+        return denoise_reject("lut_log2 must be 6 .. 10");
+    if (d->shift > 15u)
+        return denoise_reject("shift must be 0 .. 15");
+    if (d->nluts != 1u && d->nluts != static_cast<uint32_t>(n))
+        return denoise_reject("nluts must be 1 or n");
+    if (d->reserved[0] != 0u || d->reserved[1] != 0u || d->reserved[2] != 0u)
+        return denoise_reject("reserved must be 0");
+    if (!d->lut || (reinterpret_cast<uintptr_t>(d->lut) & 15u))
+        return denoise_reject("lut missing or not 16-byte aligned");
+    // elements from the first sample of the first frame to behind the last sample of the last one
+    const size_t in_ext = static_cast<size_t>(n - 1) * in_frame_stride + (H - 1u) * in_pitch + W;
+    const size_t out_ext = static_cast<size_t>(n - 1) * out_frame_stride + (H - 1u) * out_pitch + W;
+    const uintptr_t ia = reinterpret_cast<uintptr_t>(in), oa = reinterpret_cast<uintptr_t>(out);
+    if (ia < oa + 2u * out_ext && oa < ia + 2u * in_ext)
+        return denoise_reject("in and out overlap (every pixel reads its neighbours: there is no in-place form)");
+
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    DnArgs A{};
+    A.ipitch = in_pitch;
+    A.ifstride = in_frame_stride;
+    A.opitch = out_pitch;
+    A.ofstride = out_frame_stride;
+    A.W = static_cast<uint32_t>(width);
+    A.H = static_cast<uint32_t>(height);
+    A.tilesX = (A.W + DN_TW - 1u) / DN_TW;
+    const uint32_t tilesY = (A.H + DN_TH - 1u) / DN_TH;
+    A.amount = d->amount;
+    A.L = 1u << d->lut_log2;
+    A.shift = d->shift;
+    A.perframe = d->nluts != 1u ? 1u : 0u;
+    A.invec = (ia & 15u) == 0u && in_pitch % 8u == 0u && (n == 1 || in_frame_stride % 8u == 0u);
+    A.outvec = (oa & 15u) == 0u && out_pitch % 8u == 0u && (n == 1 || out_frame_stride % 8u == 0u);
+    constexpr int piece = 65535; // frames per launch (grid.y)
+    for (int f0 = 0; f0 < n; f0 += piece) {
+        const int nf = std::min(piece, n - f0);
+        A.in = in + static_cast<size_t>(f0) * in_frame_stride;
+        A.out = out + static_cast<size_t>(f0) * out_frame_stride;
+        A.lut = d->lut + (A.perframe ? static_cast<size_t>(f0) * 4u * A.L : 0u);
+        if (d->radius == 2u)
+            denoise_launch<2>(A, tilesY, static_cast<uint32_t>(nf), st);
+        else
+            denoise_launch<1>(A, tilesY, static_cast<uint32_t>(nf), st);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}

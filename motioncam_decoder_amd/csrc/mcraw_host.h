@@ -8,6 +8,8 @@
 //   mcraw_hostmem.hip  batches whose buffers are in host memory: the three-lane pipeline, tickets
 //   mcraw_shade.hip    mcraw_shade_batch: its kernel, checks and launch (it shares the context's mutex, device and stream only)
 //   mcraw_stats.hip    mcraw_stats_batch: its kernels, checks and launches (likewise)
+//   mcraw_fixpix.hip   mcraw_fixpix_batch: likewise
+//   mcraw_denoise.hip  mcraw_denoise_batch: likewise
 // Replaces the per-frame dispatch of lib/Decoder.cpp:216-234 with batched submits.  There is no CPU decode fallback in any of them.
 #pragma once
 #include <hip/hip_runtime.h>
