@@ -645,6 +645,71 @@ typedef struct mcraw_denoise {
 int mcraw_denoise_batch(mcraw_ctx *ctx, const mcraw_denoise *d, const uint16_t *in, size_t in_pitch, size_t in_frame_stride,
                         int width, int height, int n, uint16_t *out, size_t out_pitch, size_t out_frame_stride, void *stream);
 
+/* ---- uint16 mosaics -> temporally merged uint16 mosaics --------------------------------------------------------------------
+ *
+ * Noise-adaptive merge along time of `n` uint16 mosaics of width x height that show the same scene (a burst, or the
+ * neighbouring frames of a clip): output j is the base frame b = first + j, every pixel replaced by the weighted mean of
+ * itself and the samples of the other frames of b's window at the same (or a shifted) position.  A sample's weight falls with
+ * a motion measure over the cut-off that the denoiser's table gives at the pixel's level, so what moved is left out and the
+ * result costs no resolution.  `count` outputs with their own pitch and stride; pitches and frame strides count uint16
+ * elements.  Integers only: bit-exact.
+ * Members.  The members of b's window are the frames t in max(0, b - before) .. min(n - 1, b + after) with t != b: clipped at
+ * the ends of the batch, not wrapped; before + after <= 15.  A burst stacked onto its first frame is before = 0,
+ * after = n - 1, first = 0, count = 1; a sliding video filter is before = after = T, first = 0, count = n; a clip processed
+ * in overlapping batches uses first = T, count = n - 2T.
+ * Shifts.  pos: NULL, or DEVICE memory (n, 2) of int16 as (y, x) per frame, the frame's global position.  The shift of member
+ * t against base b is sy = (pos[t].y - pos[b].y) & ~1 and sx likewise, in int32 (the low bit is dropped towards minus
+ * infinity): a shift is always even and a sample keeps its CFA position.  NULL: every shift is 0.  Member t's sample for the
+ * base pixel (y, x) is a = in[t][y + sy][x + sx]; where that position is outside the frame the member weighs 0 for the pixel.
+ * Motion measure.  With e(dy, dx) = in[t][y + dy + sy][x + dx + sx] - in[b][y + dy][x + dx] and e0 = e(0, 0) = a - c:
+ *   support 0:  D = |e0|
+ *   support 1:  s = the sum over dy, dx in -1 .. 1 of e(dy, dx); a term whose base position or member position lies outside
+ *               the frame counts e0 instead (nine terms always, no reflection rule; a 1 x 1 frame is defined)
+ *               D = max(min(|s| >> 3, 65535), |e0| >> 1)
+ *   (the second operand is a per-pixel guard: without it an isolated outlier in a member leaks into the result)
+ * Per pixel of value c at CFA position p = (y & 1) * 2 + (x & 1), with L = 1 << lut_log2 and the table
+ * f = (nluts == 1 ? 0 : b) -- the denoiser's lines and the denoiser's table, so one noise table serves both stages:
+ *   r   = lut[f][p][min(c >> shift, L - 1)]              uint16: 4096 / (the cut-off in DN) at the pixel's level
+ *   for every member's sample a with its D:
+ *       x = min((D * r) >> 8, 16)                        D * r <= 65535 * 65535 < 2^32
+ *       w = 256 - x * x                                  0 .. 256; 0 where the member's position is outside the frame
+ *   num = 256 * c + sum(w * a)                           <= 4096 * 65535 < 2^28
+ *   den = 256 + sum(w)                                   256 .. 4096
+ *   m   = (num + (den >> 1)) / den                       unsigned integer division (floor)
+ *   out = c + (((m - c) * amount + 128) >> 8)            signed, arithmetic shift (floor); amount 256 gives m
+ * out lies between c and m, so there is no clamp.  A table of all 65535 returns the base frames bit for bit (any D >= 1
+ * gives x = 16; with support 1, D = 0 also admits e0 = +-1 under |s| < 8, and a sample one ABOVE c then rounds m up to c + 1:
+ * content whose samples differ by 0 or by 2 and more comes back exactly); so does before = after = 0, and so do shifts that
+ * leave the frame.  A table of all 0 with no shifts returns the rounded mean of the window, whatever `support` is.
+ * lut: the caller's DEVICE memory, 16-byte aligned, (nluts, 4, L) uint16, indexed by the base frame's index in the batch; lut
+ * and pos are read by the queued kernel in stream order and never copied into or cached by the context.
+ * There is no in-place form.  `in` and `out` may sit at any 2-byte alignment with any pitch (16-byte accesses where base,
+ * pitch, stride and shift allow it).
+ * `stream`: a hipStream_t, NULL = the context's own stream; the call queues the work and returns without synchronising.
+ * It takes no decode serial and leaves the decode slots, mcraw_ctx_errors, mcraw_ctx_last_serial and the context's stage
+ * alone.  count == 0 or n == 0 is a no-op.  The launches have no id in mcraw_ctx_kernel_ms (time them with stream events).
+ * Rejected (returns < 0, mcraw_last_error says why, starting with "mcraw_merge_batch: ", nothing is written): a NULL `m`,
+ * `in`, `out` or `lut`; an odd `in`, `out` or `pos` address; a `lut` that is not 16-byte aligned; width or height outside
+ * 1 .. 65536; a pitch below width; more than one frame on a side and a frame stride below (height - 1) * pitch + width;
+ * before + after above 15; first + count above n; support not 0 or 1; amount outside 1 .. 256; lut_log2 outside 6 .. 10;
+ * shift above 15; nluts not 1 or n; a non-zero `reserved`; input and output extents that overlap at all. */
+typedef struct mcraw_merge {
+    uint32_t before;       /* frames in front of the base that its window holds                         */
+    uint32_t after;        /* frames behind it; before + after <= 15                                    */
+    uint32_t first;        /* the base of output 0                                                      */
+    uint32_t count;        /* outputs: the bases first .. first + count - 1; first + count <= n         */
+    uint32_t support;      /* 0: per-pixel differences;  1: the 3x3 motion measure                      */
+    uint32_t amount;       /* 1 .. 256: how much of the correction is applied, 256 = all                */
+    uint32_t lut_log2;     /* 6 .. 10: L = 1 << lut_log2 entries per CFA position                       */
+    uint32_t shift;        /* 0 .. 15: entry of a pixel of value c = min(c >> shift, L - 1)             */
+    uint32_t nluts;        /* 1: one table for the batch;  n: one per input frame, back to back         */
+    uint32_t reserved;     /* must be 0                                                                 */
+    const uint16_t *lut;   /* DEVICE memory, 16-byte aligned: (nluts, 4, L)                             */
+    const int16_t *pos;    /* DEVICE memory, 2-byte aligned: (n, 2) as (y, x); or NULL                  */
+} mcraw_merge;             /* sizeof 56; after 4, first 8, count 12, support 16, amount 20, lut_log2 24, shift 28, nluts 32, reserved 36, lut 40, pos 48 */
+int mcraw_merge_batch(mcraw_ctx *ctx, const mcraw_merge *m, const uint16_t *in, size_t in_pitch, size_t in_frame_stride,
+                      int width, int height, int n, uint16_t *out, size_t out_pitch, size_t out_frame_stride, void *stream);
+
 /* ---- environment ------------------------------------------------------------------------------
  * Read when a context (or pool) is created, never afterwards:
  *   MCRAW_DEVICE=n, MCRAW_DEVICES=all|0,1,5   default device of the five-argument entry points / members of a default pool

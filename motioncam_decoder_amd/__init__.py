@@ -17,7 +17,7 @@ __all__ = ["lib_path", "load", "Context", "Pool", "Frame", "EncFrame", "FloatOut
            "RgbParams", "RgbColor", "RGB_KERNELS", "rgb_color", "Display", "transfer_lut", "DISP_U8", "DISP_U16",
            "DISP_CHW", "DISP_HWC", "Yuv", "YUV_NV12", "YUV_P010", "yuv_matrix", "yuv_planes", "Shade", "gain_map",
            "shading_map", "Stats", "STATS_ACCUMULATE", "FrameStats", "stats_white_balance", "stats_percentile",
-           "stats_clipped", "FixPix", "FIXPIX_HOT", "FIXPIX_COLD", "pack_pixels", "Denoise", "noise_lut"]
+           "stats_clipped", "FixPix", "FIXPIX_HOT", "FIXPIX_COLD", "pack_pixels", "Denoise", "noise_lut", "Merge"]
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 
@@ -46,6 +46,7 @@ ABI_SYMBOLS = [
     "mcraw_encode_bound7", "mcraw_encode_batch", "mcraw_encode7", "mcraw_ctx_set_float_out", "mcraw_pool_set_float_out",
     "mcraw_demosaic_batch", "mcraw_demosaic_display_batch", "mcraw_demosaic_yuv_batch", "mcraw_shade_batch",
     "mcraw_stats_batch", "mcraw_stats_record_bytes", "mcraw_fixpix_batch", "mcraw_denoise_batch",
+    "mcraw_merge_batch",
 ]
 
 POST_BLACK, POST_PACK12, POST_PACK10, POST_PACK14 = 1, 2, 4, 8
@@ -382,6 +383,15 @@ class Denoise(C.Structure):
     device table (nluts, 4, L) of uint16."""
     _fields_ = [("radius", C.c_uint32), ("amount", C.c_uint32), ("lut_log2", C.c_uint32), ("shift", C.c_uint32),
                 ("nluts", C.c_uint32), ("reserved", C.c_uint32 * 3), ("lut", C.c_void_p)]
+
+
+# noise-adaptive temporal merge of mosaics (mcraw_merge_batch)
+class Merge(C.Structure):
+    """struct mcraw_merge (include/mcraw_hip.h): the window, the outputs, the motion measure, amount in Q8, the table's size
+    and shift, how many tables, the device table (nluts, 4, L) of uint16 and the device positions (n, 2) of int16 or NULL."""
+    _fields_ = [("before", C.c_uint32), ("after", C.c_uint32), ("first", C.c_uint32), ("count", C.c_uint32),
+                ("support", C.c_uint32), ("amount", C.c_uint32), ("lut_log2", C.c_uint32), ("shift", C.c_uint32),
+                ("nluts", C.c_uint32), ("reserved", C.c_uint32), ("lut", C.c_void_p), ("pos", C.c_void_p)]
 
 
 def noise_lut(S, O, black, white, strength=3.0, entries=256, top=None):
@@ -760,6 +770,9 @@ def load():
     lib.mcraw_denoise_batch.restype = C.c_int
     lib.mcraw_denoise_batch.argtypes = [C.c_void_p, C.POINTER(Denoise), C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int,
                                         C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
+    lib.mcraw_merge_batch.restype = C.c_int
+    lib.mcraw_merge_batch.argtypes = [C.c_void_p, C.POINTER(Merge), C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int,
+                                      C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
     lib.mcraw_encode7.restype = C.c_size_t
     lib.mcraw_encode7.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int]
     _lib = lib
@@ -1358,6 +1371,116 @@ class Context:
             raise McrawError("mcraw_denoise_batch failed (%d): %s" % (rc, self._lib.mcraw_last_error().decode()))
         return out
 
+    def merge(self, mosaic, lut, shift, before=2, after=2, first=0, count=None, support=1, amount=1.0, pos=None, out=None):
+        """Noise-adaptive merge along time of uint16 mosaics resident on the context's device (mcraw_merge_batch): output j is
+        the base frame first + j, every pixel the weighted mean of itself and the samples at its (shifted) position in the
+        `before` frames in front of the base and the `after` frames behind it (clipped at the ends of the batch; before +
+        after <= 15).  A sample's weight is 1 - (D / cut-off)^2, 0 beyond the cut-off: D is the difference to the base pixel
+        (support 0) or the larger of an eighth of the summed differences over the 3x3 pixels around it and half the pixel's
+        own (support 1); the cut-off is what denoise()'s table says at the base pixel's level and CFA position.  mosaic: (N,
+        H, W), rows contiguous (rows and frames may be strided).  lut: uint16 (4, L) for all frames or (N, 4, L) per base
+        frame, a CUDA tensor (read in stream order) or a host array (uploaded on the current stream).  count: None means N -
+        first.  amount: a float kept as rint(amount * 256) in 1 .. 256.  pos: None, or the frames' global positions (N, 2)
+        as (y, x): an int16 CUDA tensor (read in stream order), or a host array of integers in -32768 .. 32767, uploaded on
+        the current stream; a member is read at the difference of the positions with the low bit dropped, so that a sample
+        keeps its CFA position.  out: None (a new contiguous tensor) or a uint16 tensor (count, H, W) that does not overlap
+        the mosaic.  Returns (count, H, W).  Queued on torch.cuda.current_stream(); nothing synchronises."""
+        import numpy as np
+        import torch
+        dev = self._torch_device(torch)
+        if not isinstance(mosaic, torch.Tensor) or mosaic.dtype != torch.uint16 or mosaic.device != dev or mosaic.dim() != 3:
+            raise ValueError("merge: mosaic must be a uint16 tensor (N, H, W) on %s" % dev)
+        n, h, w = (int(v) for v in mosaic.shape)
+        for name, v in (("before", before), ("after", after), ("first", first)) + ((("count", count),) if count is not None else ()):
+            if isinstance(v, bool) or v != int(v) or int(v) < 0:
+                raise ValueError("merge: %s must be a non-negative integer, not %r" % (name, v))
+        before, after, first = int(before), int(after), int(first)
+        if before + after > 15:
+            raise ValueError("merge: before + after must not exceed 15")
+        if first > n:
+            raise ValueError("merge: first must be 0 .. %d" % n)
+        count = n - first if count is None else int(count)
+        if first + count > n:
+            raise ValueError("merge: first + count must not exceed the %d frames" % n)
+        if support not in (0, 1):
+            raise ValueError("merge: support must be 0 or 1, not %r" % (support,))
+        amt = float(amount)
+        if not np.isfinite(amt) or np.rint(amt * 256.0) < 1 or np.rint(amt * 256.0) > 256:
+            raise ValueError("merge: amount * 256 must round into 1 .. 256, not %r" % (amount,))
+        if shift != int(shift) or not 0 <= int(shift) <= 15:
+            raise ValueError("merge: shift must be an integer 0 .. 15, not %r" % (shift,))
+        if out is None:
+            out = torch.empty((count, h, w), dtype=torch.uint16, device=dev)
+        elif not isinstance(out, torch.Tensor) or tuple(out.shape) != (count, h, w) or out.dtype != torch.uint16 or out.device != dev:
+            raise ValueError("merge: out must be a uint16 tensor of shape %s on %s" % ((count, h, w), dev))
+        if isinstance(lut, np.ndarray):
+            if lut.dtype != np.uint16:
+                raise ValueError("merge: a lut array must be uint16 (noise_lut makes one)")
+            lut = torch.from_numpy(np.ascontiguousarray(lut).view(np.int16)).to(dev).view(torch.uint16)
+        if not isinstance(lut, torch.Tensor) or lut.dtype != torch.uint16 or lut.device != dev or lut.dim() not in (2, 3) \
+                or not lut.is_contiguous():
+            raise ValueError("merge: lut must be a contiguous uint16 tensor (4, L) or (N, 4, L) on %s" % dev)
+        nluts, L = (int(lut.shape[0]) if lut.dim() == 3 else 1), int(lut.shape[-1])
+        if int(lut.shape[-2]) != 4 or L not in (64, 128, 256, 512, 1024) or (lut.dim() == 3 and nluts != n):
+            raise ValueError("merge: lut must hold four planes of 64 .. 1024 (a power of two) entries, for all frames or for "
+                             "each of the %d" % n)
+        if pos is not None:
+            if isinstance(pos, torch.Tensor):
+                if pos.dtype != torch.int16 or pos.device != dev or tuple(pos.shape) != (n, 2) or not pos.is_contiguous():
+                    raise ValueError("merge: a pos tensor must be a contiguous int16 tensor (%d, 2) on %s" % (n, dev))
+            else:
+                a = np.asarray(pos)
+                if a.shape != (n, 2) or a.dtype.kind not in "iu" or (a.size and (a.min() < -32768 or a.max() > 32767)):
+                    raise ValueError("merge: pos must be (%d, 2) integers (y, x) in -32768 .. 32767" % n)
+                pos = torch.from_numpy(np.ascontiguousarray(a, dtype=np.int16)).to(dev)
+        if n == 0 or count == 0 or h == 0 or w == 0:
+            return out
+        if w > 1 and (mosaic.stride(2) != 1 or out.stride(2) != 1):
+            raise ValueError("merge: the rows of the mosaic and of out must be contiguous")
+        s = Merge()
+        s.before, s.after, s.first, s.count, s.support = before, after, first, count, int(support)
+        s.amount, s.lut_log2, s.shift, s.nluts, s.reserved = int(np.rint(amt * 256.0)), L.bit_length() - 1, int(shift), nluts, 0
+        s.lut = lut.data_ptr()
+        s.pos = pos.data_ptr() if pos is not None else None
+        ip = int(mosaic.stride(1)) if h > 1 else w
+        op = int(out.stride(1)) if h > 1 else w
+        ifs = int(mosaic.stride(0)) if n > 1 else ip * h
+        ofs = int(out.stride(0)) if count > 1 else op * h
+        cur, run = self._run_stream(torch, dev)
+        try:
+            rc = self._lib.mcraw_merge_batch(self._h, C.byref(s), C.c_void_p(mosaic.data_ptr()), ip, ifs, w, h, n,
+                                             C.c_void_p(out.data_ptr()), op, ofs, C.c_void_p(run.cuda_stream))
+        finally:
+            if run is not cur:
+                mosaic.record_stream(run)
+                out.record_stream(run)
+                lut.record_stream(run)
+                if pos is not None:
+                    pos.record_stream(run)
+                cur.wait_stream(run)
+        if rc != 0:
+            raise McrawError("mcraw_merge_batch failed (%d): %s" % (rc, self._lib.mcraw_last_error().decode()))
+        return out
+
+    def stack(self, mosaic, lut, shift, ref=0, **kw):
+        """The burst form of merge(): all N <= 16 frames of mosaic (N, H, W) merged onto frame `ref`.  The keyword arguments
+        are merge()'s without before, after, first and count; out, if given, is (H, W).  Returns (H, W)."""
+        import torch
+        if not isinstance(mosaic, torch.Tensor) or mosaic.dim() != 3 or not 1 <= int(mosaic.shape[0]) <= 16:
+            raise ValueError("stack: mosaic must be a uint16 tensor (N, H, W) of 1 .. 16 frames")
+        n = int(mosaic.shape[0])
+        if isinstance(ref, bool) or ref != int(ref) or not 0 <= int(ref) < n:
+            raise ValueError("stack: ref must be 0 .. %d, not %r" % (n - 1, ref))
+        if any(k in kw for k in ("before", "after", "first", "count")):
+            raise ValueError("stack: before, after, first and count are merge()'s; the window is the whole burst")
+        out = kw.pop("out", None)
+        if out is not None:
+            if not isinstance(out, torch.Tensor) or out.dim() != 2:
+                raise ValueError("stack: out must be a uint16 tensor (H, W)")
+            out = out.unsqueeze(0)
+        ref = int(ref)
+        return self.merge(mosaic, lut, shift, before=ref, after=n - 1 - ref, first=ref, count=1, out=out, **kw)[0]
+
     def _denoise_stage(self, mos, denoise, fn):
         """denoise= of the demosaic / decode methods: denoise() with these keyword arguments into a scratch tensor of the
         caching allocator."""
@@ -1442,6 +1565,15 @@ class Context:
         afterwards.  Returns the FrameStats of the (N, H, W) batch."""
         scratch = self._decode_scratch(inputs, width, height, type, check, "decode_stats")
         return self.stats(scratch, bins=bins, shift=shift, sat=sat, roi=roi, out=out, accumulate=accumulate)
+
+    def decode_merge(self, inputs, width, height, type, *, lut, shift, check=True, **merge_kw):
+        """Decode frames of one geometry that are resident in HBM and merge them along time (merge()): the plain uint16
+        mosaics go to a scratch tensor of torch's caching allocator, both steps are queued on torch.cuda.current_stream().
+        inputs: uint8 CUDA tensors, or (device pointer, length) pairs.  check=True synchronises after the decode and raises
+        McrawError naming the frames that failed; check=False returns at once.  The stage the context had before the call is
+        restored afterwards.  merge_kw: merge()'s keyword arguments.  Returns merge()'s (count, H, W)."""
+        scratch = self._decode_scratch(inputs, width, height, type, check, "decode_merge")
+        return self.merge(scratch, lut, shift, **merge_kw)
 
     def demosaic(self, mosaic, *, algo="mhc", dtype, white, black=(0, 0, 0, 0), cfa="rggb", gain=None, matrix=None,
                  clip=False, out=None, check=True, shading=None, defects=None, denoise=None):

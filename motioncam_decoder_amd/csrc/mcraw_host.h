@@ -10,6 +10,7 @@
 //   mcraw_stats.hip    mcraw_stats_batch: its kernels, checks and launches (likewise)
 //   mcraw_fixpix.hip   mcraw_fixpix_batch: likewise
 //   mcraw_denoise.hip  mcraw_denoise_batch: likewise
+//   mcraw_merge.hip    mcraw_merge_batch: likewise
 // Replaces the per-frame dispatch of lib/Decoder.cpp:216-234 with batched submits.  There is no CPU decode fallback in any of them.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
 """Resource report of the demosaic kernels (csrc/mcraw_rgb.hip), of the lens-shading kernel (csrc/mcraw_shade.hip), of the
-statistics kernels (csrc/mcraw_stats.hip), of the defective-pixel kernels (csrc/mcraw_fixpix.hip) and of the denoising kernel
-(csrc/mcraw_denoise.hip): compiles the files for gfx950 with -Rpass-analysis=kernel-resource-usage (no GPU needed) and prints
+statistics kernels (csrc/mcraw_stats.hip), of the defective-pixel kernels (csrc/mcraw_fixpix.hip), of the denoising kernel
+(csrc/mcraw_denoise.hip) and of the temporal merge (csrc/mcraw_merge.hip): compiles the files for gfx950 with -Rpass-analysis=kernel-resource-usage (no GPU needed) and prints
 one line per instance in the format of profiles/rgb_resources.txt / display_resources.txt / yuv_resources.txt /
-shade_resources.txt / stats_resources.txt / fixpix_resources.txt / denoise_resources.txt.
+shade_resources.txt / stats_resources.txt / fixpix_resources.txt / denoise_resources.txt / merge_resources.txt.
 
     python tools/rgb_resources.py            # every instance
-    python tools/rgb_resources.py --check    # the figures in the seven committed files must equal the compiler's; exit 1 if not
+    python tools/rgb_resources.py --check    # the figures in the eight committed files must equal the compiler's; exit 1 if not
 """
 import os
 import re
@@ -28,6 +28,8 @@ FIXPIX_FILE = "fixpix_resources.txt"
 FIXPIX_NAME = r"Function Name: _ZN5mcraw\d+(kfixpix_init|kfixpix_list|kfixpix)(?:ILb([01])EEEv|E)"  # kfixpix<NT>, the list pass, the counts' init
 DENOISE_FILE = "denoise_resources.txt"
 DENOISE_NAME = r"Function Name: _ZN5mcraw\d+(kdenoise)ILi([12])ELb([01])EEEv"  # kdenoise<RADIUS, NT>
+MERGE_FILE = "merge_resources.txt"
+MERGE_NAME = r"Function Name: _ZN5mcraw\d+(kmerge)ILi([01])ELb([01])EEEv"  # kmerge<SUPPORT, NT>
 SHADE_NAME = r"Function Name: _ZN5mcraw\d+(kshade)ILb([01])EEEv"  # kshade<NT>: `sc1 nt` streaming stores or plain ones
 
 
@@ -42,6 +44,8 @@ def _label(m):
         return "kfixpix<%s>" % ("stream" if m.group(2) == "1" else "plain")
     if m.group(1) == "kdenoise":
         return "kdenoise<R=%s,%s>" % (m.group(2), "stream" if m.group(3) == "1" else "plain")
+    if m.group(1) == "kmerge":
+        return "kmerge<S=%s,%s>" % (m.group(2), "stream" if m.group(3) == "1" else "plain")
     if m.group(1) == "kshade":
         return "kshade<%s>" % ("stream" if m.group(2) == "1" else "plain")
     return "%s<%s,S=%s>" % (m.group(1), KINDS[int(m.group(2))], m.group(3))
@@ -86,12 +90,14 @@ def _check(files, rep, prefix):
 def main():
     rep, shade, stats = report(), report("mcraw_shade.hip", SHADE_NAME), report("mcraw_stats.hip", STATS_NAME)
     fixpix, denoise = report("mcraw_fixpix.hip", FIXPIX_NAME), report("mcraw_denoise.hip", DENOISE_NAME)
+    merge = report("mcraw_merge.hip", MERGE_NAME)
     if "--check" not in sys.argv:
-        for line in list(rep.values()) + list(shade.values()) + list(stats.values()) + list(fixpix.values()) + list(denoise.values()):
+        for line in list(rep.values()) + list(shade.values()) + list(stats.values()) + list(fixpix.values()) + list(denoise.values()) + \
+                list(merge.values()):
             print(line)
         return 0
     return _check(FILES, rep, "krgb_") | _check((SHADE_FILE,), shade, "kshade") | _check((STATS_FILE,), stats, "kstats") | \
-        _check((FIXPIX_FILE,), fixpix, "kfixpix") | _check((DENOISE_FILE,), denoise, "kdenoise")
+        _check((FIXPIX_FILE,), fixpix, "kfixpix") | _check((DENOISE_FILE,), denoise, "kdenoise") | _check((MERGE_FILE,), merge, "kmerge")
 
 
 if __name__ == "__main__":
