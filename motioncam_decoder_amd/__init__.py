@@ -1141,6 +1141,70 @@ class Context:
         self._side.wait_stream(cur)
         return cur, self._side
 
+    def _mosaic_arg(self, torch, dev, fn, mosaic, dims=(2, 3)):
+        """The mosaic argument of method `fn`, checked, as (mos, single, n, h, w): mos is (N, H, W); single: the caller's was
+        (H, W)."""
+        if not isinstance(mosaic, torch.Tensor) or mosaic.dtype != torch.uint16 or mosaic.device != dev or mosaic.dim() not in dims:
+            raise ValueError("%s: mosaic must be a uint16 tensor (N, H, W)%s on %s" % (fn, " or (H, W)" if 2 in dims else "", dev))
+        single = mosaic.dim() == 2
+        mos = mosaic.unsqueeze(0) if single else mosaic
+        n, h, w = (int(v) for v in mos.shape)
+        return mos, single, n, h, w
+
+    @staticmethod
+    def _out_arg(torch, dev, fn, out, shape, dtype=None, contiguous=False):
+        """The `out` argument of method `fn`: a new contiguous tensor of `shape`, or the caller's, checked."""
+        dtype = torch.uint16 if dtype is None else dtype
+        if out is None:
+            return torch.empty(tuple(shape), dtype=dtype, device=dev)
+        if not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(shape) or out.dtype != dtype or out.device != dev \
+                or (contiguous and not out.is_contiguous()):
+            raise ValueError("%s: out must be a %s%s tensor of shape %s on %s" % (
+                fn, "contiguous " if contiguous else "", str(dtype).replace("torch.", ""), tuple(shape), dev))
+        return out
+
+    @staticmethod
+    def _strided(fn, what, t, h, w):
+        """A batch of mosaics (frames, H, W) as the library takes it: (pointer, pitch, frame stride), in elements.  Rows must be
+        contiguous; the stride of a dimension of one entry means nothing and is replaced by the packed one."""
+        if w > 1 and t.stride(2) != 1:
+            raise ValueError("%s: the rows of %s must be contiguous" % (fn, what))
+        pitch = int(t.stride(1)) if h > 1 else w
+        return C.c_void_p(t.data_ptr()), pitch, (int(t.stride(0)) if int(t.shape[0]) > 1 else pitch * h)
+
+    def _noise_table(self, torch, dev, fn, lut, n):
+        """The noise table of denoise / merge (a CUDA uint16 tensor, or a host array from noise_lut, uploaded on the current
+        stream) as (tensor, nluts, L)."""
+        import numpy as np
+        if isinstance(lut, np.ndarray):
+            if lut.dtype != np.uint16:
+                raise ValueError("%s: a lut array must be uint16 (noise_lut makes one)" % fn)
+            lut = torch.from_numpy(np.ascontiguousarray(lut).view(np.int16)).to(dev).view(torch.uint16)
+        if not isinstance(lut, torch.Tensor) or lut.dtype != torch.uint16 or lut.device != dev or lut.dim() not in (2, 3) \
+                or not lut.is_contiguous():
+            raise ValueError("%s: lut must be a contiguous uint16 tensor (4, L) or (N, 4, L) on %s" % (fn, dev))
+        nluts, L = (int(lut.shape[0]) if lut.dim() == 3 else 1), int(lut.shape[-1])
+        if int(lut.shape[-2]) != 4 or L not in (64, 128, 256, 512, 1024) or (lut.dim() == 3 and nluts != n):
+            raise ValueError("%s: lut must hold four planes of 64 .. 1024 (a power of two) entries, for all frames or for "
+                             "each of the %d" % (fn, n))
+        return lut, nluts, L
+
+    def _call(self, torch, dev, symbol, tensors, *args):
+        """One call of the library's `symbol`(context, *args, stream) on _run_stream's stream.  When that is the side stream, the
+        tensors that take part (None: skipped) are recorded on it and the current stream waits for it.  A non-zero return raises
+        McrawError."""
+        cur, run = self._run_stream(torch, dev)
+        try:
+            rc = getattr(self._lib, symbol)(self._h, *args, C.c_void_p(run.cuda_stream))
+        finally:
+            if run is not cur:
+                for t in tensors:
+                    if t is not None:
+                        t.record_stream(run)
+                cur.wait_stream(run)
+        if rc != 0:
+            raise McrawError("%s failed (%d): %s" % (symbol, rc, self._lib.mcraw_last_error().decode()))
+
     def _shading_tensor(self, torch, dev, shading, n, fn):
         """The device gain map of `shading` (a CUDA uint16 tensor, or a host array from gain_map, uploaded on the current
         stream) as (tensor, maps, gh, gw)."""
@@ -1169,18 +1233,12 @@ class Context:
         shape, or the mosaic itself (in place).  Queued on torch.cuda.current_stream(); nothing synchronises."""
         import torch
         dev = self._torch_device(torch)
-        if not isinstance(mosaic, torch.Tensor) or mosaic.dtype != torch.uint16 or mosaic.device != dev or mosaic.dim() not in (2, 3):
-            raise ValueError("shade: mosaic must be a uint16 tensor (N, H, W) or (H, W) on %s" % dev)
-        if out is None:
-            out = torch.empty(tuple(mosaic.shape), dtype=torch.uint16, device=dev)
-        elif not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(mosaic.shape) or out.dtype != torch.uint16 or out.device != dev:
-            raise ValueError("shade: out must be a uint16 tensor of shape %s on %s" % (tuple(mosaic.shape), dev))
-        mos, dst = (mosaic.unsqueeze(0), out.unsqueeze(0)) if mosaic.dim() == 2 else (mosaic, out)
-        n, h, w = (int(v) for v in mos.shape)
+        mos, single, n, h, w = self._mosaic_arg(torch, dev, "shade", mosaic)
+        out = self._out_arg(torch, dev, "shade", out, mosaic.shape)
         if n == 0 or h == 0 or w == 0:
             return out
-        if w > 1 and (mos.stride(2) != 1 or dst.stride(2) != 1):
-            raise ValueError("shade: the rows of the mosaic and of out must be contiguous")
+        src = self._strided("shade", "the mosaic", mos, h, w)
+        dst = self._strided("shade", "out", out.unsqueeze(0) if single else out, h, w)
         shading, maps, gh, gw = self._shading_tensor(torch, dev, shading, n, "shade")
         black = list(black)
         if len(black) != 4:
@@ -1191,22 +1249,7 @@ class Context:
             s.black[i] = int(black[i])
         s.reserved[0] = s.reserved[1] = 0
         s.map = shading.data_ptr()
-        ip = int(mos.stride(1)) if h > 1 else w
-        op = int(dst.stride(1)) if h > 1 else w
-        ifs = int(mos.stride(0)) if n > 1 else ip * h
-        ofs = int(dst.stride(0)) if n > 1 else op * h
-        cur, run = self._run_stream(torch, dev)
-        try:
-            rc = self._lib.mcraw_shade_batch(self._h, C.byref(s), C.c_void_p(mos.data_ptr()), ip, ifs, w, h, n,
-                                             C.c_void_p(dst.data_ptr()), op, ofs, C.c_void_p(run.cuda_stream))
-        finally:
-            if run is not cur:
-                mos.record_stream(run)
-                dst.record_stream(run)
-                shading.record_stream(run)
-                cur.wait_stream(run)
-        if rc != 0:
-            raise McrawError("mcraw_shade_batch failed (%d): %s" % (rc, self._lib.mcraw_last_error().decode()))
+        self._call(torch, dev, "mcraw_shade_batch", (mos, out, shading), C.byref(s), *src, w, h, n, *dst)
         return out
 
     def fix_pixels(self, mosaic, *, black=(0, 0, 0, 0), abs_thr, rel_thr=0.0, rank=2, hot=True, cold=True, pixels=None,
@@ -1229,8 +1272,7 @@ class Context:
         import numpy as np
         import torch
         dev = self._torch_device(torch)
-        if not isinstance(mosaic, torch.Tensor) or mosaic.dtype != torch.uint16 or mosaic.device != dev or mosaic.dim() not in (2, 3):
-            raise ValueError("fix_pixels: mosaic must be a uint16 tensor (N, H, W) or (H, W) on %s" % dev)
+        mos, single, n, h, w = self._mosaic_arg(torch, dev, "fix_pixels", mosaic)
         four = lambda v: [v] * 4 if not hasattr(v, "__len__") else list(v)
         black, abs_thr = four(black), four(abs_thr)
         if len(black) != 4 or len(abs_thr) != 4 or any(v != int(v) or v < 0 or v > 65535 for v in black + abs_thr):
@@ -1242,21 +1284,15 @@ class Context:
             raise ValueError("fix_pixels: rel_thr * 256 must round into 0 .. 65535, not %r" % (rel_thr,))
         if rank not in (1, 2):
             raise ValueError("fix_pixels: rank must be 1 or 2, not %r" % (rank,))
-        single = mosaic.dim() == 2
-        if out is None:
-            out = torch.empty(tuple(mosaic.shape), dtype=torch.uint16, device=dev)
-        elif not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(mosaic.shape) or out.dtype != torch.uint16 or out.device != dev:
-            raise ValueError("fix_pixels: out must be a uint16 tensor of shape %s on %s" % (tuple(mosaic.shape), dev))
-        mos, dst = (mosaic.unsqueeze(0), out.unsqueeze(0)) if single else (mosaic, out)
-        n, h, w = (int(v) for v in mos.shape)
+        out = self._out_arg(torch, dev, "fix_pixels", out, mosaic.shape)
         cnt = torch.empty((n, 2, 4), dtype=torch.int32, device=dev) if counts else None  # (the call initialises the records)
         res = (out, cnt[0] if single else cnt) if counts else out
         if n == 0 or h == 0 or w == 0:
             if counts:
                 cnt.zero_()
             return res
-        if w > 1 and (mos.stride(2) != 1 or dst.stride(2) != 1):
-            raise ValueError("fix_pixels: the rows of the mosaic and of out must be contiguous")
+        src = self._strided("fix_pixels", "the mosaic", mos, h, w)
+        dst = self._strided("fix_pixels", "out", out.unsqueeze(0) if single else out, h, w)
         lst = None
         if pixels is not None:
             if isinstance(pixels, torch.Tensor):
@@ -1276,25 +1312,7 @@ class Context:
         s.list = lst.data_ptr() if s.nlist else None
         s.counts = cnt.data_ptr() if counts else None
         s.reserved[0] = s.reserved[1] = 0
-        ip = int(mos.stride(1)) if h > 1 else w
-        op = int(dst.stride(1)) if h > 1 else w
-        ifs = int(mos.stride(0)) if n > 1 else ip * h
-        ofs = int(dst.stride(0)) if n > 1 else op * h
-        cur, run = self._run_stream(torch, dev)
-        try:
-            rc = self._lib.mcraw_fixpix_batch(self._h, C.byref(s), C.c_void_p(mos.data_ptr()), ip, ifs, w, h, n,
-                                              C.c_void_p(dst.data_ptr()), op, ofs, C.c_void_p(run.cuda_stream))
-        finally:
-            if run is not cur:
-                mos.record_stream(run)
-                dst.record_stream(run)
-                if lst is not None:
-                    lst.record_stream(run)
-                if cnt is not None:
-                    cnt.record_stream(run)
-                cur.wait_stream(run)
-        if rc != 0:
-            raise McrawError("mcraw_fixpix_batch failed (%d): %s" % (rc, self._lib.mcraw_last_error().decode()))
+        self._call(torch, dev, "mcraw_fixpix_batch", (mos, out, lst, cnt), C.byref(s), *src, w, h, n, *dst)
         return res
 
     def _fix_defects(self, mos, defects, black, fn):
@@ -1319,8 +1337,7 @@ class Context:
         import numpy as np
         import torch
         dev = self._torch_device(torch)
-        if not isinstance(mosaic, torch.Tensor) or mosaic.dtype != torch.uint16 or mosaic.device != dev or mosaic.dim() not in (2, 3):
-            raise ValueError("denoise: mosaic must be a uint16 tensor (N, H, W) or (H, W) on %s" % dev)
+        mos, single, n, h, w = self._mosaic_arg(torch, dev, "denoise", mosaic)
         if radius not in (1, 2):
             raise ValueError("denoise: radius must be 1 or 2, not %r" % (radius,))
         amt = float(amount)
@@ -1328,47 +1345,17 @@ class Context:
             raise ValueError("denoise: amount * 256 must round into 1 .. 256, not %r" % (amount,))
         if shift != int(shift) or not 0 <= int(shift) <= 15:
             raise ValueError("denoise: shift must be an integer 0 .. 15, not %r" % (shift,))
-        if out is None:
-            out = torch.empty(tuple(mosaic.shape), dtype=torch.uint16, device=dev)
-        elif not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(mosaic.shape) or out.dtype != torch.uint16 or out.device != dev:
-            raise ValueError("denoise: out must be a uint16 tensor of shape %s on %s" % (tuple(mosaic.shape), dev))
-        mos, dst = (mosaic.unsqueeze(0), out.unsqueeze(0)) if mosaic.dim() == 2 else (mosaic, out)
-        n, h, w = (int(v) for v in mos.shape)
-        if isinstance(lut, np.ndarray):
-            if lut.dtype != np.uint16:
-                raise ValueError("denoise: a lut array must be uint16 (noise_lut makes one)")
-            lut = torch.from_numpy(np.ascontiguousarray(lut).view(np.int16)).to(dev).view(torch.uint16)
-        if not isinstance(lut, torch.Tensor) or lut.dtype != torch.uint16 or lut.device != dev or lut.dim() not in (2, 3) \
-                or not lut.is_contiguous():
-            raise ValueError("denoise: lut must be a contiguous uint16 tensor (4, L) or (N, 4, L) on %s" % dev)
-        nluts, L = (int(lut.shape[0]) if lut.dim() == 3 else 1), int(lut.shape[-1])
-        if int(lut.shape[-2]) != 4 or L not in (64, 128, 256, 512, 1024) or (lut.dim() == 3 and nluts != n):
-            raise ValueError("denoise: lut must hold four planes of 64 .. 1024 (a power of two) entries, for all frames or for "
-                             "each of the %d" % n)
+        out = self._out_arg(torch, dev, "denoise", out, mosaic.shape)
+        lut, nluts, L = self._noise_table(torch, dev, "denoise", lut, n)
         if n == 0 or h == 0 or w == 0:
             return out
-        if w > 1 and (mos.stride(2) != 1 or dst.stride(2) != 1):
-            raise ValueError("denoise: the rows of the mosaic and of out must be contiguous")
+        src = self._strided("denoise", "the mosaic", mos, h, w)
+        dst = self._strided("denoise", "out", out.unsqueeze(0) if single else out, h, w)
         s = Denoise()
         s.radius, s.amount, s.lut_log2, s.shift, s.nluts = int(radius), int(np.rint(amt * 256.0)), L.bit_length() - 1, int(shift), nluts
         s.reserved[0] = s.reserved[1] = s.reserved[2] = 0
         s.lut = lut.data_ptr()
-        ip = int(mos.stride(1)) if h > 1 else w
-        op = int(dst.stride(1)) if h > 1 else w
-        ifs = int(mos.stride(0)) if n > 1 else ip * h
-        ofs = int(dst.stride(0)) if n > 1 else op * h
-        cur, run = self._run_stream(torch, dev)
-        try:
-            rc = self._lib.mcraw_denoise_batch(self._h, C.byref(s), C.c_void_p(mos.data_ptr()), ip, ifs, w, h, n,
-                                               C.c_void_p(dst.data_ptr()), op, ofs, C.c_void_p(run.cuda_stream))
-        finally:
-            if run is not cur:
-                mos.record_stream(run)
-                dst.record_stream(run)
-                lut.record_stream(run)
-                cur.wait_stream(run)
-        if rc != 0:
-            raise McrawError("mcraw_denoise_batch failed (%d): %s" % (rc, self._lib.mcraw_last_error().decode()))
+        self._call(torch, dev, "mcraw_denoise_batch", (mos, out, lut), C.byref(s), *src, w, h, n, *dst)
         return out
 
     def merge(self, mosaic, lut, shift, before=2, after=2, first=0, count=None, support=1, amount=1.0, pos=None, out=None):
@@ -1388,9 +1375,7 @@ class Context:
         import numpy as np
         import torch
         dev = self._torch_device(torch)
-        if not isinstance(mosaic, torch.Tensor) or mosaic.dtype != torch.uint16 or mosaic.device != dev or mosaic.dim() != 3:
-            raise ValueError("merge: mosaic must be a uint16 tensor (N, H, W) on %s" % dev)
-        n, h, w = (int(v) for v in mosaic.shape)
+        mosaic, _, n, h, w = self._mosaic_arg(torch, dev, "merge", mosaic, dims=(3,))
         for name, v in (("before", before), ("after", after), ("first", first)) + ((("count", count),) if count is not None else ()):
             if isinstance(v, bool) or v != int(v) or int(v) < 0:
                 raise ValueError("merge: %s must be a non-negative integer, not %r" % (name, v))
@@ -1409,21 +1394,8 @@ class Context:
             raise ValueError("merge: amount * 256 must round into 1 .. 256, not %r" % (amount,))
         if shift != int(shift) or not 0 <= int(shift) <= 15:
             raise ValueError("merge: shift must be an integer 0 .. 15, not %r" % (shift,))
-        if out is None:
-            out = torch.empty((count, h, w), dtype=torch.uint16, device=dev)
-        elif not isinstance(out, torch.Tensor) or tuple(out.shape) != (count, h, w) or out.dtype != torch.uint16 or out.device != dev:
-            raise ValueError("merge: out must be a uint16 tensor of shape %s on %s" % ((count, h, w), dev))
-        if isinstance(lut, np.ndarray):
-            if lut.dtype != np.uint16:
-                raise ValueError("merge: a lut array must be uint16 (noise_lut makes one)")
-            lut = torch.from_numpy(np.ascontiguousarray(lut).view(np.int16)).to(dev).view(torch.uint16)
-        if not isinstance(lut, torch.Tensor) or lut.dtype != torch.uint16 or lut.device != dev or lut.dim() not in (2, 3) \
-                or not lut.is_contiguous():
-            raise ValueError("merge: lut must be a contiguous uint16 tensor (4, L) or (N, 4, L) on %s" % dev)
-        nluts, L = (int(lut.shape[0]) if lut.dim() == 3 else 1), int(lut.shape[-1])
-        if int(lut.shape[-2]) != 4 or L not in (64, 128, 256, 512, 1024) or (lut.dim() == 3 and nluts != n):
-            raise ValueError("merge: lut must hold four planes of 64 .. 1024 (a power of two) entries, for all frames or for "
-                             "each of the %d" % n)
+        out = self._out_arg(torch, dev, "merge", out, (count, h, w))
+        lut, nluts, L = self._noise_table(torch, dev, "merge", lut, n)
         if pos is not None:
             if isinstance(pos, torch.Tensor):
                 if pos.dtype != torch.int16 or pos.device != dev or tuple(pos.shape) != (n, 2) or not pos.is_contiguous():
@@ -1435,31 +1407,14 @@ class Context:
                 pos = torch.from_numpy(np.ascontiguousarray(a, dtype=np.int16)).to(dev)
         if n == 0 or count == 0 or h == 0 or w == 0:
             return out
-        if w > 1 and (mosaic.stride(2) != 1 or out.stride(2) != 1):
-            raise ValueError("merge: the rows of the mosaic and of out must be contiguous")
+        src = self._strided("merge", "the mosaic", mosaic, h, w)
+        dst = self._strided("merge", "out", out, h, w)  # (its frame stride counts for more than one OUTPUT)
         s = Merge()
         s.before, s.after, s.first, s.count, s.support = before, after, first, count, int(support)
         s.amount, s.lut_log2, s.shift, s.nluts, s.reserved = int(np.rint(amt * 256.0)), L.bit_length() - 1, int(shift), nluts, 0
         s.lut = lut.data_ptr()
         s.pos = pos.data_ptr() if pos is not None else None
-        ip = int(mosaic.stride(1)) if h > 1 else w
-        op = int(out.stride(1)) if h > 1 else w
-        ifs = int(mosaic.stride(0)) if n > 1 else ip * h
-        ofs = int(out.stride(0)) if count > 1 else op * h
-        cur, run = self._run_stream(torch, dev)
-        try:
-            rc = self._lib.mcraw_merge_batch(self._h, C.byref(s), C.c_void_p(mosaic.data_ptr()), ip, ifs, w, h, n,
-                                             C.c_void_p(out.data_ptr()), op, ofs, C.c_void_p(run.cuda_stream))
-        finally:
-            if run is not cur:
-                mosaic.record_stream(run)
-                out.record_stream(run)
-                lut.record_stream(run)
-                if pos is not None:
-                    pos.record_stream(run)
-                cur.wait_stream(run)
-        if rc != 0:
-            raise McrawError("mcraw_merge_batch failed (%d): %s" % (rc, self._lib.mcraw_last_error().decode()))
+        self._call(torch, dev, "mcraw_merge_batch", (mosaic, out, lut, pos), C.byref(s), *src, w, h, n, *dst)
         return out
 
     def stack(self, mosaic, lut, shift, ref=0, **kw):
@@ -1502,8 +1457,7 @@ class Context:
         An (H, W) mosaic drops N.  Queued on torch.cuda.current_stream(); nothing synchronises."""
         import torch
         dev = self._torch_device(torch)
-        if not isinstance(mosaic, torch.Tensor) or mosaic.dtype != torch.uint16 or mosaic.device != dev or mosaic.dim() not in (2, 3):
-            raise ValueError("stats: mosaic must be a uint16 tensor (N, H, W) or (H, W) on %s" % dev)
+        mos, single, n, h, w = self._mosaic_arg(torch, dev, "stats", mosaic)
         bins = int(bins)
         if bins < 64 or bins > 4096 or bins & (bins - 1):
             raise ValueError("stats: bins must be a power of two in 64 .. 4096, not %r" % (bins,))
@@ -1514,25 +1468,17 @@ class Context:
             shift = 0
             while (max(sat) >> shift) >= bins:
                 shift += 1
-        single = mosaic.dim() == 2
-        mos = mosaic.unsqueeze(0) if single else mosaic
-        n, h, w = (int(v) for v in mos.shape)
         if h == 0 or w == 0:
             raise ValueError("stats: empty frames have no statistics")
-        if w > 1 and mos.stride(2) != 1:
-            raise ValueError("stats: the rows of the mosaic must be contiguous")
+        src = self._strided("stats", "the mosaic", mos, h, w)
         y0, x0, rh, rw = (0, 0, h, w) if roi is None else (int(v) for v in roi)
         if min(y0, x0) < 0 or rh < 1 or rw < 1 or y0 + rh > h or x0 + rw > w:
             raise ValueError("stats: roi (y0, x0, h, w) = %r leaves the %d x %d frame" % (roi, h, w))
         rec = 16 * bins + 96
         want = (rec,) if single else (n, rec)
-        if out is None:
-            if accumulate:
-                raise ValueError("stats: accumulate=True needs the records to add to (out=)")
-            out = torch.empty(want, dtype=torch.uint8, device=dev)
-        elif not isinstance(out, torch.Tensor) or tuple(out.shape) != want or out.dtype != torch.uint8 or out.device != dev \
-                or not out.is_contiguous():
-            raise ValueError("stats: out must be a contiguous uint8 tensor of shape %s on %s" % (want, dev))
+        if out is None and accumulate:
+            raise ValueError("stats: accumulate=True needs the records to add to (out=)")
+        out = self._out_arg(torch, dev, "stats", out, want, torch.uint8, contiguous=True)
         res = FrameStats(out, bins, shift)
         if n == 0:
             return res
@@ -1541,19 +1487,7 @@ class Context:
         for i in range(4):
             s.sat[i] = sat[i]
         s.flags, s.reserved = (STATS_ACCUMULATE if accumulate else 0), 0
-        pitch = int(mos.stride(1)) if h > 1 else w
-        fstride = int(mos.stride(0)) if n > 1 else pitch * h
-        cur, run = self._run_stream(torch, dev)
-        try:
-            rc = self._lib.mcraw_stats_batch(self._h, C.byref(s), C.c_void_p(mos.data_ptr()), pitch, fstride, w, h, n,
-                                             C.c_void_p(out.data_ptr()), n * rec, C.c_void_p(run.cuda_stream))
-        finally:
-            if run is not cur:
-                mos.record_stream(run)
-                out.record_stream(run)
-                cur.wait_stream(run)
-        if rc != 0:
-            raise McrawError("mcraw_stats_batch failed (%d): %s" % (rc, self._lib.mcraw_last_error().decode()))
+        self._call(torch, dev, "mcraw_stats_batch", (mos, out), C.byref(s), *src, w, h, n, C.c_void_p(out.data_ptr()), n * rec)
         return res
 
     def decode_stats(self, inputs, width, height, type, *, bins=256, shift=None, sat=65535, roi=None, out=None,
@@ -1600,10 +1534,7 @@ class Context:
         code = _float_code(dtype)
         tdtype = {FLOAT_F32: torch.float32, FLOAT_F16: torch.float16, FLOAT_BF16: torch.bfloat16}[code]
         dev = self._torch_device(torch)
-        if not isinstance(mosaic, torch.Tensor) or mosaic.dtype != torch.uint16 or mosaic.device != dev or mosaic.dim() not in (2, 3):
-            raise ValueError("demosaic: mosaic must be a uint16 tensor (N, H, W) or (H, W) on %s" % dev)
-        single = mosaic.dim() == 2
-        mos = mosaic.unsqueeze(0) if single else mosaic
+        mos, single = self._mosaic_arg(torch, dev, "demosaic", mosaic)[:2]
         if defects is not None and mos.numel():  # into a scratch tensor, in front of the gains
             mos = self._fix_defects(mos, defects, black, "demosaic")
         if denoise is not None and mos.numel():  # on the sensor's values: behind the defects, in front of the gains
@@ -1611,33 +1542,16 @@ class Context:
         if shading is not None and mos.numel():  # into a scratch tensor: the caller's mosaic stays as it is
             mos = self.shade(mos, shading, black=black)
         n, h, w = (int(v) for v in mos.shape)
-        if n and h > 1 and mos.stride(2) != 1:
-            raise ValueError("demosaic: the rows of the mosaic must be contiguous")
+        src = self._strided("demosaic", "the mosaic", mos, h, w) if n else None
         ho, wo = (h, w) if algo == "mhc" else (h // 2, w // 2)
         shape = (n, 3, ho, wo)
         want = shape[1:] if single else shape
-        if out is None:
-            out = torch.empty(want, dtype=tdtype, device=dev)
-        elif tuple(out.shape) != tuple(want) or out.dtype != tdtype or out.device != dev or not out.is_contiguous():
-            raise ValueError("demosaic: out must be a contiguous %s tensor of shape %s on %s" % (tdtype, tuple(want), dev))
+        out = self._out_arg(torch, dev, "demosaic", out, want, tdtype, contiguous=True)
         if n == 0:
             return out
         cols, nc = _rgb_colors(gain, matrix, n, "demosaic")
         prm = _rgb_params(algo, code, FLOAT_CLIP if clip else 0, key, white, black)
-        pitch = int(mos.stride(1)) if h > 1 else w
-        fstride = int(mos.stride(0)) if n > 1 else pitch * h
-        cur, run = self._run_stream(torch, dev)
-        try:
-            rc = self._lib.mcraw_demosaic_batch(self._h, C.byref(prm), cols, nc, C.c_void_p(mos.data_ptr()), pitch, fstride, w, h,
-                                                n, C.c_void_p(out.data_ptr()), out.numel() * out.element_size(),
-                                                C.c_void_p(run.cuda_stream))
-        finally:
-            if run is not cur:
-                mos.record_stream(run)
-                out.record_stream(run)
-                cur.wait_stream(run)
-        if rc != 0:
-            raise McrawError("mcraw_demosaic_batch failed (%d): %s" % (rc, self._lib.mcraw_last_error().decode()))
+        self._call(torch, dev, "mcraw_demosaic_batch", (mos, out), C.byref(prm), cols, nc, *src, w, h, n, C.c_void_p(out.data_ptr()), out.numel() * out.element_size())
         return out
 
     def _decode_scratch(self, inputs, width, height, type, check, fn):
@@ -1748,10 +1662,7 @@ class Context:
         if layout not in _DISP_LAYOUTS:
             raise ValueError("demosaic_display: layout must be 'hwc' or 'chw', not %r" % (layout,))
         dev = self._torch_device(torch)
-        if not isinstance(mosaic, torch.Tensor) or mosaic.dtype != torch.uint16 or mosaic.device != dev or mosaic.dim() not in (2, 3):
-            raise ValueError("demosaic_display: mosaic must be a uint16 tensor (N, H, W) or (H, W) on %s" % dev)
-        single = mosaic.dim() == 2
-        mos = mosaic.unsqueeze(0) if single else mosaic
+        mos, single = self._mosaic_arg(torch, dev, "demosaic_display", mosaic)[:2]
         if defects is not None and mos.numel():  # into a scratch tensor, in front of the gains
             mos = self._fix_defects(mos, defects, black, "demosaic_display")
         if denoise is not None and mos.numel():  # on the sensor's values: behind the defects, in front of the gains
@@ -1759,15 +1670,11 @@ class Context:
         if shading is not None and mos.numel():  # into a scratch tensor: the caller's mosaic stays as it is
             mos = self.shade(mos, shading, black=black)
         n, h, w = (int(v) for v in mos.shape)
-        if n and h > 1 and mos.stride(2) != 1:
-            raise ValueError("demosaic_display: the rows of the mosaic must be contiguous")
+        src = self._strided("demosaic_display", "the mosaic", mos, h, w) if n else None
         ho, wo = (h, w) if algo == "mhc" else (h // 2, w // 2)
         shape = (n, ho, wo, 3) if layout == "hwc" else (n, 3, ho, wo)
         want = shape[1:] if single else shape
-        if out is None:
-            out = torch.empty(want, dtype=tdtype, device=dev)
-        elif tuple(out.shape) != tuple(want) or out.dtype != tdtype or out.device != dev or not out.is_contiguous():
-            raise ValueError("demosaic_display: out must be a contiguous %s tensor of shape %s on %s" % (tdtype, tuple(want), dev))
+        out = self._out_arg(torch, dev, "demosaic_display", out, want, tdtype, contiguous=True)
         if n == 0:
             return out
         lut, own = self._display_lut(torch, dev, transfer, lut_size, (8 if dcode == DISP_U8 else 16) if bits is None else bits)
@@ -1776,22 +1683,8 @@ class Context:
         d = Display()
         d.dtype, d.layout, d.lut_log2, d.reserved = dcode, _DISP_LAYOUTS[layout], int(lut.numel()).bit_length() - 1, 0
         d.lut = lut.data_ptr()
-        pitch = int(mos.stride(1)) if h > 1 else w
-        fstride = int(mos.stride(0)) if n > 1 else pitch * h
-        cur, run = self._run_stream(torch, dev)
-        try:
-            rc = self._lib.mcraw_demosaic_display_batch(self._h, C.byref(prm), C.byref(d), cols, nc, C.c_void_p(mos.data_ptr()),
-                                                        pitch, fstride, w, h, n, C.c_void_p(out.data_ptr()),
-                                                        out.numel() * out.element_size(), C.c_void_p(run.cuda_stream))
-        finally:
-            if run is not cur:
-                mos.record_stream(run)
-                out.record_stream(run)
-                if own:
-                    lut.record_stream(run)
-                cur.wait_stream(run)
-        if rc != 0:
-            raise McrawError("mcraw_demosaic_display_batch failed (%d): %s" % (rc, self._lib.mcraw_last_error().decode()))
+        self._call(torch, dev, "mcraw_demosaic_display_batch", (mos, out, lut if own else None), C.byref(prm), C.byref(d), cols, nc,
+                   *src, w, h, n, C.c_void_p(out.data_ptr()), out.numel() * out.element_size())
         return out
 
     def decode_display(self, inputs, width, height, type, *, algo="mhc", white, black=(0, 0, 0, 0), cfa="rggb", gain=None,
@@ -1837,10 +1730,7 @@ class Context:
         cy, cb, cr, sh, y_off, c_off = yuv_matrix(standard, range, bits, in_bits)
         tdtype = torch.uint8 if fcode == YUV_NV12 else torch.uint16
         dev = self._torch_device(torch)
-        if not isinstance(mosaic, torch.Tensor) or mosaic.dtype != torch.uint16 or mosaic.device != dev or mosaic.dim() not in (2, 3):
-            raise ValueError("demosaic_yuv: mosaic must be a uint16 tensor (N, H, W) or (H, W) on %s" % dev)
-        single = mosaic.dim() == 2
-        mos = mosaic.unsqueeze(0) if single else mosaic
+        mos, single = self._mosaic_arg(torch, dev, "demosaic_yuv", mosaic)[:2]
         if defects is not None and mos.numel():  # into a scratch tensor, in front of the gains
             mos = self._fix_defects(mos, defects, black, "demosaic_yuv")
         if denoise is not None and mos.numel():  # on the sensor's values: behind the defects, in front of the gains
@@ -1848,15 +1738,11 @@ class Context:
         if shading is not None and mos.numel():  # into a scratch tensor: the caller's mosaic stays as it is
             mos = self.shade(mos, shading, black=black)
         n, h, w = (int(v) for v in mos.shape)
-        if n and h > 1 and mos.stride(2) != 1:
-            raise ValueError("demosaic_yuv: the rows of the mosaic must be contiguous")
+        src = self._strided("demosaic_yuv", "the mosaic", mos, h, w) if n else None
         ho, wo = (h, w) if algo == "mhc" else (h // 2, w // 2)
         shape = (n, ho * 3 // 2, wo)
         want = shape[1:] if single else shape
-        if out is None:
-            out = torch.empty(want, dtype=tdtype, device=dev)
-        elif tuple(out.shape) != tuple(want) or out.dtype != tdtype or out.device != dev or not out.is_contiguous():
-            raise ValueError("demosaic_yuv: out must be a contiguous %s tensor of shape %s on %s" % (tdtype, tuple(want), dev))
+        out = self._out_arg(torch, dev, "demosaic_yuv", out, want, tdtype, contiguous=True)
         if n == 0:
             return out
         lut, own = self._display_lut(torch, dev, transfer, lut_size, in_bits)
@@ -1868,22 +1754,8 @@ class Context:
             y.cy[i], y.cb[i], y.cr[i] = cy[i], cb[i], cr[i]
         y.reserved = 0
         y.lut = lut.data_ptr()
-        pitch = int(mos.stride(1)) if h > 1 else w
-        fstride = int(mos.stride(0)) if n > 1 else pitch * h
-        cur, run = self._run_stream(torch, dev)
-        try:
-            rc = self._lib.mcraw_demosaic_yuv_batch(self._h, C.byref(prm), C.byref(y), cols, nc, C.c_void_p(mos.data_ptr()), pitch,
-                                                    fstride, w, h, n, C.c_void_p(out.data_ptr()),
-                                                    out.numel() * out.element_size(), C.c_void_p(run.cuda_stream))
-        finally:
-            if run is not cur:
-                mos.record_stream(run)
-                out.record_stream(run)
-                if own:
-                    lut.record_stream(run)
-                cur.wait_stream(run)
-        if rc != 0:
-            raise McrawError("mcraw_demosaic_yuv_batch failed (%d): %s" % (rc, self._lib.mcraw_last_error().decode()))
+        self._call(torch, dev, "mcraw_demosaic_yuv_batch", (mos, out, lut if own else None), C.byref(prm), C.byref(y), cols, nc,
+                   *src, w, h, n, C.c_void_p(out.data_ptr()), out.numel() * out.element_size())
         return out
 
     def decode_yuv(self, inputs, width, height, type, *, algo="mhc", white, black=(0, 0, 0, 0), cfa="rggb", gain=None,

@@ -10,15 +10,15 @@
 // rows it reads 8 + 4R samples and accumulates, for all 8 pixels, q = x * x, q * a and a over the 2R + 1 columns.  The
 // centre counts as a neighbour of itself (x = 0, weight 256): that is the contract's 256 * c and 256.  |a - c| runs packed
 // on the dwords as they lie in memory; every product has a factor below 2^24.
-#include "mcraw_dev.h"
 #include "mcraw_host.h"
+#include "mcraw_mosaic.h"
 
 namespace mcraw {
 
-constexpr int DN_T = 256;        // threads per workgroup
+constexpr int DN_T = TILE_T;     // threads per workgroup
 constexpr uint32_t DN_LX = 32u;  // lanes across a tile: 8 columns each
 constexpr uint32_t DN_LY = DN_T / DN_LX;
-constexpr uint32_t DN_TW = 8u * DN_LX;
+constexpr uint32_t DN_TW = TILE_W;
 // Tile rows: 32 re-reads 40/32 of the rows at radius 2 (21.3 KB of LDS), 16 re-reads 24/16 (12.8 KB).
 // -DMCRAW_DENOISE_TH=16 builds the other one; tools/bench_denoise.py --alt-lib runs two builds side by side.
 #ifndef MCRAW_DENOISE_TH
@@ -26,8 +26,8 @@ constexpr uint32_t DN_TW = 8u * DN_LX;
 #endif
 constexpr uint32_t DN_TH = MCRAW_DENOISE_TH;
 static_assert(DN_TH == 16u || DN_TH == 32u, "the lanes' rows are DN_LY apart: the tile is a multiple of it");
-constexpr uint32_t DN_LW = DN_TW + 16u; // LDS row: 8 columns either side (2 * RADIUS used), so that chunks stay on the 8-grid
-constexpr uint32_t DN_CH = DN_LW / 8u;  // 16-byte chunks per LDS row
+constexpr uint32_t DN_LW = TILE_LW;     // LDS row: 8 columns either side (2 * RADIUS used), so that chunks stay on the 8-grid
+constexpr uint32_t DN_CH = TILE_CH;     // 16-byte chunks per LDS row
 
 // Which stores the full aligned pieces of the output rows use: `sc1 nt` streaming stores (store_stream16) or plain ones.
 // -DMCRAW_DENOISE_FLIP_STORES builds the other one.
@@ -74,61 +74,6 @@ __device__ __forceinline__ uint32_t dn_swap(int c, int n)
     return ((c & ~1) == 2 ? 1u : 0u) | (static_cast<uint32_t>(c + 4 - n) < 2u ? 2u : 0u);
 }
 
-// Two uint16 per dword, both halves at once (v_pk_max_u16, v_pk_min_u16, v_pk_sub_u16).
-typedef unsigned short dn_u16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t dn_pkabsdiff(uint32_t a, uint32_t b)
-{
-    const dn_u16x2 x = __builtin_bit_cast(dn_u16x2, a), y = __builtin_bit_cast(dn_u16x2, b);
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(x, y) - __builtin_elementwise_min(x, y));
-}
-
-__device__ __forceinline__ uint32_t dn_half(uint32_t w, uint32_t h)
-{
-    return h ? w >> 16 : w & 0xFFFFu;
-}
-
-// v_mul_u32_u24: both factors below 2^24
-__device__ __forceinline__ uint32_t dn_mul24(uint32_t a, uint32_t b)
-{
-    return static_cast<uint32_t>(__umul24(a, b));
-}
-
-// (num + (den >> 1)) / den, exactly.  n < 2^30 and den in 256 .. 6400; the quotient is at most 65536 (a weighted mean of
-// uint16 values plus the rounding half).  In float: n rounds with a relative error of 2^-24, den is exact, v_rcp_f32 is
-// good to 1 ulp (2^-23) and the product rounds once more: the estimate is off by less than 65536 * 2^-21 = 1 / 32, so its
-// integer part is the quotient or one beside it, and one step either way by the sign of the remainder makes it exact.
-__device__ __forceinline__ uint32_t dn_div(uint32_t n, uint32_t den)
-{
-    uint32_t q = static_cast<uint32_t>(static_cast<float>(n) * __builtin_amdgcn_rcpf(static_cast<float>(den)));
-    const int32_t r = static_cast<int32_t>(n - dn_mul24(q, den)); // q <= 65537, den < 2^13: exact
-    q = r < 0 ? q - 1u : q;
-    q = r >= static_cast<int32_t>(den) ? q + 1u : q;
-    return q;
-}
-
-template <bool NT>
-__device__ __forceinline__ void dn_store8(uint16_t *dst, uint32_t n, bool vec, const uint32_t p[4])
-{
-    if (n == 8u) {
-        if (vec) {
-            const mcraw_u32x4 v = {p[0], p[1], p[2], p[3]};
-            if (NT)
-                store_stream16(dst, v);
-            else
-                *gptr<mcraw_u32x4>(dst) = v;
-        } else { // rows off the 16-byte grid: one unaligned 16-byte store
-            typedef uint32_t u32x4_u __attribute__((ext_vector_type(4), aligned(2)));
-            const u32x4_u v = {p[0], p[1], p[2], p[3]};
-            *gptr<u32x4_u>(dst) = v;
-        }
-        return;
-    }
-#pragma unroll
-    for (uint32_t i = 0; i < 8u; i++) // the cropped end of a row: element stores
-        if (i < n)
-            gptr<uint16_t>(dst)[i] = static_cast<uint16_t>(p[i >> 1] >> (16u * (i & 1u)));
-}
-
 template <int RADIUS, bool NT>
 __global__ void __launch_bounds__(DN_T) kdenoise(const DnArgs A)
 {
@@ -148,6 +93,7 @@ __global__ void __launch_bounds__(DN_T) kdenoise(const DnArgs A)
         for (uint32_t i = threadIdx.x; i < A.L / 2u; i += DN_T) // 4 * L * 2 bytes in 16-byte chunks (L >= 64)
             *reinterpret_cast<mcraw_u32x4 *>(&dn_lut[8u * i]) = *gptr<const mcraw_u32x4>(lut + 8u * i);
     }
+    // (stage_tile of mcraw_mosaic.h, written out: as a call it measured slower in this kernel)
     for (uint32_t i = threadIdx.x; i < LH * DN_CH; i += DN_T) {
         const uint32_t r = i / DN_CH, q = i % DN_CH;
         const int yy = y0 - HALO + static_cast<int>(r), xs = x0 - 8 + 8 * static_cast<int>(q);
@@ -156,13 +102,7 @@ __global__ void __launch_bounds__(DN_T) kdenoise(const DnArgs A)
         const uint16_t *row = in + static_cast<size_t>(dn_halo(yy, H)) * A.ipitch;
         mcraw_u32x4 v;
         if (q != 0u && q != DN_CH - 1u && xs + 8 <= W) { // (xs >= 0 here) a full piece of the row
-            if (A.invec) {
-                v = *gptr<const mcraw_u32x4>(row + xs);
-            } else { // rows off the 16-byte grid: one unaligned 16-byte load
-                typedef uint32_t u32x4_u __attribute__((ext_vector_type(4), aligned(2)));
-                const u32x4_u t = *gptr<const u32x4_u>(row + xs);
-                v = mcraw_u32x4{t[0], t[1], t[2], t[3]};
-            }
+            v = load16(row + xs, A.invec != 0u);
         } else { // the halo columns (the last HALO of the first chunk, the first HALO of the last) and a cropped row end:
                  // element loads through the reflection
             const int e0 = q == 0u ? 8 - HALO : 0, e1 = q == DN_CH - 1u ? HALO : 8;
@@ -211,7 +151,7 @@ __global__ void __launch_bounds__(DN_T) kdenoise(const DnArgs A)
             c[k] = *reinterpret_cast<const uint32_t *>(lane + HALO + 2u * k);
 #pragma unroll
             for (uint32_t h = 0; h < 2u; h++)
-                rv[2u * k + h] = plane[h][min(dn_half(c[k], h) >> A.shift, lmax)];
+                rv[2u * k + h] = plane[h][min(half16(c[k], h) >> A.shift, lmax)];
         }
         uint32_t sq[8], sqa[8], sa[8];
 #pragma unroll
@@ -264,14 +204,14 @@ __global__ void __launch_bounds__(DN_T) kdenoise(const DnArgs A)
 #pragma unroll
                 for (uint32_t i = 0; i < NP; i++) {
                     const uint32_t a2 = (RADIUS == 2 && i == 0u) ? far[0][k] : (RADIUS == 2 && i == NP - 1u) ? far[1][k] : w[k + i];
-                    const uint32_t d2 = dn_pkabsdiff(a2, c[k]);
+                    const uint32_t d2 = pk_absdiff(a2, c[k]);
 #pragma unroll
                     for (uint32_t h = 0; h < 2u; h++) {
-                        const uint32_t p = 2u * k + h, a = dn_half(a2, h);
-                        const uint32_t t = dn_mul24(dn_half(d2, h), rv[p]) >> 8, xx = t < 16u ? t : 16u;
-                        const uint32_t q = dn_mul24(xx, xx);
+                        const uint32_t p = 2u * k + h, a = half16(a2, h);
+                        const uint32_t t = mul24(half16(d2, h), rv[p]) >> 8, xx = t < 16u ? t : 16u;
+                        const uint32_t q = mul24(xx, xx);
                         sq[p] += q;
-                        sqa[p] += dn_mul24(q, a);
+                        sqa[p] += mul24(q, a);
                         sa[p] += a;
                     }
                 }
@@ -286,20 +226,14 @@ __global__ void __launch_bounds__(DN_T) kdenoise(const DnArgs A)
                 const uint32_t p = 2u * k + h;
                 // sum(w) = 256 * NP * NP - sum(q), sum(w * a) = 256 * sum(a) - sum(q * a), the centre (q = 0) among them
                 const uint32_t den = 256u * NP * NP - sq[p], num = 256u * sa[p] - sqa[p];
-                const int32_t cv = static_cast<int32_t>(dn_half(c[k], h));
-                const int32_t m = static_cast<int32_t>(dn_div(num + (den >> 1), den));
+                const int32_t cv = static_cast<int32_t>(half16(c[k], h));
+                const int32_t m = static_cast<int32_t>(div_round(num + (den >> 1), den));
                 res[h] = static_cast<uint32_t>(cv + (((m - cv) * static_cast<int32_t>(A.amount) + 128) >> 8));
             }
             o[k] = res[0] | (res[1] << 16);
         }
-        dn_store8<NT>(fout + static_cast<size_t>(y) * A.opitch, n, A.outvec != 0u, o);
+        store8<NT>(fout + static_cast<size_t>(y) * A.opitch, n, A.outvec != 0u, o);
     }
-}
-
-static int denoise_reject(const char *why)
-{
-    g_err = std::string("mcraw_denoise_batch: ") + why;
-    return -1;
 }
 
 template <int RADIUS>
@@ -317,44 +251,35 @@ extern "C" int mcraw_denoise_batch(mcraw_ctx *c, const mcraw_denoise *d, const u
                                    void *stream)
 {
     if (!c || !d || n < 0)
-        return denoise_reject("bad arguments");
+        return reject(__func__, "bad arguments");
     if (n == 0)
         return 0;
     if (!in || !out)
-        return denoise_reject("in or out missing");
-    if ((reinterpret_cast<uintptr_t>(in) & 1u) || (reinterpret_cast<uintptr_t>(out) & 1u))
-        return denoise_reject("in / out not aligned to uint16");
-    if (width < 1 || height < 1 || width > 65536 || height > 65536)
-        return denoise_reject("width and height must be 1 .. 65536");
-    const size_t W = static_cast<size_t>(width), H = static_cast<size_t>(height);
-    if (in_pitch < W || out_pitch < W)
-        return denoise_reject("pitch below width");
-    if (n > 1 && (in_frame_stride < (H - 1u) * in_pitch + W || out_frame_stride < (H - 1u) * out_pitch + W))
-        return denoise_reject("frame stride too small for the frames not to overlap");
+        return reject(__func__, "in or out missing");
+    const MosaicBatch I(in, in_pitch, in_frame_stride, static_cast<size_t>(n), width, height);
+    const MosaicBatch O(out, out_pitch, out_frame_stride, static_cast<size_t>(n), width, height);
+    if (const char *why = check(I, O))
+        return reject(__func__, why);
     if (d->radius != 1u && d->radius != 2u)
-        return denoise_reject("radius must be 1 or 2");
+        return reject(__func__, "radius must be 1 or 2");
     if (d->amount < 1u || d->amount > 256u)
-        return denoise_reject("amount must be 1 .. 256");
+        return reject(__func__, "amount must be 1 .. 256");
     if (d->lut_log2 < 6u || d->lut_log2 > 10u)
-        return denoise_reject("lut_log2 must be 6 .. 10");
+        return reject(__func__, "lut_log2 must be 6 .. 10");
     if (d->shift > 15u)
-        return denoise_reject("shift must be 0 .. 15");
+        return reject(__func__, "shift must be 0 .. 15");
     if (d->nluts != 1u && d->nluts != static_cast<uint32_t>(n))
-        return denoise_reject("nluts must be 1 or n");
+        return reject(__func__, "nluts must be 1 or n");
     if (d->reserved[0] != 0u || d->reserved[1] != 0u || d->reserved[2] != 0u)
-        return denoise_reject("reserved must be 0");
+        return reject(__func__, "reserved must be 0");
     if (!d->lut || (reinterpret_cast<uintptr_t>(d->lut) & 15u))
-        return denoise_reject("lut missing or not 16-byte aligned");
-    // elements from the first sample of the first frame to behind the last sample of the last one
-    const size_t in_ext = static_cast<size_t>(n - 1) * in_frame_stride + (H - 1u) * in_pitch + W;
-    const size_t out_ext = static_cast<size_t>(n - 1) * out_frame_stride + (H - 1u) * out_pitch + W;
-    const uintptr_t ia = reinterpret_cast<uintptr_t>(in), oa = reinterpret_cast<uintptr_t>(out);
-    if (ia < oa + 2u * out_ext && oa < ia + 2u * in_ext)
-        return denoise_reject("in and out overlap (every pixel reads its neighbours: there is no in-place form)");
+        return reject(__func__, "lut missing or not 16-byte aligned");
+    if (overlap(I, O))
+        return reject(__func__, "in and out overlap (every pixel reads its neighbours: there is no in-place form)");
 
     std::lock_guard<std::mutex> lk(c->mu);
     HIP_TRY(hipSetDevice(c->device));
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    hipStream_t st = stream_of(c, stream);
     DnArgs A{};
     A.ipitch = in_pitch;
     A.ifstride = in_frame_stride;
@@ -368,11 +293,10 @@ extern "C" int mcraw_denoise_batch(mcraw_ctx *c, const mcraw_denoise *d, const u
     A.L = 1u << d->lut_log2;
     A.shift = d->shift;
     A.perframe = d->nluts != 1u ? 1u : 0u;
-    A.invec = (ia & 15u) == 0u && in_pitch % 8u == 0u && (n == 1 || in_frame_stride % 8u == 0u);
-    A.outvec = (oa & 15u) == 0u && out_pitch % 8u == 0u && (n == 1 || out_frame_stride % 8u == 0u);
-    constexpr int piece = 65535; // frames per launch (grid.y)
-    for (int f0 = 0; f0 < n; f0 += piece) {
-        const int nf = std::min(piece, n - f0);
+    A.invec = I.on_grid();
+    A.outvec = O.on_grid();
+    for (int f0 = 0; f0 < n; f0 += LAUNCH_FRAMES) {
+        const int nf = std::min(LAUNCH_FRAMES, n - f0);
         A.in = in + static_cast<size_t>(f0) * in_frame_stride;
         A.out = out + static_cast<size_t>(f0) * out_frame_stride;
         A.lut = d->lut + (A.perframe ? static_cast<size_t>(f0) * 4u * A.L : 0u);

@@ -12,14 +12,14 @@
 // behind that predicate, and a wave without such a pixel skips them.  The counts stay in registers; a wave reduces them
 // with shuffles and one lane adds them to the frame's record.  kfixpix_list, queued behind it, replaces the listed pixels:
 // one thread per (entry, frame), eight searches, one element written.
-#include "mcraw_dev.h"
 #include "mcraw_host.h"
+#include "mcraw_mosaic.h"
 
 namespace mcraw {
 
-constexpr int FP_T = 256;        // threads per workgroup
+constexpr int FP_T = TILE_T;     // threads per workgroup
 constexpr uint32_t FP_LX = 32u;  // lanes across a tile: 8 columns each
-constexpr uint32_t FP_TW = 8u * FP_LX;
+constexpr uint32_t FP_TW = TILE_W;
 // Tile rows: 32 re-reads 36/32 of the rows (19.1 KB of LDS, 8 workgroups per CU), 16 re-reads 20/16 (10.6 KB).
 // -DMCRAW_FIXPIX_TH=16 builds the other one; tools/bench_fixpix.py --alt-lib runs two builds side by side.
 #ifndef MCRAW_FIXPIX_TH
@@ -27,9 +27,8 @@ constexpr uint32_t FP_TW = 8u * FP_LX;
 #endif
 constexpr uint32_t FP_TH = MCRAW_FIXPIX_TH;
 static_assert(FP_TH == 16u || FP_TH == 32u, "a pass is 16 rows: 8 lane rows x 2 rows");
-constexpr uint32_t FP_LW = FP_TW + 16u; // LDS row: 8 columns either side (2 used), so that chunks stay on the 8-grid
+constexpr uint32_t FP_LW = TILE_LW;     // LDS row: 8 columns either side (2 used), so that chunks stay on the 8-grid
 constexpr uint32_t FP_LH = FP_TH + 4u;  // 2 halo rows above and below
-constexpr uint32_t FP_CH = FP_LW / 8u;  // 16-byte chunks per LDS row
 constexpr uint32_t FP_MAXLIST = 1u << 20;
 
 // Which stores the full aligned pieces of the output rows use: `sc1 nt` streaming stores (store_stream16), as kshade and the
@@ -85,67 +84,25 @@ __device__ __forceinline__ bool fix_member(const uint32_t *list, uint32_t nlist,
     return lo < nlist && gptr<const uint32_t>(list)[lo] == key;
 }
 
-// Two uint16 per dword, both halves at once (v_pk_max_u16, v_pk_min_u16, v_pk_sub_u16, v_pk_mul_lo_u16).
-typedef unsigned short fix_u16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t fix_pkmin(uint32_t a, uint32_t b)
-{
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(fix_u16x2, a), __builtin_bit_cast(fix_u16x2, b)));
-}
-__device__ __forceinline__ uint32_t fix_pkmax(uint32_t a, uint32_t b)
-{
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(fix_u16x2, a), __builtin_bit_cast(fix_u16x2, b)));
-}
-__device__ __forceinline__ uint32_t fix_pksub(uint32_t a, uint32_t b)
-{
-    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(fix_u16x2, a) - __builtin_bit_cast(fix_u16x2, b));
-}
-// 0xFFFF in every half that is not 0
+// 0xFFFF in every half that is not 0 (v_pk_mul_lo_u16)
 __device__ __forceinline__ uint32_t fix_pknz(uint32_t a)
 {
-    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(fix_u16x2, fix_pkmin(a, 0x00010001u)) * __builtin_bit_cast(fix_u16x2, 0xFFFFFFFFu));
+    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2, pk_min(a, 0x00010001u)) * __builtin_bit_cast(u16x2, 0xFFFFFFFFu));
 }
 
 // One opposite pair for both halves: where |a - b| is strictly below `best`, `val` takes (a + b + 1) >> 1
 // (= (a | b) - ((a ^ b) >> 1), which needs no 17th bit).
 __device__ __forceinline__ void fix_pair(uint32_t a, uint32_t b, bool first, uint32_t &best, uint32_t &val)
 {
-    const uint32_t d = fix_pksub(fix_pkmax(a, b), fix_pkmin(a, b));
-    const uint32_t avg = fix_pksub(a | b, ((a ^ b) >> 1) & 0x7FFF7FFFu);
+    const uint32_t d = pk_absdiff(a, b);
+    const uint32_t avg = pk_sub(a | b, ((a ^ b) >> 1) & 0x7FFF7FFFu);
     if (first) {
         best = d, val = avg;
         return;
     }
-    const uint32_t m = fix_pkmin(best, d), lt = fix_pknz(m ^ best);
+    const uint32_t m = pk_min(best, d), lt = fix_pknz(m ^ best);
     val = (avg & lt) | (val & ~lt);
     best = m;
-}
-
-__device__ __forceinline__ uint32_t fix_half(uint32_t w, uint32_t h)
-{
-    return h ? w >> 16 : w & 0xFFFFu;
-}
-
-template <bool NT>
-__device__ __forceinline__ void fix_store8(uint16_t *dst, uint32_t n, bool vec, const uint32_t p[4])
-{
-    if (n == 8u) {
-        if (vec) {
-            const mcraw_u32x4 v = {p[0], p[1], p[2], p[3]};
-            if (NT)
-                store_stream16(dst, v);
-            else
-                *gptr<mcraw_u32x4>(dst) = v;
-        } else { // rows off the 16-byte grid: one unaligned 16-byte store
-            typedef uint32_t u32x4_u __attribute__((ext_vector_type(4), aligned(2)));
-            const u32x4_u v = {p[0], p[1], p[2], p[3]};
-            *gptr<u32x4_u>(dst) = v;
-        }
-        return;
-    }
-#pragma unroll
-    for (uint32_t i = 0; i < 8u; i++) // the cropped end of a row: element stores
-        if (i < n)
-            gptr<uint16_t>(dst)[i] = static_cast<uint16_t>(p[i >> 1] >> (16u * (i & 1u)));
 }
 
 template <bool NT>
@@ -157,32 +114,7 @@ __global__ void __launch_bounds__(FP_T) kfixpix(const FixArgs A)
     const int W = static_cast<int>(A.W), H = static_cast<int>(A.H);
     const int x0 = static_cast<int>(tx * FP_TW), y0 = static_cast<int>(ty * FP_TH);
     const uint16_t *in = A.in + static_cast<size_t>(f) * A.ifstride;
-    for (uint32_t i = threadIdx.x; i < FP_LH * FP_CH; i += FP_T) {
-        const uint32_t r = i / FP_CH, q = i % FP_CH;
-        const int yy = y0 - 2 + static_cast<int>(r), xs = x0 - 8 + 8 * static_cast<int>(q);
-        if (yy >= H + 2 || xs >= W + 2) // no output of the frame reads it
-            continue;
-        const uint16_t *row = in + static_cast<size_t>(fix_halo(yy, H)) * A.ipitch;
-        mcraw_u32x4 v;
-        if (q != 0u && q != FP_CH - 1u && xs + 8 <= W) { // (xs >= 0 here) a full piece of the row
-            if (A.invec) {
-                v = *gptr<const mcraw_u32x4>(row + xs);
-            } else { // rows off the 16-byte grid: one unaligned 16-byte load
-                typedef uint32_t u32x4_u __attribute__((ext_vector_type(4), aligned(2)));
-                const u32x4_u t = *gptr<const u32x4_u>(row + xs);
-                v = mcraw_u32x4{t[0], t[1], t[2], t[3]};
-            }
-        } else { // the halo columns (the last two of the first chunk, the first two of the last) and a cropped row end:
-                 // element loads through the reflection
-            const int e0 = q == 0u ? 6 : 0, e1 = q == FP_CH - 1u ? 2 : 8;
-            uint32_t u[8];
-#pragma unroll
-            for (int e = 0; e < 8; e++)
-                u[e] = (e >= e0 && e < e1 && xs + e < W + 2) ? gptr<const uint16_t>(row)[fix_halo(xs + e, W)] : 0u;
-            v = mcraw_u32x4{u[0] | (u[1] << 16), u[2] | (u[3] << 16), u[4] | (u[5] << 16), u[6] | (u[7] << 16)};
-        }
-        *reinterpret_cast<mcraw_u32x4 *>(&s_t[r * FP_LW + 8u * q]) = v;
-    }
+    stage_tile<FP_TH, 2, fix_halo>(s_t, in, A.ipitch, W, H, x0, y0, A.invec != 0u);
     __syncthreads();
     const uint32_t lx = threadIdx.x % FP_LX, ly = threadIdx.x / FP_LX;
     const uint32_t x = static_cast<uint32_t>(x0) + 8u * lx;
@@ -223,11 +155,11 @@ __global__ void __launch_bounds__(FP_T) kfixpix(const FixArgs A)
                 uint32_t h1 = nb[0], h2 = 0u, l1 = nb[0], l2 = 0xFFFFFFFFu;
 #pragma unroll
                 for (uint32_t j = 1; j < 8u; j++) {
-                    const uint32_t th = fix_pkmin(h1, nb[j]), tl = fix_pkmax(l1, nb[j]);
-                    h1 = fix_pkmax(h1, nb[j]);
-                    h2 = fix_pkmax(h2, th);
-                    l1 = fix_pkmin(l1, nb[j]);
-                    l2 = fix_pkmin(l2, tl);
+                    const uint32_t th = pk_min(h1, nb[j]), tl = pk_max(l1, nb[j]);
+                    h1 = pk_max(h1, nb[j]);
+                    h2 = pk_max(h2, th);
+                    l1 = pk_min(l1, nb[j]);
+                    l2 = pk_min(l2, tl);
                 }
                 Hk[k] = A.rank == 2u ? h2 : h1;
                 Lk[k] = A.rank == 2u ? l2 : l1;
@@ -237,7 +169,7 @@ __global__ void __launch_bounds__(FP_T) kfixpix(const FixArgs A)
                 // (Behind a cropped row end, 2k >= n, the LDS chunks were never staged and v, Hk, Lk are whatever LDS held:
                 // such a dword can only send the lane into the slow path below for nothing, where every test, count and
                 // store is guarded by the column's place against n.)
-                cand = cand || (fix_pksub(v, fix_pkmin(v, Hk[k])) | fix_pksub(fix_pkmax(v, Lk[k]), v)) != 0u;
+                cand = cand || (pk_sub(v, pk_min(v, Hk[k])) | pk_sub(pk_max(v, Lk[k]), v)) != 0u;
             }
             if (__any(cand)) {
                 if (cand) {
@@ -249,7 +181,7 @@ __global__ void __launch_bounds__(FP_T) kfixpix(const FixArgs A)
                         for (uint32_t h = 0; h < 2u; h++) {
                             if (2u * k + h >= n)
                                 continue;
-                            const uint32_t pv = fix_half(v, h), ph = fix_half(Hk[k], h), pl = fix_half(Lk[k], h);
+                            const uint32_t pv = half16(v, h), ph = half16(Hk[k], h), pl = half16(Lk[k], h);
                             // (every intermediate is below 2^32: at most 65535 * 65535, then 65535 + 2^24)
                             const bool hot = A.hot && pv > ph && pv - ph > abt[h] + (((ph > blk[h] ? ph - blk[h] : 0u) * A.rel) >> 8);
                             const bool cold = A.cold && pv < pl && pl - pv > abt[h] + (((pl > blk[h] ? pl - blk[h] : 0u) * A.rel) >> 8);
@@ -273,7 +205,7 @@ __global__ void __launch_bounds__(FP_T) kfixpix(const FixArgs A)
                     }
                 }
             }
-            fix_store8<NT>(fout + static_cast<size_t>(y) * A.opitch, n, A.outvec != 0u, o);
+            store8<NT>(fout + static_cast<size_t>(y) * A.opitch, n, A.outvec != 0u, o);
         }
     }
     if (!A.counts)
@@ -344,12 +276,6 @@ __global__ void __launch_bounds__(256) kfixpix_list(const FixArgs A)
             static_cast<uint16_t>(val);
 }
 
-static int fixpix_reject(const char *why)
-{
-    g_err = std::string("mcraw_fixpix_batch: ") + why;
-    return -1;
-}
-
 } // namespace mcraw
 
 using namespace mcraw;
@@ -359,49 +285,40 @@ extern "C" int mcraw_fixpix_batch(mcraw_ctx *c, const mcraw_fixpix *p, const uin
                                   void *stream)
 {
     if (!c || !p || n < 0)
-        return fixpix_reject("bad arguments");
+        return reject(__func__, "bad arguments");
     if (n == 0)
         return 0;
     if (!in || !out)
-        return fixpix_reject("in or out missing");
-    if ((reinterpret_cast<uintptr_t>(in) & 1u) || (reinterpret_cast<uintptr_t>(out) & 1u))
-        return fixpix_reject("in / out not aligned to uint16");
-    if (width < 1 || height < 1 || width > 65536 || height > 65536)
-        return fixpix_reject("width and height must be 1 .. 65536");
-    const size_t W = static_cast<size_t>(width), H = static_cast<size_t>(height);
-    if (in_pitch < W || out_pitch < W)
-        return fixpix_reject("pitch below width");
-    if (n > 1 && (in_frame_stride < (H - 1u) * in_pitch + W || out_frame_stride < (H - 1u) * out_pitch + W))
-        return fixpix_reject("frame stride too small for the frames not to overlap");
+        return reject(__func__, "in or out missing");
+    const MosaicBatch I(in, in_pitch, in_frame_stride, static_cast<size_t>(n), width, height);
+    const MosaicBatch O(out, out_pitch, out_frame_stride, static_cast<size_t>(n), width, height);
+    if (const char *why = check(I, O))
+        return reject(__func__, why);
     if (p->rank != 1u && p->rank != 2u)
-        return fixpix_reject("rank must be 1 or 2");
+        return reject(__func__, "rank must be 1 or 2");
     if (p->rel_thr > 65535u)
-        return fixpix_reject("rel_thr must be 0 .. 65535 (Q8)");
+        return reject(__func__, "rel_thr must be 0 .. 65535 (Q8)");
     if (p->flags & ~(MCRAW_FIXPIX_HOT | MCRAW_FIXPIX_COLD))
-        return fixpix_reject("unknown flag");
+        return reject(__func__, "unknown flag");
     if (p->nlist > FP_MAXLIST)
-        return fixpix_reject("nlist above 1 << 20");
+        return reject(__func__, "nlist above 1 << 20");
     if (p->nlist > 0u && (!p->list || (reinterpret_cast<uintptr_t>(p->list) & 3u)))
-        return fixpix_reject("list missing or not 4-byte aligned");
+        return reject(__func__, "list missing or not 4-byte aligned");
     if (reinterpret_cast<uintptr_t>(p->counts) & 3u)
-        return fixpix_reject("counts not 4-byte aligned");
+        return reject(__func__, "counts not 4-byte aligned");
     if (p->reserved[0] != 0u || p->reserved[1] != 0u)
-        return fixpix_reject("reserved must be 0");
-    // elements from the first sample of the first frame to behind the last sample of the last one
-    const size_t in_ext = static_cast<size_t>(n - 1) * in_frame_stride + (H - 1u) * in_pitch + W;
-    const size_t out_ext = static_cast<size_t>(n - 1) * out_frame_stride + (H - 1u) * out_pitch + W;
-    const uintptr_t ia = reinterpret_cast<uintptr_t>(in), oa = reinterpret_cast<uintptr_t>(out);
-    if (ia < oa + 2u * out_ext && oa < ia + 2u * in_ext)
-        return fixpix_reject("in and out overlap (every pixel reads its neighbours: there is no in-place form)");
+        return reject(__func__, "reserved must be 0");
+    if (overlap(I, O))
+        return reject(__func__, "in and out overlap (every pixel reads its neighbours: there is no in-place form)");
     if (p->counts) {
         const uintptr_t ca = reinterpret_cast<uintptr_t>(p->counts), cb = static_cast<size_t>(n) * 32u;
-        if ((ca < ia + 2u * in_ext && ia < ca + cb) || (ca < oa + 2u * out_ext && oa < ca + cb))
-            return fixpix_reject("counts overlaps the input or the output");
+        if (ranges_overlap(ca, cb, I.base, I.bytes()) || ranges_overlap(ca, cb, O.base, O.bytes()))
+            return reject(__func__, "counts overlaps the input or the output");
     }
 
     std::lock_guard<std::mutex> lk(c->mu);
     HIP_TRY(hipSetDevice(c->device));
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    hipStream_t st = stream_of(c, stream);
     FixArgs A{};
     A.list = p->nlist ? p->list : nullptr;
     A.nlist = p->nlist;
@@ -421,17 +338,16 @@ extern "C" int mcraw_fixpix_batch(mcraw_ctx *c, const mcraw_fixpix *p, const uin
         A.black[i] = p->black[i];
         A.abs_thr[i] = p->abs_thr[i];
     }
-    A.invec = (ia & 15u) == 0u && in_pitch % 8u == 0u && (n == 1 || in_frame_stride % 8u == 0u);
-    A.outvec = (oa & 15u) == 0u && out_pitch % 8u == 0u && (n == 1 || out_frame_stride % 8u == 0u);
+    A.invec = I.on_grid();
+    A.outvec = O.on_grid();
     if (p->counts) {
         const size_t words = static_cast<size_t>(n) * 8u;
         const uint32_t blocks = static_cast<uint32_t>(std::min<size_t>((words + 255u) / 256u, 4096u));
         hipLaunchKernelGGL(kfixpix_init, dim3(blocks), dim3(256), 0, st, p->counts, words);
         HIP_TRY(hipGetLastError());
     }
-    constexpr int piece = 65535; // frames per launch (grid.y)
-    for (int f0 = 0; f0 < n; f0 += piece) {
-        const int nf = std::min(piece, n - f0);
+    for (int f0 = 0; f0 < n; f0 += LAUNCH_FRAMES) {
+        const int nf = std::min(LAUNCH_FRAMES, n - f0);
         A.in = in + static_cast<size_t>(f0) * in_frame_stride;
         A.out = out + static_cast<size_t>(f0) * out_frame_stride;
         A.counts = p->counts ? p->counts + static_cast<size_t>(f0) * 8u : nullptr;

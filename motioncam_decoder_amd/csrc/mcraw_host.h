@@ -11,6 +11,12 @@
 //   mcraw_fixpix.hip   mcraw_fixpix_batch: likewise
 //   mcraw_denoise.hip  mcraw_denoise_batch: likewise
 //   mcraw_merge.hip    mcraw_merge_batch: likewise
+//   mcraw_mosaic.h       device helpers of those five mosaic stages: 8-sample loads and stores, packed-u16 and 24-bit arithmetic,
+//                        the exact rounding divide, the tile-plus-halo staging of the stencil stages
+//   mcraw_mosaic_args.h  one strided batch of mosaics and the checks on it (free of HIP): pointer, size, pitch, frame stride, the
+//                        extent, the 16-byte grid, the overlap of two batches
+// A new mosaic stage describes `in` and `out` as MosaicBatch, rejects with reject(__func__, why), takes its stream from
+// stream_of() and its loads, stores and staging from mcraw_mosaic.h; only its own struct's checks and its kernel are its own.
 // Replaces the per-frame dispatch of lib/Decoder.cpp:216-234 with batched submits.  There is no CPU decode fallback in any of them.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -28,6 +34,7 @@
 #include <vector>
 
 #include "../../include/mcraw_hip.h"
+#include "mcraw_mosaic_args.h"
 #include "mcraw_plan.h"
 #include "mcraw_race.h"
 
@@ -52,6 +59,13 @@ inline int fail(hipError_t e, const char *what)
 {
     g_err = std::string(what) + ": " + hipGetErrorString(e);
     return -static_cast<int>(e ? e : hipErrorUnknown);
+}
+
+// An entry point that turns its arguments down: "<fn>: <why>" for mcraw_last_error, and -1.
+inline int reject(const char *fn, const char *why)
+{
+    g_err = std::string(fn) + ": " + why;
+    return -1;
 }
 
 #define HIP_TRY(expr)                                                                                                  \
@@ -252,6 +266,9 @@ struct mcraw_ctx {
 
 namespace mcraw {
 
+// The stream a stage's launches go to: the caller's, or the context's own.
+inline hipStream_t stream_of(const mcraw_ctx *c, void *stream) { return stream ? static_cast<hipStream_t>(stream) : c->stream; }
+constexpr int LAUNCH_FRAMES = 65535; // frames per launch of a stage (grid.y)
 
 int ensure(Buf &b, size_t bytes, bool pinned);
 hipEvent_t get_event(mcraw_ctx *c);

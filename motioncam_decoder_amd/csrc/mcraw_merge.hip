@@ -13,8 +13,8 @@
 // product of a row count and a column count because the region is a rectangle.  num and den stay in registers over the
 // members.  Workgroups are numbered so that consecutive base frames of one tile run next to each other on one XCD: a member
 // is fetched from HBM once and found in that XCD's L2 by the other bases that hold it in their windows.
-#include "mcraw_dev.h"
 #include "mcraw_host.h"
+#include "mcraw_mosaic.h"
 
 namespace mcraw {
 
@@ -53,53 +53,6 @@ struct MgArgs {
     uint32_t invec, outvec; // every 8-column piece of `in` / `out` lies on the 16-byte grid
 };
 
-__device__ __forceinline__ uint32_t mg_half(uint32_t w, uint32_t h)
-{
-    return h ? w >> 16 : w & 0xFFFFu;
-}
-
-// v_mul_u32_u24: both factors below 2^24
-__device__ __forceinline__ uint32_t mg_mul24(uint32_t a, uint32_t b)
-{
-    return static_cast<uint32_t>(__umul24(a, b));
-}
-
-// (num + (den >> 1)) / den, exactly.  n < 2^29 and den in 256 .. 4096; the quotient is at most 65536.  In float: n rounds
-// with a relative error of 2^-24, den is exact, v_rcp_f32 is good to 1 ulp (2^-23) and the product rounds once more: the
-// estimate is off by less than 65536 * 2^-21 = 1 / 32, so its integer part is the quotient or one beside it, and one step
-// either way by the sign of the remainder makes it exact (DESIGN.md 19's argument; the ranges here are narrower).
-__device__ __forceinline__ uint32_t mg_div(uint32_t n, uint32_t den)
-{
-    uint32_t q = static_cast<uint32_t>(static_cast<float>(n) * __builtin_amdgcn_rcpf(static_cast<float>(den)));
-    const int32_t r = static_cast<int32_t>(n - mg_mul24(q, den)); // q <= 65537, den <= 2^12: exact
-    q = r < 0 ? q - 1u : q;
-    q = r >= static_cast<int32_t>(den) ? q + 1u : q;
-    return q;
-}
-
-template <bool NT>
-__device__ __forceinline__ void mg_store8(uint16_t *dst, uint32_t n, bool vec, const uint32_t p[4])
-{
-    if (n == 8u) {
-        if (vec) {
-            const mcraw_u32x4 v = {p[0], p[1], p[2], p[3]};
-            if (NT)
-                store_stream16(dst, v);
-            else
-                *gptr<mcraw_u32x4>(dst) = v;
-        } else { // rows off the 16-byte grid: one unaligned 16-byte store
-            typedef uint32_t u32x4_u __attribute__((ext_vector_type(4), aligned(2)));
-            const u32x4_u v = {p[0], p[1], p[2], p[3]};
-            *gptr<u32x4_u>(dst) = v;
-        }
-        return;
-    }
-#pragma unroll
-    for (uint32_t i = 0; i < 8u; i++) // the cropped end of a row: element stores
-        if (i < n)
-            gptr<uint16_t>(dst)[i] = static_cast<uint16_t>(p[i >> 1] >> (16u * (i & 1u)));
-}
-
 // Stage rows y0 - 1 .. y0 + MG_TH, columns x0 - 8 .. x0 + MG_TW + 7 of `frm` moved by (sy, sx) into s: LDS column k of LDS row
 // r holds frm[y0 - 1 + r + sy][x0 - 8 + k + sx], or 0 where that lies outside the frame.  Of the first and the last chunk only
 // the column next to the tile is read by anyone.  aligned: the pieces lie on the 16-byte grid (invec and sx % 8 == 0).
@@ -113,13 +66,7 @@ __device__ __forceinline__ void mg_stage(uint16_t *s, const uint16_t *frm, size_
         if (yy >= 0 && yy < H && xs + 8 > 0 && xs < W) {
             const uint16_t *row = frm + static_cast<size_t>(yy) * pitch;
             if (q != 0u && q != MG_CH - 1u && xs >= 0 && xs + 8 <= W) { // a full piece of the row
-                if (aligned) {
-                    v = *gptr<const mcraw_u32x4>(row + xs);
-                } else { // off the 16-byte grid (the base address, the pitch, or a shift that is no multiple of 8)
-                    typedef uint32_t u32x4_u __attribute__((ext_vector_type(4), aligned(2)));
-                    const u32x4_u t = *gptr<const u32x4_u>(row + xs);
-                    v = mcraw_u32x4{t[0], t[1], t[2], t[3]};
-                }
+                v = load16(row + xs, aligned); // (not aligned: the base address, the pitch, or a shift that is no multiple of 8)
             } else { // the halo columns and the pieces that the frame's edge cuts: element loads
                 const int e0 = q == 0u ? 7 : 0, e1 = q == MG_CH - 1u ? 1 : 8;
                 uint32_t u[8];
@@ -181,7 +128,7 @@ __global__ void __launch_bounds__(MG_T) kmerge(const MgArgs A)
             uint32_t t[2];
 #pragma unroll
             for (uint32_t h = 0; h < 2u; h++) {
-                const uint32_t cv = mg_half(c[o][k], h);
+                const uint32_t cv = half16(c[o][k], h);
                 t[h] = mg_lut[(2u * yp + h) * A.L + min(cv >> A.shift, lmax)];
                 num[o][2u * k + h] = cv << 8;
                 den[o][2u * k + h] = 256u;
@@ -227,11 +174,11 @@ __global__ void __launch_bounds__(MG_T) kmerge(const MgArgs A)
                 mg_row(lm + (o + 1u) * MG_LW, w);
 #pragma unroll
                 for (uint32_t p = 0; p < 8u; p++) {
-                    const uint32_t a = mg_half(w[1u + (p >> 1)], p & 1u), cv = mg_half(c[o][p >> 1], p & 1u);
+                    const uint32_t a = half16(w[1u + (p >> 1)], p & 1u), cv = half16(c[o][p >> 1], p & 1u);
                     const uint32_t D = a > cv ? a - cv : cv - a;
-                    const uint32_t xr = mg_mul24(D, mg_half(rv[o][p >> 1], p & 1u)) >> 8, xx = xr < 16u ? xr : 16u;
-                    const uint32_t wt = (rowv && ((colv >> (p + 1u)) & 1u)) ? 256u - mg_mul24(xx, xx) : 0u;
-                    num[o][p] += mg_mul24(wt, a);
+                    const uint32_t xr = mul24(D, half16(rv[o][p >> 1], p & 1u)) >> 8, xx = xr < 16u ? xr : 16u;
+                    const uint32_t wt = (rowv && ((colv >> (p + 1u)) & 1u)) ? 256u - mul24(xx, xx) : 0u;
+                    num[o][p] += mul24(wt, a);
                     den[o][p] += wt;
                 }
             }
@@ -253,7 +200,7 @@ __global__ void __launch_bounds__(MG_T) kmerge(const MgArgs A)
                 int e[10];
 #pragma unroll
                 for (uint32_t k = 0; k < 10u; k++) { // column x - 1 + k: half (k + 1) & 1 of dword (k + 1) >> 1
-                    const int d = static_cast<int>(mg_half(wm[(k + 1u) >> 1], (k + 1u) & 1u)) - static_cast<int>(mg_half(wb[(k + 1u) >> 1], (k + 1u) & 1u));
+                    const int d = static_cast<int>(half16(wm[(k + 1u) >> 1], (k + 1u) & 1u)) - static_cast<int>(half16(wb[(k + 1u) >> 1], (k + 1u) & 1u));
                     e[k] = (rowv && ((colv >> k) & 1u)) ? d : 0;
                 }
 #pragma unroll
@@ -276,10 +223,10 @@ __global__ void __launch_bounds__(MG_T) kmerge(const MgArgs A)
                     const int s = hs[0][p] + hs[1][p] + hs[2][p] + (9 - cnty[o] * static_cast<int>(nvx[p])) * e0;
                     const uint32_t as = static_cast<uint32_t>(s < 0 ? -s : s) >> 3, ae = static_cast<uint32_t>(e0 < 0 ? -e0 : e0) >> 1;
                     const uint32_t D = max(min(as, 65535u), ae);
-                    const uint32_t a = mg_half(am[(i - 1u) & 1u][p >> 1], p & 1u);
-                    const uint32_t xr = mg_mul24(D, mg_half(rv[o][p >> 1], p & 1u)) >> 8, xx = xr < 16u ? xr : 16u;
-                    const uint32_t wt = (cenv && ((colv >> (p + 1u)) & 1u)) ? 256u - mg_mul24(xx, xx) : 0u;
-                    num[o][p] += mg_mul24(wt, a);
+                    const uint32_t a = half16(am[(i - 1u) & 1u][p >> 1], p & 1u);
+                    const uint32_t xr = mul24(D, half16(rv[o][p >> 1], p & 1u)) >> 8, xx = xr < 16u ? xr : 16u;
+                    const uint32_t wt = (cenv && ((colv >> (p + 1u)) & 1u)) ? 256u - mul24(xx, xx) : 0u;
+                    num[o][p] += mul24(wt, a);
                     den[o][p] += wt;
                 }
             }
@@ -301,20 +248,14 @@ __global__ void __launch_bounds__(MG_T) kmerge(const MgArgs A)
 #pragma unroll
             for (uint32_t h = 0; h < 2u; h++) {
                 const uint32_t p = 2u * k + h;
-                const int32_t cv = static_cast<int32_t>(mg_half(c[o][k], h));
-                const int32_t m = static_cast<int32_t>(mg_div(num[o][p] + (den[o][p] >> 1), den[o][p]));
+                const int32_t cv = static_cast<int32_t>(half16(c[o][k], h));
+                const int32_t m = static_cast<int32_t>(div_round(num[o][p] + (den[o][p] >> 1), den[o][p]));
                 v[h] = static_cast<uint32_t>(cv + (((m - cv) * static_cast<int32_t>(A.amount) + 128) >> 8));
             }
             res[k] = v[0] | (v[1] << 16);
         }
-        mg_store8<NT>(fout + static_cast<size_t>(y) * A.opitch, n, A.outvec != 0u, res);
+        store8<NT>(fout + static_cast<size_t>(y) * A.opitch, n, A.outvec != 0u, res);
     }
-}
-
-static int merge_reject(const char *why)
-{
-    g_err = std::string("mcraw_merge_batch: ") + why;
-    return -1;
 }
 
 static void merge_launch(const MgArgs &A, uint32_t support, hipStream_t st)
@@ -336,48 +277,41 @@ extern "C" int mcraw_merge_batch(mcraw_ctx *c, const mcraw_merge *m, const uint1
                                  void *stream)
 {
     if (!c || !m || n < 0)
-        return merge_reject("bad arguments");
+        return reject(__func__, "bad arguments");
     if (n == 0 || m->count == 0u)
         return 0;
     if (!in || !out)
-        return merge_reject("in or out missing");
+        return reject(__func__, "in or out missing");
     if ((reinterpret_cast<uintptr_t>(in) & 1u) || (reinterpret_cast<uintptr_t>(out) & 1u) || (reinterpret_cast<uintptr_t>(m->pos) & 1u))
-        return merge_reject("in / out / pos not aligned to 2 bytes");
-    if (width < 1 || height < 1 || width > 65536 || height > 65536)
-        return merge_reject("width and height must be 1 .. 65536");
-    const size_t W = static_cast<size_t>(width), H = static_cast<size_t>(height);
-    if (in_pitch < W || out_pitch < W)
-        return merge_reject("pitch below width");
-    if ((n > 1 && in_frame_stride < (H - 1u) * in_pitch + W) || (m->count > 1u && out_frame_stride < (H - 1u) * out_pitch + W))
-        return merge_reject("frame stride too small for the frames not to overlap");
+        return reject(__func__, "in / out / pos not aligned to 2 bytes");
+    const MosaicBatch I(in, in_pitch, in_frame_stride, static_cast<size_t>(n), width, height);
+    const MosaicBatch O(out, out_pitch, out_frame_stride, static_cast<size_t>(m->count), width, height);
+    if (const char *why = check(I, O))
+        return reject(__func__, why);
     if (m->before > 15u || m->after > 15u || m->before + m->after > 15u)
-        return merge_reject("before + after must be 0 .. 15");
+        return reject(__func__, "before + after must be 0 .. 15");
     if (m->first > static_cast<uint32_t>(n) || m->count > static_cast<uint32_t>(n) - m->first)
-        return merge_reject("first + count must not exceed n");
+        return reject(__func__, "first + count must not exceed n");
     if (m->support > 1u)
-        return merge_reject("support must be 0 or 1");
+        return reject(__func__, "support must be 0 or 1");
     if (m->amount < 1u || m->amount > 256u)
-        return merge_reject("amount must be 1 .. 256");
+        return reject(__func__, "amount must be 1 .. 256");
     if (m->lut_log2 < 6u || m->lut_log2 > 10u)
-        return merge_reject("lut_log2 must be 6 .. 10");
+        return reject(__func__, "lut_log2 must be 6 .. 10");
     if (m->shift > 15u)
-        return merge_reject("shift must be 0 .. 15");
+        return reject(__func__, "shift must be 0 .. 15");
     if (m->nluts != 1u && m->nluts != static_cast<uint32_t>(n))
-        return merge_reject("nluts must be 1 or n");
+        return reject(__func__, "nluts must be 1 or n");
     if (m->reserved != 0u)
-        return merge_reject("reserved must be 0");
+        return reject(__func__, "reserved must be 0");
     if (!m->lut || (reinterpret_cast<uintptr_t>(m->lut) & 15u))
-        return merge_reject("lut missing or not 16-byte aligned");
-    // elements from the first sample of the first frame to behind the last sample of the last one
-    const size_t in_ext = static_cast<size_t>(n - 1) * in_frame_stride + (H - 1u) * in_pitch + W;
-    const size_t out_ext = static_cast<size_t>(m->count - 1u) * out_frame_stride + (H - 1u) * out_pitch + W;
-    const uintptr_t ia = reinterpret_cast<uintptr_t>(in), oa = reinterpret_cast<uintptr_t>(out);
-    if (ia < oa + 2u * out_ext && oa < ia + 2u * in_ext)
-        return merge_reject("in and out overlap (every output reads several frames: there is no in-place form)");
+        return reject(__func__, "lut missing or not 16-byte aligned");
+    if (overlap(I, O))
+        return reject(__func__, "in and out overlap (every output reads several frames: there is no in-place form)");
 
     std::lock_guard<std::mutex> lk(c->mu);
     HIP_TRY(hipSetDevice(c->device));
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    hipStream_t st = stream_of(c, stream);
     MgArgs A{};
     A.in = in;
     A.lut = m->lut;
@@ -397,8 +331,8 @@ extern "C" int mcraw_merge_batch(mcraw_ctx *c, const mcraw_merge *m, const uint1
     A.L = 1u << m->lut_log2;
     A.shift = m->shift;
     A.perframe = m->nluts != 1u ? 1u : 0u;
-    A.invec = (ia & 15u) == 0u && in_pitch % 8u == 0u && (n == 1 || in_frame_stride % 8u == 0u);
-    A.outvec = (oa & 15u) == 0u && out_pitch % 8u == 0u && (m->count == 1u || out_frame_stride % 8u == 0u);
+    A.invec = I.on_grid();
+    A.outvec = O.on_grid();
     const uint32_t piece = std::max(1u, std::min(65535u, 0x40000000u / A.tiles)); // outputs per launch: below 2^30 workgroups
     for (uint32_t j0 = 0; j0 < m->count; j0 += piece) {
         A.nout = std::min(piece, m->count - j0);

@@ -623,12 +623,6 @@ static RgbKernel pick_yuv_kernel(uint32_t algo, int s)
     return algo == MCRAW_RGB_MHC ? mhc[s] : bin2[s];
 }
 
-static int reject(const char *fn, const char *why)
-{
-    g_err = std::string(fn) + ": " + why;
-    return -1;
-}
-
 static bool finite_all(const float *v, int n)
 {
     for (int i = 0; i < n; i++)

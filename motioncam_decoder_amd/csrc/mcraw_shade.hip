@@ -7,8 +7,8 @@
 // every lane makes 8 consecutive columns of two rows (a 16-byte load and a 16-byte store each): per pixel one ds_read_b32 (both
 // horizontal neighbours), two 24-bit multiply-adds for G, the sample's multiply-add and the clamp.
 // Every pixel reads only itself, so out == in (in place) is fine.
-#include "mcraw_dev.h"
 #include "mcraw_host.h"
+#include "mcraw_mosaic.h"
 
 namespace mcraw {
 
@@ -44,51 +44,6 @@ struct ShadeArgs {
     uint32_t invec, outvec; // every 8-column piece of `in` / `out` lies on the 16-byte grid
 };
 
-// 8 samples of columns x .. x + 7 (the first n exist) as (even column | odd column << 16) dwords.
-__device__ __forceinline__ void shade_load8(const uint16_t *src, uint32_t n, bool vec, uint32_t p[4])
-{
-    if (n == 8u) {
-        if (vec) {
-            const mcraw_u32x4 v = *gptr<const mcraw_u32x4>(src);
-            p[0] = v[0], p[1] = v[1], p[2] = v[2], p[3] = v[3];
-        } else { // rows off the 16-byte grid: one unaligned 16-byte load
-            typedef uint32_t u32x4_u __attribute__((ext_vector_type(4), aligned(2)));
-            const u32x4_u v = *gptr<const u32x4_u>(src);
-            p[0] = v[0], p[1] = v[1], p[2] = v[2], p[3] = v[3];
-        }
-        return;
-    }
-#pragma unroll
-    for (uint32_t i = 0; i < 4u; i++) { // the cropped end of a row: element loads
-        const uint32_t lo = 2u * i < n ? gptr<const uint16_t>(src)[2u * i] : 0u;
-        const uint32_t hi = 2u * i + 1u < n ? gptr<const uint16_t>(src)[2u * i + 1u] : 0u;
-        p[i] = lo | (hi << 16);
-    }
-}
-
-template <bool NT>
-__device__ __forceinline__ void shade_store8(uint16_t *dst, uint32_t n, bool vec, const uint32_t p[4])
-{
-    if (n == 8u) {
-        if (vec) {
-            const mcraw_u32x4 v = {p[0], p[1], p[2], p[3]};
-            if (NT)
-                store_stream16(dst, v);
-            else
-                *gptr<mcraw_u32x4>(dst) = v;
-        } else {
-            typedef uint32_t u32x4_u __attribute__((ext_vector_type(4), aligned(2)));
-            const u32x4_u v = {p[0], p[1], p[2], p[3]};
-            *gptr<u32x4_u>(dst) = v;
-        }
-        return;
-    }
-#pragma unroll
-    for (uint32_t i = 0; i < 8u; i++)
-        if (i < n)
-            gptr<uint16_t>(dst)[i] = static_cast<uint16_t>(p[i >> 1] >> (16u * (i & 1u)));
-}
-
 template <bool NT>
 __global__ void __launch_bounds__(SH_T) kshade(const ShadeArgs A)
 {
@@ -110,7 +65,7 @@ __global__ void __launch_bounds__(SH_T) kshade(const ShadeArgs A)
     for (uint32_t a = 0; a < SH_NPASS; a++) {
         const uint32_t y = y0 + ly + a * SH_PASS;
         if (inside && y < A.H)
-            shade_load8(fin + static_cast<size_t>(y) * A.ipitch, n, A.invec != 0u, p[a]);
+            load8(fin + static_cast<size_t>(y) * A.ipitch, n, A.invec != 0u, p[a]);
     }
     // (x <= W - 1 gives x * sx <= (mw - 1) << 24: every map column below is inside the map)
     const uint32_t ilo = (x0 * A.sx) >> 24, cnt = ((xlast * A.sx) >> 24) - ilo + 1u;
@@ -159,14 +114,8 @@ __global__ void __launch_bounds__(SH_T) kshade(const ShadeArgs A)
             const uint32_t q = static_cast<uint32_t>(min(max(c, 0), A.top));
             o[i >> 1] = (i & 1u) ? (o[i >> 1] | (q << 16)) : q;
         }
-        shade_store8<NT>(fout + static_cast<size_t>(y) * A.opitch, n, A.outvec != 0u, o);
+        store8<NT>(fout + static_cast<size_t>(y) * A.opitch, n, A.outvec != 0u, o);
     }
-}
-
-static int shade_reject(const char *why)
-{
-    g_err = std::string("mcraw_shade_batch: ") + why;
-    return -1;
 }
 
 } // namespace mcraw
@@ -178,41 +127,32 @@ extern "C" int mcraw_shade_batch(mcraw_ctx *c, const mcraw_shade *s, const uint1
                                  void *stream)
 {
     if (!c || !s || n < 0)
-        return shade_reject("bad arguments");
+        return reject(__func__, "bad arguments");
     if (n == 0)
         return 0;
     if (!in || !out || !s->map)
-        return shade_reject("in, out or map missing");
-    if ((reinterpret_cast<uintptr_t>(in) & 1u) || (reinterpret_cast<uintptr_t>(out) & 1u))
-        return shade_reject("in / out not aligned to uint16");
+        return reject(__func__, "in, out or map missing");
+    const MosaicBatch I(in, in_pitch, in_frame_stride, static_cast<size_t>(n), width, height);
+    const MosaicBatch O(out, out_pitch, out_frame_stride, static_cast<size_t>(n), width, height);
+    if (const char *why = check(I, O))
+        return reject(__func__, why);
     if (reinterpret_cast<uintptr_t>(s->map) & 15u)
-        return shade_reject("map not 16-byte aligned");
-    if (width < 1 || height < 1 || width > 65536 || height > 65536)
-        return shade_reject("width and height must be 1 .. 65536");
-    const size_t W = static_cast<size_t>(width), H = static_cast<size_t>(height);
-    if (in_pitch < W || out_pitch < W)
-        return shade_reject("pitch below width");
-    if (n > 1 && (in_frame_stride < (H - 1u) * in_pitch + W || out_frame_stride < (H - 1u) * out_pitch + W))
-        return shade_reject("frame stride too small for the frames not to overlap");
+        return reject(__func__, "map not 16-byte aligned");
     if (s->map_w < 1u || s->map_w > SH_MAXM || s->map_h < 1u || s->map_h > SH_MAXM)
-        return shade_reject("map_w and map_h must be 1 .. 64");
+        return reject(__func__, "map_w and map_h must be 1 .. 64");
     if (s->nmaps != 1u && s->nmaps != static_cast<uint32_t>(n))
-        return shade_reject("nmaps must be 1 or n");
+        return reject(__func__, "nmaps must be 1 or n");
     if (s->top < 1u || s->top > 65535u)
-        return shade_reject("top must be 1 .. 65535");
+        return reject(__func__, "top must be 1 .. 65535");
     if (s->reserved[0] != 0u || s->reserved[1] != 0u)
-        return shade_reject("reserved must be 0");
-    // elements from the first sample of the first frame to behind the last sample of the last one
-    const size_t in_ext = static_cast<size_t>(n - 1) * in_frame_stride + (H - 1u) * in_pitch + W;
-    const size_t out_ext = static_cast<size_t>(n - 1) * out_frame_stride + (H - 1u) * out_pitch + W;
+        return reject(__func__, "reserved must be 0");
     const bool inplace = in == out && in_pitch == out_pitch && (n == 1 || in_frame_stride == out_frame_stride);
-    const uintptr_t ia = reinterpret_cast<uintptr_t>(in), oa = reinterpret_cast<uintptr_t>(out);
-    if (!inplace && ia < oa + 2u * out_ext && oa < ia + 2u * in_ext)
-        return shade_reject("in and out overlap (in place needs out == in with the same pitch and frame stride)");
+    if (!inplace && overlap(I, O))
+        return reject(__func__, "in and out overlap (in place needs out == in with the same pitch and frame stride)");
 
     std::lock_guard<std::mutex> lk(c->mu);
     HIP_TRY(hipSetDevice(c->device));
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    hipStream_t st = stream_of(c, stream);
     ShadeArgs A{};
     A.map = s->map;
     A.ipitch = in_pitch;
@@ -223,20 +163,19 @@ extern "C" int mcraw_shade_batch(mcraw_ctx *c, const mcraw_shade *s, const uint1
     A.H = static_cast<uint32_t>(height);
     A.mw = s->map_w;
     A.mh = s->map_h;
-    A.sx = width > 1 ? static_cast<uint32_t>((static_cast<uint64_t>(s->map_w - 1u) << 24) / (W - 1u)) : 0u;
-    A.sy = height > 1 ? static_cast<uint32_t>((static_cast<uint64_t>(s->map_h - 1u) << 24) / (H - 1u)) : 0u;
+    A.sx = width > 1 ? static_cast<uint32_t>((static_cast<uint64_t>(s->map_w - 1u) << 24) / (A.W - 1u)) : 0u;
+    A.sy = height > 1 ? static_cast<uint32_t>((static_cast<uint64_t>(s->map_h - 1u) << 24) / (A.H - 1u)) : 0u;
     A.tilesX = (A.W + SH_TW - 1u) / SH_TW;
     A.tilesY = (A.H + SH_TH - 1u) / SH_TH;
     A.top = static_cast<int>(s->top);
     for (int i = 0; i < 4; i++)
         A.black[i] = s->black[i];
     A.permap = s->nmaps > 1u ? 1u : 0u;
-    A.invec = (reinterpret_cast<uintptr_t>(in) & 15u) == 0u && in_pitch % 8u == 0u && (n == 1 || in_frame_stride % 8u == 0u);
-    A.outvec = (reinterpret_cast<uintptr_t>(out) & 15u) == 0u && out_pitch % 8u == 0u && (n == 1 || out_frame_stride % 8u == 0u);
+    A.invec = I.on_grid();
+    A.outvec = O.on_grid();
     const bool nt = inplace ? SH_NT_INPLACE : SH_NT_OUT;
-    constexpr int piece = 65535; // frames per launch (grid.y)
-    for (int f0 = 0; f0 < n; f0 += piece) {
-        const int nf = std::min(piece, n - f0);
+    for (int f0 = 0; f0 < n; f0 += LAUNCH_FRAMES) {
+        const int nf = std::min(LAUNCH_FRAMES, n - f0);
         A.in = in + static_cast<size_t>(f0) * in_frame_stride;
         A.out = out + static_cast<size_t>(f0) * out_frame_stride;
         A.f0 = static_cast<uint32_t>(f0);

@@ -10,8 +10,8 @@
 // content) adds 256 once.  min / max / saturated count / sum stay in registers until the workgroup ends.  At its end a
 // workgroup adds the non-zero counters to the frame's record with global integer atomics: its write traffic is at most one
 // record, whatever the number of pixels.  kstats_init writes the empty records first (unless MCRAW_STATS_ACCUMULATE).
-#include "mcraw_dev.h"
 #include "mcraw_host.h"
+#include "mcraw_mosaic.h"
 
 namespace mcraw {
 
@@ -65,14 +65,7 @@ __device__ __forceinline__ uint32_t stats_load(const StatsArgs &A, const uint16_
         m |= 256u << a;
         const uint16_t *src = fin + static_cast<size_t>(yy) * A.ipitch + x;
         if (cols == 0xFFu) {
-            if (A.vec) {
-                const mcraw_u32x4 v = *gptr<const mcraw_u32x4>(src);
-                p[a][0] = v[0], p[a][1] = v[1], p[a][2] = v[2], p[a][3] = v[3];
-            } else { // rows off the 16-byte grid: one unaligned 16-byte load
-                typedef uint32_t u32x4_u __attribute__((ext_vector_type(4), aligned(2)));
-                const u32x4_u v = *gptr<const u32x4_u>(src);
-                p[a][0] = v[0], p[a][1] = v[1], p[a][2] = v[2], p[a][3] = v[3];
-            }
+            load8(src, 8u, A.vec != 0u, p[a]);
         } else { // the window's left or right edge: element loads
 #pragma unroll
             for (uint32_t i = 0; i < 8u; i++)
@@ -81,17 +74,6 @@ __device__ __forceinline__ uint32_t stats_load(const StatsArgs &A, const uint16_
         }
     }
     return (m & 0x300u) ? m : 0u;
-}
-
-__device__ __forceinline__ uint32_t pk_min_u16(uint32_t a, uint32_t b)
-{
-    typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b)));
-}
-__device__ __forceinline__ uint32_t pk_max_u16(uint32_t a, uint32_t b)
-{
-    typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b)));
 }
 
 struct StatsAcc {
@@ -112,8 +94,8 @@ __device__ __forceinline__ void stats_tile(const StatsArgs &A, const uint32_t p[
             const uint32_t off = FULL ? 0u
                                       : ((row && (m >> (2u * k) & 1u)) ? 0u : 0xFFFFu) |
                                             ((row && (m >> (2u * k + 1u) & 1u)) ? 0u : 0xFFFF0000u);
-            S.mn[a] = pk_min_u16(S.mn[a], p[a][k] | off);
-            S.mx[a] = pk_max_u16(S.mx[a], p[a][k] & ~off);
+            S.mn[a] = pk_min(S.mn[a], p[a][k] | off);
+            S.mx[a] = pk_max(S.mx[a], p[a][k] & ~off);
         }
 #pragma unroll
         for (uint32_t par = 0; par < 2u; par++) {
@@ -237,12 +219,6 @@ __global__ void __launch_bounds__(256) kstats_init(uint32_t *out, size_t words, 
     }
 }
 
-static int stats_reject(const char *why)
-{
-    g_err = std::string("mcraw_stats_batch: ") + why;
-    return -1;
-}
-
 template <int BL>
 static void stats_launch(const StatsArgs &A, dim3 grid, hipStream_t st)
 {
@@ -268,52 +244,46 @@ extern "C" int mcraw_stats_batch(mcraw_ctx *c, const mcraw_stats *s, const uint1
                                  int width, int height, int n, void *out, size_t out_bytes, void *stream)
 {
     if (!c || !s || n < 0)
-        return stats_reject("bad arguments");
+        return reject(__func__, "bad arguments");
     if (n == 0)
         return 0;
     if (!in || !out)
-        return stats_reject("in or out missing");
+        return reject(__func__, "in or out missing");
     if (reinterpret_cast<uintptr_t>(in) & 1u)
-        return stats_reject("in not aligned to uint16");
+        return reject(__func__, "in not aligned to uint16");
     if (reinterpret_cast<uintptr_t>(out) & 7u)
-        return stats_reject("out not 8-byte aligned");
-    if (width < 1 || height < 1 || width > 65536 || height > 65536)
-        return stats_reject("width and height must be 1 .. 65536");
+        return reject(__func__, "out not 8-byte aligned");
+    const MosaicBatch I(in, in_pitch, in_frame_stride, static_cast<size_t>(n), width, height);
+    if (const char *why = I.check())
+        return reject(__func__, why);
     const size_t W = static_cast<size_t>(width), H = static_cast<size_t>(height);
-    if (in_pitch < W)
-        return stats_reject("pitch below width");
-    if (n > 1 && in_frame_stride < (H - 1u) * in_pitch + W)
-        return stats_reject("frame stride too small for the frames not to overlap");
     if (s->bins_log2 < 6u || s->bins_log2 > 12u)
-        return stats_reject("bins_log2 must be 6 .. 12");
+        return reject(__func__, "bins_log2 must be 6 .. 12");
     if (s->shift > 15u)
-        return stats_reject("shift must be 0 .. 15");
+        return reject(__func__, "shift must be 0 .. 15");
     if (s->w < 1u || s->h < 1u)
-        return stats_reject("w and h must be at least 1");
+        return reject(__func__, "w and h must be at least 1");
     if (s->x0 >= W || s->w > W - s->x0 || s->y0 >= H || s->h > H - s->y0)
-        return stats_reject("the window leaves the frame");
+        return reject(__func__, "the window leaves the frame");
     if (s->flags & ~MCRAW_STATS_ACCUMULATE)
-        return stats_reject("unknown flag");
+        return reject(__func__, "unknown flag");
     if (s->reserved != 0u)
-        return stats_reject("reserved must be 0");
+        return reject(__func__, "reserved must be 0");
     const size_t rec = mcraw_stats_record_bytes(s->bins_log2), need = static_cast<size_t>(n) * rec;
     if (out_bytes < need)
-        return stats_reject("out_bytes below n * mcraw_stats_record_bytes(bins_log2)");
-    // elements from the first sample of the first frame to behind the last sample of the last one
-    const size_t in_ext = static_cast<size_t>(n - 1) * in_frame_stride + (H - 1u) * in_pitch + W;
-    const uintptr_t ia = reinterpret_cast<uintptr_t>(in), oa = reinterpret_cast<uintptr_t>(out);
-    if (ia < oa + need && oa < ia + 2u * in_ext)
-        return stats_reject("out overlaps the input");
+        return reject(__func__, "out_bytes below n * mcraw_stats_record_bytes(bins_log2)");
+    if (ranges_overlap(I.base, I.bytes(), reinterpret_cast<uintptr_t>(out), need))
+        return reject(__func__, "out overlaps the input");
 
     std::lock_guard<std::mutex> lk(c->mu);
     HIP_TRY(hipSetDevice(c->device));
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    hipStream_t st = stream_of(c, stream);
     const uint32_t B = 1u << s->bins_log2;
     StatsArgs A{};
     A.ipitch = in_pitch;
     A.ifstride = in_frame_stride;
     A.recwords = static_cast<uint32_t>(rec / 4u);
-    A.vec = (ia & 15u) == 0u && in_pitch % 8u == 0u && (n == 1 || in_frame_stride % 8u == 0u);
+    A.vec = I.on_grid();
     A.x0 = s->x0, A.x1 = s->x0 + s->w, A.y0 = s->y0, A.y1 = s->y0 + s->h;
     A.xa = A.x0 & ~(A.vec ? 7u : 1u);
     A.ya = A.y0 & ~1u;
@@ -330,9 +300,8 @@ extern "C" int mcraw_stats_batch(mcraw_ctx *c, const mcraw_stats *s, const uint1
         hipLaunchKernelGGL(kstats_init, dim3(blocks), dim3(256), 0, st, static_cast<uint32_t *>(out), words, A.recwords, B);
         HIP_TRY(hipGetLastError());
     }
-    constexpr int piece = 65535; // frames per launch (grid.y)
-    for (int f0 = 0; f0 < n; f0 += piece) {
-        const int nf = std::min(piece, n - f0);
+    for (int f0 = 0; f0 < n; f0 += LAUNCH_FRAMES) {
+        const int nf = std::min(LAUNCH_FRAMES, n - f0);
         // a workgroup's merge costs a pass over its LDS histogram: at least B / 64 tiles each, and ST_WGS workgroups if that leaves enough
         const uint32_t want = std::max(1u, ST_WGS / static_cast<uint32_t>(nf));
         A.tpc = std::min(ST_MAXTILES, std::max(std::max(1u, B / 64u), (A.tiles + want - 1u) / want));

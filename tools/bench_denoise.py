@@ -21,7 +21,6 @@ Forms:
 its own.
 """
 import argparse
-import ctypes as C
 import json
 import os
 import sys
@@ -35,6 +34,7 @@ import _denoise_ref as D
 import _libs as L
 import _shade_ref as S
 import motioncam_decoder_amd as M
+from altlib import AltLib
 
 PEAK = 8e12
 W, H = 3840, 2160
@@ -64,34 +64,6 @@ def torch_denoise(mos, lut, shift, radius):
         num += wgt * a
         den += wgt
     return torch.div(num + (den >> 1), den, rounding_mode="floor").to(torch.uint16)
-
-
-class AltLib:
-    """Another build of the library (the other tile height or store policy), with a context of its own."""
-
-    def __init__(self, path):
-        self.name = os.path.basename(path)
-        self.lib = C.CDLL(path)
-        self.lib.mcraw_ctx_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
-        self.lib.mcraw_ctx_destroy.argtypes = [C.c_void_p]
-        self.lib.mcraw_last_error.restype = C.c_char_p
-        self.lib.mcraw_denoise_batch.argtypes = [C.c_void_p, C.POINTER(M.Denoise), C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int,
-                                                 C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
-        self.h = C.c_void_p()
-        if self.lib.mcraw_ctx_create(0, C.byref(self.h)) != 0:
-            sys.exit("alt-lib: %s" % self.lib.mcraw_last_error().decode())
-
-    def denoise(self, mos, out, stream, lut, shift, radius):
-        n, h, w = mos.shape
-        s = M.Denoise()
-        s.radius, s.amount, s.lut_log2, s.shift, s.nluts = radius, 256, int(lut.shape[-1]).bit_length() - 1, shift, 1
-        s.lut = lut.data_ptr()
-        rc = self.lib.mcraw_denoise_batch(self.h, C.byref(s), C.c_void_p(mos.data_ptr()), w, h * w, w, h, n, C.c_void_p(out.data_ptr()),
-                                          w, h * w, C.c_void_p(stream.cuda_stream))
-        assert rc == 0, self.lib.mcraw_last_error().decode()
-
-    def close(self):
-        self.lib.mcraw_ctx_destroy(self.h)
 
 
 def run(ctx, alts, n, reps, torch_frames):

@@ -18,7 +18,6 @@ Forms:
 -DMCRAW_FIXPIX_FLIP_STORES); its natural and noise forms take turns with the others, in a context of its own.
 """
 import argparse
-import ctypes as C
 import json
 import os
 import sys
@@ -32,6 +31,7 @@ import _fixpix_ref as F
 import _libs as L
 import _shade_ref as S
 import motioncam_decoder_amd as M
+from altlib import AltLib
 
 PEAK = 8e12
 W, H = 3840, 2160
@@ -67,34 +67,6 @@ def torch_fixpix(mos, black, abs_thr, rel, rank):
             val = torch.where(d < best, m, val)
             best = torch.minimum(best, d)
     return torch.where(flag, val, v).to(torch.uint16)
-
-
-class AltLib:
-    """A second build of the library (the other tile height or store policy), with a context of its own."""
-
-    def __init__(self, path):
-        self.lib = C.CDLL(path)
-        self.lib.mcraw_ctx_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
-        self.lib.mcraw_ctx_destroy.argtypes = [C.c_void_p]
-        self.lib.mcraw_last_error.restype = C.c_char_p
-        self.lib.mcraw_fixpix_batch.argtypes = [C.c_void_p, C.POINTER(M.FixPix), C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int,
-                                                C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
-        self.h = C.c_void_p()
-        if self.lib.mcraw_ctx_create(0, C.byref(self.h)) != 0:
-            sys.exit("alt-lib: %s" % self.lib.mcraw_last_error().decode())
-
-    def fix(self, mos, out, stream, black, abs_thr, rel):
-        n, h, w = mos.shape
-        s = M.FixPix()
-        s.flags, s.rank, s.rel_thr, s.nlist = 3, 2, rel, 0
-        for i in range(4):
-            s.black[i], s.abs_thr[i] = black[i], abs_thr[i]
-        rc = self.lib.mcraw_fixpix_batch(self.h, C.byref(s), C.c_void_p(mos.data_ptr()), w, h * w, w, h, n, C.c_void_p(out.data_ptr()),
-                                         w, h * w, C.c_void_p(stream.cuda_stream))
-        assert rc == 0, self.lib.mcraw_last_error().decode()
-
-    def close(self):
-        self.lib.mcraw_ctx_destroy(self.h)
 
 
 def run(ctx, alt, n, reps, torch_frames):

@@ -22,7 +22,6 @@ of its own.  --fetched-bytes: the bytes a memory-side counter run of its own (on
 row then carries their ratio to the algorithmic input bytes.
 """
 import argparse
-import ctypes as C
 import json
 import os
 import sys
@@ -36,6 +35,7 @@ import _libs as L
 import _merge_ref as R
 import _shade_ref as S
 import motioncam_decoder_amd as M
+from altlib import AltLib
 
 PEAK = 8e12
 W, H = 3840, 2160
@@ -77,35 +77,6 @@ def torch_merge(mos, lut, shift, T, first, count):
             den += wgt
         outs.append(torch.div(num + (den >> 1), den, rounding_mode="floor").to(torch.uint16))
     return torch.stack(outs)
-
-
-class AltLib:
-    """Another build of the library (the other tile height or store policy), with a context of its own."""
-
-    def __init__(self, path):
-        self.name = os.path.basename(path)
-        self.lib = C.CDLL(path)
-        self.lib.mcraw_ctx_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
-        self.lib.mcraw_ctx_destroy.argtypes = [C.c_void_p]
-        self.lib.mcraw_last_error.restype = C.c_char_p
-        self.lib.mcraw_merge_batch.argtypes = [C.c_void_p, C.POINTER(M.Merge), C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int,
-                                               C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
-        self.h = C.c_void_p()
-        if self.lib.mcraw_ctx_create(0, C.byref(self.h)) != 0:
-            sys.exit("alt-lib: %s" % self.lib.mcraw_last_error().decode())
-
-    def merge(self, mos, out, stream, lut, shift, T, support):
-        n, h, w = mos.shape
-        s = M.Merge()
-        s.before, s.after, s.first, s.count, s.support, s.amount = T, T, 0, n, support, 256
-        s.lut_log2, s.shift, s.nluts, s.reserved = int(lut.shape[-1]).bit_length() - 1, shift, 1, 0
-        s.lut, s.pos = lut.data_ptr(), None
-        rc = self.lib.mcraw_merge_batch(self.h, C.byref(s), C.c_void_p(mos.data_ptr()), w, h * w, w, h, n, C.c_void_p(out.data_ptr()),
-                                        w, h * w, C.c_void_p(stream.cuda_stream))
-        assert rc == 0, self.lib.mcraw_last_error().decode()
-
-    def close(self):
-        self.lib.mcraw_ctx_destroy(self.h)
 
 
 def parse(form):

@@ -13,7 +13,6 @@ Appends to profiles/shade_bench.jsonl.  Needs a GPU.
 with the others, in a context of its own.
 """
 import argparse
-import ctypes as C
 import json
 import os
 import sys
@@ -27,6 +26,7 @@ import _libs as L
 import _rgb_ref as R
 import _shade_ref as S
 import motioncam_decoder_amd as M
+from altlib import AltLib
 
 PEAK = 8e12
 W, H = 3840, 2160
@@ -57,35 +57,6 @@ def torch_shade(mos, fg, black, top):
         x = mos[:, py::2, px::2].to(torch.float32)
         out[:, py::2, px::2] = torch.round((x - black[p]) * g + black[p]).clamp_(0, top).to(torch.uint16)
     return out
-
-
-class AltLib:
-    """A second build of the library (the other store policy), with a context of its own."""
-
-    def __init__(self, path):
-        self.lib = C.CDLL(path)
-        self.lib.mcraw_ctx_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
-        self.lib.mcraw_ctx_destroy.argtypes = [C.c_void_p]
-        self.lib.mcraw_last_error.restype = C.c_char_p
-        self.lib.mcraw_shade_batch.argtypes = [C.c_void_p, C.POINTER(M.Shade), C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int,
-                                               C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
-        self.h = C.c_void_p()
-        if self.lib.mcraw_ctx_create(0, C.byref(self.h)) != 0:
-            sys.exit("alt-lib: %s" % self.lib.mcraw_last_error().decode())
-
-    def shade(self, mos, dmap, out, stream):
-        n, h, w = mos.shape
-        s = M.Shade()
-        s.map_w, s.map_h, s.nmaps, s.top = GW, GH, 1, TOP
-        for i in range(4):
-            s.black[i] = BLACK[i]
-        s.map = dmap.data_ptr()
-        rc = self.lib.mcraw_shade_batch(self.h, C.byref(s), C.c_void_p(mos.data_ptr()), w, h * w, w, h, n, C.c_void_p(out.data_ptr()),
-                                        w, h * w, C.c_void_p(stream.cuda_stream))
-        assert rc == 0, self.lib.mcraw_last_error().decode()
-
-    def close(self):
-        self.lib.mcraw_ctx_destroy(self.h)
 
 
 def run(ctx, alt, content, n, reps):
@@ -127,9 +98,9 @@ def run(ctx, alt, content, n, reps):
         if f == "mhc_f16_shading":
             return ctx.demosaic(mos, algo="mhc", dtype="f16", out=out_mhc, shading=dmap, **kw)
         if f == "shade_out_alt":
-            return alt.shade(mos, dmap, out16, stream)
+            return alt.shade(mos, dmap, out16, stream, GW, GH, TOP, BLACK)
         if f == "shade_inplace_alt":
-            return alt.shade(work, dmap, work, stream)
+            return alt.shade(work, dmap, work, stream, GW, GH, TOP, BLACK)
         raise KeyError(f)
 
     want0 = S.shade_ref(imgs[0], gm, BLACK, TOP)

@@ -7,7 +7,9 @@ torch stream), bytes read and the fraction of the 8 TB/s peak.  240 UHD 12-bit f
 B = 256 over a centre window of a quarter of the frame; all forms take turns rep by rep in ONE process.  The first and the last
 frame of every form are checked against the numpy reference.  Appends to profiles/stats_bench.jsonl.  Needs a GPU.
 
-    python tools/bench_stats.py [--reps 15] [--frames 240] [--content noise,smooth,flat,halfclip] [--out FILE]
+    python tools/bench_stats.py [--reps 15] [--frames 240] [--content noise,smooth,flat,halfclip] [--alt-lib PATH] [--out FILE]
+
+--alt-lib: another build of the library (tools/altlib.py); its three stats forms (*_alt) join the turns.
 """
 import argparse
 import json
@@ -22,6 +24,7 @@ import torch
 import _libs as L
 import _stats_ref as S
 import motioncam_decoder_amd as M
+from altlib import AltLib
 
 PEAK = 8e12
 W, H = 3840, 2160
@@ -29,6 +32,7 @@ SAT = 4095
 ROI = (H // 4, W // 4, H // 2, W // 2)
 DISTINCT = 4
 FORMS = ["stats_b256", "stats_b4096", "stats_b256_window", "kshade_out", "torch_ops_b256"]
+ALT_FORMS = ["stats_b256_alt", "stats_b4096_alt", "stats_b256_window_alt"]
 
 
 def frames(content, rng):
@@ -64,7 +68,7 @@ def torch_stats(mos, bins, shift, sat):
     return res
 
 
-def run(ctx, content, n, reps):
+def run(ctx, alt, content, n, reps):
     dev = torch.device("cuda:0")
     imgs = frames(content, np.random.default_rng(7))
     mos = torch.empty((n, H, W), dtype=torch.uint16, device=dev)
@@ -87,18 +91,26 @@ def run(ctx, content, n, reps):
             return ctx.shade(mos, unit, black=(64,) * 4, top=65535, out=out16)
         if f == "torch_ops_b256":
             return torch_stats(mos, 256, 4, SAT)
+        if f == "stats_b256_alt":
+            return alt.stats(mos, recs[256], stream, 256, 4, SAT)
+        if f == "stats_b4096_alt":
+            return alt.stats(mos, recs[4096], stream, 4096, 0, SAT)
+        if f == "stats_b256_window_alt":
+            return alt.stats(mos, recs[256], stream, 256, 4, SAT, ROI)
         raise KeyError(f)
+
+    forms = FORMS + (ALT_FORMS if alt else [])
 
     last = (n - 1) % DISTINCT
     pair = np.stack([imgs[0], imgs[last]])
     torch.cuda.synchronize()
-    for f in FORMS:  # correctness of the first and the last frame of every form, and warm-up
+    for f in forms:  # correctness of the first and the last frame of every form, and warm-up
         with torch.cuda.stream(stream):
             res = call(f)
         torch.cuda.synchronize()
         if f.startswith("stats_"):
-            bins, shift = (4096, 0) if f == "stats_b4096" else (256, 4)
-            want = S.record(S.stats(pair, bins, shift, (SAT,) * 4, ROI if f.endswith("window") else None))
+            bins, shift = (4096, 0) if f.startswith("stats_b4096") else (256, 4)
+            want = S.record(S.stats(pair, bins, shift, (SAT,) * 4, ROI if "window" in f else None))
             got = res.raw.cpu().numpy()
             assert np.array_equal(got[0], want[0]) and np.array_equal(got[n - 1], want[1]), f
         elif f == "torch_ops_b256":
@@ -108,10 +120,10 @@ def run(ctx, content, n, reps):
                     assert np.array_equal(hist[fr].cpu().numpy(), want["hist"][k, p]) and int(nsat[fr]) == want["nsat"][k, p]
                     assert int(sm[fr]) == want["sum"][k, p] and int(mn[fr]) == want["min"][k, p] and int(mx[fr]) == want["max"][k, p]
         del res
-    ms = {f: [] for f in FORMS}
+    ms = {f: [] for f in forms}
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     for _ in range(reps):
-        for f in FORMS:  # the forms take turns
+        for f in forms:  # the forms take turns
             with torch.cuda.stream(stream):
                 a.record(stream)
                 res = call(f)
@@ -122,9 +134,10 @@ def run(ctx, content, n, reps):
     ctx.synchronize()
     assert ctx.errors() == 0
     mosaic_bytes = n * W * H * 2
-    read = {"stats_b256_window": mosaic_bytes // 4, "kshade_out": mosaic_bytes}  # (kshade writes as many again)
+    read = {"stats_b256_window": mosaic_bytes // 4, "stats_b256_window_alt": mosaic_bytes // 4,
+            "kshade_out": mosaic_bytes}  # (kshade writes as many again)
     rows = []
-    for f in FORMS:
+    for f in forms:
         med = float(np.median(ms[f]))
         rb = read.get(f, mosaic_bytes)
         moved = 2 * rb if f == "kshade_out" else rb
@@ -145,15 +158,17 @@ def main():
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--frames", type=int, default=240)
     ap.add_argument("--content", default="noise,smooth,flat,halfclip")
+    ap.add_argument("--alt-lib", default=None)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "stats_bench.jsonl"))
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_stats.py needs a GPU")
     ctx = M.Context(0)
+    alt = AltLib(args.alt_lib) if args.alt_lib else None
     noise = {}
     with open(args.out, "a") as fh:
         for content in [c for c in args.content.split(",") if c]:
-            rows = run(ctx, content, args.frames, max(3, args.reps))
+            rows = run(ctx, alt, content, args.frames, max(3, args.reps))
             by = {r["form"]: r.get("batch_ms") for r in rows}
             if content == "noise":
                 noise = by
@@ -161,9 +176,13 @@ def main():
                 rows.append({"content": content, "form": "over_noise", "b256": round(by["stats_b256"] / noise["stats_b256"], 3),
                              "b4096": round(by["stats_b4096"] / noise["stats_b4096"], 3)})
             for r in rows:
+                if alt:
+                    r["alt_lib"] = alt.name
                 line = json.dumps(r)
                 print(line, flush=True)
                 fh.write(line + "\n")
+    if alt:
+        alt.close()
     ctx.close()
 
 
