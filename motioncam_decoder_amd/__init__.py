@@ -1526,32 +1526,63 @@ class Context:
         keyword arguments (lut, shift, radius, amount), applied behind defects= and in front of shading=, into a scratch
         tensor: the noise model holds for the sensor's values, not for the shaded ones; None: no such stage."""
         import torch
+        code = _float_code(dtype)
+        tdtype = {FLOAT_F32: torch.float32, FLOAT_F16: torch.float16, FLOAT_BF16: torch.bfloat16}[code]
+        front = self._demosaic_front("demosaic", mosaic, algo, cfa, black, defects, denoise, shading)
+        ho, wo = front[6:8]
+        out = self._demosaic_out("demosaic", front, out, (3, ho, wo), tdtype)
+        if front[2] == 0:
+            return out
+        return self._demosaic_call("mcraw_demosaic_batch", "demosaic", front, algo, code, FLOAT_CLIP if clip else 0, white, black,
+                                   gain, matrix, out)
+
+    def _demosaic_front(self, fn, mosaic, algo, cfa, black, defects, denoise, shading):
+        """What demosaic / demosaic_display / demosaic_yuv (`fn`) do alike in front of their output: the algo and cfa checks,
+        the mosaic argument, the optional stages -- defects, then denoise, then shading, each into a scratch tensor (the
+        caller's mosaic stays as it is), none for an empty batch -- and the output size.  Returns (mos, single, n, h, w, src,
+        ho, wo, key): src is _strided's triple (None for no frames), key the cfa's."""
+        import torch
         if algo not in _RGB_ALGOS:
             raise ValueError("algo must be 'mhc' or 'bin2', not %r" % (algo,))
         key = str(cfa).strip().lower()
         if key not in _CFA_CODES:
             raise ValueError("unknown cfa %r (rggb, bggr, grbg or gbrg)" % (cfa,))
-        code = _float_code(dtype)
-        tdtype = {FLOAT_F32: torch.float32, FLOAT_F16: torch.float16, FLOAT_BF16: torch.bfloat16}[code]
         dev = self._torch_device(torch)
-        mos, single = self._mosaic_arg(torch, dev, "demosaic", mosaic)[:2]
-        if defects is not None and mos.numel():  # into a scratch tensor, in front of the gains
-            mos = self._fix_defects(mos, defects, black, "demosaic")
-        if denoise is not None and mos.numel():  # on the sensor's values: behind the defects, in front of the gains
-            mos = self._denoise_stage(mos, denoise, "demosaic")
+        mos, single = self._mosaic_arg(torch, dev, fn, mosaic)[:2]
+        mos = self._pre_stages(fn, mos, black, defects, denoise)
         if shading is not None and mos.numel():  # into a scratch tensor: the caller's mosaic stays as it is
             mos = self.shade(mos, shading, black=black)
         n, h, w = (int(v) for v in mos.shape)
-        src = self._strided("demosaic", "the mosaic", mos, h, w) if n else None
+        src = self._strided(fn, "the mosaic", mos, h, w) if n else None
         ho, wo = (h, w) if algo == "mhc" else (h // 2, w // 2)
-        shape = (n, 3, ho, wo)
-        want = shape[1:] if single else shape
-        out = self._out_arg(torch, dev, "demosaic", out, want, tdtype, contiguous=True)
-        if n == 0:
-            return out
-        cols, nc = _rgb_colors(gain, matrix, n, "demosaic")
-        prm = _rgb_params(algo, code, FLOAT_CLIP if clip else 0, key, white, black)
-        self._call(torch, dev, "mcraw_demosaic_batch", (mos, out), C.byref(prm), cols, nc, *src, w, h, n, C.c_void_p(out.data_ptr()), out.numel() * out.element_size())
+        return mos, single, n, h, w, src, ho, wo, key
+
+    def _pre_stages(self, fn, mos, black, defects, denoise):
+        """defects= and denoise= of the demosaic / decode methods, in that order, each into a scratch tensor; an empty batch
+        passes through."""
+        if defects is not None and mos.numel():  # in front of the gains
+            mos = self._fix_defects(mos, defects, black, fn)
+        if denoise is not None and mos.numel():  # on the sensor's values: behind the defects, in front of the gains
+            mos = self._denoise_stage(mos, denoise, fn)
+        return mos
+
+    def _demosaic_out(self, fn, front, out, frame_shape, tdtype):
+        """`out` of a demosaic method, checked or made: frame_shape per frame, without N for an (H, W) mosaic."""
+        import torch
+        mos, single, n = front[:3]
+        want = tuple(frame_shape) if single else (n,) + tuple(frame_shape)
+        return self._out_arg(torch, mos.device, fn, out, want, tdtype, contiguous=True)
+
+    def _demosaic_call(self, symbol, fn, front, algo, dtype_code, flags, white, black, gain, matrix, out, stage=None, extra=()):
+        """The tail of the three demosaics: colours, params and the library's `symbol` (stage: its display / YUV struct, None
+        for the float entry; extra: further tensors that take part).  Returns out."""
+        import torch
+        mos, _, n, h, w, src, _, _, key = front
+        cols, nc = _rgb_colors(gain, matrix, n, fn)
+        prm = _rgb_params(algo, dtype_code, flags, key, white, black)
+        structs = (C.byref(prm),) if stage is None else (C.byref(prm), C.byref(stage))
+        self._call(torch, mos.device, symbol, (mos, out) + tuple(extra), *structs, cols, nc, *src, w, h, n,
+                   C.c_void_p(out.data_ptr()), out.numel() * out.element_size())
         return out
 
     def _decode_scratch(self, inputs, width, height, type, check, fn):
@@ -1588,6 +1619,14 @@ class Context:
                         fn, len(bad), n, ", ".join("frame %d status 0x%x" % b for b in bad[:16])))
         return scratch
 
+    def _decode_front(self, fn, inputs, width, height, type, check, black, defects, denoise, shading):
+        """The scratch mosaics of decode_rgb / decode_display / decode_yuv (`fn`), ready for the demosaic: decoded, then
+        defects= and denoise= (each into a further scratch tensor), then shading= in place."""
+        scratch = self._pre_stages(fn, self._decode_scratch(inputs, width, height, type, check, fn), black, defects, denoise)
+        if shading is not None:
+            self.shade(scratch, shading, black=black, out=scratch)
+        return scratch
+
     def decode_rgb(self, inputs, width, height, type, *, algo="mhc", dtype, white, black=(0, 0, 0, 0), cfa="rggb",
                    gain=None, matrix=None, clip=False, out=None, check=True, shading=None, defects=None, denoise=None):
         """Decode frames of one geometry that are resident in HBM and demosaic them (demosaic()): (N, 3, H, W) for "mhc",
@@ -1598,28 +1637,22 @@ class Context:
         (shade()), applied to the scratch mosaics in place before the demosaic.  defects: a dict of fix_pixels()' keyword
         arguments (black defaults to this call's), applied in front of shading= into a second scratch tensor.  denoise: a
         dict of denoise()'s keyword arguments, applied behind defects= and in front of shading=."""
-        scratch = self._decode_scratch(inputs, width, height, type, check, "decode_rgb")
-        if defects is not None and scratch.numel():
-            scratch = self._fix_defects(scratch, defects, black, "decode_rgb")
-        if denoise is not None and scratch.numel():
-            scratch = self._denoise_stage(scratch, denoise, "decode_rgb")
-        if shading is not None:
-            self.shade(scratch, shading, black=black, out=scratch)
+        scratch = self._decode_front("decode_rgb", inputs, width, height, type, check, black, defects, denoise, shading)
         return self.demosaic(scratch, algo=algo, dtype=dtype, white=white, black=black, cfa=cfa, gain=gain, matrix=matrix,
                              clip=clip, out=out, check=check)
 
-    def _display_lut(self, torch, dev, transfer, lut_size, bits):
-        """(device LUT tensor, caller-owned?) for demosaic_display: a ready 1-D uint16 LUT (CUDA tensor on `dev`, or a
-        host array, uploaded), or the built-in curve of transfer_lut, built once per (curve, size, bits, device)."""
+    def _display_lut(self, torch, dev, fn, transfer, lut_size, bits):
+        """(device LUT tensor, caller-owned?) for demosaic_display / demosaic_yuv (`fn`): a ready 1-D uint16 LUT (CUDA tensor on
+        `dev`, or a host array, uploaded), or the built-in curve of transfer_lut, built once per (curve, size, bits, device)."""
         import numpy as np
         if isinstance(transfer, torch.Tensor):
             if transfer.device != dev or transfer.dim() != 1 or transfer.dtype not in (torch.uint16, torch.int16) \
                     or not transfer.is_contiguous():
-                raise ValueError("demosaic_display: a LUT tensor must be a contiguous 1-D uint16 tensor on %s" % dev)
+                raise ValueError("%s: a LUT tensor must be a contiguous 1-D uint16 tensor on %s" % (fn, dev))
             lut, own = transfer.view(torch.uint16), True
         elif isinstance(transfer, np.ndarray):
             if transfer.ndim != 1 or transfer.dtype != np.uint16:
-                raise ValueError("demosaic_display: a LUT array must be 1-D uint16")
+                raise ValueError("%s: a LUT array must be 1-D uint16" % fn)
             lut, own = torch.from_numpy(np.ascontiguousarray(transfer).view(np.int16)).to(dev).view(torch.uint16), True
         else:
             key = (transfer if isinstance(transfer, str) else float(transfer) if not callable(transfer) else None,
@@ -1634,7 +1667,7 @@ class Context:
             own = False
         L = int(lut.numel())
         if L < 256 or L > 65536 or L & (L - 1):
-            raise ValueError("demosaic_display: the LUT length must be a power of two, 256 .. 65536, not %d" % L)
+            raise ValueError("%s: the LUT length must be a power of two, 256 .. 65536, not %d" % (fn, L))
         return lut, own
 
     def demosaic_display(self, mosaic, *, algo="mhc", white, black=(0, 0, 0, 0), cfa="rggb", gain=None, matrix=None,
@@ -1649,43 +1682,25 @@ class Context:
         torch.cuda.current_stream(); nothing synchronises, and a caller's LUT is read when the kernels run (in stream
         order).  `check` is accepted for symmetry with decode_display.  shading, defects, denoise: as demosaic()."""
         import torch
-        if algo not in _RGB_ALGOS:
-            raise ValueError("algo must be 'mhc' or 'bin2', not %r" % (algo,))
-        key = str(cfa).strip().lower()
-        if key not in _CFA_CODES:
-            raise ValueError("unknown cfa %r (rggb, bggr, grbg or gbrg)" % (cfa,))
         dtype = torch.uint8 if dtype is None else dtype
         dcode = {torch.uint8: DISP_U8, torch.uint16: DISP_U16, "u8": DISP_U8, "u16": DISP_U16}.get(dtype)
         if dcode is None:
             raise ValueError("demosaic_display: dtype must be torch.uint8 or torch.uint16, not %r" % (dtype,))
-        tdtype = torch.uint8 if dcode == DISP_U8 else torch.uint16
         if layout not in _DISP_LAYOUTS:
             raise ValueError("demosaic_display: layout must be 'hwc' or 'chw', not %r" % (layout,))
-        dev = self._torch_device(torch)
-        mos, single = self._mosaic_arg(torch, dev, "demosaic_display", mosaic)[:2]
-        if defects is not None and mos.numel():  # into a scratch tensor, in front of the gains
-            mos = self._fix_defects(mos, defects, black, "demosaic_display")
-        if denoise is not None and mos.numel():  # on the sensor's values: behind the defects, in front of the gains
-            mos = self._denoise_stage(mos, denoise, "demosaic_display")
-        if shading is not None and mos.numel():  # into a scratch tensor: the caller's mosaic stays as it is
-            mos = self.shade(mos, shading, black=black)
-        n, h, w = (int(v) for v in mos.shape)
-        src = self._strided("demosaic_display", "the mosaic", mos, h, w) if n else None
-        ho, wo = (h, w) if algo == "mhc" else (h // 2, w // 2)
-        shape = (n, ho, wo, 3) if layout == "hwc" else (n, 3, ho, wo)
-        want = shape[1:] if single else shape
-        out = self._out_arg(torch, dev, "demosaic_display", out, want, tdtype, contiguous=True)
-        if n == 0:
+        front = self._demosaic_front("demosaic_display", mosaic, algo, cfa, black, defects, denoise, shading)
+        ho, wo = front[6:8]
+        out = self._demosaic_out("demosaic_display", front, out, (ho, wo, 3) if layout == "hwc" else (3, ho, wo),
+                                 torch.uint8 if dcode == DISP_U8 else torch.uint16)
+        if front[2] == 0:
             return out
-        lut, own = self._display_lut(torch, dev, transfer, lut_size, (8 if dcode == DISP_U8 else 16) if bits is None else bits)
-        cols, nc = _rgb_colors(gain, matrix, n, "demosaic_display")
-        prm = _rgb_params(algo, 0, 0, key, white, black)
+        lut, own = self._display_lut(torch, out.device, "demosaic_display", transfer, lut_size,
+                                     (8 if dcode == DISP_U8 else 16) if bits is None else bits)
         d = Display()
         d.dtype, d.layout, d.lut_log2, d.reserved = dcode, _DISP_LAYOUTS[layout], int(lut.numel()).bit_length() - 1, 0
         d.lut = lut.data_ptr()
-        self._call(torch, dev, "mcraw_demosaic_display_batch", (mos, out, lut if own else None), C.byref(prm), C.byref(d), cols, nc,
-                   *src, w, h, n, C.c_void_p(out.data_ptr()), out.numel() * out.element_size())
-        return out
+        return self._demosaic_call("mcraw_demosaic_display_batch", "demosaic_display", front, algo, 0, 0, white, black, gain, matrix,
+                                   out, d, (lut if own else None,))
 
     def decode_display(self, inputs, width, height, type, *, algo="mhc", white, black=(0, 0, 0, 0), cfa="rggb", gain=None,
                        matrix=None, transfer="srgb", lut_size=4096, dtype=None, layout="hwc", bits=None, out=None, check=True, shading=None,
@@ -1694,13 +1709,7 @@ class Context:
         (demosaic_display()), as decode_rgb does: the plain uint16 mosaics go to a scratch tensor, both steps are queued on
         torch.cuda.current_stream(), check=True synchronises after the decode and raises McrawError naming the frames that
         failed, and the context's stage is restored afterwards.  shading, defects, denoise: as decode_rgb()."""
-        scratch = self._decode_scratch(inputs, width, height, type, check, "decode_display")
-        if defects is not None and scratch.numel():
-            scratch = self._fix_defects(scratch, defects, black, "decode_display")
-        if denoise is not None and scratch.numel():
-            scratch = self._denoise_stage(scratch, denoise, "decode_display")
-        if shading is not None:
-            self.shade(scratch, shading, black=black, out=scratch)
+        scratch = self._decode_front("decode_display", inputs, width, height, type, check, black, defects, denoise, shading)
         return self.demosaic_display(scratch, algo=algo, white=white, black=black, cfa=cfa, gain=gain, matrix=matrix,
                                      transfer=transfer, lut_size=lut_size, dtype=dtype, layout=layout, bits=bits, out=out,
                                      check=check)
@@ -1718,45 +1727,25 @@ class Context:
         LUT may hold entries of any in_bits 8 .. 16 (higher bits are masked off).  Queued on torch.cuda.current_stream();
         nothing synchronises.  `check` is accepted for symmetry with decode_yuv.  shading, defects, denoise: as demosaic()."""
         import torch
-        if algo not in _RGB_ALGOS:
-            raise ValueError("algo must be 'mhc' or 'bin2', not %r" % (algo,))
-        key = str(cfa).strip().lower()
-        if key not in _CFA_CODES:
-            raise ValueError("unknown cfa %r (rggb, bggr, grbg or gbrg)" % (cfa,))
         if fmt not in _YUV_FORMATS:
             raise ValueError("demosaic_yuv: fmt must be 'nv12' or 'p010', not %r" % (fmt,))
         fcode, bits, default_in = _YUV_FORMATS[fmt]
         in_bits = default_in if in_bits is None else in_bits
         cy, cb, cr, sh, y_off, c_off = yuv_matrix(standard, range, bits, in_bits)
-        tdtype = torch.uint8 if fcode == YUV_NV12 else torch.uint16
-        dev = self._torch_device(torch)
-        mos, single = self._mosaic_arg(torch, dev, "demosaic_yuv", mosaic)[:2]
-        if defects is not None and mos.numel():  # into a scratch tensor, in front of the gains
-            mos = self._fix_defects(mos, defects, black, "demosaic_yuv")
-        if denoise is not None and mos.numel():  # on the sensor's values: behind the defects, in front of the gains
-            mos = self._denoise_stage(mos, denoise, "demosaic_yuv")
-        if shading is not None and mos.numel():  # into a scratch tensor: the caller's mosaic stays as it is
-            mos = self.shade(mos, shading, black=black)
-        n, h, w = (int(v) for v in mos.shape)
-        src = self._strided("demosaic_yuv", "the mosaic", mos, h, w) if n else None
-        ho, wo = (h, w) if algo == "mhc" else (h // 2, w // 2)
-        shape = (n, ho * 3 // 2, wo)
-        want = shape[1:] if single else shape
-        out = self._out_arg(torch, dev, "demosaic_yuv", out, want, tdtype, contiguous=True)
-        if n == 0:
+        front = self._demosaic_front("demosaic_yuv", mosaic, algo, cfa, black, defects, denoise, shading)
+        ho, wo = front[6:8]
+        out = self._demosaic_out("demosaic_yuv", front, out, (ho * 3 // 2, wo), torch.uint8 if fcode == YUV_NV12 else torch.uint16)
+        if front[2] == 0:
             return out
-        lut, own = self._display_lut(torch, dev, transfer, lut_size, in_bits)
-        cols, nc = _rgb_colors(gain, matrix, n, "demosaic_yuv")
-        prm = _rgb_params(algo, 0, 0, key, white, black)
+        lut, own = self._display_lut(torch, out.device, "demosaic_yuv", transfer, lut_size, in_bits)
         y = Yuv()
         y.format, y.lut_log2, y.in_bits, y.sh, y.y_off, y.c_off = fcode, int(lut.numel()).bit_length() - 1, in_bits, sh, y_off, c_off
         for i in (0, 1, 2):
             y.cy[i], y.cb[i], y.cr[i] = cy[i], cb[i], cr[i]
         y.reserved = 0
         y.lut = lut.data_ptr()
-        self._call(torch, dev, "mcraw_demosaic_yuv_batch", (mos, out, lut if own else None), C.byref(prm), C.byref(y), cols, nc,
-                   *src, w, h, n, C.c_void_p(out.data_ptr()), out.numel() * out.element_size())
-        return out
+        return self._demosaic_call("mcraw_demosaic_yuv_batch", "demosaic_yuv", front, algo, 0, 0, white, black, gain, matrix, out, y,
+                                   (lut if own else None,))
 
     def decode_yuv(self, inputs, width, height, type, *, algo="mhc", white, black=(0, 0, 0, 0), cfa="rggb", gain=None,
                    matrix=None, fmt="nv12", standard="bt709", range="limited", transfer="bt709", lut_size=4096, in_bits=None,
@@ -1765,13 +1754,7 @@ class Context:
         decode_display does: the plain uint16 mosaics go to a scratch tensor, both steps are queued on
         torch.cuda.current_stream(), check=True synchronises after the decode and raises McrawError naming the frames that
         failed, and the context's stage is restored afterwards.  shading, defects, denoise: as decode_rgb()."""
-        scratch = self._decode_scratch(inputs, width, height, type, check, "decode_yuv")
-        if defects is not None and scratch.numel():
-            scratch = self._fix_defects(scratch, defects, black, "decode_yuv")
-        if denoise is not None and scratch.numel():
-            scratch = self._denoise_stage(scratch, denoise, "decode_yuv")
-        if shading is not None:
-            self.shade(scratch, shading, black=black, out=scratch)
+        scratch = self._decode_front("decode_yuv", inputs, width, height, type, check, black, defects, denoise, shading)
         return self.demosaic_yuv(scratch, algo=algo, white=white, black=black, cfa=cfa, gain=gain, matrix=matrix, fmt=fmt,
                                  standard=standard, range=range, transfer=transfer, lut_size=lut_size, in_bits=in_bits, out=out,
                                  check=check)

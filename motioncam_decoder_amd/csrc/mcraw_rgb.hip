@@ -16,13 +16,14 @@
 // 3x3 matrix: a luma sample per pixel and, from the sums over each 2x2 block of output pixels, one (Cb, Cr) pair (4:2:0,
 // chroma at the block's centre).  A lane owns whole 2x2 blocks (8 columns of a row pair), so nothing is exchanged.
 // tests/_yuv_ref.py states the stage in numpy.
-#include <cmath>
-#include <cstdlib>
-
 #include "mcraw_dev.h"
 #include "mcraw_host.h"
+#include "mcraw_rgb_args.h"
 
 namespace mcraw {
+
+static_assert(rgb_float_kind(MCRAW_FLOAT_F32) == PK_F32 && rgb_float_kind(MCRAW_FLOAT_F16) == PK_F16 &&
+                  rgb_float_kind(MCRAW_FLOAT_BF16) == PK_BF16, "mcraw_rgb_args.h names the float kinds of mcraw_plan.h");
 
 // per-frame colour as the kernels take it: k[c] = (gain[c] * inv) * scale, and the 3x3 matrix, row-major
 struct RgbCol {
@@ -56,22 +57,12 @@ struct RgbArgs {
     int32_t yoff, coff;
 };
 
-constexpr uint32_t RGB_T = 256;             // threads per workgroup
-constexpr uint32_t MHC_TW = 256;            // tile columns: 32 lanes x 8
-constexpr uint32_t MHC_TH = 32;             // tile rows: 8 row pairs x 2 passes
+// (RGB_T threads per workgroup, tiles of MHC_TW x MHC_TH, the output kinds PK_*: mcraw_rgb_args.h)
 constexpr uint32_t MHC_LW = MHC_TW + 16;    // LDS row: 8 columns either side (2 used), so that chunks stay on the 8-grid
 constexpr uint32_t MHC_LH = MHC_TH + 4;     // 2 halo rows above and below
 constexpr uint32_t MHC_CH = MHC_LW / 8u;    // 16-byte chunks per LDS row
 
-// display output kinds (beside PK_F32 / PK_F16 / PK_BF16 of mcraw_plan.h)
-constexpr int PK_DISP8 = 48, PK_DISP16 = 49;
 constexpr uint32_t DISP_LDS_MAX = 4096; // LUTs up to this many entries (8 KiB) are staged in LDS
-constexpr bool is_disp(int pk) { return pk == PK_DISP8 || pk == PK_DISP16; }
-// Y'CbCr 4:2:0 output kinds: a Y plane, then interleaved (Cb, Cr) rows; uint8, or uint16 holding a 10-bit code << 6
-constexpr int PK_NV12 = 50, PK_P010 = 51;
-constexpr bool is_yuv(int pk) { return pk == PK_NV12 || pk == PK_P010; }
-constexpr bool has_lut(int pk) { return is_disp(pk) || is_yuv(pk); } // persistent grid, LUT staged per workgroup
-constexpr uint32_t out_es(int pk) { return pk == PK_F32 ? 4u : (pk == PK_DISP8 || pk == PK_NV12) ? 1u : 2u; }
 
 static __device__ __forceinline__ int reflect101(int i, int n)
 {
@@ -89,10 +80,8 @@ __device__ __forceinline__ uint32_t bits16(float v)
     return __builtin_bit_cast(uint16_t, static_cast<__bf16>(v));
 }
 
-// E (3 channels x 8 pixels of one row) -> o_i = (m[3i] v0 + m[3i+1] v1) + m[3i+2] v2, v_c = (float)E_c * k[c], every
-// product and sum rounded on its own (no FMA), optional clamp, stored as 8 consecutive elements of row y, column x, of each
-// plane.  `n`: elements of the 8 that exist.
-// The colour stage every output kind shares: o_i = (m[3i] v0 + m[3i+1] v1) + m[3i+2] v2, v_c = (float)E_c * k[c].
+// The colour stage every output kind shares: E (3 channels x 8 pixels of one row) -> o_i = (m[3i] v0 + m[3i+1] v1) + m[3i+2] v2,
+// v_c = (float)E_c * k[c], every product and sum rounded on its own (no FMA).
 __device__ __forceinline__ void rgb_color8(const RgbCol &col, const int (&E)[3][8], float (&o)[3][8])
 {
 #pragma clang fp contract(off)
@@ -111,6 +100,8 @@ __device__ __forceinline__ void rgb_color8(const RgbCol &col, const int (&E)[3][
         }
 }
 
+// The float kinds: the colour stage, the optional clamp, then 8 consecutive elements of row y, column x, of each plane.
+// `n`: elements of the 8 that exist.
 template <int PK>
 __device__ __forceinline__ void rgb_store8(const RgbArgs &A, const RgbCol &col, uint8_t *frame_out, uint32_t y, uint32_t x,
                                            uint32_t n, const int (&E)[3][8])
@@ -266,7 +257,7 @@ __device__ __forceinline__ void disp_store8(const RgbArgs &A, const RgbCol &col,
     }
     const size_t plane = static_cast<size_t>(A.Ho) * A.Wo;
 #pragma unroll
-    for (int r = 0; r < 3; r++) {
+    for (int r = 0; r < 3; r++) { // (yuv_store8 per plane, written out: calling it changes the schedule of 12 instances)
         uint8_t *dst = frame_out + (r * plane + static_cast<size_t>(y) * A.Wo + x) * ES;
         const uintptr_t a = reinterpret_cast<uintptr_t>(dst);
         if (ES == 1u) {
@@ -566,7 +557,7 @@ __global__ void __launch_bounds__(RGB_T) krgb_bin2y(const RgbArgs A)
         const uint32_t n = min(8u, A.Wo - xo);
         int SUM[3][4] = {}; // the sums of P over the lane's four 2x2 blocks
     #pragma unroll
-        for (uint32_t a = 0; a < ROWS; a++) {
+        for (uint32_t a = 0; a < ROWS; a++) { // (krgb_bin2's load and quads, written out in both: DESIGN 22)
             const uint16_t *row0 = A.in + static_cast<size_t>(f) * A.fstride + static_cast<size_t>(2u * (yo + a)) * A.pitch + 2u * xo;
             const uint16_t *row1 = row0 + A.pitch;
             uint32_t u[2][8]; // (even column | odd column << 16) of quad i, rows 0 and 1
@@ -608,27 +599,31 @@ __global__ void __launch_bounds__(RGB_T) krgb_bin2y(const RgbArgs A)
 typedef void (*RgbKernel)(const RgbArgs);
 
 template <int PK>
-static RgbKernel pick_kernel(uint32_t algo, int s)
+static RgbKernel pick_kernel(bool mhc, int s)
 {
-    static const RgbKernel mhc[4] = {krgb_mhc<PK, 0>, krgb_mhc<PK, 1>, krgb_mhc<PK, 2>, krgb_mhc<PK, 3>};
-    static const RgbKernel bin2[4] = {krgb_bin2<PK, 0>, krgb_bin2<PK, 1>, krgb_bin2<PK, 2>, krgb_bin2<PK, 3>};
-    return algo == MCRAW_RGB_MHC ? mhc[s] : bin2[s];
+    static const RgbKernel tile[4] = {krgb_mhc<PK, 0>, krgb_mhc<PK, 1>, krgb_mhc<PK, 2>, krgb_mhc<PK, 3>};
+    if (mhc)
+        return tile[s];
+    if constexpr (is_yuv(PK)) {
+        static const RgbKernel bin2[4] = {krgb_bin2y<PK, 0>, krgb_bin2y<PK, 1>, krgb_bin2y<PK, 2>, krgb_bin2y<PK, 3>};
+        return bin2[s];
+    } else {
+        static const RgbKernel bin2[4] = {krgb_bin2<PK, 0>, krgb_bin2<PK, 1>, krgb_bin2<PK, 2>, krgb_bin2<PK, 3>};
+        return bin2[s];
+    }
 }
 
-template <int PK>
-static RgbKernel pick_yuv_kernel(uint32_t algo, int s)
+static RgbKernel pick_kernel(const RgbPlan &P)
 {
-    static const RgbKernel mhc[4] = {krgb_mhc<PK, 0>, krgb_mhc<PK, 1>, krgb_mhc<PK, 2>, krgb_mhc<PK, 3>};
-    static const RgbKernel bin2[4] = {krgb_bin2y<PK, 0>, krgb_bin2y<PK, 1>, krgb_bin2y<PK, 2>, krgb_bin2y<PK, 3>};
-    return algo == MCRAW_RGB_MHC ? mhc[s] : bin2[s];
-}
-
-static bool finite_all(const float *v, int n)
-{
-    for (int i = 0; i < n; i++)
-        if (!std::isfinite(v[i]))
-            return false;
-    return true;
+    switch (P.kind) {
+    case PK_F32: return pick_kernel<PK_F32>(P.mhc, P.shift);
+    case PK_F16: return pick_kernel<PK_F16>(P.mhc, P.shift);
+    case PK_BF16: return pick_kernel<PK_BF16>(P.mhc, P.shift);
+    case PK_DISP8: return pick_kernel<PK_DISP8>(P.mhc, P.shift);
+    case PK_DISP16: return pick_kernel<PK_DISP16>(P.mhc, P.shift);
+    case PK_NV12: return pick_kernel<PK_NV12>(P.mhc, P.shift);
+    default: return pick_kernel<PK_P010>(P.mhc, P.shift);
+    }
 }
 
 // Workgroups of a persistent display grid: what the device holds at once (compute units x resident workgroups of the
@@ -651,123 +646,49 @@ static uint32_t resident_groups(int device, RgbKernel k)
     return g;
 }
 
-// The three entry points: the checks of mcraw_demosaic_batch, those of the display stage when `d` is given or of the YUV
-// stage when `yv` is (never both), then the launches.
+// The three entry points: rgb_check (mcraw_rgb_args.h) decides about the call and plans it -- `d` given: the display stage, `yv`:
+// the YUV stage (never both) --, then the launches.
 static int demosaic_launch(const char *fn, mcraw_ctx *c, const mcraw_rgb *p, const mcraw_display *d, const mcraw_yuv *yv,
                            const mcraw_rgb_color *colors, int ncolors, const uint16_t *in, size_t in_pitch,
                            size_t in_frame_stride, int width, int height, int n, void *out, size_t out_bytes, void *stream)
 {
-    if (!c || !p || n < 0)
-        return reject(fn, "bad arguments");
-    if (n == 0)
+    RgbPlan P;
+    const char *why = c ? rgb_check(p, d, yv, colors, ncolors, in, in_pitch, in_frame_stride, width, height, n, out, out_bytes, P)
+                        : "bad arguments";
+    if (why)
+        return reject(fn, why);
+    if (P.noop)
         return 0;
-    if (width < 4 || height < 4 || (width & 1) || (height & 1) || width > 65536 || height > 65536)
-        return reject(fn, "width and height must be even, 4 .. 65536");
-    if (in_pitch < static_cast<size_t>(width))
-        return reject(fn, "in_pitch below width");
-    if (n > 1 && in_frame_stride < (static_cast<size_t>(height) - 1u) * in_pitch + static_cast<size_t>(width))
-        return reject(fn, "in_frame_stride too small for the frames not to overlap");
-    if (p->algo != MCRAW_RGB_MHC && p->algo != MCRAW_RGB_BIN2)
-        return reject(fn, "unknown algo");
-    const uint16_t *lut = d ? d->lut : yv ? yv->lut : nullptr;
-    const uint32_t lut_log2 = d ? d->lut_log2 : yv ? yv->lut_log2 : 0u;
-    if (d || yv) {
-        if (p->dtype != 0u || p->flags != 0u)
-            return reject(fn, "p->dtype and p->flags must be 0 (the display / YUV stage decides the output)");
-        if (lut_log2 < 8u || lut_log2 > 16u)
-            return reject(fn, "lut_log2 must be 8 .. 16");
-        if (!lut || (reinterpret_cast<uintptr_t>(lut) & 15u))
-            return reject(fn, "lut missing or not 16-byte aligned");
-    }
-    if (d) {
-        if (d->dtype != MCRAW_DISP_U8 && d->dtype != MCRAW_DISP_U16)
-            return reject(fn, "unknown display dtype");
-        if (d->layout != MCRAW_DISP_CHW && d->layout != MCRAW_DISP_HWC)
-            return reject(fn, "unknown display layout");
-        if (d->reserved != 0u)
-            return reject(fn, "reserved must be 0");
-    } else if (yv) {
-        if (yv->format != MCRAW_YUV_NV12 && yv->format != MCRAW_YUV_P010)
-            return reject(fn, "unknown YUV format");
-        if (yv->reserved != 0u)
-            return reject(fn, "reserved must be 0");
-        if (yv->in_bits < 8u || yv->in_bits > 16u)
-            return reject(fn, "in_bits must be 8 .. 16");
-        if (yv->sh < 1u || yv->sh > 24u)
-            return reject(fn, "sh must be 1 .. 24");
-        const int32_t top = yv->format == MCRAW_YUV_NV12 ? 255 : 1023;
-        if (yv->y_off < 0 || yv->y_off > top || yv->c_off < 0 || yv->c_off > top)
-            return reject(fn, "y_off and c_off must be 0 .. 2^bits - 1");
-        // no int32 sum can wrap: 4 * (2^in_bits - 1) * (|c0| + |c1| + |c2|) + 2^(sh + 1) < 2^31 for every row
-        const int32_t *rows[3] = {yv->cy, yv->cb, yv->cr};
-        for (const int32_t *r : rows) {
-            const int64_t mag = std::llabs(static_cast<int64_t>(r[0])) + std::llabs(static_cast<int64_t>(r[1])) +
-                                std::llabs(static_cast<int64_t>(r[2]));
-            if (4 * ((int64_t{1} << yv->in_bits) - 1) * mag + (int64_t{1} << (yv->sh + 1u)) >= (int64_t{1} << 31))
-                return reject(fn, "coefficients could overflow int32: 4 * (2^in_bits - 1) * (|c0| + |c1| + |c2|) + 2^(sh + 1) >= 2^31");
-        }
-    } else {
-        if (p->dtype != MCRAW_FLOAT_F32 && p->dtype != MCRAW_FLOAT_F16 && p->dtype != MCRAW_FLOAT_BF16)
-            return reject(fn, "unknown dtype");
-    }
-    if (p->cfa > MCRAW_CFA_GBRG)
-        return reject(fn, "unknown cfa");
-    if (p->flags & ~MCRAW_FLOAT_CLIP)
-        return reject(fn, "unknown flag");
-    const float bsum = static_cast<float>(static_cast<int>(p->black[0]) + p->black[1] + p->black[2] + p->black[3]);
-    if (!std::isfinite(p->white) || !(p->white > 0.25f * bsum))
-        return reject(fn, "white must be finite and above the mean black level");
-    if (!colors || (ncolors != 1 && ncolors != n))
-        return reject(fn, "ncolors must be 1 or n");
-    for (int i = 0; i < ncolors; i++)
-        if (!finite_all(colors[i].gain, 3) || !finite_all(colors[i].m, 9))
-            return reject(fn, "non-finite gain or matrix entry");
-    const bool mhc = p->algo == MCRAW_RGB_MHC;
-    const size_t es = d ? (d->dtype == MCRAW_DISP_U8 ? 1u : 2u) : yv ? (yv->format == MCRAW_YUV_NV12 ? 1u : 2u)
-                                                                      : p->dtype == MCRAW_FLOAT_F32 ? 4u : 2u;
-    const size_t Wo = mhc ? static_cast<size_t>(width) : static_cast<size_t>(width) / 2u;
-    const size_t Ho = mhc ? static_cast<size_t>(height) : static_cast<size_t>(height) / 2u;
-    if (yv && ((Ho | Wo) & 1u))
-        return reject(fn, "4:2:0 needs an even Ho and Wo (BIN2: width and height multiples of 4)");
-    // samples per frame: 3 planes, or a Y plane and half of one for the (Cb, Cr) rows
-    const size_t frame_samples = yv ? Ho * Wo / 2u * 3u : 3u * Ho * Wo;
-    if (out_bytes / es / frame_samples < static_cast<size_t>(n))
-        return reject(fn, yv ? "out_bytes below n * Ho * Wo * 3 / 2 * sample size" : "out_bytes below n * 3 * Ho * Wo * element size");
-    if (!in || !out || (reinterpret_cast<uintptr_t>(in) & 1u) || (reinterpret_cast<uintptr_t>(out) & (es - 1u)))
-        return reject(fn, "in / out missing or not aligned to their element size");
 
     std::lock_guard<std::mutex> lk(c->mu);
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = stream ? static_cast<hipStream_t>(stream) : c->stream;
     // (the division is in f32, as every step of the host side of the contract)
+    const float bsum = static_cast<float>(static_cast<int>(p->black[0]) + p->black[1] + p->black[2] + p->black[3]);
     const float inv = 1.0f / (p->white - 0.25f * bsum);
-    const float scale = mhc ? 0.0625f : 0.5f;
+    const float scale = P.mhc ? 0.0625f : 0.5f;
     std::vector<RgbCol> cols(static_cast<size_t>(ncolors));
     for (int i = 0; i < ncolors; i++) {
         for (int k = 0; k < 3; k++)
             cols[static_cast<size_t>(i)].k[k] = (colors[i].gain[k] * inv) * scale;
         std::memcpy(cols[static_cast<size_t>(i)].m, colors[i].m, sizeof(float) * 9);
     }
-    static const int shift_of[4] = {0, 3, 1, 2}; // MCRAW_CFA_* -> role shift: RGGB 0, BGGR 3, GRBG 1, GBRG 2
-    const int s = shift_of[p->cfa];
-    RgbKernel k = yv ? (yv->format == MCRAW_YUV_NV12 ? pick_yuv_kernel<PK_NV12>(p->algo, s) : pick_yuv_kernel<PK_P010>(p->algo, s))
-                  : d ? (d->dtype == MCRAW_DISP_U8 ? pick_kernel<PK_DISP8>(p->algo, s) : pick_kernel<PK_DISP16>(p->algo, s))
-                  : p->dtype == MCRAW_FLOAT_F32 ? pick_kernel<PK_F32>(p->algo, s)
-                  : p->dtype == MCRAW_FLOAT_F16 ? pick_kernel<PK_F16>(p->algo, s)
-                                                : pick_kernel<PK_BF16>(p->algo, s);
+    RgbKernel k = pick_kernel(P);
     RgbArgs A{};
     A.pitch = in_pitch;
     A.fstride = in_frame_stride;
     A.W = static_cast<uint32_t>(width);
     A.H = static_cast<uint32_t>(height);
-    A.Wo = static_cast<uint32_t>(Wo);
-    A.Ho = static_cast<uint32_t>(Ho);
-    A.invec = (reinterpret_cast<uintptr_t>(in) & 15u) == 0u && in_pitch % 8u == 0u && (n == 1 || in_frame_stride % 8u == 0u);
+    A.Wo = static_cast<uint32_t>(P.Wo);
+    A.Ho = static_cast<uint32_t>(P.Ho);
+    A.tilesX = P.tilesX;
+    A.units = P.units;
+    A.invec = P.invec;
     A.clip = (p->flags & MCRAW_FLOAT_CLIP) ? 1u : 0u;
     A.percol = ncolors > 1 ? 1u : 0u;
     if (d || yv) {
-        A.lut = lut;
-        A.lutn = 1u << lut_log2;
+        A.lut = d ? d->lut : yv->lut;
+        A.lutn = 1u << (d ? d->lut_log2 : yv->lut_log2);
         A.lutg = A.lutn > DISP_LDS_MAX ? 1u : 0u;
         A.hwc = d && d->layout == MCRAW_DISP_HWC ? 1u : 0u;
     }
@@ -784,31 +705,20 @@ static int demosaic_launch(const char *fn, mcraw_ctx *c, const mcraw_rgb *p, con
     }
     for (int i = 0; i < 4; i++)
         A.black[i] = p->black[i];
-    uint32_t blocks;
-    if (mhc) {
-        A.tilesX = static_cast<uint32_t>((width + MHC_TW - 1) / MHC_TW);
-        blocks = A.tilesX * static_cast<uint32_t>((height + MHC_TH - 1) / MHC_TH);
-    } else {
-        A.tilesX = static_cast<uint32_t>((Wo + 7u) / 8u);
-        // items: 8 output columns of an output row (YUV kinds: of an output row pair)
-        blocks = static_cast<uint32_t>((static_cast<size_t>(A.tilesX) * (yv ? Ho / 2u : Ho) + RGB_T - 1u) / RGB_T);
-    }
-    A.units = blocks;
-    const bool persistent = d || yv;
+    const bool persistent = has_lut(P.kind);
     const uint32_t resident = persistent ? resident_groups(c->device, k) : 0u;
-    const int kid = mhc ? MCRAW_KRGB_MHC : MCRAW_KRGB_BIN2;
+    const int kid = P.mhc ? MCRAW_KRGB_MHC : MCRAW_KRGB_BIN2;
     const int piece = A.percol ? RGB_MAXF : 65535;
-    const size_t out_frame = frame_samples * es;
     for (int f0 = 0; f0 < n; f0 += piece) {
         const int nf = std::min(piece, n - f0);
         A.in = in + static_cast<size_t>(f0) * in_frame_stride;
-        A.out = static_cast<uint8_t *>(out) + static_cast<size_t>(f0) * out_frame;
+        A.out = static_cast<uint8_t *>(out) + static_cast<size_t>(f0) * P.out_frame;
         A.nf = static_cast<uint32_t>(nf);
         for (int i = 0; i < (A.percol ? nf : 1); i++)
             A.col[i] = cols[static_cast<size_t>(A.percol ? f0 + i : 0)];
-        // display and YUV kinds: a persistent grid of at most what the device holds at once, over blocks x nf units of work
-        const dim3 grid = persistent ? dim3(static_cast<uint32_t>(std::min<uint64_t>(static_cast<uint64_t>(blocks) * nf, resident)))
-                            : dim3(blocks, static_cast<uint32_t>(nf));
+        // display and YUV kinds: a persistent grid of at most what the device holds at once, over units x nf units of work
+        const dim3 grid = persistent ? dim3(static_cast<uint32_t>(std::min<uint64_t>(static_cast<uint64_t>(P.units) * nf, resident)))
+                            : dim3(P.units, static_cast<uint32_t>(nf));
         KTimer kt(c, kid, st);
         hipLaunchKernelGGL(k, grid, dim3(RGB_T), 0, st, A);
         HIP_TRY(hipGetLastError());

@@ -1,0 +1,153 @@
+// mcraw_rgb_args.h -- what the three demosaic entry points (mcraw_demosaic_batch, _display_batch, _yuv_batch) decide about a
+// call before anything is launched: accept, reject or no-op, and on acceptance the plan of the launch (output sizes, launch
+// geometry, CFA role shift, kernel kind).  No HIP in here, so that tests/cpp/rgb_args_check.cpp can drive it on any machine.
+// The input batch is a MosaicBatch (mcraw_mosaic_args.h): its base, alignment, pitch and frame-stride checks and its 16-byte
+// grid are that header's.
+#pragma once
+#include <cmath>
+#include <cstdlib>
+
+#include "../../include/mcraw_hip.h"
+#include "mcraw_mosaic_args.h"
+
+namespace mcraw {
+
+constexpr uint32_t RGB_T = 256;  // threads per workgroup
+constexpr uint32_t MHC_TW = 256; // tile columns: 32 lanes x 8
+constexpr uint32_t MHC_TH = 32;  // tile rows: 8 row pairs x 2 passes
+
+// Output kinds.  The float kinds are mcraw_plan.h's PK_F32 / PK_F16 / PK_BF16 (mcraw_rgb.hip asserts that they agree).
+constexpr int rgb_float_kind(uint32_t dtype) { return 31 + static_cast<int>(dtype); } // MCRAW_FLOAT_* -> PK_F32 / PK_F16 / PK_BF16
+constexpr int PK_DISP8 = 48, PK_DISP16 = 49; // display: uint8 / uint16 through a transfer-curve LUT
+// Y'CbCr 4:2:0: a Y plane, then interleaved (Cb, Cr) rows; uint8, or uint16 holding a 10-bit code << 6
+constexpr int PK_NV12 = 50, PK_P010 = 51;
+constexpr bool is_disp(int pk) { return pk == PK_DISP8 || pk == PK_DISP16; }
+constexpr bool is_yuv(int pk) { return pk == PK_NV12 || pk == PK_P010; }
+constexpr bool has_lut(int pk) { return is_disp(pk) || is_yuv(pk); } // persistent grid, LUT staged per workgroup
+constexpr uint32_t out_es(int pk) { return pk == rgb_float_kind(MCRAW_FLOAT_F32) ? 4u : (pk == PK_DISP8 || pk == PK_NV12) ? 1u : 2u; }
+
+// The launch of an accepted call.
+struct RgbPlan {
+    bool noop;            // an empty batch: nothing below is set, nothing is launched
+    int kind;             // PK_*
+    int shift;            // RGGB role of CFA position p: p ^ shift
+    bool mhc;             // MCRAW_RGB_MHC, else BIN2
+    bool invec;           // every 8-column piece of every input row lies on the 16-byte grid
+    size_t es, Wo, Ho;    // bytes per output sample; output size
+    size_t frame_samples; // samples per frame: 3 planes, or a Y plane and half of one for the (Cb, Cr) rows
+    size_t out_frame;     // bytes per output frame
+    uint32_t tilesX;      // MHC: tiles per row band; BIN2: groups of 8 output columns per output row
+    uint32_t units;       // per frame: tiles (MHC), or workgroups of 256 items (BIN2; YUV kinds: an item is a row pair)
+};
+
+inline bool finite_all(const float *v, int n)
+{
+    for (int i = 0; i < n; i++)
+        if (!std::isfinite(v[i]))
+            return false;
+    return true;
+}
+
+// Why the call is rejected, or nullptr with `plan` filled.  d: the display stage, yv: the YUV stage (never both); neither:
+// the float entry.  Addresses are only looked at as numbers.
+inline const char *rgb_check(const mcraw_rgb *p, const mcraw_display *d, const mcraw_yuv *yv, const mcraw_rgb_color *colors,
+                             int ncolors, const uint16_t *in, size_t in_pitch, size_t in_frame_stride, int width, int height, int n,
+                             const void *out, size_t out_bytes, RgbPlan &plan)
+{
+    plan = RgbPlan{};
+    if (!p || n < 0)
+        return "bad arguments";
+    if (n == 0) {
+        plan.noop = true;
+        return nullptr;
+    }
+    if (width < 4 || height < 4 || (width & 1) || (height & 1) || width > 65536 || height > 65536)
+        return "width and height must be even, 4 .. 65536";
+    const MosaicBatch I(in, in_pitch, in_frame_stride, static_cast<size_t>(n), width, height);
+    if (const char *why = I.check())
+        return why;
+    if (p->algo != MCRAW_RGB_MHC && p->algo != MCRAW_RGB_BIN2)
+        return "unknown algo";
+    const uint16_t *lut = d ? d->lut : yv ? yv->lut : nullptr;
+    const uint32_t lut_log2 = d ? d->lut_log2 : yv ? yv->lut_log2 : 0u;
+    if (d || yv) {
+        if (p->dtype != 0u || p->flags != 0u)
+            return "p->dtype and p->flags must be 0 (the display / YUV stage decides the output)";
+        if (lut_log2 < 8u || lut_log2 > 16u)
+            return "lut_log2 must be 8 .. 16";
+        if (!lut || (reinterpret_cast<uintptr_t>(lut) & 15u))
+            return "lut missing or not 16-byte aligned";
+    }
+    if (d) {
+        if (d->dtype != MCRAW_DISP_U8 && d->dtype != MCRAW_DISP_U16)
+            return "unknown display dtype";
+        if (d->layout != MCRAW_DISP_CHW && d->layout != MCRAW_DISP_HWC)
+            return "unknown display layout";
+        if (d->reserved != 0u)
+            return "reserved must be 0";
+        plan.kind = d->dtype == MCRAW_DISP_U8 ? PK_DISP8 : PK_DISP16;
+    } else if (yv) {
+        if (yv->format != MCRAW_YUV_NV12 && yv->format != MCRAW_YUV_P010)
+            return "unknown YUV format";
+        if (yv->reserved != 0u)
+            return "reserved must be 0";
+        if (yv->in_bits < 8u || yv->in_bits > 16u)
+            return "in_bits must be 8 .. 16";
+        if (yv->sh < 1u || yv->sh > 24u)
+            return "sh must be 1 .. 24";
+        const int32_t top = yv->format == MCRAW_YUV_NV12 ? 255 : 1023;
+        if (yv->y_off < 0 || yv->y_off > top || yv->c_off < 0 || yv->c_off > top)
+            return "y_off and c_off must be 0 .. 2^bits - 1";
+        // no int32 sum can wrap: 4 * (2^in_bits - 1) * (|c0| + |c1| + |c2|) + 2^(sh + 1) < 2^31 for every row
+        const int32_t *rows[3] = {yv->cy, yv->cb, yv->cr};
+        for (const int32_t *r : rows) {
+            const int64_t mag = std::llabs(static_cast<int64_t>(r[0])) + std::llabs(static_cast<int64_t>(r[1])) +
+                                std::llabs(static_cast<int64_t>(r[2]));
+            if (4 * ((int64_t{1} << yv->in_bits) - 1) * mag + (int64_t{1} << (yv->sh + 1u)) >= (int64_t{1} << 31))
+                return "coefficients could overflow int32: 4 * (2^in_bits - 1) * (|c0| + |c1| + |c2|) + 2^(sh + 1) >= 2^31";
+        }
+        plan.kind = yv->format == MCRAW_YUV_NV12 ? PK_NV12 : PK_P010;
+    } else {
+        if (p->dtype != MCRAW_FLOAT_F32 && p->dtype != MCRAW_FLOAT_F16 && p->dtype != MCRAW_FLOAT_BF16)
+            return "unknown dtype";
+        plan.kind = rgb_float_kind(p->dtype);
+    }
+    if (p->cfa > MCRAW_CFA_GBRG)
+        return "unknown cfa";
+    if (p->flags & ~MCRAW_FLOAT_CLIP)
+        return "unknown flag";
+    const float bsum = static_cast<float>(static_cast<int>(p->black[0]) + p->black[1] + p->black[2] + p->black[3]);
+    if (!std::isfinite(p->white) || !(p->white > 0.25f * bsum))
+        return "white must be finite and above the mean black level";
+    if (!colors || (ncolors != 1 && ncolors != n))
+        return "ncolors must be 1 or n";
+    for (int i = 0; i < ncolors; i++)
+        if (!finite_all(colors[i].gain, 3) || !finite_all(colors[i].m, 9))
+            return "non-finite gain or matrix entry";
+    plan.mhc = p->algo == MCRAW_RGB_MHC;
+    plan.es = out_es(plan.kind);
+    plan.Wo = plan.mhc ? static_cast<size_t>(width) : static_cast<size_t>(width) / 2u;
+    plan.Ho = plan.mhc ? static_cast<size_t>(height) : static_cast<size_t>(height) / 2u;
+    if (yv && ((plan.Ho | plan.Wo) & 1u))
+        return "4:2:0 needs an even Ho and Wo (BIN2: width and height multiples of 4)";
+    plan.frame_samples = yv ? plan.Ho * plan.Wo / 2u * 3u : 3u * plan.Ho * plan.Wo;
+    if (out_bytes / plan.es / plan.frame_samples < static_cast<size_t>(n))
+        return yv ? "out_bytes below n * Ho * Wo * 3 / 2 * sample size" : "out_bytes below n * 3 * Ho * Wo * element size";
+    if (!out || (reinterpret_cast<uintptr_t>(out) & (plan.es - 1u)))
+        return "in / out missing or not aligned to their element size";
+    plan.out_frame = plan.frame_samples * plan.es;
+    plan.invec = I.on_grid();
+    constexpr int shift_of[4] = {0, 3, 1, 2}; // MCRAW_CFA_* -> role shift: RGGB 0, BGGR 3, GRBG 1, GBRG 2
+    plan.shift = shift_of[p->cfa];
+    if (plan.mhc) {
+        plan.tilesX = (static_cast<uint32_t>(width) + MHC_TW - 1u) / MHC_TW;
+        plan.units = plan.tilesX * ((static_cast<uint32_t>(height) + MHC_TH - 1u) / MHC_TH);
+    } else {
+        plan.tilesX = static_cast<uint32_t>((plan.Wo + 7u) / 8u);
+        // items: 8 output columns of an output row (YUV kinds: of an output row pair)
+        plan.units = static_cast<uint32_t>((static_cast<size_t>(plan.tilesX) * (yv ? plan.Ho / 2u : plan.Ho) + RGB_T - 1u) / RGB_T);
+    }
+    return nullptr;
+}
+
+} // namespace mcraw

@@ -12,36 +12,14 @@ import _display_ref as D
 import _libs as L
 import _rgb_ref as R
 import motioncam_decoder_amd as M
+from _demosaic_gpu import CFAS, DEV, GUARD, SENT, SRGBISH, raw_call
+from _demosaic_gpu import dev16 as _lut_dev, frames as _frames, mosaic as _mosaic, rand_lut as _rand_lut, rgb_color as _color
+from _demosaic_gpu import rgb_params as _params, to_np as _np
 
 pytestmark = pytest.mark.gpu
 
-DEV = torch.device("cuda:0")
-CFAS = ("rggb", "bggr", "grbg", "gbrg")
 TD = {"u8": torch.uint8, "u16": torch.uint16}
 ES = {"u8": 1, "u16": 2}
-SENT = 0xA5
-GUARD = 4096
-SRGBISH = np.array([[1.7, -0.5, -0.2], [-0.25, 1.4, -0.15], [0.05, -0.45, 1.4]], np.float32)
-
-
-def _np(t):
-    """uint8 / uint16 tensor -> numpy (torch has few CUDA kernels for uint16: go through int16)."""
-    a = t.detach()
-    if a.dtype == torch.uint16:
-        return a.view(torch.int16).cpu().numpy().view(np.uint16)
-    return a.cpu().numpy()
-
-
-def _lut_dev(lut):
-    return torch.from_numpy(np.ascontiguousarray(lut, dtype=np.uint16).view(np.int16)).to(DEV).view(torch.uint16)
-
-
-def _mosaic(rng, h, w, nbits):
-    return rng.integers(0, 1 << nbits, size=(h, w), dtype=np.uint16)
-
-
-def _rand_lut(rng, size):
-    return rng.integers(0, 1 << 16, size=size, dtype=np.uint16)
 
 
 def _shape(algo, h, w, layout, n=None):
@@ -163,39 +141,14 @@ def test_inf_and_nan_outputs_index_top_and_zero(gpu_ctx):
         assert np.array_equal(got, want)
 
 
-def _params(algo="mhc", white=4095.0, black=(0, 0, 0, 0), cfa="rggb", dtype=0, flags=0):
-    p = M.RgbParams()
-    p.algo = {"mhc": 1, "bin2": 2}[algo]
-    p.dtype, p.flags, p.cfa = dtype, flags, R.CFA_CODE[cfa]
-    for i in range(4):
-        p.black[i] = black[i]
-    p.white = white
-    return p
+def _raw(ctx, prm, d, *args, **kw):
+    return raw_call(ctx, "mcraw_demosaic_display_batch", prm, d, *args, **kw)
 
 
 def _disp(lut_ptr, dtype=1, layout=1, log2=12, reserved=0):
     d = M.Display()
     d.dtype, d.layout, d.lut_log2, d.reserved, d.lut = dtype, layout, log2, reserved, lut_ptr
     return d
-
-
-def _color(gain=(1, 1, 1), m=None):
-    c = M.RgbColor()
-    m = np.eye(3) if m is None else np.asarray(m)
-    for i in range(3):
-        c.gain[i] = float(gain[i])
-    for i in range(9):
-        c.m[i] = float(m.ravel()[i])
-    return c
-
-
-def _raw(ctx, prm, d, cols, ncol, in_ptr, pitch, fstride, w, h, n, out_ptr, out_bytes, stream=None):
-    arr = (M.RgbColor * max(ncol, 1))()
-    for i in range(min(ncol, len(cols))):
-        arr[i] = cols[i]
-    return M.load().mcraw_demosaic_display_batch(ctx._h, C.byref(prm) if prm is not None else None,
-                                                 C.byref(d) if d is not None else None, arr, ncol, C.c_void_p(in_ptr), pitch,
-                                                 fstride, w, h, n, C.c_void_p(out_ptr), out_bytes, C.c_void_p(stream))
 
 
 def test_rejections_write_nothing(gpu_ctx):
@@ -280,17 +233,6 @@ def test_same_lut_pointer_new_contents_between_queued_calls(gpu_ctx, size):
         got = _np(o)
         for i in range(n):
             assert np.array_equal(got[i], D.display_ref(imgs[i], algo, 4095.0, luts[k], "u16", "hwc", gain=(1.5, 1.0, 1.3))), k
-
-
-def _frames(rng, shapes, typ):
-    items = []
-    for (w, h) in shapes:
-        img = L.natural_image_np(w, h, 12, 12.0, int(rng.integers(1 << 30)))
-        buf = L.encode7(img) if typ == 7 else L.encode6(img)
-        ret, want = (L.oracle_decode7 if typ == 7 else L.oracle_decode6)(buf, w, h)
-        assert ret == w * h
-        items.append((buf, want))
-    return items
 
 
 @pytest.mark.parametrize("typ", (7, 6))

@@ -11,17 +11,14 @@ import torch
 import _libs as L
 import _rgb_ref as R
 import motioncam_decoder_amd as M
+from _demosaic_gpu import CFAS, DEV, GUARD, SENT, SRGBISH, raw_call, rgb_params
+from _demosaic_gpu import frames as _frames, mosaic as _mosaic, rgb_color as _color
 
 pytestmark = pytest.mark.gpu
 
-DEV = torch.device("cuda:0")
 DTYPES = ("f32", "f16", "bf16")
 TD = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}
 ES = {"f32": 4, "f16": 2, "bf16": 2}
-CFAS = ("rggb", "bggr", "grbg", "gbrg")
-SENT = 0xA5
-GUARD = 4096
-SRGBISH = np.array([[1.7, -0.5, -0.2], [-0.25, 1.4, -0.15], [0.05, -0.45, 1.4]], np.float32)
 
 
 def _bits(t, dtype):
@@ -31,43 +28,16 @@ def _bits(t, dtype):
     return a.numpy().view(np.uint32 if dtype == "f32" else np.uint16)
 
 
-def _mosaic(rng, h, w, nbits):
-    return rng.integers(0, 1 << nbits, size=(h, w), dtype=np.uint16)
+def _raw_call(ctx, prm, *args, **kw):
+    return raw_call(ctx, "mcraw_demosaic_batch", prm, None, *args, staged=False, **kw)
+
+
+def _params(algo="mhc", dtype="f16", white=4095.0, black=(0, 0, 0, 0), cfa="rggb", clip=False):
+    return rgb_params(algo, white, black, cfa, {"f32": 1, "f16": 2, "bf16": 3}[dtype], 1 if clip else 0)
 
 
 def _ref(img, algo, dtype, white, black, cfa, gain, matrix, clip):
     return R.ref_bits(img, algo, dtype, white, black=black, cfa=cfa, gain=gain, matrix=matrix, clip=clip)
-
-
-def _raw_call(ctx, prm, cols, ncol, in_ptr, pitch, fstride, w, h, n, out_ptr, out_bytes, stream=None):
-    lib = M.load()
-    arr = (M.RgbColor * max(ncol, 1))()
-    for i in range(min(ncol, len(cols))):
-        arr[i] = cols[i]
-    return lib.mcraw_demosaic_batch(ctx._h, C.byref(prm) if prm is not None else None, arr, ncol, C.c_void_p(in_ptr), pitch,
-                                    fstride, w, h, n, C.c_void_p(out_ptr), out_bytes, C.c_void_p(stream))
-
-
-def _params(algo="mhc", dtype="f16", white=4095.0, black=(0, 0, 0, 0), cfa="rggb", clip=False):
-    p = M.RgbParams()
-    p.algo = {"mhc": 1, "bin2": 2}[algo]
-    p.dtype = {"f32": 1, "f16": 2, "bf16": 3}[dtype]
-    p.flags = 1 if clip else 0
-    p.cfa = R.CFA_CODE[cfa]
-    for i in range(4):
-        p.black[i] = black[i]
-    p.white = white
-    return p
-
-
-def _color(gain=(1, 1, 1), m=None):
-    c = M.RgbColor()
-    m = np.eye(3) if m is None else np.asarray(m)
-    for i in range(3):
-        c.gain[i] = float(gain[i])
-    for i in range(9):
-        c.m[i] = float(m.ravel()[i])
-    return c
 
 
 @pytest.mark.parametrize("clip", (False, True))
@@ -207,17 +177,6 @@ def test_queued_batches_keep_their_colours(gpu_ctx, two_streams):
         for i in range(n):
             want = _ref(imgs[i], "mhc", "f32", 4095.0, (0, 0, 0, 0), "rggb", g[i], m[i], False)
             assert np.array_equal(_bits(o[i], "f32"), want)
-
-
-def _frames(rng, shapes, typ):
-    items = []
-    for (w, h) in shapes:
-        img = L.natural_image_np(w, h, 12, 12.0, int(rng.integers(1 << 30)))
-        buf = L.encode7(img) if typ == 7 else L.encode6(img)
-        ret, want = (L.oracle_decode7 if typ == 7 else L.oracle_decode6)(buf, w, h)
-        assert ret == w * h
-        items.append((buf, want))
-    return items
 
 
 @pytest.mark.parametrize("typ", (7, 6))

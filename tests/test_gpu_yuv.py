@@ -13,39 +13,18 @@ import _libs as L
 import _rgb_ref as R
 import _yuv_ref as Y
 import motioncam_decoder_amd as M
+from _demosaic_gpu import CFAS, DEV, GUARD, SENT, SRGBISH, raw_call
+from _demosaic_gpu import dev16 as _dev16, frames as _frames, mosaic as _mosaic, rand_lut as _rand_lut, rgb_color as _color
+from _demosaic_gpu import rgb_params as _params, to_np as _np
 
 pytestmark = pytest.mark.gpu
 
-DEV = torch.device("cuda:0")
-CFAS = ("rggb", "bggr", "grbg", "gbrg")
 TD = {"nv12": torch.uint8, "p010": torch.uint16}
 ES = {"nv12": 1, "p010": 2}
 FMT_CODE = {"nv12": 1, "p010": 2}
 DEF_IN = {"nv12": 12, "p010": 16}
-SENT = 0xA5
-GUARD = 4096
-SRGBISH = np.array([[1.7, -0.5, -0.2], [-0.25, 1.4, -0.15], [0.05, -0.45, 1.4]], np.float32)
 GEOMS = {"mhc": ((66, 18), (64, 16), (40, 12), (1002, 70), (520, 34)),
          "bin2": ((68, 20), (64, 16), (40, 12), (1004, 72), (520, 36))}
-
-
-def _np(t):
-    a = t.detach()
-    if a.dtype == torch.uint16:
-        return a.view(torch.int16).cpu().numpy().view(np.uint16)
-    return a.cpu().numpy()
-
-
-def _dev16(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint16).view(np.int16)).to(DEV).view(torch.uint16)
-
-
-def _mosaic(rng, h, w, nbits):
-    return rng.integers(0, 1 << nbits, size=(h, w), dtype=np.uint16)
-
-
-def _rand_lut(rng, size):
-    return rng.integers(0, 1 << 16, size=size, dtype=np.uint16)
 
 
 def _rand_coef(rng, fmt, in_bits):
@@ -68,14 +47,8 @@ def _shape(algo, h, w, n=None):
     return s if n is None else (n,) + s
 
 
-def _params(algo="mhc", white=4095.0, black=(0, 0, 0, 0), cfa="rggb", dtype=0, flags=0):
-    p = M.RgbParams()
-    p.algo = {"mhc": 1, "bin2": 2}[algo]
-    p.dtype, p.flags, p.cfa = dtype, flags, R.CFA_CODE[cfa]
-    for i in range(4):
-        p.black[i] = black[i]
-    p.white = white
-    return p
+def _raw(ctx, prm, y, *args, **kw):
+    return raw_call(ctx, "mcraw_demosaic_yuv_batch", prm, y, *args, **kw)
 
 
 def _yuv(lut_ptr, fmt="nv12", log2=12, in_bits=8, coef=None, reserved=0, code=None):
@@ -86,25 +59,6 @@ def _yuv(lut_ptr, fmt="nv12", log2=12, in_bits=8, coef=None, reserved=0, code=No
         y.cy[i], y.cb[i], y.cr[i] = cy[i], cb[i], cr[i]
     y.reserved, y.lut = reserved, lut_ptr
     return y
-
-
-def _color(gain=(1, 1, 1), m=None):
-    c = M.RgbColor()
-    m = np.eye(3) if m is None else np.asarray(m)
-    for i in range(3):
-        c.gain[i] = float(gain[i])
-    for i in range(9):
-        c.m[i] = float(m.ravel()[i])
-    return c
-
-
-def _raw(ctx, prm, y, cols, ncol, in_ptr, pitch, fstride, w, h, n, out_ptr, out_bytes, stream=None):
-    arr = (M.RgbColor * max(ncol, 1))()
-    for i in range(min(ncol, len(cols))):
-        arr[i] = cols[i]
-    return M.load().mcraw_demosaic_yuv_batch(ctx._h, C.byref(prm) if prm is not None else None,
-                                             C.byref(y) if y is not None else None, arr, ncol, C.c_void_p(in_ptr), pitch,
-                                             fstride, w, h, n, C.c_void_p(out_ptr), out_bytes, C.c_void_p(stream))
 
 
 def _call_raw(ctx, t, algo, fmt, lut_t, coef, in_bits, white, black, cfa, gain, matrix, out):
@@ -348,17 +302,6 @@ def test_python_rejects_odd_output_for_bin2(gpu_ctx):
         gpu_ctx.demosaic_yuv(torch.zeros((8, 8), dtype=torch.int16, device=DEV).view(torch.uint16), white=4095.0, fmt="i420")
     with pytest.raises(ValueError):  # a built-in curve needs a depth transfer_lut makes
         gpu_ctx.demosaic_yuv(torch.zeros((8, 8), dtype=torch.int16, device=DEV).view(torch.uint16), white=4095.0, in_bits=11)
-
-
-def _frames(rng, shapes, typ):
-    items = []
-    for (w, h) in shapes:
-        img = L.natural_image_np(w, h, 12, 12.0, int(rng.integers(1 << 30)))
-        buf = L.encode7(img) if typ == 7 else L.encode6(img)
-        ret, want = (L.oracle_decode7 if typ == 7 else L.oracle_decode6)(buf, w, h)
-        assert ret == w * h
-        items.append((buf, want))
-    return items
 
 
 @pytest.mark.parametrize("typ", (7, 6))

@@ -1,15 +1,63 @@
-"""A second build of the library beside the product's, for the stage benches' --alt-lib (bench_shade / stats / fixpix / denoise /
-merge .py): python -m motioncam_decoder_amd.build variant PATH -D... makes one, and so does a build of another commit.  AltLib
-loads it with ctypes, makes a context of its own in it, and has one method per stage entry point, each taking contiguous
-(N, H, W) uint16 CUDA tensors and the torch stream to queue on."""
+"""A second build of the library beside the product's, for the benches' --alt-lib (bench_shade / stats / fixpix / denoise /
+merge / rgb / display / yuv .py): python -m motioncam_decoder_amd.build variant PATH -D... makes one, and so does a build of
+another commit.  AltLib loads it with ctypes, makes a context of its own in it, and has one method per stage entry point, each
+taking contiguous (N, H, W) uint16 CUDA tensors and the torch stream to queue on.  Also what the demosaic benches build alike:
+their images and device inputs."""
 import ctypes as C
 import os
 import sys
+
+import numpy as np
+import torch
 
 import motioncam_decoder_amd as M
 
 _MOSAIC_IN = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int]  # in, pitch, frame stride, width, height, n
 _MOSAIC_OUT = [C.c_void_p, C.c_size_t, C.c_size_t]                            # out, pitch, frame stride
+_DEMOSAIC = [C.POINTER(M.RgbColor), C.c_int] + _MOSAIC_IN + [C.c_void_p, C.c_size_t, C.c_void_p]  # colours, in, out, bytes, stream
+
+
+def turn_order(forms, rep):
+    """The forms of rep `rep`: on odd reps every *_alt form runs in front of its counterpart instead of behind it, so that neither
+    build always follows a run of the same kernel on the same buffers (warm TLBs, a settled clock)."""
+    if rep % 2 == 0:
+        return list(forms)
+    order = []
+    for f in forms:
+        if f.endswith("_alt"):
+            order.insert(len(order) - 1, f)
+        else:
+            order.append(f)
+    return order
+
+
+def bench_images(content, w, h, distinct, rng):
+    """The `distinct` 12-bit images of a demosaic bench: "smooth" (natural images) or "noise"."""
+    import _libs as L
+    if content == "smooth":
+        return [L.natural_image_np(w, h, 12, 12.0, 100 + s) for s in range(distinct)]
+    return [rng.integers(0, 4096, size=(h, w), dtype=np.uint16) for _ in range(distinct)]
+
+
+def bench_mosaics(dev, imgs, n):
+    """`imgs` in turn as an (n, H, W) uint16 tensor on `dev`."""
+    h, w = imgs[0].shape
+    mos = torch.empty((n, h, w), dtype=torch.uint16, device=dev)
+    for i in range(n):
+        mos.view(torch.int16)[i].copy_(torch.from_numpy(imgs[i % len(imgs)].view(np.int16)))
+    return mos
+
+
+def bench_encoded(dev, imgs, n, encode):
+    """`imgs` in turn, encoded, resident on `dev`: (the tensor that holds them, [(pointer, length)], lengths)."""
+    bufs = [encode(im) for im in imgs]
+    ins = torch.zeros((n, max(len(b) for b in bufs) + 256), dtype=torch.uint8, device=dev)
+    lens = []
+    for i in range(n):
+        b = bufs[i % len(bufs)]
+        ins[i, :len(b)].copy_(torch.from_numpy(b))
+        lens.append(len(b))
+    return ins, [(ins[i].data_ptr(), lens[i]) for i in range(n)], lens
 
 
 class AltLib:
@@ -23,6 +71,11 @@ class AltLib:
                            ("mcraw_merge_batch", M.Merge)):
             getattr(self.lib, fn).argtypes = [C.c_void_p, C.POINTER(struct)] + _MOSAIC_IN + _MOSAIC_OUT + [C.c_void_p]
         self.lib.mcraw_stats_batch.argtypes = [C.c_void_p, C.POINTER(M.Stats)] + _MOSAIC_IN + [C.c_void_p, C.c_size_t, C.c_void_p]
+        self.lib.mcraw_demosaic_batch.argtypes = [C.c_void_p, C.POINTER(M.RgbParams)] + _DEMOSAIC
+        self.lib.mcraw_demosaic_display_batch.argtypes = [C.c_void_p, C.POINTER(M.RgbParams), C.POINTER(M.Display)] + _DEMOSAIC
+        self.lib.mcraw_demosaic_yuv_batch.argtypes = [C.c_void_p, C.POINTER(M.RgbParams), C.POINTER(M.Yuv)] + _DEMOSAIC
+        self.lib.mcraw_ctx_profile.argtypes = [C.c_void_p, C.c_int]
+        self.lib.mcraw_ctx_kernel_ms.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_int]
         self.h = C.c_void_p()
         if self.lib.mcraw_ctx_create(0, C.byref(self.h)) != 0:
             sys.exit("alt-lib: %s" % self.lib.mcraw_last_error().decode())
@@ -74,6 +127,50 @@ class AltLib:
                                         recs.numel(), C.c_void_p(stream.cuda_stream))
         assert rc == 0, self.lib.mcraw_last_error().decode()
         return M.FrameStats(recs, bins, shift)
+
+    def _demosaic_call(self, fn, prm, stage, mos, out, stream, gain, matrix):
+        n, h, w = mos.shape
+        cols, nc = M._rgb_colors(gain, matrix, n, fn)
+        structs = (C.byref(prm),) if stage is None else (C.byref(prm), C.byref(stage))
+        rc = getattr(self.lib, fn)(self.h, *structs, cols, nc, C.c_void_p(mos.data_ptr()), w, h * w, w, h, n,
+                                   C.c_void_p(out.data_ptr()), out.numel() * out.element_size(), C.c_void_p(stream.cuda_stream))
+        assert rc == 0, self.lib.mcraw_last_error().decode()
+
+    def demosaic(self, mos, out, stream, algo, dtype, white, black, gain=None, matrix=None, cfa="rggb", clip=False):
+        prm = M._rgb_params(algo, M._float_code(dtype), M.FLOAT_CLIP if clip else 0, cfa, white, black)
+        self._demosaic_call("mcraw_demosaic_batch", prm, None, mos, out, stream, gain, matrix)
+
+    def demosaic_display(self, mos, out, stream, algo, lut, layout, white, black, gain=None, matrix=None, cfa="rggb"):
+        """lut: a 1-D uint16 CUDA tensor; out's dtype (uint8 / uint16) decides the display dtype."""
+        d = M.Display()
+        d.dtype, d.layout = (M.DISP_U8 if out.dtype == torch.uint8 else M.DISP_U16), M._DISP_LAYOUTS[layout]
+        d.lut_log2, d.reserved, d.lut = int(lut.numel()).bit_length() - 1, 0, lut.data_ptr()
+        self._demosaic_call("mcraw_demosaic_display_batch", M._rgb_params(algo, 0, 0, cfa, white, black), d, mos, out, stream, gain, matrix)
+
+    def demosaic_yuv(self, mos, out, stream, algo, lut, fmt, in_bits, white, black, gain=None, matrix=None, cfa="rggb",
+                     standard="bt709", range="limited"):
+        """lut: a 1-D uint16 CUDA tensor of in_bits entries' width."""
+        fcode, bits, _ = M._YUV_FORMATS[fmt]
+        cy, cb, cr, sh, y_off, c_off = M.yuv_matrix(standard, range, bits, in_bits)
+        y = M.Yuv()
+        y.format, y.lut_log2, y.in_bits, y.sh, y.y_off, y.c_off = fcode, int(lut.numel()).bit_length() - 1, in_bits, sh, y_off, c_off
+        for i in (0, 1, 2):
+            y.cy[i], y.cb[i], y.cr[i] = cy[i], cb[i], cr[i]
+        y.reserved, y.lut = 0, lut.data_ptr()
+        self._demosaic_call("mcraw_demosaic_yuv_batch", M._rgb_params(algo, 0, 0, cfa, white, black), y, mos, out, stream, gain, matrix)
+
+    def profile(self, only):
+        """Bracket the launches of the kernels named in `only` with events (none: off), as Context.profile."""
+        mode = 0
+        for name in only:
+            mode |= 2 << M._kernel_id(name)
+        self.lib.mcraw_ctx_profile(self.h, mode)
+
+    def kernel_ms(self, name, reset=False):
+        ms, n = C.c_double(), C.c_int()
+        rc = self.lib.mcraw_ctx_kernel_ms(self.h, M._kernel_id(name), C.byref(ms), C.byref(n), 1 if reset else 0)
+        assert rc == 0, rc
+        return ms.value, n.value
 
     def close(self):
         self.lib.mcraw_ctx_destroy(self.h)

@@ -6,7 +6,10 @@ fraction of the 8 TB/s peak.  240 UHD 12-bit frames, smooth (natural images) and
 by rep in ONE process.  Frame 0 of every form is checked against the numpy reference.  Appends to
 profiles/display_bench.jsonl.
 
-    python tools/bench_display.py [--reps 7] [--frames 240] [--content smooth,noise]
+    python tools/bench_display.py [--reps 7] [--frames 240] [--content smooth,noise] [--alt-lib PATH]
+
+--alt-lib: another build of the library (of another commit, say): its display forms (*_alt) take turns with the others, in a
+context of its own, and are checked against the same reference.
 """
 import argparse
 import json
@@ -22,6 +25,7 @@ import _display_ref as D
 import _libs as L
 import _rgb_ref as R
 import motioncam_decoder_amd as M
+from altlib import AltLib, bench_encoded, bench_images, bench_mosaics, turn_order
 
 PEAK = 8e12
 W, H = 3840, 2160
@@ -50,35 +54,25 @@ def torch_srgb_u8_hwc(lin):
     return torch.round(y * 255.0).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
 
 
-def run(ctx, content, n, reps):
+def run(ctx, alt, content, n, reps):
     dev = torch.device("cuda:0")
-    rng = np.random.default_rng(7)
-    if content == "smooth":
-        imgs = [L.natural_image_np(W, H, 12, 12.0, 100 + s) for s in range(DISTINCT)]
-    else:
-        imgs = [rng.integers(0, 4096, size=(H, W), dtype=np.uint16) for _ in range(DISTINCT)]
-    mos = torch.empty((n, H, W), dtype=torch.uint16, device=dev)
-    for i in range(n):
-        mos.view(torch.int16)[i].copy_(torch.from_numpy(imgs[i % DISTINCT].view(np.int16)))
+    imgs = bench_images(content, W, H, DISTINCT, np.random.default_rng(7))
+    mos = bench_mosaics(dev, imgs, n)
     forms = [f for f in FORMS if content == "smooth" or FORMS[f][0] != "decode"]
-    inputs, inb = None, 0
-    if any(FORMS[f][0] == "decode" for f in forms):
-        bufs = [L.encode7(im) for im in imgs]
-        stride = max(len(b) for b in bufs) + 256
-        ins = torch.zeros((n, stride), dtype=torch.uint8, device=dev)
-        lens = []
-        for i in range(n):
-            b = bufs[i % DISTINCT]
-            ins[i, :len(b)].copy_(torch.from_numpy(b))
-            lens.append(len(b))
-        inputs = [(ins[i].data_ptr(), lens[i]) for i in range(n)]
+    if alt:  # (the alt library's display forms, each behind its counterpart)
+        forms = [g for f in forms for g in ([f, f + "_alt"] if FORMS[f][0] == "display" else [f])]
+    ins, inputs, inb = None, None, 0
+    if any(FORMS[f.replace("_alt", "")][0] == "decode" for f in forms):
+        ins, inputs, lens = bench_encoded(dev, imgs, n, L.encode7)
         inb = sum(lens)
     out = torch.empty(n * 3 * W * H * 2, dtype=torch.uint8, device=dev)  # room for the largest form (f16 / u16 MHC)
     stream = torch.cuda.Stream()
     lut16 = M.transfer_lut("srgb", 65536, 16)
+    to_dev = lambda a: torch.from_numpy(a.view(np.int16)).to(dev).view(torch.uint16)
+    alt_luts = {4096: to_dev(M.transfer_lut("srgb", 4096, 8)), 65536: to_dev(lut16)} if alt else None
 
     def out_view(f):
-        kind, algo, dt, layout, _ = FORMS[f]
+        kind, algo, dt, layout, _ = FORMS[f.replace("_alt", "")]
         ho, wo = (H, W) if algo == "mhc" else (H // 2, W // 2)
         shape = (n, ho, wo, 3) if layout == "hwc" else (n, 3, ho, wo)
         t = out[: n * 3 * ho * wo * ES[dt]]
@@ -86,7 +80,9 @@ def run(ctx, content, n, reps):
         return t.view(shape)
 
     def call(f):
-        kind, algo, dt, layout, size = FORMS[f]
+        kind, algo, dt, layout, size = FORMS[f.replace("_alt", "")]
+        if f.endswith("_alt"):
+            return alt.demosaic_display(mos, out_view(f), stream, algo, alt_luts[size], layout, WHITE, BLACK, GAIN, MAT)
         kw = dict(algo=algo, white=WHITE, black=BLACK, gain=GAIN, matrix=MAT)
         if kind == "linear":
             return ctx.demosaic(mos, dtype="f16", out=out_view(f), **kw)
@@ -101,7 +97,7 @@ def run(ctx, content, n, reps):
 
     torch.cuda.synchronize()
     for f in forms:  # correctness of frame 0 of every form, and warm-up
-        kind, algo, dt, layout, size = FORMS[f]
+        kind, algo, dt, layout, size = FORMS[f.replace("_alt", "")]
         with torch.cuda.stream(stream):
             res = call(f)
         torch.cuda.synchronize()
@@ -118,13 +114,15 @@ def run(ctx, content, n, reps):
             assert np.array_equal(got, want), f
     knames = ["krgb_mhc", "krgb_bin2", "k7_tiles"]
     ctx.profile(only=knames)
+    if alt:
+        alt.profile(knames[:2])
     for k in knames:
         ctx.kernel_ms(k, reset=True)
     ms = {f: [] for f in forms}
     km = {f: {} for f in forms}
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for _ in range(reps):
-        for f in forms:  # the forms take turns
+    for rep in range(reps):
+        for f in turn_order(forms, rep):  # the forms take turns
             with torch.cuda.stream(stream):
                 a.record(stream)
                 res = call(f)
@@ -133,15 +131,17 @@ def run(ctx, content, n, reps):
             del res
             ms[f].append(a.elapsed_time(b))
             for k in knames:
-                v, cnt = ctx.kernel_ms(k, reset=True)
+                v, cnt = (alt if f.endswith("_alt") else ctx).kernel_ms(k, reset=True)
                 if cnt:
                     km[f].setdefault(k, []).append(v)
     ctx.profile(enable=False)
+    if alt:
+        alt.profile(())
     ctx.synchronize()
     assert ctx.errors() == 0
     rows = []
     for f in forms:
-        kind, algo, dt, layout, size = FORMS[f]
+        kind, algo, dt, layout, size = FORMS[f.replace("_alt", "")]
         ho, wo = (H, W) if algo == "mhc" else (H // 2, W // 2)
         outb = n * 3 * ho * wo * ES[dt]
         inbytes = inb if kind == "decode" else n * W * H * 2
@@ -166,15 +166,19 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--frames", type=int, default=240)
     ap.add_argument("--content", default="smooth,noise")
+    ap.add_argument("--alt-lib", default=None)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "display_bench.jsonl"))
     args = ap.parse_args()
     ctx = M.Context(0)
+    alt = AltLib(args.alt_lib) if args.alt_lib else None
     with open(args.out, "a") as fh:
         for content in [c for c in args.content.split(",") if c]:
-            for r in run(ctx, content, args.frames, max(3, args.reps)):
+            for r in run(ctx, alt, content, args.frames, max(3, args.reps)):
                 line = json.dumps(r)
                 print(line, flush=True)
                 fh.write(line + "\n")
+    if alt:
+        alt.close()
     ctx.close()
 
 

@@ -6,7 +6,10 @@ of the 8 TB/s peak.  All forms take turns rep by rep in ONE process on one set o
 are checked against the numpy reference.  Also times an MHC written as torch ops (F.conv2d with the four 5x5 filters) on
 the same mosaics: what a user would otherwise write.
 
-    python tools/bench_rgb.py [--reps 9] [--only t7_uhd,t6_12mp]
+    python tools/bench_rgb.py [--reps 9] [--only t7_uhd,t6_12mp] [--alt-lib PATH]
+
+--alt-lib: another build of the library (of another commit, say): its demosaic forms (*_alt) take turns with the others, in a
+context of its own, and are checked against the same reference.
 """
 import argparse
 import json
@@ -22,6 +25,7 @@ import torch.nn.functional as F
 import _libs as L
 import _rgb_ref as R
 import motioncam_decoder_amd as M
+from altlib import AltLib, bench_encoded, bench_images, bench_mosaics, turn_order
 
 PEAK = 8e12
 WHITE, BLACK = 4095.0, (64, 64, 64, 64)
@@ -66,35 +70,29 @@ def torch_mhc(mos, black, out_dtype):
     return torch.stack([r, gch, b], 1).to(out_dtype)
 
 
-def run(ctx, name, reps):
+def run(ctx, alt, name, reps):
     typ, n, w, h, forms = WORKLOADS[name]
+    if alt:  # (the alt library's demosaic forms, each behind its counterpart)
+        forms = [g for f in forms for g in ([f, f + "_alt"] if FORMS[f][0] == "demosaic" else [f])]
     dev = torch.device("cuda:0")
-    imgs = [L.natural_image_np(w, h, 12, 12.0, 100 + s) for s in range(DISTINCT)]
-    bufs = [L.encode7(im) if typ == 7 else L.encode6(im) for im in imgs]
-    stride = max(len(b) for b in bufs) + 256
-    ins = torch.zeros((n, stride), dtype=torch.uint8, device=dev)
-    lens = []
-    for i in range(n):
-        b = bufs[i % DISTINCT]
-        ins[i, :len(b)].copy_(torch.from_numpy(b))
-        lens.append(len(b))
-    inputs = [(ins[i].data_ptr(), lens[i]) for i in range(n)]
-    mos = torch.empty((n, h, w), dtype=torch.uint16, device=dev)
-    for i in range(n):
-        mos.view(torch.int16)[i].copy_(torch.from_numpy(imgs[i % DISTINCT].view(np.int16)))
+    imgs = bench_images("smooth", w, h, DISTINCT, None)
+    ins, inputs, lens = bench_encoded(dev, imgs, n, L.encode7 if typ == 7 else L.encode6)
+    mos = bench_mosaics(dev, imgs, n)
     out = torch.empty(n * 3 * w * h * 4, dtype=torch.uint8, device=dev)  # room for the largest form (MHC f32)
     plain_frames = M.Context.make_frames([(inputs[i][0], lens[i], w, h, typ, mos.data_ptr() + i * w * h * 2, w * h)
                                           for i in range(n)])
     stream = torch.cuda.Stream()  # (not the null stream: the library takes NULL as its own stream)
 
     def out_view(f):
-        _, algo, dt = FORMS[f]
+        _, algo, dt = FORMS[f.replace("_alt", "")]
         ho, wo = (h, w) if algo == "mhc" else (h // 2, w // 2)
         t = out[: n * 3 * ho * wo * ES[dt]].view({"f32": torch.float32, "f16": torch.float16}[dt])
         return t.view(n, 3, ho, wo)
 
     def call(f, check):
-        kind, algo, dt = FORMS[f]
+        kind, algo, dt = FORMS[f.replace("_alt", "")]
+        if f.endswith("_alt"):
+            return alt.demosaic(mos, out_view(f), stream, algo, dt, WHITE, BLACK, GAIN, MAT)
         if kind == "plain":
             return ctx.decode_batch(plain_frames, stream=stream.cuda_stream, want_status=check)
         kw = dict(algo=algo, dtype=dt, white=WHITE, black=BLACK, gain=GAIN, matrix=MAT, out=out_view(f))
@@ -107,23 +105,25 @@ def run(ctx, name, reps):
         with torch.cuda.stream(stream):
             res = call(f, True)
         torch.cuda.synchronize()
-        if FORMS[f][0] == "plain":
+        if FORMS[f.replace("_alt", "")][0] == "plain":
             assert all(s == 0 for s in res[1]), (f, res[1][:8])
             continue
-        _, algo, dt = FORMS[f]
+        _, algo, dt = FORMS[f.replace("_alt", "")]
         for i in range(2):
             got = out_view(f)[i].cpu().numpy().view(np.uint32 if dt == "f32" else np.uint16)
             want = R.ref_bits(imgs[i % DISTINCT], algo, dt, WHITE, black=BLACK, gain=GAIN, matrix=MAT)
             assert np.array_equal(got, want), (name, f, i)
     knames = ["krgb_mhc", "krgb_bin2", DECODE_KERNEL[typ]]
     ctx.profile(only=knames)
+    if alt:
+        alt.profile(knames[:2])
     for k in knames:
         ctx.kernel_ms(k, reset=True)
     ms = {f: [] for f in forms}
     km = {f: {} for f in forms}
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for _ in range(reps):
-        for f in forms:  # the forms take turns
+    for rep in range(reps):
+        for f in turn_order(forms, rep):  # the forms take turns
             with torch.cuda.stream(stream):
                 a.record(stream)
                 call(f, False)
@@ -131,10 +131,12 @@ def run(ctx, name, reps):
             torch.cuda.synchronize()
             ms[f].append(a.elapsed_time(b))
             for k in knames:
-                v, cnt = ctx.kernel_ms(k, reset=True)
+                v, cnt = (alt if f.endswith("_alt") else ctx).kernel_ms(k, reset=True)
                 if cnt:
                     km[f].setdefault(k, []).append(v)
     ctx.profile(enable=False)
+    if alt:
+        alt.profile(())
     ctx.synchronize()
     assert ctx.errors() == 0
     # the yardstick: MHC as torch ops, on the first frames (its intermediates do not fit a whole batch comfortably)
@@ -153,7 +155,7 @@ def run(ctx, name, reps):
     inb = sum(lens)
     base = float(np.median(ms["plain"])) if "plain" in ms else None
     for f in forms:
-        kind, algo, dt = FORMS[f]
+        kind, algo, dt = FORMS[f.replace("_alt", "")]
         med = float(np.median(ms[f]))
         if kind == "plain":
             outb, inbytes = n * w * h * 2, inb
@@ -186,12 +188,16 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--only", default="")
+    ap.add_argument("--alt-lib", default=None)
     args = ap.parse_args()
     names = [s for s in args.only.split(",") if s] or list(WORKLOADS)
     ctx = M.Context(0)
+    alt = AltLib(args.alt_lib) if args.alt_lib else None
     for name in names:
-        for r in run(ctx, name, max(3, args.reps)):
+        for r in run(ctx, alt, name, max(3, args.reps)):
             print(json.dumps(r), flush=True)
+    if alt:
+        alt.close()
     ctx.close()
 
 

@@ -6,7 +6,10 @@ ms per batch (events around the call on a torch stream), the kernel's ms from th
 frames, smooth (natural images) and noise content; all forms take turns rep by rep in ONE process.  Frame 0 of every
 library form is checked against the numpy reference.  Appends to profiles/yuv_bench.jsonl.  Needs a GPU.
 
-    python tools/bench_yuv.py [--reps 7] [--frames 240] [--content smooth,noise]
+    python tools/bench_yuv.py [--reps 7] [--frames 240] [--content smooth,noise] [--alt-lib PATH]
+
+--alt-lib: another build of the library (of another commit, say): its display and YUV forms (*_alt) take turns with the others,
+in a context of its own, and are checked against the same reference.
 """
 import argparse
 import json
@@ -22,6 +25,7 @@ import _display_ref as D
 import _libs as L
 import _yuv_ref as Y
 import motioncam_decoder_amd as M
+from altlib import AltLib, bench_images, bench_mosaics, turn_order
 
 PEAK = 8e12
 W, H = 3840, 2160
@@ -64,22 +68,20 @@ def torch_nv12(rgb):
     return torch.cat([y, c], dim=1)
 
 
-def run(ctx, content, n, reps):
+def run(ctx, alt, content, n, reps):
     dev = torch.device("cuda:0")
-    rng = np.random.default_rng(7)
-    if content == "smooth":
-        imgs = [L.natural_image_np(W, H, 12, 12.0, 100 + s) for s in range(DISTINCT)]
-    else:
-        imgs = [rng.integers(0, 4096, size=(H, W), dtype=np.uint16) for _ in range(DISTINCT)]
-    mos = torch.empty((n, H, W), dtype=torch.uint16, device=dev)
-    for i in range(n):
-        mos.view(torch.int16)[i].copy_(torch.from_numpy(imgs[i % DISTINCT].view(np.int16)))
+    imgs = bench_images(content, W, H, DISTINCT, np.random.default_rng(7))
+    mos = bench_mosaics(dev, imgs, n)
     forms = list(FORMS)
+    if alt:  # (the alt library's display and YUV forms, each behind its counterpart)
+        forms = [g for f in forms for g in ([f, f + "_alt"] if FORMS[f][0] != "torch" else [f])]
+    to_dev = lambda a: torch.from_numpy(a.view(np.int16)).to(dev).view(torch.uint16)
+    alt_luts = {b: to_dev(M.transfer_lut("bt709", 4096, b)) for b in (8, 12, 16)} if alt else None
     out = torch.empty(n * 3 * W * H, dtype=torch.uint8, device=dev)  # room for the largest form (u8 HWC and P010, MHC)
     stream = torch.cuda.Stream()
 
     def out_view(f):
-        kind, algo, fmt = FORMS[f]
+        kind, algo, fmt = FORMS[f.replace("_alt", "")]
         ho, wo = (H, W) if algo == "mhc" else (H // 2, W // 2)
         t = out[: samples_out(kind, algo, fmt, n)]
         if kind == "display":
@@ -87,7 +89,11 @@ def run(ctx, content, n, reps):
         return (t.view(torch.uint16) if fmt == "p010" else t).view(n, ho * 3 // 2, wo)
 
     def call(f):
-        kind, algo, fmt = FORMS[f]
+        kind, algo, fmt = FORMS[f.replace("_alt", "")]
+        if f.endswith("_alt") and kind == "display":
+            return alt.demosaic_display(mos, out_view(f), stream, algo, alt_luts[8], "hwc", WHITE, BLACK, GAIN, MAT)
+        if f.endswith("_alt"):
+            return alt.demosaic_yuv(mos, out_view(f), stream, algo, alt_luts[IN_BITS[fmt]], fmt, IN_BITS[fmt], WHITE, BLACK, GAIN, MAT)
         kw = dict(algo=algo, white=WHITE, black=BLACK, gain=GAIN, matrix=MAT)
         if kind == "display":
             return ctx.demosaic_display(mos, transfer="bt709", lut_size=4096, dtype=torch.uint8, layout="hwc", out=out_view(f), **kw)
@@ -97,7 +103,7 @@ def run(ctx, content, n, reps):
 
     torch.cuda.synchronize()
     for f in forms:  # correctness of frame 0 of every library form, and warm-up
-        kind, algo, fmt = FORMS[f]
+        kind, algo, fmt = FORMS[f.replace("_alt", "")]
         with torch.cuda.stream(stream):
             res = call(f)
         torch.cuda.synchronize()
@@ -118,13 +124,15 @@ def run(ctx, content, n, reps):
         del res
     knames = ["krgb_mhc", "krgb_bin2"]
     ctx.profile(only=knames)
+    if alt:
+        alt.profile(knames)
     for k in knames:
         ctx.kernel_ms(k, reset=True)
     ms = {f: [] for f in forms}
     km = {f: {} for f in forms}
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for _ in range(reps):
-        for f in forms:  # the forms take turns
+    for rep in range(reps):
+        for f in turn_order(forms, rep):  # the forms take turns
             with torch.cuda.stream(stream):
                 a.record(stream)
                 res = call(f)
@@ -133,15 +141,17 @@ def run(ctx, content, n, reps):
             del res
             ms[f].append(a.elapsed_time(b))
             for k in knames:
-                v, cnt = ctx.kernel_ms(k, reset=True)
+                v, cnt = (alt if f.endswith("_alt") else ctx).kernel_ms(k, reset=True)
                 if cnt:
                     km[f].setdefault(k, []).append(v)
     ctx.profile(enable=False)
+    if alt:
+        alt.profile(())
     ctx.synchronize()
     assert ctx.errors() == 0
     rows = []
     for f in forms:
-        kind, algo, fmt = FORMS[f]
+        kind, algo, fmt = FORMS[f.replace("_alt", "")]
         outb = samples_out("display" if kind == "torch" else kind, algo, fmt, n)  # (torch: what its kernel writes, u8 CHW)
         total = n * W * H * 2 + (samples_out("yuv", algo, fmt, n) if kind == "torch" else outb)
         med = float(np.median(ms[f]))
@@ -163,17 +173,21 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--frames", type=int, default=240)
     ap.add_argument("--content", default="smooth,noise")
+    ap.add_argument("--alt-lib", default=None)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "yuv_bench.jsonl"))
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_yuv.py needs a GPU")
     ctx = M.Context(0)
+    alt = AltLib(args.alt_lib) if args.alt_lib else None
     with open(args.out, "a") as fh:
         for content in [c for c in args.content.split(",") if c]:
-            for r in run(ctx, content, args.frames, max(3, args.reps)):
+            for r in run(ctx, alt, content, args.frames, max(3, args.reps)):
                 line = json.dumps(r)
                 print(line, flush=True)
                 fh.write(line + "\n")
+    if alt:
+        alt.close()
     ctx.close()
 
 
