@@ -111,8 +111,34 @@ K6_PATH_VARIANTS = {
     "poison": ["-DMCRAW_PATHS6", "-DMCRAW_POISON_FRONT6"],
 }
 
-# The -D builds that tests/ links on the GPU box (tests/test_gpu_split.py, test_gpu_segw.py, test_gpu_lookback_fault.py, test_gpu_k6_paths.py).
-TEST_VARIANTS = (["-DMCRAW_FORCE_SEGW"], ["-DMCRAW_INJECT_MUTE7"], ["-DMCRAW_INJECT_LOST"]) + tuple(K6_PATH_VARIANTS.values())
+# k7_side with one way of its chain walk forced and every way counted (tests/test_gpu_k7_paths.py; the switches and why each is
+# valid for every input: csrc/mcraw_type7.hip).  Every name below occurs in mcraw_type7.hip alone, so a variant compiles that one source.
+#   earlyswitch  MCRAW_SEGW_RATIO=65: a unit lists at most SIDE_LCAP = 512 records, so from its 8th pass on 65 * passes >= 520 is
+#                above its count: every unit that reaches an 8th pass with the chain still in the piece hands over.  The model
+#                (tests/_side7_corpus.py, Stream.walk(ratio=65)) finds such a unit in every corpus stream of eight and more passes.
+#   coldspec     MCRAW_SPEC_WARM=4: a speculative count starts 8 bytes in front of its pieces.  The model's chain from there has
+#                not joined the true one at the part's first piece for the middle part of the refs stream of both natural frames
+#                (four parts; tests/test_side7_corpus.py asserts it).
+#   shortunits   MCRAW_SIDE_LCAP=256: the smallest the static_asserts allow (whole passes of 512 items in the offset scan).
+#   smallpieces  MCRAW_SIDE_LPT=1: pieces of 8 KiB, and with them MCRAW_SPEC_WARM=2048 -- half a piece, as in the product: a speculative
+#                count starts inside the piece in front (the kernel's static_assert).  Nothing outside #ifdefs had to change for it.
+K7_PATH_VARIANTS = {
+    "census": ["-DMCRAW_PATHS7"],
+    "segw": ["-DMCRAW_PATHS7", "-DMCRAW_FORCE_SEGW"],
+    "noswitch": ["-DMCRAW_PATHS7", "-DMCRAW_SEGW_RATIO=0u"],
+    "earlyswitch": ["-DMCRAW_PATHS7", "-DMCRAW_SEGW_RATIO=65u"],
+    "warm1": ["-DMCRAW_PATHS7", "-DMCRAW_FORCE_SEGW", "-DMCRAW_WARM_SEGS=1"],
+    "coldspec": ["-DMCRAW_PATHS7", "-DMCRAW_SPEC_WARM=4"],
+    "mute": ["-DMCRAW_PATHS7", "-DMCRAW_INJECT_MUTE7"],
+    "shortunits": ["-DMCRAW_PATHS7", "-DMCRAW_SIDE_LCAP=256"],
+    "smallpieces": ["-DMCRAW_PATHS7", "-DMCRAW_SIDE_LPT=1", "-DMCRAW_SPEC_WARM=2048"],
+    "poison": ["-DMCRAW_PATHS7", "-DMCRAW_POISON_STRIDES7"],
+}
+
+# The -D builds that tests/ links on the GPU box (tests/test_gpu_split.py, test_gpu_segw.py, test_gpu_lookback_fault.py,
+# test_gpu_k6_paths.py, test_gpu_k7_paths.py).
+TEST_VARIANTS = ((["-DMCRAW_FORCE_SEGW"], ["-DMCRAW_INJECT_MUTE7"], ["-DMCRAW_INJECT_LOST"]) + tuple(K6_PATH_VARIANTS.values())
+                 + tuple(K7_PATH_VARIANTS.values()))
 
 
 def prebuild_test_variants():

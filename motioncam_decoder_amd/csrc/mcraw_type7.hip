@@ -228,6 +228,63 @@ __device__ unsigned long long g_side_prof[2][256];
 #define SIDE_STAMP(slot)
 #endif
 
+// Test builds of k7_side (tests/test_gpu_k7_paths.py, build.K7_PATH_VARIANTS; none of this is in the product library).  Which way
+// a stream goes -- runs or segment walkers, how many units and pieces, what its parts find and say -- is decided by its content
+// and, for the hand-off, by timing.  Every switch below chooses among ways that are right for EVERY input, because the kernel
+// takes nothing on trust on any of them:
+//   MCRAW_PATHS7              the path census below
+//   MCRAW_FORCE_SEGW          the segment walkers from a stream's first record on.  They list the records of a piece from where
+//                             the chain stands, whatever stands there; the run rule is only the cheaper way to the same list.
+//   MCRAW_SEGW_RATIO=r        a unit goes over to the walkers at its 8th pass and later when it has listed fewer than r records per
+//                             pass.  0: never (runs follow any chain, one record a pass at worst).  65: every unit that reaches
+//                             an 8th pass with the chain still in the piece (8 * 65 > SIDE_LCAP >= the records of a unit); the
+//                             hand-over happens where the chain stands, a record that is not listed yet, for any r.
+//   MCRAW_WARM_SEGS=w         walker lanes of the first w segments start on the chain, the others w segments in front of their own.
+//                             Any w >= 1 will do: lane 0 is on the chain, every other lane's entry is checked against what the
+//                             lane in front of it says and walked again where it differs.  (0 would leave no lane on the chain.)
+//   MCRAW_SPEC_WARM=c         a speculative count starts c candidates in front of the part's pieces.  Where it enters them is
+//                             compared with what the part in front says; a count that entered elsewhere is thrown away.
+//   MCRAW_INJECT_MUTE7        the first part of every stream never tells, the others give up soon: a part that hears nothing
+//                             follows the chain from the stream's first record by itself, which is always possible.
+//   MCRAW_SIDE_LCAP=n         records per unit (a multiple of 256: whole passes of the offset scan).  A unit is a slice of the
+//                             list of records; where the slices end changes nothing in the list.
+//   MCRAW_SIDE_LPT=l          pieces of l * 8 KiB.  The piece is the kernel's own unit of staging; the stream knows nothing of it.
+//   MCRAW_POISON_STRIDES7     the stride table is overwritten with SIDE_DEAD before a unit is replayed: a replay has the
+//                             count's notes and needs no stride table; one that looked at the stale table would end the chain
+//                             there.  The store is wave 0's, in the slot of the pipeline in which it would walk (and read the
+//                             table) otherwise; build_strides writes the table outside that slot, behind a barrier.
+#ifdef MCRAW_PATHS7
+// What the workgroups of k7_side (one per stream, or per part of one) and the waves of k7_tiles did, summed over the launches
+// since the last reset (mcraw_diag_k7_paths).  k7_side keeps its counts in registers -- every thread those that are uniform over the
+// workgroup, wave 0 those of the walk -- and thread 0 adds them up once at the kernel's end (a rejected workgroup where it returns);
+// k7_tiles has two events per wave at most, which lane 0 adds where they happen.
+enum Path7 {
+    P7_STREAMS, P7_REJECTED,                        // workgroups that passed the header checks / were rejected there
+    P7_RECORDS,                                     // records decoded (units that are not skipped)
+    P7_UNITS, P7_UNITS_FULL, P7_PIECE_STEPS, P7_UNITS_DEAD, P7_SKIPPED_UNITS, // units of phase 2; ... that ended because the list was full or the
+                                                    // stream complete (why 1) / the piece through (2) / the chain dead (3); ... walked, not decoded
+    P7_DEAD,                                        // workgroups that report a chain that ended in front of the stream's last record
+    P7_RUN_PASSES, P7_RUN_PASSES64,                 // passes of the run rule (count and decode); ... that found 64 equal records
+    P7_SEGW_SWITCH,                                 // units that went from runs to walkers
+    P7_SEGW_PIECES, P7_SEGW_REPAIRED, P7_SEGW_ROUNDS2, // calls of seg_walk; ... with at least one / with more than one repair round
+    P7_SEGW_RESUMED,                                // walks that went on with a piece's valid s_seg (a piece listed over several units)
+    P7_PARTS, P7_PART_EMPTY, P7_COUNTED, P7_SPEC,   // workgroups of streams in parts; ... that own no piece; ... that counted; ... from a speculative start
+    P7_HO_MUTE, P7_HO_OVER, P7_HO_PASS, P7_HO_LAST, P7_HO_HIT, P7_HO_MISS, // the hand-off, one per part: the part in front never spoke / the stream is over in
+                                                    // front / an empty part passes on / the last part / the count stands / the chain enters elsewhere
+    P7_HO_MUTE_WORK, P7_HO_MUTE_PART1,              // ... of those the part in front never spoke to: the ones that own pieces; the ones that are part 1
+    P7_LASTC_REPLAYED,                              // last parts whose count stood
+    P7_REPLAY_UNITS, P7_REPLAY_PIECEFLAG,           // units replayed; ... that end in front of an entry with the piece flag
+    P7_REPLAY_TAIL,                                 // walks of a part behind its replay
+    P7_TOLD_LATE,                                   // parts that tell behind their decode
+    P7_ITEMS_BEHIND_PART0, P7_TRUNCATED_BY_TILES,   // k7_tiles: items whose offsets another part than the first wrote; reports of a payload that crosses `len`
+    P7_N
+};
+__device__ unsigned long long g_k7_paths[P7_N];
+#define K7_PATH(slot, v) (p7_[slot] += static_cast<uint32_t>(v))
+#else
+#define K7_PATH(slot, v)
+#endif
+
 // PARTS: streams may be cut into parts (W.nsplit); false: one workgroup per stream -- the instance every batch of UHD frames runs,
 // without the count, the hand-off and the replay in its code (the walker's loop is short of scalar registers as it is).
 // LASTC: the last part of a stream counts its pieces too (below) -- an instance of its own for the same reason.
@@ -271,6 +328,9 @@ __global__ __launch_bounds__(SIDE_T) __attribute__((amdgpu_waves_per_eu(4, 4))) 
     const uint32_t fs = (nsb + nsr) * f + (s ? nsb : 0u) + part;
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+#ifdef MCRAW_PATHS7
+    uint32_t p7_[P7_N] = {};
+#endif
 #ifdef MCRAW_DIAG
     const unsigned long long stamp_ = __builtin_amdgcn_s_memtime();
     uint32_t tl_n_ = 0, nsteps_ = 0;
@@ -362,8 +422,13 @@ __global__ __launch_bounds__(SIDE_T) __attribute__((amdgpu_waves_per_eu(4, 4))) 
     if (err) {
         if (tid == 0u)
             *status = err;
+#ifdef MCRAW_PATHS7
+        if (tid == 0u)
+            atomicAdd(&g_k7_paths[P7_REJECTED], 1ull);
+#endif
         return;
     }
+    K7_PATH(P7_STREAMS, 1u);
     // The pieces of this part.  Where the stream ends is not known before its chain has been followed; the split is made
     // on a guess -- the stream reaches to where the other one starts, or to the end of the frame, as encoders lay them
     // out -- and any guess gives a partition: the ranges are disjoint, the last part's is open-ended.
@@ -505,12 +570,18 @@ __global__ __launch_bounds__(SIDE_T) __attribute__((amdgpu_waves_per_eu(4, 4))) 
         // lowest such lane is right afterwards for good (the lanes below it are), so the rounds end -- after one or
         // two: wrong lanes are few and seldom neighbours, and a corrected lane mostly leaves its segment where it did before.
         uint32_t src = SEG_NONE; // where a lane that walked again started from (its chain may end right there)
+#ifdef MCRAW_PATHS7
+        uint32_t rounds7 = 0u;
+#endif
         for (uint32_t round = 0; round < 64u; round++) { // (the lowest wrong lane is right after every round)
             const uint32_t want = wave_prev(ex, ex); // (lane 0: its own, never looked at -- it is on the chain)
             const uint32_t claim = src != SEG_NONE ? src : ent != SEG_NONE ? ent : ex;
             const bool bad = act && !on_chain && claim != want;
             if (__ballot(bad) == 0ull)
                 break;
+#ifdef MCRAW_PATHS7
+            rounds7++;
+#endif
             if (bad) {
                 ent = SEG_NONE;
                 cnt = 0;
@@ -527,6 +598,11 @@ __global__ __launch_bounds__(SIDE_T) __attribute__((amdgpu_waves_per_eu(4, 4))) 
         seg_total = total;
         seg_done = 0;
         seg_valid = true;
+#ifdef MCRAW_PATHS7
+        K7_PATH(P7_SEGW_PIECES, 1u);
+        K7_PATH(P7_SEGW_REPAIRED, rounds7 >= 1u);
+        K7_PATH(P7_SEGW_ROUNDS2, rounds7 > 1u);
+#endif
     };
     // records [seg_done, seg_done + take) of the piece, in chain order, into the list: every lane walks its segment
     // once more, from its (now known) first record
@@ -568,6 +644,8 @@ __global__ __launch_bounds__(SIDE_T) __attribute__((amdgpu_waves_per_eu(4, 4))) 
                 go = take == nb && cnt < room && (nb == 64u || nxt < SIDE_DEAD);
                 SU = (go && nb != 64u) ? nxt : SU;
                 passes++;
+                K7_PATH(P7_RUN_PASSES, 1u);
+                K7_PATH(P7_RUN_PASSES64, nb == 64u);
                 // Fewer than three records per pass: the records keep changing size, runs do not pay here (a pass costs ~350
                 // cycles whatever it lists); the segment walkers take over where the chain stands (a record that is not listed
                 // yet), for the rest of the stream.  The bar is low on purpose: a chain that starts on payload bytes advances by
@@ -590,10 +668,12 @@ __global__ __launch_bounds__(SIDE_T) __attribute__((amdgpu_waves_per_eu(4, 4))) 
             }
             if (segw)
                 seg_valid = false;
+            K7_PATH(P7_SEGW_SWITCH, segw);
         } else if (!segw) {
             SU = 0u;
         }
         if (segw && pu < SIDE_HALF) {
+            K7_PATH(P7_SEGW_RESUMED, !fresh && seg_valid);
             if (fresh || !seg_valid)
                 seg_walk(pu);
             const uint32_t take = min(room - cnt, seg_total - seg_done);
@@ -718,6 +798,10 @@ __global__ __launch_bounds__(SIDE_T) __attribute__((amdgpu_waves_per_eu(4, 4))) 
         // it --: the host says so, W.side_lastc, and launches the instance that has it)
         const bool lastc = LASTC && lastp && !owns0 && rp_base != nullptr && m_chi > m_lo && m_chi != 0xFFFFFFFFu;
         const bool spec = !empty && !owns0 && (!lastp || lastc);
+        K7_PATH(P7_PARTS, 1u);
+        K7_PATH(P7_PART_EMPTY, empty);
+        K7_PATH(P7_COUNTED, !empty && (!lastp || lastc));
+        K7_PATH(P7_SPEC, spec);
         uint32_t entry = NOENTRY, cnt1 = 0u, exit1 = ENDX; // where the chain enters piece m_lo; records of the part's pieces; where it enters piece m_hi
         bool dead1 = false;                                // ... it ended inside the part's pieces
         bool counted = false;
@@ -793,6 +877,9 @@ __global__ __launch_bounds__(SIDE_T) __attribute__((amdgpu_waves_per_eu(4, 4))) 
         SIDE_STAMP(21); // the part in front has spoken
         decode_from = m_lo;
         if (!ok) { // it never spoke: from the stream's first record on, by itself (and this part says its own at the end)
+            K7_PATH(P7_HO_MUTE, 1u);
+            K7_PATH(P7_HO_MUTE_WORK, !empty);
+            K7_PATH(P7_HO_MUTE_PART1, part == 1u);
             if (empty) { // (a part that owns nothing only has to find out what to pass on)
                 decode_from = 0xFFFFFFFFu;
                 if (m_hi == 0u) {
@@ -802,23 +889,29 @@ __global__ __launch_bounds__(SIDE_T) __attribute__((amdgpu_waves_per_eu(4, 4))) 
                 }
             }
         } else if (!owns0 && (pw == ENDX || pn >= R)) { // the stream is over in front of this part
+            K7_PATH(P7_HO_OVER, 1u);
             tell(pn, ENDX);
             nothing_to_decode();
             go = false;
         } else if (empty) { // nothing of the stream falls to this part: pass it on
+            K7_PATH(P7_HO_PASS, 1u);
             tell(pn, pw);
             nothing_to_decode();
             go = false;
         } else if (lastp) {
+            K7_PATH(P7_HO_LAST, 1u);
+            K7_PATH(P7_LASTC_REPLAYED, lastc && pw == entry);
             run_piece = m_lo, run_cand = owns0 ? first_cand : pw, run_n = pn;
             if (lastc && pw == entry)
                 replay_from_count();
         } else if (owns0 || pw == entry) { // the count stands: say it, then decode
+            K7_PATH(P7_HO_HIT, 1u);
             const uint32_t upto = pn + cnt1;
             tell(min(upto, R), upto >= R || dead1 || exit1 == ENDX ? ENDX : exit1);
             run_piece = m_lo, run_cand = owns0 ? first_cand : entry, run_n = pn;
             replay_from_count();
         } else { // the chain enters this part's pieces elsewhere: decode from there, and say afterwards what comes out of it
+            K7_PATH(P7_HO_MISS, 1u);
             run_piece = m_lo, run_cand = pw, run_n = pn;
         }
         if (go && run_n >= R) { // (nothing left of the stream)
@@ -856,6 +949,11 @@ __global__ __launch_bounds__(SIDE_T) __attribute__((amdgpu_waves_per_eu(4, 4))) 
     uint4 rq = make_uint4(0u, 0u, 0u, 0u);
     auto rfetch = [&](uint32_t at) { rq = ld_b128_nt(rsp, 2u * (at + 8u * lane)); }; // (bounds-checked: zeros behind the part's entries)
     auto replay = [&](uint32_t lst, uint32_t room) {
+#ifdef MCRAW_POISON_STRIDES7 // (test builds, see MCRAW_PATHS7: a replay needs no stride table)
+        for (uint32_t i = lane; i < SIDE_HALF / 16u; i += 64u)
+            reinterpret_cast<uint4 *>(s_T)[i] = make_uint4(0x01010101u * SIDE_DEAD, 0x01010101u * SIDE_DEAD, 0x01010101u * SIDE_DEAD, 0x01010101u * SIDE_DEAD);
+#endif
+        K7_PATH(P7_REPLAY_UNITS, 1u);
         const uint32_t n = min(room, rleft);
         const uint32_t w4[4] = {rq.x, rq.y, rq.z, rq.w};
         uint32_t mine = 8u, ment = 0u; // my first entry (behind the unit's first) that opens a piece
@@ -869,6 +967,7 @@ __global__ __launch_bounds__(SIDE_T) __attribute__((amdgpu_waves_per_eu(4, 4))) 
         const unsigned long long m = __ballot(mine != 8u);
         uint32_t take = n, pu = 0u, why = 1u;
         if (m) {
+            K7_PATH(P7_REPLAY_PIECEFLAG, 1u);
             const uint32_t fl = static_cast<uint32_t>(__builtin_ctzll(m));
             take = 8u * fl + wave_lane(mine, fl);
             pu = SIDE_HALF + (wave_lane(ment, fl) & 0x7fffu);
@@ -909,6 +1008,12 @@ __global__ __launch_bounds__(SIDE_T) __attribute__((amdgpu_waves_per_eu(4, 4))) 
         const bool skip = upc < decode_from;             // a unit in front of this part's pieces: walked, not decoded
         if (!skip && n_first == 0xFFFFFFFFu)
             n_first = n;
+        K7_PATH(P7_UNITS, 1u);
+        K7_PATH(P7_UNITS_FULL, why == 1u);
+        K7_PATH(P7_PIECE_STEPS, why == 2u);
+        K7_PATH(P7_UNITS_DEAD, why == 3u);
+        K7_PATH(P7_SKIPPED_UNITS, skip);
+        K7_PATH(P7_RECORDS, skip ? 0u : total);
         if (npc > upc && npc == m_hi)
             exitc = pu - SIDE_HALF;
         if (rleft) { // (that unit was replayed: all threads keep count of what is left)
@@ -931,6 +1036,7 @@ __global__ __launch_bounds__(SIDE_T) __attribute__((amdgpu_waves_per_eu(4, 4))) 
         SIDE_STAMP(1);
         if (wave == 0u) {
             if (!last) {
+                K7_PATH(P7_REPLAY_TAIL, rleft == 0u && rnext != 0u);
                 if (rleft)
                     replay(cur ^ 1u, min(R - (n + total), SIDE_LCAP));
                 else
@@ -1021,6 +1127,8 @@ __global__ __launch_bounds__(SIDE_T) __attribute__((amdgpu_waves_per_eu(4, 4))) 
         upc = npc;
         cur ^= 1u;
     }
+    K7_PATH(P7_TOLD_LATE, !told);
+    K7_PATH(P7_DEAD, dead);
     tell(min(n, R), n >= R || dead || exitc == ENDX ? ENDX : exitc); // (a part that could not say it behind its count)
     if (s == 0u && prev_total) { // the last unit's offsets
         lds_barrier();
@@ -1046,6 +1154,12 @@ __global__ __launch_bounds__(SIDE_T) __attribute__((amdgpu_waves_per_eu(4, 4))) 
         }
     }
     }
+#ifdef MCRAW_PATHS7
+    if (tid == 0u)
+        for (uint32_t i = 0; i < P7_N; i++)
+            if (p7_[i])
+                atomicAdd(&g_k7_paths[i], static_cast<unsigned long long>(p7_[i]));
+#endif
     // one status word per stream, written once (no initialisation needed in front of the kernel)
     if (lane_err)
         atomicOr(&s_err, lane_err);
@@ -1124,6 +1238,14 @@ __device__ __forceinline__ ItemS item_scalars(const Work7 &W, uint32_t item, uin
             }
             start += sum_s;
             end = static_cast<uint32_t>(e64);
+#ifdef MCRAW_PATHS7
+            if ((threadIdx.x & 63u) == 0u) {
+                if (ps > 0u)
+                    atomicAdd(&g_k7_paths[P7_ITEMS_BEHIND_PART0], 1ull);
+                if ((g + 1u) * ITEM_BLOCKS >= nblk && e64 > F->len)
+                    atomicAdd(&g_k7_paths[P7_TRUNCATED_BY_TILES], 1ull);
+            }
+#endif
             // the payload's end against `len` (RawData.cpp:419-420: some block would cross it), checked here because no part of
             // k7_side knows the sum; by the wave of the frame's last item
             if ((g + 1u) * ITEM_BLOCKS >= nblk && e64 > F->len)
@@ -1359,6 +1481,24 @@ extern "C" void mcraw_diag_side_prof(unsigned long long *out, int reset)
         unsigned long long z[32] = {0};
         (void)hipMemcpyToSymbol(HIP_SYMBOL(g_side_prof), z, sizeof(z));
     }
+}
+#endif
+
+#ifdef MCRAW_PATHS7
+// The census, in the order of Path7 (up to n counters; returns how many there are); `reset`: and start it over.
+extern "C" int mcraw_diag_k7_paths(uint64_t *out, int n, int reset)
+{
+    (void)hipDeviceSynchronize();
+    n = n < 0 ? 0 : n < static_cast<int>(P7_N) ? n : static_cast<int>(P7_N);
+    if (out && n)
+        (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_k7_paths), sizeof(uint64_t) * static_cast<size_t>(n));
+    if (reset) {
+        void *p = nullptr;
+        (void)hipGetSymbolAddress(&p, HIP_SYMBOL(g_k7_paths));
+        (void)hipMemset(p, 0, sizeof(g_k7_paths));
+        (void)hipDeviceSynchronize(); // (the contexts' streams do not wait for the null stream)
+    }
+    return static_cast<int>(P7_N);
 }
 #endif
 
