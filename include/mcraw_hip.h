@@ -710,6 +710,71 @@ typedef struct mcraw_merge {
 int mcraw_merge_batch(mcraw_ctx *ctx, const mcraw_merge *m, const uint16_t *in, size_t in_pitch, size_t in_frame_stride,
                       int width, int height, int n, uint16_t *out, size_t out_pitch, size_t out_frame_stride, void *stream);
 
+/* ---- uint16 mosaics -> the frames' global positions (what mcraw_merge_batch takes as `pos`) ---------------------------------
+ *
+ * Estimates, for `n` uint16 mosaics of width x height that show the same scene, one global shift per frame: a coarse-to-fine
+ * search of the smallest sum of absolute differences between grey planes of half the mosaic's size.  The result is the
+ * (n, 2) int16 array that mcraw_merge_batch reads as `pos`, so a hand-held clip is merged along its motion.  Pitches and frame
+ * strides count uint16 elements.  Integers only: bit-exact, whatever the order of the additions.
+ * Grey plane.  Frame f gives G0[f] of h0 = height / 2 rows by w0 = width / 2 columns (floor: a trailing odd row or column is
+ * not looked at), stored as uint16; with s the sample at CFA position p = (row & 1) * 2 + (col & 1):
+ *   G0[y][x] = min((sum over the 4 samples of quad (y, x) of max(s - black[p], 0) + 2) >> 2, 65535)
+ * Pyramid.  Levels 0 .. levels - 1, h(l+1) = h(l) / 2, w(l+1) = w(l) / 2 (floor):
+ *   G(l+1)[y][x] = (the 4 samples of G(l) in quad (y, x), summed, + 2) >> 2
+ * Bounds.  B(l) bounds the displacement at level l and is the margin of the comparison window, so every candidate of a
+ * level is summed over the same pixels:
+ *   B(levels - 1) = radius
+ *   B(l) = 2 * B(l + 1) + 1
+ * One pair, base b and member t.  At level l, for a displacement (dy, dx), exact in 64 bits:
+ *   SAD_l(dy, dx) = sum over B(l) <= y < h(l) - B(l), B(l) <= x < w(l) - B(l) of |G_l[t][y + dy][x + dx] - G_l[b][y][x]|
+ * At the coarsest level the centre is (0, 0) and the candidates are dy, dx in -radius .. radius about it; at each finer level
+ * the centre is twice the winner of the level above and the candidates are -1 .. 1 about it.  With (ddy, ddx) the offset
+ * from the centre, the winner is the candidate with the smallest
+ *   key = (SAD, ddy * ddy + ddx * ddx, ddy, ddx)
+ * compared lexicographically: a flat or an identical pair gives (0, 0).  d(t|b) is the level-0 winner, in quads (2 samples).
+ * Sign.  d(t|b) is the (dy, dx) for which in[t][y + 2 dy][x + 2 dx] looks like in[b][y][x]: the meaning of pos[t] - pos[b]
+ * in mcraw_merge_batch.
+ * Positions, accumulated in int32:
+ *   ref = -1 (chain):    pos[0] = (0, 0),   pos[t] = pos[t - 1] + 2 * d(t|t - 1)       the pairs are (t - 1, t)
+ *   ref in 0 .. n - 1:   pos[ref] = (0, 0), pos[t] = 2 * d(t|ref)                      the pairs are (ref, t): a burst
+ * stored as int16 (n, 2) as (y, x), each component clamped to -32768 .. 32767.  Differences across a clamped entry are
+ * meaningless: a chain that drifts that far is to be cut into pieces by the caller.  (The int32 sums themselves cannot wrap
+ * below 3.7 million frames: a step is at most 2 * B(0) <= 574.)
+ * sad: NULL, or DEVICE memory, 8-byte aligned, n uint64: the level-0 winning SAD of the frame's pair, 0 for the frame that
+ * has no pair (frame 0 of a chain, frame ref).  A scene cut shows as a jump.  The window has
+ * (h0 - 2 * B(0)) * (w0 - 2 * B(0)) pixels, which normalises it.
+ * work: the caller's DEVICE memory, 16-byte aligned, of at least mcraw_align_work_bytes(width, height, n, levels, radius)
+ * bytes (0 for arguments the call would reject): the pyramids, the candidates' 64-bit sums and the levels' winners.  The call
+ * initialises what it accumulates into, on the stream; nothing is cached in the context, and two calls under way at once
+ * need two scratch areas.  pos, sad and work are written in stream order; no level waits for the host.
+ * `in` may sit at any 2-byte alignment with any pitch (16-byte loads where base, pitch and stride allow it); it is read once.
+ * `stream`: a hipStream_t, NULL = the context's own stream; the call queues the work and returns without synchronising.
+ * It takes no decode serial and leaves the decode slots, mcraw_ctx_errors, mcraw_ctx_last_serial and the context's stage
+ * alone.  n == 0 is a no-op; n == 1 writes (0, 0).  The launches have no id in mcraw_ctx_kernel_ms (time them with stream
+ * events).
+ * Out of scope: local or tile-wise motion (the merge's weights leave out what moved on its own), precision below a quad (the
+ * merge drops the low bit of a shift anyway), rotation, a region of interest, and reading gyro metadata.
+ * Rejected (returns < 0, mcraw_last_error says why, starting with "mcraw_align_batch: ", nothing is written): a NULL `a`,
+ * `in`, `pos` or `work`; an odd `in` or `pos` address; a `sad` that is not 8-byte aligned; a `work` that is not 16-byte
+ * aligned; width or height outside 1 .. 65536; a pitch below width; n > 1 and a frame stride below (height - 1) * pitch +
+ * width; levels outside 1 .. 6; radius outside 1 .. 8; ref outside -1 .. n - 1; a non-zero `reserved`; a window that is
+ * empty at any level (h(l) - 2 * B(l) < 1 or w(l) - 2 * B(l) < 1); work_bytes below mcraw_align_work_bytes(...); `work`,
+ * `pos` or `sad` overlapping the input's extent or one another. */
+typedef struct mcraw_align {
+    uint32_t levels;       /* 1 .. 6: levels of the pyramid                                             */
+    uint32_t radius;       /* 1 .. 8: the search radius at the coarsest level, in its pixels            */
+    int32_t ref;           /* -1: a chain, frame t against frame t - 1;  0 .. n - 1: all against ref    */
+    uint32_t reserved;     /* must be 0                                                                 */
+    uint16_t black[4];     /* by CFA position                                                           */
+    int16_t *pos;          /* DEVICE memory, 2-byte aligned: (n, 2) as (y, x), written                  */
+    uint64_t *sad;         /* DEVICE memory, 8-byte aligned: n, written; or NULL                        */
+    void *work;            /* DEVICE memory, 16-byte aligned: scratch of work_bytes bytes               */
+    size_t work_bytes;     /* at least mcraw_align_work_bytes(width, height, n, levels, radius)         */
+} mcraw_align;             /* sizeof 56; radius 4, ref 8, reserved 12, black 16, pos 24, sad 32, work 40, work_bytes 48 */
+size_t mcraw_align_work_bytes(int width, int height, int n, uint32_t levels, uint32_t radius);
+int mcraw_align_batch(mcraw_ctx *ctx, const mcraw_align *a, const uint16_t *in, size_t in_pitch, size_t in_frame_stride,
+                      int width, int height, int n, void *stream);
+
 /* ---- environment ------------------------------------------------------------------------------
  * Read when a context (or pool) is created, never afterwards:
  *   MCRAW_DEVICE=n, MCRAW_DEVICES=all|0,1,5   default device of the five-argument entry points / members of a default pool

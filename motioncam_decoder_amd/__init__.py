@@ -17,7 +17,8 @@ __all__ = ["lib_path", "load", "Context", "Pool", "Frame", "EncFrame", "FloatOut
            "RgbParams", "RgbColor", "RGB_KERNELS", "rgb_color", "Display", "transfer_lut", "DISP_U8", "DISP_U16",
            "DISP_CHW", "DISP_HWC", "Yuv", "YUV_NV12", "YUV_P010", "yuv_matrix", "yuv_planes", "Shade", "gain_map",
            "shading_map", "Stats", "STATS_ACCUMULATE", "FrameStats", "stats_white_balance", "stats_percentile",
-           "stats_clipped", "FixPix", "FIXPIX_HOT", "FIXPIX_COLD", "pack_pixels", "Denoise", "noise_lut", "Merge"]
+           "stats_clipped", "FixPix", "FIXPIX_HOT", "FIXPIX_COLD", "pack_pixels", "Denoise", "noise_lut", "Merge", "Align",
+           "align_window"]
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 
@@ -46,7 +47,7 @@ ABI_SYMBOLS = [
     "mcraw_encode_bound7", "mcraw_encode_batch", "mcraw_encode7", "mcraw_ctx_set_float_out", "mcraw_pool_set_float_out",
     "mcraw_demosaic_batch", "mcraw_demosaic_display_batch", "mcraw_demosaic_yuv_batch", "mcraw_shade_batch",
     "mcraw_stats_batch", "mcraw_stats_record_bytes", "mcraw_fixpix_batch", "mcraw_denoise_batch",
-    "mcraw_merge_batch",
+    "mcraw_merge_batch", "mcraw_align_batch", "mcraw_align_work_bytes",
 ]
 
 POST_BLACK, POST_PACK12, POST_PACK10, POST_PACK14 = 1, 2, 4, 8
@@ -392,6 +393,37 @@ class Merge(C.Structure):
     _fields_ = [("before", C.c_uint32), ("after", C.c_uint32), ("first", C.c_uint32), ("count", C.c_uint32),
                 ("support", C.c_uint32), ("amount", C.c_uint32), ("lut_log2", C.c_uint32), ("shift", C.c_uint32),
                 ("nluts", C.c_uint32), ("reserved", C.c_uint32), ("lut", C.c_void_p), ("pos", C.c_void_p)]
+
+
+# per-frame global shifts of mosaics (mcraw_align_batch)
+class Align(C.Structure):
+    """struct mcraw_align (include/mcraw_hip.h): the pyramid's levels, the coarsest level's radius, the reference frame (-1: a
+    chain), the blacks, the device outputs pos (n, 2) int16 and sad (n) uint64 or NULL, and the device scratch with its size."""
+    _fields_ = [("levels", C.c_uint32), ("radius", C.c_uint32), ("ref", C.c_int32), ("reserved", C.c_uint32),
+                ("black", C.c_uint16 * 4), ("pos", C.c_void_p), ("sad", C.c_void_p), ("work", C.c_void_p),
+                ("work_bytes", C.c_size_t)]
+
+
+def align_window(height, width, levels=4, radius=4):
+    """(rows, columns) of the level-0 comparison window of Context.align for frames of height x width: what its `sad` is summed
+    over, (height // 2 - 2 * B0, width // 2 - 2 * B0) with B(levels - 1) = radius, B(l) = 2 * B(l + 1) + 1.  Raises ValueError
+    for levels outside 1 .. 6, radius outside 1 .. 8, and for frames so small that the window is empty at a level: what the
+    library would reject (host only, no GPU needed)."""
+    for name, v, lo, hi in (("levels", levels, 1, 6), ("radius", radius, 1, 8)):
+        if isinstance(v, bool) or v != int(v) or not lo <= int(v) <= hi:
+            raise ValueError("align: %s must be an integer %d .. %d, not %r" % (name, lo, hi, v))
+    levels, B = int(levels), int(radius)
+    if isinstance(height, bool) or isinstance(width, bool) or height != int(height) or width != int(width) \
+            or not (1 <= int(height) <= 65536 and 1 <= int(width) <= 65536):
+        raise ValueError("align: height and width must be integers 1 .. 65536, not %r x %r" % (height, width))
+    h, w = int(height) // 2, int(width) // 2
+    for l in range(levels - 1, -1, -1):  # coarsest first
+        if (h >> l) - 2 * B < 1 or (w >> l) - 2 * B < 1:
+            raise ValueError("align: %d x %d frames leave no comparison window at level %d (a %d x %d plane, margin %d): fewer "
+                             "levels, a smaller radius or larger frames" % (height, width, l, h >> l, w >> l, B))
+        if l:
+            B = 2 * B + 1
+    return h - 2 * B, w - 2 * B
 
 
 def noise_lut(S, O, black, white, strength=3.0, entries=256, top=None):
@@ -773,6 +805,11 @@ def load():
     lib.mcraw_merge_batch.restype = C.c_int
     lib.mcraw_merge_batch.argtypes = [C.c_void_p, C.POINTER(Merge), C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int,
                                       C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
+    lib.mcraw_align_work_bytes.restype = C.c_size_t
+    lib.mcraw_align_work_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32]
+    lib.mcraw_align_batch.restype = C.c_int
+    lib.mcraw_align_batch.argtypes = [C.c_void_p, C.POINTER(Align), C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int,
+                                      C.c_void_p]
     lib.mcraw_encode7.restype = C.c_size_t
     lib.mcraw_encode7.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int]
     _lib = lib
@@ -1436,6 +1473,44 @@ class Context:
         ref = int(ref)
         return self.merge(mosaic, lut, shift, before=ref, after=n - 1 - ref, first=ref, count=1, out=out, **kw)[0]
 
+    def align(self, mosaic, *, black=(0, 0, 0, 0), levels=4, radius=4, ref=None, sad=False):
+        """One global shift per frame of uint16 mosaics resident on the context's device (mcraw_align_batch): a coarse-to-fine
+        search of the smallest sum of absolute differences between grey planes of half the mosaics' size (the mean of a quad's
+        four samples above black), `levels` pyramid levels (1 .. 6) with a search radius of `radius` (1 .. 8) pixels of the
+        coarsest, so shifts up to about radius * 2 ** levels samples between the frames of a pair are found.  mosaic: (N, H,
+        W), rows contiguous (rows and frames may be strided), odd sizes are fine.  black: one level or four, by CFA position
+        (row & 1) * 2 + (col & 1), integers 0 .. 65535.  ref=None: a chain, every frame against the one before it, the shifts
+        summed from frame 0 on (a clip); ref=r: every frame against frame r (a burst for stack(ref=r)).  Returns the frames'
+        positions, a contiguous int16 tensor (N, 2) as (y, x), clamped to -32768 .. 32767: what merge(pos=) and stack(pos=)
+        take, so ctx.merge(m, lut, shift, pos=ctx.align(m, black=...)) is the whole recipe.  sad=True also returns an int64
+        tensor (N,): the winning sum of absolute differences of the frame's pair over the align_window(H, W, levels, radius)
+        pixels of the grey plane, 0 for the frame without a pair; a scene cut shows as a jump.  Frames too small for the
+        levels and the radius raise ValueError.  The scratch is a tensor of torch's caching allocator.  Queued on
+        torch.cuda.current_stream(); nothing synchronises."""
+        import torch
+        dev = self._torch_device(torch)
+        mosaic, _, n, h, w = self._mosaic_arg(torch, dev, "align", mosaic, dims=(3,))
+        black = [black] * 4 if not hasattr(black, "__len__") else list(black)
+        if len(black) != 4 or any(v != int(v) or v < 0 or v > 65535 for v in black):
+            raise ValueError("align: black is one level or four, by CFA position (row & 1) * 2 + (col & 1), each an integer 0 .. 65535")
+        if ref is not None and (isinstance(ref, bool) or ref != int(ref) or not 0 <= int(ref) < max(n, 1)):
+            raise ValueError("align: ref must be None (a chain) or 0 .. %d, not %r" % (n - 1, ref))
+        align_window(max(h, 1), max(w, 1), levels, radius)
+        pos = torch.empty((n, 2), dtype=torch.int16, device=dev)
+        sums = torch.empty((n,), dtype=torch.int64, device=dev) if sad else None
+        if n == 0:
+            return (pos, sums) if sad else pos
+        src = self._strided("align", "the mosaic", mosaic, h, w)
+        need = int(self._lib.mcraw_align_work_bytes(w, h, n, int(levels), int(radius)))
+        work = torch.empty((need,), dtype=torch.uint8, device=dev)
+        a = Align()
+        a.levels, a.radius, a.ref, a.reserved = int(levels), int(radius), (-1 if ref is None else int(ref)), 0
+        for i in range(4):
+            a.black[i] = int(black[i])
+        a.pos, a.sad, a.work, a.work_bytes = pos.data_ptr(), (sums.data_ptr() if sad else None), work.data_ptr(), need
+        self._call(torch, dev, "mcraw_align_batch", (mosaic, pos, sums, work), C.byref(a), *src, w, h, n)
+        return (pos, sums) if sad else pos
+
     def _denoise_stage(self, mos, denoise, fn):
         """denoise= of the demosaic / decode methods: denoise() with these keyword arguments into a scratch tensor of the
         caching allocator."""
@@ -1500,13 +1575,19 @@ class Context:
         scratch = self._decode_scratch(inputs, width, height, type, check, "decode_stats")
         return self.stats(scratch, bins=bins, shift=shift, sat=sat, roi=roi, out=out, accumulate=accumulate)
 
-    def decode_merge(self, inputs, width, height, type, *, lut, shift, check=True, **merge_kw):
+    def decode_merge(self, inputs, width, height, type, *, lut, shift, check=True, align=None, **merge_kw):
         """Decode frames of one geometry that are resident in HBM and merge them along time (merge()): the plain uint16
         mosaics go to a scratch tensor of torch's caching allocator, both steps are queued on torch.cuda.current_stream().
         inputs: uint8 CUDA tensors, or (device pointer, length) pairs.  check=True synchronises after the decode and raises
         McrawError naming the frames that failed; check=False returns at once.  The stage the context had before the call is
-        restored afterwards.  merge_kw: merge()'s keyword arguments.  Returns merge()'s (count, H, W)."""
+        restored afterwards.  merge_kw: merge()'s keyword arguments.  align: None, or a dict of align()'s keyword arguments
+        (without sad): the decoded frames' positions are estimated and handed to the merge as pos.  Returns merge()'s
+        (count, H, W)."""
+        if align is not None and (not isinstance(align, dict) or "sad" in align or "pos" in merge_kw):
+            raise ValueError("decode_merge: align must be a dict of align()'s keyword arguments (without sad), and excludes pos")
         scratch = self._decode_scratch(inputs, width, height, type, check, "decode_merge")
+        if align is not None:
+            merge_kw["pos"] = self.align(scratch, **align)
         return self.merge(scratch, lut, shift, **merge_kw)
 
     def demosaic(self, mosaic, *, algo="mhc", dtype, white, black=(0, 0, 0, 0), cfa="rggb", gain=None, matrix=None,

@@ -1,4 +1,4 @@
-// mcraw_mosaic.h -- device helpers that the mosaic stages share (mcraw_shade / stats / fixpix / denoise / merge .hip: uint16 mosaics
+// mcraw_mosaic.h -- device helpers that the mosaic stages share (mcraw_shade / stats / fixpix / denoise / merge / align .hip: uint16 mosaics
 // resident in HBM in, lanes that make 8 consecutive columns as 4 dwords of (even column | odd column << 16)).  A unit's tile
 // sizes and store policy reach these helpers as template arguments: no -D switch of a unit is read in here.
 #pragma once

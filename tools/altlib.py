@@ -1,5 +1,5 @@
 """A second build of the library beside the product's, for the benches' --alt-lib (bench_shade / stats / fixpix / denoise /
-merge / rgb / display / yuv .py): python -m motioncam_decoder_amd.build variant PATH -D... makes one, and so does a build of
+merge / align / rgb / display / yuv .py): python -m motioncam_decoder_amd.build variant PATH -D... makes one, and so does a build of
 another commit.  AltLib loads it with ctypes, makes a context of its own in it, and has one method per stage entry point, each
 taking contiguous (N, H, W) uint16 CUDA tensors and the torch stream to queue on.  Also what the demosaic benches build alike:
 their images and device inputs."""
@@ -71,6 +71,8 @@ class AltLib:
                            ("mcraw_merge_batch", M.Merge)):
             getattr(self.lib, fn).argtypes = [C.c_void_p, C.POINTER(struct)] + _MOSAIC_IN + _MOSAIC_OUT + [C.c_void_p]
         self.lib.mcraw_stats_batch.argtypes = [C.c_void_p, C.POINTER(M.Stats)] + _MOSAIC_IN + [C.c_void_p, C.c_size_t, C.c_void_p]
+        if hasattr(self.lib, "mcraw_align_batch"):  # (a build of a commit in front of the stage has none)
+            self.lib.mcraw_align_batch.argtypes = [C.c_void_p, C.POINTER(M.Align)] + _MOSAIC_IN + [C.c_void_p]
         self.lib.mcraw_demosaic_batch.argtypes = [C.c_void_p, C.POINTER(M.RgbParams)] + _DEMOSAIC
         self.lib.mcraw_demosaic_display_batch.argtypes = [C.c_void_p, C.POINTER(M.RgbParams), C.POINTER(M.Display)] + _DEMOSAIC
         self.lib.mcraw_demosaic_yuv_batch.argtypes = [C.c_void_p, C.POINTER(M.RgbParams), C.POINTER(M.Yuv)] + _DEMOSAIC
@@ -113,6 +115,17 @@ class AltLib:
         s.lut_log2, s.shift, s.nluts, s.reserved = int(lut.shape[-1]).bit_length() - 1, shift, 1, 0
         s.lut, s.pos = lut.data_ptr(), None
         self._mosaic_call("mcraw_merge_batch", s, mos, out, stream)
+
+    def align(self, mos, pos, work, stream, levels, radius, black, ref=-1):
+        """Positions into `pos` (a contiguous (N, 2) int16 tensor); work: a uint8 tensor of mcraw_align_work_bytes bytes."""
+        n, h, w = mos.shape
+        a = M.Align()
+        a.levels, a.radius, a.ref, a.reserved = levels, radius, ref, 0
+        for i in range(4):
+            a.black[i] = black[i]
+        a.pos, a.sad, a.work, a.work_bytes = pos.data_ptr(), None, work.data_ptr(), work.numel()
+        rc = self.lib.mcraw_align_batch(self.h, C.byref(a), C.c_void_p(mos.data_ptr()), w, h * w, w, h, n, C.c_void_p(stream.cuda_stream))
+        assert rc == 0, self.lib.mcraw_last_error().decode()
 
     def stats(self, mos, recs, stream, bins, shift, sat, roi=None):
         """Records into `recs` (a contiguous (N, 16 * bins + 96) uint8 tensor); returns a FrameStats over it."""

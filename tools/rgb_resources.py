@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
 """Resource report of the demosaic kernels (csrc/mcraw_rgb.hip), of the lens-shading kernel (csrc/mcraw_shade.hip), of the
 statistics kernels (csrc/mcraw_stats.hip), of the defective-pixel kernels (csrc/mcraw_fixpix.hip), of the denoising kernel
-(csrc/mcraw_denoise.hip) and of the temporal merge (csrc/mcraw_merge.hip): compiles the files for gfx950 with -Rpass-analysis=kernel-resource-usage (no GPU needed) and prints
+(csrc/mcraw_denoise.hip), of the temporal merge (csrc/mcraw_merge.hip) and of the shift estimate (csrc/mcraw_align.hip): compiles the files for gfx950 with -Rpass-analysis=kernel-resource-usage (no GPU needed) and prints
 one line per instance in the format of profiles/rgb_resources.txt / display_resources.txt / yuv_resources.txt /
-shade_resources.txt / stats_resources.txt / fixpix_resources.txt / denoise_resources.txt / merge_resources.txt.
+shade_resources.txt / stats_resources.txt / fixpix_resources.txt / denoise_resources.txt / merge_resources.txt / align_resources.txt.
 
     python tools/rgb_resources.py            # every instance
-    python tools/rgb_resources.py --check    # the figures in the eight committed files must equal the compiler's; exit 1 if not
+    python tools/rgb_resources.py --check    # the figures in the nine committed files must equal the compiler's; exit 1 if not
 """
 import os
 import re
@@ -30,6 +30,8 @@ DENOISE_FILE = "denoise_resources.txt"
 DENOISE_NAME = r"Function Name: _ZN5mcraw\d+(kdenoise)ILi([12])ELb([01])EEEv"  # kdenoise<RADIUS, NT>
 MERGE_FILE = "merge_resources.txt"
 MERGE_NAME = r"Function Name: _ZN5mcraw\d+(kmerge)ILi([01])ELb([01])EEEv"  # kmerge<SUPPORT, NT>
+ALIGN_FILE = "align_resources.txt"
+ALIGN_NAME = r"Function Name: _ZN5mcraw\d+(kalign_[a-z]+)(?:ILi([01])EEEv|E)"  # kalign_sad<R = 1: nine candidates in registers; 0: a loop>, the others
 SHADE_NAME = r"Function Name: _ZN5mcraw\d+(kshade)ILb([01])EEEv"  # kshade<NT>: `sc1 nt` streaming stores or plain ones
 
 
@@ -46,6 +48,10 @@ def _label(m):
         return "kdenoise<R=%s,%s>" % (m.group(2), "stream" if m.group(3) == "1" else "plain")
     if m.group(1) == "kmerge":
         return "kmerge<S=%s,%s>" % (m.group(2), "stream" if m.group(3) == "1" else "plain")
+    if m.group(1) == "kalign_sad":
+        return "kalign_sad<%s>" % ("refine" if m.group(2) == "1" else "coarse")
+    if m.group(1).startswith("kalign_"):
+        return m.group(1)
     if m.group(1) == "kshade":
         return "kshade<%s>" % ("stream" if m.group(2) == "1" else "plain")
     return "%s<%s,S=%s>" % (m.group(1), KINDS[int(m.group(2))], m.group(3))
@@ -90,14 +96,15 @@ def _check(files, rep, prefix):
 def main():
     rep, shade, stats = report(), report("mcraw_shade.hip", SHADE_NAME), report("mcraw_stats.hip", STATS_NAME)
     fixpix, denoise = report("mcraw_fixpix.hip", FIXPIX_NAME), report("mcraw_denoise.hip", DENOISE_NAME)
-    merge = report("mcraw_merge.hip", MERGE_NAME)
+    merge, align = report("mcraw_merge.hip", MERGE_NAME), report("mcraw_align.hip", ALIGN_NAME)
     if "--check" not in sys.argv:
         for line in list(rep.values()) + list(shade.values()) + list(stats.values()) + list(fixpix.values()) + list(denoise.values()) + \
-                list(merge.values()):
+                list(merge.values()) + list(align.values()):
             print(line)
         return 0
     return _check(FILES, rep, "krgb_") | _check((SHADE_FILE,), shade, "kshade") | _check((STATS_FILE,), stats, "kstats") | \
-        _check((FIXPIX_FILE,), fixpix, "kfixpix") | _check((DENOISE_FILE,), denoise, "kdenoise") | _check((MERGE_FILE,), merge, "kmerge")
+        _check((FIXPIX_FILE,), fixpix, "kfixpix") | _check((DENOISE_FILE,), denoise, "kdenoise") | _check((MERGE_FILE,), merge, "kmerge") | \
+        _check((ALIGN_FILE,), align, "kalign")
 
 
 if __name__ == "__main__":
