@@ -448,6 +448,52 @@ int mcraw_demosaic_yuv_batch(mcraw_ctx *ctx, const mcraw_rgb *p, const mcraw_yuv
                              int ncolors, const uint16_t *in, size_t in_pitch, size_t in_frame_stride, int width,
                              int height, int n, void *out, size_t out_bytes, void *stream);
 
+/* ---- uint16 mosaics -> any output size: an area downscale of a crop window, into all three output families ---------
+ *
+ * BIN2 generalised from "one quad per output pixel" to "the quads under the pixel's footprint": a crop of cw x ch samples at
+ * (x0, y0) of every mosaic, Qw = cw / 2 by Qh = ch / 2 CFA quads, becomes out_h x out_w pixels, each the area average of the
+ * quads that its footprint covers.  One pass over the cropped mosaic, integers up to the colour stage, no interpolation.
+ * Output family: `d` and `y` NULL: the float family (mcraw_demosaic_batch: p->dtype, p->flags); `d`: the display family
+ * (mcraw_demosaic_display_batch); `y`: the YUV family (mcraw_demosaic_yuv_batch); both: rejected.  p->algo must be
+ * MCRAW_RGB_AREA, which the three other entry points keep rejecting.
+ * Bit-exact arithmetic.  e_c(qy, qx): BIN2's estimates of quad (qy, qx) of the crop, E_R = 2 d(r), E_G = d(g1) + d(g2),
+ * E_B = 2 d(b), d = s - black[p] (int32).  Per axis, Q quads (Qw, Qh) onto O pixels (out_w, out_h):
+ *   c(k, q)    = clamp(floor((256 * (q * O - k * Q) + (Q >> 1)) / Q), 0, 256)     64-bit, floor division
+ *   w(k, q)    = c(k, q + 1) - c(k, q)                                             q from q0(k) = floor(k * Q / O)
+ *   h_c(qy, k) = sum_q wx(k, q) * e_c(qy, q)                                       int32, |h| <= 256 * 131070
+ *   t_c(qy, k) = (h_c + 8) >> 4                                                    arithmetic shift; units of 1/32
+ *   v_c(j, k)  = sum_q wy(j, q) * t_c(q, k)                                        int32, |v| < 2^30
+ *   E_c(j, k)  = (v_c + 128) >> 8                                                  units of 1/32; |E| < 2^22, exact as float
+ *   host, f32: k[c] = (gain[c] * inv) * 0.03125f                                   inv as in mcraw_demosaic_batch
+ * The weights are the overlap of the footprint [k Q / O, (k + 1) Q / O) with each quad, rounded cumulatively: 256 per pixel
+ * in all, none negative, at most 17 per axis.  A flat frame comes out flat (E = 32 d), greys stay neutral, and with
+ * cw = 2 out_w, ch = 2 out_h the result is MCRAW_RGB_BIN2's of the crop, bit for bit.  From E_c and k[c] on everything is the
+ * family's own entry point: colour stage, clamp, LUT, matrix, layouts, with Ho = out_h, Wo = out_w.
+ * Accepted: x0, y0, cw, ch even, cw, ch >= 2, x0 + cw <= width, y0 + ch <= height; 1 <= out_w <= Qw <= 16 out_w and likewise
+ * out_h; the YUV family needs an even out_w and out_h; width, height, in, in_pitch, in_frame_stride, colors, out and
+ * out_bytes follow the family's entry point.  A ratio under 2 samples per pixel (more pixels than quads) needs a real
+ * demosaic in front of a resampler and is out of scope: run MCRAW_RGB_MHC and resize its output.
+ * `work`: the caller's DEVICE memory, 16-byte aligned, at least mcraw_area_work_bytes(a) bytes.  A small kernel queued on
+ * `stream` in front of the demosaic writes the per-column and per-row weight tables into it; nothing is cached in the
+ * context, nothing waits for the host, and calls queued on one stream may share one `work`.
+ * Rejected (returns < 0, mcraw_last_error says why, starting with "mcraw_demosaic_area_batch: ", nothing is written):
+ * everything the family's own entry point rejects; a NULL `a`; a p->algo other than MCRAW_RGB_AREA; both `d` and `y`; an odd,
+ * empty or out-of-frame crop; a size outside the ratio rule; a non-zero `reserved`; a NULL or misaligned `work`; work_bytes
+ * below mcraw_area_work_bytes(a).  n == 0 is a no-op.  The call takes no decode serial, leaves the decode slots,
+ * mcraw_ctx_errors and the context's stage alone, and has no kernel id of its own (time it with events on `stream`). */
+#define MCRAW_RGB_AREA 3   /* valid in mcraw_demosaic_area_batch only */
+typedef struct mcraw_area {
+    uint32_t x0, y0;        /* crop origin in the mosaic, both even                 */
+    uint32_t cw, ch;        /* crop size, both even, >= 2; x0 + cw <= width, ...    */
+    uint32_t out_w, out_h;  /* Wo, Ho                                               */
+    uint32_t reserved[2];   /* must be 0                                            */
+} mcraw_area;               /* sizeof 32; y0 4, cw 8, ch 12, out_w 16, out_h 20, reserved 24 */
+size_t mcraw_area_work_bytes(const mcraw_area *a);  /* 0 for a rejected geometry */
+int mcraw_demosaic_area_batch(mcraw_ctx *ctx, const mcraw_rgb *p, const mcraw_area *a, const mcraw_display *d,
+                              const mcraw_yuv *y, const mcraw_rgb_color *colors, int ncolors, const uint16_t *in,
+                              size_t in_pitch, size_t in_frame_stride, int width, int height, int n, void *work,
+                              size_t work_bytes, void *out, size_t out_bytes, void *stream);
+
 /* ---- uint16 mosaics -> uint16 mosaics with a lens-shading gain map applied ----------------------------------------
  *
  * Multiplies what `n` uint16 mosaics of width x height hold above their black level by a per-pixel gain that is bilinearly

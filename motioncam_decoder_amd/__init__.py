@@ -18,7 +18,7 @@ __all__ = ["lib_path", "load", "Context", "Pool", "Frame", "EncFrame", "FloatOut
            "DISP_CHW", "DISP_HWC", "Yuv", "YUV_NV12", "YUV_P010", "yuv_matrix", "yuv_planes", "Shade", "gain_map",
            "shading_map", "Stats", "STATS_ACCUMULATE", "FrameStats", "stats_white_balance", "stats_percentile",
            "stats_clipped", "FixPix", "FIXPIX_HOT", "FIXPIX_COLD", "pack_pixels", "Denoise", "noise_lut", "Merge", "Align",
-           "align_window"]
+           "align_window", "fit_crop", "Area", "RGB_AREA"]
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 
@@ -47,7 +47,7 @@ ABI_SYMBOLS = [
     "mcraw_encode_bound7", "mcraw_encode_batch", "mcraw_encode7", "mcraw_ctx_set_float_out", "mcraw_pool_set_float_out",
     "mcraw_demosaic_batch", "mcraw_demosaic_display_batch", "mcraw_demosaic_yuv_batch", "mcraw_shade_batch",
     "mcraw_stats_batch", "mcraw_stats_record_bytes", "mcraw_fixpix_batch", "mcraw_denoise_batch",
-    "mcraw_merge_batch", "mcraw_align_batch", "mcraw_align_work_bytes",
+    "mcraw_merge_batch", "mcraw_align_batch", "mcraw_align_work_bytes", "mcraw_demosaic_area_batch", "mcraw_area_work_bytes",
 ]
 
 POST_BLACK, POST_PACK12, POST_PACK10, POST_PACK14 = 1, 2, 4, 8
@@ -124,7 +124,8 @@ def float_out(dtype, white, layout="planes", black=(0, 0, 0, 0), clip=False, pla
 
 # demosaic to planar linear RGB (mcraw_demosaic_batch)
 RGB_MHC, RGB_BIN2 = 1, 2
-_RGB_ALGOS = {"mhc": RGB_MHC, "bin2": RGB_BIN2}
+RGB_AREA = 3  # mcraw_demosaic_area_batch only
+_RGB_ALGOS = {"mhc": RGB_MHC, "bin2": RGB_BIN2, "area": RGB_AREA}
 _CFA_CODES = {"rggb": 0, "bggr": 1, "grbg": 2, "gbrg": 3}
 
 
@@ -137,6 +138,34 @@ class RgbParams(C.Structure):
 class RgbColor(C.Structure):
     """struct mcraw_rgb_color (include/mcraw_hip.h): white-balance gains and a row-major 3x3 matrix, out = m . v."""
     _fields_ = [("gain", C.c_float * 3), ("m", C.c_float * 9)]
+
+
+class Area(C.Structure):
+    """struct mcraw_area (include/mcraw_hip.h): the crop window in the mosaic and the output size."""
+    _fields_ = [("x0", C.c_uint32), ("y0", C.c_uint32), ("cw", C.c_uint32), ("ch", C.c_uint32), ("out_w", C.c_uint32),
+                ("out_h", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+def fit_crop(height, width, Ho, Wo):
+    """The largest centred crop (y0, x0, h, w) of a height x width mosaic that has the output's aspect ratio Wo : Ho, for
+    algo="area": h = 2 Ho t and w = 2 Wo t for the largest t (a real number) that fits, both rounded down to even numbers, the
+    origin rounded down to even.  Raises ValueError when the sizes are no positive integers or when the crop breaks the ratio
+    rule of mcraw_demosaic_area_batch (Ho <= h / 2 <= 16 Ho, Wo <= w / 2 <= 16 Wo).  fit_crop(3024, 4032, 1080, 1920) is
+    (378, 0, 2268, 4032)."""
+    for v in (height, width, Ho, Wo):
+        if isinstance(v, bool) or v != int(v) or int(v) < 1:
+            raise ValueError("fit_crop: sizes must be positive integers, not %r" % (v,))
+    height, width, Ho, Wo = int(height), int(width), int(Ho), int(Wo)
+    if width * Ho <= height * Wo:  # the width binds
+        w = width // 2 * 2
+        h = (width * Ho) // Wo // 2 * 2
+    else:
+        h = height // 2 * 2
+        w = (height * Wo) // Ho // 2 * 2
+    if not (Ho <= h // 2 <= 16 * Ho and Wo <= w // 2 <= 16 * Wo):
+        raise ValueError("fit_crop: a %d x %d crop of a %d x %d mosaic onto %d x %d is outside 1 .. 16 quads per pixel"
+                         % (h, w, height, width, Ho, Wo))
+    return ((height - h) // 4 * 2, (width - w) // 4 * 2, h, w)
 
 
 # display-ready integer RGB through a transfer-curve LUT (mcraw_demosaic_display_batch)
@@ -810,6 +839,12 @@ def load():
     lib.mcraw_align_batch.restype = C.c_int
     lib.mcraw_align_batch.argtypes = [C.c_void_p, C.POINTER(Align), C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int,
                                       C.c_void_p]
+    lib.mcraw_area_work_bytes.restype = C.c_size_t
+    lib.mcraw_area_work_bytes.argtypes = [C.POINTER(Area)]
+    lib.mcraw_demosaic_area_batch.restype = C.c_int
+    lib.mcraw_demosaic_area_batch.argtypes = [C.c_void_p, C.POINTER(RgbParams), C.POINTER(Area), C.POINTER(Display), C.POINTER(Yuv),
+                                              C.POINTER(RgbColor), C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int,
+                                              C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.mcraw_encode7.restype = C.c_size_t
     lib.mcraw_encode7.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int]
     _lib = lib
@@ -1591,7 +1626,7 @@ class Context:
         return self.merge(scratch, lut, shift, **merge_kw)
 
     def demosaic(self, mosaic, *, algo="mhc", dtype, white, black=(0, 0, 0, 0), cfa="rggb", gain=None, matrix=None,
-                 clip=False, out=None, check=True, shading=None, defects=None, denoise=None):
+                 clip=False, out=None, check=True, shading=None, defects=None, denoise=None, size=None, crop=None):
         """uint16 mosaics resident on the context's device -> planar linear RGB, (N, 3, H, W) for algo "mhc" (Malvar-He-
         Cutler) or (N, 3, H/2, W/2) for "bin2" (one pixel per 2x2 quad), as torch.float32 / float16 / bfloat16 ("f32" /
         "f16" / "bf16").  mosaic: a CUDA uint16 tensor (N, H, W) or (H, W) whose rows are contiguous (rows and frames may
@@ -1605,11 +1640,16 @@ class Context:
         defaults to this call's): the defective pixels are taken out first, into a scratch tensor, in front of shading=
         (gains change the differences between neighbours); None: no such stage.  denoise: a dict of denoise()'s
         keyword arguments (lut, shift, radius, amount), applied behind defects= and in front of shading=, into a scratch
-        tensor: the noise model holds for the sensor's values, not for the shaded ones; None: no such stage."""
+        tensor: the noise model holds for the sensor's values, not for the shaded ones; None: no such stage.
+        algo "area" with size=(Ho, Wo) and crop=(y0, x0, h, w) (default: the whole frame; fit_crop gives a centred one of the
+        output's aspect ratio) is an area downscale (mcraw_demosaic_area_batch): every output pixel is the average of the
+        CFA quads under its footprint in the crop, 1 .. 16 quads per pixel along each axis, the origin and size of the crop
+        even; the result is (N, 3, Ho, Wo), and with h = 2 Ho, w = 2 Wo it is "bin2" of the crop, bit for bit.  The stages in
+        front run on the whole mosaic.  size= or crop= with another algo, or "area" without size=, raises ValueError."""
         import torch
         code = _float_code(dtype)
         tdtype = {FLOAT_F32: torch.float32, FLOAT_F16: torch.float16, FLOAT_BF16: torch.bfloat16}[code]
-        front = self._demosaic_front("demosaic", mosaic, algo, cfa, black, defects, denoise, shading)
+        front = self._demosaic_front("demosaic", mosaic, algo, cfa, black, defects, denoise, shading, size, crop)
         ho, wo = front[6:8]
         out = self._demosaic_out("demosaic", front, out, (3, ho, wo), tdtype)
         if front[2] == 0:
@@ -1617,14 +1657,19 @@ class Context:
         return self._demosaic_call("mcraw_demosaic_batch", "demosaic", front, algo, code, FLOAT_CLIP if clip else 0, white, black,
                                    gain, matrix, out)
 
-    def _demosaic_front(self, fn, mosaic, algo, cfa, black, defects, denoise, shading):
+    def _demosaic_front(self, fn, mosaic, algo, cfa, black, defects, denoise, shading, size=None, crop=None):
         """What demosaic / demosaic_display / demosaic_yuv (`fn`) do alike in front of their output: the algo and cfa checks,
         the mosaic argument, the optional stages -- defects, then denoise, then shading, each into a scratch tensor (the
         caller's mosaic stays as it is), none for an empty batch -- and the output size.  Returns (mos, single, n, h, w, src,
-        ho, wo, key): src is _strided's triple (None for no frames), key the cfa's."""
+        ho, wo, key, area): src is _strided's triple (None for no frames), key the cfa's, area the (y0, x0, h, w) crop of algo
+        "area" (None for the other algos), whose output size is `size`."""
         import torch
         if algo not in _RGB_ALGOS:
-            raise ValueError("algo must be 'mhc' or 'bin2', not %r" % (algo,))
+            raise ValueError("algo must be 'mhc', 'bin2' or 'area', not %r" % (algo,))
+        if algo != "area" and (size is not None or crop is not None):
+            raise ValueError("%s: size= and crop= belong to algo='area', not %r" % (fn, algo))
+        if algo == "area" and size is None:
+            raise ValueError("%s: algo='area' needs size=(Ho, Wo)" % fn)
         key = str(cfa).strip().lower()
         if key not in _CFA_CODES:
             raise ValueError("unknown cfa %r (rggb, bggr, grbg or gbrg)" % (cfa,))
@@ -1635,8 +1680,18 @@ class Context:
             mos = self.shade(mos, shading, black=black)
         n, h, w = (int(v) for v in mos.shape)
         src = self._strided(fn, "the mosaic", mos, h, w) if n else None
-        ho, wo = (h, w) if algo == "mhc" else (h // 2, w // 2)
-        return mos, single, n, h, w, src, ho, wo, key
+        area = None
+        if algo == "area":
+            try:
+                ho, wo = (int(v) for v in size)
+                area = (0, 0, h // 2 * 2, w // 2 * 2) if crop is None else tuple(int(v) for v in crop)
+            except (TypeError, ValueError):
+                raise ValueError("%s: size must be (Ho, Wo) and crop (y0, x0, h, w)" % fn) from None
+            if len(area) != 4 or min(area) < 0 or ho < 1 or wo < 1 or max(area + (ho, wo)) > 65536:
+                raise ValueError("%s: size must be (Ho, Wo) and crop (y0, x0, h, w), all 0 .. 65536, not %r and %r" % (fn, size, crop))
+        else:
+            ho, wo = (h, w) if algo == "mhc" else (h // 2, w // 2)
+        return mos, single, n, h, w, src, ho, wo, key, area
 
     def _pre_stages(self, fn, mos, black, defects, denoise):
         """defects= and denoise= of the demosaic / decode methods, in that order, each into a scratch tensor; an empty batch
@@ -1658,9 +1713,24 @@ class Context:
         """The tail of the three demosaics: colours, params and the library's `symbol` (stage: its display / YUV struct, None
         for the float entry; extra: further tensors that take part).  Returns out."""
         import torch
-        mos, _, n, h, w, src, _, _, key = front
+        mos, _, n, h, w, src, ho, wo, key, area = front
         cols, nc = _rgb_colors(gain, matrix, n, fn)
         prm = _rgb_params(algo, dtype_code, flags, key, white, black)
+        if area is not None:  # one entry point for the three families; its scratch lives as long as the call's other tensors
+            a = Area()
+            a.y0, a.x0, a.ch, a.cw = area
+            a.out_h, a.out_w = ho, wo
+            need = int(self._lib.mcraw_area_work_bytes(C.byref(a)))
+            if need == 0:
+                raise ValueError("%s: crop %r onto size %r: the crop must be even and not empty, and hold 1 .. 16 quads per output "
+                                 "pixel along each axis" % (fn, area, (ho, wo)))
+            work = torch.empty((need,), dtype=torch.uint8, device=mos.device)
+            d = C.byref(stage) if isinstance(stage, Display) else None
+            y = C.byref(stage) if isinstance(stage, Yuv) else None
+            self._call(torch, mos.device, "mcraw_demosaic_area_batch", (mos, out, work) + tuple(extra), C.byref(prm), C.byref(a), d, y,
+                       cols, nc, *src, w, h, n, C.c_void_p(work.data_ptr()), need, C.c_void_p(out.data_ptr()),
+                       out.numel() * out.element_size())
+            return out
         structs = (C.byref(prm),) if stage is None else (C.byref(prm), C.byref(stage))
         self._call(torch, mos.device, symbol, (mos, out) + tuple(extra), *structs, cols, nc, *src, w, h, n,
                    C.c_void_p(out.data_ptr()), out.numel() * out.element_size())
@@ -1709,9 +1779,10 @@ class Context:
         return scratch
 
     def decode_rgb(self, inputs, width, height, type, *, algo="mhc", dtype, white, black=(0, 0, 0, 0), cfa="rggb",
-                   gain=None, matrix=None, clip=False, out=None, check=True, shading=None, defects=None, denoise=None):
+                   gain=None, matrix=None, clip=False, out=None, check=True, shading=None, defects=None, denoise=None, size=None,
+                   crop=None):
         """Decode frames of one geometry that are resident in HBM and demosaic them (demosaic()): (N, 3, H, W) for "mhc",
-        (N, 3, H/2, W/2) for "bin2".  inputs: uint8 CUDA tensors, or (device pointer, length) pairs.  The plain uint16
+        (N, 3, H/2, W/2) for "bin2", (N, 3, Ho, Wo) for "area" with size=(Ho, Wo) and crop=.  inputs: uint8 CUDA tensors, or (device pointer, length) pairs.  The plain uint16
         mosaics go to a scratch tensor of torch's caching allocator; both steps are queued on torch.cuda.current_stream().
         check=True synchronises after the decode and raises McrawError naming the frames that failed; check=False returns
         at once.  The stage the context had before the call is restored afterwards.  shading: a lens-shading gain map
@@ -1720,7 +1791,7 @@ class Context:
         dict of denoise()'s keyword arguments, applied behind defects= and in front of shading=."""
         scratch = self._decode_front("decode_rgb", inputs, width, height, type, check, black, defects, denoise, shading)
         return self.demosaic(scratch, algo=algo, dtype=dtype, white=white, black=black, cfa=cfa, gain=gain, matrix=matrix,
-                             clip=clip, out=out, check=check)
+                             clip=clip, out=out, check=check, size=size, crop=crop)
 
     def _display_lut(self, torch, dev, fn, transfer, lut_size, bits):
         """(device LUT tensor, caller-owned?) for demosaic_display / demosaic_yuv (`fn`): a ready 1-D uint16 LUT (CUDA tensor on
@@ -1753,7 +1824,7 @@ class Context:
 
     def demosaic_display(self, mosaic, *, algo="mhc", white, black=(0, 0, 0, 0), cfa="rggb", gain=None, matrix=None,
                          transfer="srgb", lut_size=4096, dtype=None, layout="hwc", bits=None, out=None, check=True, shading=None,
-                         defects=None, denoise=None):
+                         defects=None, denoise=None, size=None, crop=None):
         """uint16 mosaics resident on the context's device -> display-ready integer RGB: the demosaic and colours of
         demosaic(), then clamp to [0, 1], index a transfer-curve LUT of L entries at rint(c * (L - 1)) and store the entry
         (its low byte for uint8).  dtype: torch.uint8 (default) or torch.uint16; layout "hwc" gives (N, Ho, Wo, 3), "chw"
@@ -1761,7 +1832,8 @@ class Context:
         on [0, 1] -- built by transfer_lut(transfer, lut_size, bits), bits 8 for uint8 and 16 for uint16 unless given --
         or a ready 1-D uint16 LUT (host array or CUDA tensor) whose length is a power of two, 256 .. 65536.  Queued on
         torch.cuda.current_stream(); nothing synchronises, and a caller's LUT is read when the kernels run (in stream
-        order).  `check` is accepted for symmetry with decode_display.  shading, defects, denoise: as demosaic()."""
+        order).  `check` is accepted for symmetry with decode_display.  shading, defects, denoise, and algo "area" with size=
+        and crop=: as demosaic()."""
         import torch
         dtype = torch.uint8 if dtype is None else dtype
         dcode = {torch.uint8: DISP_U8, torch.uint16: DISP_U16, "u8": DISP_U8, "u16": DISP_U16}.get(dtype)
@@ -1769,7 +1841,7 @@ class Context:
             raise ValueError("demosaic_display: dtype must be torch.uint8 or torch.uint16, not %r" % (dtype,))
         if layout not in _DISP_LAYOUTS:
             raise ValueError("demosaic_display: layout must be 'hwc' or 'chw', not %r" % (layout,))
-        front = self._demosaic_front("demosaic_display", mosaic, algo, cfa, black, defects, denoise, shading)
+        front = self._demosaic_front("demosaic_display", mosaic, algo, cfa, black, defects, denoise, shading, size, crop)
         ho, wo = front[6:8]
         out = self._demosaic_out("demosaic_display", front, out, (ho, wo, 3) if layout == "hwc" else (3, ho, wo),
                                  torch.uint8 if dcode == DISP_U8 else torch.uint16)
@@ -1785,7 +1857,7 @@ class Context:
 
     def decode_display(self, inputs, width, height, type, *, algo="mhc", white, black=(0, 0, 0, 0), cfa="rggb", gain=None,
                        matrix=None, transfer="srgb", lut_size=4096, dtype=None, layout="hwc", bits=None, out=None, check=True, shading=None,
-                       defects=None, denoise=None):
+                       defects=None, denoise=None, size=None, crop=None):
         """Decode frames of one geometry that are resident in HBM and turn them into display-ready RGB
         (demosaic_display()), as decode_rgb does: the plain uint16 mosaics go to a scratch tensor, both steps are queued on
         torch.cuda.current_stream(), check=True synchronises after the decode and raises McrawError naming the frames that
@@ -1793,11 +1865,11 @@ class Context:
         scratch = self._decode_front("decode_display", inputs, width, height, type, check, black, defects, denoise, shading)
         return self.demosaic_display(scratch, algo=algo, white=white, black=black, cfa=cfa, gain=gain, matrix=matrix,
                                      transfer=transfer, lut_size=lut_size, dtype=dtype, layout=layout, bits=bits, out=out,
-                                     check=check)
+                                     check=check, size=size, crop=crop)
 
     def demosaic_yuv(self, mosaic, *, algo="mhc", white, black=(0, 0, 0, 0), cfa="rggb", gain=None, matrix=None, fmt="nv12",
                      standard="bt709", range="limited", transfer="bt709", lut_size=4096, in_bits=None, out=None, check=True, shading=None,
-                     defects=None, denoise=None):
+                     defects=None, denoise=None, size=None, crop=None):
         """uint16 mosaics resident on the context's device -> video-ready Y'CbCr 4:2:0: the demosaic, colours, clamp and
         transfer-curve LUT of demosaic_display(), then the integer matrix of yuv_matrix(standard, range) and a 2x2 box
         average for the chroma (sited at the block's centre).  fmt "nv12": torch.uint8; "p010": torch.uint16 holding
@@ -1806,14 +1878,15 @@ class Context:
         gives the two as views.  Ho and Wo must be even (bin2: H and W multiples of 4).  transfer: as demosaic_display; a
         built-in curve is transfer_lut(transfer, lut_size, in_bits), in_bits defaulting to 12 (nv12) or 16 (p010); a ready
         LUT may hold entries of any in_bits 8 .. 16 (higher bits are masked off).  Queued on torch.cuda.current_stream();
-        nothing synchronises.  `check` is accepted for symmetry with decode_yuv.  shading, defects, denoise: as demosaic()."""
+        nothing synchronises.  `check` is accepted for symmetry with decode_yuv.  shading, defects, denoise, and algo "area"
+        with size= (both even) and crop=: as demosaic()."""
         import torch
         if fmt not in _YUV_FORMATS:
             raise ValueError("demosaic_yuv: fmt must be 'nv12' or 'p010', not %r" % (fmt,))
         fcode, bits, default_in = _YUV_FORMATS[fmt]
         in_bits = default_in if in_bits is None else in_bits
         cy, cb, cr, sh, y_off, c_off = yuv_matrix(standard, range, bits, in_bits)
-        front = self._demosaic_front("demosaic_yuv", mosaic, algo, cfa, black, defects, denoise, shading)
+        front = self._demosaic_front("demosaic_yuv", mosaic, algo, cfa, black, defects, denoise, shading, size, crop)
         ho, wo = front[6:8]
         out = self._demosaic_out("demosaic_yuv", front, out, (ho * 3 // 2, wo), torch.uint8 if fcode == YUV_NV12 else torch.uint16)
         if front[2] == 0:
@@ -1830,7 +1903,7 @@ class Context:
 
     def decode_yuv(self, inputs, width, height, type, *, algo="mhc", white, black=(0, 0, 0, 0), cfa="rggb", gain=None,
                    matrix=None, fmt="nv12", standard="bt709", range="limited", transfer="bt709", lut_size=4096, in_bits=None,
-                   out=None, check=True, shading=None, defects=None, denoise=None):
+                   out=None, check=True, shading=None, defects=None, denoise=None, size=None, crop=None):
         """Decode frames of one geometry that are resident in HBM and turn them into NV12 / P010 (demosaic_yuv()), as
         decode_display does: the plain uint16 mosaics go to a scratch tensor, both steps are queued on
         torch.cuda.current_stream(), check=True synchronises after the decode and raises McrawError naming the frames that
@@ -1838,7 +1911,7 @@ class Context:
         scratch = self._decode_front("decode_yuv", inputs, width, height, type, check, black, defects, denoise, shading)
         return self.demosaic_yuv(scratch, algo=algo, white=white, black=black, cfa=cfa, gain=gain, matrix=matrix, fmt=fmt,
                                  standard=standard, range=range, transfer=transfer, lut_size=lut_size, in_bits=in_bits, out=out,
-                                 check=check)
+                                 check=check, size=size, crop=crop)
 
     def profile(self, enable=True, only=None, every=1):
         """Bracket kernel launches with events: all kernels, or just the names in `only`; every `every`-th launch."""

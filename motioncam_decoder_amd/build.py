@@ -45,7 +45,7 @@ HIP_SOURCES = ("mcraw_abi.hip", "mcraw_submit.hip", "mcraw_tune.hip", "mcraw_dev
                "mcraw_type7.hip", "mcraw_type6.hip", "mcraw_encode7.hip", "mcraw_rgb.hip", "mcraw_shade.hip", "mcraw_stats.hip",
                "mcraw_fixpix.hip", "mcraw_denoise.hip", "mcraw_merge.hip", "mcraw_align.hip")
 HIP_HEADERS = ("mcraw_plan.h", "mcraw_dev.h", "mcraw_host.h", "mcraw_race.h", "mcraw_mosaic.h", "mcraw_mosaic_args.h",
-               "mcraw_rgb_args.h", "mcraw_align_args.h")
+               "mcraw_rgb_args.h", "mcraw_align_args.h", "mcraw_area_args.h")
 HIP_FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc"]
 
 

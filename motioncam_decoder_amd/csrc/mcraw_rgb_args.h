@@ -48,26 +48,11 @@ inline bool finite_all(const float *v, int n)
     return true;
 }
 
-// Why the call is rejected, or nullptr with `plan` filled.  d: the display stage, yv: the YUV stage (never both); neither:
-// the float entry.  Addresses are only looked at as numbers.
-inline const char *rgb_check(const mcraw_rgb *p, const mcraw_display *d, const mcraw_yuv *yv, const mcraw_rgb_color *colors,
-                             int ncolors, const uint16_t *in, size_t in_pitch, size_t in_frame_stride, int width, int height, int n,
-                             const void *out, size_t out_bytes, RgbPlan &plan)
+// The pieces of rgb_check that mcraw_demosaic_area_batch's check (mcraw_area_args.h) runs as well, in rgb_check's order.
+// rgb_check_stage: the display / YUV struct, dtype, cfa, flags, white and the colours; sets plan.kind.
+inline const char *rgb_check_stage(const mcraw_rgb *p, const mcraw_display *d, const mcraw_yuv *yv, const mcraw_rgb_color *colors,
+                                   int ncolors, int n, RgbPlan &plan)
 {
-    plan = RgbPlan{};
-    if (!p || n < 0)
-        return "bad arguments";
-    if (n == 0) {
-        plan.noop = true;
-        return nullptr;
-    }
-    if (width < 4 || height < 4 || (width & 1) || (height & 1) || width > 65536 || height > 65536)
-        return "width and height must be even, 4 .. 65536";
-    const MosaicBatch I(in, in_pitch, in_frame_stride, static_cast<size_t>(n), width, height);
-    if (const char *why = I.check())
-        return why;
-    if (p->algo != MCRAW_RGB_MHC && p->algo != MCRAW_RGB_BIN2)
-        return "unknown algo";
     const uint16_t *lut = d ? d->lut : yv ? yv->lut : nullptr;
     const uint32_t lut_log2 = d ? d->lut_log2 : yv ? yv->lut_log2 : 0u;
     if (d || yv) {
@@ -124,21 +109,54 @@ inline const char *rgb_check(const mcraw_rgb *p, const mcraw_display *d, const m
     for (int i = 0; i < ncolors; i++)
         if (!finite_all(colors[i].gain, 3) || !finite_all(colors[i].m, 9))
             return "non-finite gain or matrix entry";
-    plan.mhc = p->algo == MCRAW_RGB_MHC;
+    return nullptr;
+}
+
+// rgb_check_out: `out` against plan.kind, plan.Ho and plan.Wo; sets es, frame_samples, out_frame and the CFA's shift.
+inline const char *rgb_check_out(const mcraw_rgb *p, bool yuv, int n, const void *out, size_t out_bytes, RgbPlan &plan)
+{
     plan.es = out_es(plan.kind);
+    plan.frame_samples = yuv ? plan.Ho * plan.Wo / 2u * 3u : 3u * plan.Ho * plan.Wo;
+    if (out_bytes / plan.es / plan.frame_samples < static_cast<size_t>(n))
+        return yuv ? "out_bytes below n * Ho * Wo * 3 / 2 * sample size" : "out_bytes below n * 3 * Ho * Wo * element size";
+    if (!out || (reinterpret_cast<uintptr_t>(out) & (plan.es - 1u)))
+        return "in / out missing or not aligned to their element size";
+    plan.out_frame = plan.frame_samples * plan.es;
+    constexpr int shift_of[4] = {0, 3, 1, 2}; // MCRAW_CFA_* -> role shift: RGGB 0, BGGR 3, GRBG 1, GBRG 2
+    plan.shift = shift_of[p->cfa];
+    return nullptr;
+}
+
+// Why the call is rejected, or nullptr with `plan` filled.  d: the display stage, yv: the YUV stage (never both); neither:
+// the float entry.  Addresses are only looked at as numbers.
+inline const char *rgb_check(const mcraw_rgb *p, const mcraw_display *d, const mcraw_yuv *yv, const mcraw_rgb_color *colors,
+                             int ncolors, const uint16_t *in, size_t in_pitch, size_t in_frame_stride, int width, int height, int n,
+                             const void *out, size_t out_bytes, RgbPlan &plan)
+{
+    plan = RgbPlan{};
+    if (!p || n < 0)
+        return "bad arguments";
+    if (n == 0) {
+        plan.noop = true;
+        return nullptr;
+    }
+    if (width < 4 || height < 4 || (width & 1) || (height & 1) || width > 65536 || height > 65536)
+        return "width and height must be even, 4 .. 65536";
+    const MosaicBatch I(in, in_pitch, in_frame_stride, static_cast<size_t>(n), width, height);
+    if (const char *why = I.check())
+        return why;
+    if (p->algo != MCRAW_RGB_MHC && p->algo != MCRAW_RGB_BIN2)
+        return "unknown algo";
+    if (const char *why = rgb_check_stage(p, d, yv, colors, ncolors, n, plan))
+        return why;
+    plan.mhc = p->algo == MCRAW_RGB_MHC;
     plan.Wo = plan.mhc ? static_cast<size_t>(width) : static_cast<size_t>(width) / 2u;
     plan.Ho = plan.mhc ? static_cast<size_t>(height) : static_cast<size_t>(height) / 2u;
     if (yv && ((plan.Ho | plan.Wo) & 1u))
         return "4:2:0 needs an even Ho and Wo (BIN2: width and height multiples of 4)";
-    plan.frame_samples = yv ? plan.Ho * plan.Wo / 2u * 3u : 3u * plan.Ho * plan.Wo;
-    if (out_bytes / plan.es / plan.frame_samples < static_cast<size_t>(n))
-        return yv ? "out_bytes below n * Ho * Wo * 3 / 2 * sample size" : "out_bytes below n * 3 * Ho * Wo * element size";
-    if (!out || (reinterpret_cast<uintptr_t>(out) & (plan.es - 1u)))
-        return "in / out missing or not aligned to their element size";
-    plan.out_frame = plan.frame_samples * plan.es;
+    if (const char *why = rgb_check_out(p, yv != nullptr, n, out, out_bytes, plan))
+        return why;
     plan.invec = I.on_grid();
-    constexpr int shift_of[4] = {0, 3, 1, 2}; // MCRAW_CFA_* -> role shift: RGGB 0, BGGR 3, GRBG 1, GBRG 2
-    plan.shift = shift_of[p->cfa];
     if (plan.mhc) {
         plan.tilesX = (static_cast<uint32_t>(width) + MHC_TW - 1u) / MHC_TW;
         plan.units = plan.tilesX * ((static_cast<uint32_t>(height) + MHC_TH - 1u) / MHC_TH);
