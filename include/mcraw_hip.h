@@ -494,6 +494,61 @@ int mcraw_demosaic_area_batch(mcraw_ctx *ctx, const mcraw_rgb *p, const mcraw_ar
                               size_t in_pitch, size_t in_frame_stride, int width, int height, int n, void *work,
                               size_t work_bytes, void *out, size_t out_bytes, void *stream);
 
+/* ---- uint16 mosaics -> any output size from half to twice a crop window: MHC behind a polyphase filter ---------------
+ *
+ * The band that the area downscale leaves out: a crop of cw x ch samples at (x0, y0) of every mosaic becomes out_h x out_w
+ * pixels, ceil(cw / 2) <= out_w <= 2 cw and likewise out_h, by resampling the full-resolution Malvar-He-Cutler image with a
+ * separable linear or cubic (Catmull-Rom) filter, horizontally first.  Output family: `d` and `y` NULL: the float family;
+ * `d`: the display family; `y`: the YUV family; both: rejected, as in mcraw_demosaic_area_batch.  p->algo must be
+ * MCRAW_RGB_RESAMPLE, which every other entry point keeps rejecting.
+ * Bit-exact arithmetic.  e_c(y, x): MCRAW_RGB_MHC's integer estimates of the WHOLE frame, in 1/16 DN, |e| < 2^22; outside the
+ * frame e_c(y, x) = e_c(reflect101(y, height), reflect101(x, width)) (taps reach at most 4 samples beyond the crop and MHC 2
+ * more: one reflection suffices for frames of 8 and up).  Taps that leave the crop but stay in the frame read the real
+ * pixels there.  Per axis, C crop samples (cw, ch) onto O pixels (out_w, out_h), pixel centres aligned, the filter stretched
+ * by max(1, C / O); j counts from the crop's origin and may be negative or >= C:
+ *   D = 2 max(C, O);  n(k, j) = 2 O j - ((2 k + 1) C - O);  a = floor((1024 |n| + D / 2) / D)          64-bit
+ *   linear: f = max(0, 1024 - a)
+ *   cubic:  f = 3 a^3 - 5 * 1024 a^2 + 2 * 1024^3                      a <= 1024
+ *           f = -a^3 + 5 * 1024 a^2 - 8 * 1024^2 a + 4 * 1024^3        1024 < a < 2048;  0 otherwise
+ *   F = sum_j f;  w(k, j) = floor((4096 f + F / 2) / F)               floor division; then the residual 4096 - sum_j w is
+ *           added to the tap of smallest |n|; two taps of equal smallest |n| take half of it each (it is even then)
+ *   t_c(y, k) = (sum_j wx(k, j) e_c(y, x0 + j) + 2048) >> 12          exact sum, arithmetic shift; 1/16 DN; |t| < 2^23
+ *   E_c(i, k) = (sum_j wy(i, j) t_c(y0 + j, k) + 2048) >> 12          likewise; |E| < 2^24, exact as float
+ *   host, f32: k[c] = (gain[c] * inv) * 0.0625f                       as MCRAW_RGB_MHC
+ * The weights of a pixel add up to 4096 exactly, sum |w| <= 5600 (cubic; 4096 linear), at most 5 (linear) or 9 (cubic) taps
+ * per axis, the taps of pixel k mirror those of pixel O - 1 - k, and O = C gives the single tap 4096 at j = k.  The sums do not
+ * fit int32 as they stand (2^22 * 5600); with v = 256 vh + vl, vl = v & 255, A = sum w vh and B = sum w vl fit (|A| < 2^28,
+ * 0 <= |B| < 2^21) and (256 A + B + 2048) >> 12 == (A + ((B + 2048) >> 8)) >> 4.  A flat frame comes out flat (E = 16 d),
+ * greys stay neutral, and with out_w = cw, out_h = ch the result is MCRAW_RGB_MHC's output cut to the crop, bit for bit, in
+ * every family.  From E_c and k[c] on everything is the family's own entry point: colour stage, clamp, LUT, matrix, layouts,
+ * with Ho = out_h, Wo = out_w.
+ * Accepted: width, height even and >= 8; x0, y0, cw, ch even, cw, ch >= 2, x0 + cw <= width, y0 + ch <= height; the size
+ * rule above; filter MCRAW_FILTER_LINEAR or MCRAW_FILTER_CUBIC; the YUV family needs an even out_w and out_h; in, in_pitch,
+ * in_frame_stride, colors, out and out_bytes follow the family's entry point.
+ * `work`: the caller's DEVICE memory, 16-byte aligned, at least mcraw_resample_work_bytes(r) bytes; a small kernel queued on
+ * `stream` in front writes the tap tables into it, as for the area downscale: nothing is cached, nothing waits for the host,
+ * and calls queued on one stream may share one `work`.
+ * Rejected (returns < 0, mcraw_last_error says why, starting with "mcraw_demosaic_resample_batch: ", nothing is written):
+ * everything the family's own entry point rejects; a NULL `r`; a p->algo other than MCRAW_RGB_RESAMPLE; both `d` and `y`; a
+ * frame under 8 x 8; an odd, empty or out-of-frame crop; a size outside the rule; an unknown filter; a non-zero `reserved`;
+ * a NULL or misaligned `work`; work_bytes below mcraw_resample_work_bytes(r).  n == 0 is a no-op.  The call takes no decode
+ * serial, leaves the decode slots, mcraw_ctx_errors and the context's stage alone, and has no kernel id of its own. */
+#define MCRAW_RGB_RESAMPLE 4   /* valid in mcraw_demosaic_resample_batch only */
+#define MCRAW_FILTER_LINEAR 0
+#define MCRAW_FILTER_CUBIC 1
+typedef struct mcraw_resample {
+    uint32_t x0, y0;        /* crop origin in the mosaic, both even                 */
+    uint32_t cw, ch;        /* crop size, both even, >= 2; x0 + cw <= width, ...    */
+    uint32_t out_w, out_h;  /* Wo, Ho                                               */
+    uint32_t filter;        /* MCRAW_FILTER_*                                       */
+    uint32_t reserved;      /* must be 0                                            */
+} mcraw_resample;           /* sizeof 32; y0 4, cw 8, ch 12, out_w 16, out_h 20, filter 24, reserved 28 */
+size_t mcraw_resample_work_bytes(const mcraw_resample *r);  /* 0 for a rejected geometry */
+int mcraw_demosaic_resample_batch(mcraw_ctx *ctx, const mcraw_rgb *p, const mcraw_resample *r, const mcraw_display *d,
+                                  const mcraw_yuv *y, const mcraw_rgb_color *colors, int ncolors, const uint16_t *in,
+                                  size_t in_pitch, size_t in_frame_stride, int width, int height, int n, void *work,
+                                  size_t work_bytes, void *out, size_t out_bytes, void *stream);
+
 /* ---- uint16 mosaics -> uint16 mosaics with a lens-shading gain map applied ----------------------------------------
  *
  * Multiplies what `n` uint16 mosaics of width x height hold above their black level by a per-pixel gain that is bilinearly

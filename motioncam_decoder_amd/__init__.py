@@ -18,7 +18,8 @@ __all__ = ["lib_path", "load", "Context", "Pool", "Frame", "EncFrame", "FloatOut
            "DISP_CHW", "DISP_HWC", "Yuv", "YUV_NV12", "YUV_P010", "yuv_matrix", "yuv_planes", "Shade", "gain_map",
            "shading_map", "Stats", "STATS_ACCUMULATE", "FrameStats", "stats_white_balance", "stats_percentile",
            "stats_clipped", "FixPix", "FIXPIX_HOT", "FIXPIX_COLD", "pack_pixels", "Denoise", "noise_lut", "Merge", "Align",
-           "align_window", "fit_crop", "Area", "RGB_AREA"]
+           "align_window", "fit_crop", "Area", "RGB_AREA", "Resample", "RGB_RESAMPLE",
+           "FILTER_LINEAR", "FILTER_CUBIC"]
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 
@@ -48,6 +49,7 @@ ABI_SYMBOLS = [
     "mcraw_demosaic_batch", "mcraw_demosaic_display_batch", "mcraw_demosaic_yuv_batch", "mcraw_shade_batch",
     "mcraw_stats_batch", "mcraw_stats_record_bytes", "mcraw_fixpix_batch", "mcraw_denoise_batch",
     "mcraw_merge_batch", "mcraw_align_batch", "mcraw_align_work_bytes", "mcraw_demosaic_area_batch", "mcraw_area_work_bytes",
+    "mcraw_demosaic_resample_batch", "mcraw_resample_work_bytes",
 ]
 
 POST_BLACK, POST_PACK12, POST_PACK10, POST_PACK14 = 1, 2, 4, 8
@@ -125,7 +127,10 @@ def float_out(dtype, white, layout="planes", black=(0, 0, 0, 0), clip=False, pla
 # demosaic to planar linear RGB (mcraw_demosaic_batch)
 RGB_MHC, RGB_BIN2 = 1, 2
 RGB_AREA = 3  # mcraw_demosaic_area_batch only
-_RGB_ALGOS = {"mhc": RGB_MHC, "bin2": RGB_BIN2, "area": RGB_AREA}
+RGB_RESAMPLE = 4  # mcraw_demosaic_resample_batch only
+FILTER_LINEAR, FILTER_CUBIC = 0, 1
+_RGB_ALGOS = {"mhc": RGB_MHC, "bin2": RGB_BIN2, "area": RGB_AREA, "resample": RGB_RESAMPLE}
+_FILTERS = {"linear": FILTER_LINEAR, "cubic": FILTER_CUBIC}
 _CFA_CODES = {"rggb": 0, "bggr": 1, "grbg": 2, "gbrg": 3}
 
 
@@ -146,12 +151,21 @@ class Area(C.Structure):
                 ("out_h", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
-def fit_crop(height, width, Ho, Wo):
+class Resample(C.Structure):
+    """struct mcraw_resample (include/mcraw_hip.h): the crop window in the mosaic, the output size and the filter."""
+    _fields_ = [("x0", C.c_uint32), ("y0", C.c_uint32), ("cw", C.c_uint32), ("ch", C.c_uint32), ("out_w", C.c_uint32),
+                ("out_h", C.c_uint32), ("filter", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+def fit_crop(height, width, Ho, Wo, algo="area"):
     """The largest centred crop (y0, x0, h, w) of a height x width mosaic that has the output's aspect ratio Wo : Ho, for
     algo="area": h = 2 Ho t and w = 2 Wo t for the largest t (a real number) that fits, both rounded down to even numbers, the
     origin rounded down to even.  Raises ValueError when the sizes are no positive integers or when the crop breaks the ratio
     rule of mcraw_demosaic_area_batch (Ho <= h / 2 <= 16 Ho, Wo <= w / 2 <= 16 Wo).  fit_crop(3024, 4032, 1080, 1920) is
-    (378, 0, 2268, 4032)."""
+    (378, 0, 2268, 4032).  algo="resample": the same crop under the rule of mcraw_demosaic_resample_batch (h / 2 <= Ho <= 2 h,
+    w / 2 <= Wo <= 2 w): fit_crop(3024, 4032, 2160, 3840, algo="resample") is (378, 0, 2268, 4032)."""
+    if algo not in ("area", "resample"):
+        raise ValueError("fit_crop: algo must be 'area' or 'resample', not %r" % (algo,))
     for v in (height, width, Ho, Wo):
         if isinstance(v, bool) or v != int(v) or int(v) < 1:
             raise ValueError("fit_crop: sizes must be positive integers, not %r" % (v,))
@@ -162,7 +176,11 @@ def fit_crop(height, width, Ho, Wo):
     else:
         h = height // 2 * 2
         w = (height * Wo) // Ho // 2 * 2
-    if not (Ho <= h // 2 <= 16 * Ho and Wo <= w // 2 <= 16 * Wo):
+    if algo == "resample":
+        if not (2 <= h <= 2 * Ho <= 4 * h and 2 <= w <= 2 * Wo <= 4 * w):
+            raise ValueError("fit_crop: a %d x %d crop of a %d x %d mosaic onto %d x %d is outside 1/2 .. 2 samples per pixel"
+                             % (h, w, height, width, Ho, Wo))
+    elif not (Ho <= h // 2 <= 16 * Ho and Wo <= w // 2 <= 16 * Wo):
         raise ValueError("fit_crop: a %d x %d crop of a %d x %d mosaic onto %d x %d is outside 1 .. 16 quads per pixel"
                          % (h, w, height, width, Ho, Wo))
     return ((height - h) // 4 * 2, (width - w) // 4 * 2, h, w)
@@ -841,6 +859,12 @@ def load():
                                       C.c_void_p]
     lib.mcraw_area_work_bytes.restype = C.c_size_t
     lib.mcraw_area_work_bytes.argtypes = [C.POINTER(Area)]
+    lib.mcraw_resample_work_bytes.restype = C.c_size_t
+    lib.mcraw_resample_work_bytes.argtypes = [C.POINTER(Resample)]
+    lib.mcraw_demosaic_resample_batch.restype = C.c_int
+    lib.mcraw_demosaic_resample_batch.argtypes = [C.c_void_p, C.POINTER(RgbParams), C.POINTER(Resample), C.POINTER(Display),
+                                                  C.POINTER(Yuv), C.POINTER(RgbColor), C.c_int, C.c_void_p, C.c_size_t, C.c_size_t,
+                                                  C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.mcraw_demosaic_area_batch.restype = C.c_int
     lib.mcraw_demosaic_area_batch.argtypes = [C.c_void_p, C.POINTER(RgbParams), C.POINTER(Area), C.POINTER(Display), C.POINTER(Yuv),
                                               C.POINTER(RgbColor), C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int,
@@ -1626,7 +1650,7 @@ class Context:
         return self.merge(scratch, lut, shift, **merge_kw)
 
     def demosaic(self, mosaic, *, algo="mhc", dtype, white, black=(0, 0, 0, 0), cfa="rggb", gain=None, matrix=None,
-                 clip=False, out=None, check=True, shading=None, defects=None, denoise=None, size=None, crop=None):
+                 clip=False, out=None, check=True, shading=None, defects=None, denoise=None, size=None, crop=None, filter=None):
         """uint16 mosaics resident on the context's device -> planar linear RGB, (N, 3, H, W) for algo "mhc" (Malvar-He-
         Cutler) or (N, 3, H/2, W/2) for "bin2" (one pixel per 2x2 quad), as torch.float32 / float16 / bfloat16 ("f32" /
         "f16" / "bf16").  mosaic: a CUDA uint16 tensor (N, H, W) or (H, W) whose rows are contiguous (rows and frames may
@@ -1645,11 +1669,16 @@ class Context:
         output's aspect ratio) is an area downscale (mcraw_demosaic_area_batch): every output pixel is the average of the
         CFA quads under its footprint in the crop, 1 .. 16 quads per pixel along each axis, the origin and size of the crop
         even; the result is (N, 3, Ho, Wo), and with h = 2 Ho, w = 2 Wo it is "bin2" of the crop, bit for bit.  The stages in
-        front run on the whole mosaic.  size= or crop= with another algo, or "area" without size=, raises ValueError."""
+        front run on the whole mosaic.  size= or crop= with another algo, or "area" without size=, raises ValueError.
+        algo "resample" with size=, crop= (as "area") and filter="cubic" (Catmull-Rom, the default) or "linear" covers the sizes
+        from half to twice the crop (mcraw_demosaic_resample_batch): the "mhc" image of the whole frame behind a separable
+        polyphase filter, in integers; with size= the crop's own size it is "mhc" cut to the crop, bit for bit.  The crop marks
+        the sample positions: taps that leave it read the frame's real pixels (a stabilisation window; align_window gives
+        one), and reflect at the frame's edges.  filter= with another algo raises ValueError."""
         import torch
         code = _float_code(dtype)
         tdtype = {FLOAT_F32: torch.float32, FLOAT_F16: torch.float16, FLOAT_BF16: torch.bfloat16}[code]
-        front = self._demosaic_front("demosaic", mosaic, algo, cfa, black, defects, denoise, shading, size, crop)
+        front = self._demosaic_front("demosaic", mosaic, algo, cfa, black, defects, denoise, shading, size, crop, filter)
         ho, wo = front[6:8]
         out = self._demosaic_out("demosaic", front, out, (3, ho, wo), tdtype)
         if front[2] == 0:
@@ -1657,19 +1686,27 @@ class Context:
         return self._demosaic_call("mcraw_demosaic_batch", "demosaic", front, algo, code, FLOAT_CLIP if clip else 0, white, black,
                                    gain, matrix, out)
 
-    def _demosaic_front(self, fn, mosaic, algo, cfa, black, defects, denoise, shading, size=None, crop=None):
+    def _demosaic_front(self, fn, mosaic, algo, cfa, black, defects, denoise, shading, size=None, crop=None, filter=None):
         """What demosaic / demosaic_display / demosaic_yuv (`fn`) do alike in front of their output: the algo and cfa checks,
         the mosaic argument, the optional stages -- defects, then denoise, then shading, each into a scratch tensor (the
         caller's mosaic stays as it is), none for an empty batch -- and the output size.  Returns (mos, single, n, h, w, src,
         ho, wo, key, area): src is _strided's triple (None for no frames), key the cfa's, area the (y0, x0, h, w) crop of algo
-        "area" (None for the other algos), whose output size is `size`."""
+        "area" or "resample" (None for the other algos), whose output size is `size`, filt: the MCRAW_FILTER_* code of algo
+        "resample" (None for the other algos)."""
         import torch
         if algo not in _RGB_ALGOS:
-            raise ValueError("algo must be 'mhc', 'bin2' or 'area', not %r" % (algo,))
-        if algo != "area" and (size is not None or crop is not None):
-            raise ValueError("%s: size= and crop= belong to algo='area', not %r" % (fn, algo))
-        if algo == "area" and size is None:
-            raise ValueError("%s: algo='area' needs size=(Ho, Wo)" % fn)
+            raise ValueError("algo must be 'mhc', 'bin2', 'area' or 'resample', not %r" % (algo,))
+        if algo not in ("area", "resample") and (size is not None or crop is not None):
+            raise ValueError("%s: size= and crop= belong to algo='area' and 'resample', not %r" % (fn, algo))
+        if algo in ("area", "resample") and size is None:
+            raise ValueError("%s: algo=%r needs size=(Ho, Wo)" % (fn, algo))
+        if filter is not None and algo != "resample":
+            raise ValueError("%s: filter= belongs to algo='resample', not %r" % (fn, algo))
+        filt = None
+        if algo == "resample":
+            filt = _FILTERS.get("cubic" if filter is None else filter)
+            if filt is None:
+                raise ValueError("%s: filter must be 'cubic' or 'linear', not %r" % (fn, filter))
         key = str(cfa).strip().lower()
         if key not in _CFA_CODES:
             raise ValueError("unknown cfa %r (rggb, bggr, grbg or gbrg)" % (cfa,))
@@ -1681,7 +1718,7 @@ class Context:
         n, h, w = (int(v) for v in mos.shape)
         src = self._strided(fn, "the mosaic", mos, h, w) if n else None
         area = None
-        if algo == "area":
+        if algo in ("area", "resample"):
             try:
                 ho, wo = (int(v) for v in size)
                 area = (0, 0, h // 2 * 2, w // 2 * 2) if crop is None else tuple(int(v) for v in crop)
@@ -1691,7 +1728,7 @@ class Context:
                 raise ValueError("%s: size must be (Ho, Wo) and crop (y0, x0, h, w), all 0 .. 65536, not %r and %r" % (fn, size, crop))
         else:
             ho, wo = (h, w) if algo == "mhc" else (h // 2, w // 2)
-        return mos, single, n, h, w, src, ho, wo, key, area
+        return mos, single, n, h, w, src, ho, wo, key, area, filt
 
     def _pre_stages(self, fn, mos, black, defects, denoise):
         """defects= and denoise= of the demosaic / decode methods, in that order, each into a scratch tensor; an empty batch
@@ -1713,9 +1750,24 @@ class Context:
         """The tail of the three demosaics: colours, params and the library's `symbol` (stage: its display / YUV struct, None
         for the float entry; extra: further tensors that take part).  Returns out."""
         import torch
-        mos, _, n, h, w, src, ho, wo, key, area = front
+        mos, _, n, h, w, src, ho, wo, key, area, filt = front
         cols, nc = _rgb_colors(gain, matrix, n, fn)
         prm = _rgb_params(algo, dtype_code, flags, key, white, black)
+        if filt is not None:  # algo "resample": as "area" below, with its own struct and entry point
+            a = Resample()
+            a.y0, a.x0, a.ch, a.cw = area
+            a.out_h, a.out_w, a.filter, a.reserved = ho, wo, filt, 0
+            need = int(self._lib.mcraw_resample_work_bytes(C.byref(a)))
+            if need == 0:
+                raise ValueError("%s: crop %r onto size %r: the crop must be even and not empty, and the size 1/2 .. 2 of it "
+                                 "along each axis" % (fn, area, (ho, wo)))
+            work = torch.empty((need,), dtype=torch.uint8, device=mos.device)
+            d = C.byref(stage) if isinstance(stage, Display) else None
+            y = C.byref(stage) if isinstance(stage, Yuv) else None
+            self._call(torch, mos.device, "mcraw_demosaic_resample_batch", (mos, out, work) + tuple(extra), C.byref(prm), C.byref(a), d,
+                       y, cols, nc, *src, w, h, n, C.c_void_p(work.data_ptr()), need, C.c_void_p(out.data_ptr()),
+                       out.numel() * out.element_size())
+            return out
         if area is not None:  # one entry point for the three families; its scratch lives as long as the call's other tensors
             a = Area()
             a.y0, a.x0, a.ch, a.cw = area
@@ -1780,7 +1832,7 @@ class Context:
 
     def decode_rgb(self, inputs, width, height, type, *, algo="mhc", dtype, white, black=(0, 0, 0, 0), cfa="rggb",
                    gain=None, matrix=None, clip=False, out=None, check=True, shading=None, defects=None, denoise=None, size=None,
-                   crop=None):
+                   crop=None, filter=None):
         """Decode frames of one geometry that are resident in HBM and demosaic them (demosaic()): (N, 3, H, W) for "mhc",
         (N, 3, H/2, W/2) for "bin2", (N, 3, Ho, Wo) for "area" with size=(Ho, Wo) and crop=.  inputs: uint8 CUDA tensors, or (device pointer, length) pairs.  The plain uint16
         mosaics go to a scratch tensor of torch's caching allocator; both steps are queued on torch.cuda.current_stream().
@@ -1791,7 +1843,7 @@ class Context:
         dict of denoise()'s keyword arguments, applied behind defects= and in front of shading=."""
         scratch = self._decode_front("decode_rgb", inputs, width, height, type, check, black, defects, denoise, shading)
         return self.demosaic(scratch, algo=algo, dtype=dtype, white=white, black=black, cfa=cfa, gain=gain, matrix=matrix,
-                             clip=clip, out=out, check=check, size=size, crop=crop)
+                             clip=clip, out=out, check=check, size=size, crop=crop, filter=filter)
 
     def _display_lut(self, torch, dev, fn, transfer, lut_size, bits):
         """(device LUT tensor, caller-owned?) for demosaic_display / demosaic_yuv (`fn`): a ready 1-D uint16 LUT (CUDA tensor on
@@ -1824,7 +1876,7 @@ class Context:
 
     def demosaic_display(self, mosaic, *, algo="mhc", white, black=(0, 0, 0, 0), cfa="rggb", gain=None, matrix=None,
                          transfer="srgb", lut_size=4096, dtype=None, layout="hwc", bits=None, out=None, check=True, shading=None,
-                         defects=None, denoise=None, size=None, crop=None):
+                         defects=None, denoise=None, size=None, crop=None, filter=None):
         """uint16 mosaics resident on the context's device -> display-ready integer RGB: the demosaic and colours of
         demosaic(), then clamp to [0, 1], index a transfer-curve LUT of L entries at rint(c * (L - 1)) and store the entry
         (its low byte for uint8).  dtype: torch.uint8 (default) or torch.uint16; layout "hwc" gives (N, Ho, Wo, 3), "chw"
@@ -1841,7 +1893,7 @@ class Context:
             raise ValueError("demosaic_display: dtype must be torch.uint8 or torch.uint16, not %r" % (dtype,))
         if layout not in _DISP_LAYOUTS:
             raise ValueError("demosaic_display: layout must be 'hwc' or 'chw', not %r" % (layout,))
-        front = self._demosaic_front("demosaic_display", mosaic, algo, cfa, black, defects, denoise, shading, size, crop)
+        front = self._demosaic_front("demosaic_display", mosaic, algo, cfa, black, defects, denoise, shading, size, crop, filter)
         ho, wo = front[6:8]
         out = self._demosaic_out("demosaic_display", front, out, (ho, wo, 3) if layout == "hwc" else (3, ho, wo),
                                  torch.uint8 if dcode == DISP_U8 else torch.uint16)
@@ -1857,7 +1909,7 @@ class Context:
 
     def decode_display(self, inputs, width, height, type, *, algo="mhc", white, black=(0, 0, 0, 0), cfa="rggb", gain=None,
                        matrix=None, transfer="srgb", lut_size=4096, dtype=None, layout="hwc", bits=None, out=None, check=True, shading=None,
-                       defects=None, denoise=None, size=None, crop=None):
+                       defects=None, denoise=None, size=None, crop=None, filter=None):
         """Decode frames of one geometry that are resident in HBM and turn them into display-ready RGB
         (demosaic_display()), as decode_rgb does: the plain uint16 mosaics go to a scratch tensor, both steps are queued on
         torch.cuda.current_stream(), check=True synchronises after the decode and raises McrawError naming the frames that
@@ -1865,11 +1917,11 @@ class Context:
         scratch = self._decode_front("decode_display", inputs, width, height, type, check, black, defects, denoise, shading)
         return self.demosaic_display(scratch, algo=algo, white=white, black=black, cfa=cfa, gain=gain, matrix=matrix,
                                      transfer=transfer, lut_size=lut_size, dtype=dtype, layout=layout, bits=bits, out=out,
-                                     check=check, size=size, crop=crop)
+                                     check=check, size=size, crop=crop, filter=filter)
 
     def demosaic_yuv(self, mosaic, *, algo="mhc", white, black=(0, 0, 0, 0), cfa="rggb", gain=None, matrix=None, fmt="nv12",
                      standard="bt709", range="limited", transfer="bt709", lut_size=4096, in_bits=None, out=None, check=True, shading=None,
-                     defects=None, denoise=None, size=None, crop=None):
+                     defects=None, denoise=None, size=None, crop=None, filter=None):
         """uint16 mosaics resident on the context's device -> video-ready Y'CbCr 4:2:0: the demosaic, colours, clamp and
         transfer-curve LUT of demosaic_display(), then the integer matrix of yuv_matrix(standard, range) and a 2x2 box
         average for the chroma (sited at the block's centre).  fmt "nv12": torch.uint8; "p010": torch.uint16 holding
@@ -1886,7 +1938,7 @@ class Context:
         fcode, bits, default_in = _YUV_FORMATS[fmt]
         in_bits = default_in if in_bits is None else in_bits
         cy, cb, cr, sh, y_off, c_off = yuv_matrix(standard, range, bits, in_bits)
-        front = self._demosaic_front("demosaic_yuv", mosaic, algo, cfa, black, defects, denoise, shading, size, crop)
+        front = self._demosaic_front("demosaic_yuv", mosaic, algo, cfa, black, defects, denoise, shading, size, crop, filter)
         ho, wo = front[6:8]
         out = self._demosaic_out("demosaic_yuv", front, out, (ho * 3 // 2, wo), torch.uint8 if fcode == YUV_NV12 else torch.uint16)
         if front[2] == 0:
@@ -1903,7 +1955,7 @@ class Context:
 
     def decode_yuv(self, inputs, width, height, type, *, algo="mhc", white, black=(0, 0, 0, 0), cfa="rggb", gain=None,
                    matrix=None, fmt="nv12", standard="bt709", range="limited", transfer="bt709", lut_size=4096, in_bits=None,
-                   out=None, check=True, shading=None, defects=None, denoise=None, size=None, crop=None):
+                   out=None, check=True, shading=None, defects=None, denoise=None, size=None, crop=None, filter=None):
         """Decode frames of one geometry that are resident in HBM and turn them into NV12 / P010 (demosaic_yuv()), as
         decode_display does: the plain uint16 mosaics go to a scratch tensor, both steps are queued on
         torch.cuda.current_stream(), check=True synchronises after the decode and raises McrawError naming the frames that
@@ -1911,7 +1963,7 @@ class Context:
         scratch = self._decode_front("decode_yuv", inputs, width, height, type, check, black, defects, denoise, shading)
         return self.demosaic_yuv(scratch, algo=algo, white=white, black=black, cfa=cfa, gain=gain, matrix=matrix, fmt=fmt,
                                  standard=standard, range=range, transfer=transfer, lut_size=lut_size, in_bits=in_bits, out=out,
-                                 check=check, size=size, crop=crop)
+                                 check=check, size=size, crop=crop, filter=filter)
 
     def profile(self, enable=True, only=None, every=1):
         """Bracket kernel launches with events: all kernels, or just the names in `only`; every `every`-th launch."""

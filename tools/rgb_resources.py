@@ -4,10 +4,11 @@ statistics kernels (csrc/mcraw_stats.hip), of the defective-pixel kernels (csrc/
 (csrc/mcraw_denoise.hip), of the temporal merge (csrc/mcraw_merge.hip) and of the shift estimate (csrc/mcraw_align.hip): compiles the files for gfx950 with -Rpass-analysis=kernel-resource-usage (no GPU needed) and prints
 one line per instance in the format of profiles/rgb_resources.txt / display_resources.txt / yuv_resources.txt /
 shade_resources.txt / stats_resources.txt / fixpix_resources.txt / denoise_resources.txt / merge_resources.txt / align_resources.txt /
-area_resources.txt (the area downscale's instances, krgb_area and karea_tab, which live in csrc/mcraw_rgb.hip).
+area_resources.txt (the area downscale's instances, krgb_area and karea_tab, which live in csrc/mcraw_rgb.hip) /
+resample_resources.txt (csrc/mcraw_resample.hip: krgb_resample and kres_tab).
 
     python tools/rgb_resources.py            # every instance
-    python tools/rgb_resources.py --check    # the figures in the ten committed files must equal the compiler's; exit 1 if not
+    python tools/rgb_resources.py --check    # the figures in the eleven committed files must equal the compiler's; exit 1 if not
 """
 import os
 import re
@@ -35,6 +36,8 @@ ALIGN_FILE = "align_resources.txt"
 ALIGN_NAME = r"Function Name: _ZN5mcraw\d+(kalign_[a-z]+)(?:ILi([01])EEEv|E)"  # kalign_sad<R = 1: nine candidates in registers; 0: a loop>, the others
 AREA_FILE = "area_resources.txt"
 AREA_NAME = r"Function Name: _ZN5mcraw\d+(krgb_area|karea_tab)(?:ILi(\d+)ELi(\d)EEEv|E)"  # krgb_area<kind, CFA shift>, and the kernel that writes the taps
+RESAMPLE_FILE = "resample_resources.txt"
+RESAMPLE_NAME = r"Function Name: _ZN5mcraw\d+(krgb_resample|kres_tab)(?:ILi(\d+)ELi(\d)EEEv|E)"  # krgb_resample<kind, CFA shift>, and the kernel that writes the taps
 SHADE_NAME = r"Function Name: _ZN5mcraw\d+(kshade)ILb([01])EEEv"  # kshade<NT>: `sc1 nt` streaming stores or plain ones
 
 
@@ -55,8 +58,8 @@ def _label(m):
         return "kalign_sad<%s>" % ("refine" if m.group(2) == "1" else "coarse")
     if m.group(1).startswith("kalign_"):
         return m.group(1)
-    if m.group(1) == "karea_tab":
-        return "karea_tab"
+    if m.group(1) in ("karea_tab", "kres_tab"):
+        return m.group(1)
     if m.group(1) == "kshade":
         return "kshade<%s>" % ("stream" if m.group(2) == "1" else "plain")
     return "%s<%s,S=%s>" % (m.group(1), KINDS[int(m.group(2))], m.group(3))
@@ -106,14 +109,16 @@ def main():
     fixpix, denoise = report("mcraw_fixpix.hip", FIXPIX_NAME), report("mcraw_denoise.hip", DENOISE_NAME)
     merge, align = report("mcraw_merge.hip", MERGE_NAME), report("mcraw_align.hip", ALIGN_NAME)
     area = report("mcraw_rgb.hip", AREA_NAME)
+    resample = report("mcraw_resample.hip", RESAMPLE_NAME)
     if "--check" not in sys.argv:
         for line in list(rep.values()) + list(shade.values()) + list(stats.values()) + list(fixpix.values()) + list(denoise.values()) + \
-                list(merge.values()) + list(align.values()) + list(area.values()):
+                list(merge.values()) + list(align.values()) + list(area.values()) + list(resample.values()):
             print(line)
         return 0
     return _check(FILES, rep, "krgb_") | _check((SHADE_FILE,), shade, "kshade") | _check((STATS_FILE,), stats, "kstats") | \
         _check((FIXPIX_FILE,), fixpix, "kfixpix") | _check((DENOISE_FILE,), denoise, "kdenoise") | _check((MERGE_FILE,), merge, "kmerge") | \
-        _check((ALIGN_FILE,), align, "kalign") | _check((AREA_FILE,), area, ("krgb_area", "karea_tab"))
+        _check((ALIGN_FILE,), align, "kalign") | _check((AREA_FILE,), area, ("krgb_area", "karea_tab")) | \
+        _check((RESAMPLE_FILE,), resample, ("krgb_resample", "kres_tab"))
 
 
 if __name__ == "__main__":
