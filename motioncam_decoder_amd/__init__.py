@@ -8,6 +8,7 @@ the HIP library and the C++ ``motioncam::Decoder`` facade under ``host/``.
 There is no CPU decode path here: if the HIP library is missing or no GPU is
 present, every decode call raises.
 """
+import collections
 import ctypes as C
 import functools
 import os
@@ -157,6 +158,22 @@ class Resample(C.Structure):
                 ("out_h", C.c_uint32), ("filter", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+# The scaled algos of the demosaic methods (size=, crop=): algo -> (the window struct, the library's work-bytes function, its entry
+# point for the three families, the geometry rule as the ValueError states it).
+_SCALED = {
+    "area": (Area, "mcraw_area_work_bytes", "mcraw_demosaic_area_batch",
+             "the crop must be even and not empty, and hold 1 .. 16 quads per output pixel along each axis"),
+    "resample": (Resample, "mcraw_resample_work_bytes", "mcraw_demosaic_resample_batch",
+                 "the crop must be even and not empty, and the size 1/2 .. 2 of it along each axis"),
+}
+
+# What the demosaic methods know in front of their output (Context._demosaic_front).  mos: the mosaics (N, H, W) behind the
+# optional stages; single: the caller's was (H, W); n, h, w: their shape; src: _strided's triple (None for no frames); ho, wo: the
+# output size; key: the cfa's; area: the (y0, x0, h, w) crop of a scaled algo (None for the others); filt: the MCRAW_FILTER_* code
+# of algo "resample" (None for the others).
+_Front = collections.namedtuple("_Front", "mos single n h w src ho wo key area filt")
+
+
 def fit_crop(height, width, Ho, Wo, algo="area"):
     """The largest centred crop (y0, x0, h, w) of a height x width mosaic that has the output's aspect ratio Wo : Ho, for
     algo="area": h = 2 Ho t and w = 2 Wo t for the largest t (a real number) that fits, both rounded down to even numbers, the
@@ -164,7 +181,7 @@ def fit_crop(height, width, Ho, Wo, algo="area"):
     rule of mcraw_demosaic_area_batch (Ho <= h / 2 <= 16 Ho, Wo <= w / 2 <= 16 Wo).  fit_crop(3024, 4032, 1080, 1920) is
     (378, 0, 2268, 4032).  algo="resample": the same crop under the rule of mcraw_demosaic_resample_batch (h / 2 <= Ho <= 2 h,
     w / 2 <= Wo <= 2 w): fit_crop(3024, 4032, 2160, 3840, algo="resample") is (378, 0, 2268, 4032)."""
-    if algo not in ("area", "resample"):
+    if algo not in _SCALED:
         raise ValueError("fit_crop: algo must be 'area' or 'resample', not %r" % (algo,))
     for v in (height, width, Ho, Wo):
         if isinstance(v, bool) or v != int(v) or int(v) < 1:
@@ -1679,9 +1696,9 @@ class Context:
         code = _float_code(dtype)
         tdtype = {FLOAT_F32: torch.float32, FLOAT_F16: torch.float16, FLOAT_BF16: torch.bfloat16}[code]
         front = self._demosaic_front("demosaic", mosaic, algo, cfa, black, defects, denoise, shading, size, crop, filter)
-        ho, wo = front[6:8]
+        ho, wo = front.ho, front.wo
         out = self._demosaic_out("demosaic", front, out, (3, ho, wo), tdtype)
-        if front[2] == 0:
+        if front.n == 0:
             return out
         return self._demosaic_call("mcraw_demosaic_batch", "demosaic", front, algo, code, FLOAT_CLIP if clip else 0, white, black,
                                    gain, matrix, out)
@@ -1689,16 +1706,15 @@ class Context:
     def _demosaic_front(self, fn, mosaic, algo, cfa, black, defects, denoise, shading, size=None, crop=None, filter=None):
         """What demosaic / demosaic_display / demosaic_yuv (`fn`) do alike in front of their output: the algo and cfa checks,
         the mosaic argument, the optional stages -- defects, then denoise, then shading, each into a scratch tensor (the
-        caller's mosaic stays as it is), none for an empty batch -- and the output size.  Returns (mos, single, n, h, w, src,
-        ho, wo, key, area): src is _strided's triple (None for no frames), key the cfa's, area the (y0, x0, h, w) crop of algo
-        "area" or "resample" (None for the other algos), whose output size is `size`, filt: the MCRAW_FILTER_* code of algo
-        "resample" (None for the other algos)."""
+        caller's mosaic stays as it is), none for an empty batch -- and the output size (`size` for the scaled algos).  Returns a
+        _Front."""
         import torch
         if algo not in _RGB_ALGOS:
             raise ValueError("algo must be 'mhc', 'bin2', 'area' or 'resample', not %r" % (algo,))
-        if algo not in ("area", "resample") and (size is not None or crop is not None):
+        scaled = algo in _SCALED
+        if not scaled and (size is not None or crop is not None):
             raise ValueError("%s: size= and crop= belong to algo='area' and 'resample', not %r" % (fn, algo))
-        if algo in ("area", "resample") and size is None:
+        if scaled and size is None:
             raise ValueError("%s: algo=%r needs size=(Ho, Wo)" % (fn, algo))
         if filter is not None and algo != "resample":
             raise ValueError("%s: filter= belongs to algo='resample', not %r" % (fn, algo))
@@ -1718,7 +1734,7 @@ class Context:
         n, h, w = (int(v) for v in mos.shape)
         src = self._strided(fn, "the mosaic", mos, h, w) if n else None
         area = None
-        if algo in ("area", "resample"):
+        if scaled:
             try:
                 ho, wo = (int(v) for v in size)
                 area = (0, 0, h // 2 * 2, w // 2 * 2) if crop is None else tuple(int(v) for v in crop)
@@ -1728,7 +1744,7 @@ class Context:
                 raise ValueError("%s: size must be (Ho, Wo) and crop (y0, x0, h, w), all 0 .. 65536, not %r and %r" % (fn, size, crop))
         else:
             ho, wo = (h, w) if algo == "mhc" else (h // 2, w // 2)
-        return mos, single, n, h, w, src, ho, wo, key, area, filt
+        return _Front(mos, single, n, h, w, src, ho, wo, key, area, filt)
 
     def _pre_stages(self, fn, mos, black, defects, denoise):
         """defects= and denoise= of the demosaic / decode methods, in that order, each into a scratch tensor; an empty batch
@@ -1742,46 +1758,31 @@ class Context:
     def _demosaic_out(self, fn, front, out, frame_shape, tdtype):
         """`out` of a demosaic method, checked or made: frame_shape per frame, without N for an (H, W) mosaic."""
         import torch
-        mos, single, n = front[:3]
-        want = tuple(frame_shape) if single else (n,) + tuple(frame_shape)
-        return self._out_arg(torch, mos.device, fn, out, want, tdtype, contiguous=True)
+        want = tuple(frame_shape) if front.single else (front.n,) + tuple(frame_shape)
+        return self._out_arg(torch, front.mos.device, fn, out, want, tdtype, contiguous=True)
 
     def _demosaic_call(self, symbol, fn, front, algo, dtype_code, flags, white, black, gain, matrix, out, stage=None, extra=()):
         """The tail of the three demosaics: colours, params and the library's `symbol` (stage: its display / YUV struct, None
         for the float entry; extra: further tensors that take part).  Returns out."""
         import torch
-        mos, _, n, h, w, src, ho, wo, key, area, filt = front
+        mos, n, h, w, src = front.mos, front.n, front.h, front.w, front.src
         cols, nc = _rgb_colors(gain, matrix, n, fn)
-        prm = _rgb_params(algo, dtype_code, flags, key, white, black)
-        if filt is not None:  # algo "resample": as "area" below, with its own struct and entry point
-            a = Resample()
-            a.y0, a.x0, a.ch, a.cw = area
-            a.out_h, a.out_w, a.filter, a.reserved = ho, wo, filt, 0
-            need = int(self._lib.mcraw_resample_work_bytes(C.byref(a)))
+        prm = _rgb_params(algo, dtype_code, flags, front.key, white, black)
+        if algo in _SCALED:  # one entry point for the three families; its scratch lives as long as the call's other tensors
+            struct, work_symbol, batch_symbol, rule = _SCALED[algo]
+            a = struct()
+            a.y0, a.x0, a.ch, a.cw = front.area
+            a.out_h, a.out_w = front.ho, front.wo
+            if front.filt is not None:
+                a.filter = front.filt
+            need = int(getattr(self._lib, work_symbol)(C.byref(a)))
             if need == 0:
-                raise ValueError("%s: crop %r onto size %r: the crop must be even and not empty, and the size 1/2 .. 2 of it "
-                                 "along each axis" % (fn, area, (ho, wo)))
+                raise ValueError("%s: crop %r onto size %r: %s" % (fn, front.area, (front.ho, front.wo), rule))
             work = torch.empty((need,), dtype=torch.uint8, device=mos.device)
             d = C.byref(stage) if isinstance(stage, Display) else None
             y = C.byref(stage) if isinstance(stage, Yuv) else None
-            self._call(torch, mos.device, "mcraw_demosaic_resample_batch", (mos, out, work) + tuple(extra), C.byref(prm), C.byref(a), d,
-                       y, cols, nc, *src, w, h, n, C.c_void_p(work.data_ptr()), need, C.c_void_p(out.data_ptr()),
-                       out.numel() * out.element_size())
-            return out
-        if area is not None:  # one entry point for the three families; its scratch lives as long as the call's other tensors
-            a = Area()
-            a.y0, a.x0, a.ch, a.cw = area
-            a.out_h, a.out_w = ho, wo
-            need = int(self._lib.mcraw_area_work_bytes(C.byref(a)))
-            if need == 0:
-                raise ValueError("%s: crop %r onto size %r: the crop must be even and not empty, and hold 1 .. 16 quads per output "
-                                 "pixel along each axis" % (fn, area, (ho, wo)))
-            work = torch.empty((need,), dtype=torch.uint8, device=mos.device)
-            d = C.byref(stage) if isinstance(stage, Display) else None
-            y = C.byref(stage) if isinstance(stage, Yuv) else None
-            self._call(torch, mos.device, "mcraw_demosaic_area_batch", (mos, out, work) + tuple(extra), C.byref(prm), C.byref(a), d, y,
-                       cols, nc, *src, w, h, n, C.c_void_p(work.data_ptr()), need, C.c_void_p(out.data_ptr()),
-                       out.numel() * out.element_size())
+            self._call(torch, mos.device, batch_symbol, (mos, out, work) + tuple(extra), C.byref(prm), C.byref(a), d, y, cols, nc, *src,
+                       w, h, n, C.c_void_p(work.data_ptr()), need, C.c_void_p(out.data_ptr()), out.numel() * out.element_size())
             return out
         structs = (C.byref(prm),) if stage is None else (C.byref(prm), C.byref(stage))
         self._call(torch, mos.device, symbol, (mos, out) + tuple(extra), *structs, cols, nc, *src, w, h, n,
@@ -1894,10 +1895,10 @@ class Context:
         if layout not in _DISP_LAYOUTS:
             raise ValueError("demosaic_display: layout must be 'hwc' or 'chw', not %r" % (layout,))
         front = self._demosaic_front("demosaic_display", mosaic, algo, cfa, black, defects, denoise, shading, size, crop, filter)
-        ho, wo = front[6:8]
+        ho, wo = front.ho, front.wo
         out = self._demosaic_out("demosaic_display", front, out, (ho, wo, 3) if layout == "hwc" else (3, ho, wo),
                                  torch.uint8 if dcode == DISP_U8 else torch.uint16)
-        if front[2] == 0:
+        if front.n == 0:
             return out
         lut, own = self._display_lut(torch, out.device, "demosaic_display", transfer, lut_size,
                                      (8 if dcode == DISP_U8 else 16) if bits is None else bits)
@@ -1939,9 +1940,9 @@ class Context:
         in_bits = default_in if in_bits is None else in_bits
         cy, cb, cr, sh, y_off, c_off = yuv_matrix(standard, range, bits, in_bits)
         front = self._demosaic_front("demosaic_yuv", mosaic, algo, cfa, black, defects, denoise, shading, size, crop, filter)
-        ho, wo = front[6:8]
+        ho, wo = front.ho, front.wo
         out = self._demosaic_out("demosaic_yuv", front, out, (ho * 3 // 2, wo), torch.uint8 if fcode == YUV_NV12 else torch.uint16)
-        if front[2] == 0:
+        if front.n == 0:
             return out
         lut, own = self._display_lut(torch, out.device, "demosaic_yuv", transfer, lut_size, in_bits)
         y = Yuv()

@@ -2,19 +2,14 @@
 // accept, reject or no-op; on acceptance the plan of the launch (the workgroup's tile, the LDS segment, the staging mode) and the
 // layout of the caller's scratch; and the weight formula itself, as a plain function that the table kernel and the tests share.
 // No HIP in here, so that tests/cpp/area_args_check.cpp can drive it on any machine.  The family's own rules (display / YUV
-// struct, dtype, cfa, white, colours, `out`) are rgb_check's pieces (mcraw_rgb_args.h), run in rgb_check's order.
+// struct, dtype, cfa, white, colours, `out`) are rgb_check's pieces (mcraw_rgb_args.h), run in rgb_check's order; the sequence
+// of the checks, the crop's rules and the scratch's layout are that header's window layer, shared with mcraw_resample_args.h.
 #pragma once
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
 
 #include "mcraw_rgb_args.h"
-
-#if defined(__HIPCC__)
-#define MCRAW_HD __host__ __device__
-#else
-#define MCRAW_HD
-#endif
 
 namespace mcraw {
 
@@ -24,7 +19,7 @@ constexpr uint32_t AREA_TILE_Q = 2560u; // LDS: quad slots of a workgroup's tile
 constexpr uint32_t AREA_WXN = 4096u;    // LDS: horizontal weights of a workgroup's columns (uint16, 8 KiB)
 constexpr uint32_t AREA_YN = 128u;      // LDS: (first quad row, taps) of a group's output rows; 2 per row pair, at most 64 row pairs
 constexpr uint32_t AREA_BAND = 8u;      // groups of row pairs that a workgroup makes with one set of horizontal weights
-constexpr size_t AREA_SECTION = 256u;   // the tables of the scratch start on multiples of this
+constexpr size_t AREA_SECTION = TAB_SECTION; // the tables of the scratch start on multiples of this
 
 // One output column or row in the scratch: the first quad under it, how many quads carry weight, and the weights (256 in
 // all; those behind `nt` are 0).
@@ -40,8 +35,7 @@ static_assert(sizeof(AreaTap) == 40, "the scratch is laid out in entries of 40 b
 MCRAW_HD inline int32_t area_c(uint32_t k, uint32_t q, uint32_t Q, uint32_t O)
 {
     const int64_t num = 256 * (static_cast<int64_t>(q) * O - static_cast<int64_t>(k) * Q) + static_cast<int64_t>(Q >> 1);
-    const int64_t d = static_cast<int64_t>(Q);
-    const int64_t fl = num >= 0 ? num / d : -((-num + d - 1) / d); // floor
+    const int64_t fl = floordiv(num, static_cast<int64_t>(Q));
     return static_cast<int32_t>(fl < 0 ? 0 : fl > 256 ? 256 : fl);
 }
 
@@ -82,10 +76,8 @@ struct AreaPlan {
     {
         if (a->reserved[0] != 0u || a->reserved[1] != 0u)
             return "reserved must be 0";
-        if ((a->x0 | a->y0 | a->cw | a->ch) & 1u)
-            return "x0, y0, cw and ch must be even";
-        if (a->cw < 2u || a->ch < 2u || a->cw > 65536u || a->ch > 65536u || a->x0 > 65536u || a->y0 > 65536u)
-            return "the crop must be 2 .. 65536 wide and high";
+        if (const char *why = crop_check(a->x0, a->y0, a->cw, a->ch))
+            return why;
         Qw = a->cw / 2u, Qh = a->ch / 2u;
         const uint32_t Wo = a->out_w, Ho = a->out_h;
         if (Wo < 1u || Wo > Qw || Qw > static_cast<uint64_t>(AREA_MAXRATIO) * Wo || Ho < 1u || Ho > Qh ||
@@ -113,10 +105,8 @@ struct AreaPlan {
         groups = (pairs + ly - 1u) / ly;
         bands = (groups + AREA_BAND - 1u) / AREA_BAND;
         units = tilesX * bands;
-        const auto up = [](size_t v) { return (v + AREA_SECTION - 1u) / AREA_SECTION * AREA_SECTION; };
-        xtab = 0;
-        ytab = up(static_cast<size_t>(Wo) * sizeof(AreaTap));
-        total = up(ytab + static_cast<size_t>(Ho) * sizeof(AreaTap));
+        const TabLayout L = tab_layout(Wo, Ho, sizeof(AreaTap));
+        xtab = L.xtab, ytab = L.ytab, total = L.total;
         return nullptr;
     }
 };
@@ -128,39 +118,13 @@ inline const char *area_check(const mcraw_rgb *p, const mcraw_area *a, const mcr
                               int width, int height, int n, const void *work, size_t work_bytes, const void *out, size_t out_bytes,
                               AreaPlan &plan)
 {
-    plan = AreaPlan{};
-    if (!p || !a || n < 0)
-        return "bad arguments";
-    if (d && yv)
-        return "a display stage and a YUV stage at once";
-    if (n == 0) {
-        plan.rgb.noop = true;
-        return nullptr;
-    }
-    if (width < 4 || height < 4 || (width & 1) || (height & 1) || width > 65536 || height > 65536)
-        return "width and height must be even, 4 .. 65536";
+    constexpr ScaledRules R{MCRAW_RGB_AREA, 4, "width and height must be even, 4 .. 65536", "p->algo must be MCRAW_RGB_AREA",
+                            "work_bytes below mcraw_area_work_bytes(a)"};
     const MosaicBatch I(in, in_pitch, in_frame_stride, static_cast<size_t>(n), width, height);
-    if (const char *why = I.check())
-        return why;
-    if (p->algo != MCRAW_RGB_AREA)
-        return "p->algo must be MCRAW_RGB_AREA";
-    if (const char *why = rgb_check_stage(p, d, yv, colors, ncolors, n, plan.rgb))
-        return why;
-    if (const char *why = plan.geometry(a))
-        return why;
-    if (static_cast<uint64_t>(a->x0) + a->cw > static_cast<uint64_t>(width) || static_cast<uint64_t>(a->y0) + a->ch > static_cast<uint64_t>(height))
-        return "the crop leaves the frame: x0 + cw > width or y0 + ch > height";
-    if (yv && ((plan.rgb.Ho | plan.rgb.Wo) & 1u))
-        return "4:2:0 needs an even out_h and out_w";
-    if (const char *why = rgb_check_out(p, yv != nullptr, n, out, out_bytes, plan.rgb))
-        return why;
-    const uintptr_t k = reinterpret_cast<uintptr_t>(work);
-    if (!k || (k & 15u))
-        return "work missing or not 16-byte aligned";
-    if (work_bytes < plan.total)
-        return "work_bytes below mcraw_area_work_bytes(a)";
-    plan.mode = I.on_grid() ? 2u : ((I.base & 3u) == 0u && I.pitch % 2u == 0u && (I.frames == 1u || I.fstride % 2u == 0u)) ? 1u : 0u;
-    return nullptr;
+    const char *why = scaled_check(R, p, a, d, yv, colors, ncolors, I, n, work, work_bytes, out, out_bytes, plan);
+    if (!why && !plan.rgb.noop)
+        plan.mode = I.on_grid() ? 2u : ((I.base & 3u) == 0u && I.pitch % 2u == 0u && (I.frames == 1u || I.fstride % 2u == 0u)) ? 1u : 0u;
+    return why;
 }
 
 } // namespace mcraw

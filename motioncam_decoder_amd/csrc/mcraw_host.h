@@ -12,9 +12,12 @@
 //   mcraw_denoise.hip  mcraw_denoise_batch: likewise
 //   mcraw_merge.hip    mcraw_merge_batch: likewise
 //   mcraw_align.hip    mcraw_align_batch: likewise (its geometry and scratch layout, free of HIP: mcraw_align_args.h)
-//   mcraw_rgb.hip      the demosaic entry points, mcraw_demosaic_area_batch among them (its checks, plan and weights, free of HIP:
-//                      mcraw_area_args.h on top of mcraw_rgb_args.h); what its kernels share with mcraw_resample.hip: mcraw_rgb_dev.h
+//   mcraw_rgb.hip      the demosaic entry points of mhc and bin2 (their checks and plan, free of HIP: mcraw_rgb_args.h, which also
+//                      holds the window layer that the checks of the two scaled entry points below share)
+//   mcraw_area.hip     mcraw_demosaic_area_batch (its checks, plan and weights, free of HIP: mcraw_area_args.h)
 //   mcraw_resample.hip mcraw_demosaic_resample_batch (its checks, plan and taps, free of HIP: mcraw_resample_args.h)
+//   mcraw_rgb_dev.h      what the kernels of those three share: the kernel arguments, the colour stage, the stores, the LUT staging
+//   mcraw_rgb_launch.h   what their host sides share: the colours, the argument fill, the choice of an instance, the piece loop
 //   mcraw_mosaic.h       device helpers of those six mosaic stages: 8-sample loads and stores, packed-u16 and 24-bit arithmetic,
 //                        the exact rounding divide, the tile-plus-halo staging of the stencil stages
 //   mcraw_mosaic_args.h  one strided batch of mosaics and the checks on it (free of HIP): pointer, size, pitch, frame stride, the

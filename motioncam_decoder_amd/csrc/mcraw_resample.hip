@@ -2,7 +2,7 @@
 // (mcraw_demosaic_resample_batch): the Malvar-He-Cutler estimates of krgb_mhc behind a separable polyphase filter, linear or
 // cubic, into the float, display and YUV families.  The contract and its weights: include/mcraw_hip.h; the checks, the plan
 // and the tap formula, free of HIP: mcraw_resample_args.h; the numpy statement: tests/_resample_ref.py.  The colour stage and
-// the stores are the siblings' (mcraw_rgb_dev.h).
+// the stores are the siblings' (mcraw_rgb_dev.h), the host side of the launch theirs too (mcraw_rgb_launch.h).
 //
 //   kres_tab       the taps of every output column and row, into the caller's scratch, queued in front
 //   krgb_resample  one instance per (output kind, CFA), as the siblings
@@ -22,6 +22,7 @@
 #include "mcraw_host.h"
 #include "mcraw_rgb_args.h"
 #include "mcraw_rgb_dev.h"
+#include "mcraw_rgb_launch.h"
 #include "mcraw_resample_args.h"
 
 namespace mcraw {
@@ -244,92 +245,21 @@ __global__ void __launch_bounds__(RGB_T) krgb_resample(const RgbArgs A, const Re
     } while (LUT && (t += gridDim.x) < A.units * A.nf);
 }
 
-typedef void (*ResKernel)(const RgbArgs, const ResGeo);
-
-template <int PK>
-static ResKernel pick_res(int s)
-{
-    static const ResKernel k[4] = {krgb_resample<PK, 0>, krgb_resample<PK, 1>, krgb_resample<PK, 2>, krgb_resample<PK, 3>};
-    return k[s];
-}
-
-static ResKernel pick_res(const RgbPlan &P)
-{
-    switch (P.kind) {
-    case PK_F32: return pick_res<PK_F32>(P.shift);
-    case PK_F16: return pick_res<PK_F16>(P.shift);
-    case PK_BF16: return pick_res<PK_BF16>(P.shift);
-    case PK_DISP8: return pick_res<PK_DISP8>(P.shift);
-    case PK_DISP16: return pick_res<PK_DISP16>(P.shift);
-    case PK_NV12: return pick_res<PK_NV12>(P.shift);
-    default: return pick_res<PK_P010>(P.shift);
-    }
-}
-
-// Workgroups of a persistent grid that the device holds at once, found once per (device, kernel), as mcraw_rgb.hip's.
-static uint32_t resident_res_groups(int device, ResKernel k)
-{
-    static std::mutex mu;
-    static std::vector<std::pair<std::pair<int, ResKernel>, uint32_t>> seen;
-    std::lock_guard<std::mutex> lk(mu);
-    for (const auto &e : seen)
-        if (e.first.first == device && e.first.second == k)
-            return e.second;
-    int cus = 0, per = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0)
-        cus = 256;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, reinterpret_cast<const void *>(k), RGB_T, 0) != hipSuccess || per <= 0)
-        per = 2;
-    const uint32_t g = static_cast<uint32_t>(cus) * static_cast<uint32_t>(per);
-    seen.push_back({{device, k}, g});
-    return g;
-}
+struct ResK {
+    template <int PK, int S>
+    static auto at() { return &krgb_resample<PK, S>; }
+};
 
 static int resample_launch(mcraw_ctx *c, const mcraw_rgb *p, const mcraw_resample *r, const mcraw_display *d, const mcraw_yuv *yv,
                            const mcraw_rgb_color *colors, int ncolors, const uint16_t *in, size_t in_pitch, size_t in_frame_stride,
                            int width, int height, int n, void *work, const ResamplePlan &P, void *out, hipStream_t st)
 {
-    // (the division is in f32, as every step of the host side of the contract)
-    const float bsum = static_cast<float>(static_cast<int>(p->black[0]) + p->black[1] + p->black[2] + p->black[3]);
-    const float inv = 1.0f / (p->white - 0.25f * bsum);
-    std::vector<RgbCol> cols(static_cast<size_t>(ncolors));
-    for (int i = 0; i < ncolors; i++) {
-        for (int k = 0; k < 3; k++)
-            cols[static_cast<size_t>(i)].k[k] = (colors[i].gain[k] * inv) * 0.0625f;
-        std::memcpy(cols[static_cast<size_t>(i)].m, colors[i].m, sizeof(float) * 9);
-    }
-    ResKernel k = pick_res(P.rgb);
-    RgbArgs A{};
-    A.pitch = in_pitch;
-    A.fstride = in_frame_stride;
-    A.W = static_cast<uint32_t>(width);
-    A.H = static_cast<uint32_t>(height);
+    RgbArgs A = rgb_args(p, d, yv, in_pitch, in_frame_stride, width, height, ncolors);
     A.Wo = static_cast<uint32_t>(P.rgb.Wo);
     A.Ho = static_cast<uint32_t>(P.rgb.Ho);
     A.tilesX = P.tilesX;
     A.units = P.units;
     A.invec = P.rgb.invec;
-    A.clip = (p->flags & MCRAW_FLOAT_CLIP) ? 1u : 0u;
-    A.percol = ncolors > 1 ? 1u : 0u;
-    if (d || yv) {
-        A.lut = d ? d->lut : yv->lut;
-        A.lutn = 1u << (d ? d->lut_log2 : yv->lut_log2);
-        A.lutg = A.lutn > DISP_LDS_MAX ? 1u : 0u;
-        A.hwc = d && d->layout == MCRAW_DISP_HWC ? 1u : 0u;
-    }
-    if (yv) {
-        for (int i = 0; i < 3; i++) {
-            A.ycf[i] = yv->cy[i];
-            A.ycf[3 + i] = yv->cb[i];
-            A.ycf[6 + i] = yv->cr[i];
-        }
-        A.ymask = (1u << yv->in_bits) - 1u;
-        A.ysh = yv->sh;
-        A.yoff = yv->y_off;
-        A.coff = yv->c_off;
-    }
-    for (int i = 0; i < 4; i++)
-        A.black[i] = p->black[i];
     ResGeo G{};
     G.xt = reinterpret_cast<const ResampleTap *>(static_cast<const char *>(work) + P.xtab);
     G.yt = reinterpret_cast<const ResampleTap *>(static_cast<const char *>(work) + P.ytab);
@@ -339,22 +269,7 @@ static int resample_launch(mcraw_ctx *c, const mcraw_rgb *p, const mcraw_resampl
     hipLaunchKernelGGL(kres_tab, dim3((A.Wo + A.Ho + RGB_T - 1u) / RGB_T), dim3(RGB_T), 0, st, const_cast<ResampleTap *>(G.xt),
                        const_cast<ResampleTap *>(G.yt), r->cw, A.Wo, r->ch, A.Ho, r->filter);
     HIP_TRY(hipGetLastError());
-    const bool persistent = has_lut(P.rgb.kind);
-    const uint32_t resident = persistent ? resident_res_groups(c->device, k) : 0u;
-    const int piece = A.percol ? RGB_MAXF : 65535;
-    for (int f0 = 0; f0 < n; f0 += piece) {
-        const int nf = std::min(piece, n - f0);
-        A.in = in + static_cast<size_t>(f0) * in_frame_stride;
-        A.out = static_cast<uint8_t *>(out) + static_cast<size_t>(f0) * P.rgb.out_frame;
-        A.nf = static_cast<uint32_t>(nf);
-        for (int i = 0; i < (A.percol ? nf : 1); i++)
-            A.col[i] = cols[static_cast<size_t>(A.percol ? f0 + i : 0)];
-        const dim3 grid = persistent ? dim3(static_cast<uint32_t>(std::min<uint64_t>(static_cast<uint64_t>(P.units) * nf, resident)))
-                                     : dim3(P.units, static_cast<uint32_t>(nf));
-        hipLaunchKernelGGL(k, grid, dim3(RGB_T), 0, st, A, G);
-        HIP_TRY(hipGetLastError());
-    }
-    return 0;
+    return rgb_launch(c, rgb_pick<ResK>(P.rgb), A, P.rgb, rgb_cols(p, colors, ncolors, 0.0625f), in, n, out, -1, st, G);
 }
 
 } // namespace mcraw

@@ -2,19 +2,14 @@
 // launched: accept, reject or no-op; on acceptance the plan of the launch (the workgroup's tile, its LDS arrays) and the layout
 // of the caller's scratch; and the tap formula itself, as a plain function that the table kernel and the tests share.
 // No HIP in here, so that tests/cpp/resample_args_check.cpp can drive it on any machine.  The family's own rules (display / YUV
-// struct, dtype, cfa, white, colours, `out`) are rgb_check's pieces (mcraw_rgb_args.h), run in area_check's order.
+// struct, dtype, cfa, white, colours, `out`) are rgb_check's pieces (mcraw_rgb_args.h), run in area_check's order: the sequence
+// of the checks, the crop's rules and the scratch's layout are that header's window layer, shared with mcraw_area_args.h.
 #pragma once
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
 
 #include "mcraw_rgb_args.h"
-
-#if defined(__HIPCC__)
-#define MCRAW_RHD __host__ __device__
-#else
-#define MCRAW_RHD
-#endif
 
 namespace mcraw {
 
@@ -26,7 +21,7 @@ constexpr uint32_t RES_TSTRIDE = 68u; // LDS: dwords of a row of t: the tile's 6
 constexpr uint32_t RES_G = 4u;        // LDS: source row pairs whose MHC estimates are held at a time
 constexpr uint32_t RES_ECOLS = 144u;  // LDS: source columns of the estimates (18 pieces of 8)
 constexpr uint32_t RES_RAWW = RES_ECOLS + 16u; // LDS: raw samples of a row: 8 either side of the estimates (2 used), as krgb_mhc
-constexpr size_t RES_SECTION = 256u;  // the tables of the scratch start on multiples of this
+constexpr size_t RES_SECTION = TAB_SECTION; // the tables of the scratch start on multiples of this
 
 // One output column or row in the scratch: the first sample that carries weight, relative to the crop (negative in front of
 // it), how many do, and the weights (4096 in all; those behind `nt` are 0).
@@ -37,19 +32,14 @@ struct ResampleTap {
 };
 static_assert(sizeof(ResampleTap) == 24, "the scratch is laid out in entries of 24 bytes");
 
-MCRAW_RHD inline int64_t res_floordiv(int64_t a, int64_t b) // b > 0
-{
-    return a >= 0 ? a / b : -((-a + b - 1) / b);
-}
-
 // n(k, j) of the contract: 2 O times the distance of crop sample j from output pixel k's position.
-MCRAW_RHD inline int64_t res_n(uint32_t k, int64_t j, uint32_t C, uint32_t O)
+MCRAW_HD inline int64_t res_n(uint32_t k, int64_t j, uint32_t C, uint32_t O)
 {
     return 2 * static_cast<int64_t>(O) * j - ((2 * static_cast<int64_t>(k) + 1) * C - static_cast<int64_t>(O));
 }
 
 // The raw kernel value f of the contract at distance |n| / D of the stretched unit.
-MCRAW_RHD inline int64_t res_f(int64_t n, int64_t D, uint32_t filter)
+MCRAW_HD inline int64_t res_f(int64_t n, int64_t D, uint32_t filter)
 {
     const int64_t a = (1024 * (n < 0 ? -n : n) + D / 2) / D;
     if (filter == 0u)
@@ -64,11 +54,11 @@ MCRAW_RHD inline int64_t res_f(int64_t n, int64_t D, uint32_t filter)
 // The taps of output pixel k: C crop samples onto O pixels, ceil(C / 2) <= O <= 2 C.  The residual 4096 - sum w goes to the tap
 // nearest to the pixel's position (smallest |n|); two taps equally near (the position lies half way between them, every tap has
 // a mirror image, the residual is even) take half of it each.
-MCRAW_RHD inline void resample_taps(uint32_t k, uint32_t C, uint32_t O, uint32_t filter, ResampleTap &t)
+MCRAW_HD inline void resample_taps(uint32_t k, uint32_t C, uint32_t O, uint32_t filter, ResampleTap &t)
 {
     constexpr int CAND = 12;
     const int64_t D = 2 * static_cast<int64_t>(C > O ? C : O);
-    const int64_t jc = res_floordiv((2 * static_cast<int64_t>(k) + 1) * C - static_cast<int64_t>(O), 2 * static_cast<int64_t>(O));
+    const int64_t jc = floordiv((2 * static_cast<int64_t>(k) + 1) * C - static_cast<int64_t>(O), 2 * static_cast<int64_t>(O));
     int64_t f[CAND], F = 0;
     int first = -1, last = -1;
     for (int i = 0; i < CAND; i++) { // |j - u| < 2 r <= 4 and jc = floor(u): jc - 3 .. jc + 4 can carry weight
@@ -87,7 +77,7 @@ MCRAW_RHD inline void resample_taps(uint32_t k, uint32_t C, uint32_t O, uint32_t
     for (int i = 0; i < static_cast<int>(RES_TAPS); i++) {
         int64_t w = 0;
         if (first + i <= last) {
-            w = res_floordiv(4096 * f[first + i] + F / 2, F);
+            w = floordiv(4096 * f[first + i] + F / 2, F);
             const int64_t n = res_n(k, jc - 5 + first + i, C, O), an = n < 0 ? -n : n;
             if (best < 0 || an < best)
                 best = an, near0 = i, near1 = -1;
@@ -141,10 +131,8 @@ struct ResamplePlan {
             return "reserved must be 0";
         if (r->filter != MCRAW_FILTER_LINEAR && r->filter != MCRAW_FILTER_CUBIC)
             return "unknown filter";
-        if ((r->x0 | r->y0 | r->cw | r->ch) & 1u)
-            return "x0, y0, cw and ch must be even";
-        if (r->cw < 2u || r->ch < 2u || r->cw > 65536u || r->ch > 65536u || r->x0 > 65536u || r->y0 > 65536u)
-            return "the crop must be 2 .. 65536 wide and high";
+        if (const char *why = crop_check(r->x0, r->y0, r->cw, r->ch))
+            return why;
         const uint32_t Wo = r->out_w, Ho = r->out_h;
         if (2u * Wo < r->cw || Wo > 2u * r->cw || 2u * Ho < r->ch || Ho > 2u * r->ch)
             return "the output must be 1/2 .. 2 of the crop: ceil(cw / 2) <= out_w <= 2 cw, likewise out_h";
@@ -158,10 +146,8 @@ struct ResamplePlan {
         tilesX = (Wo + RES_TW - 1u) / RES_TW;
         bands = ((Ho + 1u) / 2u + ly - 1u) / ly;
         units = tilesX * bands;
-        const auto up = [](size_t v) { return (v + RES_SECTION - 1u) / RES_SECTION * RES_SECTION; };
-        xtab = 0;
-        ytab = up(static_cast<size_t>(Wo) * sizeof(ResampleTap));
-        total = up(ytab + static_cast<size_t>(Ho) * sizeof(ResampleTap));
+        const TabLayout L = tab_layout(Wo, Ho, sizeof(ResampleTap));
+        xtab = L.xtab, ytab = L.ytab, total = L.total;
         return nullptr;
     }
 };
@@ -175,39 +161,13 @@ inline const char *resample_check(const mcraw_rgb *p, const mcraw_resample *r, c
                                   size_t in_frame_stride, int width, int height, int n, const void *work, size_t work_bytes,
                                   const void *out, size_t out_bytes, ResamplePlan &plan)
 {
-    plan = ResamplePlan{};
-    if (!p || !r || n < 0)
-        return "bad arguments";
-    if (d && yv)
-        return "a display stage and a YUV stage at once";
-    if (n == 0) {
-        plan.rgb.noop = true;
-        return nullptr;
-    }
-    if (width < 8 || height < 8 || (width & 1) || (height & 1) || width > 65536 || height > 65536)
-        return "width and height must be even, 8 .. 65536";
+    constexpr ScaledRules R{MCRAW_RGB_RESAMPLE, 8, "width and height must be even, 8 .. 65536", "p->algo must be MCRAW_RGB_RESAMPLE",
+                            "work_bytes below mcraw_resample_work_bytes(r)"};
     const MosaicBatch I(in, in_pitch, in_frame_stride, static_cast<size_t>(n), width, height);
-    if (const char *why = I.check())
-        return why;
-    if (p->algo != MCRAW_RGB_RESAMPLE)
-        return "p->algo must be MCRAW_RGB_RESAMPLE";
-    if (const char *why = rgb_check_stage(p, d, yv, colors, ncolors, n, plan.rgb))
-        return why;
-    if (const char *why = plan.geometry(r))
-        return why;
-    if (static_cast<uint64_t>(r->x0) + r->cw > static_cast<uint64_t>(width) || static_cast<uint64_t>(r->y0) + r->ch > static_cast<uint64_t>(height))
-        return "the crop leaves the frame: x0 + cw > width or y0 + ch > height";
-    if (yv && ((plan.rgb.Ho | plan.rgb.Wo) & 1u))
-        return "4:2:0 needs an even out_h and out_w";
-    if (const char *why = rgb_check_out(p, yv != nullptr, n, out, out_bytes, plan.rgb))
-        return why;
-    const uintptr_t k = reinterpret_cast<uintptr_t>(work);
-    if (!k || (k & 15u))
-        return "work missing or not 16-byte aligned";
-    if (work_bytes < plan.total)
-        return "work_bytes below mcraw_resample_work_bytes(r)";
-    plan.rgb.invec = I.on_grid();
-    return nullptr;
+    const char *why = scaled_check(R, p, r, d, yv, colors, ncolors, I, n, work, work_bytes, out, out_bytes, plan);
+    if (!why && !plan.rgb.noop)
+        plan.rgb.invec = I.on_grid();
+    return why;
 }
 
 } // namespace mcraw

@@ -2,9 +2,12 @@
 // call before anything is launched: accept, reject or no-op, and on acceptance the plan of the launch (output sizes, launch
 // geometry, CFA role shift, kernel kind).  No HIP in here, so that tests/cpp/rgb_args_check.cpp can drive it on any machine.
 // The input batch is a MosaicBatch (mcraw_mosaic_args.h): its base, alignment, pitch and frame-stride checks and its 16-byte
-// grid are that header's.
+// grid are that header's.  At the end, the window layer: what the checks of the two scaled entry points (mcraw_area_args.h,
+// mcraw_resample_args.h) share.
 #pragma once
 #include <cmath>
+#include <cstddef>
+#include <cstdint>
 #include <cstdlib>
 
 #include "../../include/mcraw_hip.h"
@@ -165,6 +168,94 @@ inline const char *rgb_check(const mcraw_rgb *p, const mcraw_display *d, const m
         // items: 8 output columns of an output row (YUV kinds: of an output row pair)
         plan.units = static_cast<uint32_t>((static_cast<size_t>(plan.tilesX) * (yv ? plan.Ho / 2u : plan.Ho) + RGB_T - 1u) / RGB_T);
     }
+    return nullptr;
+}
+
+// ---- the window layer ---------------------------------------------------------------------------------------------------
+//
+// What the scaled entry points (mcraw_demosaic_area_batch: mcraw_area_args.h; mcraw_demosaic_resample_batch:
+// mcraw_resample_args.h) share: both map a crop window (x0, y0, cw, ch) of the frame onto out_w x out_h pixels through two tables
+// of taps in the caller's scratch.  A scaled stage brings its window struct, a plan with `rgb`, `total` and a geometry() for the
+// struct's own rules (reserved fields, ratio, tiles), and its tap formula; the sequence of the checks is scaled_check's.
+#if defined(__HIPCC__)
+#define MCRAW_HD __host__ __device__
+#else
+#define MCRAW_HD
+#endif
+
+MCRAW_HD inline int64_t floordiv(int64_t a, int64_t b) // b > 0
+{
+    return a >= 0 ? a / b : -((-a + b - 1) / b);
+}
+
+constexpr size_t TAB_SECTION = 256u; // the tables of the scratch start on multiples of this
+
+// The scratch of a scaled call: the taps of the Wo columns, then of the Ho rows, `tap` bytes each.
+struct TabLayout {
+    size_t xtab, ytab, total; // byte offsets of the two tables, and the size
+};
+inline TabLayout tab_layout(size_t Wo, size_t Ho, size_t tap)
+{
+    const auto up = [](size_t v) { return (v + TAB_SECTION - 1u) / TAB_SECTION * TAB_SECTION; };
+    const size_t ytab = up(Wo * tap);
+    return {0u, ytab, up(ytab + Ho * tap)};
+}
+
+// Why the window is none on its own (whether it fits the frame is scaled_check's question).
+inline const char *crop_check(uint32_t x0, uint32_t y0, uint32_t cw, uint32_t ch)
+{
+    if ((x0 | y0 | cw | ch) & 1u)
+        return "x0, y0, cw and ch must be even";
+    if (cw < 2u || ch < 2u || cw > 65536u || ch > 65536u || x0 > 65536u || y0 > 65536u)
+        return "the crop must be 2 .. 65536 wide and high";
+    return nullptr;
+}
+
+// Where the two stages' checks differ: the algo code, the smallest frame, and the messages that name either.
+struct ScaledRules {
+    uint32_t algo;
+    int min_side;
+    const char *side_why, *algo_why, *work_why;
+};
+
+// Why the call is rejected, or nullptr with plan.rgb and the plan's geometry filled (plan.rgb.noop: an empty batch, nothing else
+// is set); how the input is fetched (I.on_grid()) is left to the caller.  d: the display family, yv: the YUV family (never both);
+// neither: the float family.  Addresses are only looked at as numbers.
+template <class Win, class Plan>
+inline const char *scaled_check(const ScaledRules &R, const mcraw_rgb *p, const Win *w, const mcraw_display *d, const mcraw_yuv *yv,
+                                const mcraw_rgb_color *colors, int ncolors, const MosaicBatch &I, int n, const void *work,
+                                size_t work_bytes, const void *out, size_t out_bytes, Plan &plan)
+{
+    plan = Plan{};
+    if (!p || !w || n < 0)
+        return "bad arguments";
+    if (d && yv)
+        return "a display stage and a YUV stage at once";
+    if (n == 0) {
+        plan.rgb.noop = true;
+        return nullptr;
+    }
+    if (I.W < R.min_side || I.H < R.min_side || (I.W & 1) || (I.H & 1) || I.W > 65536 || I.H > 65536)
+        return R.side_why;
+    if (const char *why = I.check())
+        return why;
+    if (p->algo != R.algo)
+        return R.algo_why;
+    if (const char *why = rgb_check_stage(p, d, yv, colors, ncolors, n, plan.rgb))
+        return why;
+    if (const char *why = plan.geometry(w))
+        return why;
+    if (static_cast<uint64_t>(w->x0) + w->cw > static_cast<uint64_t>(I.W) || static_cast<uint64_t>(w->y0) + w->ch > static_cast<uint64_t>(I.H))
+        return "the crop leaves the frame: x0 + cw > width or y0 + ch > height";
+    if (yv && ((plan.rgb.Ho | plan.rgb.Wo) & 1u))
+        return "4:2:0 needs an even out_h and out_w";
+    if (const char *why = rgb_check_out(p, yv != nullptr, n, out, out_bytes, plan.rgb))
+        return why;
+    const uintptr_t k = reinterpret_cast<uintptr_t>(work);
+    if (!k || (k & 15u))
+        return "work missing or not 16-byte aligned";
+    if (work_bytes < plan.total)
+        return R.work_why;
     return nullptr;
 }
 

@@ -1,7 +1,8 @@
-// mcraw_rgb_dev.h -- the device code that every demosaic kernel shares (csrc/mcraw_rgb.hip: krgb_mhc, krgb_bin2, krgb_area;
-// csrc/mcraw_resample.hip: krgb_resample): the kernel arguments, the colour stage and the stores of the float, display and YUV
-// families, and the LUT staging.  Moved here from mcraw_rgb.hip as it stood: tools/rgb_resources.py --check holds every instance
-// of that file to its committed figures.
+// mcraw_rgb_dev.h -- the device code that every demosaic kernel shares (csrc/mcraw_rgb.hip: krgb_mhc, krgb_bin2;
+// csrc/mcraw_area.hip: krgb_area; csrc/mcraw_resample.hip: krgb_resample): the kernel arguments, the colour stage and the stores
+// of the float, display and YUV families, and the LUT staging.  Moved here from mcraw_rgb.hip as it stood:
+// tools/rgb_resources.py --check holds every instance of those files to its committed figures.  The host side that the three
+// files share: mcraw_rgb_launch.h.
 #pragma once
 #include "mcraw_dev.h"
 #include "mcraw_host.h"

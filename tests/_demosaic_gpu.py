@@ -1,5 +1,5 @@
-"""What the GPU tests of the three demosaic entry points (test_gpu_rgb / _display / _yuv .py) build alike: constants, tensors
-to and from numpy, random inputs, the C structs, encoded frames with the oracle's decode, and the raw C call."""
+"""What the GPU tests of the demosaic entry points (test_gpu_rgb / _display / _yuv / _area / _resample .py) build alike:
+constants, tensors to and from numpy, random inputs, the C structs, encoded frames with the oracle's decode, and the raw C calls."""
 import ctypes as C
 
 import numpy as np
@@ -7,6 +7,7 @@ import torch
 
 import _libs as L
 import _rgb_ref as R
+import _yuv_ref as Y
 import motioncam_decoder_amd as M
 
 DEV = torch.device("cuda:0")
@@ -78,3 +79,58 @@ def raw_call(ctx, symbol, prm, stage, cols, ncol, in_ptr, pitch, fstride, w, h, 
         structs.append(C.byref(stage) if stage is not None else None)
     return getattr(M.load(), symbol)(ctx._h, *structs, arr, ncol, C.c_void_p(in_ptr), pitch, fstride, w, h, n, C.c_void_p(out_ptr),
                                      out_bytes, C.c_void_p(stream))
+
+
+# ---- the scaled entry points (test_gpu_area / _resample .py)
+
+FLOATS = (("f32", torch.int32), ("f16", torch.int16), ("bf16", torch.int16))
+TD = {"u8": torch.uint8, "u16": torch.uint16, "nv12": torch.uint8, "p010": torch.uint16}
+IN_BITS = 11
+
+
+def bits(t, view):
+    return t.contiguous().view(view).cpu().numpy().view(np.uint32 if view == torch.int32 else np.uint16)
+
+
+def as_int(t):
+    return t.view(torch.int16) if t.dtype == torch.uint16 else t
+
+
+def display(lut_ptr, dtype="u8", layout="hwc", log2=12):
+    d = M.Display()
+    d.dtype, d.layout, d.lut_log2, d.reserved, d.lut = M.DISP_U8 if dtype == "u8" else M.DISP_U16, M._DISP_LAYOUTS[layout], log2, 0, lut_ptr
+    return d
+
+
+def yuv(lut_ptr, fmt="nv12", log2=12, in_bits=IN_BITS):
+    cy, cb, cr, sh, y_off, c_off = M.yuv_matrix("bt709", "limited", Y.BITS[fmt], in_bits)
+    y = M.Yuv()
+    y.format, y.lut_log2, y.in_bits, y.sh, y.y_off, y.c_off = (1 if fmt == "nv12" else 2), log2, in_bits, sh, y_off, c_off
+    for i in range(3):
+        y.cy[i], y.cb[i], y.cr[i] = cy[i], cb[i], cr[i]
+    y.reserved, y.lut = 0, lut_ptr
+    return y
+
+
+def colours(gain, matrix, i):
+    g = np.asarray(gain, dtype=np.float32)
+    m = np.asarray(matrix, dtype=np.float32)
+    return (g[i] if g.ndim == 2 else g), (m[i] if m.ndim == 3 else m)
+
+
+def raw_scaled_call(symbol, ctx, prm, win, d, y, cols, ncol, in_ptr, pitch, fstride, w, h, n, work_ptr, work_bytes, out_ptr, out_bytes,
+                    stream=None):
+    """The C entry point `symbol` of a scaled algo as it is: prm, win (its window struct), d and y may be None (NULL pointers)."""
+    arr = (M.RgbColor * max(ncol, 1))()
+    for i in range(min(ncol, len(cols))):
+        arr[i] = cols[i]
+    ref = [C.byref(s) if s is not None else None for s in (prm, win, d, y)]
+    return getattr(M.load(), symbol)(ctx._h, *ref, arr, ncol, C.c_void_p(in_ptr), pitch, fstride, w, h, n, C.c_void_p(work_ptr),
+                                     work_bytes, C.c_void_p(out_ptr), out_bytes, C.c_void_p(stream))
+
+
+def work_bytes(symbol, win):
+    """The scratch that the window struct `win` needs, from the library's `symbol`."""
+    need = int(getattr(M.load(), symbol)(C.byref(win)))
+    assert need > 0
+    return need

@@ -369,6 +369,44 @@ int main()
                          c.n, reinterpret_cast<const void *>(c.work), c.work_bytes, reinterpret_cast<const void *>(c.out), c.out_bytes, AP);
         CHECK(why && std::strcmp(why, "p->algo must be MCRAW_RGB_AREA") == 0);
     }
+    { // the faults that the two scaled entry points share come out of one sequence: the same text from both
+        const auto both = [&](const char *text, auto bend) { // bend(call, is it the area call): the fault, nullptr: none
+            Call c[2] = {good(), good()};
+            const char *why[2];
+            for (int area = 0; area < 2; area++) {
+                Call &k = c[area];
+                k.p.algo = area ? MCRAW_RGB_AREA : MCRAW_RGB_RESAMPLE;
+                k.width = k.height = 16, k.pitch = 16, k.fstride = 256, k.n = 1;
+                k.r.x0 = k.r.y0 = 0, k.r.cw = k.r.ch = 16, k.r.out_w = k.r.out_h = 8;
+                bend(k, area != 0);
+            }
+            ResamplePlan RP;
+            why[0] = run(c[0], RP);
+            const Call &k = c[1];
+            mcraw_area a;
+            std::memset(&a, 0, sizeof a);
+            a.x0 = k.r.x0, a.y0 = k.r.y0, a.cw = k.r.cw, a.ch = k.r.ch, a.out_w = k.r.out_w, a.out_h = k.r.out_h;
+            AreaPlan AP;
+            why[1] = area_check(k.has_p ? &k.p : nullptr, k.has_r ? &a : nullptr, k.has_d ? &k.d : nullptr, k.has_y ? &k.y : nullptr, k.col,
+                                k.ncolors, reinterpret_cast<const uint16_t *>(k.in), k.pitch, k.fstride, k.width, k.height, k.n,
+                                reinterpret_cast<const void *>(k.work), k.work_bytes, reinterpret_cast<const void *>(k.out), k.out_bytes, AP);
+            if (!text)
+                CHECK(!why[0] && !why[1] && !RP.rgb.noop && !AP.rgb.noop);
+            else
+                CHECK(why[0] && why[1] && std::strcmp(why[0], why[1]) == 0 && std::strcmp(why[0], text) == 0);
+        };
+        both(nullptr, [](Call &, bool) {});
+        both(nullptr, [](Call &k, bool) { k.has_y = true, k.p.dtype = 0; });
+        both("bad arguments", [](Call &k, bool) { k.has_p = false; });
+        both("a display stage and a YUV stage at once", [](Call &k, bool) { k.has_d = k.has_y = true, k.p.dtype = 0; });
+        both("x0, y0, cw and ch must be even", [](Call &k, bool) { k.r.x0 = 1; });
+        both("the crop must be 2 .. 65536 wide and high", [](Call &k, bool) { k.r.cw = 0; });
+        both("the crop leaves the frame: x0 + cw > width or y0 + ch > height", [](Call &k, bool) { k.r.x0 = 2; });
+        // (an odd out_w inside either's ratio rule: at most the crop's 8 quads for area, at least half the crop's 16 samples here)
+        both("4:2:0 needs an even out_h and out_w", [](Call &k, bool area) { k.has_y = true, k.p.dtype = 0, k.r.out_w = area ? 7 : 9; });
+        both("work missing or not 16-byte aligned", [](Call &k, bool) { k.work = 0; });
+        both("work missing or not 16-byte aligned", [](Call &k, bool) { k.work += 8; });
+    }
 
     // seeded tuples of geometry, family and pointers
     std::mt19937 rng(20261019u);

@@ -17,21 +17,12 @@ import motioncam_decoder_amd as M
 from _demosaic_gpu import CFAS, DEV, GUARD, SENT, SRGBISH
 from _demosaic_gpu import dev16 as _dev16, frames as _frames, mosaic as _mosaic, rand_lut as _rand_lut, rgb_color as _color
 from _demosaic_gpu import rgb_params as _params, to_np as _np
+from _demosaic_gpu import FLOATS, IN_BITS, TD, as_int as _as_int, bits as _bits, colours as _colours, display as _display, yuv as _yuv
+from _demosaic_gpu import raw_scaled_call, work_bytes
 
 pytestmark = pytest.mark.gpu
 
 SYM = "mcraw_demosaic_resample_batch"
-FLOATS = (("f32", torch.int32), ("f16", torch.int16), ("bf16", torch.int16))
-TD = {"u8": torch.uint8, "u16": torch.uint16, "nv12": torch.uint8, "p010": torch.uint16}
-IN_BITS = 11
-
-
-def _bits(t, view):
-    return t.contiguous().view(view).cpu().numpy().view(np.uint32 if view == torch.int32 else np.uint16)
-
-
-def _as_int(t):
-    return t.view(torch.int16) if t.dtype == torch.uint16 else t
 
 
 def _rparams(white=4095.0, black=(0, 0, 0, 0), cfa="rggb", dtype=1, flags=0, algo=4):
@@ -49,42 +40,13 @@ def _res(crop, size, filt=1, reserved=0):
     return r
 
 
-def _display(lut_ptr, dtype="u8", layout="hwc", log2=12):
-    d = M.Display()
-    d.dtype, d.layout, d.lut_log2, d.reserved, d.lut = M.DISP_U8 if dtype == "u8" else M.DISP_U16, M._DISP_LAYOUTS[layout], log2, 0, lut_ptr
-    return d
-
-
-def _yuv(lut_ptr, fmt="nv12", log2=12, in_bits=IN_BITS):
-    cy, cb, cr, sh, y_off, c_off = M.yuv_matrix("bt709", "limited", Y.BITS[fmt], in_bits)
-    y = M.Yuv()
-    y.format, y.lut_log2, y.in_bits, y.sh, y.y_off, y.c_off = (1 if fmt == "nv12" else 2), log2, in_bits, sh, y_off, c_off
-    for i in range(3):
-        y.cy[i], y.cb[i], y.cr[i] = cy[i], cb[i], cr[i]
-    y.reserved, y.lut = 0, lut_ptr
-    return y
-
-
-def _raw(ctx, prm, res, d, y, cols, ncol, in_ptr, pitch, fstride, w, h, n, work_ptr, work_bytes, out_ptr, out_bytes, stream=None):
+def _raw(ctx, *args, **kw):
     """The C entry point as it is: prm, res, d and y may be None (NULL pointers)."""
-    arr = (M.RgbColor * max(ncol, 1))()
-    for i in range(min(ncol, len(cols))):
-        arr[i] = cols[i]
-    ref = [C.byref(s) if s is not None else None for s in (prm, res, d, y)]
-    return M.load().mcraw_demosaic_resample_batch(ctx._h, *ref, arr, ncol, C.c_void_p(in_ptr), pitch, fstride, w, h, n,
-                                                  C.c_void_p(work_ptr), work_bytes, C.c_void_p(out_ptr), out_bytes, C.c_void_p(stream))
+    return raw_scaled_call(SYM, ctx, *args, **kw)
 
 
 def _work_bytes(crop, size):
-    need = int(M.load().mcraw_resample_work_bytes(C.byref(_res(crop, size))))
-    assert need > 0
-    return need
-
-
-def _colours(gain, matrix, i):
-    g = np.asarray(gain, dtype=np.float32)
-    m = np.asarray(matrix, dtype=np.float32)
-    return (g[i] if g.ndim == 2 else g), (m[i] if m.ndim == 3 else m)
+    return work_bytes("mcraw_resample_work_bytes", _res(crop, size))
 
 
 def _check_families(ctx, t, imgs, crop, size, cfa="rggb", black=(0, 0, 0, 0), white=4095.0, gain=(1.8, 1.0, 1.3), matrix=SRGBISH,

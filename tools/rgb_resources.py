@@ -4,7 +4,7 @@ statistics kernels (csrc/mcraw_stats.hip), of the defective-pixel kernels (csrc/
 (csrc/mcraw_denoise.hip), of the temporal merge (csrc/mcraw_merge.hip) and of the shift estimate (csrc/mcraw_align.hip): compiles the files for gfx950 with -Rpass-analysis=kernel-resource-usage (no GPU needed) and prints
 one line per instance in the format of profiles/rgb_resources.txt / display_resources.txt / yuv_resources.txt /
 shade_resources.txt / stats_resources.txt / fixpix_resources.txt / denoise_resources.txt / merge_resources.txt / align_resources.txt /
-area_resources.txt (the area downscale's instances, krgb_area and karea_tab, which live in csrc/mcraw_rgb.hip) /
+area_resources.txt (csrc/mcraw_area.hip: krgb_area and karea_tab) /
 resample_resources.txt (csrc/mcraw_resample.hip: krgb_resample and kres_tab).
 
     python tools/rgb_resources.py            # every instance
@@ -108,7 +108,7 @@ def main():
     rep, shade, stats = report(), report("mcraw_shade.hip", SHADE_NAME), report("mcraw_stats.hip", STATS_NAME)
     fixpix, denoise = report("mcraw_fixpix.hip", FIXPIX_NAME), report("mcraw_denoise.hip", DENOISE_NAME)
     merge, align = report("mcraw_merge.hip", MERGE_NAME), report("mcraw_align.hip", ALIGN_NAME)
-    area = report("mcraw_rgb.hip", AREA_NAME)
+    area = report("mcraw_area.hip", AREA_NAME)
     resample = report("mcraw_resample.hip", RESAMPLE_NAME)
     if "--check" not in sys.argv:
         for line in list(rep.values()) + list(shade.values()) + list(stats.values()) + list(fixpix.values()) + list(denoise.values()) + \
