@@ -87,8 +87,11 @@ def build_variant(out, flags=()):
     import re
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     names = [re.sub(r"^-D([A-Za-z0-9_]+).*$", r"\1", f) for f in flags if f.startswith("-D")]
-    everything = len(names) != len(flags) or any(n in open(os.path.join(CSRC, h)).read() for n in names for h in HIP_HEADERS)
-    touched = [s for s in hip_sources() if everything or any(n in open(s).read() for n in names)]
+    def mentions(path):  # (whole names: MCRAW_INJECT_LOST is not in a file that only has MCRAW_INJECT_LOSTE)
+        text = open(path).read()
+        return any(re.search(r"\b%s\b" % n, text) for n in names)
+    everything = len(names) != len(flags) or any(mentions(os.path.join(CSRC, h)) for h in HIP_HEADERS)
+    touched = [s for s in hip_sources() if everything or mentions(s)]
     tag = ".v" + hashlib.sha1(" ".join(flags).encode()).hexdigest()[:10]
     plain, _ = _objects(only=[s for s in hip_sources() if s not in touched])
     special, _ = _objects(flags, tag, only=touched)
@@ -136,10 +139,23 @@ K7_PATH_VARIANTS = {
     "poison": ["-DMCRAW_PATHS7", "-DMCRAW_POISON_STRIDES7"],
 }
 
+# The encoder's two kernels with every path counted and one forced or injected (tests/test_gpu_enc7_paths.py; the switches and why
+# each is valid for every input: csrc/mcraw_encode7.hip).  Every name below occurs in mcraw_encode7.hip alone, so a variant
+# compiles that one source.
+#   wrap  MCRAW_EPOCH0E=0xFFFFFFFD: the epoch of a context's third encode batch wraps to 1.
+ENC7_PATH_VARIANTS = {
+    "census": ["-DMCRAW_PATHSE"],
+    "refetch": ["-DMCRAW_PATHSE", "-DMCRAW_FORCE_REFETCHE"],
+    "aggonly": ["-DMCRAW_PATHSE", "-DMCRAW_FORCE_AGGONLYE"],
+    "slow": ["-DMCRAW_PATHSE", "-DMCRAW_INJECT_SLOWE"],
+    "lost": ["-DMCRAW_PATHSE", "-DMCRAW_INJECT_LOSTE"],
+    "wrap": ["-DMCRAW_PATHSE", "-DMCRAW_EPOCH0E=0xFFFFFFFDu"],
+}
+
 # The -D builds that tests/ links on the GPU box (tests/test_gpu_split.py, test_gpu_segw.py, test_gpu_lookback_fault.py,
-# test_gpu_k6_paths.py, test_gpu_k7_paths.py).
+# test_gpu_k6_paths.py, test_gpu_k7_paths.py, test_gpu_enc7_paths.py).
 TEST_VARIANTS = ((["-DMCRAW_FORCE_SEGW"], ["-DMCRAW_INJECT_MUTE7"], ["-DMCRAW_INJECT_LOST"]) + tuple(K6_PATH_VARIANTS.values())
-                 + tuple(K7_PATH_VARIANTS.values()))
+                 + tuple(K7_PATH_VARIANTS.values()) + tuple(ENC7_PATH_VARIANTS.values()))
 
 
 def prebuild_test_variants():

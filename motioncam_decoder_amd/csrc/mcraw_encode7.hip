@@ -26,7 +26,102 @@ constexpr uint32_t SIDE_STRIDE = 9;            // uint4 per lane in k7e_side's L
 // Look-back words (EncWork::look, never cleared): epoch << 32 | state << 30 | payload bytes / 8.  A word is complete in
 // itself, so it is published by ONE relaxed device-scope store and read by relaxed device-scope loads: no fence.
 constexpr uint32_t LB_AGG = 1u, LB_PREFIX = 2u, LB_FAIL = 3u;
+#ifdef MCRAW_INJECT_LOSTE // test builds (below): a segment of the batch's first frame never publishes
+constexpr uint32_t SPIN7E = 1u << 12;
+#else
 constexpr uint32_t SPIN7E = 1u << 20; // polls of an unchanged window before the frame is given up (status MCRAW_E_DEVICE)
+#endif
+
+// Test builds of the encoder (tests/test_gpu_enc7_paths.py, build.ENC7_PATH_VARIANTS; none of this is in the product library).
+// Which way a workgroup of k7e_payload goes is decided by the frame's content and geometry -- loads, classes, records -- and by
+// timing: whether its guess was its ticket, and what its look-back finds published.  Every switch below chooses among ways that
+// are right for EVERY input:
+//   MCRAW_PATHSE              the path census below
+//   MCRAW_FORCE_REFETCHE      the guess is never fetched; every live workgroup fetches its segment behind the ticket.  The
+//                             guess is only a prefetch: what a workgroup encodes is always the segment of its ticket.
+//   MCRAW_FORCE_AGGONLYE      a segment behind the first never upgrades its word to LB_PREFIX (it still publishes LB_FAIL).  A
+//                             look-back adds aggregates until it meets a prefix, and segment 0's word is a prefix from the
+//                             start, so every look-back walks to segment 0: the sum of all aggregates in front, which IS the
+//                             prefix.  A word that stays an aggregate says nothing wrong; it only says less.
+//   MCRAW_INJECT_SLOWE        workgroups whose segment is 3 mod 8 sleep in front of their first look_put: 64 times s_sleep 127,
+//                             520192 clocks.  Their successors poll meanwhile.  SPIN7E polls are 2^20 times s_sleep 1 and a
+//                             load: above 2^26 clocks, 129 times the sleep, so no look-back gives up.  Only WHEN a word
+//                             appears changes; the kernel is right for any time.
+//   MCRAW_INJECT_LOSTE        in launches of an odd epoch, the workgroup that takes segment 3 of frame 0 returns behind its
+//                             ticket (and the ticket's reset): it publishes nothing and stores nothing -- where the frame has a
+//                             segment 4 to wait for it; a frame that ends with segment 3 would otherwise be left with no
+//                             failure recorded and no total.  SPIN7E is 2^12, as the legacy decoder's lost-word build has
+//                             SPIN6: every later segment of the frame gives up within its bound or meets the LB_FAIL of one
+//                             that has, the frame comes back with MCRAW_E_DEVICE and the launch ends.  Every wait keeps its
+//                             bound.  So that
+//                             LB_FAIL is also MET, not only published, the frame's segments from 8 on first poll segment
+//                             4's word until it says LB_FAIL -- it must give up, and they poll 2^16 times at most, bounded
+//                             as well -- and then find that failure or one behind it within their first window (without the
+//                             wait they add those words up and give up at segment 3 themselves: either is right).
+//   MCRAW_EPOCH0E=v           the epoch a context's encode state starts from.  Any value is a valid state: it is what the
+//                             counter holds after v batches, but for the workspace's words, and a fresh workspace holds zeros,
+//                             which no launch's epoch equals.  0xFFFFFFFD: the third batch of a context wraps to 1.
+#ifdef MCRAW_PATHSE
+// What the workgroups of the two kernels did, summed over the launches since the last reset (mcraw_diag_k7e_paths).  Both kernels
+// keep their counts in registers -- KE_ONE: thread 0 counts what is uniform over the workgroup or over wave 0, KE_LANE: every
+// lane counts its own -- and where the workgroup ends, every early return included, KE_FLUSH sums the lanes and thread 0 adds the
+// sums once.
+enum PathE {
+    // ---- k7e_payload
+    PE_LIVE, PE_IDLE,                   // workgroups whose ticket is a segment of the frame / lies behind it (seg >= F.nseg)
+    PE_HIT, PE_REFETCHED,               // live workgroups whose guess was their ticket / that fetched again behind it
+    PE_LOADS16, PE_LOADS_EDGE,          // loads of the segment encoded, per lane and tile round: 16 bytes / the clamp_par loop
+    PE_LOADS_CLAMPED_ROW,               // ... of a row below the frame (4 ty + r >= h)
+    PE_DEAD_TILES,                      // tiles behind the frame in live segments
+    PE_CLASS0,                          // blocks of the frame at each class 0..16 (17 counters)
+    PE_ROWS = PE_CLASS0 + 17,           // 8-byte payload rows stored (agg)
+    PE_REFS_CLAMPED,                    // refs records whose minimum is above the header's 12 bits (rmn > 4095)
+    PE_LOOKBACKS,                       // look-backs started (seg > 0)
+    PE_WINDOWS,                         // windows that a look-back took words from
+    PE_WORDS,                           // predecessor words added into acc
+    PE_POLLS,                           // polls of a window whose nearest word is not there
+    PE_GAVE_UP, PE_MET_FAIL,            // look-backs that ran out of polls / that met LB_FAIL
+    PE_NEVER,                           // hits of the bound check behind the look-back
+    // ---- k7e_side
+    PE_SIDE_BAD, PE_SIDE_FAIL, PE_SIDE_IDLE, // workgroups that return for F.bad || !F.nseg / for a failed look-back / for first >= R
+    PE_SIDE_CHUNKS,                     // workgroups that write records with chunk > 0 (records of their stream in front: pre)
+    PE_BITS_REC0,                       // records written in the bits stream at each header class 0..15
+    PE_REFS_REC0 = PE_BITS_REC0 + 16,   // ... in the refs stream
+    PE_HEADERS = PE_REFS_REC0 + 16,     // frame headers written
+    PE_N,
+    PE_SIDE0 = PE_SIDE_BAD              // (the first counter of k7e_side)
+};
+__device__ unsigned long long g_k7e_paths[PE_N];
+#define KE_ONE(slot, v)                                                                                                \
+    do {                                                                                                               \
+        if (tid == 0u)                                                                                                 \
+            pe_[slot] += static_cast<uint32_t>(v);                                                                     \
+    } while (0)
+#define KE_LANE(slot, v) (pe_[slot] += static_cast<uint32_t>(v))
+// (every thread of the workgroup is here: the returns it stands in front of are uniform)
+#define KE_FLUSH(LO, HI)                                                                                               \
+    do {                                                                                                               \
+        _Pragma("unroll") for (uint32_t i_ = LO; i_ < HI; i_++)                                                        \
+        {                                                                                                              \
+            const uint32_t v_ = wave_sum(pe_[i_]);                                                                     \
+            if (lane == 0u)                                                                                            \
+                s_pe[wave][i_ - LO] = v_;                                                                              \
+        }                                                                                                              \
+        __syncthreads();                                                                                               \
+        if (tid == 0u)                                                                                                 \
+            for (uint32_t i_ = 0; i_ < HI - LO; i_++) {                                                                \
+                uint32_t v_ = 0;                                                                                       \
+                for (uint32_t k_ = 0; k_ < EB_T / 64u; k_++)                                                           \
+                    v_ += s_pe[k_][i_];                                                                                \
+                if (v_)                                                                                                \
+                    atomicAdd(&g_k7e_paths[LO + i_], static_cast<unsigned long long>(v_));                             \
+            }                                                                                                          \
+    } while (0)
+#else
+#define KE_ONE(slot, v)
+#define KE_LANE(slot, v)
+#define KE_FLUSH(LO, HI)
+#endif
 
 // One frame of an encode batch as the kernels see it (uploaded per batch).
 struct EncF {
@@ -202,6 +297,10 @@ __global__ __launch_bounds__(EB_T) void k7e_payload(const EncWork W)
     __shared__ uint8_t s_nb[SEG_BLOCKS];
     __shared__ uint16_t s_ref[SEG_BLOCKS];
     __shared__ uint32_t s_wsum[EB_T / 64], s_ticket, s_base;
+#ifdef MCRAW_PATHSE
+    __shared__ uint32_t s_pe[EB_T / 64][PE_SIDE0];
+    uint32_t pe_[PE_N] = {};
+#endif
 
     const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
     const uint32_t f = blockIdx.x % W.n, guess = blockIdx.x / W.n;
@@ -224,10 +323,13 @@ __global__ __launch_bounds__(EB_T) void k7e_payload(const EncWork W)
             const uint32_t ty = t / F.tilesX, tx = t - ty * F.tilesX;
             const uint32_t y = clamp_par(4u * ty + r, h), x0 = 64u * tx + 8u * c;
             const uint16_t *row = F.in + static_cast<size_t>(y) * w;
+            KE_LANE(PE_LOADS_CLAMPED_ROW, 4u * ty + r >= h);
             if (x0 + 8u <= w) {
+                KE_LANE(PE_LOADS16, 1);
                 const u32x4_a2 a = *gptr<const u32x4_a2>(row + x0);
                 v[q] = make_uint4(a.x, a.y, a.z, a.w);
             } else { // the frame's right edge
+                KE_LANE(PE_LOADS_EDGE, 1);
                 uint32_t p[8];
 #pragma unroll
                 for (uint32_t k = 0; k < 8u; k++)
@@ -236,16 +338,40 @@ __global__ __launch_bounds__(EB_T) void k7e_payload(const EncWork W)
             }
         }
     };
+#ifndef MCRAW_FORCE_REFETCHE
     if (guess < F.nseg)
         fetch(guess);
+#endif
     __syncthreads();
     const uint32_t seg = s_ticket;
     if (seg == W.smax - 1u && tid == 0) // the frame's last ticket: its counter is back at zero for the next launch
         __hip_atomic_store(W.tickets + f * TICKET_STRIDE7E, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (seg >= F.nseg)
+    if (seg >= F.nseg) {
+        KE_ONE(PE_IDLE, 1);
+        KE_FLUSH(0, PE_LOADS16); // (what the lanes counted while they fetched the guess is of no segment)
         return;
+    }
+    KE_ONE(PE_LIVE, 1);
+#ifdef MCRAW_FORCE_REFETCHE
+    (void)guess;
+    KE_ONE(PE_REFETCHED, 1);
+    fetch(seg);
+#else
+    KE_ONE(PE_HIT, seg == guess);
+    KE_ONE(PE_REFETCHED, seg != guess);
+#ifdef MCRAW_PATHSE
+    if (seg != guess) // (the loads counted are those of the segment encoded)
+        pe_[PE_LOADS16] = pe_[PE_LOADS_EDGE] = pe_[PE_LOADS_CLAMPED_ROW] = 0u;
+#endif
     if (seg != guess)
         fetch(seg);
+#endif
+#ifdef MCRAW_INJECT_LOSTE
+    if ((W.epoch & 1u) && f == 0u && seg == 3u && F.nseg > 4u) {
+        KE_FLUSH(0, PE_LOADS16); // (it encodes no segment: its loads are not counted)
+        return;
+    }
+#endif
 
     // ---- per block: min / max across the 16 lanes that hold it (rows r and r + 2, columns 0..7), residuals -> LDS
 #pragma unroll
@@ -264,6 +390,7 @@ __global__ __launch_bounds__(EB_T) void k7e_payload(const EncWork W)
             mx = __builtin_elementwise_max(mx, as_u16x2(swz_xor(as_u32(mx), m)));
         }
         const uint32_t mb = 4u * tl + 2u * (r & 1u); // block of the even columns; +1: odd columns
+        KE_LANE(PE_DEAD_TILES, !live && (lane & 31u) == 0u);
         if (live) {
             const uint32_t mnw = as_u32(mn);
             const uint32_t d0 = as_u32(a0 - mn), d1 = as_u32(a1 - mn), d2 = as_u32(a2 - mn), d3 = as_u32(a3 - mn);
@@ -291,6 +418,11 @@ __global__ __launch_bounds__(EB_T) void k7e_payload(const EncWork W)
     const uint32_t m = tid;
     const uint32_t nbm = s_nb[m], refm = s_ref[m];
     const uint32_t lm = len7_of(nbm);
+#ifdef MCRAW_PATHSE
+#pragma unroll
+    for (uint32_t k = 0; k <= 16u; k++)
+        pe_[PE_CLASS0 + k] += seg * SEG_BLOCKS + m < 4u * F.ntiles && nbm == k;
+#endif
     uint32_t wtot;
     const uint32_t excl = wave_excl_scan(lm, lane, &wtot);
     if (lane == 0u)
@@ -304,6 +436,7 @@ __global__ __launch_bounds__(EB_T) void k7e_payload(const EncWork W)
         const uint32_t bmn = wave_min(nbm), bmx = wave_max(nbm), rmn = wave_min(refm), rmx = wave_max(refm);
         if (lane == 0u) {
             const uint32_t bref = bmn, rref = min(rmn, 4095u);
+            KE_LANE(PE_REFS_CLAMPED, rmn > 4095u);
             const uint32_t bhb = min(15u, 32u - __clz(bmx - bref)), rhb = min(15u, 32u - __clz(rmx - rref));
             const size_t rb = static_cast<size_t>(f) * 2u * W.rmax;
             W.rh[rb + rec] = static_cast<uint16_t>(bhb << 12 | bref);
@@ -325,11 +458,26 @@ __global__ __launch_bounds__(EB_T) void k7e_payload(const EncWork W)
     uint64_t *const look = W.look + static_cast<size_t>(f) * W.smax;
     const uint32_t agg = total >> 3; // every block length is a multiple of 8
     if (wave == 0u) {
+#ifdef MCRAW_INJECT_SLOWE
+        if (seg % 8u == 3u)
+            for (uint32_t k = 0; k < 64u; k++)
+                __builtin_amdgcn_s_sleep(127);
+#endif
         if (tid == 0)
             look_put(look + seg, W.epoch, (seg ? LB_AGG : LB_PREFIX) << 30 | agg);
         uint32_t acc = 0;
         bool failed = false;
+#ifdef MCRAW_INJECT_LOSTE
+        if ((W.epoch & 1u) && f == 0u && seg >= 8u && F.nseg > 4u) // (until segment 4 has given up, sixteen give-ups long at most)
+            for (uint32_t k = 0; k < 16u * SPIN7E; k++) {
+                uint32_t w4;
+                if (look_get(look + 4, W.epoch, &w4) && w4 >> 30 == LB_FAIL)
+                    break;
+                __builtin_amdgcn_s_sleep(1);
+            }
+#endif
         if (seg > 0u) {
+            KE_ONE(PE_LOOKBACKS, 1);
             int32_t i = static_cast<int32_t>(seg) - 1;
             uint32_t spins = 0;
             while (true) {
@@ -343,20 +491,30 @@ __global__ __launch_bounds__(EB_T) void k7e_payload(const EncWork W)
                 if (fst < fnr) { // a prefix (or a failure) with only aggregates in front of it
                     acc += wave_sum(lane <= fst ? val : 0u);
                     failed = __shfl(static_cast<int>(st), static_cast<int>(fst)) == static_cast<int>(LB_FAIL);
+                    KE_ONE(PE_WINDOWS, 1);
+                    KE_ONE(PE_WORDS, min(static_cast<int32_t>(fst), i) + 1); // (lanes in front of segment 0 hold no word)
+                    KE_ONE(PE_MET_FAIL, failed);
                     break;
                 }
                 if (fnr > 0u) {
                     acc += wave_sum(lane < fnr ? val : 0u);
                     i -= static_cast<int32_t>(fnr);
                     spins = 0;
+                    KE_ONE(PE_WINDOWS, 1);
+                    KE_ONE(PE_WORDS, fnr);
                 } else if (++spins > SPIN7E) {
                     failed = true;
+                    KE_ONE(PE_GAVE_UP, 1);
                     break;
                 } else {
+                    KE_ONE(PE_POLLS, 1);
                     __builtin_amdgcn_s_sleep(1);
                 }
             }
             if (tid == 0) {
+#ifdef MCRAW_FORCE_AGGONLYE
+                if (failed)
+#endif
                 look_put(look + seg, W.epoch, (failed ? LB_FAIL : LB_PREFIX) << 30 | ((acc + agg) & 0x3FFFFFFFu));
                 if (failed)
                     W.fail[f] = W.epoch;
@@ -364,6 +522,7 @@ __global__ __launch_bounds__(EB_T) void k7e_payload(const EncWork W)
         }
         if (!failed && 16u + 8ull * (acc + agg) + 2u * (4u + 130ull * F.R) > F.bound) { // (never: a look-back word is wrong)
             failed = true;
+            KE_ONE(PE_NEVER, 1);
             if (tid == 0)
                 W.fail[f] = W.epoch;
         }
@@ -375,8 +534,10 @@ __global__ __launch_bounds__(EB_T) void k7e_payload(const EncWork W)
     }
     __syncthreads();
     const uint32_t base = s_base;
-    if (base == 0xFFFFFFFFu)
+    if (base == 0xFFFFFFFFu) {
+        KE_FLUSH(0, PE_SIDE0);
         return;
+    }
 
     // ---- pack and store: task = 8-byte row q of the segment's payload (only rows that exist: 16 per block would leave most
     // lanes idle on natural frames), consecutive lanes -> consecutive bytes
@@ -386,6 +547,8 @@ __global__ __launch_bounds__(EB_T) void k7e_payload(const EncWork W)
         const uint32_t mb = s_row[q];
         st8(dst + 8u * q, pack_row7(s_nb[mb], q - (s_off[mb] >> 3), sv + mb * 8u));
     }
+    KE_ONE(PE_ROWS, agg);
+    KE_FLUSH(0, PE_SIDE0);
 }
 
 // ---------------------------------------------------------------------------------------------------- k7e_side
@@ -394,6 +557,10 @@ __global__ __launch_bounds__(EB_T) void k7e_side(const EncWork W)
 {
     __shared__ __attribute__((aligned(16))) uint4 s_v[EB_T * SIDE_STRIDE];
     __shared__ uint32_t s_red[3][EB_T / 64];
+#ifdef MCRAW_PATHSE
+    __shared__ uint32_t s_pe[EB_T / 64][PE_N - PE_SIDE0];
+    uint32_t pe_[PE_N] = {};
+#endif
 
     const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
     const uint32_t f = blockIdx.x % W.n, rest = blockIdx.x / W.n, s = rest % 2u, chunk = rest / 2u;
@@ -407,6 +574,8 @@ __global__ __launch_bounds__(EB_T) void k7e_side(const EncWork W)
             if (F.len_out)
                 *F.len_out = 0;
         }
+        KE_ONE(PE_SIDE_BAD, 1);
+        KE_FLUSH(PE_SIDE0, PE_N);
         return;
     }
     if (W.fail[f] == W.epoch) { // a look-back of this launch gave up
@@ -416,11 +585,17 @@ __global__ __launch_bounds__(EB_T) void k7e_side(const EncWork W)
             if (F.len_out)
                 *F.len_out = 0;
         }
+        KE_ONE(PE_SIDE_FAIL, 1);
+        KE_FLUSH(PE_SIDE0, PE_N);
         return;
     }
     const uint32_t first = chunk * SIDE_RECS;
-    if (first >= R)
+    if (first >= R) {
+        KE_ONE(PE_SIDE_IDLE, 1);
+        KE_FLUSH(PE_SIDE0, PE_N);
         return;
+    }
+    KE_ONE(PE_SIDE_CHUNKS, chunk > 0u);
     const uint16_t *const rh = W.rh + static_cast<size_t>(f) * 2u * W.rmax;
 
     // ---- lengths: my stream's records in front of my chunk; the bits stream's total (refs); the refs stream's total (head)
@@ -474,7 +649,16 @@ __global__ __launch_bounds__(EB_T) void k7e_side(const EncWork W)
         W.wst[f] = MCRAW_OK;
         if (F.len_out)
             *F.len_out = len;
+        KE_ONE(PE_HEADERS, 1);
     }
+#ifdef MCRAW_PATHSE
+#pragma unroll
+    for (uint32_t k = 0; k < 16u; k++) { // (the record every live lane writes below)
+        pe_[PE_BITS_REC0 + k] += live && s == 0u && hb == k;
+        pe_[PE_REFS_REC0 + k] += live && s == 1u && hb == k;
+    }
+#endif
+    KE_FLUSH(PE_SIDE0, PE_N); // (in front of the lanes' own return: the workgroup is whole here)
     if (!live)
         return;
 
@@ -520,7 +704,11 @@ __global__ __launch_bounds__(EB_T) void k7e_side(const EncWork W)
 // The encode arena of a context: grown on first use, grow-only; independent of every decode slot.
 struct EncState {
     Buf fr, look, tickets, bnb, bref, rh, tot, fail, wlen, wst; // HBM
+#ifdef MCRAW_EPOCH0E // test builds (above)
+    uint32_t epoch = MCRAW_EPOCH0E;
+#else
     uint32_t epoch = 0;
+#endif
     hipEvent_t done = nullptr; // behind the last batch's kernels (the next batch, on whatever stream, waits for it)
     std::vector<EncF> hfr;
     std::vector<uint64_t> hlen;
@@ -550,8 +738,10 @@ size_t enc_bound7(int width, int height)
 
 namespace {
 
-// Grow a zero-initialised workspace array (its old contents are not kept: the caller has waited for every earlier batch).
-int grow_zero(Buf &b, size_t bytes, bool *grew)
+// Grow a zero-initialised workspace array (its old contents are not kept: the caller has waited for every earlier batch).  The
+// zeros are written on the batch's own stream, in front of its kernels: a context's streams do not wait for the null stream,
+// and a hipMemset there may still be queued -- behind another thread's work -- when the kernels run.
+int grow_zero(Buf &b, size_t bytes, hipStream_t st, bool *grew)
 {
     if (bytes <= b.cap)
         return 0;
@@ -561,7 +751,7 @@ int grow_zero(Buf &b, size_t bytes, bool *grew)
     b.cap = 0;
     const size_t want = up(std::max<size_t>(bytes, 4096), 1 << 16);
     HIP_TRY(hipMalloc(&b.p, want));
-    HIP_TRY(hipMemset(b.p, 0, want));
+    HIP_TRY(hipMemsetAsync(b.p, 0, want, st));
     b.cap = want;
     *grew = true;
     return 0;
@@ -614,11 +804,11 @@ int encode_device(mcraw_ctx *c, const mcraw_enc_frame *frames, int n, hipStream_
         HIP_TRY(hipEventSynchronize(E.done));
     bool grew = false;
     int rc = 0;
-    if ((rc = grow_zero(E.fr, nn * sizeof(EncF), &grew)) || (rc = grow_zero(E.look, nn * smax * 8u, &grew)) ||
-        (rc = grow_zero(E.tickets, nn * TICKET_STRIDE7E * 4u, &grew)) || (rc = grow_zero(E.bnb, nn * rmax * 64u, &grew)) ||
-        (rc = grow_zero(E.bref, nn * rmax * 128u, &grew)) || (rc = grow_zero(E.rh, nn * 2u * rmax * 2u, &grew)) ||
-        (rc = grow_zero(E.tot, nn * 4u, &grew)) || (rc = grow_zero(E.fail, nn * 4u, &grew)) ||
-        (rc = grow_zero(E.wlen, nn * 8u, &grew)) || (rc = grow_zero(E.wst, nn * 4u, &grew)))
+    if ((rc = grow_zero(E.fr, nn * sizeof(EncF), st, &grew)) || (rc = grow_zero(E.look, nn * smax * 8u, st, &grew)) ||
+        (rc = grow_zero(E.tickets, nn * TICKET_STRIDE7E * 4u, st, &grew)) || (rc = grow_zero(E.bnb, nn * rmax * 64u, st, &grew)) ||
+        (rc = grow_zero(E.bref, nn * rmax * 128u, st, &grew)) || (rc = grow_zero(E.rh, nn * 2u * rmax * 2u, st, &grew)) ||
+        (rc = grow_zero(E.tot, nn * 4u, st, &grew)) || (rc = grow_zero(E.fail, nn * 4u, st, &grew)) ||
+        (rc = grow_zero(E.wlen, nn * 8u, st, &grew)) || (rc = grow_zero(E.wst, nn * 4u, st, &grew)))
         return rc;
     if (++E.epoch == 0u) // (a fresh look-back array holds zeros: epoch 0 never matches)
         E.epoch = 1u;
@@ -725,6 +915,24 @@ int encode_host(mcraw_ctx *c, const mcraw_enc_frame *frames, int n, size_t *writ
 } // namespace mcraw
 
 using namespace mcraw;
+
+#ifdef MCRAW_PATHSE
+// The census, in the order of PathE (up to n counters; returns how many there are); `reset`: and start it over.
+extern "C" int mcraw_diag_k7e_paths(uint64_t *out, int n, int reset)
+{
+    (void)hipDeviceSynchronize();
+    n = n < 0 ? 0 : n < static_cast<int>(PE_N) ? n : static_cast<int>(PE_N);
+    if (out && n)
+        (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_k7e_paths), sizeof(uint64_t) * static_cast<size_t>(n));
+    if (reset) {
+        void *p = nullptr;
+        (void)hipGetSymbolAddress(&p, HIP_SYMBOL(g_k7e_paths));
+        (void)hipMemset(p, 0, sizeof(g_k7e_paths));
+        (void)hipDeviceSynchronize(); // (the contexts' streams do not wait for the null stream)
+    }
+    return static_cast<int>(PE_N);
+}
+#endif
 
 extern "C" {
 

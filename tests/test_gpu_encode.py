@@ -11,6 +11,7 @@ import torch
 
 import _libs as L
 import motioncam_decoder_amd as M
+from _enc7_model import BIG65, BIG130, KINDS, SHAPES, classes_image, content, records_image  # noqa: F401  (the corpus lives with its model)
 
 pytestmark = pytest.mark.gpu
 
@@ -60,48 +61,6 @@ def check_equal(img, written, status, got, what=""):
     assert (got[written: written + 64] == 0xA5).all(), "bytes written behind the frame"
 
 
-def classes_image(w=256, h=64, seed=5):
-    """Blocks of every class 0..16: block m of the frame (tile order) gets the range 2^(m % 17) - 1 (0 for class 0)."""
-    rng = np.random.default_rng(seed)
-    img = np.zeros((h, w), dtype=np.uint16)
-    tiles_x = (w + 63) // 64
-    m = 0
-    for ty in range(h // 4):
-        for tx in range(tiles_x):
-            for b in range(4):
-                nb = m % 17
-                lo = int(rng.integers(0, 65536 - (1 << nb) + 1)) if nb < 16 else 0
-                span = (1 << nb) - 1
-                vals = lo + rng.integers(0, span + 1, size=64) if span else np.full(64, lo)
-                if span:
-                    vals[0], vals[1] = lo, lo + span
-                ys = 4 * ty + (b >> 1) + 2 * (np.arange(64) >> 5)
-                xs = 64 * tx + 2 * (np.arange(64) & 31) + (b & 1)
-                img[ys, xs] = vals.astype(np.uint16)
-                m += 1
-    return img
-
-
-SHAPES = [(1, 1), (2, 2), (3, 5), (63, 3), (64, 4), (65, 5), (127, 7), (200, 100)]
-
-
-def content(kind, w, h, seed):
-    if kind.startswith("nat"):
-        return L.natural_image_np(w, h, int(kind[3:]), 8.0, seed)
-    if kind.startswith("uni"):
-        return L.uniform_image_np(w, h, int(kind[3:]), seed)
-    if kind == "zero":
-        return np.zeros((h, w), dtype=np.uint16)
-    if kind == "max":
-        return np.full((h, w), 65535, dtype=np.uint16)
-    if kind == "highref":  # refs above 4095 (the side stream's 12-bit ref clamp) with small ranges
-        return (np.uint16(50000) + L.uniform_image_np(w, h, 6, seed)).astype(np.uint16)
-    raise ValueError(kind)
-
-
-KINDS = ["nat10", "nat12", "nat14", "uni8", "uni12", "uni16", "zero", "max", "highref"]
-
-
 @pytest.mark.parametrize("kind", KINDS)
 def test_bytes_equal_small_shapes(gpu_ctx, kind):
     imgs = [content(kind, w, h, 11 + i) for i, (w, h) in enumerate(SHAPES)]
@@ -126,6 +85,61 @@ def test_every_class_occurs(gpu_ctx):
     assert set(bits) == set(range(17)), sorted(set(bits))
     written, status, got, _, _ = encode_device(gpu_ctx, [img])
     check_equal(img, written[0], status[0], got[0], "classes")
+
+
+def test_every_record_class_occurs(gpu_ctx):
+    """28 side-stream records made for their header classes: refs records of every class 0..15 (with the 12-bit ref clamp at
+    4095, 4096, 50000 and 65535), bits records of every class 0..5 (tests/test_enc7_model.py checks that on the synthesiser)."""
+    img = records_image()
+    written, status, got, _, _ = encode_device(gpu_ctx, [img])
+    check_equal(img, written[0], status[0], got[0], "records")
+
+
+def test_segment_behind_the_first_window(gpu_ctx):
+    """1024 x 1028: 65 segments (one look-back of more than a window of 64) and 257 records (one in k7e_side's second chunk)."""
+    kind, w, h, seed = BIG65
+    img = content(kind, w, h, seed)
+    written, status, got, _, _ = encode_device(gpu_ctx, [img])
+    check_equal(img, written[0], status[0], got[0], "65 segments")
+
+
+def test_big_tiny_big_on_one_context():
+    """The workspace's strides (segments and records of the batch's largest frame) shrink and grow over stale contents."""
+    ctx = M.Context(0)
+    kind, w, h, seed = BIG130
+    big, tiny = content(kind, w, h, seed), content("zero", 1, 1, 0)
+    for img in (big, tiny, big):
+        written, status, got, _, _ = encode_device(ctx, [img])
+        check_equal(img, written[0], status[0], got[0], "big / tiny / big")
+    ctx.close()
+
+
+def test_fresh_workspace_is_zeroed_in_front_of_its_first_kernels():
+    """A context's first encode batch allocates its workspace and zeroes it.  The zeros must be written in order with the batch's
+    kernels, whatever the null stream is busy with: a context's streams do not wait for the null stream, and a hipMemset of
+    device memory returns before it has run (measured on an MI355X: back after 0.012 ms with the null stream busy for another
+    20.8 ms).  Zeroed there, the workspace of test_two_contexts_two_threads was cleared behind the other thread's fills, under
+    the running kernels: one frame of one run came back 33360 bytes short with status 0.  Here the null stream spins while a
+    fresh context encodes its first batch; a context that encoded another frame of the same shape at the same epoch was closed
+    just before, so memory handed out again would hold its look-back words, record headers and totals.  (The old code passed
+    this in its one run -- the allocator handed out other memory, and zeros that arrive behind the kernels do no harm; what
+    this pins is the condition, the order is in encode_device.)"""
+    kind, w, h, seed = BIG65
+    first, second = content("uni8", w, h, seed + 1), content(kind, w, h, seed)
+    ctx = M.Context(0)
+    written, status, got, _, _ = encode_device(ctx, [first])
+    check_equal(first, written[0], status[0], got[0], "first context")
+    ctx.close()
+    ctx = M.Context(0)
+    cap = M.encode_bound7(w, h)
+    ti, to = _dev(second), torch.full((cap + 64,), 0xA5, dtype=torch.uint8, device=DEV)
+    frames = M.Context.make_enc_frames([(ti.data_ptr(), w, h, to.data_ptr(), cap)])
+    torch.cuda.synchronize()
+    torch.cuda._sleep(20_000_000)  # (a few milliseconds on the null stream; the call returns at once)
+    written, status = ctx.encode_batch(frames)
+    torch.cuda.synchronize()
+    check_equal(second, written[0], status[0], to.cpu().numpy(), "second context")
+    ctx.close()
 
 
 def decode_bits(buf, nblk):
