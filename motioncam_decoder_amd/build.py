@@ -152,10 +152,21 @@ ENC7_PATH_VARIANTS = {
     "wrap": ["-DMCRAW_PATHSE", "-DMCRAW_EPOCH0E=0xFFFFFFFDu"],
 }
 
+# k7_tiles with every item, block, lean and store path counted and one forced (tests/test_gpu_k7t_paths.py; the switches and why
+# each is valid for every input: the head of csrc/mcraw_type7.hip).  Every name below occurs in mcraw_type7.hip alone -- the store
+# helpers of mcraw_dev.h count through a hook that only that source defines --, so a variant compiles that one source.
+K7T_PATH_VARIANTS = {
+    "census": ["-DMCRAW_PATHST"],
+    "nolean": ["-DMCRAW_PATHST", "-DMCRAW_FORCE_NOLEANT"],
+    "slowstore": ["-DMCRAW_PATHST", "-DMCRAW_FORCE_SLOWSTORET"],
+    "nomerge": ["-DMCRAW_PATHST", "-DMCRAW_FORCE_NOMERGET"],
+    "poison": ["-DMCRAW_PATHST", "-DMCRAW_POISON_PAYT"],
+}
+
 # The -D builds that tests/ links on the GPU box (tests/test_gpu_split.py, test_gpu_segw.py, test_gpu_lookback_fault.py,
-# test_gpu_k6_paths.py, test_gpu_k7_paths.py, test_gpu_enc7_paths.py).
+# test_gpu_k6_paths.py, test_gpu_k7_paths.py, test_gpu_enc7_paths.py, test_gpu_k7t_paths.py).
 TEST_VARIANTS = ((["-DMCRAW_FORCE_SEGW"], ["-DMCRAW_INJECT_MUTE7"], ["-DMCRAW_INJECT_LOST"]) + tuple(K6_PATH_VARIANTS.values())
-                 + tuple(K7_PATH_VARIANTS.values()) + tuple(ENC7_PATH_VARIANTS.values()))
+                 + tuple(K7_PATH_VARIANTS.values()) + tuple(ENC7_PATH_VARIANTS.values()) + tuple(K7T_PATH_VARIANTS.values()))
 
 
 def prebuild_test_variants():

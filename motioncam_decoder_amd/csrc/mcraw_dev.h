@@ -275,6 +275,20 @@ __device__ __forceinline__ void store_stream8(void *dst, mcraw_u32x2 v)
     asm volatile("global_store_dwordx2 %0, %1, off " MCRAW_STORE_POLICY ::"v"(dst), "v"(v) : "memory");
 }
 
+// The forms in which the helpers below store an 8-sample piece of a row.  A test build of a kernel may count them: it defines
+// MCRAW_STORE_PATH(form, cond) -- "the active lanes for which `cond` holds take `form`" -- in front of this header (the path census
+// of k7_tiles, csrc/mcraw_type7.hip).  Everywhere else the hook is empty.
+enum StorePath {
+    SP_ALIGNED,     // the whole piece on its natural grid (`quick`): vector stores, streaming where the instance has them
+    SP_UNALIGNED,   // the whole piece off that grid: unaligned vector stores (10- and 14-bit strips: bytes)
+    SP_CROPPED,     // the cropped end of a row: elements or bytes, the odd nibble and the masked last byte among them
+    SP_MERGED_FWD,  // post_store8_merged with the first bytes of the row's next piece
+    SP_MERGED_BACK, // post_store8_merged with the last bytes of the previous piece
+};
+#ifndef MCRAW_STORE_PATH
+#define MCRAW_STORE_PATH(form, cond)
+#endif
+
 // Bytes [0, nb) of the dwords o[] to dst, the last one masked by `last` (the cropped end of a strip row).
 __device__ __forceinline__ void post_store_bytes(uint8_t *dst, const uint32_t *o, uint32_t nb, uint32_t last, uint32_t maxb)
 {
@@ -309,6 +323,7 @@ __device__ __forceinline__ void post_store8(uint16_t *out, const Post &post, uin
             post_pack_be<(PB == 10 ? 10 : 14), true>(p, o);
         uint8_t *dst = reinterpret_cast<uint8_t *>(out) + static_cast<size_t>(y) * post_row_bytes(width, post.mode) + (x >> 3) * B;
         if (quick && n == 8u) {
+            MCRAW_STORE_PATH(SP_ALIGNED, true);
             typedef uint32_t u32x2_u __attribute__((ext_vector_type(2), aligned(2)));
             typedef uint32_t u32x3_u __attribute__((ext_vector_type(3), aligned(2)));
             if (PB == 10) {
@@ -321,6 +336,8 @@ __device__ __forceinline__ void post_store8(uint16_t *out, const Post &post, uin
                 *gptr<uint16_t>(dst + 12) = static_cast<uint16_t>(o[3]);
             }
         } else { // rows off the 2-byte grid, and the cropped end of a row (a last sample may end inside a byte)
+            MCRAW_STORE_PATH(SP_UNALIGNED, n == 8u);
+            MCRAW_STORE_PATH(SP_CROPPED, n != 8u);
             const uint32_t bitsn = n * B, nb = (bitsn + 7u) >> 3;
             post_store_bytes(dst, o, nb, (bitsn & 7u) ? (0xffu << (8u - (bitsn & 7u))) & 0xffu : 0xffu, 14u);
         }
@@ -334,6 +351,7 @@ __device__ __forceinline__ void post_store8(uint16_t *out, const Post &post, uin
             post_pack12(p, o);
         uint8_t *dst = reinterpret_cast<uint8_t *>(out) + static_cast<size_t>(y) * post_row_bytes(width, post.mode) + (x >> 3) * 12u;
         if (quick && n == 8u) {
+            MCRAW_STORE_PATH(SP_ALIGNED, true);
             typedef uint32_t u32x3 __attribute__((ext_vector_type(3), aligned(4)));
             const u32x3 v = {o[0], o[1], o[2]};
             if (NT)
@@ -341,10 +359,12 @@ __device__ __forceinline__ void post_store8(uint16_t *out, const Post &post, uin
             else
                 *gptr<u32x3>(dst) = v;
         } else if (n == 8u) { // a strip row off the dword grid: one unaligned 12-byte store
+            MCRAW_STORE_PATH(SP_UNALIGNED, true);
             typedef uint32_t u32x3_u __attribute__((ext_vector_type(3), aligned(1)));
             const u32x3_u v = {o[0], o[1], o[2]};
             *gptr<u32x3_u>(dst) = v;
         } else { // the cropped end of a row: bytes; an odd last sample owns the high nibble of its second byte
+            MCRAW_STORE_PATH(SP_CROPPED, true);
             const uint32_t nb = (n * 12u + 7u) >> 3;
 #pragma unroll
             for (uint32_t i = 0; i < 12u; i++)
@@ -359,6 +379,7 @@ __device__ __forceinline__ void post_store8(uint16_t *out, const Post &post, uin
     }
     uint16_t *dst = out + static_cast<size_t>(y) * width + x;
     if (quick && n == 8u) {
+        MCRAW_STORE_PATH(SP_ALIGNED, true);
         typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
         const u32x4 v = {p[0], p[1], p[2], p[3]};
         if (NT)
@@ -366,10 +387,12 @@ __device__ __forceinline__ void post_store8(uint16_t *out, const Post &post, uin
         else
             *gptr<u32x4>(dst) = v;
     } else if (n == 8u) { // rows off the 16-byte grid: one unaligned 16-byte store
+        MCRAW_STORE_PATH(SP_UNALIGNED, true);
         typedef uint32_t u32x4_u __attribute__((ext_vector_type(4), aligned(2)));
         const u32x4_u v = {p[0], p[1], p[2], p[3]};
         *gptr<u32x4_u>(dst) = v;
     } else {
+        MCRAW_STORE_PATH(SP_CROPPED, true);
 #pragma unroll
         for (uint32_t i = 0; i < 8u; i++)
             if (i < n)
@@ -432,6 +455,8 @@ __device__ __forceinline__ void float_store8(uint16_t *out, const Post &post, co
     if (!(post.mode & POST_PLANES)) {
         uint8_t *dst = base + (static_cast<size_t>(y) * width + x) * ES;
         if (n == 8u) {
+            MCRAW_STORE_PATH(SP_ALIGNED, quick);
+            MCRAW_STORE_PATH(SP_UNALIGNED, !quick);
 #pragma unroll
             for (uint32_t h = 0; h < ES / 2u; h++) { // 16-byte pieces
                 const mcraw_u32x4 w = {e[4 * h], e[4 * h + 1], e[4 * h + 2], e[4 * h + 3]};
@@ -446,6 +471,7 @@ __device__ __forceinline__ void float_store8(uint16_t *out, const Post &post, co
                 }
             }
         } else { // the cropped end of a row: element stores
+            MCRAW_STORE_PATH(SP_CROPPED, true);
 #pragma unroll
             for (uint32_t i = 0; i < 8u; i++)
                 if (i < n) {
@@ -462,6 +488,8 @@ __device__ __forceinline__ void float_store8(uint16_t *out, const Post &post, co
     uint8_t *const de = base + (static_cast<size_t>((post.plane4 >> sh) & 3u) * pstride + prow) * ES;
     uint8_t *const dodd = base + (static_cast<size_t>((post.plane4 >> (sh + 8u)) & 3u) * pstride + prow) * ES;
     if (n == 8u) {
+        MCRAW_STORE_PATH(SP_ALIGNED, quick);
+        MCRAW_STORE_PATH(SP_UNALIGNED, !quick);
         if (ES == 4u) {
             const mcraw_u32x4 we = {e[0], e[2], e[4], e[6]}, wo = {e[1], e[3], e[5], e[7]};
             if (quick && NT) {
@@ -493,6 +521,7 @@ __device__ __forceinline__ void float_store8(uint16_t *out, const Post &post, co
         }
         return;
     }
+    MCRAW_STORE_PATH(SP_CROPPED, true);
 #pragma unroll
     for (uint32_t i = 0; i < 8u; i++) // the cropped end of a row (n even: PLANES needs an even width)
         if (i < n) {
@@ -533,6 +562,8 @@ __device__ __forceinline__ void post_store8_merged(uint16_t *out, const Post &po
     uint8_t *dst = reinterpret_cast<uint8_t *>(out) + static_cast<size_t>(y) * post_row_bytes(width, post.mode) + (x >> 3) * B;
     typedef uint32_t u32x4_u __attribute__((ext_vector_type(4), aligned(2)));
     u32x4_u v;
+    MCRAW_STORE_PATH(SP_MERGED_FWD, has_next);
+    MCRAW_STORE_PATH(SP_MERGED_BACK, !has_next);
     if (PB == 10) {
         const uint32_t n0 = next(o[0]), n1 = next(o[1]), m1 = prev(o[1]), m2 = prev(o[2]);
         const u32x4_u fwd = {o[0], o[1], (o[2] & 0xffffu) | (n0 << 16), (n0 >> 16) | (n1 << 16)};                               // at dst

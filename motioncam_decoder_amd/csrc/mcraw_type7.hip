@@ -13,6 +13,76 @@
 #include <algorithm>
 #include <cstdlib>
 
+// Test builds of k7_tiles (tests/test_gpu_k7t_paths.py, build.K7T_PATH_VARIANTS; none of this is in the product library).  Every
+// thing k7_tiles does -- which items are valid, short or empty, how a span is staged, whether an item's strip stores are lean,
+// which of its store forms a row piece takes -- is decided by content and geometry, never by timing: the model of
+// tests/_tiles7_model.py predicts every counter below exactly.  The switches choose among ways that are right for EVERY input:
+//   MCRAW_PATHST              the path census below (mcraw_diag_k7t_paths).  The store helpers of mcraw_dev.h count through the
+//                             hook MCRAW_STORE_PATH, which is empty unless this file defines it in front of the header: the
+//                             header names no -D switch, so a variant compiles this one source (build.build_variant).
+//   MCRAW_FORCE_NOLEANT       I.lean is always 0.  Lean only SKIPS work that cannot change a sample (the saturating subtraction of
+//                             black levels that are off the references already, the clamp of samples that cannot reach 2^bits);
+//                             the general path does that work for any sample.
+//   MCRAW_FORCE_SLOWSTORET    I.fast is read as 0.  `fast` only says that the pieces sit on their natural grid; the unaligned
+//                             whole-piece stores and the element / byte stores are valid at any alignment the ABI accepts
+//                             (2 bytes, 4 for f32), and the merged 14-bit form declines when a lane is not `in`, which needs fast.
+//   MCRAW_FORCE_NOMERGET      the 14-bit merged form is never taken: it is an interior shortcut of post_store8<14>, which
+//                             stores any piece of any row by itself.
+//   MCRAW_POISON_PAYT         before a wave stages its span it fills its whole s_pay slice with a non-zero pattern, and the s_blk /
+//                             s_ref entries of lanes that hold no real block get one too.  unpack8<true> reads every term
+//                             branch-free: short and empty blocks read bytes the item never staged (the 32 bytes of slack behind
+//                             the span among them) and rely on zero field masks to drop them; entries of no real block belong to
+//                             tiles that item_decode skips.  What was in the LDS before must not matter: a pixel that changes
+//                             proves a dependence on unstaged LDS.
+#ifdef MCRAW_PATHST
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+namespace mcraw {
+// What the waves of k7_tiles did, summed over the launches since the last reset.  Events are counted per wave (one lane adds 1) or
+// per lane through a ballot (the first active lane adds the population count).
+enum PathT {
+    PT_WAVES,                                       // waves with item < total
+    PT_INVALID,                                     // ... whose group lies beyond their frame (a mixed size class), or whose frame failed
+    PT_SHORT,                                       // valid items with fewer than ITEM_BLOCKS real blocks
+    PT_TILES_SKIPPED,                               // tiles of valid items that lie beyond the frame (tile * 4 >= nblk)
+    PT_SPAN_EMPTY, PT_SPAN_FULL, PT_HEAD,           // valid items with n16 == 0 / n16 == PAY_CHUNKS / head != 0
+    PT_WG_REMAP, PT_WG_CHUNKED,                     // workgroups dealt by xcd_remap (xcd_chunk == 0) / by xcd_chunked
+    PT_CLS0, PT_CLS9 = PT_CLS0 + 9,                 // real blocks per storage class (cls7_of)
+    PT_PAIR_DIFF,                                   // sibling pairs (blocks 2r, 2r + 1 of a tile) whose classes differ
+    PT_WRAP_LANES,                                  // 8-sample lanes (per block) whose reference add passes 65535 in at least one sample
+    PT_LEAN, PT_NOTLEAN,                            // strip instances: valid items that are lean / are not
+    PT_FAIL_BITS, PT_FAIL_REF, PT_FAIL_TOP, PT_FAIL_WRAP, // ... with at least one real lane that fails b <= 10 / r >= bl /
+                                                    // r - bl + 2^sw - 1 <= 2^POST - 1 (as integers) / r + 2^sw - 1 <= 65535
+    PT_DROP_Y, PT_DROP_X,                           // 8-sample pieces of a row: dropped by y >= rows / by x >= width
+    PT_ST_ALIGNED, PT_ST_UNALIGNED, PT_ST_CROPPED,  // ... stored whole on the fast grid / whole off it / as the cropped end (mcraw_dev.h: StorePath)
+    PT_ST_MERGED_FWD, PT_ST_MERGED_BACK,            // ... stored by the merged 14-bit form, with the next piece's first bytes / the previous one's last
+    PT_DECL_PARTIAL, PT_DECL_NOTIN,                 // rounds of a wave that declined the merged form: not all 64 lanes there / a lane not `in`
+    PT_N
+};
+__device__ unsigned long long g_k7t_paths[PT_N];
+// the active lanes for which `cond` holds (all active lanes of the wave must call this together)
+__device__ __forceinline__ void k7t_count(uint32_t slot, bool cond)
+{
+    const unsigned long long m = __ballot(cond), act = __ballot(true);
+    if (m != 0ull && (threadIdx.x & 63u) == static_cast<uint32_t>(__builtin_ctzll(act)))
+        atomicAdd(&g_k7t_paths[slot], static_cast<unsigned long long>(__popcll(m)));
+}
+// one per wave (the lanes that are here) when `cond`, which is uniform over them, holds
+__device__ __forceinline__ void k7t_wave(uint32_t slot, bool cond)
+{
+    const unsigned long long act = __ballot(true);
+    if (cond && (threadIdx.x & 63u) == static_cast<uint32_t>(__builtin_ctzll(act)))
+        atomicAdd(&g_k7t_paths[slot], 1ull);
+}
+} // namespace mcraw
+#define MCRAW_STORE_PATH(form, cond) ::mcraw::k7t_count(::mcraw::PT_ST_ALIGNED + static_cast<uint32_t>(form), (cond))
+#define K7T_COUNT(slot, cond) k7t_count(slot, (cond))
+#define K7T_WAVE(slot, cond) k7t_wave(slot, (cond))
+#else
+#define K7T_COUNT(slot, cond)
+#define K7T_WAVE(slot, cond)
+#endif
+
 #include "mcraw_dev.h"
 
 #include "../../include/mcraw_hip.h"
@@ -1267,6 +1337,14 @@ __device__ __forceinline__ ItemS item_scalars(const Work7 &W, uint32_t item, uin
     I.meta = static_cast<size_t>(f) * W.Rmax * 64u + static_cast<size_t>(g) * ITEM_BLOCKS;
     I.lean = 0u;
     I.pstride = F->pstride;
+#ifdef MCRAW_FORCE_SLOWSTORET
+    I.fast = 0u;
+#endif
+    K7T_WAVE(PT_INVALID, !I.valid);
+    K7T_WAVE(PT_SHORT, I.valid && nblk - g * ITEM_BLOCKS < static_cast<uint32_t>(ITEM_BLOCKS));
+    K7T_WAVE(PT_SPAN_EMPTY, I.valid && I.n16 == 0u);
+    K7T_WAVE(PT_SPAN_FULL, I.valid && I.n16 == PAY_CHUNKS);
+    K7T_WAVE(PT_HEAD, I.valid && I.head != 0u);
     return I;
 }
 
@@ -1276,6 +1354,8 @@ template <bool NT = false, int POST = 0> // POST: 0 = the plain mosaic, else pos
 __device__ __forceinline__ void store_px8(const ItemS &I, const Post &post, uint32_t y, uint32_t x, uint32_t p[4])
 {
     const uint32_t width = static_cast<uint32_t>(I.width);
+    K7T_COUNT(PT_DROP_Y, y >= static_cast<uint32_t>(I.rows));
+    K7T_COUNT(PT_DROP_X, y < static_cast<uint32_t>(I.rows) && x >= width);
     if (y >= static_cast<uint32_t>(I.rows) || x >= width)
         return;
     if constexpr (POST >= PK_F32) { // normalised float rows or planes (mcraw_dev.h)
@@ -1287,6 +1367,7 @@ __device__ __forceinline__ void store_px8(const ItemS &I, const Post &post, uint
     }
     uint16_t *dst = I.out + static_cast<size_t>(y) * static_cast<size_t>(width) + x;
     if (I.fast && x + 8u <= width) {
+        K7T_COUNT(PT_ST_ALIGNED, true);
         typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
         const u32x4 v = {p[0], p[1], p[2], p[3]};
         if (NT)
@@ -1297,10 +1378,12 @@ __device__ __forceinline__ void store_px8(const ItemS &I, const Post &post, uint
         // a row that does not start on a 16-byte boundary (width % 8 != 0, or an odd output address):
         // still one 16-byte store -- global memory takes it at any 2-byte alignment -- instead of eight
         // 2-byte ones
+        K7T_COUNT(PT_ST_UNALIGNED, true);
         typedef uint32_t u32x4_u __attribute__((ext_vector_type(4), aligned(2)));
         const u32x4_u v = {p[0], p[1], p[2], p[3]};
         *gptr<u32x4_u>(dst) = v;
     } else { // the cropped end of a row: element stores
+        K7T_COUNT(PT_ST_CROPPED, true);
         const uint32_t n = width - x;
 #pragma unroll
         for (uint32_t i = 0; i < 8u; i++)
@@ -1324,6 +1407,10 @@ __device__ __forceinline__ void item_decode(const ItemS &I, const Post &post, ui
                                             const uint4 *s_tab)
 {
     const uint32_t tile = I.g * ITEM_TILES + tt;
+#ifdef MCRAW_PATHST
+    if (I.valid && tile * 4u >= I.nblk)
+        K7T_COUNT(PT_TILES_SKIPPED, (threadIdx.x & 15u) == 0u);
+#endif
     if (!I.valid || tile * 4u >= I.nblk) // uniform over the 16 lanes of a tile
         return;
     const bool whole = __ballot(true) == ~0ull; // (10- / 14-bit strips: the whole wave is here, lanes can fetch from each other)
@@ -1340,6 +1427,20 @@ __device__ __forceinline__ void item_decode(const ItemS &I, const Post &post, ui
         A = unpack8<true>(s_pay, mb.x & 0xffffu, mb.x >> 16, k, s_tab);
         B = unpack8<true>(s_pay, mb.y & 0xffffu, mb.y >> 16, k, s_tab);
     }
+#ifdef MCRAW_PATHST
+    {
+        K7T_COUNT(PT_PAIR_DIFF, k == 0u && (mb.x >> 16) != (mb.y >> 16));
+        const uint32_t ra = refs2 & 0xffffu, rb = refs2 >> 16;
+        bool wa = false, wb = false;
+#pragma unroll
+        for (int m = 0; m < 4; m++) {
+            wa = wa || (A.x[m] & 0xffffu) + ra > 65535u || (A.x[m] >> 16) + ra > 65535u;
+            wb = wb || (B.x[m] & 0xffffu) + rb > 65535u || (B.x[m] >> 16) + rb > 65535u;
+        }
+        K7T_COUNT(PT_WRAP_LANES, wa);
+        K7T_COUNT(PT_WRAP_LANES, wb);
+    }
+#endif
 
     // Bayer interleave (RawData.cpp:582-592): pixel 2i from block 2r, 2i+1 from 2r+1;
     // add both references with uint16 wrap-around in one packed add.
@@ -1373,6 +1474,7 @@ __device__ __forceinline__ void item_decode(const ItemS &I, const Post &post, ui
     }
     const uint32_t x = 64u * tx + 8u * (2u * (k & 3u) + (k >> 2));
     const uint32_t y = 4u * ty + r;
+#ifndef MCRAW_FORCE_NOMERGET
     if (POST == 14) { // (10-bit rows the same way -- 16-byte stores 10 bytes apart, six bytes written twice -- are 1.5 % SLOWER than 8 + 2)
         // the interior of the frame: one 16-byte store per lane and row (post_store8_merged).  The row's next 8 samples: lane
         // k + 4 for the first four lanes of a (tile, row pair) group, k - 3 for the next three, and the first lane of the next
@@ -1388,7 +1490,12 @@ __device__ __forceinline__ void item_decode(const ItemS &I, const Post &post, ui
             post_store8_merged<14>(I.out, post, width, y + 2u, x, p1, I.lean != 0u, src, has_next);
             return;
         }
+        K7T_WAVE(PT_DECL_PARTIAL, !whole);
+        K7T_WAVE(PT_DECL_NOTIN, whole);
     }
+#else
+    (void)whole;
+#endif
     store_px8<NT, POST>(I, post, y, x, p0);
     store_px8<NT, POST>(I, post, y + 2u, x, p1);
 }
@@ -1418,6 +1525,11 @@ __global__ __launch_bounds__(256) void k7_tiles(const Work7 W, uint32_t total, u
     I.n16 = 0;
     if (item < total)
         I = item_scalars(W, item, first_frame, class_groups);
+#ifdef MCRAW_PATHST
+    if (tid == 0u)
+        atomicAdd(&g_k7t_paths[W.xcd_chunk ? PT_WG_CHUNKED : PT_WG_REMAP], 1ull);
+    K7T_WAVE(PT_WAVES, item < total);
+#endif
 
     // span -> registers: 16-byte chunks lane, lane+64, ... (ITEM_SPAN + alignment head)
     constexpr uint32_t NV = (PAY_CHUNKS + 63u) / 64u;
@@ -1447,9 +1559,30 @@ __global__ __launch_bounds__(256) void k7_tiles(const Work7 W, uint32_t total, u
         // (r + 2^sw - 1 <= 65535: the reference add of the decode does not wrap either, RawData.cpp:581-593)
         const bool fits = !real || (b <= 10u && r >= bl && r - bl + ((1u << sw) - 1u) <= (1u << POST) - 1u && r + ((1u << sw) - 1u) <= 65535u);
         I.lean = __ballot(!fits) == 0ull ? 1u : 0u;
+#ifdef MCRAW_FORCE_NOLEANT
+        I.lean = 0u;
+#endif
+#ifdef MCRAW_PATHST
+        if (I.valid) { // (the four conditions one by one, as integers: which of them an item fails, whatever the others say)
+            const int32_t top = static_cast<int32_t>(r) - static_cast<int32_t>(bl) + static_cast<int32_t>((1u << sw) - 1u);
+            K7T_WAVE(PT_LEAN, I.lean != 0u);
+            K7T_WAVE(PT_NOTLEAN, I.lean == 0u);
+            K7T_WAVE(PT_FAIL_BITS, __ballot(real && b > 10u) != 0ull);
+            K7T_WAVE(PT_FAIL_REF, __ballot(real && r < bl) != 0ull);
+            K7T_WAVE(PT_FAIL_TOP, __ballot(real && top > static_cast<int32_t>((1u << POST) - 1u)) != 0ull);
+            K7T_WAVE(PT_FAIL_WRAP, __ballot(real && r + ((1u << sw) - 1u) > 65535u) != 0ull);
+        }
+#endif
         if (I.lean)
             r -= bl;
     }
+#ifdef MCRAW_PATHST
+    {
+        const bool realb = I.valid && lane < ITEM_BLOCKS && I.g * ITEM_BLOCKS + lane < I.nblk;
+        for (uint32_t c = 0; c < 10u; c++)
+            K7T_COUNT(PT_CLS0 + c, realb && cls7_of(b) == c);
+    }
+#endif
 
     uint32_t tot;
     const uint32_t ex = wave_excl_scan(lane < ITEM_BLOCKS ? len7_of(b) : 0u, lane, &tot);
@@ -1458,6 +1591,16 @@ __global__ __launch_bounds__(256) void k7_tiles(const Work7 W, uint32_t total, u
         s_ref[wave][lane] = static_cast<uint16_t>(r);
     }
     uint4 *pay4 = reinterpret_cast<uint4 *>(s_pay[wave]);
+#ifdef MCRAW_POISON_PAYT
+    // (the wave's own LDS operations are executed in order: the staging stores below land on top of the pattern)
+    static_assert(PAY_LDS % 16 == 0, "whole 16-byte pieces");
+    for (uint32_t i = lane; i < PAY_LDS / 16u; i += 64u)
+        pay4[i] = make_uint4(0xA5C3E1F7u, 0x5A3C1E7Fu, 0xFFFFFFFFu, 0x96696996u);
+    if (lane < ITEM_BLOCKS && !(I.valid && I.g * ITEM_BLOCKS + lane < I.nblk)) { // no real block: a raw-16 block in the pattern, a reference
+        s_blk[wave][lane] = 0x0F8u | (9u << 16);
+        s_ref[wave][lane] = 0xA5A5u;
+    }
+#endif
 #pragma unroll
     for (uint32_t c = 0; c < NV; c++)
         if (lane + 64u * c < I.n16)
@@ -1499,6 +1642,24 @@ extern "C" int mcraw_diag_k7_paths(uint64_t *out, int n, int reset)
         (void)hipDeviceSynchronize(); // (the contexts' streams do not wait for the null stream)
     }
     return static_cast<int>(P7_N);
+}
+#endif
+
+#ifdef MCRAW_PATHST
+// The census of k7_tiles, in the order of PathT (up to n counters; returns how many there are); `reset`: and start it over.
+extern "C" int mcraw_diag_k7t_paths(uint64_t *out, int n, int reset)
+{
+    (void)hipDeviceSynchronize();
+    n = n < 0 ? 0 : n < static_cast<int>(PT_N) ? n : static_cast<int>(PT_N);
+    if (out && n)
+        (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_k7t_paths), sizeof(uint64_t) * static_cast<size_t>(n));
+    if (reset) {
+        void *p = nullptr;
+        (void)hipGetSymbolAddress(&p, HIP_SYMBOL(g_k7t_paths));
+        (void)hipMemset(p, 0, sizeof(g_k7t_paths));
+        (void)hipDeviceSynchronize(); // (the contexts' streams do not wait for the null stream)
+    }
+    return static_cast<int>(PT_N);
 }
 #endif
 

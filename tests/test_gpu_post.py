@@ -152,7 +152,8 @@ def test_post_stage_large_batch_under_load(gpu_ctx, typ, bits, bright):
     registers are overwritten before it has read them wrote wrong 12-bit strips for the bench's 240-frame batch while every
     small-frame test passed.  `bright`: frames whose samples reach 4095 and whose references lie below the black levels in
     places, so that the items of one batch take both paths of the 12-bit stage (the lean one: no clamp, black levels off the
-    references; and the general one)."""
+    references; and the general one).  (That both are taken, and for which reason an item is not lean, is counted and held
+    against a model in tests/test_gpu_k7t_paths.py; here it is the content's promise.)"""
     dev = torch.device("cuda:0")
     w, h, n, distinct = 3840, 2160, (120 if typ == 7 else 32), 4
     black = [64, 60, 68, 72] if not bright else [300, 2, 1200, 40]
@@ -193,7 +194,9 @@ def test_14_bit_rows_one_store_per_lane_every_neighbour_case(gpu_ctx):
     frame's last tile column -- the last two bytes of the previous piece in front of its own.  Geometries that put every case
     on every position: one to nine tile columns (a pass holds four tiles: rows wrap inside passes), heights that end
     inside a tile row, widths off the 64 grid (their cropped tiles take the old path), natural content (lean items) and
-    noise with raw blocks (not lean), with and without black levels, dword-misaligned buffers."""
+    noise with raw blocks (not lean), with and without black levels, dword-misaligned buffers.  (Lean and not lean items, the
+    merged store forward and back and its two declines are counted per piece and compared with a model in
+    tests/test_gpu_k7t_paths.py.)"""
     rng = np.random.default_rng(77)
     items = []
     for w in (64, 128, 192, 256, 320, 448, 576, 200, 1000):
