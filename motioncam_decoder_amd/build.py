@@ -46,7 +46,7 @@ HIP_SOURCES = ("mcraw_abi.hip", "mcraw_submit.hip", "mcraw_tune.hip", "mcraw_dev
                "mcraw_fixpix.hip", "mcraw_denoise.hip", "mcraw_merge.hip", "mcraw_align.hip", "mcraw_area.hip", "mcraw_resample.hip")
 HIP_HEADERS = ("mcraw_plan.h", "mcraw_dev.h", "mcraw_host.h", "mcraw_race.h", "mcraw_mosaic.h", "mcraw_mosaic_args.h",
                "mcraw_rgb_args.h", "mcraw_align_args.h", "mcraw_area_args.h", "mcraw_rgb_dev.h", "mcraw_rgb_launch.h",
-               "mcraw_resample_args.h")
+               "mcraw_resample_args.h", "mcraw_rgb_paths.h")
 HIP_FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc"]
 
 
@@ -163,10 +163,24 @@ K7T_PATH_VARIANTS = {
     "poison": ["-DMCRAW_PATHST", "-DMCRAW_POISON_PAYT"],
 }
 
+# The demosaic kernels (krgb_mhc, krgb_bin2, krgb_bin2y, krgb_area, krgb_resample) with every path counted and the persistent loop
+# forced (tests/test_gpu_rgb_paths.py; the switches and why each is valid for every input: the head of csrc/mcraw_rgb.hip).  Every
+# name below occurs in mcraw_rgb.hip, mcraw_area.hip and mcraw_resample.hip alone -- the shared headers count, cap and poison
+# through hooks that only those sources define --, so a variant compiles those three sources.
+#   grid1  one workgroup walks every unit of every frame in order
+#   grid3  successive units of a workgroup skip columns, rows and frames
+RGB_PATH_VARIANTS = {
+    "census": ["-DMCRAW_PATHSR"],
+    "grid1": ["-DMCRAW_PATHSR", "-DMCRAW_RGB_GRID_CAP=1"],
+    "grid3": ["-DMCRAW_PATHSR", "-DMCRAW_RGB_GRID_CAP=3"],
+    "poison": ["-DMCRAW_PATHSR", "-DMCRAW_POISON_RGB"],
+    "poison1": ["-DMCRAW_PATHSR", "-DMCRAW_RGB_GRID_CAP=1", "-DMCRAW_POISON_RGB"],
+}
+
 # The -D builds that tests/ links on the GPU box (tests/test_gpu_split.py, test_gpu_segw.py, test_gpu_lookback_fault.py,
-# test_gpu_k6_paths.py, test_gpu_k7_paths.py, test_gpu_enc7_paths.py, test_gpu_k7t_paths.py).
+# test_gpu_k6_paths.py, test_gpu_k7_paths.py, test_gpu_enc7_paths.py, test_gpu_k7t_paths.py, test_gpu_rgb_paths.py).
 TEST_VARIANTS = ((["-DMCRAW_FORCE_SEGW"], ["-DMCRAW_INJECT_MUTE7"], ["-DMCRAW_INJECT_LOST"]) + tuple(K6_PATH_VARIANTS.values())
-                 + tuple(K7_PATH_VARIANTS.values()) + tuple(ENC7_PATH_VARIANTS.values()) + tuple(K7T_PATH_VARIANTS.values()))
+                 + tuple(K7_PATH_VARIANTS.values()) + tuple(ENC7_PATH_VARIANTS.values()) + tuple(K7T_PATH_VARIANTS.values()) + tuple(RGB_PATH_VARIANTS.values()))
 
 
 def prebuild_test_variants():

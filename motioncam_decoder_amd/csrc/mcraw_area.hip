@@ -4,6 +4,12 @@
 //
 //   karea_tab  the taps of every output column and row, into the caller's scratch, queued in front
 //   krgb_area  one instance per (output kind, CFA), as the siblings
+#ifdef MCRAW_PATHSR // (the test builds' three switches: the head of mcraw_rgb.hip)
+#include "mcraw_rgb_paths.h"
+#endif
+#ifdef MCRAW_RGB_GRID_CAP
+#define RGB_GRID_LIMIT(resident) (static_cast<void>(resident), static_cast<uint32_t>(MCRAW_RGB_GRID_CAP))
+#endif
 #include "mcraw_dev.h"
 #include "mcraw_host.h"
 #include "mcraw_rgb_args.h"
@@ -58,18 +64,26 @@ __global__ void __launch_bounds__(RGB_T) krgb_area(const RgbArgs A, const AreaGe
     __shared__ uint32_t s_y[AREA_YN];
     __shared__ __attribute__((aligned(16))) uint16_t s_lut[LUT ? DISP_LDS_MAX : 8u];
     uint32_t t = blockIdx.x;
+    RGB_WALK_DECL;
     if constexpr (LUT)
         stage_lut(A, s_lut);
     const uint32_t lx = 1u << G.lxl, lxid = threadIdx.x & (lx - 1u), lyid = threadIdx.x >> G.lxl;
     const bool lane_on = lyid < G.ly;
     do {
         const uint32_t f = LUT ? t / A.units : blockIdx.y, u = LUT ? t % A.units : blockIdx.x;
+        RGB_WALK(RF_AREA, f, LUT, A.lutg);
         const uint32_t tx = u % G.tilesX, band = u / G.tilesX;
         const uint32_t k0 = (tx * 8u) << G.lxl, xo = k0 + 8u * lxid;
         const uint32_t n = xo < A.Wo ? min(8u, A.Wo - xo) : 0u;
         const uint32_t qb = (G.qx0 + G.xt[k0].q0) & ~7u; // the segment's first quad column in the frame: on the 32-byte grid
         const uint16_t *in = A.in + static_cast<size_t>(f) * A.fstride;
         __syncthreads(); // the LUT is staged; the previous unit's LDS reads are done
+#ifdef MCRAW_POISON_RGB
+        rgb_poison(s_q, sizeof(s_q), 0x5a5a5a5bu);
+        rgb_poison(s_wx, sizeof(s_wx), 0x5a5a5a5bu);
+        rgb_poison(s_y, sizeof(s_y), 0x01000001u); // (one tap from quad row 1: a stale entry would still read inside the frame)
+        __syncthreads();
+#endif
         for (uint32_t e = threadIdx.x; e < ((8u * G.ntx) << G.lxl); e += RGB_T) {
             const uint32_t tp = e >> (3u + G.lxl), cc = e & (8u * lx - 1u), k = k0 + cc;
             s_wx[((tp * 8u + (cc & 7u)) << G.lxl) + (cc >> 3)] = k < A.Wo ? gptr<const uint16_t>(G.xt[k].w)[tp] : uint16_t{0};
@@ -100,6 +114,7 @@ __global__ void __launch_bounds__(RGB_T) krgb_area(const RgbArgs A, const AreaGe
             for (uint32_t a = 0; a < 2u; a++) {
                 const uint32_t j = 2u * (rp0 + lyid) + a;
                 const bool row_on = lane_on && n != 0u && j < A.Ho;
+                RGB_PATH(RP_IDLE_AREA, !row_on);
                 int acc[3][8] = {};
     #pragma unroll 1
                 for (uint32_t s = 0; s < G.nty; s++) {
@@ -108,6 +123,7 @@ __global__ void __launch_bounds__(RGB_T) krgb_area(const RgbArgs A, const AreaGe
                     for (uint32_t c = threadIdx.x; c < G.ly * G.nch; c += RGB_T) {
                         const uint32_t lyc = __umulhi(c, G.nchm), ch = c - lyc * G.nch;
                         const uint32_t yy = s_y[2u * lyc + a];
+                        RGB_PATH(RP_LD_AREA_SKIP, s >= (yy >> 24));
                         if (s >= (yy >> 24))
                             continue;
                         const uint32_t qy = G.qy0 + (yy & 0xffffffu) + s, aq = qb + 4u * ch;
@@ -115,11 +131,15 @@ __global__ void __launch_bounds__(RGB_T) krgb_area(const RgbArgs A, const AreaGe
                         const uint16_t *row1 = row0 + A.pitch;
                         uint32_t r0[4], r1[4];
                         if (G.mode == 2u && aq + 4u <= G.QW) {
+                            RGB_PATH(RP_LD_AREA_M2, true);
                             const mcraw_u32x4 v0 = *gptr<const mcraw_u32x4>(row0), v1 = *gptr<const mcraw_u32x4>(row1);
     #pragma unroll
                             for (int e = 0; e < 4; e++)
                                 r0[e] = v0[e], r1[e] = v1[e];
                         } else {
+                            RGB_PATH(RP_LD_AREA_M1, G.mode != 0u);
+                            RGB_PATH(RP_LD_AREA_M0, G.mode == 0u);
+                            RGB_PATH(RP_LD_AREA_TAIL, aq + 3u >= G.QW);
     #pragma unroll
                             for (uint32_t e = 0; e < 4u; e++) {
                                 r0[e] = r1[e] = 0u;
@@ -213,6 +233,10 @@ static int area_launch(mcraw_ctx *c, const mcraw_rgb *p, const mcraw_area *a, co
     HIP_TRY(hipGetLastError());
     return rgb_launch(c, rgb_pick<AreaK>(P.rgb), A, P.rgb, rgb_cols(p, colors, ncolors, 0.03125f), in, n, out, -1, st, G);
 }
+
+#ifdef MCRAW_PATHSR
+void rgb_paths_read_area(uint64_t *out, int n, int reset) { rgb_paths_read(out, n, reset); } // (mcraw_diag_rgb_paths: mcraw_rgb.hip)
+#endif
 
 } // namespace mcraw
 

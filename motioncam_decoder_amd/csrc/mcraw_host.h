@@ -18,6 +18,7 @@
 //   mcraw_resample.hip mcraw_demosaic_resample_batch (its checks, plan and taps, free of HIP: mcraw_resample_args.h)
 //   mcraw_rgb_dev.h      what the kernels of those three share: the kernel arguments, the colour stage, the stores, the LUT staging
 //   mcraw_rgb_launch.h   what their host sides share: the colours, the argument fill, the choice of an instance, the piece loop
+//   mcraw_rgb_paths.h    test builds only: the path census of those three (counters and the hooks' definitions)
 //   mcraw_mosaic.h       device helpers of those six mosaic stages: 8-sample loads and stores, packed-u16 and 24-bit arithmetic,
 //                        the exact rounding divide, the tile-plus-halo staging of the stencil stages
 //   mcraw_mosaic_args.h  one strided batch of mosaics and the checks on it (free of HIP): pointer, size, pitch, frame stride, the

@@ -18,6 +18,12 @@
 //           row store (the YUV kinds carry their 2x2 sums over the pair)
 // Every sum of taps is exact in two int32 accumulators: v = 256 vh + vl, A = sum w vh, B = sum w vl (the header's bounds),
 // 24-bit multiplies (|w| < 2^13, |vh| < 2^15).
+#ifdef MCRAW_PATHSR // (the test builds' three switches: the head of mcraw_rgb.hip)
+#include "mcraw_rgb_paths.h"
+#endif
+#ifdef MCRAW_RGB_GRID_CAP
+#define RGB_GRID_LIMIT(resident) (static_cast<void>(resident), static_cast<uint32_t>(MCRAW_RGB_GRID_CAP))
+#endif
 #include "mcraw_dev.h"
 #include "mcraw_host.h"
 #include "mcraw_rgb_args.h"
@@ -110,11 +116,13 @@ __global__ void __launch_bounds__(RGB_T) krgb_resample(const RgbArgs A, const Re
     __shared__ __attribute__((aligned(16))) ResampleTap s_xt[RES_TW];
     __shared__ __attribute__((aligned(16))) uint16_t s_lut[LUT ? DISP_LDS_MAX : 8u];
     uint32_t t = blockIdx.x;
+    RGB_WALK_DECL;
     if constexpr (LUT)
         stage_lut(A, s_lut);
     const int W = static_cast<int>(A.W), H = static_cast<int>(A.H);
     do {
         const uint32_t f = LUT ? t / A.units : blockIdx.y, u = LUT ? t % A.units : blockIdx.x;
+        RGB_WALK(RF_RES, f, LUT, A.lutg);
         const uint32_t tx = u % G.tilesX, band = u / G.tilesX;
         const uint32_t k0 = tx * RES_TW, k1 = min(k0 + RES_TW, A.Wo) - 1u;               // the tile's first and last column
         const uint32_t i0 = band * 2u * G.ly, i1 = min(i0 + 2u * G.ly, A.Ho) - 1u;        // ... and row
@@ -132,6 +140,13 @@ __global__ void __launch_bounds__(RGB_T) krgb_resample(const RgbArgs A, const Re
         const uint32_t np = min(static_cast<uint32_t>((rl - pb) >> 1) + 1u, RES_TROWS / 2u);
         const uint16_t *in = A.in + static_cast<size_t>(f) * A.fstride;
         __syncthreads(); // the LUT is staged; the previous tile's LDS reads are done
+#ifdef MCRAW_POISON_RGB
+        rgb_poison(s_raw, sizeof(s_raw), 0x5a5a5a5bu);
+        rgb_poison(s_e, sizeof(s_e), 0x5a5a5a5bu);
+        rgb_poison(s_t, sizeof(s_t), 0x5a5a5a5bu);
+        rgb_poison(s_xt, sizeof(s_xt), 0x5a5a5a5bu);
+        __syncthreads();
+#endif
         // raw rows pb - 2 .. pb + 2 np + 1, columns eb - 8 .. eb + 8 ne + 7
         const uint32_t nch = ne + 2u;
         for (uint32_t i = threadIdx.x; i < (2u * np + 4u) * nch; i += RGB_T) {
@@ -140,8 +155,10 @@ __global__ void __launch_bounds__(RGB_T) krgb_resample(const RgbArgs A, const Re
             const int xs = eb - 8 + 8 * static_cast<int>(q);
             mcraw_u32x4 v;
             if (A.invec && xs >= 0 && xs + 8 <= W) {
+                RGB_PATH(RP_LD_RES_VEC, true);
                 v = *gptr<const mcraw_u32x4>(row + xs);
             } else {
+                RGB_PATH(RP_LD_RES_ELEM, true);
                 uint32_t e[8];
 #pragma unroll
                 for (int k = 0; k < 8; k++)
@@ -200,6 +217,7 @@ __global__ void __launch_bounds__(RGB_T) krgb_resample(const RgbArgs A, const Re
         // C: (8 output columns, output row pair)
         const uint32_t lxid = threadIdx.x & 7u, lyid = threadIdx.x >> 3;
         const uint32_t xo = k0 + 8u * lxid;
+        RGB_PATH(RP_IDLE_RES, !(lyid < G.ly && xo < A.Wo && i0 + 2u * lyid <= i1));
         if (lyid < G.ly && xo < A.Wo && i0 + 2u * lyid <= i1) {
             const uint32_t n = min(8u, A.Wo - xo);
             const RgbCol &col = A.col[A.percol ? f : 0u];
@@ -271,6 +289,10 @@ static int resample_launch(mcraw_ctx *c, const mcraw_rgb *p, const mcraw_resampl
     HIP_TRY(hipGetLastError());
     return rgb_launch(c, rgb_pick<ResK>(P.rgb), A, P.rgb, rgb_cols(p, colors, ncolors, 0.0625f), in, n, out, -1, st, G);
 }
+
+#ifdef MCRAW_PATHSR
+void rgb_paths_read_resample(uint64_t *out, int n, int reset) { rgb_paths_read(out, n, reset); } // (mcraw_diag_rgb_paths: mcraw_rgb.hip)
+#endif
 
 } // namespace mcraw
 

@@ -19,6 +19,23 @@
 //
 // The scaled siblings (krgb_area: mcraw_area.hip, krgb_resample: mcraw_resample.hip) share the device side through
 // mcraw_rgb_dev.h and the host side of the launch through mcraw_rgb_launch.h.
+//
+// Test builds of the demosaic kernels (tests/test_gpu_rgb_paths.py, build.RGB_PATH_VARIANTS; none of this is in the product
+// library).  The three switches are read by this file, mcraw_area.hip and mcraw_resample.hip alone; the shared headers only have
+// hooks that are empty unless defined in front of them.  Each switch chooses among ways that are right for EVERY input:
+//   MCRAW_PATHSR            the path census (mcraw_rgb_paths.h; mcraw_diag_rgb_paths below adds up the three sources' counters).
+//   MCRAW_RGB_GRID_CAP=N    a persistent launch uses min(units x frames, N) workgroups, not min(units x frames, resident): the
+//                           loop's condition makes any grid of 1 .. units x frames workgroups walk every unit exactly once.  The
+//                           float kinds have no loop and are untouched.
+//   MCRAW_POISON_RGB        a workgroup fills every LDS array it stages per unit with a non-zero pattern at the start of every
+//                           unit, the first included, and syncs: a unit may read only what it staged itself, so a byte that
+//                           changes proves a dependence on stale LDS.  s_lut, staged once per workgroup, is left alone.
+#ifdef MCRAW_PATHSR
+#include "mcraw_rgb_paths.h"
+#endif
+#ifdef MCRAW_RGB_GRID_CAP
+#define RGB_GRID_LIMIT(resident) (static_cast<void>(resident), static_cast<uint32_t>(MCRAW_RGB_GRID_CAP))
+#endif
 #include "mcraw_dev.h"
 #include "mcraw_host.h"
 #include "mcraw_rgb_args.h"
@@ -43,12 +60,18 @@ __global__ void __launch_bounds__(RGB_T) krgb_mhc(const RgbArgs A)
     __shared__ __attribute__((aligned(16))) uint16_t s_t[MHC_LH * MHC_LW];
     __shared__ __attribute__((aligned(16))) uint16_t s_lut[DISP ? DISP_LDS_MAX : 8u];
     uint32_t t = blockIdx.x;
+    RGB_WALK_DECL;
     if constexpr (DISP)
         stage_lut(A, s_lut);
     do {
         if constexpr (DISP)
             __syncthreads(); // the LUT is staged; the previous tile's LDS reads are done
+#ifdef MCRAW_POISON_RGB
+        rgb_poison(s_t, sizeof(s_t), 0x5a5a5a5bu);
+        __syncthreads();
+#endif
         const uint32_t f = DISP ? t / A.units : blockIdx.y, u = DISP ? t % A.units : blockIdx.x;
+        RGB_WALK(RF_MHC, f, DISP, A.lutg);
         const uint32_t tx = u % A.tilesX, ty = u / A.tilesX;
         const int W = static_cast<int>(A.W), H = static_cast<int>(A.H);
         const int x0 = static_cast<int>(tx * MHC_TW), y0 = static_cast<int>(ty * MHC_TH);
@@ -59,8 +82,10 @@ __global__ void __launch_bounds__(RGB_T) krgb_mhc(const RgbArgs A)
             const int xs = x0 - 8 + 8 * static_cast<int>(q);
             mcraw_u32x4 v;
             if (A.invec && xs >= 0 && xs + 8 <= W) {
+                RGB_PATH(RP_LD_MHC_VEC, true);
                 v = *gptr<const mcraw_u32x4>(row + xs);
             } else {
+                RGB_PATH(RP_LD_MHC_ELEM, true);
                 uint32_t u[8];
     #pragma unroll
                 for (int e = 0; e < 8; e++)
@@ -72,6 +97,7 @@ __global__ void __launch_bounds__(RGB_T) krgb_mhc(const RgbArgs A)
         __syncthreads();
         const uint32_t lx = threadIdx.x & 31u, ly = threadIdx.x >> 5;
         const uint32_t x = static_cast<uint32_t>(x0) + 8u * lx;
+        RGB_PATH(RP_IDLE_MHC_LANE, x >= A.W);
         if (x >= A.W)
             continue;
         const uint32_t n = min(8u, A.W - x);
@@ -80,6 +106,7 @@ __global__ void __launch_bounds__(RGB_T) krgb_mhc(const RgbArgs A)
     #pragma unroll 1
         for (uint32_t pass = 0; pass < MHC_TH / 16u; pass++) {
             const uint32_t rp = ly + 8u * pass, y = static_cast<uint32_t>(y0) + 2u * rp;
+            RGB_PATH(RP_IDLE_MHC_ROWS, y >= A.H);
             if (y >= A.H)
                 break;
             // window: rows y-2 .. y+3, columns x-2 .. x+9, black subtracted: d[r][j] at image (y - 2 + r, x - 2 + j)
@@ -146,13 +173,16 @@ __global__ void __launch_bounds__(RGB_T) krgb_bin2(const RgbArgs A)
     constexpr bool DISP = is_disp(PK);
     __shared__ __attribute__((aligned(16))) uint16_t s_lut[DISP ? DISP_LDS_MAX : 8u];
     uint32_t t = blockIdx.x;
+    RGB_WALK_DECL;
     if constexpr (DISP) {
         stage_lut(A, s_lut);
         __syncthreads();
     }
     do {
         const uint32_t f = DISP ? t / A.units : blockIdx.y, item = (DISP ? t % A.units : blockIdx.x) * RGB_T + threadIdx.x;
+        RGB_WALK(RF_BIN2, f, DISP, A.lutg);
         const uint32_t yo = item / A.tilesX, xo = 8u * (item % A.tilesX);
+        RGB_PATH(RP_IDLE_BIN2, yo >= A.Ho);
         if (yo >= A.Ho)
             continue;
         const uint32_t n = min(8u, A.Wo - xo);
@@ -160,6 +190,7 @@ __global__ void __launch_bounds__(RGB_T) krgb_bin2(const RgbArgs A)
         const uint16_t *row1 = row0 + A.pitch;
         uint32_t u[2][8]; // (even column | odd column << 16) of quad i, rows 0 and 1
         if (A.invec && n == 8u) {
+            RGB_PATH(RP_LD_BIN2_VEC, true);
             const mcraw_u32x4 a0 = gptr<const mcraw_u32x4>(row0)[0], a1 = gptr<const mcraw_u32x4>(row0)[1];
             const mcraw_u32x4 b0 = gptr<const mcraw_u32x4>(row1)[0], b1 = gptr<const mcraw_u32x4>(row1)[1];
     #pragma unroll
@@ -170,6 +201,7 @@ __global__ void __launch_bounds__(RGB_T) krgb_bin2(const RgbArgs A)
                 u[1][4 + i] = b1[i];
             }
         } else {
+            RGB_PATH(RP_LD_BIN2_ELEM, true);
     #pragma unroll
             for (uint32_t i = 0; i < 8u; i++) {
                 const uint32_t k = i < n ? 2u * i : 0u;
@@ -206,11 +238,14 @@ __global__ void __launch_bounds__(RGB_T) krgb_bin2y(const RgbArgs A)
     constexpr uint32_t ROWS = 2u; // output rows per item
     __shared__ __attribute__((aligned(16))) uint16_t s_lut[DISP_LDS_MAX];
     uint32_t t = blockIdx.x;
+    RGB_WALK_DECL;
     stage_lut(A, s_lut);
     __syncthreads();
     do {
         const uint32_t f = t / A.units, item = (t % A.units) * RGB_T + threadIdx.x;
+        RGB_WALK(RF_BIN2Y, f, true, A.lutg);
         const uint32_t yo = item / A.tilesX * ROWS, xo = 8u * (item % A.tilesX);
+        RGB_PATH(RP_IDLE_BIN2, yo >= A.Ho);
         if (yo >= A.Ho)
             continue;
         const uint32_t n = min(8u, A.Wo - xo);
@@ -221,6 +256,7 @@ __global__ void __launch_bounds__(RGB_T) krgb_bin2y(const RgbArgs A)
             const uint16_t *row1 = row0 + A.pitch;
             uint32_t u[2][8]; // (even column | odd column << 16) of quad i, rows 0 and 1
             if (A.invec && n == 8u) {
+                RGB_PATH(RP_LD_BIN2Y_VEC, true);
                 const mcraw_u32x4 a0 = gptr<const mcraw_u32x4>(row0)[0], a1 = gptr<const mcraw_u32x4>(row0)[1];
                 const mcraw_u32x4 b0 = gptr<const mcraw_u32x4>(row1)[0], b1 = gptr<const mcraw_u32x4>(row1)[1];
     #pragma unroll
@@ -231,6 +267,7 @@ __global__ void __launch_bounds__(RGB_T) krgb_bin2y(const RgbArgs A)
                     u[1][4 + i] = b1[i];
                 }
             } else {
+                RGB_PATH(RP_LD_BIN2Y_ELEM, true);
     #pragma unroll
                 for (uint32_t i = 0; i < 8u; i++) {
                     const uint32_t k = i < n ? 2u * i : 0u;
@@ -297,11 +334,35 @@ static int demosaic_launch(const char *fn, mcraw_ctx *c, const mcraw_rgb *p, con
                       out, P.mhc ? MCRAW_KRGB_MHC : MCRAW_KRGB_BIN2, stream_of(c, stream));
 }
 
+#ifdef MCRAW_PATHSR
+void rgb_paths_read_rgb(uint64_t *out, int n, int reset) { rgb_paths_read(out, n, reset); }
+void rgb_paths_read_area(uint64_t *out, int n, int reset);     // mcraw_area.hip
+void rgb_paths_read_resample(uint64_t *out, int n, int reset); // mcraw_resample.hip
+#endif
+
 } // namespace mcraw
 
 using namespace mcraw;
 
 extern "C" {
+
+#ifdef MCRAW_PATHSR
+// The census of the demosaic kernels, in the order of RgbPath, summed over the three sources (up to n counters; returns how many
+// there are); `reset`: and start it over.
+int mcraw_diag_rgb_paths(uint64_t *out, int n, int reset)
+{
+    n = n < 0 ? 0 : n < static_cast<int>(RP_N) ? n : static_cast<int>(RP_N);
+    for (int i = 0; out && i < n; i++)
+        out[i] = 0u;
+    if (out || reset) {
+        uint64_t none[RP_N];
+        rgb_paths_read_rgb(out ? out : none, out ? n : 0, reset);
+        rgb_paths_read_area(out ? out : none, out ? n : 0, reset);
+        rgb_paths_read_resample(out ? out : none, out ? n : 0, reset);
+    }
+    return static_cast<int>(RP_N);
+}
+#endif
 
 int mcraw_demosaic_batch(mcraw_ctx *c, const mcraw_rgb *p, const mcraw_rgb_color *colors, int ncolors, const uint16_t *in,
                          size_t in_pitch, size_t in_frame_stride, int width, int height, int n, void *out, size_t out_bytes,

@@ -8,6 +8,18 @@
 #include "mcraw_host.h"
 #include "mcraw_rgb_args.h"
 
+// The hooks of the path census (csrc/mcraw_rgb_paths.h; tests/test_gpu_rgb_paths.py): empty unless a source defines them in front
+// of this header, so that this header names no switch of a test build.
+//   RGB_PATH(slot, cond)            the active lanes for which `cond` holds take path `slot`
+//   RGB_PATH_YUV(slot, dst, n, es)  8 samples of a YUV row at dst: the form yuv_store8 takes
+//   RGB_WALK_DECL, RGB_WALK(family, f, lut, lutg)   a workgroup takes a unit of frame f
+#ifndef RGB_PATH
+#define RGB_PATH(slot, cond)
+#define RGB_PATH_YUV(slot, dst, n, es)
+#define RGB_WALK_DECL
+#define RGB_WALK(family, f, lut, lutg)
+#endif
+
 namespace mcraw {
 
 static_assert(rgb_float_kind(MCRAW_FLOAT_F32) == PK_F32 && rgb_float_kind(MCRAW_FLOAT_F16) == PK_F16 &&
@@ -123,6 +135,7 @@ __device__ __forceinline__ void rgb_store8(const RgbArgs &A, const RgbCol &col, 
             // f16 / bf16: 16 bytes per lane, whole lines per instruction: streaming stores.  f32: each instruction covers half
             // of every 32-byte lane piece; streamed, those half lines reach HBM on their own (6x slower, measured): plain
             // stores, which L2 merges.
+            RGB_PATH(RP_ST_F_FAST, true);
 #pragma unroll
             for (uint32_t h = 0; h < ES / 2u; h++) {
                 const mcraw_u32x4 w = {e[4 * h], e[4 * h + 1], e[4 * h + 2], e[4 * h + 3]};
@@ -132,6 +145,8 @@ __device__ __forceinline__ void rgb_store8(const RgbArgs &A, const RgbCol &col, 
                     *gptr<mcraw_u32x4>(dst + 16u * h) = w;
             }
         } else { // a cropped row end, or a row off the 16-byte grid
+            RGB_PATH(RP_ST_F_CROP, n != 8u);
+            RGB_PATH(RP_ST_F_OFF, n == 8u);
 #pragma unroll
             for (uint32_t i = 0; i < 8u; i++)
                 if (i < n) {
@@ -207,13 +222,16 @@ __device__ __forceinline__ void disp_store8(const RgbArgs &A, const RgbCol &col,
                 w[j >> 2] |= q[j % 3][j / 3] << (8 * (j & 3));
             if (full && (a & 7u) == 0u) {
                 if ((a & 8u) == 0u) {
+                    RGB_PATH(RP_ST_H8_16_8, true);
                     *gptr<mcraw_u32x4>(dst) = mcraw_u32x4{w[0], w[1], w[2], w[3]};
                     *gptr<mcraw_u32x2>(dst + 16) = mcraw_u32x2{w[4], w[5]};
                 } else {
+                    RGB_PATH(RP_ST_H8_8_16, true);
                     *gptr<mcraw_u32x2>(dst) = mcraw_u32x2{w[0], w[1]};
                     *gptr<mcraw_u32x4>(dst + 8) = mcraw_u32x4{w[2], w[3], w[4], w[5]};
                 }
             } else {
+                RGB_PATH(RP_ST_H8_ELEM, true);
 #pragma unroll
                 for (uint32_t i = 0; i < 8u; i++)
                     if (i < n) {
@@ -228,10 +246,12 @@ __device__ __forceinline__ void disp_store8(const RgbArgs &A, const RgbCol &col,
             for (int k = 0; k < 12; k++)
                 w[k] = q[(2 * k) % 3][(2 * k) / 3] | (q[(2 * k + 1) % 3][(2 * k + 1) / 3] << 16);
             if (full && (a & 15u) == 0u) {
+                RGB_PATH(RP_ST_H16_FAST, true);
 #pragma unroll
                 for (int h = 0; h < 3; h++)
                     *gptr<mcraw_u32x4>(dst + 16 * h) = mcraw_u32x4{w[4 * h], w[4 * h + 1], w[4 * h + 2], w[4 * h + 3]};
             } else {
+                RGB_PATH(RP_ST_H16_ELEM, true);
 #pragma unroll
                 for (uint32_t i = 0; i < 8u; i++)
                     if (i < n) {
@@ -252,8 +272,11 @@ __device__ __forceinline__ void disp_store8(const RgbArgs &A, const RgbCol &col,
             const uint32_t w0 = q[r][0] | (q[r][1] << 8) | (q[r][2] << 16) | (q[r][3] << 24);
             const uint32_t w1 = q[r][4] | (q[r][5] << 8) | (q[r][6] << 16) | (q[r][7] << 24);
             if (full && (a & 7u) == 0u) {
+                RGB_PATH(RP_ST_C8_FAST, true);
                 *gptr<mcraw_u32x2>(dst) = mcraw_u32x2{w0, w1};
             } else {
+                RGB_PATH(RP_ST_C8_CROP, !full);
+                RGB_PATH(RP_ST_C8_OFF, full);
 #pragma unroll
                 for (uint32_t i = 0; i < 8u; i++)
                     if (i < n)
@@ -261,9 +284,12 @@ __device__ __forceinline__ void disp_store8(const RgbArgs &A, const RgbCol &col,
             }
         } else {
             if (full && (a & 15u) == 0u) {
+                RGB_PATH(RP_ST_C16_FAST, true);
                 *gptr<mcraw_u32x4>(dst) = mcraw_u32x4{q[r][0] | (q[r][1] << 16), q[r][2] | (q[r][3] << 16),
                                                       q[r][4] | (q[r][5] << 16), q[r][6] | (q[r][7] << 16)};
             } else {
+                RGB_PATH(RP_ST_C16_CROP, !full);
+                RGB_PATH(RP_ST_C16_OFF, full);
 #pragma unroll
                 for (uint32_t i = 0; i < 8u; i++)
                     if (i < n)
@@ -328,6 +354,7 @@ __device__ __forceinline__ void yuv_row8(const RgbArgs &A, const RgbCol &col, co
         const int s = __mul24(A.ycf[0], P[0][i]) + __mul24(A.ycf[1], P[1][i]) + __mul24(A.ycf[2], P[2][i]) + rnd;
         v[i] = static_cast<uint32_t>(min(max((s >> A.ysh) + A.yoff, 0), TOP)) << SHL;
     }
+    RGB_PATH_YUV(RP_ST_YL_FAST, frame_out + (static_cast<size_t>(y) * A.Wo + x) * ES, n, ES);
     yuv_store8<ES>(frame_out + (static_cast<size_t>(y) * A.Wo + x) * ES, n, v);
 #pragma unroll
     for (int c = 0; c < 3; c++)
@@ -344,7 +371,15 @@ __device__ __forceinline__ void yuv_row8(const RgbArgs &A, const RgbCol &col, co
                           4 * rnd;
             v[2 * k + r - 1] = static_cast<uint32_t>(min(max((s >> (A.ysh + 2u)) + A.coff, 0), TOP)) << SHL;
         }
+    RGB_PATH_YUV(RP_ST_YC_FAST, frame_out + ((static_cast<size_t>(A.Ho) + (y >> 1)) * A.Wo + x) * ES, n, ES);
     yuv_store8<ES>(frame_out + ((static_cast<size_t>(A.Ho) + (y >> 1)) * A.Wo + x) * ES, n, v);
+}
+
+// (test builds of the kernels) The workgroup fills an LDS array with `pattern`; the caller syncs.
+__device__ __forceinline__ void rgb_poison(void *a, uint32_t bytes, uint32_t pattern)
+{
+    for (uint32_t i = threadIdx.x; i < bytes / 4u; i += RGB_T)
+        static_cast<uint32_t *>(a)[i] = pattern;
 }
 
 // A display kernel's workgroup stages an LDS-sized LUT once, before its first tile (the caller syncs).

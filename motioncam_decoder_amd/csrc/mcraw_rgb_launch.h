@@ -9,6 +9,13 @@
 #include "mcraw_rgb_args.h"
 #include "mcraw_rgb_dev.h"
 
+// The hook of the test builds that force a persistent grid's size (tests/test_gpu_rgb_paths.py): what the device holds at once,
+// unless a source defines another limit in front of this header.  Any grid from 1 to units x frames workgroups walks every unit
+// exactly once (the kernels' loop condition), so every limit >= 1 is valid for every input.
+#ifndef RGB_GRID_LIMIT
+#define RGB_GRID_LIMIT(resident) (resident)
+#endif
+
 namespace mcraw {
 
 // k[c] = (gain[c] * inv) * scale per colour, `scale` undoing the weight of the kernel's integer estimates.
@@ -122,7 +129,7 @@ int rgb_launch(mcraw_ctx *c, Kernel k, RgbArgs A, const RgbPlan &P, const std::v
         A.nf = static_cast<uint32_t>(nf);
         for (int i = 0; i < (A.percol ? nf : 1); i++)
             A.col[i] = cols[static_cast<size_t>(A.percol ? f0 + i : 0)];
-        const dim3 grid = persistent ? dim3(static_cast<uint32_t>(std::min<uint64_t>(static_cast<uint64_t>(A.units) * nf, resident)))
+        const dim3 grid = persistent ? dim3(static_cast<uint32_t>(std::min<uint64_t>(static_cast<uint64_t>(A.units) * nf, RGB_GRID_LIMIT(resident))))
                                      : dim3(A.units, static_cast<uint32_t>(nf));
         std::optional<KTimer> kt;
         if (kid >= 0)

@@ -1,0 +1,106 @@
+// mcraw_rgb_paths.h -- the path census of the demosaic kernels (krgb_mhc, krgb_bin2, krgb_bin2y: csrc/mcraw_rgb.hip; krgb_area:
+// csrc/mcraw_area.hip; krgb_resample: csrc/mcraw_resample.hip), for test builds only (tests/test_gpu_rgb_paths.py,
+// build.RGB_PATH_VARIANTS).  A source that wants the census includes this header IN FRONT of mcraw_rgb_dev.h and mcraw_rgb_launch.h,
+// under a -D switch of its own: the hooks of those headers (RGB_PATH, RGB_PATH_YUV, RGB_WALK, RGB_WALK_DECL) are empty unless
+// defined, as MCRAW_STORE_PATH is in mcraw_dev.h, and this header names no switch, so a variant compiles the three sources alone.
+// The library is linked without relocatable device code: every source has a counter array of its own (g_rgb_paths, internal
+// linkage), and rgb_paths_read of each adds its counters to the caller's.
+//
+// Every counter is fixed by geometry, by the alignment of the caller's buffers and by the grid size: tests/_rgb_paths_model.py
+// predicts each one exactly.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace mcraw {
+
+enum RgbFamily { RF_MHC, RF_BIN2, RF_BIN2Y, RF_AREA, RF_RES, RF_N };
+
+enum RgbPath {
+    // per family (RP_WALK + 4 * family + ..): workgroups launched; units taken as a workgroup's first / as a later one; later units
+    // whose frame differs from the workgroup's previous unit
+    RP_WALK,
+    RP_WG = 0, RP_FIRST, RP_LATER, RP_CROSS,
+    RP_WALK_END = RP_WALK + 4 * RF_N,
+    // units with the LUT in LDS / read from global memory (the kinds with a LUT)
+    RP_LUT_LDS = RP_WALK_END, RP_LUT_GLOBAL,
+    // idle work: MHC lanes past W; MHC lanes that leave a tile's passes at a row pair past H; BIN2 / bin2y items past Ho; area
+    // lanes with !row_on, per group and row; resample phase-C lanes outside the tile
+    RP_IDLE_MHC_LANE, RP_IDLE_MHC_ROWS, RP_IDLE_BIN2, RP_IDLE_AREA, RP_IDLE_RES,
+    // loads: 16-byte staging pieces of MHC and resample, as one vector load / as 8 reflected elements; BIN2 and bin2y item rows
+    // (bin2y: two per item) as vectors / as elements
+    RP_LD_MHC_VEC, RP_LD_MHC_ELEM, RP_LD_RES_VEC, RP_LD_RES_ELEM, RP_LD_BIN2_VEC, RP_LD_BIN2_ELEM, RP_LD_BIN2Y_VEC, RP_LD_BIN2Y_ELEM,
+    // krgb_area's pieces of 4 quads: two 16-byte loads / dwords / uint16 pairs; the dword and uint16 pieces with a zero-filled tail
+    // (aq + 3 >= QW); pieces skipped by s >= nt
+    RP_LD_AREA_M2, RP_LD_AREA_M1, RP_LD_AREA_M0, RP_LD_AREA_TAIL, RP_LD_AREA_SKIP,
+    // stores, per 8-sample row piece and plane: whole on the grid / the cropped row end (n < 8) / whole off the grid
+    RP_ST_F_FAST, RP_ST_F_CROP, RP_ST_F_OFF,          // the float kinds
+    RP_ST_C8_FAST, RP_ST_C8_CROP, RP_ST_C8_OFF,       // display CHW uint8
+    RP_ST_C16_FAST, RP_ST_C16_CROP, RP_ST_C16_OFF,    // display CHW uint16
+    RP_ST_H8_16_8, RP_ST_H8_8_16, RP_ST_H8_ELEM,      // display HWC uint8 (per piece): 16 + 8 bytes / 8 + 16 / elements
+    RP_ST_H16_FAST, RP_ST_H16_ELEM,                   // display HWC uint16 (per piece): 3 x 16 bytes / elements
+    RP_ST_YL_FAST, RP_ST_YL_CROP, RP_ST_YL_OFF,       // YUV luma rows
+    RP_ST_YC_FAST, RP_ST_YC_CROP, RP_ST_YC_OFF,       // YUV chroma rows
+    RP_N
+};
+
+static __device__ unsigned long long g_rgb_paths[RP_N];
+
+// the active lanes for which `cond` holds (all active lanes of the wave call this together)
+__device__ __forceinline__ void rgb_path(uint32_t slot, bool cond)
+{
+    const unsigned long long m = __ballot(cond), act = __ballot(true);
+    if (m != 0ull && (threadIdx.x & 63u) == static_cast<uint32_t>(__builtin_ctzll(act)))
+        atomicAdd(&g_rgb_paths[slot], static_cast<unsigned long long>(__popcll(m)));
+}
+
+// 8 samples of a YUV row at dst: slot (whole, on the grid of 8 es bytes), slot + 1 (n < 8), slot + 2 (whole, off the grid)
+__device__ __forceinline__ void rgb_path_yuv(uint32_t slot, const void *dst, uint32_t n, uint32_t es)
+{
+    const bool on = (reinterpret_cast<uintptr_t>(dst) & (8u * es - 1u)) == 0u;
+    rgb_path(slot, n == 8u && on);
+    rgb_path(slot + 1u, n != 8u);
+    rgb_path(slot + 2u, n == 8u && !on);
+}
+
+// A workgroup takes a unit of frame f (every thread calls this at the top of the unit; prev: ~0 in front of the first).
+__device__ __forceinline__ void rgb_walk(uint32_t family, uint32_t f, bool lut, bool lutg, uint32_t &prev)
+{
+    if (threadIdx.x == 0u) {
+        unsigned long long *w = &g_rgb_paths[RP_WALK + 4u * family];
+        if (prev == 0xffffffffu) {
+            atomicAdd(&w[RP_WG], 1ull);
+            atomicAdd(&w[RP_FIRST], 1ull);
+        } else {
+            atomicAdd(&w[RP_LATER], 1ull);
+            if (prev != f)
+                atomicAdd(&w[RP_CROSS], 1ull);
+        }
+        if (lut)
+            atomicAdd(&g_rgb_paths[lutg ? RP_LUT_GLOBAL : RP_LUT_LDS], 1ull);
+    }
+    prev = f;
+}
+
+// This source's counters added to out[0 .. n) (n <= RP_N); `reset`: and start them over.  Defined once per source (internal).
+static void rgb_paths_read(uint64_t *out, int n, int reset)
+{
+    uint64_t h[RP_N];
+    (void)hipDeviceSynchronize();
+    (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_rgb_paths), sizeof(h));
+    for (int i = 0; i < n; i++)
+        out[i] += h[i];
+    if (reset) {
+        void *p = nullptr;
+        (void)hipGetSymbolAddress(&p, HIP_SYMBOL(g_rgb_paths));
+        (void)hipMemset(p, 0, sizeof(g_rgb_paths));
+        (void)hipDeviceSynchronize(); // (the contexts' streams do not wait for the null stream)
+    }
+}
+
+} // namespace mcraw
+
+#define RGB_PATH(slot, cond) ::mcraw::rgb_path(::mcraw::slot, (cond))
+#define RGB_PATH_YUV(slot, dst, n, es) ::mcraw::rgb_path_yuv(::mcraw::slot, (dst), (n), (es))
+#define RGB_WALK_DECL uint32_t rgb_walk_prev = 0xffffffffu
+#define RGB_WALK(family, f, lut, lutg) ::mcraw::rgb_walk(::mcraw::family, (f), (lut), (lutg) != 0u, rgb_walk_prev)
