@@ -853,8 +853,9 @@ int mcraw_merge_batch(mcraw_ctx *ctx, const mcraw_merge *m, const uint16_t *in, 
  * It takes no decode serial and leaves the decode slots, mcraw_ctx_errors, mcraw_ctx_last_serial and the context's stage
  * alone.  n == 0 is a no-op; n == 1 writes (0, 0).  The launches have no id in mcraw_ctx_kernel_ms (time them with stream
  * events).
- * Out of scope: local or tile-wise motion (the merge's weights leave out what moved on its own), precision below a quad (the
- * merge drops the low bit of a shift anyway), rotation, a region of interest, and reading gyro metadata.
+ * One shift per frame: local or tile-wise motion and rotation are mcraw_align_cells_batch's, which takes this call's result as its
+ * centre.  Out of scope: precision below a quad (the merge drops the low bit of a shift anyway), a region of interest, and
+ * reading gyro metadata.
  * Rejected (returns < 0, mcraw_last_error says why, starting with "mcraw_align_batch: ", nothing is written): a NULL `a`,
  * `in`, `pos` or `work`; an odd `in` or `pos` address; a `sad` that is not 8-byte aligned; a `work` that is not 16-byte
  * aligned; width or height outside 1 .. 65536; a pitch below width; n > 1 and a frame stride below (height - 1) * pitch +
@@ -875,6 +876,101 @@ typedef struct mcraw_align {
 size_t mcraw_align_work_bytes(int width, int height, int n, uint32_t levels, uint32_t radius);
 int mcraw_align_batch(mcraw_ctx *ctx, const mcraw_align *a, const uint16_t *in, size_t in_pitch, size_t in_frame_stride,
                       int width, int height, int n, void *stream);
+
+/* ---- uint16 mosaics -> a field of local positions, one per cell of every frame, and the merge that follows it ----------------
+ *
+ * The position field.  A cell is cell_h x cell_w samples of the mosaic: cell_w a multiple of 256 and cell_h a multiple of 32
+ * (each at most 65536), so that no tile of the merge straddles a cell and a cell is a whole number of pixels at pyramid levels
+ * 0 .. 2; anything else is rejected.  cells_y = ceil(height / cell_h), cells_x = ceil(width / cell_w): the last row and column
+ * of cells may be partial.  A field is DEVICE memory, 2-byte aligned, (n, cells_y, cells_x, 2) int16 as (y, x): the position of
+ * that cell of that frame, with the meaning of `pos` in mcraw_merge_batch.  Roll of a hand-held camera, rolling-shutter wobble
+ * and parallax move the parts of a frame against each other; one shift per frame leaves everything off the dominant motion to
+ * the merge's weights, which can only reject it.
+ *
+ * mcraw_align_cells_batch estimates the field.  Integers only: bit-exact, whatever the order of the additions.  Pitches and
+ * frame strides count uint16 elements.
+ * Grey plane and pyramid.  G0 and G(l + 1) of mcraw_align_batch, word for word (the same black[4], the same rounding, built by
+ * the same kernel); levels in 1 .. 3; h(l) = height >> (l + 1), w(l) = width >> (l + 1), and a plane may be empty.
+ * Pairs.  As in mcraw_align_batch: ref = -1 gives the chain (t - 1, t), ref = r gives (r, t).
+ * Centre.  gpos: NULL (zeros), or DEVICE memory, 2-byte aligned, (n, 2) int16 as (y, x), read in stream order: the global
+ * estimate, what mcraw_align_batch writes.  For the pair (b, t), g = (gpos[t] - gpos[b]) >> 1 per component, in int32 with an
+ * arithmetic shift (quads); the centre at the coarsest level K - 1 = levels - 1 is g >> (K - 1) (arithmetic).
+ * Per cell (i, j), level l, displacement (dy, dx), exact in 64 bits:
+ *   SAD = sum over the cell's pixels (y, x) of G_l[b] of |G_l[t][clamp(y + dy, 0, h(l) - 1)][clamp(x + dx, 0, w(l) - 1)] - G_l[b][y][x]|
+ * The cell's pixels at level l are the rows (i * cell_h) >> (l + 1) up to min(((i + 1) * cell_h) >> (l + 1), h(l)), and the
+ * columns likewise with j, cell_w and w(l).  A cell with no pixel at a level has SAD 0 for every candidate.  Coordinates are
+ * clamped (edge replicate): there is no margin, and border cells are defined like all others.
+ * Search.  The candidates are -radius .. radius (radius 1 .. 4) about the centre at level K - 1, and -1 .. 1 about twice the
+ * winner at each finer level.  With (ddy, ddx) the offset from the level's centre, the winner is the candidate with the smallest
+ *   key = (SAD, ddy * ddy + ddx * ddx, ddy, ddx)
+ * compared lexicographically (mcraw_align_batch's key), so a flat or an identical cell keeps its centre.  d(t|b)[i][j] is the
+ * level-0 winner in quads, absolute (the centre included).
+ * Field, accumulated in int32 per cell, mcraw_align_batch's formulas cell by cell:
+ *   ref = -1 (chain):    pos[0][i][j] = (0, 0),   pos[t][i][j] = pos[t - 1][i][j] + 2 * d(t|t - 1)[i][j]
+ *   ref in 0 .. n - 1:   pos[ref][i][j] = (0, 0), pos[t][i][j] = 2 * d(t|ref)[i][j]
+ * each component clamped to -32768 .. 32767 on store.  (A step is below 2^16 + 64, so the int32 sums cannot wrap below 32 000
+ * frames.)  Chaining per cell ignores that the content of a cell drifts between cells over a long chain: the sum at cell (i, j)
+ * adds steps that were measured where the content was at each frame's own cell (i, j), not where the base frame's content has
+ * gone.  This is exact for ref = r, and a second-order error over a merge window (the drift inside a window times the field's
+ * gradient).
+ * sad: NULL, or DEVICE memory, 8-byte aligned, (n, cells_y, cells_x) uint64: the level-0 winning SAD, 0 where a frame has no
+ * pair.
+ * work: the caller's DEVICE memory, 16-byte aligned, of at least mcraw_align_cells_work_bytes(width, height, n, levels, radius,
+ * cell_h, cell_w) bytes (0 for arguments the call would reject): the pyramids, the candidates' 64-bit sums per cell and the
+ * levels' winners.  The call initialises what it accumulates into, on the stream; nothing is cached in the context, and two
+ * calls under way at once need two scratch areas.  pos, sad and work are written in stream order; no level waits for the host.
+ * `stream`: a hipStream_t, NULL = the context's own stream; the call queues the work and returns without synchronising.  It
+ * takes no decode serial and leaves the decode slots, mcraw_ctx_errors, mcraw_ctx_last_serial and the context's stage alone.
+ * n == 0 is a no-op; n == 1 writes zeros.  The launches have no id in mcraw_ctx_kernel_ms (time them with stream events).
+ * Rejected (returns < 0, mcraw_last_error says why, starting with "mcraw_align_cells_batch: ", nothing is written): a NULL `a`,
+ * `in`, `pos` or `work`; an odd `in`, `pos` or `gpos` address; a `sad` that is not 8-byte aligned; a `work` that is not
+ * 16-byte aligned; width or height outside 1 .. 65536; a pitch below width; n > 1 and a frame stride below (height - 1) * pitch
+ * + width; levels outside 1 .. 3; radius outside 1 .. 4; ref outside -1 .. n - 1; cell_h no multiple of 32 or cell_w no
+ * multiple of 256 in 1 .. 65536; a non-zero `reserved`; work_bytes below mcraw_align_cells_work_bytes(...); `work`, `pos` or
+ * `sad` overlapping the input's extent or one another; `gpos` overlapping `pos`, `sad` or `work`.
+ * The steps that follow, not done here: precision below a quad (the merge drops the low bit); cells smaller than a merge tile;
+ * smoothing or regularising the field; pairwise estimation of every (base, member) pair of a sliding window; gyro metadata; a
+ * cells path for the resampling demosaic's stabilisation window. */
+typedef struct mcraw_align_cells {
+    uint32_t levels;       /* 1 .. 3: levels of the pyramid                                             */
+    uint32_t radius;       /* 1 .. 4: the search radius at the coarsest level, in its pixels            */
+    int32_t ref;           /* -1: a chain, frame t against frame t - 1;  0 .. n - 1: all against ref    */
+    uint32_t reserved;     /* must be 0                                                                 */
+    uint32_t cell_h;       /* a multiple of 32                                                          */
+    uint32_t cell_w;       /* a multiple of 256                                                         */
+    uint16_t black[4];     /* by CFA position                                                           */
+    const int16_t *gpos;   /* DEVICE memory, 2-byte aligned: (n, 2) as (y, x), the centres; or NULL     */
+    int16_t *pos;          /* DEVICE memory, 2-byte aligned: (n, cells_y, cells_x, 2), written          */
+    uint64_t *sad;         /* DEVICE memory, 8-byte aligned: (n, cells_y, cells_x), written; or NULL    */
+    void *work;            /* DEVICE memory, 16-byte aligned: scratch of work_bytes bytes               */
+    size_t work_bytes;     /* at least mcraw_align_cells_work_bytes(...)                                */
+} mcraw_align_cells;       /* sizeof 72; radius 4, ref 8, reserved 12, cell_h 16, cell_w 20, black 24, gpos 32, pos 40, sad 48, work 56, work_bytes 64 */
+size_t mcraw_align_cells_work_bytes(int width, int height, int n, uint32_t levels, uint32_t radius, uint32_t cell_h, uint32_t cell_w);
+int mcraw_align_cells_batch(mcraw_ctx *ctx, const mcraw_align_cells *a, const uint16_t *in, size_t in_pitch, size_t in_frame_stride,
+                            int width, int height, int n, void *stream);
+
+/* mcraw_merge_cells_batch is mcraw_merge_batch, word for word, except for the shift of member t at the base pixel (y, x), which
+ * comes from a position field F = cells->pos:
+ *   sy = (F[t][y / cell_h][x / cell_w].y - F[b][y / cell_h][x / cell_w].y) & ~1, and sx likewise
+ * All nine terms of support 1 use the shift of the base pixel's own cell, also where a neighbour lies in the next cell (what a
+ * tile that stages its own halo computes); "outside the frame" keeps its meaning, with that shift.  m->pos must be NULL.  A
+ * field that is the same in every cell gives mcraw_merge_batch with that `pos`, bit for bit.  The field is read by the queued
+ * kernel in stream order and never copied.
+ * Rejected, each starting with "mcraw_merge_cells_batch: " and with nothing written: everything mcraw_merge_batch rejects; a
+ * NULL `cells`; a non-NULL m->pos; cell_h no multiple of 32 or cell_w no multiple of 256; cells_y or cells_x that are not
+ * ceil(height / cell_h), ceil(width / cell_w); a non-zero cells->reserved; a NULL or odd cells->pos; a field overlapping the
+ * output's extent. */
+typedef struct mcraw_cells {
+    uint32_t cell_h;       /* a multiple of 32                                                          */
+    uint32_t cell_w;       /* a multiple of 256                                                         */
+    uint32_t cells_y;      /* ceil(height / cell_h)                                                     */
+    uint32_t cells_x;      /* ceil(width / cell_w)                                                      */
+    uint32_t reserved;     /* must be 0                                                                 */
+    const int16_t *pos;    /* DEVICE memory, 2-byte aligned: (n, cells_y, cells_x, 2) as (y, x)         */
+} mcraw_cells;             /* sizeof 32; cell_w 4, cells_y 8, cells_x 12, reserved 16, pos 24 */
+int mcraw_merge_cells_batch(mcraw_ctx *ctx, const mcraw_merge *m, const mcraw_cells *cells, const uint16_t *in, size_t in_pitch,
+                            size_t in_frame_stride, int width, int height, int n, uint16_t *out, size_t out_pitch,
+                            size_t out_frame_stride, void *stream);
 
 /* ---- environment ------------------------------------------------------------------------------
  * Read when a context (or pool) is created, never afterwards:

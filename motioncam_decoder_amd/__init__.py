@@ -19,7 +19,7 @@ __all__ = ["lib_path", "load", "Context", "Pool", "Frame", "EncFrame", "FloatOut
            "DISP_CHW", "DISP_HWC", "Yuv", "YUV_NV12", "YUV_P010", "yuv_matrix", "yuv_planes", "Shade", "gain_map",
            "shading_map", "Stats", "STATS_ACCUMULATE", "FrameStats", "stats_white_balance", "stats_percentile",
            "stats_clipped", "FixPix", "FIXPIX_HOT", "FIXPIX_COLD", "pack_pixels", "Denoise", "noise_lut", "Merge", "Align",
-           "align_window", "fit_crop", "Area", "RGB_AREA", "Resample", "RGB_RESAMPLE",
+           "AlignCells", "Cells", "cell_grid", "align_window", "fit_crop", "Area", "RGB_AREA", "Resample", "RGB_RESAMPLE",
            "FILTER_LINEAR", "FILTER_CUBIC"]
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
@@ -51,6 +51,7 @@ ABI_SYMBOLS = [
     "mcraw_stats_batch", "mcraw_stats_record_bytes", "mcraw_fixpix_batch", "mcraw_denoise_batch",
     "mcraw_merge_batch", "mcraw_align_batch", "mcraw_align_work_bytes", "mcraw_demosaic_area_batch", "mcraw_area_work_bytes",
     "mcraw_demosaic_resample_batch", "mcraw_resample_work_bytes",
+    "mcraw_align_cells_batch", "mcraw_align_cells_work_bytes", "mcraw_merge_cells_batch",
 ]
 
 POST_BLACK, POST_PACK12, POST_PACK10, POST_PACK14 = 1, 2, 4, 8
@@ -468,6 +469,36 @@ class Align(C.Structure):
                 ("work_bytes", C.c_size_t)]
 
 
+# a field of local shifts, one per cell of every frame (mcraw_align_cells_batch), and the merge that follows it (mcraw_merge_cells_batch)
+class AlignCells(C.Structure):
+    """struct mcraw_align_cells (include/mcraw_hip.h): the pyramid's levels (1 .. 3), the coarsest level's radius (1 .. 4), the
+    reference frame (-1: a chain), the cell in samples, the blacks, the device centres gpos (n, 2) int16 or NULL, the device
+    outputs pos (n, cells_y, cells_x, 2) int16 and sad (n, cells_y, cells_x) uint64 or NULL, and the device scratch with its size."""
+    _fields_ = [("levels", C.c_uint32), ("radius", C.c_uint32), ("ref", C.c_int32), ("reserved", C.c_uint32),
+                ("cell_h", C.c_uint32), ("cell_w", C.c_uint32), ("black", C.c_uint16 * 4), ("gpos", C.c_void_p),
+                ("pos", C.c_void_p), ("sad", C.c_void_p), ("work", C.c_void_p), ("work_bytes", C.c_size_t)]
+
+
+class Cells(C.Structure):
+    """struct mcraw_cells (include/mcraw_hip.h): the cell in samples, the grid's size and the device field (n, cells_y, cells_x,
+    2) of int16 that mcraw_merge_cells_batch reads."""
+    _fields_ = [("cell_h", C.c_uint32), ("cell_w", C.c_uint32), ("cells_y", C.c_uint32), ("cells_x", C.c_uint32),
+                ("reserved", C.c_uint32), ("pos", C.c_void_p)]
+
+
+def cell_grid(height, width, cell=(64, 256)):
+    """(cells_y, cells_x) of the position field of height x width frames for cells of cell = (cell_h, cell_w) samples: the
+    ceilings.  Raises ValueError for a cell_h that is no multiple of 32 or a cell_w that is no multiple of 256 (host only)."""
+    try:
+        ch, cw = cell
+    except (TypeError, ValueError):
+        raise ValueError("cell must be (cell_h, cell_w), not %r" % (cell,))
+    for name, v, g in (("cell_h", ch, 32), ("cell_w", cw, 256)):
+        if isinstance(v, bool) or v != int(v) or int(v) < g or int(v) % g or int(v) > 65536:
+            raise ValueError("cell: %s must be a multiple of %d in %d .. 65536, not %r" % (name, g, g, v))
+    return (int(height) + int(ch) - 1) // int(ch), (int(width) + int(cw) - 1) // int(cw)
+
+
 def align_window(height, width, levels=4, radius=4):
     """(rows, columns) of the level-0 comparison window of Context.align for frames of height x width: what its `sad` is summed
     over, (height // 2 - 2 * B0, width // 2 - 2 * B0) with B(levels - 1) = radius, B(l) = 2 * B(l + 1) + 1.  Raises ValueError
@@ -874,6 +905,14 @@ def load():
     lib.mcraw_align_batch.restype = C.c_int
     lib.mcraw_align_batch.argtypes = [C.c_void_p, C.POINTER(Align), C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int,
                                       C.c_void_p]
+    lib.mcraw_align_cells_work_bytes.restype = C.c_size_t
+    lib.mcraw_align_cells_work_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
+    lib.mcraw_align_cells_batch.restype = C.c_int
+    lib.mcraw_align_cells_batch.argtypes = [C.c_void_p, C.POINTER(AlignCells), C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int,
+                                            C.c_int, C.c_void_p]
+    lib.mcraw_merge_cells_batch.restype = C.c_int
+    lib.mcraw_merge_cells_batch.argtypes = [C.c_void_p, C.POINTER(Merge), C.POINTER(Cells), C.c_void_p, C.c_size_t, C.c_size_t, C.c_int,
+                                            C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
     lib.mcraw_area_work_bytes.restype = C.c_size_t
     lib.mcraw_area_work_bytes.argtypes = [C.POINTER(Area)]
     lib.mcraw_resample_work_bytes.restype = C.c_size_t
@@ -1471,7 +1510,7 @@ class Context:
         self._call(torch, dev, "mcraw_denoise_batch", (mos, out, lut), C.byref(s), *src, w, h, n, *dst)
         return out
 
-    def merge(self, mosaic, lut, shift, before=2, after=2, first=0, count=None, support=1, amount=1.0, pos=None, out=None):
+    def merge(self, mosaic, lut, shift, before=2, after=2, first=0, count=None, support=1, amount=1.0, pos=None, out=None, cell=None):
         """Noise-adaptive merge along time of uint16 mosaics resident on the context's device (mcraw_merge_batch): output j is
         the base frame first + j, every pixel the weighted mean of itself and the samples at its (shifted) position in the
         `before` frames in front of the base and the `after` frames behind it (clipped at the ends of the batch; before +
@@ -1483,12 +1522,21 @@ class Context:
         first.  amount: a float kept as rint(amount * 256) in 1 .. 256.  pos: None, or the frames' global positions (N, 2)
         as (y, x): an int16 CUDA tensor (read in stream order), or a host array of integers in -32768 .. 32767, uploaded on
         the current stream; a member is read at the difference of the positions with the low bit dropped, so that a sample
-        keeps its CFA position.  out: None (a new contiguous tensor) or a uint16 tensor (count, H, W) that does not overlap
-        the mosaic.  Returns (count, H, W).  Queued on torch.cuda.current_stream(); nothing synchronises."""
+        keeps its CFA position.  A 4-D pos (N, Cy, Cx, 2) with cell=(cell_h, cell_w) is a position field, what align_cells()
+        returns (mcraw_merge_cells_batch): every cell_h x cell_w samples of a frame have a position of their own, (Cy, Cx) =
+        cell_grid(H, W, cell), cell_h a multiple of 32 and cell_w of 256; a tensor or a host array as above.  out: None (a new
+        contiguous tensor) or a uint16 tensor (count, H, W) that does not overlap the mosaic.  Returns (count, H, W).  Queued on
+        torch.cuda.current_stream(); nothing synchronises."""
         import numpy as np
         import torch
         dev = self._torch_device(torch)
         mosaic, _, n, h, w = self._mosaic_arg(torch, dev, "merge", mosaic, dims=(3,))
+        if pos is not None and not isinstance(pos, torch.Tensor):
+            pos = np.asarray(pos)  # (a nested list is a host array too)
+        field = pos is not None and pos.ndim == 4
+        if field != (cell is not None):
+            raise ValueError("merge: cell=(cell_h, cell_w) goes with a 4-D pos (N, Cy, Cx, 2), and only with one")
+        pshape = (n,) + cell_grid(h, w, cell) + (2,) if field else (n, 2)
         for name, v in (("before", before), ("after", after), ("first", first)) + ((("count", count),) if count is not None else ()):
             if isinstance(v, bool) or v != int(v) or int(v) < 0:
                 raise ValueError("merge: %s must be a non-negative integer, not %r" % (name, v))
@@ -1511,12 +1559,12 @@ class Context:
         lut, nluts, L = self._noise_table(torch, dev, "merge", lut, n)
         if pos is not None:
             if isinstance(pos, torch.Tensor):
-                if pos.dtype != torch.int16 or pos.device != dev or tuple(pos.shape) != (n, 2) or not pos.is_contiguous():
-                    raise ValueError("merge: a pos tensor must be a contiguous int16 tensor (%d, 2) on %s" % (n, dev))
+                if pos.dtype != torch.int16 or pos.device != dev or tuple(pos.shape) != pshape or not pos.is_contiguous():
+                    raise ValueError("merge: a pos tensor must be a contiguous int16 tensor %r on %s" % (pshape, dev))
             else:
                 a = np.asarray(pos)
-                if a.shape != (n, 2) or a.dtype.kind not in "iu" or (a.size and (a.min() < -32768 or a.max() > 32767)):
-                    raise ValueError("merge: pos must be (%d, 2) integers (y, x) in -32768 .. 32767" % n)
+                if a.shape != pshape or a.dtype.kind not in "iu" or (a.size and (a.min() < -32768 or a.max() > 32767)):
+                    raise ValueError("merge: pos must be %r integers (y, x) in -32768 .. 32767" % (pshape,))
                 pos = torch.from_numpy(np.ascontiguousarray(a, dtype=np.int16)).to(dev)
         if n == 0 or count == 0 or h == 0 or w == 0:
             return out
@@ -1526,13 +1574,20 @@ class Context:
         s.before, s.after, s.first, s.count, s.support = before, after, first, count, int(support)
         s.amount, s.lut_log2, s.shift, s.nluts, s.reserved = int(np.rint(amt * 256.0)), L.bit_length() - 1, int(shift), nluts, 0
         s.lut = lut.data_ptr()
+        if field:
+            g = Cells()
+            g.cell_h, g.cell_w, g.cells_y, g.cells_x, g.reserved, g.pos = int(cell[0]), int(cell[1]), pshape[1], pshape[2], 0, pos.data_ptr()
+            s.pos = None
+            self._call(torch, dev, "mcraw_merge_cells_batch", (mosaic, out, lut, pos), C.byref(s), C.byref(g), *src, w, h, n, *dst)
+            return out
         s.pos = pos.data_ptr() if pos is not None else None
         self._call(torch, dev, "mcraw_merge_batch", (mosaic, out, lut, pos), C.byref(s), *src, w, h, n, *dst)
         return out
 
     def stack(self, mosaic, lut, shift, ref=0, **kw):
         """The burst form of merge(): all N <= 16 frames of mosaic (N, H, W) merged onto frame `ref`.  The keyword arguments
-        are merge()'s without before, after, first and count; out, if given, is (H, W).  Returns (H, W)."""
+        are merge()'s without before, after, first and count (pos= and cell= pass through: a field from align_cells(ref=ref)
+        stacks along local motion); out, if given, is (H, W).  Returns (H, W)."""
         import torch
         if not isinstance(mosaic, torch.Tensor) or mosaic.dim() != 3 or not 1 <= int(mosaic.shape[0]) <= 16:
             raise ValueError("stack: mosaic must be a uint16 tensor (N, H, W) of 1 .. 16 frames")
@@ -1586,6 +1641,59 @@ class Context:
         a.pos, a.sad, a.work, a.work_bytes = pos.data_ptr(), (sums.data_ptr() if sad else None), work.data_ptr(), need
         self._call(torch, dev, "mcraw_align_batch", (mosaic, pos, sums, work), C.byref(a), *src, w, h, n)
         return (pos, sums) if sad else pos
+
+    def align_cells(self, mosaic, *, pos=None, black=(0, 0, 0, 0), cell=(64, 256), levels=3, radius=2, ref=None, sad=False):
+        """A field of local shifts of uint16 mosaics resident on the context's device (mcraw_align_cells_batch): align()'s grey
+        pyramid and coarse-to-fine search, with the sums kept per cell of cell = (cell_h, cell_w) samples (cell_h a multiple of
+        32, cell_w of 256) instead of per frame, so roll, rolling-shutter wobble and parallax are followed where one shift per
+        frame leaves them to the merge's weights.  mosaic: (N, H, W), rows contiguous (rows and frames may be strided), any
+        size.  pos: None, or the frames' global positions (N, 2) as align() returns them (an int16 CUDA tensor read in stream
+        order, or a host array of integers): the centre of every cell's search, so the field needs to find only what the parts
+        of a frame do against the whole.  levels 1 .. 3, radius 1 .. 4 pixels of the coarsest level about that centre.  black,
+        ref: align()'s.  Returns the field, a contiguous int16 tensor (N, Cy, Cx, 2) as (y, x) with (Cy, Cx) = cell_grid(H, W,
+        cell), clamped to -32768 .. 32767: what merge(pos=, cell=) takes.  sad=True also returns an int64 tensor (N, Cy, Cx):
+        the winning sum of absolute differences of each cell's level-0 pixels, 0 for the frame without a pair.  The scratch is
+        a tensor of torch's caching allocator.  Queued on torch.cuda.current_stream(); nothing synchronises."""
+        import numpy as np
+        import torch
+        dev = self._torch_device(torch)
+        mosaic, _, n, h, w = self._mosaic_arg(torch, dev, "align_cells", mosaic, dims=(3,))
+        black = [black] * 4 if not hasattr(black, "__len__") else list(black)
+        if len(black) != 4 or any(v != int(v) or v < 0 or v > 65535 for v in black):
+            raise ValueError("align_cells: black is one level or four, by CFA position (row & 1) * 2 + (col & 1), each an integer 0 .. 65535")
+        if ref is not None and (isinstance(ref, bool) or ref != int(ref) or not 0 <= int(ref) < max(n, 1)):
+            raise ValueError("align_cells: ref must be None (a chain) or 0 .. %d, not %r" % (n - 1, ref))
+        for name, v, hi in (("levels", levels, 3), ("radius", radius, 4)):
+            if isinstance(v, bool) or v != int(v) or not 1 <= int(v) <= hi:
+                raise ValueError("align_cells: %s must be an integer 1 .. %d, not %r" % (name, hi, v))
+        if h == 0 or w == 0:
+            raise ValueError("align_cells: empty frames have no positions")
+        cy, cx = cell_grid(h, w, cell)
+        if pos is not None:
+            if isinstance(pos, torch.Tensor):
+                if pos.dtype != torch.int16 or pos.device != dev or tuple(pos.shape) != (n, 2) or not pos.is_contiguous():
+                    raise ValueError("align_cells: a pos tensor must be a contiguous int16 tensor (%d, 2) on %s" % (n, dev))
+            else:
+                g = np.asarray(pos)
+                if g.shape != (n, 2) or g.dtype.kind not in "iu" or (g.size and (g.min() < -32768 or g.max() > 32767)):
+                    raise ValueError("align_cells: pos must be (%d, 2) integers (y, x) in -32768 .. 32767" % n)
+                pos = torch.from_numpy(np.ascontiguousarray(g, dtype=np.int16)).to(dev)
+        field = torch.empty((n, cy, cx, 2), dtype=torch.int16, device=dev)
+        sums = torch.empty((n, cy, cx), dtype=torch.int64, device=dev) if sad else None
+        if n == 0:
+            return (field, sums) if sad else field
+        src = self._strided("align_cells", "the mosaic", mosaic, h, w)
+        need = int(self._lib.mcraw_align_cells_work_bytes(w, h, n, int(levels), int(radius), int(cell[0]), int(cell[1])))
+        work = torch.empty((need,), dtype=torch.uint8, device=dev)
+        a = AlignCells()
+        a.levels, a.radius, a.ref, a.reserved = int(levels), int(radius), (-1 if ref is None else int(ref)), 0
+        a.cell_h, a.cell_w = int(cell[0]), int(cell[1])
+        for i in range(4):
+            a.black[i] = int(black[i])
+        a.gpos = pos.data_ptr() if pos is not None else None
+        a.pos, a.sad, a.work, a.work_bytes = field.data_ptr(), (sums.data_ptr() if sad else None), work.data_ptr(), need
+        self._call(torch, dev, "mcraw_align_cells_batch", (mosaic, field, sums, work, pos), C.byref(a), *src, w, h, n)
+        return (field, sums) if sad else field
 
     def _denoise_stage(self, mos, denoise, fn):
         """denoise= of the demosaic / decode methods: denoise() with these keyword arguments into a scratch tensor of the
@@ -1657,13 +1765,24 @@ class Context:
         inputs: uint8 CUDA tensors, or (device pointer, length) pairs.  check=True synchronises after the decode and raises
         McrawError naming the frames that failed; check=False returns at once.  The stage the context had before the call is
         restored afterwards.  merge_kw: merge()'s keyword arguments.  align: None, or a dict of align()'s keyword arguments
-        (without sad): the decoded frames' positions are estimated and handed to the merge as pos.  Returns merge()'s
+        (without sad): the decoded frames' positions are estimated and handed to the merge as pos.  With "cell": (cell_h,
+        cell_w) among them, align() runs without it, align_cells() about its result with the same black and ref (its own levels
+        and radius: "cell_levels", default 3, and "cell_radius", default 2), and the merge follows the field.  Returns merge()'s
         (count, H, W)."""
-        if align is not None and (not isinstance(align, dict) or "sad" in align or "pos" in merge_kw):
-            raise ValueError("decode_merge: align must be a dict of align()'s keyword arguments (without sad), and excludes pos")
+        if align is not None and (not isinstance(align, dict) or "sad" in align or "pos" in merge_kw or "cell" in merge_kw):
+            raise ValueError("decode_merge: align must be a dict of align()'s keyword arguments (without sad), and excludes pos and cell")
         scratch = self._decode_scratch(inputs, width, height, type, check, "decode_merge")
         if align is not None:
+            align = dict(align)
+            cell = align.pop("cell", None)
+            ckw = {"levels": align.pop("cell_levels", 3), "radius": align.pop("cell_radius", 2)}
+            if cell is None and (ckw["levels"], ckw["radius"]) != (3, 2):
+                raise ValueError("decode_merge: cell_levels and cell_radius go with cell")
             merge_kw["pos"] = self.align(scratch, **align)
+            if cell is not None:
+                ckw.update({k: align[k] for k in ("black", "ref") if k in align})
+                merge_kw["pos"] = self.align_cells(scratch, pos=merge_kw["pos"], cell=cell, **ckw)
+                merge_kw["cell"] = cell
         return self.merge(scratch, lut, shift, **merge_kw)
 
     def demosaic(self, mosaic, *, algo="mhc", dtype, white, black=(0, 0, 0, 0), cfa="rggb", gain=None, matrix=None,

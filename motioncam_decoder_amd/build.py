@@ -40,13 +40,13 @@ def _run(cmd):
     subprocess.run(cmd, check=True)
 
 
-# The gfx950 library: kernels (mcraw_type7 / mcraw_type6, the encoder mcraw_encode7, the demosaic mcraw_rgb, the lens-shading stage mcraw_shade, the statistics mcraw_stats, the defective-pixel stage mcraw_fixpix, the denoiser mcraw_denoise, the temporal merge mcraw_merge, the shift estimate mcraw_align, the area-average demosaic mcraw_area, the resampling demosaic mcraw_resample), the host side of the C ABI in its units (csrc/mcraw_host.h) and the device pool.
+# The gfx950 library: kernels (mcraw_type7 / mcraw_type6, the encoder mcraw_encode7, the demosaic mcraw_rgb, the lens-shading stage mcraw_shade, the statistics mcraw_stats, the defective-pixel stage mcraw_fixpix, the denoiser mcraw_denoise, the temporal merge mcraw_merge, the shift estimate mcraw_align and its cell-wise form mcraw_cells, the area-average demosaic mcraw_area, the resampling demosaic mcraw_resample), the host side of the C ABI in its units (csrc/mcraw_host.h) and the device pool.
 HIP_SOURCES = ("mcraw_abi.hip", "mcraw_submit.hip", "mcraw_tune.hip", "mcraw_device.hip", "mcraw_hostmem.hip", "mcraw_pool.hip",
                "mcraw_type7.hip", "mcraw_type6.hip", "mcraw_encode7.hip", "mcraw_rgb.hip", "mcraw_shade.hip", "mcraw_stats.hip",
-               "mcraw_fixpix.hip", "mcraw_denoise.hip", "mcraw_merge.hip", "mcraw_align.hip", "mcraw_area.hip", "mcraw_resample.hip")
+               "mcraw_fixpix.hip", "mcraw_denoise.hip", "mcraw_merge.hip", "mcraw_align.hip", "mcraw_area.hip", "mcraw_resample.hip", "mcraw_cells.hip")
 HIP_HEADERS = ("mcraw_plan.h", "mcraw_dev.h", "mcraw_host.h", "mcraw_race.h", "mcraw_mosaic.h", "mcraw_mosaic_args.h",
                "mcraw_rgb_args.h", "mcraw_align_args.h", "mcraw_area_args.h", "mcraw_rgb_dev.h", "mcraw_rgb_launch.h",
-               "mcraw_resample_args.h", "mcraw_rgb_paths.h")
+               "mcraw_resample_args.h", "mcraw_rgb_paths.h", "mcraw_align_pyr.h", "mcraw_cells_args.h")
 HIP_FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc"]
 
 
@@ -177,10 +177,28 @@ RGB_PATH_VARIANTS = {
     "poison1": ["-DMCRAW_PATHSR", "-DMCRAW_RGB_GRID_CAP=1", "-DMCRAW_POISON_RGB"],
 }
 
+# The merge with tiles of 16 rows instead of 32 (tools/bench_merge.py --alt-lib, tests/test_gpu_merge_cells.py): the name occurs in
+# mcraw_merge.hip alone.
+MERGE_ALT_FLAGS = ["-DMCRAW_MERGE_TH=16"]
+
+
+def build_merge_alt():
+    """lib/alt/libmcraw_hip_th16_<tag>.so, the MCRAW_MERGE_TH=16 build, made once per state of the sources (the tag is a hash of
+    them, so a library left from other sources is never taken for this one)."""
+    import hashlib
+    h = hashlib.sha1()
+    for f in hip_sources() + [os.path.join(CSRC, f) for f in HIP_HEADERS] + [os.path.join(ROOT, "include", "mcraw_hip.h")]:
+        h.update(open(f, "rb").read())
+    out = os.path.join(LIB, "alt", "libmcraw_hip_th16_%s.so" % h.hexdigest()[:12])
+    if not os.path.exists(out):
+        build_variant(out, MERGE_ALT_FLAGS)
+    return out
+
+
 # The -D builds that tests/ links on the GPU box (tests/test_gpu_split.py, test_gpu_segw.py, test_gpu_lookback_fault.py,
 # test_gpu_k6_paths.py, test_gpu_k7_paths.py, test_gpu_enc7_paths.py, test_gpu_k7t_paths.py, test_gpu_rgb_paths.py).
 TEST_VARIANTS = ((["-DMCRAW_FORCE_SEGW"], ["-DMCRAW_INJECT_MUTE7"], ["-DMCRAW_INJECT_LOST"]) + tuple(K6_PATH_VARIANTS.values())
-                 + tuple(K7_PATH_VARIANTS.values()) + tuple(ENC7_PATH_VARIANTS.values()) + tuple(K7T_PATH_VARIANTS.values()) + tuple(RGB_PATH_VARIANTS.values()))
+                 + tuple(K7_PATH_VARIANTS.values()) + tuple(ENC7_PATH_VARIANTS.values()) + tuple(K7T_PATH_VARIANTS.values()) + tuple(RGB_PATH_VARIANTS.values()) + (MERGE_ALT_FLAGS,))
 
 
 def prebuild_test_variants():

@@ -17,17 +17,14 @@
 //                   candidate's 32-bit sum (4096 differences of at most 65535) to its 64-bit sum with one atomic.
 //   kalign_pick     a pair's winner at the level by the contract's key; the next level's centre is twice it.
 //   kalign_final    the chain's prefix sum over n in int32 (or the anchor form), the clamp, pos and sad.
-#include "mcraw_host.h"
-#include "mcraw_mosaic.h"
-#include "mcraw_align_args.h"
+// The pyramid's launches (align_pyramid), the pair rule and the nine-candidate refinement (al_refine) are shared with the cell-wise
+// estimate, mcraw_cells.hip, through mcraw_align_pyr.h.
+#include "mcraw_align_pyr.h"
 
 namespace mcraw {
 
-constexpr int AL_T = 256;        // threads per workgroup
 constexpr uint32_t AL_PW = 256u; // kalign_pyr's tile: 32 lanes across with 8 columns each,
-constexpr uint32_t AL_PH = 64u;  //   8 lanes down with 8 rows each
-constexpr uint32_t AL_TW = 128u; // kalign_sad's tile: 32 lanes across with 4 pixels each,
-constexpr uint32_t AL_TH = 32u;  //   8 lanes down with 4 rows each
+constexpr uint32_t AL_PH = 64u;  //   8 lanes down with 8 rows each (kalign_sad's tile: AL_TW x AL_TH of mcraw_align_pyr.h)
 // A build for timing the parts (tools/bench_align.py): the call stops after MCRAW_ALIGN_STOP of them -- the pyramid, then one per
 // level, coarsest first -- and writes no positions.  Not the product.
 #ifdef MCRAW_ALIGN_STOP
@@ -156,12 +153,6 @@ __global__ void __launch_bounds__(AL_T) kalign_zero(unsigned long long *p, size_
         p[i] = 0ull;
 }
 
-// The pair of frame t (0 .. n - 1): its base, or -1 for the frame that has none.
-__device__ __forceinline__ int al_base(int t, int ref)
-{
-    return ref < 0 ? t - 1 : (t == ref ? -1 : ref);
-}
-
 struct AlSadArgs {
     const uint16_t *pyr; // frame 0's pyramid
     unsigned long long *acc; // frame 0's sums
@@ -186,55 +177,6 @@ __device__ __forceinline__ void al_stage(uint32_t *s, uint32_t LW, const uint16_
         if (yy < h && col < pitch)
             v = *gptr<const uint32_t>(plane + static_cast<size_t>(yy) * pitch + col);
         s[r * (LW / 2u) + j] = v;
-    }
-}
-
-// The pair of columns that starts at column c + o of dwords lo = (c, c + 1), hi = (c + 2, c + 3); o: 0 or 1
-__device__ __forceinline__ uint32_t al_pair(uint32_t lo, uint32_t hi, uint32_t o)
-{
-    return o ? __builtin_amdgcn_alignbit(hi, lo, 16u) : lo;
-}
-
-// A lane's 4 x 4 pixels against the nine candidates of a refinement level: acc[3 * (ddy + 1) + (ddx + 1)].  sb, sm: the staged
-// tiles (LD dwords per row); ob, om: which half of its first dword a row's first column is; nx, ny: the lane's columns and rows
-// inside the window (FULL: 4 and 4 for every lane of the wave).  A pixel outside the window is 0 on both sides.
-template <bool FULL>
-__device__ __forceinline__ void al_refine(const uint32_t *sb, const uint32_t *sm, uint32_t LD, uint32_t lx, uint32_t ly, uint32_t ob,
-                                          uint32_t om, uint32_t nx, uint32_t ny, uint32_t acc[9])
-{
-    uint32_t mk[4][2], bp[4][2];
-#pragma unroll
-    for (uint32_t i = 0; i < 4u; i++) {
-        const uint32_t rowm = i < ny ? 0xFFFFFFFFu : 0u;
-        mk[i][0] = FULL ? 0xFFFFFFFFu : rowm & ((nx > 0u ? 0xFFFFu : 0u) | (nx > 1u ? 0xFFFF0000u : 0u));
-        mk[i][1] = FULL ? 0xFFFFFFFFu : rowm & ((nx > 2u ? 0xFFFFu : 0u) | (nx > 3u ? 0xFFFF0000u : 0u));
-        const uint32_t *q = &sb[(4u * ly + i) * LD + 2u * lx];
-        const uint32_t d0 = q[0], d1 = q[1], d2 = q[2];
-        bp[i][0] = al_pair(d0, d1, ob) & mk[i][0];
-        bp[i][1] = al_pair(d1, d2, ob) & mk[i][1];
-    }
-#pragma unroll
-    for (uint32_t c = 0; c < 9u; c++)
-        acc[c] = 0u;
-#pragma unroll
-    for (uint32_t rr = 0; rr < 6u; rr++) { // the member's rows 4 ly + rr: base row i meets it as ddy = rr - i - 1
-        const uint32_t *q = &sm[(4u * ly + rr) * LD + 2u * lx];
-        const uint32_t d0 = q[0], d1 = q[1], d2 = q[2], d3 = q[3];
-        const uint32_t e1 = __builtin_amdgcn_alignbit(d1, d0, 16u), e3 = __builtin_amdgcn_alignbit(d2, d1, 16u),
-                       e5 = __builtin_amdgcn_alignbit(d3, d2, 16u);
-        // f[k]: the pair that starts k columns behind the member's column for the lane's first pixel and ddx = -1
-        const uint32_t f[5] = {om ? e1 : d0, om ? d1 : e1, om ? e3 : d1, om ? d2 : e3, om ? e5 : d2};
-#pragma unroll
-        for (uint32_t i = 0; i < 4u; i++) {
-            if (rr < i || rr > i + 2u)
-                continue;
-            const uint32_t ddy = rr - i; // + 1 already: 0 .. 2
-#pragma unroll
-            for (uint32_t ddx = 0; ddx < 3u; ddx++) { // + 1 already
-                acc[3u * ddy + ddx] = __builtin_amdgcn_sad_u16(f[ddx] & mk[i][0], bp[i][0], acc[3u * ddy + ddx]);
-                acc[3u * ddy + ddx] = __builtin_amdgcn_sad_u16(f[ddx + 2u] & mk[i][1], bp[i][1], acc[3u * ddy + ddx]);
-            }
-        }
     }
 }
 
@@ -397,6 +339,35 @@ extern "C" size_t mcraw_align_work_bytes(int width, int height, int n, uint32_t 
     return P.total;
 }
 
+// The pyramids of the n frames (mcraw_align_pyr.h): the launch loop of the mosaic stages, grid.y frames at a time.
+int mcraw::align_pyramid(hipStream_t st, const MosaicBatch &I, const uint16_t *in, int n, const uint16_t black[4], const AlPyramid &G, uint16_t *pyr)
+{
+    AlPyrArgs Y{};
+    Y.ipitch = I.pitch, Y.ifstride = I.fstride, Y.pstride = G.frame_elems;
+    Y.W = static_cast<uint32_t>(I.W), Y.H = static_cast<uint32_t>(I.H);
+    Y.tilesX = (Y.W + AL_PW - 1u) / AL_PW;
+    Y.levels = G.levels, Y.vec = I.on_grid();
+    Y.blk[0] = black[0] | (static_cast<uint32_t>(black[1]) << 16);
+    Y.blk[1] = black[2] | (static_cast<uint32_t>(black[3]) << 16);
+    for (uint32_t l = 0; l < G.levels; l++)
+        Y.L.h[l] = G.h[l], Y.L.w[l] = G.w[l], Y.L.pitch[l] = G.pitch[l], Y.L.off[l] = G.off[l];
+    for (int f0 = 0; f0 < n; f0 += LAUNCH_FRAMES) {
+        const uint32_t nf = static_cast<uint32_t>(std::min(LAUNCH_FRAMES, n - f0));
+        Y.in = in + static_cast<size_t>(f0) * I.fstride;
+        Y.pyr = pyr + static_cast<size_t>(f0) * G.frame_elems;
+        hipLaunchKernelGGL(kalign_pyr, dim3(Y.tilesX * ((Y.H + AL_PH - 1u) / AL_PH), nf), dim3(AL_T), 0, st, Y);
+        HIP_TRY(hipGetLastError());
+        for (uint32_t l = 3; l < G.levels; l++) {
+            if (G.h[l] == 0u || G.w[l] == 0u)
+                break;
+            hipLaunchKernelGGL(kalign_down, dim3((G.h[l] * G.w[l] + AL_T - 1u) / AL_T, nf), dim3(AL_T), 0, st, Y.pyr, G.frame_elems, G.off[l - 1u],
+                               G.pitch[l - 1u], G.off[l], G.pitch[l], G.h[l], G.w[l]);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    return 0;
+}
+
 static int mcraw_align_launch(mcraw_ctx *c, const mcraw_align *a, const MosaicBatch &I, const AlignPlan &P, const uint16_t *in, int n,
                               hipStream_t st)
 {
@@ -408,27 +379,12 @@ static int mcraw_align_launch(mcraw_ctx *c, const mcraw_align *a, const MosaicBa
         const size_t words = static_cast<size_t>(n) * P.nacc;
         hipLaunchKernelGGL(kalign_zero, dim3(static_cast<uint32_t>(std::min<size_t>((words + AL_T - 1u) / AL_T, 4096u))), dim3(AL_T), 0, st, acc, words);
         HIP_TRY(hipGetLastError());
-        AlPyrArgs Y{};
-        Y.ipitch = I.pitch, Y.ifstride = I.fstride, Y.pstride = P.frame_elems;
-        Y.W = static_cast<uint32_t>(I.W), Y.H = static_cast<uint32_t>(I.H);
-        Y.tilesX = (Y.W + AL_PW - 1u) / AL_PW;
-        Y.levels = P.levels, Y.vec = I.on_grid();
-        Y.blk[0] = a->black[0] | (static_cast<uint32_t>(a->black[1]) << 16);
-        Y.blk[1] = a->black[2] | (static_cast<uint32_t>(a->black[3]) << 16);
+        AlPyramid G{};
+        G.levels = P.levels, G.frame_elems = P.frame_elems;
         for (uint32_t l = 0; l < P.levels; l++)
-            Y.L.h[l] = P.h[l], Y.L.w[l] = P.w[l], Y.L.pitch[l] = P.pitch[l], Y.L.off[l] = P.off[l];
-        for (int f0 = 0; f0 < n; f0 += LAUNCH_FRAMES) { // the launch loop of the mosaic stages: grid.y frames at a time
-            const uint32_t nf = static_cast<uint32_t>(std::min(LAUNCH_FRAMES, n - f0));
-            Y.in = in + static_cast<size_t>(f0) * I.fstride;
-            Y.pyr = pyr + static_cast<size_t>(f0) * P.frame_elems;
-            hipLaunchKernelGGL(kalign_pyr, dim3(Y.tilesX * ((Y.H + AL_PH - 1u) / AL_PH), nf), dim3(AL_T), 0, st, Y);
-            HIP_TRY(hipGetLastError());
-            for (uint32_t l = 3; l < P.levels; l++) {
-                hipLaunchKernelGGL(kalign_down, dim3((P.h[l] * P.w[l] + AL_T - 1u) / AL_T, nf), dim3(AL_T), 0, st, Y.pyr, P.frame_elems, P.off[l - 1u],
-                                   P.pitch[l - 1u], P.off[l], P.pitch[l], P.h[l], P.w[l]);
-                HIP_TRY(hipGetLastError());
-            }
-        }
+            G.h[l] = P.h[l], G.w[l] = P.w[l], G.pitch[l] = P.pitch[l], G.off[l] = P.off[l];
+        if (const int rc = align_pyramid(st, I, in, n, a->black, G, pyr))
+            return rc;
         if (AL_STOP == 1u)
             return 0;
         for (uint32_t l = P.levels; l-- > 0u;) { // coarsest first

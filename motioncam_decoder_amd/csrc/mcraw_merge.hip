@@ -13,8 +13,11 @@
 // product of a row count and a column count because the region is a rectangle.  num and den stay in registers over the
 // members.  Workgroups are numbered so that consecutive base frames of one tile run next to each other on one XCD: a member
 // is fetched from HBM once and found in that XCD's L2 by the other bases that hold it in their windows.
+// kmerge<SUPPORT, NT, true, MgCellArgs> (mcraw_merge_cells_batch): the same kernel, a tile reading its shifts from the cell of a
+// position field that it lies in.
 #include "mcraw_host.h"
 #include "mcraw_mosaic.h"
+#include "mcraw_cells_args.h"
 
 namespace mcraw {
 
@@ -89,8 +92,14 @@ __device__ __forceinline__ void mg_row(const uint16_t *p, uint32_t w[6])
     w[0] = a0, w[1] = a1[0], w[2] = a1[1], w[3] = a1[2], w[4] = a1[3], w[5] = a2;
 }
 
-template <int SUPPORT, bool NT>
-__global__ void __launch_bounds__(MG_T) kmerge(const MgArgs A)
+// mcraw_merge_cells_batch: `pos` is a field (n, cells_y, cells_x, 2), and a tile reads the shifts of the cell it lies in.
+struct MgCellArgs : MgArgs {
+    uint32_t cell_h, cell_w, cells_x, cells; // a cell in samples (whole tiles); cells across, cells per frame
+};
+
+// FIELD changes only where by, bx, sy, sx are read: A.pos[(frame * cells + the tile's cell) * 2 ..] instead of A.pos[frame * 2 ..].
+template <int SUPPORT, bool NT, bool FIELD = false, class ARGS = MgArgs>
+__global__ void __launch_bounds__(MG_T) kmerge(const ARGS A)
 {
     __shared__ __attribute__((aligned(16))) uint16_t s_b[MG_LH * MG_LW];      // the base's tile and its halo
     __shared__ __attribute__((aligned(16))) uint16_t s_m[MG_LH * MG_LW];      // one member's, moved by its shift
@@ -138,7 +147,12 @@ __global__ void __launch_bounds__(MG_T) kmerge(const MgArgs A)
     }
     const uint32_t tlo = b > A.before ? b - A.before : 0u, thi = min(A.n - 1u, b + A.after);
     int by = 0, bx = 0;
-    if (A.pos) {
+    const int16_t *fpos = nullptr; // FIELD: the entry of the tile's cell in frame 0's field; frame f's is A.cells entries on
+    if constexpr (FIELD) {
+        fpos = A.pos + 2u * (static_cast<size_t>(static_cast<uint32_t>(y0) / A.cell_h) * A.cells_x + static_cast<uint32_t>(x0) / A.cell_w);
+        by = fpos[2u * (static_cast<size_t>(b) * A.cells)];
+        bx = fpos[2u * (static_cast<size_t>(b) * A.cells) + 1u];
+    } else if (A.pos) {
         by = A.pos[2u * b];
         bx = A.pos[2u * b + 1u];
     }
@@ -147,7 +161,10 @@ __global__ void __launch_bounds__(MG_T) kmerge(const MgArgs A)
         if (t == b)
             continue;
         int sy = 0, sx = 0;
-        if (A.pos) {
+        if constexpr (FIELD) {
+            sy = (static_cast<int>(fpos[2u * (static_cast<size_t>(t) * A.cells)]) - by) & ~1;
+            sx = (static_cast<int>(fpos[2u * (static_cast<size_t>(t) * A.cells) + 1u]) - bx) & ~1;
+        } else if (A.pos) {
             sy = (static_cast<int>(A.pos[2u * t]) - by) & ~1;
             sx = (static_cast<int>(A.pos[2u * t + 1u]) - bx) & ~1;
         }
@@ -258,6 +275,16 @@ __global__ void __launch_bounds__(MG_T) kmerge(const MgArgs A)
     }
 }
 
+static void merge_launch(const MgCellArgs &A, uint32_t support, hipStream_t st)
+{
+    const dim3 grid(A.per * MG_XCDS), block(MG_T);
+    const size_t dyn = static_cast<size_t>(A.L) * 8u;
+    if (support)
+        hipLaunchKernelGGL((MG_NT ? kmerge<1, true, true, MgCellArgs> : kmerge<1, false, true, MgCellArgs>), grid, block, dyn, st, A);
+    else
+        hipLaunchKernelGGL((MG_NT ? kmerge<0, true, true, MgCellArgs> : kmerge<0, false, true, MgCellArgs>), grid, block, dyn, st, A);
+}
+
 static void merge_launch(const MgArgs &A, uint32_t support, hipStream_t st)
 {
     const dim3 grid(A.per * MG_XCDS), block(MG_T);
@@ -272,50 +299,57 @@ static void merge_launch(const MgArgs &A, uint32_t support, hipStream_t st)
 
 using namespace mcraw;
 
-extern "C" int mcraw_merge_batch(mcraw_ctx *c, const mcraw_merge *m, const uint16_t *in, size_t in_pitch, size_t in_frame_stride,
-                                 int width, int height, int n, uint16_t *out, size_t out_pitch, size_t out_frame_stride,
-                                 void *stream)
+// Both entry points: the checks on what they share, then the launches.  cells: NULL (mcraw_merge_batch), or the field's grid.
+static int merge_entry(const char *fn, mcraw_ctx *c, const mcraw_merge *m, const mcraw_cells *cells, const uint16_t *in, size_t in_pitch,
+                       size_t in_frame_stride, int width, int height, int n, uint16_t *out, size_t out_pitch, size_t out_frame_stride, void *stream)
 {
     if (!c || !m || n < 0)
-        return reject(__func__, "bad arguments");
+        return reject(fn, "bad arguments");
     if (n == 0 || m->count == 0u)
         return 0;
     if (!in || !out)
-        return reject(__func__, "in or out missing");
+        return reject(fn, "in or out missing");
     if ((reinterpret_cast<uintptr_t>(in) & 1u) || (reinterpret_cast<uintptr_t>(out) & 1u) || (reinterpret_cast<uintptr_t>(m->pos) & 1u))
-        return reject(__func__, "in / out / pos not aligned to 2 bytes");
+        return reject(fn, "in / out / pos not aligned to 2 bytes");
     const MosaicBatch I(in, in_pitch, in_frame_stride, static_cast<size_t>(n), width, height);
     const MosaicBatch O(out, out_pitch, out_frame_stride, static_cast<size_t>(m->count), width, height);
     if (const char *why = check(I, O))
-        return reject(__func__, why);
+        return reject(fn, why);
     if (m->before > 15u || m->after > 15u || m->before + m->after > 15u)
-        return reject(__func__, "before + after must be 0 .. 15");
+        return reject(fn, "before + after must be 0 .. 15");
     if (m->first > static_cast<uint32_t>(n) || m->count > static_cast<uint32_t>(n) - m->first)
-        return reject(__func__, "first + count must not exceed n");
+        return reject(fn, "first + count must not exceed n");
     if (m->support > 1u)
-        return reject(__func__, "support must be 0 or 1");
+        return reject(fn, "support must be 0 or 1");
     if (m->amount < 1u || m->amount > 256u)
-        return reject(__func__, "amount must be 1 .. 256");
+        return reject(fn, "amount must be 1 .. 256");
     if (m->lut_log2 < 6u || m->lut_log2 > 10u)
-        return reject(__func__, "lut_log2 must be 6 .. 10");
+        return reject(fn, "lut_log2 must be 6 .. 10");
     if (m->shift > 15u)
-        return reject(__func__, "shift must be 0 .. 15");
+        return reject(fn, "shift must be 0 .. 15");
     if (m->nluts != 1u && m->nluts != static_cast<uint32_t>(n))
-        return reject(__func__, "nluts must be 1 or n");
+        return reject(fn, "nluts must be 1 or n");
     if (m->reserved != 0u)
-        return reject(__func__, "reserved must be 0");
+        return reject(fn, "reserved must be 0");
     if (!m->lut || (reinterpret_cast<uintptr_t>(m->lut) & 15u))
-        return reject(__func__, "lut missing or not 16-byte aligned");
+        return reject(fn, "lut missing or not 16-byte aligned");
     if (overlap(I, O))
-        return reject(__func__, "in and out overlap (every output reads several frames: there is no in-place form)");
+        return reject(fn, "in and out overlap (every output reads several frames: there is no in-place form)");
+    if (cells) {
+        if (m->pos)
+            return reject(fn, "m->pos must be NULL: the positions are the cells'");
+        if (const char *why = check_merge_cells(O, static_cast<size_t>(n), width, height, cells->cell_h, cells->cell_w, cells->cells_y,
+                                                cells->cells_x, cells->reserved, cells->pos))
+            return reject(fn, why);
+    }
 
     std::lock_guard<std::mutex> lk(c->mu);
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = stream_of(c, stream);
-    MgArgs A{};
+    MgCellArgs A{};
     A.in = in;
     A.lut = m->lut;
-    A.pos = m->pos;
+    A.pos = cells ? cells->pos : m->pos;
     A.ipitch = in_pitch;
     A.ifstride = in_frame_stride;
     A.opitch = out_pitch;
@@ -333,14 +367,37 @@ extern "C" int mcraw_merge_batch(mcraw_ctx *c, const mcraw_merge *m, const uint1
     A.perframe = m->nluts != 1u ? 1u : 0u;
     A.invec = I.on_grid();
     A.outvec = O.on_grid();
+    if (cells) {
+        A.cell_h = cells->cell_h, A.cell_w = cells->cell_w, A.cells_x = cells->cells_x;
+        A.cells = cells->cells_y * cells->cells_x;
+    }
     const uint32_t piece = std::max(1u, std::min(65535u, 0x40000000u / A.tiles)); // outputs per launch: below 2^30 workgroups
     for (uint32_t j0 = 0; j0 < m->count; j0 += piece) {
         A.nout = std::min(piece, m->count - j0);
         A.first = m->first + j0;
         A.out = out + static_cast<size_t>(j0) * out_frame_stride;
         A.per = (A.tiles * A.nout + MG_XCDS - 1u) / MG_XCDS;
-        merge_launch(A, m->support, st);
+        if (cells)
+            merge_launch(A, m->support, st);
+        else
+            merge_launch(static_cast<const MgArgs &>(A), m->support, st);
         HIP_TRY(hipGetLastError());
     }
     return 0;
+}
+
+extern "C" int mcraw_merge_batch(mcraw_ctx *c, const mcraw_merge *m, const uint16_t *in, size_t in_pitch, size_t in_frame_stride,
+                                 int width, int height, int n, uint16_t *out, size_t out_pitch, size_t out_frame_stride,
+                                 void *stream)
+{
+    return merge_entry(__func__, c, m, nullptr, in, in_pitch, in_frame_stride, width, height, n, out, out_pitch, out_frame_stride, stream);
+}
+
+extern "C" int mcraw_merge_cells_batch(mcraw_ctx *c, const mcraw_merge *m, const mcraw_cells *cells, const uint16_t *in, size_t in_pitch,
+                                       size_t in_frame_stride, int width, int height, int n, uint16_t *out, size_t out_pitch,
+                                       size_t out_frame_stride, void *stream)
+{
+    if (!cells)
+        return reject(__func__, "cells missing");
+    return merge_entry(__func__, c, m, cells, in, in_pitch, in_frame_stride, width, height, n, out, out_pitch, out_frame_stride, stream);
 }

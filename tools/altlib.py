@@ -73,6 +73,8 @@ class AltLib:
         self.lib.mcraw_stats_batch.argtypes = [C.c_void_p, C.POINTER(M.Stats)] + _MOSAIC_IN + [C.c_void_p, C.c_size_t, C.c_void_p]
         if hasattr(self.lib, "mcraw_align_batch"):  # (a build of a commit in front of the stage has none)
             self.lib.mcraw_align_batch.argtypes = [C.c_void_p, C.POINTER(M.Align)] + _MOSAIC_IN + [C.c_void_p]
+        if hasattr(self.lib, "mcraw_merge_cells_batch"):  # (likewise)
+            self.lib.mcraw_merge_cells_batch.argtypes = [C.c_void_p, C.POINTER(M.Merge), C.POINTER(M.Cells)] + _MOSAIC_IN + _MOSAIC_OUT + [C.c_void_p]
         self.lib.mcraw_demosaic_batch.argtypes = [C.c_void_p, C.POINTER(M.RgbParams)] + _DEMOSAIC
         self.lib.mcraw_demosaic_display_batch.argtypes = [C.c_void_p, C.POINTER(M.RgbParams), C.POINTER(M.Display)] + _DEMOSAIC
         self.lib.mcraw_demosaic_yuv_batch.argtypes = [C.c_void_p, C.POINTER(M.RgbParams), C.POINTER(M.Yuv)] + _DEMOSAIC
@@ -115,6 +117,19 @@ class AltLib:
         s.lut_log2, s.shift, s.nluts, s.reserved = int(lut.shape[-1]).bit_length() - 1, shift, 1, 0
         s.lut, s.pos = lut.data_ptr(), None
         self._mosaic_call("mcraw_merge_batch", s, mos, out, stream)
+
+    def merge_cells(self, mos, out, stream, lut, shift, T, support, field, cell, amount=256):
+        """mcraw_merge_cells_batch: field, a contiguous (N, Cy, Cx, 2) int16 tensor for cells of cell = (cell_h, cell_w)."""
+        s = M.Merge()
+        s.before, s.after, s.first, s.count, s.support, s.amount = T, T, 0, int(mos.shape[0]), support, amount
+        s.lut_log2, s.shift, s.nluts, s.reserved = int(lut.shape[-1]).bit_length() - 1, shift, 1, 0
+        s.lut, s.pos = lut.data_ptr(), None
+        g = M.Cells()
+        g.cell_h, g.cell_w, g.cells_y, g.cells_x, g.reserved, g.pos = cell[0], cell[1], int(field.shape[1]), int(field.shape[2]), 0, field.data_ptr()
+        n, h, w = mos.shape
+        rc = self.lib.mcraw_merge_cells_batch(self.h, C.byref(s), C.byref(g), C.c_void_p(mos.data_ptr()), w, h * w, w, h, n,
+                                              C.c_void_p(out.data_ptr()), w, h * w, C.c_void_p(stream.cuda_stream))
+        assert rc == 0, self.lib.mcraw_last_error().decode()
 
     def align(self, mos, pos, work, stream, levels, radius, black, ref=-1):
         """Positions into `pos` (a contiguous (N, 2) int16 tensor); work: a uint8 tensor of mcraw_align_work_bytes bytes."""

@@ -1,14 +1,14 @@
 #!/usr/bin/env python3
 """Resource report of the demosaic kernels (csrc/mcraw_rgb.hip), of the lens-shading kernel (csrc/mcraw_shade.hip), of the
 statistics kernels (csrc/mcraw_stats.hip), of the defective-pixel kernels (csrc/mcraw_fixpix.hip), of the denoising kernel
-(csrc/mcraw_denoise.hip), of the temporal merge (csrc/mcraw_merge.hip) and of the shift estimate (csrc/mcraw_align.hip): compiles the files for gfx950 with -Rpass-analysis=kernel-resource-usage (no GPU needed) and prints
+(csrc/mcraw_denoise.hip), of the temporal merge (csrc/mcraw_merge.hip), of the shift estimate (csrc/mcraw_align.hip) and of the position field (csrc/mcraw_cells.hip and the merge's kmerge<..., field> instances): compiles the files for gfx950 with -Rpass-analysis=kernel-resource-usage (no GPU needed) and prints
 one line per instance in the format of profiles/rgb_resources.txt / display_resources.txt / yuv_resources.txt /
 shade_resources.txt / stats_resources.txt / fixpix_resources.txt / denoise_resources.txt / merge_resources.txt / align_resources.txt /
-area_resources.txt (csrc/mcraw_area.hip: krgb_area and karea_tab) /
+cells_resources.txt (kcells_* and kmerge<..., field>) / area_resources.txt (csrc/mcraw_area.hip: krgb_area and karea_tab) /
 resample_resources.txt (csrc/mcraw_resample.hip: krgb_resample and kres_tab).
 
     python tools/rgb_resources.py            # every instance
-    python tools/rgb_resources.py --check    # the figures in the eleven committed files must equal the compiler's; exit 1 if not
+    python tools/rgb_resources.py --check    # the figures in the twelve committed files must equal the compiler's; exit 1 if not
 """
 import os
 import re
@@ -31,7 +31,9 @@ FIXPIX_NAME = r"Function Name: _ZN5mcraw\d+(kfixpix_init|kfixpix_list|kfixpix)(?
 DENOISE_FILE = "denoise_resources.txt"
 DENOISE_NAME = r"Function Name: _ZN5mcraw\d+(kdenoise)ILi([12])ELb([01])EEEv"  # kdenoise<RADIUS, NT>
 MERGE_FILE = "merge_resources.txt"
-MERGE_NAME = r"Function Name: _ZN5mcraw\d+(kmerge)ILi([01])ELb([01])EEEv"  # kmerge<SUPPORT, NT>
+MERGE_NAME = r"Function Name: _ZN5mcraw\d+(kmerge)ILi([01])ELb([01])ELb([01])ENS_\d+Mg(?:Cell)?ArgsEEEvT2_"  # kmerge<SUPPORT, NT, FIELD, ARGS>: FIELD 0, the shifts per frame (merge_resources.txt); 1, per cell (cells_resources.txt)
+CELLS_FILE = "cells_resources.txt"
+CELLS_NAME = r"Function Name: _ZN5mcraw\d+(kcells_[a-z]+)(?:ILi([01])EEEv|E)"  # kcells_sad<R = 1: nine candidates in registers; 0: a loop>, the others
 ALIGN_FILE = "align_resources.txt"
 ALIGN_NAME = r"Function Name: _ZN5mcraw\d+(kalign_[a-z]+)(?:ILi([01])EEEv|E)"  # kalign_sad<R = 1: nine candidates in registers; 0: a loop>, the others
 AREA_FILE = "area_resources.txt"
@@ -53,7 +55,11 @@ def _label(m):
     if m.group(1) == "kdenoise":
         return "kdenoise<R=%s,%s>" % (m.group(2), "stream" if m.group(3) == "1" else "plain")
     if m.group(1) == "kmerge":
-        return "kmerge<S=%s,%s>" % (m.group(2), "stream" if m.group(3) == "1" else "plain")
+        return "kmerge<S=%s,%s%s>" % (m.group(2), "stream" if m.group(3) == "1" else "plain", ",field" if m.group(4) == "1" else "")
+    if m.group(1) == "kcells_sad":
+        return "kcells_sad<%s>" % ("refine" if m.group(2) == "1" else "coarse")
+    if m.group(1).startswith("kcells_"):
+        return m.group(1)
     if m.group(1) == "kalign_sad":
         return "kalign_sad<%s>" % ("refine" if m.group(2) == "1" else "coarse")
     if m.group(1).startswith("kalign_"):
@@ -107,18 +113,20 @@ def _check(files, rep, prefix):
 def main():
     rep, shade, stats = report(), report("mcraw_shade.hip", SHADE_NAME), report("mcraw_stats.hip", STATS_NAME)
     fixpix, denoise = report("mcraw_fixpix.hip", FIXPIX_NAME), report("mcraw_denoise.hip", DENOISE_NAME)
-    merge, align = report("mcraw_merge.hip", MERGE_NAME), report("mcraw_align.hip", ALIGN_NAME)
+    both, align = report("mcraw_merge.hip", MERGE_NAME), report("mcraw_align.hip", ALIGN_NAME)
+    merge = {k: v for k, v in both.items() if not k.endswith(",field>")}
     area = report("mcraw_area.hip", AREA_NAME)
+    cells = dict(report("mcraw_cells.hip", CELLS_NAME), **{k: v for k, v in both.items() if k.endswith(",field>")})
     resample = report("mcraw_resample.hip", RESAMPLE_NAME)
     if "--check" not in sys.argv:
         for line in list(rep.values()) + list(shade.values()) + list(stats.values()) + list(fixpix.values()) + list(denoise.values()) + \
-                list(merge.values()) + list(align.values()) + list(area.values()) + list(resample.values()):
+                list(merge.values()) + list(align.values()) + list(area.values()) + list(resample.values()) + list(cells.values()):
             print(line)
         return 0
     return _check(FILES, rep, "krgb_") | _check((SHADE_FILE,), shade, "kshade") | _check((STATS_FILE,), stats, "kstats") | \
         _check((FIXPIX_FILE,), fixpix, "kfixpix") | _check((DENOISE_FILE,), denoise, "kdenoise") | _check((MERGE_FILE,), merge, "kmerge") | \
         _check((ALIGN_FILE,), align, "kalign") | _check((AREA_FILE,), area, ("krgb_area", "karea_tab")) | \
-        _check((RESAMPLE_FILE,), resample, ("krgb_resample", "kres_tab"))
+        _check((RESAMPLE_FILE,), resample, ("krgb_resample", "kres_tab")) | _check((CELLS_FILE,), cells, ("kcells_", "kmerge<"))
 
 
 if __name__ == "__main__":
