@@ -549,6 +549,56 @@ int mcraw_demosaic_resample_batch(mcraw_ctx *ctx, const mcraw_rgb *p, const mcra
                                   size_t in_pitch, size_t in_frame_stride, int width, int height, int n, void *work,
                                   size_t work_bytes, void *out, size_t out_bytes, void *stream);
 
+/* ---- uint16 mosaics -> the MHC image sampled along one affine map per frame: the stabilisation warp ----------------
+ *
+ * out_h x out_w pixels per frame, each the full-resolution Malvar-He-Cutler image of its mosaic sampled at an affine position:
+ * translation to 1/256 sample, roll up to about 14 degrees, zoom 0.75 .. 1.25.  Output family: `d` and `y` NULL: the float
+ * family; `d`: the display family; `y`: the YUV family; both: rejected.  p->algo must be MCRAW_RGB_WARP, which every other
+ * entry point keeps rejecting.
+ * A map is six int32 in HOST memory, {ayy, ayx, ty, axy, axx, tx}: the linear part in 1/65536, the translation in 1/256
+ * sample; `maps` holds nmaps of them, 1 (one map for the batch) or n, read before the call returns, like `colors`.  Output
+ * pixel (i, k) of frame f reads the position (64-bit, arithmetic shifts; integer coordinates are sample centres)
+ *   Y = ty + ((ayy i + ayx k + 128) >> 8)      iy = Y >> 8,  py = Y & 255
+ *   X = tx + ((axy i + axx k + 128) >> 8)      ix = X >> 8,  px = X & 255
+ * so that {65536, 0, 0, 0, 65536, 0} reads sample (i, k).  One table of 256 phases x 4 taps, at j = -1 .. 2 about iy (or ix),
+ * serves both axes:
+ *   linear: w(p) = (0, 16 (256 - p), 16 p, 0)
+ *   cubic:  a = 4 |256 j - p|; f(a), F = sum_j f, w = floor((4096 f + F / 2) / F) and the residual rule are those of
+ *           mcraw_demosaic_resample_batch (Catmull-Rom): the residual goes to the tap of smallest distance, half each to two
+ *           equally near.  F = 2 * 1024^3 for every phase, sum w = 4096, sum |w| <= 5120, w >= -303, w(0) = (0, 4096, 0, 0),
+ *           w(128) = (-256, 2304, 2304, -256), and w(p) mirrors w(256 - p).
+ * e_c(y, x): MCRAW_RGB_MHC's integer estimates of the WHOLE frame, in 1/16 DN, |e| < 2^22; outside the frame
+ * e_c(y, x) = e_c(reflect101(y, height), reflect101(x, width)).  Horizontally first, with the resample's two roundings:
+ *   t_c(r, k) = (sum_j w(px)[j] e_c(r, ix - 1 + j) + 2048) >> 12      r = iy - 1 .. iy + 2; exact sum, arithmetic shift
+ *   E_c(i, k) = (sum_j w(py)[j] t_c(iy - 1 + j, k) + 2048) >> 12      likewise; exact as float
+ *   host, f32: k[c] = (gain[c] * inv) * 0.0625f                       as MCRAW_RGB_MHC
+ * (the sums through v = 256 vh + vl, as the resample).  From E_c and k[c] on everything is the family's own entry point, with
+ * Ho = out_h, Wo = out_w.  With the identity linear part and a translation of whole samples (256 a, 256 b) the result is
+ * MCRAW_RGB_MHC's output cut at (a, b), bit for bit, in every family and for both filters; a flat frame comes out flat and
+ * greys stay neutral.  The filter is not stretched: zoom-out (a linear part above 65536, down to 0.75 of the size) aliases
+ * slightly.
+ * Accepted: width, height even and >= 8; out_w, out_h 1 .. 65536, both even for the YUV family; filter MCRAW_FILTER_LINEAR or
+ * MCRAW_FILTER_CUBIC; nmaps 1 or n; per map |ayy - 65536|, |axx - 65536|, |ayx|, |axy| <= 16384, and the four corner pixels
+ * (0, 0), (0, Wo - 1), (Ho - 1, 0), (Ho - 1, Wo - 1) with 0 <= Y <= 256 (height - 1) and 0 <= X <= 256 (width - 1): Y and X are
+ * monotone in i and k, so the corners bound every pixel, taps and MHC's halo leave the frame by at most 4 samples and one
+ * reflection suffices.  in, in_pitch, in_frame_stride, colors, out and out_bytes follow the family's entry point.
+ * Rejected (returns < 0, mcraw_last_error says why, starting with "mcraw_demosaic_warp_batch: ", nothing is written; a
+ * message about a map names the frame of the first bad one): everything the family's own entry point rejects; a NULL `wp` or
+ * `maps`; a p->algo other than MCRAW_RGB_WARP; both `d` and `y`; a frame under 8 x 8; a non-zero `reserved`; an unknown
+ * filter; a size outside 1 .. 65536; a linear part or a corner outside the rules above; nmaps other than 1 or n.  n == 0 is
+ * a no-op.  The call needs no scratch, takes no decode serial, leaves the decode slots, mcraw_ctx_errors and the context's
+ * stage alone, and has no kernel id of its own. */
+#define MCRAW_RGB_WARP 5       /* valid in mcraw_demosaic_warp_batch only */
+typedef struct mcraw_warp {
+    uint32_t out_w, out_h;  /* Wo, Ho                                               */
+    uint32_t filter;        /* MCRAW_FILTER_*                                       */
+    uint32_t reserved;      /* must be 0                                            */
+} mcraw_warp;               /* sizeof 16; out_h 4, filter 8, reserved 12 */
+int mcraw_demosaic_warp_batch(mcraw_ctx *ctx, const mcraw_rgb *p, const mcraw_warp *wp, const mcraw_display *d,
+                              const mcraw_yuv *y, const mcraw_rgb_color *colors, int ncolors, const int32_t *maps, int nmaps,
+                              const uint16_t *in, size_t in_pitch, size_t in_frame_stride, int width, int height, int n,
+                              void *out, size_t out_bytes, void *stream);
+
 /* ---- uint16 mosaics -> uint16 mosaics with a lens-shading gain map applied ----------------------------------------
  *
  * Multiplies what `n` uint16 mosaics of width x height hold above their black level by a per-pixel gain that is bilinearly

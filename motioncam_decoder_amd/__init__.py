@@ -20,7 +20,7 @@ __all__ = ["lib_path", "load", "Context", "Pool", "Frame", "EncFrame", "FloatOut
            "shading_map", "Stats", "STATS_ACCUMULATE", "FrameStats", "stats_white_balance", "stats_percentile",
            "stats_clipped", "FixPix", "FIXPIX_HOT", "FIXPIX_COLD", "pack_pixels", "Denoise", "noise_lut", "Merge", "Align",
            "AlignCells", "Cells", "cell_grid", "align_window", "fit_crop", "Area", "RGB_AREA", "Resample", "RGB_RESAMPLE",
-           "FILTER_LINEAR", "FILTER_CUBIC"]
+           "FILTER_LINEAR", "FILTER_CUBIC", "Warp", "RGB_WARP", "quantize_affine", "fit_affine", "stabilize"]
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 
@@ -50,7 +50,7 @@ ABI_SYMBOLS = [
     "mcraw_demosaic_batch", "mcraw_demosaic_display_batch", "mcraw_demosaic_yuv_batch", "mcraw_shade_batch",
     "mcraw_stats_batch", "mcraw_stats_record_bytes", "mcraw_fixpix_batch", "mcraw_denoise_batch",
     "mcraw_merge_batch", "mcraw_align_batch", "mcraw_align_work_bytes", "mcraw_demosaic_area_batch", "mcraw_area_work_bytes",
-    "mcraw_demosaic_resample_batch", "mcraw_resample_work_bytes",
+    "mcraw_demosaic_resample_batch", "mcraw_resample_work_bytes", "mcraw_demosaic_warp_batch",
     "mcraw_align_cells_batch", "mcraw_align_cells_work_bytes", "mcraw_merge_cells_batch",
 ]
 
@@ -130,8 +130,9 @@ def float_out(dtype, white, layout="planes", black=(0, 0, 0, 0), clip=False, pla
 RGB_MHC, RGB_BIN2 = 1, 2
 RGB_AREA = 3  # mcraw_demosaic_area_batch only
 RGB_RESAMPLE = 4  # mcraw_demosaic_resample_batch only
+RGB_WARP = 5  # mcraw_demosaic_warp_batch only
 FILTER_LINEAR, FILTER_CUBIC = 0, 1
-_RGB_ALGOS = {"mhc": RGB_MHC, "bin2": RGB_BIN2, "area": RGB_AREA, "resample": RGB_RESAMPLE}
+_RGB_ALGOS = {"mhc": RGB_MHC, "bin2": RGB_BIN2, "area": RGB_AREA, "resample": RGB_RESAMPLE, "warp": RGB_WARP}
 _FILTERS = {"linear": FILTER_LINEAR, "cubic": FILTER_CUBIC}
 _CFA_CODES = {"rggb": 0, "bggr": 1, "grbg": 2, "gbrg": 3}
 
@@ -159,6 +160,11 @@ class Resample(C.Structure):
                 ("out_h", C.c_uint32), ("filter", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class Warp(C.Structure):
+    """struct mcraw_warp (include/mcraw_hip.h): the output size and the filter of mcraw_demosaic_warp_batch."""
+    _fields_ = [("out_w", C.c_uint32), ("out_h", C.c_uint32), ("filter", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 # The scaled algos of the demosaic methods (size=, crop=): algo -> (the window struct, the library's work-bytes function, its entry
 # point for the three families, the geometry rule as the ValueError states it).
 _SCALED = {
@@ -171,8 +177,8 @@ _SCALED = {
 # What the demosaic methods know in front of their output (Context._demosaic_front).  mos: the mosaics (N, H, W) behind the
 # optional stages; single: the caller's was (H, W); n, h, w: their shape; src: _strided's triple (None for no frames); ho, wo: the
 # output size; key: the cfa's; area: the (y0, x0, h, w) crop of a scaled algo (None for the others); filt: the MCRAW_FILTER_* code
-# of algo "resample" (None for the others).
-_Front = collections.namedtuple("_Front", "mos single n h w src ho wo key area filt")
+# of algo "resample" and "warp" (None for the others); maps: the int32 (nmaps, 6) host array of algo "warp" (None for the others).
+_Front = collections.namedtuple("_Front", "mos single n h w src ho wo key area filt maps", defaults=(None,))
 
 
 def fit_crop(height, width, Ho, Wo, algo="area"):
@@ -202,6 +208,130 @@ def fit_crop(height, width, Ho, Wo, algo="area"):
         raise ValueError("fit_crop: a %d x %d crop of a %d x %d mosaic onto %d x %d is outside 1 .. 16 quads per pixel"
                          % (h, w, height, width, Ho, Wo))
     return ((height - h) // 4 * 2, (width - w) // 4 * 2, h, w)
+
+
+_WARP_ONE, _WARP_DEV = 65536, 16384  # the linear part's unit and its largest deviation from the identity (include/mcraw_hip.h)
+
+
+def quantize_affine(affine):
+    """Float maps (2, 3) or (N, 2, 3), rows [[ayy, ayx, ty], [axy, axx, tx]] in samples, as the int32 maps (6,) or (N, 6) that
+    mcraw_demosaic_warp_batch takes, {ayy, ayx, ty, axy, axx, tx}: floor(v * 65536 + 0.5) for the linear part,
+    floor(v * 256 + 0.5) for the translation (host only, float64).  Raises ValueError for another shape and for values that
+    are not finite or leave int32."""
+    import numpy as np
+    a = np.asarray(affine, dtype=np.float64)
+    if a.shape[-2:] != (2, 3) or a.ndim not in (2, 3):
+        raise ValueError("quantize_affine: maps must be (2, 3) or (N, 2, 3), not %r" % (a.shape,))
+    if not np.isfinite(a).all():
+        raise ValueError("quantize_affine: a map entry is not finite")
+    q = np.floor(a * np.array([65536.0, 65536.0, 256.0]) + 0.5)
+    if q.size and (q.min() < -2 ** 31 or q.max() > 2 ** 31 - 1):
+        raise ValueError("quantize_affine: a map entry leaves int32")
+    return np.ascontiguousarray(q.astype(np.int32).reshape(a.shape[:-2] + (6,)))
+
+
+def _affine_maps(fn, affine, n):
+    """affine= of the demosaic methods as the contiguous int32 host array (nmaps, 6), nmaps 1 or n.  A tensor on the device is
+    brought to the host, which synchronises."""
+    import numpy as np
+    if hasattr(affine, "detach") and hasattr(affine, "cpu"):  # a torch tensor, wherever it lives
+        affine = affine.detach().cpu().numpy()
+    a = np.asarray(affine)
+    if a.dtype.kind in "iu":
+        if a.dtype != np.int32 or a.ndim not in (1, 2) or a.shape[-1] != 6:
+            raise ValueError("%s: integer maps must be int32 (6,) or (N, 6), not %s %r" % (fn, a.dtype, a.shape))
+        maps = np.ascontiguousarray(a.reshape(-1, 6))
+    elif a.dtype.kind == "f":
+        try:
+            maps = quantize_affine(a).reshape(-1, 6)
+        except ValueError as e:
+            raise ValueError("%s: affine: %s" % (fn, e)) from None
+    else:
+        raise ValueError("%s: affine must be int32 (6,) / (N, 6) or float (2, 3) / (N, 2, 3)" % fn)
+    if n and maps.shape[0] not in (1, n):
+        raise ValueError("%s: affine holds %d maps for %d frames (one for all, or one each)" % (fn, maps.shape[0], n))
+    return maps
+
+
+def fit_affine(pos, height, width, cell=None):
+    """The displacement model of a clip, float64 (N, 2, 3): D_t(y, x) = D[t, :, :2] @ (y, x) + D[t, :, 2] ~ pos_t at (y, x), rows
+    (y, x) as everywhere.  pos (N, 2), as Context.align returns it: a zero linear part and the translation.  pos (N, Cy, Cx, 2)
+    with cell=(cell_h, cell_w), as Context.align_cells returns it for (Cy, Cx) = cell_grid(height, width, cell): the least-
+    squares affine over the cell centres (i * cell_h + cell_h / 2, j * cell_w + cell_w / 2); a grid with a single row or column
+    of cells leaves that axis's slope 0.  Host only (a tensor is brought to the host); stabilize() turns the model into maps."""
+    import numpy as np
+    if hasattr(pos, "detach") and hasattr(pos, "cpu"):
+        pos = pos.detach().cpu().numpy()
+    p = np.asarray(pos, dtype=np.float64)
+    if p.ndim == 2 and p.shape[1] == 2 and cell is None:
+        D = np.zeros((p.shape[0], 2, 3))
+        D[:, :, 2] = p
+        return D
+    if p.ndim != 4 or p.shape[3] != 2 or cell is None:
+        raise ValueError("fit_affine: pos must be (N, 2), or (N, Cy, Cx, 2) with cell=(cell_h, cell_w), not %r" % (p.shape,))
+    if tuple(p.shape[1:3]) != cell_grid(height, width, cell):
+        raise ValueError("fit_affine: a %r field is not the cell_grid of %d x %d frames with cells %r" % (tuple(p.shape[1:3]), height, width, tuple(cell)))
+    n, cy, cx = p.shape[:3]
+    yc = np.arange(cy) * float(cell[0]) + cell[0] / 2.0
+    xc = np.arange(cx) * float(cell[1]) + cell[1] / 2.0
+    Y, X = np.meshgrid(yc, xc, indexing="ij")
+    cols = [Y.ravel() - Y.mean() if cy > 1 else None, X.ravel() - X.mean() if cx > 1 else None]
+    A = np.stack([c for c in cols if c is not None] + [np.ones(cy * cx)], axis=1)   # centred: well conditioned
+    sol = np.linalg.lstsq(A, p.reshape(n, cy * cx, 2).transpose(1, 0, 2).reshape(cy * cx, n * 2), rcond=None)[0].reshape(A.shape[1], n, 2)
+    D = np.zeros((n, 2, 3))
+    k = 0
+    for axis, c in enumerate(cols):
+        if c is not None:
+            D[:, :, axis] = sol[k]
+            k += 1
+    D[:, :, 2] = sol[k] - D[:, :, 0] * Y.mean() - D[:, :, 1] * X.mean()
+    return D
+
+
+def stabilize(D, height, width, size, window=0, limit=True):
+    """The maps that stabilise a clip, int32 (N, 6) for affine= of the demosaic methods, from its displacement model D (N, 2, 3)
+    (fit_affine).  The sign follows mcraw_merge_batch's pos: in[t][q + pos[t] - pos[b]] looks like in[b][q], so
+    out_t(q) = in[t][q + D_t(q) - S_t(q)], with S_t the coefficient-wise mean of D over frames t - window .. t + window (clipped
+    to the batch): the smooth path that stays in the result.  window=0: S = 0, a lock onto the frame of position 0.  Output
+    pixel (i, k) of size = (Ho, Wo) is q = (i + (height - Ho) // 2, k + (width - Wo) // 2): the centred window.  limit=True
+    clamps each frame's translation per axis so that the four corners of the output read inside the frame, as the library
+    demands, and raises ValueError where no translation can do that (the size is too large for the roll and zoom) or where the
+    linear part leaves the library's bounds (|a - identity| <= 1/4); limit=False returns the maps as they are.  Host only."""
+    import numpy as np
+    D = np.asarray(D, dtype=np.float64)
+    if D.ndim != 3 or D.shape[1:] != (2, 3):
+        raise ValueError("stabilize: D must be (N, 2, 3), not %r" % (D.shape,))
+    try:
+        ho, wo = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError("stabilize: size must be (Ho, Wo)") from None
+    height, width, window = int(height), int(width), int(window)
+    if not (1 <= ho <= height and 1 <= wo <= width) or window < 0:
+        raise ValueError("stabilize: size %r must fit the %d x %d frame, and window be >= 0" % (size, height, width))
+    n = D.shape[0]
+    S = np.zeros_like(D)
+    if window:
+        for t in range(n):
+            S[t] = D[max(0, t - window):min(n, t + window + 1)].mean(axis=0)
+    R = D - S
+    off = np.array([(height - ho) // 2, (width - wo) // 2], dtype=np.float64)
+    M = R[:, :, :2] + np.eye(2)
+    A = np.concatenate([M, (M @ off + R[:, :, 2])[:, :, None]], axis=2)
+    maps = quantize_affine(A).reshape(n, 6)
+    if not limit:
+        return maps
+    for t in range(n):
+        m = maps[t].astype(np.int64)
+        if max(abs(m[0] - _WARP_ONE), abs(m[4] - _WARP_ONE), abs(m[1]), abs(m[3])) > _WARP_DEV:
+            raise ValueError("stabilize: the linear part of frame %d leaves the warp's bounds (|a - identity| <= 1/4)" % t)
+        for base, side, name in ((0, height, "rows"), (3, width, "columns")):
+            c = [(m[base] * i + m[base + 1] * k + 128) >> 8 for i in (0, ho - 1) for k in (0, wo - 1)]
+            lo, hi = -min(c), 256 * (side - 1) - max(c)
+            if lo > hi:
+                raise ValueError("stabilize: frame %d: a %d x %d output cannot stay inside the frame's %s under this roll and zoom"
+                                 % (t, ho, wo, name))
+            maps[t, base + 2] = min(max(int(m[base + 2]), lo), hi)
+    return maps
 
 
 # display-ready integer RGB through a transfer-curve LUT (mcraw_demosaic_display_batch)
@@ -921,6 +1051,10 @@ def load():
     lib.mcraw_demosaic_resample_batch.argtypes = [C.c_void_p, C.POINTER(RgbParams), C.POINTER(Resample), C.POINTER(Display),
                                                   C.POINTER(Yuv), C.POINTER(RgbColor), C.c_int, C.c_void_p, C.c_size_t, C.c_size_t,
                                                   C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.mcraw_demosaic_warp_batch.restype = C.c_int
+    lib.mcraw_demosaic_warp_batch.argtypes = [C.c_void_p, C.POINTER(RgbParams), C.POINTER(Warp), C.POINTER(Display), C.POINTER(Yuv),
+                                              C.POINTER(RgbColor), C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_size_t,
+                                              C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.mcraw_demosaic_area_batch.restype = C.c_int
     lib.mcraw_demosaic_area_batch.argtypes = [C.c_void_p, C.POINTER(RgbParams), C.POINTER(Area), C.POINTER(Display), C.POINTER(Yuv),
                                               C.POINTER(RgbColor), C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int,
@@ -1786,7 +1920,7 @@ class Context:
         return self.merge(scratch, lut, shift, **merge_kw)
 
     def demosaic(self, mosaic, *, algo="mhc", dtype, white, black=(0, 0, 0, 0), cfa="rggb", gain=None, matrix=None,
-                 clip=False, out=None, check=True, shading=None, defects=None, denoise=None, size=None, crop=None, filter=None):
+                 clip=False, out=None, check=True, shading=None, defects=None, denoise=None, size=None, crop=None, filter=None, affine=None):
         """uint16 mosaics resident on the context's device -> planar linear RGB, (N, 3, H, W) for algo "mhc" (Malvar-He-
         Cutler) or (N, 3, H/2, W/2) for "bin2" (one pixel per 2x2 quad), as torch.float32 / float16 / bfloat16 ("f32" /
         "f16" / "bf16").  mosaic: a CUDA uint16 tensor (N, H, W) or (H, W) whose rows are contiguous (rows and frames may
@@ -1810,11 +1944,19 @@ class Context:
         from half to twice the crop (mcraw_demosaic_resample_batch): the "mhc" image of the whole frame behind a separable
         polyphase filter, in integers; with size= the crop's own size it is "mhc" cut to the crop, bit for bit.  The crop marks
         the sample positions: taps that leave it read the frame's real pixels (a stabilisation window; align_window gives
-        one), and reflect at the frame's edges.  filter= with another algo raises ValueError."""
+        one), and reflect at the frame's edges.  filter= with another algo raises ValueError.
+        algo "warp" with size=(Ho, Wo), affine= and filter= (as "resample") samples the "mhc" image along one affine map per frame
+        (mcraw_demosaic_warp_batch): the stabilisation warp, translation to 1/256 sample, roll up to about 14 degrees, zoom 0.75 ..
+        1.25, in integers; with the identity and a translation of whole samples it is "mhc" cut there, bit for bit.  affine: an
+        int32 array or tensor (6,) or (N, 6), {ayy, ayx, ty, axy, axx, tx} as the library takes them (stabilize() makes them), or
+        a float array or tensor (2, 3) or (N, 2, 3), [[ayy, ayx, ty], [axy, axx, tx]] in samples, quantised by quantize_affine().
+        The maps are host memory: a tensor on the device is brought to the host, which synchronises.  The four corners of the
+        output must read inside the frame.  affine= with another algo, "warp" without size= or affine=, or crop= with "warp"
+        raises ValueError."""
         import torch
         code = _float_code(dtype)
         tdtype = {FLOAT_F32: torch.float32, FLOAT_F16: torch.float16, FLOAT_BF16: torch.bfloat16}[code]
-        front = self._demosaic_front("demosaic", mosaic, algo, cfa, black, defects, denoise, shading, size, crop, filter)
+        front = self._demosaic_front("demosaic", mosaic, algo, cfa, black, defects, denoise, shading, size, crop, filter, affine)
         ho, wo = front.ho, front.wo
         out = self._demosaic_out("demosaic", front, out, (3, ho, wo), tdtype)
         if front.n == 0:
@@ -1822,23 +1964,30 @@ class Context:
         return self._demosaic_call("mcraw_demosaic_batch", "demosaic", front, algo, code, FLOAT_CLIP if clip else 0, white, black,
                                    gain, matrix, out)
 
-    def _demosaic_front(self, fn, mosaic, algo, cfa, black, defects, denoise, shading, size=None, crop=None, filter=None):
+    def _demosaic_front(self, fn, mosaic, algo, cfa, black, defects, denoise, shading, size=None, crop=None, filter=None, affine=None):
         """What demosaic / demosaic_display / demosaic_yuv (`fn`) do alike in front of their output: the algo and cfa checks,
         the mosaic argument, the optional stages -- defects, then denoise, then shading, each into a scratch tensor (the
         caller's mosaic stays as it is), none for an empty batch -- and the output size (`size` for the scaled algos).  Returns a
         _Front."""
         import torch
         if algo not in _RGB_ALGOS:
-            raise ValueError("algo must be 'mhc', 'bin2', 'area' or 'resample', not %r" % (algo,))
+            raise ValueError("algo must be 'mhc', 'bin2', 'area', 'resample' or 'warp', not %r" % (algo,))
         scaled = algo in _SCALED
-        if not scaled and (size is not None or crop is not None):
+        warp = algo == "warp"
+        if affine is not None and not warp:
+            raise ValueError("%s: affine= belongs to algo='warp', not %r" % (fn, algo))
+        if warp and crop is not None:
+            raise ValueError("%s: crop= does not go with algo='warp' (the maps say where every pixel reads)" % fn)
+        if warp and (size is None or affine is None):
+            raise ValueError("%s: algo='warp' needs size=(Ho, Wo) and affine=" % fn)
+        if not scaled and not warp and (size is not None or crop is not None):
             raise ValueError("%s: size= and crop= belong to algo='area' and 'resample', not %r" % (fn, algo))
         if scaled and size is None:
             raise ValueError("%s: algo=%r needs size=(Ho, Wo)" % (fn, algo))
-        if filter is not None and algo != "resample":
+        if filter is not None and algo not in ("resample", "warp"):
             raise ValueError("%s: filter= belongs to algo='resample', not %r" % (fn, algo))
         filt = None
-        if algo == "resample":
+        if algo in ("resample", "warp"):
             filt = _FILTERS.get("cubic" if filter is None else filter)
             if filt is None:
                 raise ValueError("%s: filter must be 'cubic' or 'linear', not %r" % (fn, filter))
@@ -1861,9 +2010,17 @@ class Context:
                 raise ValueError("%s: size must be (Ho, Wo) and crop (y0, x0, h, w)" % fn) from None
             if len(area) != 4 or min(area) < 0 or ho < 1 or wo < 1 or max(area + (ho, wo)) > 65536:
                 raise ValueError("%s: size must be (Ho, Wo) and crop (y0, x0, h, w), all 0 .. 65536, not %r and %r" % (fn, size, crop))
+        elif warp:
+            try:
+                ho, wo = (int(v) for v in size)
+            except (TypeError, ValueError):
+                raise ValueError("%s: size must be (Ho, Wo)" % fn) from None
+            if ho < 1 or wo < 1 or max(ho, wo) > 65536:
+                raise ValueError("%s: size must be (Ho, Wo), both 1 .. 65536, not %r" % (fn, size))
+            maps = _affine_maps(fn, affine, n)
         else:
             ho, wo = (h, w) if algo == "mhc" else (h // 2, w // 2)
-        return _Front(mos, single, n, h, w, src, ho, wo, key, area, filt)
+        return _Front(mos, single, n, h, w, src, ho, wo, key, area, filt, maps if warp else None)
 
     def _pre_stages(self, fn, mos, black, defects, denoise):
         """defects= and denoise= of the demosaic / decode methods, in that order, each into a scratch tensor; an empty batch
@@ -1887,6 +2044,16 @@ class Context:
         mos, n, h, w, src = front.mos, front.n, front.h, front.w, front.src
         cols, nc = _rgb_colors(gain, matrix, n, fn)
         prm = _rgb_params(algo, dtype_code, flags, front.key, white, black)
+        if algo == "warp":  # one entry point for the three families; the maps are host memory, read before the call returns
+            a = Warp()
+            a.out_h, a.out_w, a.filter, a.reserved = front.ho, front.wo, front.filt, 0
+            d = C.byref(stage) if isinstance(stage, Display) else None
+            y = C.byref(stage) if isinstance(stage, Yuv) else None
+            maps = front.maps
+            self._call(torch, mos.device, "mcraw_demosaic_warp_batch", (mos, out) + tuple(extra), C.byref(prm), C.byref(a), d, y, cols, nc,
+                       maps.ctypes.data_as(C.POINTER(C.c_int32)), int(maps.shape[0]), *src, w, h, n, C.c_void_p(out.data_ptr()),
+                       out.numel() * out.element_size())
+            return out
         if algo in _SCALED:  # one entry point for the three families; its scratch lives as long as the call's other tensors
             struct, work_symbol, batch_symbol, rule = _SCALED[algo]
             a = struct()
@@ -1952,7 +2119,7 @@ class Context:
 
     def decode_rgb(self, inputs, width, height, type, *, algo="mhc", dtype, white, black=(0, 0, 0, 0), cfa="rggb",
                    gain=None, matrix=None, clip=False, out=None, check=True, shading=None, defects=None, denoise=None, size=None,
-                   crop=None, filter=None):
+                   crop=None, filter=None, affine=None):
         """Decode frames of one geometry that are resident in HBM and demosaic them (demosaic()): (N, 3, H, W) for "mhc",
         (N, 3, H/2, W/2) for "bin2", (N, 3, Ho, Wo) for "area" with size=(Ho, Wo) and crop=.  inputs: uint8 CUDA tensors, or (device pointer, length) pairs.  The plain uint16
         mosaics go to a scratch tensor of torch's caching allocator; both steps are queued on torch.cuda.current_stream().
@@ -1963,7 +2130,7 @@ class Context:
         dict of denoise()'s keyword arguments, applied behind defects= and in front of shading=."""
         scratch = self._decode_front("decode_rgb", inputs, width, height, type, check, black, defects, denoise, shading)
         return self.demosaic(scratch, algo=algo, dtype=dtype, white=white, black=black, cfa=cfa, gain=gain, matrix=matrix,
-                             clip=clip, out=out, check=check, size=size, crop=crop, filter=filter)
+                             clip=clip, out=out, check=check, size=size, crop=crop, filter=filter, affine=affine)
 
     def _display_lut(self, torch, dev, fn, transfer, lut_size, bits):
         """(device LUT tensor, caller-owned?) for demosaic_display / demosaic_yuv (`fn`): a ready 1-D uint16 LUT (CUDA tensor on
@@ -1996,7 +2163,7 @@ class Context:
 
     def demosaic_display(self, mosaic, *, algo="mhc", white, black=(0, 0, 0, 0), cfa="rggb", gain=None, matrix=None,
                          transfer="srgb", lut_size=4096, dtype=None, layout="hwc", bits=None, out=None, check=True, shading=None,
-                         defects=None, denoise=None, size=None, crop=None, filter=None):
+                         defects=None, denoise=None, size=None, crop=None, filter=None, affine=None):
         """uint16 mosaics resident on the context's device -> display-ready integer RGB: the demosaic and colours of
         demosaic(), then clamp to [0, 1], index a transfer-curve LUT of L entries at rint(c * (L - 1)) and store the entry
         (its low byte for uint8).  dtype: torch.uint8 (default) or torch.uint16; layout "hwc" gives (N, Ho, Wo, 3), "chw"
@@ -2013,7 +2180,7 @@ class Context:
             raise ValueError("demosaic_display: dtype must be torch.uint8 or torch.uint16, not %r" % (dtype,))
         if layout not in _DISP_LAYOUTS:
             raise ValueError("demosaic_display: layout must be 'hwc' or 'chw', not %r" % (layout,))
-        front = self._demosaic_front("demosaic_display", mosaic, algo, cfa, black, defects, denoise, shading, size, crop, filter)
+        front = self._demosaic_front("demosaic_display", mosaic, algo, cfa, black, defects, denoise, shading, size, crop, filter, affine)
         ho, wo = front.ho, front.wo
         out = self._demosaic_out("demosaic_display", front, out, (ho, wo, 3) if layout == "hwc" else (3, ho, wo),
                                  torch.uint8 if dcode == DISP_U8 else torch.uint16)
@@ -2029,7 +2196,7 @@ class Context:
 
     def decode_display(self, inputs, width, height, type, *, algo="mhc", white, black=(0, 0, 0, 0), cfa="rggb", gain=None,
                        matrix=None, transfer="srgb", lut_size=4096, dtype=None, layout="hwc", bits=None, out=None, check=True, shading=None,
-                       defects=None, denoise=None, size=None, crop=None, filter=None):
+                       defects=None, denoise=None, size=None, crop=None, filter=None, affine=None):
         """Decode frames of one geometry that are resident in HBM and turn them into display-ready RGB
         (demosaic_display()), as decode_rgb does: the plain uint16 mosaics go to a scratch tensor, both steps are queued on
         torch.cuda.current_stream(), check=True synchronises after the decode and raises McrawError naming the frames that
@@ -2037,11 +2204,11 @@ class Context:
         scratch = self._decode_front("decode_display", inputs, width, height, type, check, black, defects, denoise, shading)
         return self.demosaic_display(scratch, algo=algo, white=white, black=black, cfa=cfa, gain=gain, matrix=matrix,
                                      transfer=transfer, lut_size=lut_size, dtype=dtype, layout=layout, bits=bits, out=out,
-                                     check=check, size=size, crop=crop, filter=filter)
+                                     check=check, size=size, crop=crop, filter=filter, affine=affine)
 
     def demosaic_yuv(self, mosaic, *, algo="mhc", white, black=(0, 0, 0, 0), cfa="rggb", gain=None, matrix=None, fmt="nv12",
                      standard="bt709", range="limited", transfer="bt709", lut_size=4096, in_bits=None, out=None, check=True, shading=None,
-                     defects=None, denoise=None, size=None, crop=None, filter=None):
+                     defects=None, denoise=None, size=None, crop=None, filter=None, affine=None):
         """uint16 mosaics resident on the context's device -> video-ready Y'CbCr 4:2:0: the demosaic, colours, clamp and
         transfer-curve LUT of demosaic_display(), then the integer matrix of yuv_matrix(standard, range) and a 2x2 box
         average for the chroma (sited at the block's centre).  fmt "nv12": torch.uint8; "p010": torch.uint16 holding
@@ -2058,7 +2225,7 @@ class Context:
         fcode, bits, default_in = _YUV_FORMATS[fmt]
         in_bits = default_in if in_bits is None else in_bits
         cy, cb, cr, sh, y_off, c_off = yuv_matrix(standard, range, bits, in_bits)
-        front = self._demosaic_front("demosaic_yuv", mosaic, algo, cfa, black, defects, denoise, shading, size, crop, filter)
+        front = self._demosaic_front("demosaic_yuv", mosaic, algo, cfa, black, defects, denoise, shading, size, crop, filter, affine)
         ho, wo = front.ho, front.wo
         out = self._demosaic_out("demosaic_yuv", front, out, (ho * 3 // 2, wo), torch.uint8 if fcode == YUV_NV12 else torch.uint16)
         if front.n == 0:
@@ -2075,7 +2242,7 @@ class Context:
 
     def decode_yuv(self, inputs, width, height, type, *, algo="mhc", white, black=(0, 0, 0, 0), cfa="rggb", gain=None,
                    matrix=None, fmt="nv12", standard="bt709", range="limited", transfer="bt709", lut_size=4096, in_bits=None,
-                   out=None, check=True, shading=None, defects=None, denoise=None, size=None, crop=None, filter=None):
+                   out=None, check=True, shading=None, defects=None, denoise=None, size=None, crop=None, filter=None, affine=None):
         """Decode frames of one geometry that are resident in HBM and turn them into NV12 / P010 (demosaic_yuv()), as
         decode_display does: the plain uint16 mosaics go to a scratch tensor, both steps are queued on
         torch.cuda.current_stream(), check=True synchronises after the decode and raises McrawError naming the frames that
@@ -2083,7 +2250,7 @@ class Context:
         scratch = self._decode_front("decode_yuv", inputs, width, height, type, check, black, defects, denoise, shading)
         return self.demosaic_yuv(scratch, algo=algo, white=white, black=black, cfa=cfa, gain=gain, matrix=matrix, fmt=fmt,
                                  standard=standard, range=range, transfer=transfer, lut_size=lut_size, in_bits=in_bits, out=out,
-                                 check=check, size=size, crop=crop, filter=filter)
+                                 check=check, size=size, crop=crop, filter=filter, affine=affine)
 
     def profile(self, enable=True, only=None, every=1):
         """Bracket kernel launches with events: all kernels, or just the names in `only`; every `every`-th launch."""

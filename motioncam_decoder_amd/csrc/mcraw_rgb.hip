@@ -334,6 +334,10 @@ static int demosaic_launch(const char *fn, mcraw_ctx *c, const mcraw_rgb *p, con
                       out, P.mhc ? MCRAW_KRGB_MHC : MCRAW_KRGB_BIN2, stream_of(c, stream));
 }
 
+// What a persistent grid may hold, for a demosaic unit that names no switch of a test build (csrc/mcraw_warp.hip): this source's
+// RGB_GRID_LIMIT, so that a build with a capped grid caps that unit's grid as well.
+uint32_t rgb_grid_limit(uint32_t resident) { return RGB_GRID_LIMIT(resident); }
+
 #ifdef MCRAW_PATHSR
 void rgb_paths_read_rgb(uint64_t *out, int n, int reset) { rgb_paths_read(out, n, reset); }
 void rgb_paths_read_area(uint64_t *out, int n, int reset);     // mcraw_area.hip

@@ -1,0 +1,316 @@
+// mcraw_warp.hip -- gfx950 kernels for uint16 mosaics resident in HBM -> RGB sampled along one affine map per frame
+// (mcraw_demosaic_warp_batch): the Malvar-He-Cutler estimates of krgb_mhc behind a 4 x 4 gather, linear or cubic, into the float,
+// display and YUV families.  The contract and its weights: include/mcraw_hip.h; the checks, the phase tables, the position
+// arithmetic and the plan, free of HIP: mcraw_warp_args.h; the numpy statement: tests/_warp_ref.py.  The colour stage and the
+// stores are the siblings' (mcraw_rgb_dev.h), the host side of the launch theirs too (mcraw_rgb_launch.h).
+//
+//   krgb_warp  one instance per (output kind, CFA), as the siblings
+//
+// A workgroup owns a tile of WARP_TW x WARP_TH output pixels.
+//   stage   the raw samples under the bounding box of the tile's four corner positions, with the taps (-1 .. +2) and MHC's halo
+//           of 2, reflected at the frame's edges, as 16-byte pieces on the frame's 8-column grid (s_raw, krgb_mhc's layout)
+//   A       a lane takes 8 source columns on the 8-grid of one source row -- the row's parity is uniform in a wave, the columns'
+//           is fixed by the slot, so the CFA role of every slot is known when the kernel is compiled (template S), as in
+//           krgb_resample -- and writes the estimates e of the whole window to s_e, once per source pixel
+//   gather  a lane takes 4 output columns of an output row -- every lane of the workgroup has its pixels, whatever the kind --:
+//           per pixel the 4 x 4 taps over s_e, horizontally first; behind a barrier the tile's E takes the place of the
+//           first estimates in s_e
+//   store   a lane takes 8 output columns of an output row (the YUV kinds: of a row pair, carrying their 2x2 sums as
+//           krgb_bin2y) out of the tile's E and calls the family's row store
+// Every sum of taps is exact in two int32 accumulators: v = 256 vh + vl, A = sum w vh, B = sum w vl (the header's bounds),
+// 24-bit multiplies (|w| < 2^13, |vh| < 2^15).  The phase table in use sits in LDS; the maps travel in the kernel arguments,
+// beside the colours, in pieces of RGB_MAXF frames.
+#include "mcraw_dev.h"
+#include "mcraw_host.h"
+#include "mcraw_rgb_args.h"
+#include "mcraw_rgb_dev.h"
+// The persistent grid's limit is mcraw_rgb.hip's: this unit names no switch of a test build, and a build of that source with a
+// capped grid (build.RGB_PATH_VARIANTS) caps this unit's grid too (tests/test_gpu_warp_paths.py).
+namespace mcraw {
+uint32_t rgb_grid_limit(uint32_t resident);
+}
+#define RGB_GRID_LIMIT(resident) ::mcraw::rgb_grid_limit(resident)
+#include "mcraw_rgb_launch.h"
+#include "mcraw_warp_args.h"
+
+namespace mcraw {
+
+struct WarpGeo {
+    int32_t m[RGB_MAXF][6]; // the maps of this launch's frames (permap), or one in m[0]
+    uint32_t permap;
+    uint32_t tilesX;
+    uint32_t filter;
+};
+
+__device__ const WarpTable g_warp_cubic = warp_table(MCRAW_FILTER_CUBIC);
+
+// Phase A of one lane: the estimates of 8 columns of source row 2 rp + AR of the window (AR: the row's parity) from the raw
+// window in LDS: krgb_mhc's arithmetic, one row of it.
+template <int S, int AR>
+__device__ __forceinline__ void warp_mhc_row(const RgbArgs &A, const uint16_t *s_raw, int32_t *s_e, uint32_t rp, uint32_t q)
+{
+    int d[5][12]; // rows 2 rp + AR - 2 .. + 2 of the estimates' grid, columns 8 q - 2 .. 8 q + 9
+#pragma unroll
+    for (int r = 0; r < 5; r++) {
+        const uint16_t *lrow = &s_raw[(2u * rp + static_cast<uint32_t>(AR + r)) * WARP_RAWW + 8u * q];
+        const mcraw_u32x4 c0 = *reinterpret_cast<const mcraw_u32x4 *>(lrow);
+        const mcraw_u32x4 c1 = *reinterpret_cast<const mcraw_u32x4 *>(lrow + 8);
+        const uint32_t c2 = *reinterpret_cast<const uint32_t *>(lrow + 16);
+        const uint32_t w[6] = {c0[3], c1[0], c1[1], c1[2], c1[3], c2};
+#pragma unroll
+        for (int j = 0; j < 12; j++)
+            d[r][j] = static_cast<int>((w[j >> 1] >> (16u * (j & 1))) & 0xffffu) - A.black[((AR + r) & 1) * 2 + (j & 1)];
+    }
+    int E[3][8];
+#pragma unroll
+    for (int b = 0; b < 8; b++) {
+        constexpr int R = 2;
+        const int J = b + 2;
+        const int C = d[R][J];
+        const int n1 = d[R - 1][J], s1 = d[R + 1][J], w1 = d[R][J - 1], e1 = d[R][J + 1];
+        const int v2 = d[R - 2][J] + d[R + 2][J], h2 = d[R][J - 2] + d[R][J + 2];
+        const int dg = (d[R - 1][J - 1] + d[R - 1][J + 1]) + (d[R + 1][J - 1] + d[R + 1][J + 1]);
+        const int role = (AR * 2 + (b & 1)) ^ S;
+        const int nat = 16 * C;
+        if (role == 0 || role == 3) { // R or B site
+            const int g = 8 * C + 4 * ((n1 + s1) + (w1 + e1)) - 2 * (v2 + h2);
+            const int o = 12 * C + 4 * dg - 3 * (v2 + h2);
+            E[0][b] = role == 0 ? nat : o;
+            E[1][b] = g;
+            E[2][b] = role == 0 ? o : nat;
+        } else { // G site: role 1 has R left / right, role 2 has B left / right
+            const int hz = 10 * C + 8 * (w1 + e1) - 2 * h2 - 2 * dg + v2;
+            const int vt = 10 * C + 8 * (n1 + s1) - 2 * v2 - 2 * dg + h2;
+            E[0][b] = role == 1 ? hz : vt;
+            E[1][b] = nat;
+            E[2][b] = role == 1 ? vt : hz;
+        }
+    }
+#pragma unroll
+    for (uint32_t c = 0; c < 3u; c++) {
+        int32_t *dst = &s_e[(c * WARP_EROWS + 2u * rp + static_cast<uint32_t>(AR)) * WARP_ESTRIDE + 8u * q];
+        *reinterpret_cast<mcraw_u32x4 *>(dst) = mcraw_u32x4{static_cast<uint32_t>(E[c][0]), static_cast<uint32_t>(E[c][1]),
+                                                            static_cast<uint32_t>(E[c][2]), static_cast<uint32_t>(E[c][3])};
+        *reinterpret_cast<mcraw_u32x4 *>(dst + 4) = mcraw_u32x4{static_cast<uint32_t>(E[c][4]), static_cast<uint32_t>(E[c][5]),
+                                                                static_cast<uint32_t>(E[c][6]), static_cast<uint32_t>(E[c][7])};
+    }
+}
+
+// The four weights of phase p out of the table in LDS.
+__device__ __forceinline__ void warp_weights(const int16_t *s_w, uint32_t p, int32_t (&w)[4])
+{
+    const mcraw_u32x2 v = *reinterpret_cast<const mcraw_u32x2 *>(&s_w[4u * p]);
+    w[0] = static_cast<int32_t>(v[0] << 16) >> 16;
+    w[1] = static_cast<int32_t>(v[0]) >> 16;
+    w[2] = static_cast<int32_t>(v[1] << 16) >> 16;
+    w[3] = static_cast<int32_t>(v[1]) >> 16;
+}
+
+// One output pixel at position (Y, X): the 4 x 4 taps over the window's estimates (held from row pb, column eb of the frame on),
+// horizontally first.  Whatever the position, the reads stay inside the array.
+__device__ __forceinline__ void warp_pixel(const int32_t *s_e, const int16_t *s_w, int64_t Y, int64_t X, int32_t pb, int32_t eb,
+                                           int32_t (&E)[3])
+{
+    int32_t wy[4], wx[4];
+    warp_weights(s_w, static_cast<uint32_t>(Y) & 255u, wy);
+    warp_weights(s_w, static_cast<uint32_t>(X) & 255u, wx);
+    const int32_t r0 = min(max(static_cast<int32_t>(Y >> 8) - 1 - pb, 0), static_cast<int32_t>(WARP_EROWS) - 4);
+    const int32_t c0 = min(max(static_cast<int32_t>(X >> 8) - 1 - eb, 0), static_cast<int32_t>(WARP_ECOLS) - 4);
+#pragma unroll
+    for (uint32_t c = 0; c < 3u; c++) {
+        const int32_t *src = &s_e[(c * WARP_EROWS + static_cast<uint32_t>(r0)) * WARP_ESTRIDE + static_cast<uint32_t>(c0)];
+        int32_t a2 = 0, b2 = 0;
+#pragma unroll
+        for (uint32_t r = 0; r < 4u; r++) {
+            int32_t a = 0, b = 0;
+#pragma unroll
+            for (uint32_t j = 0; j < 4u; j++) {
+                const int32_t v = src[r * WARP_ESTRIDE + j];
+                a += __mul24(wx[j], v >> 8);
+                b += __mul24(wx[j], v & 255);
+            }
+            const int32_t t = (a + ((b + 2048) >> 8)) >> 4;
+            a2 += __mul24(wy[r], t >> 8);
+            b2 += __mul24(wy[r], t & 255);
+        }
+        E[c] = (a2 + ((b2 + 2048) >> 8)) >> 4;
+    }
+}
+
+template <int PK, int S>
+__global__ void __launch_bounds__(RGB_T) krgb_warp(const RgbArgs A, const WarpGeo G)
+{
+    constexpr bool LUT = has_lut(PK);
+    constexpr uint32_t ROWS = is_yuv(PK) ? 2u : 1u; // output rows of a lane
+    __shared__ __attribute__((aligned(16))) uint16_t s_raw[WARP_RAWH * WARP_RAWW];
+    __shared__ __attribute__((aligned(16))) int32_t s_e[3u * WARP_EROWS * WARP_ESTRIDE];
+    __shared__ __attribute__((aligned(16))) int16_t s_w[256u * 4u];
+    __shared__ __attribute__((aligned(16))) uint16_t s_lut[LUT ? DISP_LDS_MAX : 8u];
+    uint32_t t = blockIdx.x;
+    if constexpr (LUT)
+        stage_lut(A, s_lut);
+    for (uint32_t i = threadIdx.x; i < 256u; i += RGB_T) { // the phase table in use: four int16 per phase
+        mcraw_u32x2 v;
+        if (G.filter == MCRAW_FILTER_LINEAR)
+            v = mcraw_u32x2{(16u * (256u - i)) << 16, 16u * i};
+        else
+            v = *reinterpret_cast<const mcraw_u32x2 *>(g_warp_cubic.w[i]);
+        *reinterpret_cast<mcraw_u32x2 *>(&s_w[4u * i]) = v;
+    }
+    const int W = static_cast<int>(A.W), H = static_cast<int>(A.H);
+    do {
+        const uint32_t f = LUT ? t / A.units : blockIdx.y, u = LUT ? t % A.units : blockIdx.x;
+        const uint32_t tx = u % G.tilesX, ty = u / G.tilesX;
+        const uint32_t k0 = tx * WARP_TW, k1 = min(k0 + WARP_TW, A.Wo) - 1u; // the tile's first and last column
+        const uint32_t i0 = ty * WARP_TH, i1 = min(i0 + WARP_TH, A.Ho) - 1u; // ... and row
+        const int32_t *m = G.m[G.permap ? f : 0u];
+        const int32_t map[6] = {m[0], m[1], m[2], m[3], m[4], m[5]};
+        // the estimates the tile needs: from row pb (even) and column eb (on the 8-grid) of the frame on, np row pairs and ne
+        // pieces of 8 columns (tests/cpp/warp_args_check.cpp holds every tap of every tile against this window and the arrays)
+        const WarpWin win = warp_window(map, i0, i1, k0, k1);
+        const int32_t pb = win.pb, eb = win.eb;
+        const uint32_t np = min(win.np, WARP_EROWS / 2u), ne = min(win.ne, WARP_ECOLS / 8u);
+        const uint16_t *in = A.in + static_cast<size_t>(f) * A.fstride;
+        __syncthreads(); // the LUT and the table are staged; the previous tile's LDS reads are done
+        // raw rows pb - 2 .. pb + 2 np + 1, columns eb - 8 .. eb + 8 ne + 7
+        const uint32_t nch = ne + 2u;
+        for (uint32_t i = threadIdx.x; i < (2u * np + 4u) * nch; i += RGB_T) {
+            const uint32_t r = i / nch, q = i % nch;
+            const uint16_t *row = in + static_cast<size_t>(reflect101(pb - 2 + static_cast<int>(r), H)) * A.pitch;
+            const int xs = eb - 8 + 8 * static_cast<int>(q);
+            mcraw_u32x4 v;
+            if (A.invec && xs >= 0 && xs + 8 <= W) {
+                v = *gptr<const mcraw_u32x4>(row + xs);
+            } else {
+                uint32_t e[8];
+#pragma unroll
+                for (int k = 0; k < 8; k++)
+                    e[k] = gptr<const uint16_t>(row)[reflect101(xs + k, W)];
+                v = mcraw_u32x4{e[0] | (e[1] << 16), e[2] | (e[3] << 16), e[4] | (e[5] << 16), e[6] | (e[7] << 16)};
+            }
+            *reinterpret_cast<mcraw_u32x4 *>(&s_raw[r * WARP_RAWW + 8u * q]) = v;
+        }
+        __syncthreads();
+        // A: rows of parity 0 in the first half of the workgroup, of parity 1 in the second (uniform in a wave)
+        if (threadIdx.x < RGB_T / 2u) {
+            for (uint32_t it = threadIdx.x; it < np * ne; it += RGB_T / 2u)
+                warp_mhc_row<S, 0>(A, s_raw, s_e, it / ne, it % ne);
+        } else {
+            for (uint32_t it = threadIdx.x - RGB_T / 2u; it < np * ne; it += RGB_T / 2u)
+                warp_mhc_row<S, 1>(A, s_raw, s_e, it / ne, it % ne);
+        }
+        __syncthreads();
+        // gather: a lane takes 4 output columns of one output row: every lane of the workgroup has its pixels
+        {
+            const uint32_t gr = threadIdx.x / (WARP_TW / 4u), gc = 4u * (threadIdx.x % (WARP_TW / 4u));
+            const uint32_t j = i0 + gr, x = k0 + gc;
+            int32_t E4[3][4] = {};
+            if (j <= i1 && x <= k1) {
+                const int64_t by = static_cast<int64_t>(map[0]) * j + static_cast<int64_t>(map[1]) * x + 128;
+                const int64_t bx = static_cast<int64_t>(map[3]) * j + static_cast<int64_t>(map[4]) * x + 128;
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    int32_t e3[3];
+                    warp_pixel(s_e, s_w, map[2] + ((by + static_cast<int64_t>(map[1]) * i) >> 8),
+                               map[5] + ((bx + static_cast<int64_t>(map[4]) * i) >> 8), pb, eb, e3);
+                    E4[0][i] = e3[0], E4[1][i] = e3[1], E4[2][i] = e3[2];
+                }
+            }
+            __syncthreads(); // every tap is read: the tile's E takes the place of the first estimates
+#pragma unroll
+            for (uint32_t c = 0; c < 3u; c++)
+                *reinterpret_cast<mcraw_u32x4 *>(&s_e[(c * WARP_TH + gr) * WARP_TW + gc]) =
+                    mcraw_u32x4{static_cast<uint32_t>(E4[c][0]), static_cast<uint32_t>(E4[c][1]), static_cast<uint32_t>(E4[c][2]),
+                                static_cast<uint32_t>(E4[c][3])};
+            __syncthreads();
+        }
+        // store: (8 output columns, output row or row pair) out of the tile's E
+        const uint32_t lxid = threadIdx.x & (WARP_TW / 8u - 1u), lyid = threadIdx.x / (WARP_TW / 8u);
+        const uint32_t xo = k0 + 8u * lxid, j0 = i0 + ROWS * lyid;
+        if (lyid < WARP_TH / ROWS && xo < A.Wo && j0 <= i1) {
+            const uint32_t n = min(8u, A.Wo - xo);
+            const RgbCol &col = A.col[A.percol ? f : 0u];
+            uint8_t *fout = A.out + static_cast<size_t>(f) * 3u * A.Ho * A.Wo * out_es(PK) / (is_yuv(PK) ? 2u : 1u);
+            int SUM[3][4] = {}; // YUV kinds: the sums of P over the lane's four 2x2 blocks
+#pragma unroll 1
+            for (uint32_t a = 0; a < ROWS; a++) {
+                const uint32_t j = j0 + a; // (the YUV kinds: Ho is even, a row pair always has both rows)
+                int E[3][8];
+#pragma unroll
+                for (uint32_t c = 0; c < 3u; c++) {
+                    const int32_t *src = &s_e[(c * WARP_TH + (j - i0)) * WARP_TW + 8u * lxid];
+                    const mcraw_u32x4 v0 = *reinterpret_cast<const mcraw_u32x4 *>(src);
+                    const mcraw_u32x4 v1 = *reinterpret_cast<const mcraw_u32x4 *>(src + 4);
+#pragma unroll
+                    for (int i = 0; i < 8; i++)
+                        E[c][i] = static_cast<int32_t>(i < 4 ? v0[i] : v1[i - 4]);
+                }
+                if constexpr (is_yuv(PK))
+                    yuv_row8<PK>(A, col, s_lut, fout, j, xo, n, static_cast<int>(a), E, SUM);
+                else if constexpr (is_disp(PK))
+                    disp_store8<PK>(A, col, s_lut, fout, j, xo, n, E);
+                else
+                    rgb_store8<PK>(A, col, fout, j, xo, n, E);
+            }
+        }
+    } while (LUT && (t += gridDim.x) < A.units * A.nf);
+}
+
+struct WarpK {
+    template <int PK, int S>
+    static auto at() { return &krgb_warp<PK, S>; }
+};
+
+static int warp_launch(mcraw_ctx *c, const mcraw_rgb *p, const mcraw_warp *wp, const mcraw_display *d, const mcraw_yuv *yv,
+                       const mcraw_rgb_color *colors, int ncolors, const int32_t *maps, const uint16_t *in, size_t in_pitch,
+                       size_t in_frame_stride, int width, int height, int n, const WarpPlan &P, void *out, hipStream_t st)
+{
+    RgbArgs A = rgb_args(p, d, yv, in_pitch, in_frame_stride, width, height, ncolors);
+    A.Wo = static_cast<uint32_t>(P.rgb.Wo);
+    A.Ho = static_cast<uint32_t>(P.rgb.Ho);
+    A.tilesX = P.tilesX;
+    A.units = P.units;
+    A.invec = P.rgb.invec;
+    WarpGeo G{};
+    G.permap = P.permap ? 1u : 0u;
+    G.tilesX = P.tilesX;
+    G.filter = wp->filter;
+    const std::vector<RgbCol> cols = rgb_cols(p, colors, ncolors, 0.0625f);
+    // pieces of RGB_MAXF frames where the maps or the colours are per frame: both travel in the kernel arguments
+    const int piece = (P.permap || A.percol) ? RGB_MAXF : n;
+    for (int f0 = 0; f0 < n; f0 += piece) {
+        const int nf = std::min(piece, n - f0);
+        std::memcpy(G.m, maps + (P.permap ? 6 * static_cast<size_t>(f0) : 0u), sizeof(int32_t) * 6u * static_cast<size_t>(P.permap ? nf : 1));
+        const std::vector<RgbCol> pc = A.percol ? std::vector<RgbCol>(cols.begin() + f0, cols.begin() + f0 + nf) : cols;
+        if (int rc = rgb_launch(c, rgb_pick<WarpK>(P.rgb), A, P.rgb, pc, in + static_cast<size_t>(f0) * in_frame_stride, nf,
+                                static_cast<uint8_t *>(out) + static_cast<size_t>(f0) * P.rgb.out_frame, -1, st, G))
+            return rc;
+    }
+    return 0;
+}
+
+} // namespace mcraw
+
+using namespace mcraw;
+
+extern "C" {
+
+int mcraw_demosaic_warp_batch(mcraw_ctx *c, const mcraw_rgb *p, const mcraw_warp *wp, const mcraw_display *d, const mcraw_yuv *y,
+                              const mcraw_rgb_color *colors, int ncolors, const int32_t *maps, int nmaps, const uint16_t *in,
+                              size_t in_pitch, size_t in_frame_stride, int width, int height, int n, void *out, size_t out_bytes,
+                              void *stream)
+{
+    WarpPlan P;
+    const char *why = c ? warp_check(p, wp, d, y, colors, ncolors, maps, nmaps, in, in_pitch, in_frame_stride, width, height, n, out,
+                                     out_bytes, P)
+                        : "bad arguments";
+    if (why)
+        return reject("mcraw_demosaic_warp_batch", why);
+    if (P.rgb.noop)
+        return 0;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipSetDevice(c->device));
+    return warp_launch(c, p, wp, d, y, colors, ncolors, maps, in, in_pitch, in_frame_stride, width, height, n, P, out, stream_of(c, stream));
+}
+
+} // extern "C"
