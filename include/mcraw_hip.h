@@ -362,7 +362,7 @@ int mcraw_ctx_set_float_out(mcraw_ctx *ctx, const mcraw_float_out *f);
 #define MCRAW_CFA_GRBG 2
 #define MCRAW_CFA_GBRG 3
 typedef struct mcraw_rgb {
-    uint32_t algo;     /* MCRAW_RGB_MHC or MCRAW_RGB_BIN2                                    */
+    uint32_t algo;     /* MCRAW_RGB_MHC, MCRAW_RGB_BIN2 or MCRAW_RGB_HA (below)               */
     uint32_t dtype;    /* MCRAW_FLOAT_F32 / _F16 / _BF16                                      */
     uint32_t flags;    /* MCRAW_FLOAT_CLIP or 0                                               */
     uint32_t cfa;      /* MCRAW_CFA_* (the container's sensorArrangment)                      */
@@ -447,6 +447,40 @@ typedef struct mcraw_yuv {
 int mcraw_demosaic_yuv_batch(mcraw_ctx *ctx, const mcraw_rgb *p, const mcraw_yuv *y, const mcraw_rgb_color *colors,
                              int ncolors, const uint16_t *in, size_t in_pitch, size_t in_frame_stride, int width,
                              int height, int n, void *out, size_t out_bytes, void *stream);
+
+/* ---- the edge-directed demosaic: MCRAW_RGB_HA, in all three output families ----------------------------------------
+ *
+ * A second full-resolution algorithm beside MCRAW_RGB_MHC, accepted by mcraw_demosaic_batch, mcraw_demosaic_display_batch and
+ * mcraw_demosaic_yuv_batch with every rule of theirs: Ho = height, Wo = width, no further struct, no scratch.  Hamilton-Adams
+ * adaptive colour-plane interpolation in integers: green is interpolated along the axis with the smaller gradient, R and B from
+ * their differences against green.  The area, resample and warp entry points keep rejecting it, and the latter two keep
+ * sampling MCRAW_RGB_MHC's estimates.
+ * Bit-exact arithmetic.  d(y, x) = (int)s(y, x) - (int)black[p] as for MHC; reads outside the frame are reflected 101-style, by
+ * up to 3 samples (frames are at least 4 x 4: one reflection is enough).  role = p ^ shift(cfa) in RGGB terms.
+ *   The green plane g, in 1/8 DN, on the frame and a ring of one pixel around it (the ring from the reflected d):
+ *     at a green site     g = 8 d
+ *     at an R or B site, C = d there:
+ *       ch = 2 C - d[y][x-2] - d[y][x+2]                  cv: the transpose
+ *       gh = 2 (d[y][x-1] + d[y][x+1]) + ch               gv: the transpose
+ *       DH = |d[y][x-1] - d[y][x+1]| + |ch|               DV: the transpose
+ *       g  = 2 gh if DH < DV, 2 gv if DV < DH, gh + gv if they are equal
+ *   The estimates E_c, in 1/32 DN:
+ *     E_G = 4 g;  the native channel 32 d
+ *     for a pair of opposite neighbours a, b that carry the wanted colour:
+ *       n(a, b) = 8 (d_a + d_b) + (2 g - g_a - g_b)       D(a, b) = 8 |d_a - d_b| + |2 g - g_a - g_b|
+ *     R or B at a green site    2 n(left, right) or 2 n(up, down), whichever axis carries that colour
+ *     R at B, B at R            N = (nw, se), P = (ne, sw): 2 n(N) if D(N) < D(P), 2 n(P) if D(P) < D(N), n(N) + n(P) if equal
+ *   Range, with |d| <= 65535 =: M, each step a sum of bounded terms:
+ *     |ch| <= 4 M, |gh| <= 4 M + 4 M = 8 M, so |g| <= 16 M at an R or B site and 8 M at a green one: |g| <= 16 * 65535;
+ *     |E_G| = 4 |g| <= 64 M;  at a green site the neighbours a, b are R / B sites: |2 g - g_a - g_b| <= 16 M + 32 M = 48 M,
+ *     |n| <= 16 M + 48 M = 64 M, |E| <= 128 M;  at an R or B site |2 g - g_a - g_b| <= 32 M + 32 M = 64 M, |n| <= 80 M,
+ *     |E| <= 160 M = 10 485 600 < 2^24;  D <= 16 M + 64 M.  Everything fits int32 and (float)E_c is exact.
+ *   From E_c on it is MHC's stage, unchanged: k[c] = (gain[c] * inv) * 0.03125f, then v_c, o_i, the clip and the float,
+ *   display and YUV stores.
+ * What follows: a flat frame gives E_c = 32 d everywhere; transposing the mosaic, its black levels and its CFA transposes the
+ * result, bit for bit; mirroring the columns mirrors it.
+ * Kernel: krgb_ha (csrc/mcraw_ha.hip); it has no kernel id (mcraw_ctx_kernel_ms does not see it). */
+#define MCRAW_RGB_HA 6   /* valid where MCRAW_RGB_MHC is: the three entry points above */
 
 /* ---- uint16 mosaics -> any output size: an area downscale of a crop window, into all three output families ---------
  *

@@ -308,6 +308,10 @@ struct Bin2K { // (the YUV kinds have a kernel of their own)
     }
 };
 
+// krgb_ha's launches (csrc/mcraw_ha.hip)
+int ha_launch(mcraw_ctx *c, const RgbArgs &A, const RgbPlan &P, const std::vector<RgbCol> &cols, const uint16_t *in, int n, void *out,
+              hipStream_t st);
+
 // The three entry points: rgb_check (mcraw_rgb_args.h) decides about the call and plans it -- `d` given: the display stage, `yv`:
 // the YUV stage (never both) --, then the launches.
 static int demosaic_launch(const char *fn, mcraw_ctx *c, const mcraw_rgb *p, const mcraw_display *d, const mcraw_yuv *yv,
@@ -330,6 +334,8 @@ static int demosaic_launch(const char *fn, mcraw_ctx *c, const mcraw_rgb *p, con
     A.tilesX = P.tilesX;
     A.units = P.units;
     A.invec = P.invec;
+    if (P.ha) // the edge-directed demosaic: MHC's geometry, estimates in 1/32 (csrc/mcraw_ha.hip)
+        return ha_launch(c, A, P, rgb_cols(p, colors, ncolors, 0.03125f), in, n, out, stream_of(c, stream));
     return rgb_launch(c, P.mhc ? rgb_pick<MhcK>(P) : rgb_pick<Bin2K>(P), A, P, rgb_cols(p, colors, ncolors, P.mhc ? 0.0625f : 0.5f), in, n,
                       out, P.mhc ? MCRAW_KRGB_MHC : MCRAW_KRGB_BIN2, stream_of(c, stream));
 }

@@ -34,13 +34,14 @@ struct RgbPlan {
     bool noop;            // an empty batch: nothing below is set, nothing is launched
     int kind;             // PK_*
     int shift;            // RGGB role of CFA position p: p ^ shift
-    bool mhc;             // MCRAW_RGB_MHC, else BIN2
+    bool mhc;             // MCRAW_RGB_MHC, else BIN2 (or HA: `ha`)
     bool invec;           // every 8-column piece of every input row lies on the 16-byte grid
     size_t es, Wo, Ho;    // bytes per output sample; output size
     size_t frame_samples; // samples per frame: 3 planes, or a Y plane and half of one for the (Cb, Cr) rows
     size_t out_frame;     // bytes per output frame
     uint32_t tilesX;      // MHC: tiles per row band; BIN2: groups of 8 output columns per output row
     uint32_t units;       // per frame: tiles (MHC), or workgroups of 256 items (BIN2; YUV kinds: an item is a row pair)
+    bool ha;              // MCRAW_RGB_HA (csrc/mcraw_ha.hip): MHC's output size and tiles, estimates in 1/32
 };
 
 inline bool finite_all(const float *v, int n)
@@ -148,19 +149,21 @@ inline const char *rgb_check(const mcraw_rgb *p, const mcraw_display *d, const m
     const MosaicBatch I(in, in_pitch, in_frame_stride, static_cast<size_t>(n), width, height);
     if (const char *why = I.check())
         return why;
-    if (p->algo != MCRAW_RGB_MHC && p->algo != MCRAW_RGB_BIN2)
+    if (p->algo != MCRAW_RGB_MHC && p->algo != MCRAW_RGB_BIN2 && p->algo != MCRAW_RGB_HA)
         return "unknown algo";
     if (const char *why = rgb_check_stage(p, d, yv, colors, ncolors, n, plan))
         return why;
     plan.mhc = p->algo == MCRAW_RGB_MHC;
-    plan.Wo = plan.mhc ? static_cast<size_t>(width) : static_cast<size_t>(width) / 2u;
-    plan.Ho = plan.mhc ? static_cast<size_t>(height) : static_cast<size_t>(height) / 2u;
+    plan.ha = p->algo == MCRAW_RGB_HA;
+    const bool full = plan.mhc || plan.ha; // full resolution, in tiles of MHC_TW x MHC_TH
+    plan.Wo = full ? static_cast<size_t>(width) : static_cast<size_t>(width) / 2u;
+    plan.Ho = full ? static_cast<size_t>(height) : static_cast<size_t>(height) / 2u;
     if (yv && ((plan.Ho | plan.Wo) & 1u))
         return "4:2:0 needs an even Ho and Wo (BIN2: width and height multiples of 4)";
     if (const char *why = rgb_check_out(p, yv != nullptr, n, out, out_bytes, plan))
         return why;
     plan.invec = I.on_grid();
-    if (plan.mhc) {
+    if (full) {
         plan.tilesX = (static_cast<uint32_t>(width) + MHC_TW - 1u) / MHC_TW;
         plan.units = plan.tilesX * ((static_cast<uint32_t>(height) + MHC_TH - 1u) / MHC_TH);
     } else {

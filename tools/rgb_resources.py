@@ -5,10 +5,11 @@ statistics kernels (csrc/mcraw_stats.hip), of the defective-pixel kernels (csrc/
 one line per instance in the format of profiles/rgb_resources.txt / display_resources.txt / yuv_resources.txt /
 shade_resources.txt / stats_resources.txt / fixpix_resources.txt / denoise_resources.txt / merge_resources.txt / align_resources.txt /
 cells_resources.txt (kcells_* and kmerge<..., field>) / area_resources.txt (csrc/mcraw_area.hip: krgb_area and karea_tab) /
-resample_resources.txt (csrc/mcraw_resample.hip: krgb_resample and kres_tab) / warp_resources.txt (csrc/mcraw_warp.hip: krgb_warp).
+resample_resources.txt (csrc/mcraw_resample.hip: krgb_resample and kres_tab) / warp_resources.txt (csrc/mcraw_warp.hip: krgb_warp) /
+ha_resources.txt (csrc/mcraw_ha.hip: krgb_ha).
 
     python tools/rgb_resources.py            # every instance
-    python tools/rgb_resources.py --check    # the figures in the thirteen committed files must equal the compiler's; exit 1 if not
+    python tools/rgb_resources.py --check    # the figures in the fourteen committed files must equal the compiler's; exit 1 if not
 """
 import os
 import re
@@ -42,6 +43,8 @@ RESAMPLE_FILE = "resample_resources.txt"
 RESAMPLE_NAME = r"Function Name: _ZN5mcraw\d+(krgb_resample|kres_tab)(?:ILi(\d+)ELi(\d)EEEv|E)"  # krgb_resample<kind, CFA shift>, and the kernel that writes the taps
 WARP_FILE = "warp_resources.txt"
 WARP_NAME = r"Function Name: _ZN5mcraw\d+(krgb_warp)ILi(\d+)ELi(\d)EEEv"  # krgb_warp<kind, CFA shift>
+HA_FILE = "ha_resources.txt"
+HA_NAME = r"Function Name: _ZN5mcraw\d+(krgb_ha)ILi(\d+)ELi(\d)EEEv"  # krgb_ha<kind, CFA shift>
 SHADE_NAME = r"Function Name: _ZN5mcraw\d+(kshade)ILb([01])EEEv"  # kshade<NT>: `sc1 nt` streaming stores or plain ones
 
 
@@ -121,16 +124,17 @@ def main():
     cells = dict(report("mcraw_cells.hip", CELLS_NAME), **{k: v for k, v in both.items() if k.endswith(",field>")})
     resample = report("mcraw_resample.hip", RESAMPLE_NAME)
     warp = report("mcraw_warp.hip", WARP_NAME)
+    ha = report("mcraw_ha.hip", HA_NAME)
     if "--check" not in sys.argv:
         for line in list(rep.values()) + list(shade.values()) + list(stats.values()) + list(fixpix.values()) + list(denoise.values()) + \
-                list(merge.values()) + list(align.values()) + list(area.values()) + list(resample.values()) + list(cells.values()) + list(warp.values()):
+                list(merge.values()) + list(align.values()) + list(area.values()) + list(resample.values()) + list(cells.values()) + list(warp.values()) + list(ha.values()):
             print(line)
         return 0
     return _check(FILES, rep, "krgb_") | _check((SHADE_FILE,), shade, "kshade") | _check((STATS_FILE,), stats, "kstats") | \
         _check((FIXPIX_FILE,), fixpix, "kfixpix") | _check((DENOISE_FILE,), denoise, "kdenoise") | _check((MERGE_FILE,), merge, "kmerge") | \
         _check((ALIGN_FILE,), align, "kalign") | _check((AREA_FILE,), area, ("krgb_area", "karea_tab")) | \
         _check((RESAMPLE_FILE,), resample, ("krgb_resample", "kres_tab")) | _check((CELLS_FILE,), cells, ("kcells_", "kmerge<")) | \
-        _check((WARP_FILE,), warp, "krgb_warp")
+        _check((WARP_FILE,), warp, "krgb_warp") | _check((HA_FILE,), ha, "krgb_ha")
 
 
 if __name__ == "__main__":
