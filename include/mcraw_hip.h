@@ -1056,6 +1056,79 @@ int mcraw_merge_cells_batch(mcraw_ctx *ctx, const mcraw_merge *m, const mcraw_ce
                             size_t in_frame_stride, int width, int height, int n, uint16_t *out, size_t out_pitch,
                             size_t out_frame_stride, void *stream);
 
+/* ---- uint16 mosaics -> uint16 mosaics with the clipped highlights neutralised or rebuilt ------------------------------------
+ *
+ * A clipped sensor reaches the colour stage as (gain_r, gain_g, gain_b) x range, and a colour matrix with negative off-diagonal
+ * terms turns that magenta.  This stage sits in front of the lens-shading gains (which move the clip level by position) and of
+ * the demosaic, and either clips every CFA position to the lowest white-balanced clip level (MCRAW_HL_CLIP: a blown region becomes
+ * exactly neutral) or rebuilds the clipped samples from their unclipped neighbours of the other colours (MCRAW_HL_REBUILD).  The
+ * output is a mosaic of the same black level whose samples may exceed `sat`: everything that takes a mosaic takes it, and with
+ * the demosaic's `white` left as it was the rebuilt samples map above 1.0 in front of the matrix.  Pitches and frame strides count
+ * uint16 elements.  Integers only: bit-exact.
+ * By CFA position p = (y & 1) * 2 + (x & 1): black[4]; sat[4], a sample s >= sat[p] is clipped, sat[p] > black[p]; gain[4], the
+ * white-balance gain in Q4.12 (4096 is 1.0), 256 .. 65535; lo[4], used by the measure call only.  cfa: MCRAW_CFA_*, which says
+ * which two positions are green (RGGB and BGGR: 1 and 2; GRBG and GBRG: 0 and 3).  top: 1 .. 65535.  The host derives
+ *   inv[p] = ((1 << 24) + gain[p] / 2) / gain[p]                                            256 .. 65536
+ * Width and height are 2 .. 65536, odd sizes are fine.  Neighbour coordinates reflect as -1 -> 1 and n -> n - 2, for rows and
+ * columns independently, which keeps the CFA parity (hence no size of 1).
+ * The white-balanced value of a sample s at position q:
+ *   d = max(s - black[q], 0);   v = (d * gain[q] + 2048) >> 12          d * gain + 2048 < 2^32 and v < 2^20: uint32 suffices
+ * The reference at a pixel, from the v of its eight neighbours:
+ *   Hm = (left + right + 1) >> 1;   Vm = (up + down + 1) >> 1;   Dm = (the four diagonals + 2) >> 2
+ *   at a green position  ref = (Hm + Vm + 1) >> 1                         the two other colours (the diagonals are green again)
+ *   at a red or blue one ref = (((Hm + Vm + 1) >> 1) + Dm + 1) >> 1       the mean of green and the opposite colour
+ * Measure (mcraw_highlights_measure_batch) writes records of int64 sum[4]; uint32 cnt[4]; uint32 pad[4] (64 bytes, indexed by p,
+ * pad written as 0) to `rec`, 8-byte aligned DEVICE memory: nrec == n, one per frame, or nrec == 1, one for the whole batch.
+ * A pixel of the frame takes part when lo[p] <= s < sat[p] and all eight neighbours are below their own sat; for each such
+ * pixel sum[p] += v - ref and cnt[p] += 1.  |v - ref| < 2^20 and a frame has at most 2^30 samples per position, so the sums fit;
+ * integer sums do not depend on the order.  The call initialises the records itself on the stream; with MCRAW_HL_ACCUMULATE in
+ * `flags` it adds to what is there instead (one record over a clip, against flicker; cnt then wraps modulo 2^32).
+ * mode, top and `out` mean nothing to it, but mode and top are checked all the same.
+ * Apply (mcraw_highlights_batch), by `mode`:
+ *   MCRAW_HL_CLIP     m = min over p of (((sat[p] - black[p]) * gain[p] + 2048) >> 12)
+ *                     cap[p] = black[p] + ((m * inv[p] + 2048) >> 12)     in uint64 on the host
+ *                     out = min(s, cap[p])                                never raises a sample; rec, nrec and top unused
+ *   MCRAW_HL_REBUILD  chroma[p] = cnt[p] ? sum[p] / cnt[p] : 0, C's int64 division (towards zero), then clamped to
+ *                     -2^20 .. 2^20 (a record that the measure call wrote never reaches that); of the frame's record, of
+ *                     record 0 with nrec == 1, 0 with rec == NULL and nrec == 0.
+ *                     An unclipped sample is copied bit for bit.  A clipped one with cand = ref + chroma[p] <= v (signed) too.
+ *                     Otherwise out = max(s, min(black[p] + ((cand * inv[p] + 2048) >> 12), top)), the product in uint64
+ *                     (cand <= 2^21, inv <= 65536).  It never lowers a sample.
+ * MCRAW_HL_ACCUMULATE in `flags` means nothing to the apply call.  The apply kernel reads the records and does the four
+ * divisions itself, so measure and apply are queued back to back with no host round trip between them.
+ * `rec` is the caller's memory, read (written) by the queued kernels in stream order and never copied into or cached by the
+ * context (two calls with the same pointer and new contents in between each see their own).
+ * There is no in-place form: every pixel reads its neighbours.  `in` and `out` may sit at any 2-byte alignment with any pitch
+ * (16-byte accesses where base, pitch and stride allow it).
+ * `stream`: a hipStream_t, NULL = the context's own stream; the calls queue the work and return without synchronising.
+ * They take no decode serial and leave the decode slots, mcraw_ctx_errors, mcraw_ctx_last_serial and the context's stage
+ * alone.  n == 0 is a no-op.  The launches have no id in mcraw_ctx_kernel_ms (time them with stream events).
+ * Rejected (returns < 0, mcraw_last_error says why, starting with the function's name and ": ", nothing is written): a NULL `h`,
+ * `in` or `out`; an odd `in` or `out` address; width or height outside 2 .. 65536; a pitch below width; n > 1 and a frame stride
+ * below (height - 1) * pitch + width; an unknown mode, cfa or flag; gain[p] < 256; sat[p] <= black[p]; top outside 1 .. 65535;
+ * nrec not 0, 1 or n (measure: not 1 or n); a NULL `rec` with nrec > 0, a non-NULL one with nrec == 0, or one that is not 8-byte
+ * aligned; a non-zero `reserved`; input and output extents that overlap at all; records that overlap either extent. */
+#define MCRAW_HL_CLIP 0u        /* mode: min(s, cap[p])                                          */
+#define MCRAW_HL_REBUILD 1u     /* mode: clipped samples from their neighbours' colour           */
+#define MCRAW_HL_ACCUMULATE 1u  /* flags: the measure call adds to the records that are there    */
+typedef struct mcraw_highlights {
+    uint32_t mode;           /* MCRAW_HL_CLIP or MCRAW_HL_REBUILD                                 */
+    uint32_t cfa;            /* MCRAW_CFA_*                                                       */
+    uint32_t flags;          /* MCRAW_HL_ACCUMULATE or 0                                          */
+    uint32_t top;            /* 1 .. 65535: the largest sample REBUILD writes                     */
+    uint16_t black[4];       /* by CFA position                                                   */
+    uint16_t sat[4];         /* by CFA position: s >= sat[p] is clipped; above black[p]           */
+    uint16_t gain[4];        /* by CFA position, Q4.12, 256 .. 65535                              */
+    uint16_t lo[4];          /* by CFA position: measure takes lo[p] <= s < sat[p]                */
+    void *rec;               /* DEVICE memory, 8-byte aligned: nrec records of 64 bytes; or NULL  */
+    uint32_t nrec;           /* 0 (no record: chroma 0), 1 (one for the batch) or n (per frame)   */
+    uint32_t reserved;       /* must be 0                                                         */
+} mcraw_highlights;          /* sizeof 64; cfa 4, flags 8, top 12, black 16, sat 24, gain 32, lo 40, rec 48, nrec 56, reserved 60 */
+int mcraw_highlights_measure_batch(mcraw_ctx *ctx, const mcraw_highlights *h, const uint16_t *in, size_t in_pitch,
+                                   size_t in_frame_stride, int width, int height, int n, void *stream);
+int mcraw_highlights_batch(mcraw_ctx *ctx, const mcraw_highlights *h, const uint16_t *in, size_t in_pitch, size_t in_frame_stride,
+                           int width, int height, int n, uint16_t *out, size_t out_pitch, size_t out_frame_stride, void *stream);
+
 /* ---- environment ------------------------------------------------------------------------------
  * Read when a context (or pool) is created, never afterwards:
  *   MCRAW_DEVICE=n, MCRAW_DEVICES=all|0,1,5   default device of the five-argument entry points / members of a default pool

@@ -20,7 +20,8 @@ __all__ = ["lib_path", "load", "Context", "Pool", "Frame", "EncFrame", "FloatOut
            "shading_map", "Stats", "STATS_ACCUMULATE", "FrameStats", "stats_white_balance", "stats_percentile",
            "stats_clipped", "FixPix", "FIXPIX_HOT", "FIXPIX_COLD", "pack_pixels", "Denoise", "noise_lut", "Merge", "Align",
            "AlignCells", "Cells", "cell_grid", "align_window", "fit_crop", "Area", "RGB_AREA", "Resample", "RGB_RESAMPLE",
-           "FILTER_LINEAR", "FILTER_CUBIC", "Warp", "RGB_WARP", "quantize_affine", "fit_affine", "stabilize", "RGB_HA"]
+           "FILTER_LINEAR", "FILTER_CUBIC", "Warp", "RGB_WARP", "quantize_affine", "fit_affine", "stabilize", "RGB_HA",
+           "Highlights", "HighlightChroma", "HL_CLIP", "HL_REBUILD", "HL_ACCUMULATE", "highlight_gains"]
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 
@@ -52,6 +53,7 @@ ABI_SYMBOLS = [
     "mcraw_merge_batch", "mcraw_align_batch", "mcraw_align_work_bytes", "mcraw_demosaic_area_batch", "mcraw_area_work_bytes",
     "mcraw_demosaic_resample_batch", "mcraw_resample_work_bytes", "mcraw_demosaic_warp_batch",
     "mcraw_align_cells_batch", "mcraw_align_cells_work_bytes", "mcraw_merge_cells_batch",
+    "mcraw_highlights_measure_batch", "mcraw_highlights_batch",
 ]
 
 POST_BLACK, POST_PACK12, POST_PACK10, POST_PACK14 = 1, 2, 4, 8
@@ -574,6 +576,113 @@ def pack_pixels(xy):
     return np.ascontiguousarray(packed, dtype=np.uint32)
 
 
+# clipped highlights of mosaics (mcraw_highlights_batch, mcraw_highlights_measure_batch)
+HL_CLIP, HL_REBUILD = 0, 1
+HL_ACCUMULATE = 1
+_HL_MODES = {"clip": HL_CLIP, "rebuild": HL_REBUILD}
+_HL_KEYS = ("sat", "black", "gain", "cfa", "mode", "chroma", "lo", "top")
+
+
+class Highlights(C.Structure):
+    """struct mcraw_highlights (include/mcraw_hip.h): mode, cfa, flags, top, then black, sat, gain (Q4.12) and lo by CFA
+    position, the device records and how many there are."""
+    _fields_ = [("mode", C.c_uint32), ("cfa", C.c_uint32), ("flags", C.c_uint32), ("top", C.c_uint32),
+                ("black", C.c_uint16 * 4), ("sat", C.c_uint16 * 4), ("gain", C.c_uint16 * 4), ("lo", C.c_uint16 * 4),
+                ("rec", C.c_void_p), ("nrec", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class HighlightChroma:
+    """The records of Context.highlight_chroma: `raw`, an int64 tensor (R, 8) of R records of 64 bytes as the library lays them
+    out (R: N, or 1 for the whole batch); `sum`, int64 (R, 4), and `cnt`, int32 (R, 4), are views of it by CFA position: the sum
+    of v - ref over the pixels that took part and how many there were."""
+
+    def __init__(self, raw):
+        import torch
+        self.raw = raw
+        self.sum = raw[:, :4]
+        self.cnt = raw.view(torch.int32)[:, 8:12]
+
+    def cpu(self):
+        """(sum int64 (R, 4), cnt uint32 (R, 4)) as numpy arrays; synchronises."""
+        import numpy as np
+        a = self.raw.cpu().numpy()
+        return a[:, :4].copy(), np.ascontiguousarray(a[:, 4:6]).view(np.uint32).copy()
+
+
+def highlight_gains(gain, cfa="rggb"):
+    """The white-balance gains (r, g, b) that the demosaic methods take (rgb_color gives them) as the highlight stage takes
+    them: four Q4.12 integers by CFA position p = (y & 1) * 2 + (x & 1) for the sensor arrangement `cfa`, rint(g * 4096), where
+    16.0 itself becomes 65535.  Raises ValueError for a gain outside 1/16 .. 16 or not finite."""
+    import numpy as np
+    planes = cfa_planes(cfa)  # plane[p]: 0 R, 1 G (R row), 2 G (B row), 3 B
+    g = np.asarray(gain, dtype=np.float64).reshape(-1)
+    if g.size != 3 or not np.isfinite(g).all() or (g < 1.0 / 16.0).any() or (g > 16.0).any():
+        raise ValueError("highlight_gains: gain must be three finite values (r, g, b) in 1/16 .. 16, not %r" % (gain,))
+    q = np.minimum(np.rint(g * 4096.0), 65535.0).astype(np.int64)
+    return [int(q[(0, 1, 1, 2)[planes[p]]]) for p in range(4)]
+
+
+def _hl_struct(fn, sat, black, gain, cfa, lo, top, mode):
+    """struct mcraw_highlights for method `fn` from its arguments (rec, nrec and flags are left 0)."""
+    key = str(cfa).strip().lower()
+    if key not in _CFA_CODES:
+        raise ValueError("unknown cfa %r (rggb, bggr, grbg or gbrg)" % (cfa,))
+    if mode not in _HL_MODES:
+        raise ValueError("%s: mode must be 'rebuild' or 'clip', not %r" % (fn, mode))
+    four = lambda v: [v] * 4 if not hasattr(v, "__len__") else list(v)
+    sat, black = four(sat), four(black)
+    if len(sat) != 4 or len(black) != 4 or any(v != int(v) or v < 0 or v > 65535 for v in sat + black):
+        raise ValueError("%s: sat and black are one level or four, by CFA position (row & 1) * 2 + (col & 1), each an integer "
+                         "0 .. 65535" % fn)
+    sat, black = [int(v) for v in sat], [int(v) for v in black]
+    if any(s <= b for s, b in zip(sat, black)):
+        raise ValueError("%s: sat must be above black at every CFA position" % fn)
+    if gain is None:
+        raise ValueError("%s: gain is needed: (r, g, b) as the demosaic takes them, or four Q4.12 integers by CFA position" % fn)
+    gain = list(gain)
+    if len(gain) == 3:
+        gain = highlight_gains(gain, key)
+    elif len(gain) != 4 or any(v != int(v) or v < 256 or v > 65535 for v in gain):
+        raise ValueError("%s: gain is (r, g, b), or four Q4.12 integers 256 .. 65535 by CFA position" % fn)
+    lo = [b + (s - b) // 2 for s, b in zip(sat, black)] if lo is None else four(lo)
+    if len(lo) != 4 or any(v != int(v) or v < 0 or v > 65535 for v in lo):
+        raise ValueError("%s: lo is one level or four, each an integer 0 .. 65535" % fn)
+    if top != int(top) or top < 1 or top > 65535:
+        raise ValueError("%s: top must be an integer 1 .. 65535, not %r" % (fn, top))
+    s = Highlights()
+    s.mode, s.cfa, s.flags, s.top = _HL_MODES[mode], _CFA_CODES[key], 0, int(top)
+    for i in range(4):
+        s.black[i], s.sat[i], s.gain[i], s.lo[i] = black[i], sat[i], int(gain[i]), int(lo[i])
+    s.rec, s.nrec, s.reserved = None, 0, 0
+    return s
+
+
+def _hl_kwargs(fn, highlights, white, black, cfa, gain):
+    """The keyword arguments of Context.highlights() for highlights= of method `fn`: the dict's own, and for what it leaves out
+    the method's: sat from white, black, cfa and gain.  Raises ValueError for what is no dict, an unknown key, a gain per frame
+    with none in the dict (the stage takes one gain for the batch) and a fractional white without a sat."""
+    import numpy as np
+    if not isinstance(highlights, dict):
+        raise ValueError("%s: highlights must be a dict of highlights()' keyword arguments (without out)" % fn)
+    unknown = [k for k in highlights if k not in _HL_KEYS]
+    if unknown:
+        raise ValueError("%s: highlights has no key %r (%s)" % (fn, unknown[0], ", ".join(_HL_KEYS)))
+    kw = dict(highlights)
+    if "gain" not in kw:
+        g = None if gain is None else np.asarray(gain.cpu() if hasattr(gain, "cpu") else gain, dtype=np.float64)
+        if g is not None and g.ndim > 1:
+            raise ValueError("%s: highlights takes one gain for the batch; with a gain per frame give it one of its own "
+                             "('gain': (r, g, b))" % fn)
+        kw["gain"] = (1.0, 1.0, 1.0) if g is None else tuple(float(v) for v in g)
+    if "sat" not in kw:
+        if white != int(white):
+            raise ValueError("%s: highlights needs an integer 'sat' when white=%r is none" % (fn, white))
+        kw["sat"] = int(white)
+    kw.setdefault("black", black)
+    kw.setdefault("cfa", cfa)
+    return kw
+
+
 # noise-adaptive denoising of mosaics (mcraw_denoise_batch)
 class Denoise(C.Structure):
     """struct mcraw_denoise (include/mcraw_hip.h): radius, amount in Q8, the table's size and shift, how many tables, and the
@@ -1025,6 +1134,12 @@ def load():
     lib.mcraw_fixpix_batch.restype = C.c_int
     lib.mcraw_fixpix_batch.argtypes = [C.c_void_p, C.POINTER(FixPix), C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int,
                                        C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
+    lib.mcraw_highlights_measure_batch.restype = C.c_int
+    lib.mcraw_highlights_measure_batch.argtypes = [C.c_void_p, C.POINTER(Highlights), C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int,
+                                                   C.c_int, C.c_void_p]
+    lib.mcraw_highlights_batch.restype = C.c_int
+    lib.mcraw_highlights_batch.argtypes = [C.c_void_p, C.POINTER(Highlights), C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int,
+                                           C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
     lib.mcraw_denoise_batch.restype = C.c_int
     lib.mcraw_denoise_batch.argtypes = [C.c_void_p, C.POINTER(Denoise), C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int,
                                         C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
@@ -1609,6 +1724,88 @@ class Context:
             raise ValueError("%s: defects must be a dict of fix_pixels' keyword arguments (without counts and out)" % fn)
         return self.fix_pixels(mos, **{"black": black, **defects})
 
+    def highlight_chroma(self, mosaic, *, sat, black=(0, 0, 0, 0), gain, cfa="rggb", lo=None, scope="frame", into=None):
+        """Measure the colour that highlights() keeps when it rebuilds clipped samples (mcraw_highlights_measure_batch): per
+        CFA position the sum and the count of v - ref over the pixels with lo <= sample < sat whose eight neighbours are all
+        below their sat, where v is the white-balanced sample and ref the mean of the neighbours' other colours.  mosaic:
+        (N, H, W) or (H, W), H, W >= 2, rows contiguous (rows and frames may be strided).  sat, black: one level or four, by CFA
+        position (row & 1) * 2 + (col & 1).  gain: (r, g, b) as the demosaic takes them (highlight_gains makes the Q4.12 integers),
+        or four Q4.12 integers by CFA position.  lo=None: black + (sat - black) // 2.  scope "frame": one record per frame;
+        "batch": one for all frames.  into: a HighlightChroma (or its raw int64 tensor (R, 8), R as scope says) whose records
+        are added to instead of started anew: one record over a clip, against flicker.  Returns a HighlightChroma.  Queued on
+        torch.cuda.current_stream(); nothing synchronises."""
+        import torch
+        fn = "highlight_chroma"
+        dev = self._torch_device(torch)
+        mos, single, n, h, w = self._mosaic_arg(torch, dev, fn, mosaic)
+        if scope not in ("frame", "batch"):
+            raise ValueError("%s: scope must be 'frame' or 'batch', not %r" % (fn, scope))
+        s = _hl_struct(fn, sat, black, gain, cfa, lo, 65535, "rebuild")
+        if h < 2 or w < 2:
+            raise ValueError("%s: frames must be at least 2 x 2" % fn)
+        nrec = 1 if scope == "batch" else n
+        raw = into.raw if isinstance(into, HighlightChroma) else into
+        if raw is None:
+            raw = torch.zeros((nrec, 8), dtype=torch.int64, device=dev)  # (the call initialises them; an empty batch leaves zeros)
+        elif not isinstance(raw, torch.Tensor) or raw.dtype != torch.int64 or raw.device != dev or tuple(raw.shape) != (nrec, 8) \
+                or not raw.is_contiguous():
+            raise ValueError("%s: into must hold a contiguous int64 tensor %r on %s" % (fn, (nrec, 8), dev))
+        res = into if isinstance(into, HighlightChroma) else HighlightChroma(raw)
+        if n == 0:
+            return res
+        s.flags = HL_ACCUMULATE if into is not None else 0
+        s.rec, s.nrec = raw.data_ptr(), nrec
+        src = self._strided(fn, "the mosaic", mos, h, w)
+        self._call(torch, dev, "mcraw_highlights_measure_batch", (mos, raw), C.byref(s), *src, w, h, n)
+        return res
+
+    def highlights(self, mosaic, *, sat, black=(0, 0, 0, 0), gain, cfa="rggb", mode="rebuild", chroma="frame", lo=None, top=65535,
+                   out=None):
+        """Take the magenta out of clipped highlights of uint16 mosaics resident on the context's device (mcraw_highlights_batch),
+        in front of shading= and the demosaic.  A sample >= sat is clipped.  mode "clip": every CFA position is cut at the
+        level where the lowest white-balanced clip level lies, so a blown region becomes exactly neutral; no sample is raised.
+        mode "rebuild": a clipped sample becomes what its eight neighbours' other colours say, ref + chroma in white-balanced
+        units taken back to the sample's scale, where that is above the sample (and at most `top`); unclipped samples are
+        copied bit for bit and no sample is lowered.  The result is a mosaic of the same black level whose samples may exceed
+        sat; leave the demosaic's white= as it was, and rebuilt samples lie above 1.0 in front of the matrix.  sat, black, gain,
+        cfa, lo: as highlight_chroma().  chroma: "frame" or "batch" (highlight_chroma() with that scope runs first, back to back
+        on the same stream), None (no colour: the neighbours' mean as it is) or records that highlight_chroma() returned, one
+        or N.  out: None (a new contiguous tensor) or a uint16 tensor of the mosaic's shape that does not overlap it (there is
+        no in-place form).  Queued on torch.cuda.current_stream(); nothing synchronises."""
+        import torch
+        fn = "highlights"
+        dev = self._torch_device(torch)
+        mos, single, n, h, w = self._mosaic_arg(torch, dev, fn, mosaic)
+        s = _hl_struct(fn, sat, black, gain, cfa, lo, top, mode)
+        raw = None
+        if s.mode == HL_REBUILD and chroma is not None:
+            if isinstance(chroma, str):
+                if chroma not in ("frame", "batch"):
+                    raise ValueError("%s: chroma must be 'frame', 'batch', None or highlight_chroma()'s records, not %r" % (fn, chroma))
+            else:
+                raw = chroma.raw if isinstance(chroma, HighlightChroma) else chroma
+                if not isinstance(raw, torch.Tensor) or raw.dtype != torch.int64 or raw.device != dev or raw.dim() != 2 \
+                        or int(raw.shape[1]) != 8 or int(raw.shape[0]) not in (1, n) or not raw.is_contiguous():
+                    raise ValueError("%s: chroma records must be a contiguous int64 tensor (1, 8) or (%d, 8) on %s" % (fn, n, dev))
+        out = self._out_arg(torch, dev, fn, out, mosaic.shape)
+        if n == 0 or h == 0 or w == 0:
+            return out
+        if h < 2 or w < 2:
+            raise ValueError("%s: frames must be at least 2 x 2" % fn)
+        if s.mode == HL_REBUILD and isinstance(chroma, str):
+            raw = self.highlight_chroma(mos, sat=list(s.sat), black=list(s.black), gain=list(s.gain), cfa=cfa, lo=list(s.lo), scope=chroma).raw
+        if raw is not None:
+            s.rec, s.nrec = raw.data_ptr(), int(raw.shape[0])
+        src = self._strided(fn, "the mosaic", mos, h, w)
+        dst = self._strided(fn, "out", out.unsqueeze(0) if single else out, h, w)
+        self._call(torch, dev, "mcraw_highlights_batch", (mos, out, raw), C.byref(s), *src, w, h, n, *dst)
+        return out
+
+    def _highlights_stage(self, mos, highlights, fn, white, black, cfa, gain):
+        """highlights= of the demosaic / decode methods: highlights() with these keyword arguments (_hl_kwargs fills in the
+        method's own) into a scratch tensor of the caching allocator."""
+        return self.highlights(mos, **_hl_kwargs(fn, highlights, white, black, cfa, gain))
+
     def denoise(self, mosaic, lut, shift, radius=2, amount=1.0, out=None):
         """Noise-adaptive smoothing of uint16 mosaics resident on the context's device (mcraw_denoise_batch): every pixel
         becomes the weighted mean of itself and its 8 (radius 1) or 24 (radius 2) neighbours of the same colour (distances
@@ -1921,7 +2118,7 @@ class Context:
         return self.merge(scratch, lut, shift, **merge_kw)
 
     def demosaic(self, mosaic, *, algo="mhc", dtype, white, black=(0, 0, 0, 0), cfa="rggb", gain=None, matrix=None,
-                 clip=False, out=None, check=True, shading=None, defects=None, denoise=None, size=None, crop=None, filter=None, affine=None):
+                 clip=False, out=None, check=True, shading=None, defects=None, denoise=None, size=None, crop=None, filter=None, affine=None, highlights=None):
         """uint16 mosaics resident on the context's device -> planar linear RGB, (N, 3, H, W) for algo "mhc" (Malvar-He-
         Cutler) or (N, 3, H/2, W/2) for "bin2" (one pixel per 2x2 quad), as torch.float32 / float16 / bfloat16 ("f32" /
         "f16" / "bf16").  mosaic: a CUDA uint16 tensor (N, H, W) or (H, W) whose rows are contiguous (rows and frames may
@@ -1935,7 +2132,12 @@ class Context:
         defaults to this call's): the defective pixels are taken out first, into a scratch tensor, in front of shading=
         (gains change the differences between neighbours); None: no such stage.  denoise: a dict of denoise()'s
         keyword arguments (lut, shift, radius, amount), applied behind defects= and in front of shading=, into a scratch
-        tensor: the noise model holds for the sensor's values, not for the shaded ones; None: no such stage.
+        tensor: the noise model holds for the sensor's values, not for the shaded ones; None: no such stage.  highlights: a dict
+        of highlights()' keyword arguments (mode, chroma, sat, lo, top, black, gain, cfa), applied behind denoise= and in front
+        of shading= (gains move the clip level by position), into a scratch tensor; what the dict leaves out comes from this
+        call: sat from white, black, cfa and gain (one gain for the batch: with a gain per frame the dict must bring its own,
+        else ValueError).  An unknown key raises ValueError.  white= stays what it is: rebuilt samples lie above it.  None: no
+        such stage.
         algo "area" with size=(Ho, Wo) and crop=(y0, x0, h, w) (default: the whole frame; fit_crop gives a centred one of the
         output's aspect ratio) is an area downscale (mcraw_demosaic_area_batch): every output pixel is the average of the
         CFA quads under its footprint in the crop, 1 .. 16 quads per pixel along each axis, the origin and size of the crop
@@ -1962,7 +2164,8 @@ class Context:
         import torch
         code = _float_code(dtype)
         tdtype = {FLOAT_F32: torch.float32, FLOAT_F16: torch.float16, FLOAT_BF16: torch.bfloat16}[code]
-        front = self._demosaic_front("demosaic", mosaic, algo, cfa, black, defects, denoise, shading, size, crop, filter, affine)
+        front = self._demosaic_front("demosaic", mosaic, algo, cfa, black, defects, denoise, shading, size, crop, filter, affine,
+                                     highlights, white, gain)
         ho, wo = front.ho, front.wo
         out = self._demosaic_out("demosaic", front, out, (3, ho, wo), tdtype)
         if front.n == 0:
@@ -1970,9 +2173,10 @@ class Context:
         return self._demosaic_call("mcraw_demosaic_batch", "demosaic", front, algo, code, FLOAT_CLIP if clip else 0, white, black,
                                    gain, matrix, out)
 
-    def _demosaic_front(self, fn, mosaic, algo, cfa, black, defects, denoise, shading, size=None, crop=None, filter=None, affine=None):
+    def _demosaic_front(self, fn, mosaic, algo, cfa, black, defects, denoise, shading, size=None, crop=None, filter=None, affine=None,
+                        highlights=None, white=None, gain=None):
         """What demosaic / demosaic_display / demosaic_yuv (`fn`) do alike in front of their output: the algo and cfa checks,
-        the mosaic argument, the optional stages -- defects, then denoise, then shading, each into a scratch tensor (the
+        the mosaic argument, the optional stages -- defects, then denoise, then highlights, then shading, each into a scratch tensor (the
         caller's mosaic stays as it is), none for an empty batch -- and the output size (`size` for the scaled algos).  Returns a
         _Front."""
         import torch
@@ -2002,7 +2206,7 @@ class Context:
             raise ValueError("unknown cfa %r (rggb, bggr, grbg or gbrg)" % (cfa,))
         dev = self._torch_device(torch)
         mos, single = self._mosaic_arg(torch, dev, fn, mosaic)[:2]
-        mos = self._pre_stages(fn, mos, black, defects, denoise)
+        mos = self._pre_stages(fn, mos, black, defects, denoise, highlights, white, key, gain)
         if shading is not None and mos.numel():  # into a scratch tensor: the caller's mosaic stays as it is
             mos = self.shade(mos, shading, black=black)
         n, h, w = (int(v) for v in mos.shape)
@@ -2028,13 +2232,15 @@ class Context:
             ho, wo = (h, w) if algo in ("mhc", "ha") else (h // 2, w // 2)
         return _Front(mos, single, n, h, w, src, ho, wo, key, area, filt, maps if warp else None)
 
-    def _pre_stages(self, fn, mos, black, defects, denoise):
-        """defects= and denoise= of the demosaic / decode methods, in that order, each into a scratch tensor; an empty batch
-        passes through."""
+    def _pre_stages(self, fn, mos, black, defects, denoise, highlights=None, white=None, cfa=None, gain=None):
+        """defects=, denoise= and highlights= of the demosaic / decode methods, in that order, each into a scratch tensor; an
+        empty batch passes through."""
         if defects is not None and mos.numel():  # in front of the gains
             mos = self._fix_defects(mos, defects, black, fn)
         if denoise is not None and mos.numel():  # on the sensor's values: behind the defects, in front of the gains
             mos = self._denoise_stage(mos, denoise, fn)
+        if highlights is not None and mos.numel():  # behind the denoiser, in front of the gains, which move the clip level by position
+            mos = self._highlights_stage(mos, highlights, fn, white, black, cfa, gain)
         return mos
 
     def _demosaic_out(self, fn, front, out, frame_shape, tdtype):
@@ -2115,17 +2321,19 @@ class Context:
                         fn, len(bad), n, ", ".join("frame %d status 0x%x" % b for b in bad[:16])))
         return scratch
 
-    def _decode_front(self, fn, inputs, width, height, type, check, black, defects, denoise, shading):
+    def _decode_front(self, fn, inputs, width, height, type, check, black, defects, denoise, shading, highlights=None, white=None,
+                      cfa=None, gain=None):
         """The scratch mosaics of decode_rgb / decode_display / decode_yuv (`fn`), ready for the demosaic: decoded, then
-        defects= and denoise= (each into a further scratch tensor), then shading= in place."""
-        scratch = self._pre_stages(fn, self._decode_scratch(inputs, width, height, type, check, fn), black, defects, denoise)
+        defects=, denoise= and highlights= (each into a further scratch tensor), then shading= in place."""
+        scratch = self._pre_stages(fn, self._decode_scratch(inputs, width, height, type, check, fn), black, defects, denoise, highlights,
+                                   white, cfa, gain)
         if shading is not None:
             self.shade(scratch, shading, black=black, out=scratch)
         return scratch
 
     def decode_rgb(self, inputs, width, height, type, *, algo="mhc", dtype, white, black=(0, 0, 0, 0), cfa="rggb",
                    gain=None, matrix=None, clip=False, out=None, check=True, shading=None, defects=None, denoise=None, size=None,
-                   crop=None, filter=None, affine=None):
+                   crop=None, filter=None, affine=None, highlights=None):
         """Decode frames of one geometry that are resident in HBM and demosaic them (demosaic()): (N, 3, H, W) for "mhc",
         (N, 3, H/2, W/2) for "bin2", (N, 3, Ho, Wo) for "area" with size=(Ho, Wo) and crop=.  inputs: uint8 CUDA tensors, or (device pointer, length) pairs.  The plain uint16
         mosaics go to a scratch tensor of torch's caching allocator; both steps are queued on torch.cuda.current_stream().
@@ -2133,8 +2341,10 @@ class Context:
         at once.  The stage the context had before the call is restored afterwards.  shading: a lens-shading gain map
         (shade()), applied to the scratch mosaics in place before the demosaic.  defects: a dict of fix_pixels()' keyword
         arguments (black defaults to this call's), applied in front of shading= into a second scratch tensor.  denoise: a
-        dict of denoise()'s keyword arguments, applied behind defects= and in front of shading=."""
-        scratch = self._decode_front("decode_rgb", inputs, width, height, type, check, black, defects, denoise, shading)
+        dict of denoise()'s keyword arguments, applied behind defects= and in front of shading=.  highlights: a dict of
+        highlights()' keyword arguments, as demosaic() fills it in, applied behind denoise= and in front of shading=."""
+        scratch = self._decode_front("decode_rgb", inputs, width, height, type, check, black, defects, denoise, shading, highlights,
+                                     white, cfa, gain)
         return self.demosaic(scratch, algo=algo, dtype=dtype, white=white, black=black, cfa=cfa, gain=gain, matrix=matrix,
                              clip=clip, out=out, check=check, size=size, crop=crop, filter=filter, affine=affine)
 
@@ -2169,7 +2379,7 @@ class Context:
 
     def demosaic_display(self, mosaic, *, algo="mhc", white, black=(0, 0, 0, 0), cfa="rggb", gain=None, matrix=None,
                          transfer="srgb", lut_size=4096, dtype=None, layout="hwc", bits=None, out=None, check=True, shading=None,
-                         defects=None, denoise=None, size=None, crop=None, filter=None, affine=None):
+                         defects=None, denoise=None, size=None, crop=None, filter=None, affine=None, highlights=None):
         """uint16 mosaics resident on the context's device -> display-ready integer RGB: the demosaic and colours of
         demosaic(), then clamp to [0, 1], index a transfer-curve LUT of L entries at rint(c * (L - 1)) and store the entry
         (its low byte for uint8).  dtype: torch.uint8 (default) or torch.uint16; layout "hwc" gives (N, Ho, Wo, 3), "chw"
@@ -2177,8 +2387,8 @@ class Context:
         on [0, 1] -- built by transfer_lut(transfer, lut_size, bits), bits 8 for uint8 and 16 for uint16 unless given --
         or a ready 1-D uint16 LUT (host array or CUDA tensor) whose length is a power of two, 256 .. 65536.  Queued on
         torch.cuda.current_stream(); nothing synchronises, and a caller's LUT is read when the kernels run (in stream
-        order).  `check` is accepted for symmetry with decode_display.  shading, defects, denoise, and algo "area" with size=
-        and crop=: as demosaic()."""
+        order).  `check` is accepted for symmetry with decode_display.  shading, defects, denoise, highlights, and algo
+        "area" with size= and crop=: as demosaic()."""
         import torch
         dtype = torch.uint8 if dtype is None else dtype
         dcode = {torch.uint8: DISP_U8, torch.uint16: DISP_U16, "u8": DISP_U8, "u16": DISP_U16}.get(dtype)
@@ -2186,7 +2396,8 @@ class Context:
             raise ValueError("demosaic_display: dtype must be torch.uint8 or torch.uint16, not %r" % (dtype,))
         if layout not in _DISP_LAYOUTS:
             raise ValueError("demosaic_display: layout must be 'hwc' or 'chw', not %r" % (layout,))
-        front = self._demosaic_front("demosaic_display", mosaic, algo, cfa, black, defects, denoise, shading, size, crop, filter, affine)
+        front = self._demosaic_front("demosaic_display", mosaic, algo, cfa, black, defects, denoise, shading, size, crop, filter, affine,
+                                     highlights, white, gain)
         ho, wo = front.ho, front.wo
         out = self._demosaic_out("demosaic_display", front, out, (ho, wo, 3) if layout == "hwc" else (3, ho, wo),
                                  torch.uint8 if dcode == DISP_U8 else torch.uint16)
@@ -2202,19 +2413,20 @@ class Context:
 
     def decode_display(self, inputs, width, height, type, *, algo="mhc", white, black=(0, 0, 0, 0), cfa="rggb", gain=None,
                        matrix=None, transfer="srgb", lut_size=4096, dtype=None, layout="hwc", bits=None, out=None, check=True, shading=None,
-                       defects=None, denoise=None, size=None, crop=None, filter=None, affine=None):
+                       defects=None, denoise=None, size=None, crop=None, filter=None, affine=None, highlights=None):
         """Decode frames of one geometry that are resident in HBM and turn them into display-ready RGB
         (demosaic_display()), as decode_rgb does: the plain uint16 mosaics go to a scratch tensor, both steps are queued on
         torch.cuda.current_stream(), check=True synchronises after the decode and raises McrawError naming the frames that
-        failed, and the context's stage is restored afterwards.  shading, defects, denoise: as decode_rgb()."""
-        scratch = self._decode_front("decode_display", inputs, width, height, type, check, black, defects, denoise, shading)
+        failed, and the context's stage is restored afterwards.  shading, defects, denoise, highlights: as decode_rgb()."""
+        scratch = self._decode_front("decode_display", inputs, width, height, type, check, black, defects, denoise, shading, highlights,
+                                     white, cfa, gain)
         return self.demosaic_display(scratch, algo=algo, white=white, black=black, cfa=cfa, gain=gain, matrix=matrix,
                                      transfer=transfer, lut_size=lut_size, dtype=dtype, layout=layout, bits=bits, out=out,
                                      check=check, size=size, crop=crop, filter=filter, affine=affine)
 
     def demosaic_yuv(self, mosaic, *, algo="mhc", white, black=(0, 0, 0, 0), cfa="rggb", gain=None, matrix=None, fmt="nv12",
                      standard="bt709", range="limited", transfer="bt709", lut_size=4096, in_bits=None, out=None, check=True, shading=None,
-                     defects=None, denoise=None, size=None, crop=None, filter=None, affine=None):
+                     defects=None, denoise=None, size=None, crop=None, filter=None, affine=None, highlights=None):
         """uint16 mosaics resident on the context's device -> video-ready Y'CbCr 4:2:0: the demosaic, colours, clamp and
         transfer-curve LUT of demosaic_display(), then the integer matrix of yuv_matrix(standard, range) and a 2x2 box
         average for the chroma (sited at the block's centre).  fmt "nv12": torch.uint8; "p010": torch.uint16 holding
@@ -2223,15 +2435,16 @@ class Context:
         gives the two as views.  Ho and Wo must be even (bin2: H and W multiples of 4).  transfer: as demosaic_display; a
         built-in curve is transfer_lut(transfer, lut_size, in_bits), in_bits defaulting to 12 (nv12) or 16 (p010); a ready
         LUT may hold entries of any in_bits 8 .. 16 (higher bits are masked off).  Queued on torch.cuda.current_stream();
-        nothing synchronises.  `check` is accepted for symmetry with decode_yuv.  shading, defects, denoise, and algo "area"
-        with size= (both even) and crop=: as demosaic()."""
+        nothing synchronises.  `check` is accepted for symmetry with decode_yuv.  shading, defects, denoise, highlights, and algo
+        "area" with size= (both even) and crop=: as demosaic()."""
         import torch
         if fmt not in _YUV_FORMATS:
             raise ValueError("demosaic_yuv: fmt must be 'nv12' or 'p010', not %r" % (fmt,))
         fcode, bits, default_in = _YUV_FORMATS[fmt]
         in_bits = default_in if in_bits is None else in_bits
         cy, cb, cr, sh, y_off, c_off = yuv_matrix(standard, range, bits, in_bits)
-        front = self._demosaic_front("demosaic_yuv", mosaic, algo, cfa, black, defects, denoise, shading, size, crop, filter, affine)
+        front = self._demosaic_front("demosaic_yuv", mosaic, algo, cfa, black, defects, denoise, shading, size, crop, filter, affine,
+                                     highlights, white, gain)
         ho, wo = front.ho, front.wo
         out = self._demosaic_out("demosaic_yuv", front, out, (ho * 3 // 2, wo), torch.uint8 if fcode == YUV_NV12 else torch.uint16)
         if front.n == 0:
@@ -2248,12 +2461,13 @@ class Context:
 
     def decode_yuv(self, inputs, width, height, type, *, algo="mhc", white, black=(0, 0, 0, 0), cfa="rggb", gain=None,
                    matrix=None, fmt="nv12", standard="bt709", range="limited", transfer="bt709", lut_size=4096, in_bits=None,
-                   out=None, check=True, shading=None, defects=None, denoise=None, size=None, crop=None, filter=None, affine=None):
+                   out=None, check=True, shading=None, defects=None, denoise=None, size=None, crop=None, filter=None, affine=None, highlights=None):
         """Decode frames of one geometry that are resident in HBM and turn them into NV12 / P010 (demosaic_yuv()), as
         decode_display does: the plain uint16 mosaics go to a scratch tensor, both steps are queued on
         torch.cuda.current_stream(), check=True synchronises after the decode and raises McrawError naming the frames that
-        failed, and the context's stage is restored afterwards.  shading, defects, denoise: as decode_rgb()."""
-        scratch = self._decode_front("decode_yuv", inputs, width, height, type, check, black, defects, denoise, shading)
+        failed, and the context's stage is restored afterwards.  shading, defects, denoise, highlights: as decode_rgb()."""
+        scratch = self._decode_front("decode_yuv", inputs, width, height, type, check, black, defects, denoise, shading, highlights,
+                                     white, cfa, gain)
         return self.demosaic_yuv(scratch, algo=algo, white=white, black=black, cfa=cfa, gain=gain, matrix=matrix, fmt=fmt,
                                  standard=standard, range=range, transfer=transfer, lut_size=lut_size, in_bits=in_bits, out=out,
                                  check=check, size=size, crop=crop, filter=filter, affine=affine)

@@ -40,13 +40,15 @@ def _run(cmd):
     subprocess.run(cmd, check=True)
 
 
-# The gfx950 library: kernels (mcraw_type7 / mcraw_type6, the encoder mcraw_encode7, the demosaic mcraw_rgb, the lens-shading stage mcraw_shade, the statistics mcraw_stats, the defective-pixel stage mcraw_fixpix, the denoiser mcraw_denoise, the temporal merge mcraw_merge, the shift estimate mcraw_align and its cell-wise form mcraw_cells, the area-average demosaic mcraw_area, the resampling demosaic mcraw_resample, the affine warp mcraw_warp, the edge-directed demosaic mcraw_ha), the host side of the C ABI in its units (csrc/mcraw_host.h) and the device pool.
+# The gfx950 library: kernels (mcraw_type7 / mcraw_type6, the encoder mcraw_encode7, the demosaic mcraw_rgb, the lens-shading stage mcraw_shade, the statistics mcraw_stats, the defective-pixel stage mcraw_fixpix, the denoiser mcraw_denoise, the temporal merge mcraw_merge, the shift estimate mcraw_align and its cell-wise form mcraw_cells, the area-average demosaic mcraw_area, the resampling demosaic mcraw_resample, the affine warp mcraw_warp, the edge-directed demosaic mcraw_ha, the highlight stage mcraw_highlights), the host side of the C ABI in its units (csrc/mcraw_host.h) and the device pool.
 HIP_SOURCES = ("mcraw_abi.hip", "mcraw_submit.hip", "mcraw_tune.hip", "mcraw_device.hip", "mcraw_hostmem.hip", "mcraw_pool.hip",
                "mcraw_type7.hip", "mcraw_type6.hip", "mcraw_encode7.hip", "mcraw_rgb.hip", "mcraw_shade.hip", "mcraw_stats.hip",
-               "mcraw_fixpix.hip", "mcraw_denoise.hip", "mcraw_merge.hip", "mcraw_align.hip", "mcraw_area.hip", "mcraw_resample.hip", "mcraw_cells.hip", "mcraw_warp.hip", "mcraw_ha.hip")
+               "mcraw_fixpix.hip", "mcraw_denoise.hip", "mcraw_merge.hip", "mcraw_align.hip", "mcraw_area.hip", "mcraw_resample.hip", "mcraw_cells.hip", "mcraw_warp.hip", "mcraw_ha.hip",
+               "mcraw_highlights.hip")
 HIP_HEADERS = ("mcraw_plan.h", "mcraw_dev.h", "mcraw_host.h", "mcraw_race.h", "mcraw_mosaic.h", "mcraw_mosaic_args.h",
                "mcraw_rgb_args.h", "mcraw_align_args.h", "mcraw_area_args.h", "mcraw_rgb_dev.h", "mcraw_rgb_launch.h",
-               "mcraw_resample_args.h", "mcraw_rgb_paths.h", "mcraw_align_pyr.h", "mcraw_cells_args.h", "mcraw_warp_args.h", "mcraw_ha_args.h")
+               "mcraw_resample_args.h", "mcraw_rgb_paths.h", "mcraw_align_pyr.h", "mcraw_cells_args.h", "mcraw_warp_args.h", "mcraw_ha_args.h",
+               "mcraw_highlights_args.h")
 HIP_FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc"]
 
 
