@@ -633,6 +633,60 @@ int mcraw_demosaic_warp_batch(mcraw_ctx *ctx, const mcraw_rgb *p, const mcraw_wa
                               const uint16_t *in, size_t in_pitch, size_t in_frame_stride, int width, int height, int n,
                               void *out, size_t out_bytes, void *stream);
 
+/* ---- uint16 mosaics -> the MHC image sampled along one displacement mesh per frame: lens geometry, local motion ------
+ *
+ * The affine warp above with the position of every output pixel taken from a mesh of source positions in DEVICE memory instead
+ * of six numbers in host memory: lens distortion (DNG WarpRectilinear, a vendor grid), rolling-shutter wobble, parallax, a
+ * projective map.  Output family, `p`, `d`, `y`, `colors`, in, out: as mcraw_demosaic_warp_batch; p->algo must be
+ * MCRAW_RGB_MESH, which every other entry point keeps rejecting.
+ * A mesh is My x Mx nodes, My = ceil(out_h / 32) + 1, Mx = ceil(out_w / 32) + 1 (MCRAW_MESH_STEP output pixels between nodes,
+ * both axes: one node per corner of the kernel's tile).  A node is two int32, (Y, X): node (a, b) is the source position of
+ * output pixel (32 a, 32 b) in 1/256 sample.  Row-major, contiguous, 8-byte aligned, meshes back to back; nmesh is 1 (one mesh
+ * for the batch: a lens) or n (one per frame: a clip).  The nodes are read by the queued kernel in stream order and never copied:
+ * a kernel that wrote them earlier on the stream is seen, and nothing waits for the host.
+ * Output pixel (i, k) has a = i >> 5, u = i & 31, b = k >> 5, v = k & 31 and, with Y00 .. Y11 the Y of nodes (a, b), (a, b + 1),
+ * (a + 1, b), (a + 1, b + 1), the position (exact in 64 bits, arithmetic shift)
+ *   Yr = (Y00 (32-u)(32-v) + Y01 (32-u) v + Y10 u (32-v) + Y11 u v + 512) >> 10        Y = min(max(Yr, 0), 256 (height - 1))
+ * and X likewise with `width`.  The clamp is per pixel, not per node (a node behind the last partial tile may lie anywhere): a
+ * position that leaves the frame reads the frame's edge.  Adjacent tiles agree on their common edge.
+ * The window of a tile (its rows i0 .. i1, columns k0 .. k1): over the clamped positions of its four corner pixels (i0 | i1,
+ * k0 | k1), with ylo, yhi, xlo, xhi their extremes,
+ *   pb = ((ylo >> 8) - 1) & ~1     np = (((yhi >> 8) + 2 - pb) >> 1) + 1     np' = min(np, 26)
+ *   eb = ((xlo >> 8) - 1) & ~7     ne = (((xhi >> 8) + 2 - eb) >> 3) + 1     ne' = min(ne, 8)
+ * A pixel's first tap row iy - 1 is clamped to [pb, pb + 2 np' - 4], its first tap column ix - 1 to [eb, eb + 8 ne' - 4]; the
+ * phases py, px stay those of (Y, X).  A bilinear function takes its extremes over a rectangle at its corners, and the floor and
+ * the clamp are monotone, so the four corner pixels bound every position of the tile: in the regime np <= 26, ne <= 8 -- every
+ * map inside the affine warp's bounds, and zoom-out to 0.75 anywhere -- the tap clamp never acts.  Outside it the result is
+ * still defined and deterministic for ANY node content: no tap and no staged sample leaves the frame by more than 4.
+ * From (Y, X) and the tap origin on everything is mcraw_demosaic_warp_batch's: the phase table of `filter`, horizontally first
+ * with the two roundings, e_c = MCRAW_RGB_MHC's estimates of the whole frame reflected 101, k[c] = (gain[c] * inv) * 0.0625f,
+ * then the family's stage.  A mesh with nodes 256 (32 a + ty, 32 b + tx) gives MCRAW_RGB_MHC's output cut at (ty, tx), bit for
+ * bit, in every family and for both filters; the mesh of a map with the identity linear part (fractional translation included)
+ * gives mcraw_demosaic_warp_batch's output under that map, bit for bit; a flat frame stays flat and greys stay neutral.
+ * mcraw_mesh_nodes: My * Mx, or 0 for a rejected geometry.  mcraw_mesh_check: nmesh >= 1 meshes in HOST memory against width x
+ * height frames, without a GPU or a context: 0, or < 0 with mcraw_last_error ("mcraw_mesh_check: ...") naming the first frame
+ * and tile (ty, tx) whose window leaves the regime; with flags & 1 also the first tile where a corner pixel's unclamped position
+ * leaves the frame.
+ * Rejected (returns < 0, mcraw_last_error says why, starting with "mcraw_demosaic_mesh_batch: ", nothing is written):
+ * everything the family's own entry point rejects; a NULL `m` or `nodes`; a p->algo other than MCRAW_RGB_MESH; both `d` and
+ * `y`; a frame under 8 x 8 or odd; a non-zero `reserved`; an unknown filter; a size outside 1 .. 65536, or odd for the YUV
+ * family; nmesh other than 1 or n; `nodes` not 8-byte aligned; nodes_bytes below nmesh * My * Mx * 8.  n == 0 is a no-op.  The
+ * call needs no scratch, takes no decode serial, leaves the decode slots, mcraw_ctx_errors and the context's stage alone, and
+ * has no kernel id of its own. */
+#define MCRAW_RGB_MESH  7      /* valid in mcraw_demosaic_mesh_batch only */
+#define MCRAW_MESH_STEP 32     /* output pixels between nodes, both axes   */
+typedef struct mcraw_mesh {
+    uint32_t out_w, out_h;  /* Wo, Ho                                               */
+    uint32_t filter;        /* MCRAW_FILTER_*                                       */
+    uint32_t reserved;      /* must be 0                                            */
+} mcraw_mesh;               /* sizeof 16; out_h 4, filter 8, reserved 12 */
+size_t mcraw_mesh_nodes(const mcraw_mesh *m);  /* My * Mx, 0 for a rejected geometry */
+int mcraw_mesh_check(const mcraw_mesh *m, const int32_t *nodes_host, int nmesh, int width, int height, int flags);
+int mcraw_demosaic_mesh_batch(mcraw_ctx *ctx, const mcraw_rgb *p, const mcraw_mesh *m, const mcraw_display *d,
+                              const mcraw_yuv *y, const mcraw_rgb_color *colors, int ncolors, const int32_t *nodes,
+                              size_t nodes_bytes, int nmesh, const uint16_t *in, size_t in_pitch, size_t in_frame_stride,
+                              int width, int height, int n, void *out, size_t out_bytes, void *stream);
+
 /* ---- uint16 mosaics -> uint16 mosaics with a lens-shading gain map applied ----------------------------------------
  *
  * Multiplies what `n` uint16 mosaics of width x height hold above their black level by a per-pixel gain that is bilinearly

@@ -21,6 +21,7 @@ __all__ = ["lib_path", "load", "Context", "Pool", "Frame", "EncFrame", "FloatOut
            "stats_clipped", "FixPix", "FIXPIX_HOT", "FIXPIX_COLD", "pack_pixels", "Denoise", "noise_lut", "Merge", "Align",
            "AlignCells", "Cells", "cell_grid", "align_window", "fit_crop", "Area", "RGB_AREA", "Resample", "RGB_RESAMPLE",
            "FILTER_LINEAR", "FILTER_CUBIC", "Warp", "RGB_WARP", "quantize_affine", "fit_affine", "stabilize", "RGB_HA",
+           "Mesh", "RGB_MESH", "MESH_STEP", "mesh_grid", "affine_mesh", "distortion_mesh", "stabilize_mesh", "mesh_check",
            "Highlights", "HighlightChroma", "HL_CLIP", "HL_REBUILD", "HL_ACCUMULATE", "highlight_gains"]
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
@@ -54,6 +55,7 @@ ABI_SYMBOLS = [
     "mcraw_demosaic_resample_batch", "mcraw_resample_work_bytes", "mcraw_demosaic_warp_batch",
     "mcraw_align_cells_batch", "mcraw_align_cells_work_bytes", "mcraw_merge_cells_batch",
     "mcraw_highlights_measure_batch", "mcraw_highlights_batch",
+    "mcraw_mesh_nodes", "mcraw_mesh_check", "mcraw_demosaic_mesh_batch",
 ]
 
 POST_BLACK, POST_PACK12, POST_PACK10, POST_PACK14 = 1, 2, 4, 8
@@ -134,8 +136,11 @@ RGB_AREA = 3  # mcraw_demosaic_area_batch only
 RGB_RESAMPLE = 4  # mcraw_demosaic_resample_batch only
 RGB_WARP = 5  # mcraw_demosaic_warp_batch only
 RGB_HA = 6  # the edge-directed demosaic (Hamilton-Adams): full resolution, valid where RGB_MHC is
+RGB_MESH = 7  # mcraw_demosaic_mesh_batch only
+MESH_STEP = 32  # output pixels between the nodes of a mesh, both axes
 FILTER_LINEAR, FILTER_CUBIC = 0, 1
-_RGB_ALGOS = {"mhc": RGB_MHC, "bin2": RGB_BIN2, "area": RGB_AREA, "resample": RGB_RESAMPLE, "warp": RGB_WARP, "ha": RGB_HA}
+_RGB_ALGOS = {"mhc": RGB_MHC, "bin2": RGB_BIN2, "area": RGB_AREA, "resample": RGB_RESAMPLE, "warp": RGB_WARP, "ha": RGB_HA,
+              "mesh": RGB_MESH}
 _FILTERS = {"linear": FILTER_LINEAR, "cubic": FILTER_CUBIC}
 _CFA_CODES = {"rggb": 0, "bggr": 1, "grbg": 2, "gbrg": 3}
 
@@ -168,6 +173,11 @@ class Warp(C.Structure):
     _fields_ = [("out_w", C.c_uint32), ("out_h", C.c_uint32), ("filter", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class Mesh(C.Structure):
+    """struct mcraw_mesh (include/mcraw_hip.h): the output size and the filter of mcraw_demosaic_mesh_batch."""
+    _fields_ = [("out_w", C.c_uint32), ("out_h", C.c_uint32), ("filter", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 # The scaled algos of the demosaic methods (size=, crop=): algo -> (the window struct, the library's work-bytes function, its entry
 # point for the three families, the geometry rule as the ValueError states it).
 _SCALED = {
@@ -180,8 +190,9 @@ _SCALED = {
 # What the demosaic methods know in front of their output (Context._demosaic_front).  mos: the mosaics (N, H, W) behind the
 # optional stages; single: the caller's was (H, W); n, h, w: their shape; src: _strided's triple (None for no frames); ho, wo: the
 # output size; key: the cfa's; area: the (y0, x0, h, w) crop of a scaled algo (None for the others); filt: the MCRAW_FILTER_* code
-# of algo "resample" and "warp" (None for the others); maps: the int32 (nmaps, 6) host array of algo "warp" (None for the others).
-_Front = collections.namedtuple("_Front", "mos single n h w src ho wo key area filt maps", defaults=(None,))
+# of algo "resample", "warp" and "mesh" (None for the others); maps: the int32 (nmaps, 6) host array of algo "warp" (None for the
+# others); mesh: the int32 (nmesh, My, Mx, 2) device tensor of algo "mesh" (None for the others).
+_Front = collections.namedtuple("_Front", "mos single n h w src ho wo key area filt maps mesh", defaults=(None, None))
 
 
 def fit_crop(height, width, Ho, Wo, algo="area"):
@@ -335,6 +346,187 @@ def stabilize(D, height, width, size, window=0, limit=True):
                                  % (t, ho, wo, name))
             maps[t, base + 2] = min(max(int(m[base + 2]), lo), hi)
     return maps
+
+
+def mesh_grid(Ho, Wo):
+    """(My, Mx): the nodes of the mesh of an Ho x Wo output, ceil(Ho / 32) + 1 and ceil(Wo / 32) + 1 (host only)."""
+    for v in (Ho, Wo):
+        if isinstance(v, bool) or v != int(v) or not 1 <= int(v) <= 65536:
+            raise ValueError("mesh_grid: Ho and Wo must be integers 1 .. 65536, not %r" % (v,))
+    return (int(Ho) + MESH_STEP - 1) // MESH_STEP + 1, (int(Wo) + MESH_STEP - 1) // MESH_STEP + 1
+
+
+def _mesh_size(fn, size):
+    try:
+        ho, wo = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError("%s: size must be (Ho, Wo)" % fn) from None
+    if not (1 <= ho <= 65536 and 1 <= wo <= 65536):
+        raise ValueError("%s: size must be (Ho, Wo), both 1 .. 65536, not %r" % (fn, size))
+    return ho, wo
+
+
+def _mesh_round(fn, v):
+    """floor(v * 256 + 0.5) as int32; ValueError where that is not finite or leaves int32."""
+    import numpy as np
+    q = np.floor(np.asarray(v, dtype=np.float64) * 256.0 + 0.5)
+    if not np.isfinite(q).all() or (q.size and (q.min() < -2 ** 31 or q.max() > 2 ** 31 - 1)):
+        raise ValueError("%s: a node is not finite or leaves int32" % fn)
+    return np.ascontiguousarray(q.astype(np.int32))
+
+
+def _mesh_maps(fn, maps):
+    """Affine maps as int32 (N, 6): _affine_maps, which also takes integers of another width (a list of Python ints)."""
+    import numpy as np
+    if hasattr(maps, "detach") and hasattr(maps, "cpu"):
+        maps = maps.detach().cpu().numpy()
+    a = np.asarray(maps)
+    if a.dtype.kind in "iu" and a.dtype != np.int32 and a.size and -2 ** 31 <= a.min() and a.max() < 2 ** 31:
+        a = a.astype(np.int32)
+    return _affine_maps(fn, a, 0)
+
+
+def affine_mesh(maps, size):
+    """The meshes of affine maps, int32 (N, My, Mx, 2): the position mcraw_demosaic_warp_batch gives output pixel (32 a, 32 b)
+    under each map, at every node -- also those behind the last partial tile --, so that algo="mesh" follows algo="warp" to
+    within 1/256 sample, and bit for bit where the linear part is the identity.  maps: int32 (6,) or (N, 6) as the library takes
+    them, or float (2, 3) / (N, 2, 3) (quantize_affine).  Host only."""
+    import numpy as np
+    ho, wo = _mesh_size("affine_mesh", size)
+    m = _mesh_maps("affine_mesh", maps).astype(np.int64)
+    my, mx = mesh_grid(ho, wo)
+    i = (MESH_STEP * np.arange(my, dtype=np.int64))[None, :, None]
+    k = (MESH_STEP * np.arange(mx, dtype=np.int64))[None, None, :]
+    c = [m[:, j][:, None, None] for j in range(6)]
+    Y = c[2] + ((c[0] * i + c[1] * k + 128) >> 8)
+    X = c[5] + ((c[3] * i + c[4] * k + 128) >> 8)
+    out = np.stack([Y, X], axis=-1)
+    if out.min() < -2 ** 31 or out.max() > 2 ** 31 - 1:
+        raise ValueError("affine_mesh: a node leaves int32")
+    return np.ascontiguousarray(out.astype(np.int32))
+
+
+def _affine_float(fn, affine):
+    """Stabilise maps, int32 (6,) / (N, 6) or float (2, 3) / (N, 2, 3), as float64 (N, 2, 3) in samples."""
+    import numpy as np
+    m = _mesh_maps(fn, affine).astype(np.float64).reshape(-1, 2, 3)
+    return m / np.array([65536.0, 65536.0, 256.0])
+
+
+def distortion_mesh(height, width, size, radial=(1.0, 0.0, 0.0, 0.0), tangential=(0.0, 0.0), center=(0.5, 0.5), affine=None):
+    """The mesh of DNG's WarpRectilinear for one plane, int32 (My, Mx, 2), or (N, My, Mx, 2) with affine= (N, 6): output pixel q
+    reads the frame at c + f(r) d + tangential terms, with c = center * (width - 1, height - 1) (center is (cx, cy) in 0 .. 1 as
+    in DNG), d = (q - c) / m, m the largest distance from c to a corner of the frame, r^2 = dx^2 + dy^2,
+    f = k0 + k1 r^2 + k2 r^4 + k3 r^6, and the tangential terms (kt0, kt1) of the DNG specification:
+    x: 2 kt0 dx dy + kt1 (r^2 + 2 dx^2), y: kt0 (r^2 + 2 dy^2) + 2 kt1 dx dy; the result is scaled back by m.  q of output pixel
+    (i, k): the centred window, (i + (height - Ho) // 2, k + (width - Wo) // 2), or with affine= (stabilise maps of stabilize(),
+    (6,) or (N, 6)) the position that map gives -- it is applied first, so one pass undistorts and stabilises.  float64, rounded
+    as floor(v * 256 + 0.5).  Host only."""
+    import numpy as np
+    fn = "distortion_mesh"
+    ho, wo = _mesh_size(fn, size)
+    height, width = int(height), int(width)
+    try:
+        k = [float(v) for v in radial]
+        kt = [float(v) for v in tangential]
+        cx, cy = (float(v) for v in center)
+    except (TypeError, ValueError):
+        raise ValueError("%s: radial (k0, k1, k2, k3), tangential (kt0, kt1) and center (cx, cy) must be numbers" % fn) from None
+    if len(k) != 4 or len(kt) != 2 or height < 1 or width < 1:
+        raise ValueError("%s: radial holds four terms, tangential two, and the frame is at least 1 x 1" % fn)
+    my, mx = mesh_grid(ho, wo)
+    i = (MESH_STEP * np.arange(my, dtype=np.float64))[None, :, None]
+    kk = (MESH_STEP * np.arange(mx, dtype=np.float64))[None, None, :]
+    batched = False
+    if affine is None:
+        qy = i + float((height - ho) // 2) + 0.0 * kk
+        qx = kk + float((width - wo) // 2) + 0.0 * i
+    else:
+        A = _affine_float(fn, affine)
+        batched = tuple(np.shape(affine)) not in ((6,), (2, 3))  # one map gives one mesh, without N
+        qy = A[:, 0, 0][:, None, None] * i + A[:, 0, 1][:, None, None] * kk + A[:, 0, 2][:, None, None]
+        qx = A[:, 1, 0][:, None, None] * i + A[:, 1, 1][:, None, None] * kk + A[:, 1, 2][:, None, None]
+    py, px = cy * (height - 1), cx * (width - 1)
+    m = max(np.hypot(px - x, py - y) for x in (0.0, width - 1.0) for y in (0.0, height - 1.0))
+    m = m if m > 0 else 1.0
+    dy, dx = (qy - py) / m, (qx - px) / m
+    r2 = dx * dx + dy * dy
+    f = k[0] + r2 * (k[1] + r2 * (k[2] + r2 * k[3]))
+    sy = py + m * (f * dy + kt[0] * (r2 + 2.0 * dy * dy) + 2.0 * kt[1] * dx * dy)
+    sx = px + m * (f * dx + 2.0 * kt[0] * dx * dy + kt[1] * (r2 + 2.0 * dx * dx))
+    out = _mesh_round(fn, np.stack([sy, sx], axis=-1))
+    return out if batched else out[0]
+
+
+def stabilize_mesh(field, height, width, cell, size, window=0, limit=True):
+    """The meshes that stabilise a clip cell by cell, int32 (N, My, Mx, 2), from the field of local positions (N, Cy, Cx, 2) that
+    Context.align_cells returns for (Cy, Cx) = cell_grid(height, width, cell): what fit_affine would flatten to six numbers per
+    frame.  R_t = field_t minus the per-cell mean over frames t - window .. t + window (clipped to the batch; window=0: R = field,
+    a lock onto the frame of position 0, stabilize()'s sign); R_t(q) is bilinear between the cell centres
+    (i cell_h + cell_h / 2, j cell_w + cell_w / 2) and continues linearly beyond the outermost ones (constant along an axis with
+    one cell).  Node = 256 (q + R_t(q)) at q, the centred window's pixel (32 a + (height - Ho) // 2, 32 b + (width - Wo) // 2),
+    rounded as floor(v + 0.5).  limit=True raises ValueError where mesh_check() rejects a tile.  Host only."""
+    import numpy as np
+    fn = "stabilize_mesh"
+    if hasattr(field, "detach") and hasattr(field, "cpu"):
+        field = field.detach().cpu().numpy()
+    p = np.asarray(field, dtype=np.float64)
+    ho, wo = _mesh_size(fn, size)
+    height, width, window = int(height), int(width), int(window)
+    if p.ndim != 4 or p.shape[3] != 2 or tuple(p.shape[1:3]) != cell_grid(height, width, cell):
+        raise ValueError("%s: field must be (N, Cy, Cx, 2), the cell_grid of %d x %d frames with cells %r, not %r"
+                         % (fn, height, width, tuple(cell), p.shape))
+    if not (ho <= height and wo <= width) or window < 0:
+        raise ValueError("%s: size %r must fit the %d x %d frame, and window be >= 0" % (fn, size, height, width))
+    n, cy, cx = p.shape[:3]
+    R = p.copy()
+    if window:
+        for t in range(n):
+            R[t] = p[t] - p[max(0, t - window):min(n, t + window + 1)].mean(axis=0)
+    my, mx = mesh_grid(ho, wo)
+    qy = MESH_STEP * np.arange(my, dtype=np.float64) + float((height - ho) // 2)
+    qx = MESH_STEP * np.arange(mx, dtype=np.float64) + float((width - wo) // 2)
+
+    def axis(q, cells, step):  # the two cells about q and the weight of the second: linear beyond the outermost centres
+        if cells == 1:
+            return np.zeros(q.size, dtype=np.int64), np.zeros(q.size, dtype=np.int64), np.zeros(q.size)
+        g = (q - step / 2.0) / step
+        lo = np.clip(np.floor(g).astype(np.int64), 0, cells - 2)
+        return lo, lo + 1, g - lo
+
+    y0, y1, fy = axis(qy, cy, float(cell[0]))
+    x0, x1, fx = axis(qx, cx, float(cell[1]))
+    fy, fx = fy[None, :, None, None], fx[None, None, :, None]
+    top = R[:, y0][:, :, x0] * (1.0 - fx) + R[:, y0][:, :, x1] * fx
+    bot = R[:, y1][:, :, x0] * (1.0 - fx) + R[:, y1][:, :, x1] * fx
+    Rq = top * (1.0 - fy) + bot * fy                                     # (N, My, Mx, 2)
+    q = np.stack(np.meshgrid(qy, qx, indexing="ij"), axis=-1)[None]
+    out = _mesh_round(fn, q + Rq)
+    if limit:
+        try:
+            mesh_check(out, height, width, (ho, wo))
+        except ValueError as e:
+            raise ValueError("%s: %s" % (fn, e)) from None
+    return out
+
+
+def mesh_check(mesh, height, width, size, inside=False):
+    """mcraw_mesh_check on a host mesh, int32 (My, Mx, 2) or (N, My, Mx, 2) for size = (Ho, Wo): raises ValueError with the
+    library's message naming the first frame and tile whose source window is larger than the kernel holds (the tap clamp would
+    act there), or -- inside=True -- whose corner pixel reads outside the height x width frame (the border rule would act).
+    Needs neither a GPU nor a context."""
+    import numpy as np
+    ho, wo = _mesh_size("mesh_check", size)
+    a = np.asarray(mesh)
+    grid = mesh_grid(ho, wo) + (2,)
+    if a.dtype != np.int32 or a.ndim not in (3, 4) or tuple(a.shape[-3:]) != grid or a.size == 0:
+        raise ValueError("mesh_check: mesh must be int32 %r or (N, ...), not %s %r" % (grid, a.dtype, a.shape))
+    a = np.ascontiguousarray(a.reshape((-1,) + grid))
+    lib = load()
+    m = Mesh()
+    m.out_h, m.out_w, m.filter, m.reserved = ho, wo, FILTER_CUBIC, 0
+    if lib.mcraw_mesh_check(C.byref(m), a.ctypes.data_as(C.POINTER(C.c_int32)), int(a.shape[0]), int(width), int(height), 1 if inside else 0) != 0:
+        raise ValueError(lib.mcraw_last_error().decode())
 
 
 # display-ready integer RGB through a transfer-curve LUT (mcraw_demosaic_display_batch)
@@ -1170,6 +1362,14 @@ def load():
     lib.mcraw_demosaic_warp_batch.restype = C.c_int
     lib.mcraw_demosaic_warp_batch.argtypes = [C.c_void_p, C.POINTER(RgbParams), C.POINTER(Warp), C.POINTER(Display), C.POINTER(Yuv),
                                               C.POINTER(RgbColor), C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_size_t,
+                                              C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.mcraw_mesh_nodes.restype = C.c_size_t
+    lib.mcraw_mesh_nodes.argtypes = [C.POINTER(Mesh)]
+    lib.mcraw_mesh_check.restype = C.c_int
+    lib.mcraw_mesh_check.argtypes = [C.POINTER(Mesh), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.mcraw_demosaic_mesh_batch.restype = C.c_int
+    lib.mcraw_demosaic_mesh_batch.argtypes = [C.c_void_p, C.POINTER(RgbParams), C.POINTER(Mesh), C.POINTER(Display), C.POINTER(Yuv),
+                                              C.POINTER(RgbColor), C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t,
                                               C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.mcraw_demosaic_area_batch.restype = C.c_int
     lib.mcraw_demosaic_area_batch.argtypes = [C.c_void_p, C.POINTER(RgbParams), C.POINTER(Area), C.POINTER(Display), C.POINTER(Yuv),
@@ -2118,7 +2318,7 @@ class Context:
         return self.merge(scratch, lut, shift, **merge_kw)
 
     def demosaic(self, mosaic, *, algo="mhc", dtype, white, black=(0, 0, 0, 0), cfa="rggb", gain=None, matrix=None,
-                 clip=False, out=None, check=True, shading=None, defects=None, denoise=None, size=None, crop=None, filter=None, affine=None, highlights=None):
+                 clip=False, out=None, check=True, shading=None, defects=None, denoise=None, size=None, crop=None, filter=None, affine=None, highlights=None, mesh=None):
         """uint16 mosaics resident on the context's device -> planar linear RGB, (N, 3, H, W) for algo "mhc" (Malvar-He-
         Cutler) or (N, 3, H/2, W/2) for "bin2" (one pixel per 2x2 quad), as torch.float32 / float16 / bfloat16 ("f32" /
         "f16" / "bf16").  mosaic: a CUDA uint16 tensor (N, H, W) or (H, W) whose rows are contiguous (rows and frames may
@@ -2160,12 +2360,20 @@ class Context:
         (N, 3, H, W) as "mhc" and with every argument of "mhc": green follows the axis with the smaller gradient, R and B their
         differences against green, which keeps fine detail and high-contrast edges free of the zipper and false colour of the
         fixed 5x5 filter; on noisy input the direction follows the noise, so denoise= belongs in front of it.  "resample" and
-        "warp" keep sampling the "mhc" image."""
+        "warp" keep sampling the "mhc" image.
+        algo "mesh" with size=(Ho, Wo), mesh= and filter= (as "warp") samples the "mhc" image along a mesh of source positions
+        (mcraw_demosaic_mesh_batch): what is not affine -- lens distortion (distortion_mesh), the local motion that align_cells
+        measures (stabilize_mesh), or any map (affine_mesh gives "warp"'s).  mesh: int32 (My, Mx, 2), (1, My, Mx, 2) or
+        (N, My, Mx, 2) with (My, Mx) = mesh_grid(Ho, Wo), node (a, b) the position (Y, X) of output pixel (32 a, 32 b) in 1/256
+        sample; positions in between are bilinear, and one that leaves the frame reads the frame's edge.  A contiguous CUDA tensor
+        is used in place and nothing synchronises; a numpy array or CPU tensor is checked by mesh_check() first (ValueError with
+        its message; check=False takes it as it is) and uploaded on the current stream.  mesh= with another algo, "mesh" without
+        size= or mesh=, crop= or affine= with "mesh", or a wrong shape or dtype raises ValueError."""
         import torch
         code = _float_code(dtype)
         tdtype = {FLOAT_F32: torch.float32, FLOAT_F16: torch.float16, FLOAT_BF16: torch.bfloat16}[code]
         front = self._demosaic_front("demosaic", mosaic, algo, cfa, black, defects, denoise, shading, size, crop, filter, affine,
-                                     highlights, white, gain)
+                                     highlights, white, gain, mesh, check)
         ho, wo = front.ho, front.wo
         out = self._demosaic_out("demosaic", front, out, (3, ho, wo), tdtype)
         if front.n == 0:
@@ -2174,30 +2382,37 @@ class Context:
                                    gain, matrix, out)
 
     def _demosaic_front(self, fn, mosaic, algo, cfa, black, defects, denoise, shading, size=None, crop=None, filter=None, affine=None,
-                        highlights=None, white=None, gain=None):
+                        highlights=None, white=None, gain=None, mesh=None, check=True):
         """What demosaic / demosaic_display / demosaic_yuv (`fn`) do alike in front of their output: the algo and cfa checks,
         the mosaic argument, the optional stages -- defects, then denoise, then highlights, then shading, each into a scratch tensor (the
         caller's mosaic stays as it is), none for an empty batch -- and the output size (`size` for the scaled algos).  Returns a
         _Front."""
         import torch
         if algo not in _RGB_ALGOS:
-            raise ValueError("algo must be 'mhc', 'ha', 'bin2', 'area', 'resample' or 'warp', not %r" % (algo,))
+            raise ValueError("algo must be 'mhc', 'ha', 'bin2', 'area', 'resample', 'warp' or 'mesh', not %r" % (algo,))
         scaled = algo in _SCALED
         warp = algo == "warp"
+        meshed = algo == "mesh"
+        if mesh is not None and not meshed:
+            raise ValueError("%s: mesh= belongs to algo='mesh', not %r" % (fn, algo))
+        if meshed and (crop is not None or affine is not None):
+            raise ValueError("%s: crop= and affine= do not go with algo='mesh' (the nodes say where every pixel reads)" % fn)
+        if meshed and (size is None or mesh is None):
+            raise ValueError("%s: algo='mesh' needs size=(Ho, Wo) and mesh=" % fn)
         if affine is not None and not warp:
             raise ValueError("%s: affine= belongs to algo='warp', not %r" % (fn, algo))
         if warp and crop is not None:
             raise ValueError("%s: crop= does not go with algo='warp' (the maps say where every pixel reads)" % fn)
         if warp and (size is None or affine is None):
             raise ValueError("%s: algo='warp' needs size=(Ho, Wo) and affine=" % fn)
-        if not scaled and not warp and (size is not None or crop is not None):
+        if not scaled and not warp and not meshed and (size is not None or crop is not None):
             raise ValueError("%s: size= and crop= belong to algo='area' and 'resample', not %r" % (fn, algo))
         if scaled and size is None:
             raise ValueError("%s: algo=%r needs size=(Ho, Wo)" % (fn, algo))
-        if filter is not None and algo not in ("resample", "warp"):
+        if filter is not None and algo not in ("resample", "warp", "mesh"):
             raise ValueError("%s: filter= belongs to algo='resample', not %r" % (fn, algo))
         filt = None
-        if algo in ("resample", "warp"):
+        if algo in ("resample", "warp", "mesh"):
             filt = _FILTERS.get("cubic" if filter is None else filter)
             if filt is None:
                 raise ValueError("%s: filter must be 'cubic' or 'linear', not %r" % (fn, filter))
@@ -2220,17 +2435,47 @@ class Context:
                 raise ValueError("%s: size must be (Ho, Wo) and crop (y0, x0, h, w)" % fn) from None
             if len(area) != 4 or min(area) < 0 or ho < 1 or wo < 1 or max(area + (ho, wo)) > 65536:
                 raise ValueError("%s: size must be (Ho, Wo) and crop (y0, x0, h, w), all 0 .. 65536, not %r and %r" % (fn, size, crop))
-        elif warp:
+        elif warp or meshed:
             try:
                 ho, wo = (int(v) for v in size)
             except (TypeError, ValueError):
                 raise ValueError("%s: size must be (Ho, Wo)" % fn) from None
             if ho < 1 or wo < 1 or max(ho, wo) > 65536:
                 raise ValueError("%s: size must be (Ho, Wo), both 1 .. 65536, not %r" % (fn, size))
-            maps = _affine_maps(fn, affine, n)
+            if warp:
+                maps = _affine_maps(fn, affine, n)
+            else:
+                nodes = self._mesh_tensor(torch, dev, fn, mesh, n, h, w, (ho, wo), check)
         else:
             ho, wo = (h, w) if algo in ("mhc", "ha") else (h // 2, w // 2)
-        return _Front(mos, single, n, h, w, src, ho, wo, key, area, filt, maps if warp else None)
+        return _Front(mos, single, n, h, w, src, ho, wo, key, area, filt, maps if warp else None, nodes if meshed else None)
+
+    def _mesh_tensor(self, torch, dev, fn, mesh, n, h, w, size, check):
+        """mesh= of the demosaic methods as the contiguous int32 device tensor (nmesh, My, Mx, 2), nmesh 1 or n.  A tensor on the
+        device is used in place and nothing synchronises; a host array or CPU tensor goes through mcraw_mesh_check first (check)
+        and is uploaded on the current stream."""
+        import numpy as np
+        grid = mesh_grid(*size)
+        def shape_ok(shape):
+            shape = tuple(int(v) for v in shape)
+            return shape == grid + (2,) or (len(shape) == 4 and shape[1:] == grid + (2,) and (shape[0] in (1, n) or not n))
+        if isinstance(mesh, torch.Tensor) and mesh.device.type != "cpu":
+            if mesh.dtype != torch.int32 or mesh.device != dev or not mesh.is_contiguous() or not shape_ok(mesh.shape):
+                raise ValueError("%s: a mesh tensor must be contiguous int32 %r, (1, ...) or (%d, ...) on %s, not %s %r"
+                                 % (fn, grid + (2,), n, dev, mesh.dtype, tuple(mesh.shape)))
+            return mesh.reshape((-1,) + grid + (2,))
+        if isinstance(mesh, torch.Tensor):
+            mesh = mesh.detach().numpy()
+        a = np.asarray(mesh)
+        if a.dtype != np.int32 or not shape_ok(a.shape):
+            raise ValueError("%s: mesh must be int32 %r, (1, ...) or (%d, ...), not %s %r" % (fn, grid + (2,), n, a.dtype, a.shape))
+        a = np.ascontiguousarray(a.reshape((-1,) + grid + (2,)))
+        if check and n:  # (an empty batch is a no-op whatever its frames' geometry)
+            try:
+                mesh_check(a, h, w, size)
+            except ValueError as e:
+                raise ValueError("%s: mesh: %s" % (fn, e)) from None
+        return torch.from_numpy(a).to(dev, non_blocking=False)
 
     def _pre_stages(self, fn, mos, black, defects, denoise, highlights=None, white=None, cfa=None, gain=None):
         """defects=, denoise= and highlights= of the demosaic / decode methods, in that order, each into a scratch tensor; an
@@ -2265,6 +2510,16 @@ class Context:
             self._call(torch, mos.device, "mcraw_demosaic_warp_batch", (mos, out) + tuple(extra), C.byref(prm), C.byref(a), d, y, cols, nc,
                        maps.ctypes.data_as(C.POINTER(C.c_int32)), int(maps.shape[0]), *src, w, h, n, C.c_void_p(out.data_ptr()),
                        out.numel() * out.element_size())
+            return out
+        if algo == "mesh":  # one entry point for the three families; the nodes are device memory, read by the queued kernel
+            a = Mesh()
+            a.out_h, a.out_w, a.filter, a.reserved = front.ho, front.wo, front.filt, 0
+            d = C.byref(stage) if isinstance(stage, Display) else None
+            y = C.byref(stage) if isinstance(stage, Yuv) else None
+            nodes = front.mesh
+            self._call(torch, mos.device, "mcraw_demosaic_mesh_batch", (mos, out, nodes) + tuple(extra), C.byref(prm), C.byref(a), d, y, cols,
+                       nc, C.c_void_p(nodes.data_ptr()), nodes.numel() * 4, int(nodes.shape[0]), *src, w, h, n,
+                       C.c_void_p(out.data_ptr()), out.numel() * out.element_size())
             return out
         if algo in _SCALED:  # one entry point for the three families; its scratch lives as long as the call's other tensors
             struct, work_symbol, batch_symbol, rule = _SCALED[algo]
@@ -2333,7 +2588,7 @@ class Context:
 
     def decode_rgb(self, inputs, width, height, type, *, algo="mhc", dtype, white, black=(0, 0, 0, 0), cfa="rggb",
                    gain=None, matrix=None, clip=False, out=None, check=True, shading=None, defects=None, denoise=None, size=None,
-                   crop=None, filter=None, affine=None, highlights=None):
+                   crop=None, filter=None, affine=None, highlights=None, mesh=None):
         """Decode frames of one geometry that are resident in HBM and demosaic them (demosaic()): (N, 3, H, W) for "mhc",
         (N, 3, H/2, W/2) for "bin2", (N, 3, Ho, Wo) for "area" with size=(Ho, Wo) and crop=.  inputs: uint8 CUDA tensors, or (device pointer, length) pairs.  The plain uint16
         mosaics go to a scratch tensor of torch's caching allocator; both steps are queued on torch.cuda.current_stream().
@@ -2346,7 +2601,7 @@ class Context:
         scratch = self._decode_front("decode_rgb", inputs, width, height, type, check, black, defects, denoise, shading, highlights,
                                      white, cfa, gain)
         return self.demosaic(scratch, algo=algo, dtype=dtype, white=white, black=black, cfa=cfa, gain=gain, matrix=matrix,
-                             clip=clip, out=out, check=check, size=size, crop=crop, filter=filter, affine=affine)
+                             clip=clip, out=out, check=check, size=size, crop=crop, filter=filter, affine=affine, mesh=mesh)
 
     def _display_lut(self, torch, dev, fn, transfer, lut_size, bits):
         """(device LUT tensor, caller-owned?) for demosaic_display / demosaic_yuv (`fn`): a ready 1-D uint16 LUT (CUDA tensor on
@@ -2379,7 +2634,7 @@ class Context:
 
     def demosaic_display(self, mosaic, *, algo="mhc", white, black=(0, 0, 0, 0), cfa="rggb", gain=None, matrix=None,
                          transfer="srgb", lut_size=4096, dtype=None, layout="hwc", bits=None, out=None, check=True, shading=None,
-                         defects=None, denoise=None, size=None, crop=None, filter=None, affine=None, highlights=None):
+                         defects=None, denoise=None, size=None, crop=None, filter=None, affine=None, highlights=None, mesh=None):
         """uint16 mosaics resident on the context's device -> display-ready integer RGB: the demosaic and colours of
         demosaic(), then clamp to [0, 1], index a transfer-curve LUT of L entries at rint(c * (L - 1)) and store the entry
         (its low byte for uint8).  dtype: torch.uint8 (default) or torch.uint16; layout "hwc" gives (N, Ho, Wo, 3), "chw"
@@ -2397,7 +2652,7 @@ class Context:
         if layout not in _DISP_LAYOUTS:
             raise ValueError("demosaic_display: layout must be 'hwc' or 'chw', not %r" % (layout,))
         front = self._demosaic_front("demosaic_display", mosaic, algo, cfa, black, defects, denoise, shading, size, crop, filter, affine,
-                                     highlights, white, gain)
+                                     highlights, white, gain, mesh, check)
         ho, wo = front.ho, front.wo
         out = self._demosaic_out("demosaic_display", front, out, (ho, wo, 3) if layout == "hwc" else (3, ho, wo),
                                  torch.uint8 if dcode == DISP_U8 else torch.uint16)
@@ -2413,7 +2668,7 @@ class Context:
 
     def decode_display(self, inputs, width, height, type, *, algo="mhc", white, black=(0, 0, 0, 0), cfa="rggb", gain=None,
                        matrix=None, transfer="srgb", lut_size=4096, dtype=None, layout="hwc", bits=None, out=None, check=True, shading=None,
-                       defects=None, denoise=None, size=None, crop=None, filter=None, affine=None, highlights=None):
+                       defects=None, denoise=None, size=None, crop=None, filter=None, affine=None, highlights=None, mesh=None):
         """Decode frames of one geometry that are resident in HBM and turn them into display-ready RGB
         (demosaic_display()), as decode_rgb does: the plain uint16 mosaics go to a scratch tensor, both steps are queued on
         torch.cuda.current_stream(), check=True synchronises after the decode and raises McrawError naming the frames that
@@ -2422,11 +2677,11 @@ class Context:
                                      white, cfa, gain)
         return self.demosaic_display(scratch, algo=algo, white=white, black=black, cfa=cfa, gain=gain, matrix=matrix,
                                      transfer=transfer, lut_size=lut_size, dtype=dtype, layout=layout, bits=bits, out=out,
-                                     check=check, size=size, crop=crop, filter=filter, affine=affine)
+                                     check=check, size=size, crop=crop, filter=filter, affine=affine, mesh=mesh)
 
     def demosaic_yuv(self, mosaic, *, algo="mhc", white, black=(0, 0, 0, 0), cfa="rggb", gain=None, matrix=None, fmt="nv12",
                      standard="bt709", range="limited", transfer="bt709", lut_size=4096, in_bits=None, out=None, check=True, shading=None,
-                     defects=None, denoise=None, size=None, crop=None, filter=None, affine=None, highlights=None):
+                     defects=None, denoise=None, size=None, crop=None, filter=None, affine=None, highlights=None, mesh=None):
         """uint16 mosaics resident on the context's device -> video-ready Y'CbCr 4:2:0: the demosaic, colours, clamp and
         transfer-curve LUT of demosaic_display(), then the integer matrix of yuv_matrix(standard, range) and a 2x2 box
         average for the chroma (sited at the block's centre).  fmt "nv12": torch.uint8; "p010": torch.uint16 holding
@@ -2444,7 +2699,7 @@ class Context:
         in_bits = default_in if in_bits is None else in_bits
         cy, cb, cr, sh, y_off, c_off = yuv_matrix(standard, range, bits, in_bits)
         front = self._demosaic_front("demosaic_yuv", mosaic, algo, cfa, black, defects, denoise, shading, size, crop, filter, affine,
-                                     highlights, white, gain)
+                                     highlights, white, gain, mesh, check)
         ho, wo = front.ho, front.wo
         out = self._demosaic_out("demosaic_yuv", front, out, (ho * 3 // 2, wo), torch.uint8 if fcode == YUV_NV12 else torch.uint16)
         if front.n == 0:
@@ -2461,7 +2716,7 @@ class Context:
 
     def decode_yuv(self, inputs, width, height, type, *, algo="mhc", white, black=(0, 0, 0, 0), cfa="rggb", gain=None,
                    matrix=None, fmt="nv12", standard="bt709", range="limited", transfer="bt709", lut_size=4096, in_bits=None,
-                   out=None, check=True, shading=None, defects=None, denoise=None, size=None, crop=None, filter=None, affine=None, highlights=None):
+                   out=None, check=True, shading=None, defects=None, denoise=None, size=None, crop=None, filter=None, affine=None, highlights=None, mesh=None):
         """Decode frames of one geometry that are resident in HBM and turn them into NV12 / P010 (demosaic_yuv()), as
         decode_display does: the plain uint16 mosaics go to a scratch tensor, both steps are queued on
         torch.cuda.current_stream(), check=True synchronises after the decode and raises McrawError naming the frames that
@@ -2470,7 +2725,7 @@ class Context:
                                      white, cfa, gain)
         return self.demosaic_yuv(scratch, algo=algo, white=white, black=black, cfa=cfa, gain=gain, matrix=matrix, fmt=fmt,
                                  standard=standard, range=range, transfer=transfer, lut_size=lut_size, in_bits=in_bits, out=out,
-                                 check=check, size=size, crop=crop, filter=filter, affine=affine)
+                                 check=check, size=size, crop=crop, filter=filter, affine=affine, mesh=mesh)
 
     def profile(self, enable=True, only=None, every=1):
         """Bracket kernel launches with events: all kernels, or just the names in `only`; every `every`-th launch."""

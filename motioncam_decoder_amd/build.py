@@ -40,15 +40,15 @@ def _run(cmd):
     subprocess.run(cmd, check=True)
 
 
-# The gfx950 library: kernels (mcraw_type7 / mcraw_type6, the encoder mcraw_encode7, the demosaic mcraw_rgb, the lens-shading stage mcraw_shade, the statistics mcraw_stats, the defective-pixel stage mcraw_fixpix, the denoiser mcraw_denoise, the temporal merge mcraw_merge, the shift estimate mcraw_align and its cell-wise form mcraw_cells, the area-average demosaic mcraw_area, the resampling demosaic mcraw_resample, the affine warp mcraw_warp, the edge-directed demosaic mcraw_ha, the highlight stage mcraw_highlights), the host side of the C ABI in its units (csrc/mcraw_host.h) and the device pool.
+# The gfx950 library: kernels (mcraw_type7 / mcraw_type6, the encoder mcraw_encode7, the demosaic mcraw_rgb, the lens-shading stage mcraw_shade, the statistics mcraw_stats, the defective-pixel stage mcraw_fixpix, the denoiser mcraw_denoise, the temporal merge mcraw_merge, the shift estimate mcraw_align and its cell-wise form mcraw_cells, the area-average demosaic mcraw_area, the resampling demosaic mcraw_resample, the affine warp mcraw_warp and the mesh warp mcraw_mesh, the edge-directed demosaic mcraw_ha, the highlight stage mcraw_highlights), the host side of the C ABI in its units (csrc/mcraw_host.h) and the device pool.
 HIP_SOURCES = ("mcraw_abi.hip", "mcraw_submit.hip", "mcraw_tune.hip", "mcraw_device.hip", "mcraw_hostmem.hip", "mcraw_pool.hip",
                "mcraw_type7.hip", "mcraw_type6.hip", "mcraw_encode7.hip", "mcraw_rgb.hip", "mcraw_shade.hip", "mcraw_stats.hip",
                "mcraw_fixpix.hip", "mcraw_denoise.hip", "mcraw_merge.hip", "mcraw_align.hip", "mcraw_area.hip", "mcraw_resample.hip", "mcraw_cells.hip", "mcraw_warp.hip", "mcraw_ha.hip",
-               "mcraw_highlights.hip")
+               "mcraw_highlights.hip", "mcraw_mesh.hip")
 HIP_HEADERS = ("mcraw_plan.h", "mcraw_dev.h", "mcraw_host.h", "mcraw_race.h", "mcraw_mosaic.h", "mcraw_mosaic_args.h",
                "mcraw_rgb_args.h", "mcraw_align_args.h", "mcraw_area_args.h", "mcraw_rgb_dev.h", "mcraw_rgb_launch.h",
                "mcraw_resample_args.h", "mcraw_rgb_paths.h", "mcraw_align_pyr.h", "mcraw_cells_args.h", "mcraw_warp_args.h", "mcraw_ha_args.h",
-               "mcraw_highlights_args.h")
+               "mcraw_highlights_args.h", "mcraw_warp_dev.h", "mcraw_mesh_args.h")
 HIP_FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc"]
 
 
@@ -168,9 +168,9 @@ K7T_PATH_VARIANTS = {
 # The demosaic kernels (krgb_mhc, krgb_bin2, krgb_bin2y, krgb_area, krgb_resample) with every path counted and the persistent loop
 # forced (tests/test_gpu_rgb_paths.py; the switches and why each is valid for every input: the head of csrc/mcraw_rgb.hip).  Every
 # name below occurs in mcraw_rgb.hip, mcraw_area.hip and mcraw_resample.hip alone -- the shared headers count, cap and poison
-# through hooks that only those sources define --, so a variant compiles those three sources; mcraw_warp.hip and mcraw_ha.hip
-# name none of them and take their grids' limit from mcraw_rgb.hip (krgb_warp: tests/test_gpu_warp_paths.py; krgb_ha:
-# tests/test_gpu_ha_paths.py).
+# through hooks that only those sources define --, so a variant compiles those three sources; mcraw_warp.hip, mcraw_mesh.hip and
+# mcraw_ha.hip name none of them and take their grids' limit from mcraw_rgb.hip (krgb_warp: tests/test_gpu_warp_paths.py; krgb_mesh:
+# tests/test_gpu_mesh_paths.py; krgb_ha: tests/test_gpu_ha_paths.py).
 #   grid1  one workgroup walks every unit of every frame in order
 #   grid3  successive units of a workgroup skip columns, rows and frames
 RGB_PATH_VARIANTS = {

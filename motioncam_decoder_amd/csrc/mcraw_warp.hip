@@ -2,7 +2,8 @@
 // (mcraw_demosaic_warp_batch): the Malvar-He-Cutler estimates of krgb_mhc behind a 4 x 4 gather, linear or cubic, into the float,
 // display and YUV families.  The contract and its weights: include/mcraw_hip.h; the checks, the phase tables, the position
 // arithmetic and the plan, free of HIP: mcraw_warp_args.h; the numpy statement: tests/_warp_ref.py.  The colour stage and the
-// stores are the siblings' (mcraw_rgb_dev.h), the host side of the launch theirs too (mcraw_rgb_launch.h).
+// stores are the siblings' (mcraw_rgb_dev.h), the host side of the launch theirs too (mcraw_rgb_launch.h); staging, phase A, the
+// weights, the taps of a pixel and the store phase are shared with krgb_mesh (mcraw_warp_dev.h).
 //
 //   krgb_warp  one instance per (output kind, CFA), as the siblings
 //
@@ -32,6 +33,7 @@ uint32_t rgb_grid_limit(uint32_t resident);
 #define RGB_GRID_LIMIT(resident) ::mcraw::rgb_grid_limit(resident)
 #include "mcraw_rgb_launch.h"
 #include "mcraw_warp_args.h"
+#include "mcraw_warp_dev.h"
 
 namespace mcraw {
 
@@ -44,68 +46,6 @@ struct WarpGeo {
 
 __device__ const WarpTable g_warp_cubic = warp_table(MCRAW_FILTER_CUBIC);
 
-// Phase A of one lane: the estimates of 8 columns of source row 2 rp + AR of the window (AR: the row's parity) from the raw
-// window in LDS: krgb_mhc's arithmetic, one row of it.
-template <int S, int AR>
-__device__ __forceinline__ void warp_mhc_row(const RgbArgs &A, const uint16_t *s_raw, int32_t *s_e, uint32_t rp, uint32_t q)
-{
-    int d[5][12]; // rows 2 rp + AR - 2 .. + 2 of the estimates' grid, columns 8 q - 2 .. 8 q + 9
-#pragma unroll
-    for (int r = 0; r < 5; r++) {
-        const uint16_t *lrow = &s_raw[(2u * rp + static_cast<uint32_t>(AR + r)) * WARP_RAWW + 8u * q];
-        const mcraw_u32x4 c0 = *reinterpret_cast<const mcraw_u32x4 *>(lrow);
-        const mcraw_u32x4 c1 = *reinterpret_cast<const mcraw_u32x4 *>(lrow + 8);
-        const uint32_t c2 = *reinterpret_cast<const uint32_t *>(lrow + 16);
-        const uint32_t w[6] = {c0[3], c1[0], c1[1], c1[2], c1[3], c2};
-#pragma unroll
-        for (int j = 0; j < 12; j++)
-            d[r][j] = static_cast<int>((w[j >> 1] >> (16u * (j & 1))) & 0xffffu) - A.black[((AR + r) & 1) * 2 + (j & 1)];
-    }
-    int E[3][8];
-#pragma unroll
-    for (int b = 0; b < 8; b++) {
-        constexpr int R = 2;
-        const int J = b + 2;
-        const int C = d[R][J];
-        const int n1 = d[R - 1][J], s1 = d[R + 1][J], w1 = d[R][J - 1], e1 = d[R][J + 1];
-        const int v2 = d[R - 2][J] + d[R + 2][J], h2 = d[R][J - 2] + d[R][J + 2];
-        const int dg = (d[R - 1][J - 1] + d[R - 1][J + 1]) + (d[R + 1][J - 1] + d[R + 1][J + 1]);
-        const int role = (AR * 2 + (b & 1)) ^ S;
-        const int nat = 16 * C;
-        if (role == 0 || role == 3) { // R or B site
-            const int g = 8 * C + 4 * ((n1 + s1) + (w1 + e1)) - 2 * (v2 + h2);
-            const int o = 12 * C + 4 * dg - 3 * (v2 + h2);
-            E[0][b] = role == 0 ? nat : o;
-            E[1][b] = g;
-            E[2][b] = role == 0 ? o : nat;
-        } else { // G site: role 1 has R left / right, role 2 has B left / right
-            const int hz = 10 * C + 8 * (w1 + e1) - 2 * h2 - 2 * dg + v2;
-            const int vt = 10 * C + 8 * (n1 + s1) - 2 * v2 - 2 * dg + h2;
-            E[0][b] = role == 1 ? hz : vt;
-            E[1][b] = nat;
-            E[2][b] = role == 1 ? vt : hz;
-        }
-    }
-#pragma unroll
-    for (uint32_t c = 0; c < 3u; c++) {
-        int32_t *dst = &s_e[(c * WARP_EROWS + 2u * rp + static_cast<uint32_t>(AR)) * WARP_ESTRIDE + 8u * q];
-        *reinterpret_cast<mcraw_u32x4 *>(dst) = mcraw_u32x4{static_cast<uint32_t>(E[c][0]), static_cast<uint32_t>(E[c][1]),
-                                                            static_cast<uint32_t>(E[c][2]), static_cast<uint32_t>(E[c][3])};
-        *reinterpret_cast<mcraw_u32x4 *>(dst + 4) = mcraw_u32x4{static_cast<uint32_t>(E[c][4]), static_cast<uint32_t>(E[c][5]),
-                                                                static_cast<uint32_t>(E[c][6]), static_cast<uint32_t>(E[c][7])};
-    }
-}
-
-// The four weights of phase p out of the table in LDS.
-__device__ __forceinline__ void warp_weights(const int16_t *s_w, uint32_t p, int32_t (&w)[4])
-{
-    const mcraw_u32x2 v = *reinterpret_cast<const mcraw_u32x2 *>(&s_w[4u * p]);
-    w[0] = static_cast<int32_t>(v[0] << 16) >> 16;
-    w[1] = static_cast<int32_t>(v[0]) >> 16;
-    w[2] = static_cast<int32_t>(v[1] << 16) >> 16;
-    w[3] = static_cast<int32_t>(v[1]) >> 16;
-}
-
 // One output pixel at position (Y, X): the 4 x 4 taps over the window's estimates (held from row pb, column eb of the frame on),
 // horizontally first.  Whatever the position, the reads stay inside the array.
 __device__ __forceinline__ void warp_pixel(const int32_t *s_e, const int16_t *s_w, int64_t Y, int64_t X, int32_t pb, int32_t eb,
@@ -116,32 +56,13 @@ __device__ __forceinline__ void warp_pixel(const int32_t *s_e, const int16_t *s_
     warp_weights(s_w, static_cast<uint32_t>(X) & 255u, wx);
     const int32_t r0 = min(max(static_cast<int32_t>(Y >> 8) - 1 - pb, 0), static_cast<int32_t>(WARP_EROWS) - 4);
     const int32_t c0 = min(max(static_cast<int32_t>(X >> 8) - 1 - eb, 0), static_cast<int32_t>(WARP_ECOLS) - 4);
-#pragma unroll
-    for (uint32_t c = 0; c < 3u; c++) {
-        const int32_t *src = &s_e[(c * WARP_EROWS + static_cast<uint32_t>(r0)) * WARP_ESTRIDE + static_cast<uint32_t>(c0)];
-        int32_t a2 = 0, b2 = 0;
-#pragma unroll
-        for (uint32_t r = 0; r < 4u; r++) {
-            int32_t a = 0, b = 0;
-#pragma unroll
-            for (uint32_t j = 0; j < 4u; j++) {
-                const int32_t v = src[r * WARP_ESTRIDE + j];
-                a += __mul24(wx[j], v >> 8);
-                b += __mul24(wx[j], v & 255);
-            }
-            const int32_t t = (a + ((b + 2048) >> 8)) >> 4;
-            a2 += __mul24(wy[r], t >> 8);
-            b2 += __mul24(wy[r], t & 255);
-        }
-        E[c] = (a2 + ((b2 + 2048) >> 8)) >> 4;
-    }
+    warp_taps(s_e, wy, wx, r0, c0, E);
 }
 
 template <int PK, int S>
 __global__ void __launch_bounds__(RGB_T) krgb_warp(const RgbArgs A, const WarpGeo G)
 {
     constexpr bool LUT = has_lut(PK);
-    constexpr uint32_t ROWS = is_yuv(PK) ? 2u : 1u; // output rows of a lane
     __shared__ __attribute__((aligned(16))) uint16_t s_raw[WARP_RAWH * WARP_RAWW];
     __shared__ __attribute__((aligned(16))) int32_t s_e[3u * WARP_EROWS * WARP_ESTRIDE];
     __shared__ __attribute__((aligned(16))) int16_t s_w[256u * 4u];
@@ -172,24 +93,7 @@ __global__ void __launch_bounds__(RGB_T) krgb_warp(const RgbArgs A, const WarpGe
         const uint32_t np = min(win.np, WARP_EROWS / 2u), ne = min(win.ne, WARP_ECOLS / 8u);
         const uint16_t *in = A.in + static_cast<size_t>(f) * A.fstride;
         __syncthreads(); // the LUT and the table are staged; the previous tile's LDS reads are done
-        // raw rows pb - 2 .. pb + 2 np + 1, columns eb - 8 .. eb + 8 ne + 7
-        const uint32_t nch = ne + 2u;
-        for (uint32_t i = threadIdx.x; i < (2u * np + 4u) * nch; i += RGB_T) {
-            const uint32_t r = i / nch, q = i % nch;
-            const uint16_t *row = in + static_cast<size_t>(reflect101(pb - 2 + static_cast<int>(r), H)) * A.pitch;
-            const int xs = eb - 8 + 8 * static_cast<int>(q);
-            mcraw_u32x4 v;
-            if (A.invec && xs >= 0 && xs + 8 <= W) {
-                v = *gptr<const mcraw_u32x4>(row + xs);
-            } else {
-                uint32_t e[8];
-#pragma unroll
-                for (int k = 0; k < 8; k++)
-                    e[k] = gptr<const uint16_t>(row)[reflect101(xs + k, W)];
-                v = mcraw_u32x4{e[0] | (e[1] << 16), e[2] | (e[3] << 16), e[4] | (e[5] << 16), e[6] | (e[7] << 16)};
-            }
-            *reinterpret_cast<mcraw_u32x4 *>(&s_raw[r * WARP_RAWW + 8u * q]) = v;
-        }
+        warp_stage(A, in, s_raw, pb, eb, np, ne, W, H); // raw rows pb - 2 .. pb + 2 np + 1, columns eb - 8 .. eb + 8 ne + 7
         __syncthreads();
         // A: rows of parity 0 in the first half of the workgroup, of parity 1 in the second (uniform in a wave)
         if (threadIdx.x < RGB_T / 2u) {
@@ -224,35 +128,7 @@ __global__ void __launch_bounds__(RGB_T) krgb_warp(const RgbArgs A, const WarpGe
                                 static_cast<uint32_t>(E4[c][3])};
             __syncthreads();
         }
-        // store: (8 output columns, output row or row pair) out of the tile's E
-        const uint32_t lxid = threadIdx.x & (WARP_TW / 8u - 1u), lyid = threadIdx.x / (WARP_TW / 8u);
-        const uint32_t xo = k0 + 8u * lxid, j0 = i0 + ROWS * lyid;
-        if (lyid < WARP_TH / ROWS && xo < A.Wo && j0 <= i1) {
-            const uint32_t n = min(8u, A.Wo - xo);
-            const RgbCol &col = A.col[A.percol ? f : 0u];
-            uint8_t *fout = A.out + static_cast<size_t>(f) * 3u * A.Ho * A.Wo * out_es(PK) / (is_yuv(PK) ? 2u : 1u);
-            int SUM[3][4] = {}; // YUV kinds: the sums of P over the lane's four 2x2 blocks
-#pragma unroll 1
-            for (uint32_t a = 0; a < ROWS; a++) {
-                const uint32_t j = j0 + a; // (the YUV kinds: Ho is even, a row pair always has both rows)
-                int E[3][8];
-#pragma unroll
-                for (uint32_t c = 0; c < 3u; c++) {
-                    const int32_t *src = &s_e[(c * WARP_TH + (j - i0)) * WARP_TW + 8u * lxid];
-                    const mcraw_u32x4 v0 = *reinterpret_cast<const mcraw_u32x4 *>(src);
-                    const mcraw_u32x4 v1 = *reinterpret_cast<const mcraw_u32x4 *>(src + 4);
-#pragma unroll
-                    for (int i = 0; i < 8; i++)
-                        E[c][i] = static_cast<int32_t>(i < 4 ? v0[i] : v1[i - 4]);
-                }
-                if constexpr (is_yuv(PK))
-                    yuv_row8<PK>(A, col, s_lut, fout, j, xo, n, static_cast<int>(a), E, SUM);
-                else if constexpr (is_disp(PK))
-                    disp_store8<PK>(A, col, s_lut, fout, j, xo, n, E);
-                else
-                    rgb_store8<PK>(A, col, fout, j, xo, n, E);
-            }
-        }
+        warp_store<PK>(A, s_e, s_lut, f, i0, i1, k0); // (8 output columns, output row or row pair) out of the tile's E
     } while (LUT && (t += gridDim.x) < A.units * A.nf);
 }
 

@@ -6,10 +6,10 @@ one line per instance in the format of profiles/rgb_resources.txt / display_reso
 shade_resources.txt / stats_resources.txt / fixpix_resources.txt / denoise_resources.txt / merge_resources.txt / align_resources.txt /
 cells_resources.txt (kcells_* and kmerge<..., field>) / area_resources.txt (csrc/mcraw_area.hip: krgb_area and karea_tab) /
 resample_resources.txt (csrc/mcraw_resample.hip: krgb_resample and kres_tab) / warp_resources.txt (csrc/mcraw_warp.hip: krgb_warp) /
-ha_resources.txt (csrc/mcraw_ha.hip: krgb_ha) / highlights_resources.txt (csrc/mcraw_highlights.hip: khl_apply, khl_clip, khl_measure, khl_init).
+mesh_resources.txt (csrc/mcraw_mesh.hip: krgb_mesh) / ha_resources.txt (csrc/mcraw_ha.hip: krgb_ha) / highlights_resources.txt (csrc/mcraw_highlights.hip: khl_apply, khl_clip, khl_measure, khl_init).
 
     python tools/rgb_resources.py            # every instance
-    python tools/rgb_resources.py --check    # the figures in the fifteen committed files must equal the compiler's; exit 1 if not
+    python tools/rgb_resources.py --check    # the figures in the sixteen committed files must equal the compiler's; exit 1 if not
 """
 import os
 import re
@@ -43,6 +43,8 @@ RESAMPLE_FILE = "resample_resources.txt"
 RESAMPLE_NAME = r"Function Name: _ZN5mcraw\d+(krgb_resample|kres_tab)(?:ILi(\d+)ELi(\d)EEEv|E)"  # krgb_resample<kind, CFA shift>, and the kernel that writes the taps
 WARP_FILE = "warp_resources.txt"
 WARP_NAME = r"Function Name: _ZN5mcraw\d+(krgb_warp)ILi(\d+)ELi(\d)EEEv"  # krgb_warp<kind, CFA shift>
+MESH_FILE = "mesh_resources.txt"
+MESH_NAME = r"Function Name: _ZN5mcraw\d+(krgb_mesh)ILi(\d+)ELi(\d)EEEv"  # krgb_mesh<kind, CFA shift>
 HA_FILE = "ha_resources.txt"
 HA_NAME = r"Function Name: _ZN5mcraw\d+(krgb_ha)ILi(\d+)ELi(\d)EEEv"  # krgb_ha<kind, CFA shift>
 HL_FILE = "highlights_resources.txt"
@@ -131,10 +133,11 @@ def main():
     resample = report("mcraw_resample.hip", RESAMPLE_NAME)
     warp = report("mcraw_warp.hip", WARP_NAME)
     ha = report("mcraw_ha.hip", HA_NAME)
+    mesh = report("mcraw_mesh.hip", MESH_NAME)
     hl = report("mcraw_highlights.hip", HL_NAME)
     if "--check" not in sys.argv:
         for line in list(rep.values()) + list(shade.values()) + list(stats.values()) + list(fixpix.values()) + list(denoise.values()) + \
-                list(merge.values()) + list(align.values()) + list(area.values()) + list(resample.values()) + list(cells.values()) + list(warp.values()) + list(ha.values()) + list(hl.values()):
+                list(merge.values()) + list(align.values()) + list(area.values()) + list(resample.values()) + list(cells.values()) + list(warp.values()) + list(ha.values()) + list(hl.values()) + list(mesh.values()):
             print(line)
         return 0
     return _check(FILES, rep, "krgb_") | _check((SHADE_FILE,), shade, "kshade") | _check((STATS_FILE,), stats, "kstats") | \
@@ -142,7 +145,7 @@ def main():
         _check((ALIGN_FILE,), align, "kalign") | _check((AREA_FILE,), area, ("krgb_area", "karea_tab")) | \
         _check((RESAMPLE_FILE,), resample, ("krgb_resample", "kres_tab")) | _check((CELLS_FILE,), cells, ("kcells_", "kmerge<")) | \
         _check((WARP_FILE,), warp, "krgb_warp") | _check((HA_FILE,), ha, "krgb_ha") | \
-        _check((HL_FILE,), hl, "khl_")
+        _check((HL_FILE,), hl, "khl_") | _check((MESH_FILE,), mesh, "krgb_mesh")
 
 
 if __name__ == "__main__":
