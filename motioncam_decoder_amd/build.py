@@ -48,7 +48,7 @@ HIP_SOURCES = ("mcraw_abi.hip", "mcraw_submit.hip", "mcraw_tune.hip", "mcraw_dev
 HIP_HEADERS = ("mcraw_plan.h", "mcraw_dev.h", "mcraw_host.h", "mcraw_race.h", "mcraw_mosaic.h", "mcraw_mosaic_args.h",
                "mcraw_rgb_args.h", "mcraw_align_args.h", "mcraw_area_args.h", "mcraw_rgb_dev.h", "mcraw_rgb_launch.h",
                "mcraw_resample_args.h", "mcraw_rgb_paths.h", "mcraw_align_pyr.h", "mcraw_cells_args.h", "mcraw_warp_args.h", "mcraw_ha_args.h",
-               "mcraw_highlights_args.h", "mcraw_warp_dev.h", "mcraw_mesh_args.h")
+               "mcraw_highlights_args.h", "mcraw_warp_dev.h", "mcraw_mesh_args.h", "mcraw_mosaic_paths.h")
 HIP_FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc"]
 
 
@@ -181,6 +181,20 @@ RGB_PATH_VARIANTS = {
     "poison1": ["-DMCRAW_PATHSR", "-DMCRAW_RGB_GRID_CAP=1", "-DMCRAW_POISON_RGB"],
 }
 
+# The mosaic stages (kshade, kstats, kfixpix, kfixpix_list, kdenoise, kmerge, khl_apply, khl_measure, khl_clip) with every path counted
+# and the guarded ones forced, and the sweep of div_round (tests/test_gpu_mosaic_paths.py; the switches and why each is valid for
+# every input: the head of csrc/mcraw_mosaic_paths.h).  Every name below occurs in the stage sources alone (mcraw_shade.hip,
+# mcraw_stats.hip, mcraw_fixpix.hip, mcraw_denoise.hip, mcraw_merge.hip, mcraw_highlights.hip) -- the helpers of mcraw_mosaic.h count through hooks that only those
+# sources define --, so a variant compiles those sources and nothing else.
+MOSAIC_PATH_VARIANTS = {
+    "census": ["-DMCRAW_PATHSM"],
+    "slow": ["-DMCRAW_PATHSM", "-DMCRAW_FORCE_SLOWM"],
+    "poison": ["-DMCRAW_PATHSM", "-DMCRAW_POISON_M"],
+    "poisonslow": ["-DMCRAW_PATHSM", "-DMCRAW_POISON_M", "-DMCRAW_FORCE_SLOWM"],
+    "pieces": ["-DMCRAW_PATHSM", "-DMCRAW_MERGE_PIECE=3", "-DMCRAW_STATS_MAXTILES=2"],
+    "th16": ["-DMCRAW_PATHSM", "-DMCRAW_MERGE_TH=16", "-DMCRAW_DENOISE_TH=16", "-DMCRAW_FIXPIX_TH=16"],
+}
+
 # The merge with tiles of 16 rows instead of 32 (tools/bench_merge.py --alt-lib, tests/test_gpu_merge_cells.py): the name occurs in
 # mcraw_merge.hip alone.
 MERGE_ALT_FLAGS = ["-DMCRAW_MERGE_TH=16"]
@@ -200,9 +214,10 @@ def build_merge_alt():
 
 
 # The -D builds that tests/ links on the GPU box (tests/test_gpu_split.py, test_gpu_segw.py, test_gpu_lookback_fault.py,
-# test_gpu_k6_paths.py, test_gpu_k7_paths.py, test_gpu_enc7_paths.py, test_gpu_k7t_paths.py, test_gpu_rgb_paths.py).
+# test_gpu_k6_paths.py, test_gpu_k7_paths.py, test_gpu_enc7_paths.py, test_gpu_k7t_paths.py, test_gpu_rgb_paths.py,
+# test_gpu_mosaic_paths.py).
 TEST_VARIANTS = ((["-DMCRAW_FORCE_SEGW"], ["-DMCRAW_INJECT_MUTE7"], ["-DMCRAW_INJECT_LOST"]) + tuple(K6_PATH_VARIANTS.values())
-                 + tuple(K7_PATH_VARIANTS.values()) + tuple(ENC7_PATH_VARIANTS.values()) + tuple(K7T_PATH_VARIANTS.values()) + tuple(RGB_PATH_VARIANTS.values()) + (MERGE_ALT_FLAGS,))
+                 + tuple(K7_PATH_VARIANTS.values()) + tuple(ENC7_PATH_VARIANTS.values()) + tuple(K7T_PATH_VARIANTS.values()) + tuple(RGB_PATH_VARIANTS.values()) + tuple(MOSAIC_PATH_VARIANTS.values()) + (MERGE_ALT_FLAGS,))
 
 
 def prebuild_test_variants():

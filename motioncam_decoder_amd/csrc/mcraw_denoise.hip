@@ -10,7 +10,14 @@
 // rows it reads 8 + 4R samples and accumulates, for all 8 pixels, q = x * x, q * a and a over the 2R + 1 columns.  The
 // centre counts as a neighbour of itself (x = 0, weight 256): that is the contract's 256 * c and 256.  |a - c| runs packed
 // on the dwords as they lie in memory; every product has a factor below 2^24.
+//
+// Test builds (build.MOSAIC_PATH_VARIANTS, tests/test_gpu_mosaic_paths.py; why each is valid: the head of mcraw_mosaic_paths.h):
+//   MCRAW_PATHSM      the path census, and the sweep of div_round at the end of this file
+//   MCRAW_POISON_M    s_t filled with 0xFFFF in front of staging
 #include "mcraw_host.h"
+#ifdef MCRAW_PATHSM
+#include "mcraw_mosaic_paths.h"
+#endif
 #include "mcraw_mosaic.h"
 
 namespace mcraw {
@@ -68,7 +75,7 @@ __device__ __forceinline__ int dn_halo(int h, int n)
 // halo coordinates that hold the distance-2 reader's sample.  For such a c the contract's rule gives the neighbours at -4
 // and at +4 the same coordinate (c - 4 is outside, so -4 means c + 4 or c, and +4 means c + 4 or, c - 4 being outside, c;
 // likewise on the high side), so the pixel reads the other side: bit 0 = take +4 for -4, bit 1 = take -4 for +4, both = the
-// pixel itself for both (n = 6, 7).
+// pixel itself for both (n = 5, 6, 7: c = 2 of n = 5 has neither c - 4 nor c + 4 inside).
 __device__ __forceinline__ uint32_t dn_swap(int c, int n)
 {
     return ((c & ~1) == 2 ? 1u : 0u) | (static_cast<uint32_t>(c + 4 - n) < 2u ? 2u : 0u);
@@ -88,6 +95,10 @@ __global__ void __launch_bounds__(DN_T) kdenoise(const DnArgs A)
     const int W = static_cast<int>(A.W), H = static_cast<int>(A.H);
     const int x0 = static_cast<int>(tx * DN_TW), y0 = static_cast<int>(ty * DN_TH);
     const uint16_t *in = A.in + static_cast<size_t>(f) * A.ifstride;
+    MOS_PATH(MP_WG, threadIdx.x == 0u);
+#ifdef MCRAW_POISON_M
+    poison_tile(s_t, LH * DN_LW);
+#endif
     {
         const uint16_t *lut = A.lut + (A.perframe ? static_cast<size_t>(f) * 4u * A.L : 0u);
         for (uint32_t i = threadIdx.x; i < A.L / 2u; i += DN_T) // 4 * L * 2 bytes in 16-byte chunks (L >= 64)
@@ -97,8 +108,10 @@ __global__ void __launch_bounds__(DN_T) kdenoise(const DnArgs A)
     for (uint32_t i = threadIdx.x; i < LH * DN_CH; i += DN_T) {
         const uint32_t r = i / DN_CH, q = i % DN_CH;
         const int yy = y0 - HALO + static_cast<int>(r), xs = x0 - 8 + 8 * static_cast<int>(q);
+        MOS_PATH(MP_STG_SKIP, yy >= H + HALO || xs >= W + HALO);
         if (yy >= H + HALO || xs >= W + HALO) // no output of the frame reads it
             continue;
+        MOS_STAGE(q != 0u && q != DN_CH - 1u, xs + 8 <= W, A.invec != 0u);
         const uint16_t *row = in + static_cast<size_t>(dn_halo(yy, H)) * A.ipitch;
         mcraw_u32x4 v;
         if (q != 0u && q != DN_CH - 1u && xs + 8 <= W) { // (xs >= 0 here) a full piece of the row
@@ -118,6 +131,7 @@ __global__ void __launch_bounds__(DN_T) kdenoise(const DnArgs A)
     const uint32_t lx = threadIdx.x % DN_LX, ly = threadIdx.x / DN_LX;
     const uint32_t x = static_cast<uint32_t>(x0) + 8u * lx;
     const uint32_t n = x < A.W ? min(8u, A.W - x) : 0u;
+    MOS_PATH(MP_IDLE_LANE, n == 0u);
     if (n == 0u)
         return;
     // the lane's rows all have the parity of ly (y0 and DN_LY are even): two of the table's four planes
@@ -135,15 +149,23 @@ __global__ void __launch_bounds__(DN_T) kdenoise(const DnArgs A)
                 mhi[k] |= (s & 2u) ? 0xFFFFu << (16u * h) : 0u;
                 edgex = edgex || s != 0u;
             }
+        MOS_PATH(MP_DN_EDGEX, edgex);
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; k++)
+            MOS_PATH(MP_DN_BOTH, (mlo[k] & mhi[k]) != 0u);
     }
     uint16_t *fout = A.out + static_cast<size_t>(f) * A.ofstride + x;
     const uint32_t lmax = A.L - 1u;
 #pragma unroll 1
     for (uint32_t rr = ly; rr < DN_TH; rr += DN_LY) {
         const uint32_t y = static_cast<uint32_t>(y0) + rr;
+        MOS_PATH(MP_ROW_BREAK, y >= A.H);
         if (y >= A.H)
             break;
         const uint32_t sy = RADIUS == 2 ? dn_swap(static_cast<int>(y), H) : 0u;
+        MOS_PATH(MP_DN_SY1, (sy & 1u) != 0u);
+        MOS_PATH(MP_DN_SY2, (sy & 2u) != 0u);
+        MOS_PATH(MP_DN_SY3, sy == 3u);
         const uint16_t *lane = &s_t[(rr + HALO) * DN_LW + 8u * lx + 8u - HALO]; // the pixel row, column x - HALO
         uint32_t c[4], rv[8];
 #pragma unroll
@@ -242,9 +264,73 @@ static void denoise_launch(const DnArgs &A, uint32_t tilesY, uint32_t nf, hipStr
     hipLaunchKernelGGL((DN_NT ? kdenoise<RADIUS, true> : kdenoise<RADIUS, false>), dim3(A.tilesX * tilesY, nf), dim3(DN_T), static_cast<size_t>(A.L) * 8u, st, A);
 }
 
+#ifdef MCRAW_PATHSM
+void mos_paths_read_denoise(uint64_t *out, int n, int reset) { mos_paths_read(out, n, reset); } // (mcraw_diag_mosaic_paths: mcraw_shade.hip)
+
+// The sweep of div_round over the edges of its proven domain: workgroup b takes den = b + 1, its threads the quotients k =
+// 0 .. 65536, each with n = k * den + {-1, 0, 1, den / 2, den - 1}; an n below 0 or from 2^30 on, or one whose quotient exceeds
+// 65536, is passed over.  The device's own integer division is the reference.
+struct DivSweep {
+    unsigned long long evals, bad;
+    uint32_t n, den, got, pad;
+};
+
+constexpr uint32_t DIV_MAXDEN = 6400u, DIV_MAXQ = 65536u;
+
+__global__ void __launch_bounds__(256) kdiv_sweep(DivSweep *R)
+{
+    const uint32_t den = blockIdx.x + 1u;
+    unsigned long long evals = 0ull;
+    for (uint32_t k = threadIdx.x; k <= DIV_MAXQ; k += 256u) {
+        const long long base = static_cast<long long>(k) * den;
+        const long long off[5] = {-1, 0, 1, static_cast<long long>(den / 2u), static_cast<long long>(den) - 1};
+#pragma unroll
+        for (uint32_t i = 0; i < 5u; i++) {
+            const long long nn = base + off[i];
+            if (nn < 0 || nn >= (1ll << 30))
+                continue;
+            const uint32_t n = static_cast<uint32_t>(nn), want = n / den;
+            if (want > DIV_MAXQ)
+                continue;
+            evals++;
+            const uint32_t got = div_round(n, den);
+            if (got != want && atomicAdd(&R->bad, 1ull) == 0ull)
+                R->n = n, R->den = den, R->got = got;
+        }
+    }
+    atomicAdd(&R->evals, evals);
+}
+#endif
+
 } // namespace mcraw
 
 using namespace mcraw;
+
+#ifdef MCRAW_PATHSM
+// The sweep on the current device: out[0 .. 8) = evaluations, mismatches, the first mismatch's n, den and result, and from this
+// source's census div_round's calls, steps down and steps up (the census of this source starts over).
+extern "C" int mcraw_diag_div_sweep(uint64_t *out)
+{
+    if (!out)
+        return -1;
+    uint64_t none[MP_N] = {};
+    mos_paths_read(none, 0, 1);
+    DivSweep *R = nullptr, h{};
+    if (hipMalloc(&R, sizeof(DivSweep)) != hipSuccess || hipMemset(R, 0, sizeof(DivSweep)) != hipSuccess)
+        return -1;
+    hipLaunchKernelGGL(kdiv_sweep, dim3(DIV_MAXDEN), dim3(256), 0, nullptr, R);
+    const bool ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
+                    hipMemcpy(&h, R, sizeof(h), hipMemcpyDeviceToHost) == hipSuccess;
+    (void)hipFree(R);
+    if (!ok)
+        return -1;
+    uint64_t paths[MP_N] = {};
+    mos_paths_read(paths, MP_N, 1);
+    out[0] = h.evals, out[1] = h.bad, out[2] = h.n, out[3] = h.den, out[4] = h.got;
+    out[5] = paths[MP_DIV_CALLS], out[6] = paths[MP_DIV_DOWN], out[7] = paths[MP_DIV_UP];
+    return 0;
+}
+#endif
 
 extern "C" int mcraw_denoise_batch(mcraw_ctx *c, const mcraw_denoise *d, const uint16_t *in, size_t in_pitch, size_t in_frame_stride,
                                    int width, int height, int n, uint16_t *out, size_t out_pitch, size_t out_frame_stride,

@@ -12,7 +12,15 @@
 // behind that predicate, and a wave without such a pixel skips them.  The counts stay in registers; a wave reduces them
 // with shuffles and one lane adds them to the frame's record.  kfixpix_list, queued behind it, replaces the listed pixels:
 // one thread per (entry, frame), eight searches, one element written.
+//
+// Test builds (build.MOSAIC_PATH_VARIANTS, tests/test_gpu_mosaic_paths.py; why each is valid: the head of mcraw_mosaic_paths.h):
+//   MCRAW_PATHSM       the path census
+//   MCRAW_FORCE_SLOWM  `cand` is true for every lane
+//   MCRAW_POISON_M     s_t filled with 0xFFFF in front of staging
 #include "mcraw_host.h"
+#ifdef MCRAW_PATHSM
+#include "mcraw_mosaic_paths.h"
+#endif
 #include "mcraw_mosaic.h"
 
 namespace mcraw {
@@ -114,11 +122,16 @@ __global__ void __launch_bounds__(FP_T) kfixpix(const FixArgs A)
     const int W = static_cast<int>(A.W), H = static_cast<int>(A.H);
     const int x0 = static_cast<int>(tx * FP_TW), y0 = static_cast<int>(ty * FP_TH);
     const uint16_t *in = A.in + static_cast<size_t>(f) * A.ifstride;
+    MOS_PATH(MP_WG, threadIdx.x == 0u);
+#ifdef MCRAW_POISON_M
+    poison_tile(s_t, FP_LH * FP_LW);
+#endif
     stage_tile<FP_TH, 2, fix_halo>(s_t, in, A.ipitch, W, H, x0, y0, A.invec != 0u);
     __syncthreads();
     const uint32_t lx = threadIdx.x % FP_LX, ly = threadIdx.x / FP_LX;
     const uint32_t x = static_cast<uint32_t>(x0) + 8u * lx;
     const uint32_t n = x < A.W ? min(8u, A.W - x) : 0u;
+    MOS_PATH(MP_IDLE_LANE, n == 0u);
     // the lane's rows all have the parity of ly (y0 is even): its counters are those of two CFA positions
     const uint32_t rowpar = ly & 1u;
     const uint32_t blk[2] = {A.black[2u * rowpar], A.black[2u * rowpar + 1u]};
@@ -128,6 +141,8 @@ __global__ void __launch_bounds__(FP_T) kfixpix(const FixArgs A)
 #pragma unroll 1
     for (uint32_t pass = 0; pass < FP_TH / 16u; pass++) {
         const uint32_t rb = 16u * pass + 4u * (ly >> 1) + rowpar; // the lane's rows of the tile: rb and rb + 2
+        MOS_PATH(MP_ROW_CONT, n != 0u && static_cast<uint32_t>(y0) + rb >= A.H);
+        MOS_PATH(MP_ROW_CONT, n != 0u && static_cast<uint32_t>(y0) + rb + 2u >= A.H);
         if (n == 0u || static_cast<uint32_t>(y0) + rb >= A.H)
             continue;
         // LDS rows rb, rb + 2, rb + 4, rb + 6 are frame rows y - 2, y, y + 2, y + 4; w[.][j]: columns x - 2 + 2j, x - 1 + 2j
@@ -171,6 +186,12 @@ __global__ void __launch_bounds__(FP_T) kfixpix(const FixArgs A)
                 // store is guarded by the column's place against n.)
                 cand = cand || (pk_sub(v, pk_min(v, Hk[k])) | pk_sub(pk_max(v, Lk[k]), v)) != 0u;
             }
+#ifdef MCRAW_FORCE_SLOWM
+            cand = true;
+#endif
+            MOS_WAVE(MP_FP_WAVE_ANY, __any(cand));
+            MOS_WAVE(MP_FP_WAVE_NONE, !__any(cand));
+            MOS_PATH(MP_FP_CAND, cand);
             if (__any(cand)) {
                 if (cand) {
 #pragma unroll
@@ -185,15 +206,26 @@ __global__ void __launch_bounds__(FP_T) kfixpix(const FixArgs A)
                             // (every intermediate is below 2^32: at most 65535 * 65535, then 65535 + 2^24)
                             const bool hot = A.hot && pv > ph && pv - ph > abt[h] + (((ph > blk[h] ? ph - blk[h] : 0u) * A.rel) >> 8);
                             const bool cold = A.cold && pv < pl && pl - pv > abt[h] + (((pl > blk[h] ? pl - blk[h] : 0u) * A.rel) >> 8);
+                            MOS_PATH(MP_FP_HOT, hot);
+                            MOS_PATH(MP_FP_COLD, cold);
                             if (hot || cold) {
                                 flag |= 0xFFFFu << (16u * h);
                                 // a pixel that the search finds in the list is not counted
+#ifdef MCRAW_PATHSM
+                                // (the census counts the search's answer: one search, kept in a local; the product's own
+                                // form below compiles to other code with such a local)
+                                const bool listed = A.counts && A.nlist && fix_member(A.list, A.nlist, (y << 16) | (x + 2u * k + h));
+                                MOS_PATH(MP_FP_LISTED, listed);
+                                if (A.counts && !listed) {
+#else
                                 if (A.counts && !(A.nlist && fix_member(A.list, A.nlist, (y << 16) | (x + 2u * k + h)))) {
+#endif
                                     nhot[h] += hot ? 1u : 0u;
                                     ncold[h] += cold ? 1u : 0u;
                                 }
                             }
                         }
+                        MOS_PATH(MP_FP_FLAG, flag != 0u);
                         if (flag) {
                             uint32_t best, val;
                             fix_pair(R1[k], R1[k + 2u], true, best, val);       // (W, E)
@@ -246,11 +278,14 @@ __global__ void __launch_bounds__(256) kfixpix_init(uint32_t *counts, size_t wor
 __global__ void __launch_bounds__(256) kfixpix_list(const FixArgs A)
 {
     const uint32_t e = blockIdx.x * 256u + threadIdx.x, f = blockIdx.y;
+    MOS_PATH(MP_FL_WG, threadIdx.x == 0u);
+    MOS_PATH(MP_FL_PAST, e >= A.nlist);
     if (e >= A.nlist)
         return;
     const uint32_t key = gptr<const uint32_t>(A.list)[e];
     const int x = static_cast<int>(key & 0xFFFFu), y = static_cast<int>(key >> 16);
     const int W = static_cast<int>(A.W), H = static_cast<int>(A.H);
+    MOS_PATH(MP_FL_OUTSIDE, x >= W || y >= H);
     if (x >= W || y >= H)
         return;
     const int xs[3] = {fix_neighbour(x, -2, W), x, fix_neighbour(x, 2, W)};
@@ -271,10 +306,16 @@ __global__ void __launch_bounds__(256) kfixpix_list(const FixArgs A)
         if (d < best)
             best = d, val = (a + b + 1u) >> 1;
     }
+    MOS_PATH(MP_FL_WRITTEN, best != 0xFFFFFFFFu);
+    MOS_PATH(MP_FL_NOPAIR, best == 0xFFFFFFFFu);
     if (best != 0xFFFFFFFFu) // no eligible pair: the dynamic pass's result stands
         gptr<uint16_t>(A.out)[static_cast<size_t>(f) * A.ofstride + static_cast<size_t>(y) * A.opitch + static_cast<size_t>(x)] =
             static_cast<uint16_t>(val);
 }
+
+#ifdef MCRAW_PATHSM
+void mos_paths_read_fixpix(uint64_t *out, int n, int reset) { mos_paths_read(out, n, reset); } // (mcraw_diag_mosaic_paths: mcraw_shade.hip)
+#endif
 
 } // namespace mcraw
 

@@ -12,8 +12,16 @@
 // are made by four threads per workgroup while the others stage.  khl_measure keeps two sums and two counts per lane, reduces
 // them over the 32 lanes of a row parity with shuffles, then over the workgroup in LDS, and adds the non-zero ones to the record
 // with global atomics (kstats' way).  khl_clip (CLIP) is one packed min per dword and needs no neighbours: it loads and stores directly, as kshade does.
+//
+// Test builds (build.MOSAIC_PATH_VARIANTS, tests/test_gpu_mosaic_paths.py; why each is valid: the head of mcraw_mosaic_paths.h):
+//   MCRAW_PATHSM       the path census
+//   MCRAW_FORCE_SLOWM  khl_apply's `clipped` is true for every lane
+//   MCRAW_POISON_M     s_t filled with 0xFFFF in front of staging
 #include "mcraw_host.h"
 #include "mcraw_highlights_args.h"
+#ifdef MCRAW_PATHSM
+#include "mcraw_mosaic_paths.h"
+#endif
 #include "mcraw_mosaic.h"
 
 namespace mcraw {
@@ -134,6 +142,10 @@ __global__ void __launch_bounds__(HL_T) khl_apply(const HlArgs A)
         cnt = gptr<const uint32_t>(rec)[8u + threadIdx.x];
     }
     const uint16_t *in = A.in + static_cast<size_t>(f) * A.ifstride;
+    MOS_PATH(MP_WG, threadIdx.x == 0u);
+#ifdef MCRAW_POISON_M
+    poison_tile(s_t, HL_LH * HL_LW);
+#endif
     stage_tile<HL_TH, 1, hl_halo>(s_t, in, A.ipitch, W, H, x0, y0, A.invec != 0u);
     if (threadIdx.x < 4u) {
         long long c = cnt ? sum / static_cast<long long>(cnt) : 0;
@@ -146,10 +158,12 @@ __global__ void __launch_bounds__(HL_T) khl_apply(const HlArgs A)
     const uint32_t n = x < A.W ? min(8u, A.W - x) : 0u;
     const uint32_t rp = ly & 1u; // y0 and HL_PASS are even: every row of the lane has this parity
     const uint32_t satm1 = A.satm1[rp];
+    MOS_PATH(MP_IDLE_LANE, n == 0u);
     uint16_t *fout = A.out + static_cast<size_t>(f) * A.ofstride + x;
 #pragma unroll 1
     for (uint32_t pass = 0; pass < HL_TH / HL_PASS; pass++) {
         const uint32_t r = HL_PASS * pass + ly, y = static_cast<uint32_t>(y0) + r;
+        MOS_PATH(MP_ROW_CONT, n != 0u && y >= A.H);
         if (n == 0u || y >= A.H)
             continue;
         const mcraw_u32x4 own = *reinterpret_cast<const mcraw_u32x4 *>(&s_t[(r + 1u) * HL_LW + 8u + 8u * lx]);
@@ -160,6 +174,11 @@ __global__ void __launch_bounds__(HL_T) khl_apply(const HlArgs A)
 #pragma unroll
         for (uint32_t k = 0; k < 4u; k++)
             clipped = clipped || pk_sub(o[k], pk_min(o[k], satm1)) != 0u;
+#ifdef MCRAW_FORCE_SLOWM
+        clipped = true;
+#endif
+        MOS_PATH(MP_HL_CLIPPED, clipped);
+        MOS_PATH(MP_HL_UNCLIPPED, !clipped);
         if (clipped) {
             const HlLane P = hl_lane(A, rp);
             uint32_t w[3][6];
@@ -172,11 +191,14 @@ __global__ void __launch_bounds__(HL_T) khl_apply(const HlArgs A)
                     continue;
                 const int32_t v = static_cast<int32_t>(hl_wbd(s, P.blk[0][c], P.gn[0][c]));
                 const int32_t cand = static_cast<int32_t>(hl_ref(w, i, P)) + s_ch[2u * rp + c];
+                MOS_PATH(MP_HL_LEFT, cand <= v);
+                MOS_PATH(MP_HL_REBUILT, cand > v);
                 if (cand <= v)
                     continue;
                 // (cand <= 2^21 and inv <= 2^16: the product needs 64 bits, the result is below 2^26)
                 const uint32_t inv = rp ? A.inv[2u + c] : A.inv[c];
                 const uint32_t back = P.blk[0][c] + static_cast<uint32_t>((static_cast<uint64_t>(static_cast<uint32_t>(cand)) * inv + 2048u) >> 12);
+                MOS_PATH(MP_HL_TOP, back > A.top);
                 const uint32_t q = max(s, min(back, A.top));
                 o[i >> 1] = c ? (o[i >> 1] & 0xFFFFu) | (q << 16) : (o[i >> 1] & 0xFFFF0000u) | q;
             }
@@ -197,12 +219,17 @@ __global__ void __launch_bounds__(HL_T) khl_measure(const HlArgs A)
     const uint16_t *in = A.in + static_cast<size_t>(f) * A.ifstride;
     if (threadIdx.x < 4u)
         s_sum[threadIdx.x] = 0ull, s_cnt[threadIdx.x] = 0u;
+    MOS_PATH(MP_WG, threadIdx.x == 0u);
+#ifdef MCRAW_POISON_M
+    poison_tile(s_t, HL_LH * HL_LW);
+#endif
     stage_tile<HL_TH, 1, hl_halo>(s_t, in, A.ipitch, W, H, x0, y0, A.invec != 0u);
     __syncthreads();
     const uint32_t lx = threadIdx.x % HL_LX, ly = threadIdx.x / HL_LX;
     const uint32_t x = static_cast<uint32_t>(x0) + 8u * lx;
     const uint32_t n = x < A.W ? min(8u, A.W - x) : 0u;
     const uint32_t rp = ly & 1u;
+    MOS_PATH(MP_IDLE_LANE, n == 0u);
     const HlLane P = hl_lane(A, rp);
     // sat - 1 and lo of the lane's own rows [0] and of the rows above and below [1], by column parity
     uint32_t sm[2][2], lo[2];
@@ -218,6 +245,7 @@ __global__ void __launch_bounds__(HL_T) khl_measure(const HlArgs A)
 #pragma unroll 1
     for (uint32_t pass = 0; pass < HL_TH / HL_PASS; pass++) {
         const uint32_t r = HL_PASS * pass + ly, y = static_cast<uint32_t>(y0) + r;
+        MOS_PATH(MP_ROW_CONT, n != 0u && y >= A.H);
         if (n == 0u || y >= A.H)
             continue;
         uint32_t w[3][6];
@@ -226,11 +254,16 @@ __global__ void __launch_bounds__(HL_T) khl_measure(const HlArgs A)
         for (int i = 0; i < 8; i++) {
             const uint32_t c = static_cast<uint32_t>(i) & 1u, o = c ^ 1u;
             const uint32_t s = hl_at(w, 1, i);
+            MOS_PATH(MP_HM_OWN, static_cast<uint32_t>(i) < n && (s < lo[c] || s > sm[0][c]));
             if (static_cast<uint32_t>(i) >= n || s < lo[c] || s > sm[0][c])
                 continue;
+            MOS_PATH(MP_HM_NEIGHBOUR,
+                     hl_at(w, 1, i - 1) > sm[0][o] || hl_at(w, 1, i + 1) > sm[0][o] || hl_at(w, 0, i) > sm[1][c] || hl_at(w, 2, i) > sm[1][c] ||
+                         hl_at(w, 0, i - 1) > sm[1][o] || hl_at(w, 0, i + 1) > sm[1][o] || hl_at(w, 2, i - 1) > sm[1][o] || hl_at(w, 2, i + 1) > sm[1][o]);
             if (hl_at(w, 1, i - 1) > sm[0][o] || hl_at(w, 1, i + 1) > sm[0][o] || hl_at(w, 0, i) > sm[1][c] || hl_at(w, 2, i) > sm[1][c] ||
                 hl_at(w, 0, i - 1) > sm[1][o] || hl_at(w, 0, i + 1) > sm[1][o] || hl_at(w, 2, i - 1) > sm[1][o] || hl_at(w, 2, i + 1) > sm[1][o])
                 continue;
+            MOS_PATH(MP_HM_MEASURED, true);
             acc[c] += static_cast<int32_t>(hl_wbd(s, P.blk[0][c], P.gn[0][c])) - static_cast<int32_t>(hl_ref(w, i, P));
             cnt[c] += 1u;
         }
@@ -278,6 +311,8 @@ __global__ void __launch_bounds__(HL_T) khl_clip(const HlArgs A)
     const uint32_t ty = tile / A.tilesX, tx = tile - ty * A.tilesX;
     const uint32_t lx = threadIdx.x % HL_LX, ly = threadIdx.x / HL_LX;
     const uint32_t x = tx * HL_TW + 8u * lx, y0 = ty * HL_CTH + ly;
+    MOS_PATH(MP_WG, threadIdx.x == 0u);
+    MOS_PATH(MP_IDLE_LANE, x >= A.W);
     if (x >= A.W)
         return;
     const uint32_t n = min(8u, A.W - x);
@@ -294,6 +329,7 @@ __global__ void __launch_bounds__(HL_T) khl_clip(const HlArgs A)
 #pragma unroll
     for (uint32_t a = 0; a < 2u; a++) {
         const uint32_t y = y0 + a * HL_PASS;
+        MOS_PATH(MP_ROW_CONT, y >= A.H);
         if (y >= A.H)
             continue;
 #pragma unroll
@@ -334,6 +370,10 @@ static HlArgs hl_args(const mcraw_highlights &h, const MosaicBatch &I, const Mos
     }
     return A;
 }
+
+#ifdef MCRAW_PATHSM
+void mos_paths_read_highlights(uint64_t *out, int n, int reset) { mos_paths_read(out, n, reset); } // (mcraw_diag_mosaic_paths: mcraw_shade.hip)
+#endif
 
 } // namespace mcraw
 

@@ -15,7 +15,16 @@
 // is fetched from HBM once and found in that XCD's L2 by the other bases that hold it in their windows.
 // kmerge<SUPPORT, NT, true, MgCellArgs> (mcraw_merge_cells_batch): the same kernel, a tile reading its shifts from the cell of a
 // position field that it lies in.
+//
+// Test builds (build.MOSAIC_PATH_VARIANTS, tests/test_gpu_mosaic_paths.py; why each is valid: the head of mcraw_mosaic_paths.h):
+//   MCRAW_PATHSM         the path census
+//   MCRAW_FORCE_SLOWM    a member that weighs 0 for the whole tile is staged like any other
+//   MCRAW_POISON_M       s_b filled with 0xFFFF in front of the base's staging, s_m in front of every member's
+//   MCRAW_MERGE_PIECE=N  N outputs per launch
 #include "mcraw_host.h"
+#ifdef MCRAW_PATHSM
+#include "mcraw_mosaic_paths.h"
+#endif
 #include "mcraw_mosaic.h"
 #include "mcraw_cells_args.h"
 
@@ -36,6 +45,17 @@ constexpr uint32_t MG_LW = MG_TW + 16u;    // LDS row: 8 columns either side (1 
 constexpr uint32_t MG_CH = MG_LW / 8u;     // 16-byte chunks per LDS row
 constexpr uint32_t MG_LH = MG_TH + 2u;
 constexpr uint32_t MG_XCDS = 8u;           // workgroups are dealt round-robin over the XCDs
+#ifdef MCRAW_MERGE_PIECE
+constexpr uint32_t MG_PIECE = MCRAW_MERGE_PIECE; // outputs per launch
+static_assert(MG_PIECE >= 1u && MG_PIECE <= 2048u, "a frame has at most 2^19 tiles: tiles * outputs stays below 2^30 workgroups");
+#else
+constexpr uint32_t MG_PIECE = 0u; // as many as keep a launch below 2^30 workgroups
+#endif
+#ifdef MCRAW_FORCE_SLOWM
+constexpr bool MG_SKIP_OK = false;
+#else
+constexpr bool MG_SKIP_OK = true; // a member that weighs 0 for every pixel of the tile is not staged
+#endif
 
 #ifdef MCRAW_MERGE_FLIP_STORES
 constexpr bool MG_NT = false;
@@ -66,7 +86,10 @@ __device__ __forceinline__ void mg_stage(uint16_t *s, const uint16_t *frm, size_
         const uint32_t r = i / MG_CH, q = i % MG_CH;
         const int yy = y0 - 1 + static_cast<int>(r) + sy, xs = x0 - 8 + 8 * static_cast<int>(q) + sx;
         mcraw_u32x4 v = {0u, 0u, 0u, 0u};
+        MOS_PATH(MP_MG_ZERO, !(yy >= 0 && yy < H && xs + 8 > 0 && xs < W));
         if (yy >= 0 && yy < H && xs + 8 > 0 && xs < W) {
+            MOS_STAGE(q != 0u && q != MG_CH - 1u, xs >= 0 && xs + 8 <= W, aligned);
+            MOS_PATH(MP_MG_CUT, q != 0u && q != MG_CH - 1u && xs < 0);
             const uint16_t *row = frm + static_cast<size_t>(yy) * pitch;
             if (q != 0u && q != MG_CH - 1u && xs >= 0 && xs + 8 <= W) { // a full piece of the row
                 v = load16(row + xs, aligned); // (not aligned: the base address, the pitch, or a shift that is no multiple of 8)
@@ -106,6 +129,9 @@ __global__ void __launch_bounds__(MG_T) kmerge(const ARGS A)
     extern __shared__ __attribute__((aligned(16))) uint16_t mg_lut[];         // the base's table: 4 * L entries (the launch sizes it)
     // consecutive workgroup ids go to consecutive XCDs: XCD k takes the k-th run of `per` (tile, output) pairs, outputs fastest
     const uint32_t l = (blockIdx.x % MG_XCDS) * A.per + blockIdx.x / MG_XCDS;
+    MOS_PATH(MP_WG, threadIdx.x == 0u);
+    MOS_PATH(MP_MG_LAUNCH, threadIdx.x == 0u && blockIdx.x == 0u);
+    MOS_PATH(MP_MG_SHORT, threadIdx.x == 0u && l >= A.tiles * A.nout);
     if (l >= A.tiles * A.nout) // the last XCD's run may be short
         return;
     const uint32_t tile = l / A.nout, j = l - tile * A.nout;
@@ -118,6 +144,9 @@ __global__ void __launch_bounds__(MG_T) kmerge(const ARGS A)
         for (uint32_t i = threadIdx.x; i < A.L / 2u; i += MG_T) // 4 * L * 2 bytes in 16-byte chunks (L >= 64)
             *reinterpret_cast<mcraw_u32x4 *>(&mg_lut[8u * i]) = *gptr<const mcraw_u32x4>(lut + 8u * i);
     }
+#ifdef MCRAW_POISON_M
+    poison_tile(s_b, MG_LH * MG_LW);
+#endif
     mg_stage(s_b, A.in + static_cast<size_t>(b) * A.ifstride, A.ipitch, W, H, y0, x0, 0, 0, A.invec != 0u);
     __syncthreads();
     const uint32_t lx = threadIdx.x % MG_LX, ly = threadIdx.x / MG_LX;
@@ -158,6 +187,7 @@ __global__ void __launch_bounds__(MG_T) kmerge(const ARGS A)
     }
 #pragma unroll 1
     for (uint32_t t = tlo; t <= thi; t++) {
+        MOS_PATH(MP_MG_SELF, threadIdx.x == 0u && t == b);
         if (t == b)
             continue;
         int sy = 0, sx = 0;
@@ -170,9 +200,20 @@ __global__ void __launch_bounds__(MG_T) kmerge(const ARGS A)
         }
         // the valid region in the base's coordinates: the frame intersected with the frame moved by the shift
         const int ry0 = max(0, -sy), ry1 = min(H, H - sy), rx0 = max(0, -sx), rx1 = min(W, W - sx);
-        if (ry0 >= ry1 || rx0 >= rx1 || ry1 <= y0 || ry0 >= y0 + static_cast<int>(MG_TH) || rx1 <= x0 || rx0 >= x0 + static_cast<int>(MG_TW))
+        MOS_PATH(MP_MG_ZEROW, threadIdx.x == 0u && MG_SKIP_OK &&
+                                  (ry0 >= ry1 || rx0 >= rx1 || ry1 <= y0 || ry0 >= y0 + static_cast<int>(MG_TH) || rx1 <= x0 ||
+                                   rx0 >= x0 + static_cast<int>(MG_TW)));
+        if (MG_SKIP_OK &&
+            (ry0 >= ry1 || rx0 >= rx1 || ry1 <= y0 || ry0 >= y0 + static_cast<int>(MG_TH) || rx1 <= x0 || rx0 >= x0 + static_cast<int>(MG_TW)))
             continue; // the member weighs 0 for every pixel of the tile (uniform over the workgroup)
+        MOS_PATH(MP_MG_STAGED, threadIdx.x == 0u);
+        MOS_PATH(MP_MG_M_ALIGNED, threadIdx.x == 0u && A.invec != 0u && (sx & 7) == 0);
+        MOS_PATH(MP_MG_M_SX, threadIdx.x == 0u && A.invec != 0u && (sx & 7) != 0);
+        MOS_PATH(MP_MG_M_INVEC, threadIdx.x == 0u && A.invec == 0u);
         __syncthreads(); // everyone has read the member before
+#ifdef MCRAW_POISON_M
+        poison_tile(s_m, MG_LH * MG_LW);
+#endif
         mg_stage(s_m, A.in + static_cast<size_t>(t) * A.ifstride, A.ipitch, W, H, y0, x0, sy, sx, A.invec != 0u && (sx & 7) == 0);
         __syncthreads();
         // columns x - 1 .. x + 8: bit i says that column x - 1 + i is in the region
@@ -250,12 +291,14 @@ __global__ void __launch_bounds__(MG_T) kmerge(const ARGS A)
         }
     }
     const uint32_t n = x < A.W ? min(8u, A.W - x) : 0u;
+    MOS_PATH(MP_IDLE_LANE, n == 0u);
     if (n == 0u)
         return;
     uint16_t *fout = A.out + static_cast<size_t>(j) * A.ofstride + x;
 #pragma unroll
     for (uint32_t o = 0; o < MG_RPL; o++) {
         const uint32_t y = static_cast<uint32_t>(y0) + r0 + o;
+        MOS_PATH(MP_ROW_BREAK, y >= A.H);
         if (y >= A.H)
             break;
         uint32_t res[4];
@@ -274,6 +317,10 @@ __global__ void __launch_bounds__(MG_T) kmerge(const ARGS A)
         store8<NT>(fout + static_cast<size_t>(y) * A.opitch, n, A.outvec != 0u, res);
     }
 }
+
+#ifdef MCRAW_PATHSM
+void mos_paths_read_merge(uint64_t *out, int n, int reset) { mos_paths_read(out, n, reset); } // (mcraw_diag_mosaic_paths: mcraw_shade.hip)
+#endif
 
 static void merge_launch(const MgCellArgs &A, uint32_t support, hipStream_t st)
 {
@@ -371,7 +418,7 @@ static int merge_entry(const char *fn, mcraw_ctx *c, const mcraw_merge *m, const
         A.cell_h = cells->cell_h, A.cell_w = cells->cell_w, A.cells_x = cells->cells_x;
         A.cells = cells->cells_y * cells->cells_x;
     }
-    const uint32_t piece = std::max(1u, std::min(65535u, 0x40000000u / A.tiles)); // outputs per launch: below 2^30 workgroups
+    const uint32_t piece = MG_PIECE ? MG_PIECE : std::max(1u, std::min(65535u, 0x40000000u / A.tiles)); // outputs per launch: below 2^30 workgroups
     for (uint32_t j0 = 0; j0 < m->count; j0 += piece) {
         A.nout = std::min(piece, m->count - j0);
         A.first = m->first + j0;

@@ -4,6 +4,21 @@
 #pragma once
 #include "mcraw_dev.h"
 
+// The hooks of the path census of the stages (mcraw_mosaic_paths.h, test builds only): empty unless a source defined them in front
+// of this header.
+#ifndef MOS_PATH
+#define MOS_PATH(slot, cond)
+#endif
+#ifndef MOS_WAVE
+#define MOS_WAVE(slot, cond)
+#endif
+#ifndef MOS_STAGE
+#define MOS_STAGE(inner, whole, vec)
+#endif
+#ifndef MOS_DIV
+#define MOS_DIV(r, den)
+#endif
+
 namespace mcraw {
 
 __device__ __forceinline__ uint32_t half16(uint32_t w, uint32_t h)
@@ -21,11 +36,14 @@ __device__ __forceinline__ uint32_t mul24(uint32_t a, uint32_t b)
 // n < 2^30, den <= 6400, quotient <= 65536 (a weighted mean of uint16 values plus the rounding half).  In float: n rounds with a
 // relative error of 2^-24, den is exact, v_rcp_f32 is good to 1 ulp (2^-23) and the product rounds once more: the estimate is off
 // by less than 65536 * 2^-21 = 1 / 32, so its integer part is the quotient or one beside it, and one step either way by the sign
-// of the remainder makes it exact.
+// of the remainder makes it exact.  Outside that range the result is merely some number: nothing here traps or is
+// undefined for any n and any den >= 1 (kdenoise and kmerge also call it for a lane's columns past the row end, whose sums come
+// from samples that no output reads; their den is still 256 .. 6400, and the result is never stored).
 __device__ __forceinline__ uint32_t div_round(uint32_t n, uint32_t den)
 {
     uint32_t q = static_cast<uint32_t>(static_cast<float>(n) * __builtin_amdgcn_rcpf(static_cast<float>(den)));
     const int32_t r = static_cast<int32_t>(n - mul24(q, den)); // q <= 65537, den < 2^13: exact
+    MOS_DIV(r, den);
     q = r < 0 ? q - 1u : q;
     q = r >= static_cast<int32_t>(den) ? q + 1u : q;
     return q;
@@ -65,6 +83,9 @@ __device__ __forceinline__ mcraw_u32x4 load16(const uint16_t *src, bool vec)
 // 8 samples of columns x .. x + 7 (the first n exist) as (even column | odd column << 16) dwords.
 __device__ __forceinline__ void load8(const uint16_t *src, uint32_t n, bool vec, uint32_t p[4])
 {
+    MOS_PATH(MP_LD_VEC, n == 8u && vec);
+    MOS_PATH(MP_LD_UNAL, n == 8u && !vec);
+    MOS_PATH(MP_LD_ELEM, n != 8u);
     if (n == 8u) {
         const mcraw_u32x4 v = load16(src, vec);
         p[0] = v[0], p[1] = v[1], p[2] = v[2], p[3] = v[3];
@@ -83,6 +104,9 @@ __device__ __forceinline__ void load8(const uint16_t *src, uint32_t n, bool vec,
 template <bool NT>
 __device__ __forceinline__ void store8(uint16_t *dst, uint32_t n, bool vec, const uint32_t p[4])
 {
+    MOS_PATH(MP_ST_VEC, n == 8u && vec);
+    MOS_PATH(MP_ST_UNAL, n == 8u && !vec);
+    MOS_PATH(MP_ST_ELEM, n != 8u);
     if (n == 8u) {
         if (vec) {
             const mcraw_u32x4 v = {p[0], p[1], p[2], p[3]};
@@ -122,8 +146,10 @@ __device__ __forceinline__ void stage_tile(uint16_t *s, const uint16_t *in, size
     for (uint32_t i = threadIdx.x; i < LH * TILE_CH; i += TILE_T) {
         const uint32_t r = i / TILE_CH, q = i % TILE_CH;
         const int yy = y0 - HALO + static_cast<int>(r), xs = x0 - 8 + 8 * static_cast<int>(q);
+        MOS_PATH(MP_STG_SKIP, yy >= H + HALO || xs >= W + HALO);
         if (yy >= H + HALO || xs >= W + HALO) // no output of the frame reads it
             continue;
+        MOS_STAGE(q != 0u && q != TILE_CH - 1u, xs + 8 <= W, vec);
         const uint16_t *row = in + static_cast<size_t>(MAP(yy, H)) * pitch;
         mcraw_u32x4 v;
         if (q != 0u && q != TILE_CH - 1u && xs + 8 <= W) { // (xs >= 0 here) a full piece of the row
@@ -138,6 +164,15 @@ __device__ __forceinline__ void stage_tile(uint16_t *s, const uint16_t *in, size
         }
         *reinterpret_cast<mcraw_u32x4 *>(&s[r * TILE_LW + 8u * q]) = v;
     }
+}
+
+// `samples` (a multiple of 8) samples of an LDS tile buffer filled with 0xFFFF, and a barrier: what a test build puts in front
+// of staging, so that the chunks that staging leaves as they are hold the most hostile value instead of what LDS held.
+__device__ __forceinline__ void poison_tile(uint16_t *s, uint32_t samples)
+{
+    for (uint32_t i = threadIdx.x; i < samples / 8u; i += blockDim.x)
+        *reinterpret_cast<mcraw_u32x4 *>(&s[8u * i]) = mcraw_u32x4{0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+    __syncthreads();
 }
 
 } // namespace mcraw

@@ -7,7 +7,13 @@
 // every lane makes 8 consecutive columns of two rows (a 16-byte load and a 16-byte store each): per pixel one ds_read_b32 (both
 // horizontal neighbours), two 24-bit multiply-adds for G, the sample's multiply-add and the clamp.
 // Every pixel reads only itself, so out == in (in place) is fine.
+//
+// Test builds (build.MOSAIC_PATH_VARIANTS, tests/test_gpu_mosaic_paths.py; why each is valid: the head of mcraw_mosaic_paths.h):
+//   MCRAW_PATHSM  the path census; mcraw_diag_mosaic_paths below adds up the stage sources' counters
 #include "mcraw_host.h"
+#ifdef MCRAW_PATHSM
+#include "mcraw_mosaic_paths.h"
+#endif
 #include "mcraw_mosaic.h"
 
 namespace mcraw {
@@ -61,9 +67,12 @@ __global__ void __launch_bounds__(SH_T) kshade(const ShadeArgs A)
     const uint16_t *fin = A.in + static_cast<size_t>(f) * A.ifstride + x;
     uint16_t *fout = A.out + static_cast<size_t>(f) * A.ofstride + x;
     uint32_t p[SH_NPASS][4];
+    MOS_PATH(MP_WG, threadIdx.x == 0u);
+    MOS_PATH(MP_IDLE_LANE, !inside);
 #pragma unroll
     for (uint32_t a = 0; a < SH_NPASS; a++) {
         const uint32_t y = y0 + ly + a * SH_PASS;
+        MOS_PATH(MP_ROW_CONT, inside && y >= A.H);
         if (inside && y < A.H)
             load8(fin + static_cast<size_t>(y) * A.ipitch, n, A.invec != 0u, p[a]);
     }
@@ -118,9 +127,38 @@ __global__ void __launch_bounds__(SH_T) kshade(const ShadeArgs A)
     }
 }
 
+#ifdef MCRAW_PATHSM
+void mos_paths_read_fixpix(uint64_t *out, int n, int reset);     // mcraw_fixpix.hip
+void mos_paths_read_denoise(uint64_t *out, int n, int reset);    // mcraw_denoise.hip
+void mos_paths_read_highlights(uint64_t *out, int n, int reset); // mcraw_highlights.hip
+void mos_paths_read_stats(uint64_t *out, int n, int reset);      // mcraw_stats.hip
+void mos_paths_read_merge(uint64_t *out, int n, int reset);      // mcraw_merge.hip
+#endif
+
 } // namespace mcraw
 
 using namespace mcraw;
+
+#ifdef MCRAW_PATHSM
+// The census of the mosaic stages, in the order of MosPath, summed over the sources that have one (up to n counters; returns how
+// many there are); `reset`: and start it over.
+extern "C" int mcraw_diag_mosaic_paths(uint64_t *out, int n, int reset)
+{
+    n = n < 0 ? 0 : n < static_cast<int>(MP_N) ? n : static_cast<int>(MP_N);
+    for (int i = 0; out && i < n; i++)
+        out[i] = 0u;
+    if (out || reset) {
+        uint64_t none[MP_N];
+        mos_paths_read(out ? out : none, out ? n : 0, reset);
+        mos_paths_read_fixpix(out ? out : none, out ? n : 0, reset);
+        mos_paths_read_denoise(out ? out : none, out ? n : 0, reset);
+        mos_paths_read_highlights(out ? out : none, out ? n : 0, reset);
+        mos_paths_read_stats(out ? out : none, out ? n : 0, reset);
+        mos_paths_read_merge(out ? out : none, out ? n : 0, reset);
+    }
+    return static_cast<int>(MP_N);
+}
+#endif
 
 extern "C" int mcraw_shade_batch(mcraw_ctx *c, const mcraw_shade *s, const uint16_t *in, size_t in_pitch, size_t in_frame_stride,
                                  int width, int height, int n, uint16_t *out, size_t out_pitch, size_t out_frame_stride,

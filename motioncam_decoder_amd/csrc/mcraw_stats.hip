@@ -10,7 +10,15 @@
 // content) adds 256 once.  min / max / saturated count / sum stay in registers until the workgroup ends.  At its end a
 // workgroup adds the non-zero counters to the frame's record with global integer atomics: its write traffic is at most one
 // record, whatever the number of pixels.  kstats_init writes the empty records first (unless MCRAW_STATS_ACCUMULATE).
+//
+// Test builds (build.MOSAIC_PATH_VARIANTS, tests/test_gpu_mosaic_paths.py; why each is valid: the head of mcraw_mosaic_paths.h):
+//   MCRAW_PATHSM            the path census
+//   MCRAW_FORCE_SLOWM       no wave takes stats_tile<BL, true>, and with it none the one-bin shortcut
+//   MCRAW_STATS_MAXTILES=N  at most N tiles per workgroup
 #include "mcraw_host.h"
+#ifdef MCRAW_PATHSM
+#include "mcraw_mosaic_paths.h"
+#endif
 #include "mcraw_mosaic.h"
 
 namespace mcraw {
@@ -20,7 +28,16 @@ constexpr uint32_t ST_LX = 32u;  // lanes across a tile: 8 columns each
 constexpr uint32_t ST_TW = 8u * ST_LX;
 constexpr uint32_t ST_TH = 2u * (ST_T / ST_LX); // 2 rows per lane
 // Tiles per workgroup at most: a lane's 32-bit sum of a position grows by at most 4 * 65535 per tile, 8192 * 4 * 65535 < 2^32.
-constexpr uint32_t ST_MAXTILES = 8192u;
+#ifndef MCRAW_STATS_MAXTILES
+#define MCRAW_STATS_MAXTILES 8192
+#endif
+constexpr uint32_t ST_MAXTILES = MCRAW_STATS_MAXTILES;
+static_assert(ST_MAXTILES >= 1u && ST_MAXTILES <= 8192u, "a lane's 32-bit sums hold 8192 tiles at most");
+#ifdef MCRAW_FORCE_SLOWM
+constexpr bool ST_FULL_OK = false;
+#else
+constexpr bool ST_FULL_OK = true; // waves whose samples are all inside the window take stats_tile<BL, true>
+#endif
 constexpr uint32_t ST_WGS = 2048u; // workgroups a launch aims at (8 per CU)
 constexpr uint32_t ST_NOBIN = 0xFFFFFFFFu;
 
@@ -60,8 +77,10 @@ __device__ __forceinline__ uint32_t stats_load(const StatsArgs &A, const uint16_
     for (uint32_t a = 0; a < 2u; a++) {
         p[a][0] = p[a][1] = p[a][2] = p[a][3] = 0u;
         const uint32_t yy = y + a;
+        MOS_PATH(MP_SS_ROW_OUT, cols == 0u || yy < A.y0 || yy >= A.y1);
         if (cols == 0u || yy < A.y0 || yy >= A.y1)
             continue;
+        MOS_PATH(MP_SS_LD_EDGE, cols != 0xFFu);
         m |= 256u << a;
         const uint16_t *src = fin + static_cast<size_t>(yy) * A.ipitch + x;
         if (cols == 0xFFu) {
@@ -114,6 +133,7 @@ __device__ __forceinline__ void stats_tile(const StatsArgs &A, const uint32_t p[
             if (FULL) { // flat or clipped content: the wave's 256 samples of this position in one bin, one add
                 const uint32_t first = __builtin_amdgcn_readfirstlane(b[0]);
                 if (__all(b[0] == first && b[1] == first && b[2] == first && b[3] == first)) {
+                    MOS_WAVE(MP_SS_ONEBIN, true);
                     if (__lane_id() == 0u)
                         atomicAdd(h + first, 4u * 64u);
                     continue;
@@ -142,6 +162,7 @@ __global__ void __launch_bounds__(ST_T) kstats(const StatsArgs A)
     const uint32_t f = blockIdx.y, t0 = blockIdx.x * A.tpc, t1 = min(t0 + A.tpc, A.tiles);
     const uint32_t lx = threadIdx.x % ST_LX, ly = threadIdx.x / ST_LX;
     const uint16_t *fin = A.in + static_cast<size_t>(f) * A.ifstride;
+    MOS_PATH(MP_WG, threadIdx.x == 0u);
     uint32_t cur[2][4], nxt[2][4];
     uint32_t curm = stats_load(A, fin, t0, lx, ly, cur), nxtm = 0u; // in flight while LDS is cleared
     for (uint32_t i = threadIdx.x; i < NC * CS; i += ST_T)
@@ -155,9 +176,13 @@ __global__ void __launch_bounds__(ST_T) kstats(const StatsArgs A)
     S.mn[0] = S.mn[1] = 0xFFFFFFFFu;
     S.mx[0] = S.mx[1] = 0u;
     for (uint32_t t = t0; t < t1; t++) {
+        MOS_PATH(MP_SS_PREFETCH, threadIdx.x == 0u && t + 1u < t1);
         if (t + 1u < t1)
             nxtm = stats_load(A, fin, t + 1u, lx, ly, nxt); // the next tile's loads fly while this one is counted
-        if (__all(curm == 0x3FFu))
+        MOS_WAVE(MP_SS_FULL, ST_FULL_OK && __all(curm == 0x3FFu));
+        MOS_WAVE(MP_SS_PARTIAL, !(ST_FULL_OK && __all(curm == 0x3FFu)) && __any(curm != 0u));
+        MOS_WAVE(MP_SS_EMPTY, !__any(curm != 0u));
+        if (ST_FULL_OK && __all(curm == 0x3FFu))
             stats_tile<BL, true>(A, cur, curm, hc, S);
         else if (__any(curm != 0u))
             stats_tile<BL, false>(A, cur, curm, hc, S);
@@ -230,6 +255,10 @@ static uint32_t stats_parity(uint32_t lo, uint32_t hi, uint32_t par)
 {
     return ((hi + 1u - par) >> 1) - ((lo + 1u - par) >> 1);
 }
+
+#ifdef MCRAW_PATHSM
+void mos_paths_read_stats(uint64_t *out, int n, int reset) { mos_paths_read(out, n, reset); } // (mcraw_diag_mosaic_paths: mcraw_shade.hip)
+#endif
 
 } // namespace mcraw
 
