@@ -775,6 +775,53 @@ size_t mcraw_stats_record_bytes(uint32_t bins_log2);   /* 16 * B + 96; 0 for a b
 int mcraw_stats_batch(mcraw_ctx *ctx, const mcraw_stats *s, const uint16_t *in, size_t in_pitch, size_t in_frame_stride,
                       int width, int height, int n, void *out, size_t out_bytes, void *stream);
 
+/* ---- uint16 mosaics -> per-frame histograms of local noise energy by CFA position and signal level --------------------
+ *
+ * Measures what a noise profile (variance = S * x + O per CFA position: the table of mcraw_denoise_batch and
+ * mcraw_merge_batch) is fitted to.  Pitches and frame strides count uint16 elements.  Everything is an integer, so the
+ * result does not depend on the order of the additions: it is bit-exact.
+ * One window (x0, y0, w, h) in frame pixels, x0 and y0 even, w, h >= 16, is cut into blocks of 16 x 16 samples at
+ * (y0 + 16 j, x0 + 16 i); only whole blocks count, floor(h / 16) x floor(w / 16) of them, and only their samples are
+ * read.  Within a block each CFA position p = (y & 1) * 2 + (x & 1) holds an 8 x 8 plane b[r][c] of same-colour samples:
+ *   s = sum of b[r][c]                                                                        (below 2^22)
+ *   T = sum over r, c = 1 .. 6 of (b[r][c-1] - 2 b[r][c] + b[r][c+1])^2
+ *     + sum over r = 1 .. 6, c of (b[r-1][c] - 2 b[r][c] + b[r+1][c])^2
+ * 96 squared second differences: each has expectation 6 sigma^2 under white noise and is 0 on a linear gradient, so
+ * E[T] = 576 sigma^2.  |d| <= 4 * 65535, d^2 < 2^37, T < 2^43: 64-bit sums.  No halo, so nothing reflects.
+ * The (block, position) is rejected, nrej[p] += 1, if any of its 64 samples is >= sat[p] or < lo[p] (clipping at either
+ * end shrinks the variance; lo[p] = 0 disables the lower test, sat[p] = 0 rejects everything).  Otherwise
+ *   l  = min((s >> 6) >> shift, 31)                                                           the level bin
+ *   vb = 0 if T < 16, else with e = floor(log2 T), f = (T >> (e - 2)) & 3:  vb = min(4 * (e - 4) + f + 1, 127)
+ *   hist[p][l][vb] += 1;  nblk[p] += 1
+ * The energy bins are quarter octaves whose lower edges are 2^e * (1 + f / 4); mcraw_noise_energy_bin(T) is that formula.
+ * The record of one frame, records back to back in `out` (8-byte aligned):
+ *   uint32 hist[4][32][128];  uint32 nblk[4];  uint32 nrej[4]                                 65 568 bytes
+ * A frame of at most 65536 x 65536 has at most 2^24 blocks: no counter can wrap.
+ * Without MCRAW_NOISE_ACCUMULATE the call initialises the n records itself, on the stream; with it the call adds to the
+ * records that are there (a clip over several batches), and the counters wrap modulo 2^32 once the caller's total does.
+ * `in` may sit at any 2-byte alignment with any pitch (16-byte loads where base, pitch, stride and x0 allow it).
+ * `stream`: a hipStream_t, NULL = the context's own stream; the call queues the work and returns without synchronising.
+ * It takes no decode serial and leaves the decode slots, mcraw_ctx_errors, mcraw_ctx_last_serial and the context's stage
+ * alone.  n == 0 is a no-op; n may exceed 65535.  The launches have no id in mcraw_ctx_kernel_ms.
+ * Rejected (returns < 0, mcraw_last_error says why, starting with "mcraw_noise_batch: ", nothing is written): a NULL `s`, `in`
+ * or `out`; an odd `in` address; an `out` that is not 8-byte aligned; width or height outside 1 .. 65536; a pitch below
+ * width; n > 1 and a frame stride below (height - 1) * pitch + width; shift above 15; an odd x0 or y0; w or h below 16; a
+ * window that leaves the frame (computed without overflow); an unknown flag; a non-zero `reserved`;
+ * out_bytes < n * mcraw_noise_record_bytes(); an `out` range that overlaps the input's extent. */
+#define MCRAW_NOISE_ACCUMULATE 1u   /* flags: add to the records already at `out` instead of initialising them */
+typedef struct mcraw_noise {
+    uint32_t shift;          /* 0 .. 15: level bin of a plane = min(mean >> shift, 31)            */
+    uint32_t x0, y0, w, h;   /* the window, in frame pixels; x0, y0 even; w, h >= 16              */
+    uint16_t sat[4];         /* by CFA position: a plane with a sample >= sat[p] is rejected      */
+    uint16_t lo[4];          /* by CFA position: ... or with a sample < lo[p]                     */
+    uint32_t flags;          /* MCRAW_NOISE_ACCUMULATE or 0                                       */
+    uint32_t reserved;       /* must be 0                                                         */
+} mcraw_noise;               /* sizeof 44; x0 4, sat 20, lo 28, flags 36, reserved 40             */
+size_t mcraw_noise_record_bytes(void);                 /* 65568 */
+uint32_t mcraw_noise_energy_bin(uint64_t T);           /* the energy bin vb of T, on the host */
+int mcraw_noise_batch(mcraw_ctx *ctx, const mcraw_noise *s, const uint16_t *in, size_t in_pitch, size_t in_frame_stride,
+                      int width, int height, int n, void *out, size_t out_bytes, void *stream);
+
 /* ---- uint16 mosaics -> uint16 mosaics with the defective pixels taken out ------------------------------------------------
  *
  * Finds hot, dead and stuck pixels in `n` uint16 mosaics of width x height and replaces them, and replaces the pixels of an

@@ -22,7 +22,8 @@ __all__ = ["lib_path", "load", "Context", "Pool", "Frame", "EncFrame", "FloatOut
            "AlignCells", "Cells", "cell_grid", "align_window", "fit_crop", "Area", "RGB_AREA", "Resample", "RGB_RESAMPLE",
            "FILTER_LINEAR", "FILTER_CUBIC", "Warp", "RGB_WARP", "quantize_affine", "fit_affine", "stabilize", "RGB_HA",
            "Mesh", "RGB_MESH", "MESH_STEP", "mesh_grid", "affine_mesh", "distortion_mesh", "stabilize_mesh", "mesh_check",
-           "Highlights", "HighlightChroma", "HL_CLIP", "HL_REBUILD", "HL_ACCUMULATE", "highlight_gains"]
+           "Highlights", "HighlightChroma", "HL_CLIP", "HL_REBUILD", "HL_ACCUMULATE", "highlight_gains",
+           "Noise", "NoiseStats", "NOISE_ACCUMULATE", "noise_fit", "noise_quantile_gain"]
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 
@@ -56,6 +57,7 @@ ABI_SYMBOLS = [
     "mcraw_align_cells_batch", "mcraw_align_cells_work_bytes", "mcraw_merge_cells_batch",
     "mcraw_highlights_measure_batch", "mcraw_highlights_batch",
     "mcraw_mesh_nodes", "mcraw_mesh_check", "mcraw_demosaic_mesh_batch",
+    "mcraw_noise_batch", "mcraw_noise_record_bytes", "mcraw_noise_energy_bin",
 ]
 
 POST_BLACK, POST_PACK12, POST_PACK10, POST_PACK14 = 1, 2, 4, 8
@@ -732,6 +734,161 @@ def stats_clipped(st):
     return r[0] if single else r
 
 
+# the noise measurement of mosaics (mcraw_noise_batch)
+NOISE_ACCUMULATE = 1
+NOISE_LEVELS, NOISE_BINS = 32, 128
+NOISE_RECORD_BYTES = 4 * (4 * NOISE_LEVELS * NOISE_BINS + 8)
+
+
+class Noise(C.Structure):
+    """struct mcraw_noise (include/mcraw_hip.h): the level shift, the window, the rejection levels by CFA position, flags."""
+    _fields_ = [("shift", C.c_uint32), ("x0", C.c_uint32), ("y0", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32),
+                ("sat", C.c_uint16 * 4), ("lo", C.c_uint16 * 4), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class NoiseStats:
+    """What Context.noise_stats returns: `raw`, the (N, 65568) uint8 tensor of mcraw_noise_batch's records ((65568,) for an
+    (H, W) mosaic), and exact views into it, by CFA position p = (y & 1) * 2 + (x & 1): hist (N, 4, 32, 128) int32, the
+    count of accepted 16 x 16 blocks by level bin and energy bin; nblk, nrej (N, 4) int32, the accepted and the rejected
+    ones; shift as given.  A frame has at most 2^24 blocks, so the signed views are exact; records that were accumulated
+    into can pass 2^31: reinterpret them as unsigned.  The views are device tensors: reading them synchronises."""
+
+    def __init__(self, raw, shift):
+        import torch
+        self.raw, self.shift = raw, int(shift)
+        nh = 16 * NOISE_LEVELS * NOISE_BINS
+        self.hist = raw[..., :nh].view(torch.int32).unflatten(-1, (4, NOISE_LEVELS, NOISE_BINS))
+        self.nblk = raw[..., nh:nh + 16].view(torch.int32)
+        self.nrej = raw[..., nh + 16:nh + 32].view(torch.int32)
+
+    def cpu(self):
+        """The fields as numpy arrays on the host (a dict with hist, nblk, nrej, shift): what noise_fit takes."""
+        d = {k: getattr(self, k).cpu().numpy() for k in ("hist", "nblk", "nrej")}
+        d["shift"] = self.shift
+        return d
+
+
+def _noise_energy(planes):
+    """T of 8 x 8 planes (..., 8, 8) of integers: the sum of the 96 squared second differences along rows and columns."""
+    import numpy as np
+    b = np.asarray(planes).astype(np.int64)
+    dh = b[..., :, :-2] - 2 * b[..., :, 1:-1] + b[..., :, 2:]
+    dv = b[..., :-2, :] - 2 * b[..., 1:-1, :] + b[..., 2:, :]
+    return (dh * dh).sum((-1, -2)) + (dv * dv).sum((-1, -2))
+
+
+def _noise_energy_bin(T):
+    """The energy bin of T (int64 array, 0 <= T < 2^53): 0 below 16, else min(4 * (e - 4) + f + 1, 127)."""
+    import numpy as np
+    T = np.asarray(T, dtype=np.int64)
+    e = np.frexp(np.maximum(T, 16).astype(np.float64))[1].astype(np.int64) - 1  # floor(log2 T): exact below 2^53
+    f = (np.maximum(T, 16) >> (e - 2)) & 3
+    return np.where(T < 16, 0, np.minimum(4 * (e - 4) + f + 1, NOISE_BINS - 1))
+
+
+def _noise_edge(vb):
+    """The lower edge of energy bin vb >= 1: 2^e * (1 + f / 4)."""
+    return float(1 << (4 + (vb - 1) // 4)) * (1.0 + ((vb - 1) % 4) / 4.0)
+
+
+def _noise_quantile(counts, q):
+    """The point below which the fraction q of a 128-bin energy histogram lies, linear in log2 between the edges of the bin
+    that holds it.  Bins 0 and 127 have no two edges and never carry the answer: the point is clamped into bins 1 .. 126."""
+    import numpy as np
+    c = np.asarray(counts, dtype=np.float64)
+    cum = np.cumsum(c)
+    t = q * cum[-1]
+    j = min(max(int(np.searchsorted(cum, t)), 1), NOISE_BINS - 2)
+    fr = min(max((t - cum[j - 1]) / max(c[j], 1.0), 0.0), 1.0)
+    lo, hi = np.log2(_noise_edge(j)), np.log2(_noise_edge(j + 1))
+    return float(2.0 ** (lo + fr * (hi - lo)))
+
+
+@functools.lru_cache(maxsize=None)
+def noise_quantile_gain(quantile):
+    """K(quantile): the `quantile` point of T / sigma^2 of pure Gaussian noise, by a seeded simulation through the stage's own
+    arithmetic -- 3 x 16384 planes of rounded samples around level 32768 with sigma 16, 64 and 256, their T binned and the
+    point read from the histogram as noise_fit reads it -- and the mean of the three.  The mean of T / sigma^2 is 576; the
+    lower quantiles lie below it (K(0.15) is about 441, K(0.1) about 410).  Deterministic, cached per quantile."""
+    import numpy as np
+    rng = np.random.default_rng(0x6E6F6973)
+    ks = []
+    for sigma in (16.0, 64.0, 256.0):
+        planes = np.rint(32768.0 + sigma * rng.standard_normal((16384, 8, 8))).astype(np.int64)
+        h = np.bincount(_noise_energy_bin(_noise_energy(planes)), minlength=NOISE_BINS)
+        ks.append(_noise_quantile(h, quantile) / sigma ** 2)
+    return float(np.mean(ks))
+
+
+def _noise_line(x, y, w):
+    """Least squares of y = a * x + b with weights w under a, b >= 0: the free solution where it is feasible, else the better
+    of the two on the boundary."""
+    import numpy as np
+    sw, sx, sy = w.sum(), (w * x).sum(), (w * y).sum()
+    sxx, sxy = (w * x * x).sum(), (w * x * y).sum()
+    det = sw * sxx - sx * sx
+    if det > 0:
+        a, b = (sw * sxy - sx * sy) / det, (sxx * sy - sx * sxy) / det
+        if a >= 0 and b >= 0:
+            return a, b
+    cands = [(0.0, max(sy / sw, 0.0)), (max(sxy / sxx, 0.0) if sxx > 0 else 0.0, 0.0)]
+    return min(cands, key=lambda ab: float((w * (ab[0] * x + ab[1] - y) ** 2).sum()))
+
+
+def noise_fit(st, black, white, quantile=0.15, min_blocks=200, pool=True):
+    """The noise profile (S, O) -- variance = S * x + O on values x normalised to [0, 1], per CFA position
+    (row & 1) * 2 + (col & 1): what noise_lut takes -- from a NoiseStats (or its arrays on the CPU).  Each (4,) float64 over
+    the frames pooled, or (N, 4) per frame with pool=False.  On the CPU in float64, deterministic.
+    For every position p and level bin l with at least min_blocks accepted blocks the `quantile` point of the energy
+    histogram is read (linear in log2 between the bin's edges; bins 0 and 127 never carry it) and divided by
+    noise_quantile_gain(quantile), the same point of T / sigma^2 under pure Gaussian noise: the variance in DN^2 at the bin's
+    mid level m = (l << shift) + (1 << shift) / 2.  A textured block or one across an edge can only raise T, so a low
+    quantile follows the noise while most of a level's blocks may be textured.  var(m) = a * (m - black[p]) + b is fitted by
+    least squares, a, b >= 0, the weight of a bin being its block count over the square of its variance (a quantile of n blocks is
+    off by a fraction of itself that goes with 1 / sqrt(n)), and S = a / R, O = b / R^2 with R = white - black[p] invert
+    noise_lut's formula.  Raises ValueError when fewer than two level bins of a position qualify."""
+    import numpy as np
+    if isinstance(st, NoiseStats):
+        st = st.cpu()
+    get = st.__getitem__ if isinstance(st, dict) else (lambda k: getattr(st, k))
+    hist = np.asarray(get("hist")).astype(np.int64) & 0xFFFFFFFF
+    shift = int(get("shift"))
+    if hist.shape[-3:] != (4, NOISE_LEVELS, NOISE_BINS) or hist.ndim not in (3, 4):
+        raise ValueError("noise_fit: hist must be (4, 32, 128) or (N, 4, 32, 128)")
+    if not 0 < quantile < 1:
+        raise ValueError("noise_fit: quantile must be inside 0 .. 1")
+    hist = hist[None] if hist.ndim == 3 else hist
+    if pool:
+        hist = hist.sum(axis=0, keepdims=True)
+    black = np.asarray(black, dtype=np.float64)
+    black = np.full(4, float(black)) if black.ndim == 0 else black
+    white = float(white)
+    if black.shape != (4,) or not (white > black).all():
+        raise ValueError("noise_fit: black is one level or four, by CFA position, and white lies above them")
+    K = noise_quantile_gain(float(quantile))
+    mid = (np.arange(NOISE_LEVELS, dtype=np.float64) * (1 << shift)) + (1 << shift) / 2.0
+    S, O = np.zeros((hist.shape[0], 4)), np.zeros((hist.shape[0], 4))
+    for f in range(hist.shape[0]):
+        for p in range(4):
+            cnt = hist[f, p].sum(axis=-1)
+            use = np.nonzero(cnt >= max(int(min_blocks), 1))[0]
+            if use.size < 2:
+                raise ValueError("noise_fit: CFA position %d%s has %d level bins with at least %d accepted blocks, two are "
+                                 "needed (blocks by level bin: %s)" % (p, "" if pool else " of frame %d" % f, use.size,
+                                                                       min_blocks, cnt.tolist()))
+            var = np.array([_noise_quantile(hist[f, p, l], quantile) / K for l in use])
+            # A quantile of n blocks is off by a fraction of itself that goes with 1 / sqrt(n), whatever the variance: the weight
+            # of a bin is n / var^2, var first as measured, then twice as fitted (a measured one would favour the bins that
+            # came out low).
+            x, model = mid[use] - black[p], var
+            for _ in range(3):
+                a, b = _noise_line(x, var, cnt[use] / (model * model))
+                model = np.maximum(a * x + b, 0.25 * var)
+            R = white - black[p]
+            S[f, p], O[f, p] = a / R, b / (R * R)
+    return (S[0], O[0]) if pool else (S, O)
+
+
 # defective pixels of mosaics (mcraw_fixpix_batch)
 FIXPIX_HOT, FIXPIX_COLD = 1, 2
 FIXPIX_MAX_LIST = 1 << 20
@@ -1322,6 +1479,13 @@ def load():
     lib.mcraw_stats_record_bytes.argtypes = [C.c_uint32]
     lib.mcraw_stats_batch.restype = C.c_int
     lib.mcraw_stats_batch.argtypes = [C.c_void_p, C.POINTER(Stats), C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int,
+                                      C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.mcraw_noise_record_bytes.restype = C.c_size_t
+    lib.mcraw_noise_record_bytes.argtypes = []
+    lib.mcraw_noise_energy_bin.restype = C.c_uint32
+    lib.mcraw_noise_energy_bin.argtypes = [C.c_uint64]
+    lib.mcraw_noise_batch.restype = C.c_int
+    lib.mcraw_noise_batch.argtypes = [C.c_void_p, C.POINTER(Noise), C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int,
                                       C.c_void_p, C.c_size_t, C.c_void_p]
     lib.mcraw_fixpix_batch.restype = C.c_int
     lib.mcraw_fixpix_batch.argtypes = [C.c_void_p, C.POINTER(FixPix), C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int,
@@ -2290,6 +2454,75 @@ class Context:
         afterwards.  Returns the FrameStats of the (N, H, W) batch."""
         scratch = self._decode_scratch(inputs, width, height, type, check, "decode_stats")
         return self.stats(scratch, bins=bins, shift=shift, sat=sat, roi=roi, out=out, accumulate=accumulate)
+
+    def noise_stats(self, mosaic, *, shift=None, sat=65535, lo=0, roi=None, out=None, accumulate=False):
+        """Per-frame histograms of the local noise energy of uint16 mosaics resident on the context's device
+        (mcraw_noise_batch), by CFA position p = (y & 1) * 2 + (x & 1): the window is cut into blocks of 16 x 16 samples, each
+        position's 8 x 8 plane of a block gives its sum s and the sum T of its 96 squared second differences, and
+        hist[p][min((s >> 6) >> shift, 31)][energy bin of T] counts the block unless one of the plane's samples is >= sat[p] or
+        < lo[p] (nrej counts those).  mosaic: (N, H, W) or (H, W), rows contiguous (rows and frames may be strided).
+        shift=None: the smallest shift with (max(sat) >> shift) < 32.  sat, lo: one level or four, by CFA position.
+        roi=(y0, x0, h, w): the window, y0 and x0 even, h and w at least 16; only its whole blocks count and are read; None:
+        the whole frame.  Returns a NoiseStats over a new (N, 65568) uint8 tensor, or over `out` (a contiguous uint8 tensor of
+        that shape, 8-byte aligned), which the call initialises itself; accumulate=True adds to the records already in `out`
+        (a clip over several batches).  An (H, W) mosaic drops N.  noise_fit turns the result into the (S, O) of noise_lut.
+        Queued on torch.cuda.current_stream(); nothing synchronises."""
+        import torch
+        dev = self._torch_device(torch)
+        mos, single, n, h, w = self._mosaic_arg(torch, dev, "noise_stats", mosaic)
+
+        def four(v, name):
+            v = [int(v)] * 4 if not hasattr(v, "__len__") else [int(x) for x in v]
+            if len(v) != 4 or any(x < 0 or x > 65535 for x in v):
+                raise ValueError("%s: one level or four, by CFA position (row & 1) * 2 + (col & 1), each 0 .. 65535" % name)
+            return v
+
+        sat, lo = four(sat, "sat"), four(lo, "lo")
+        if shift is None:
+            shift = 0
+            while (max(sat) >> shift) >= NOISE_LEVELS:
+                shift += 1
+        y0, x0, rh, rw = (0, 0, h, w) if roi is None else (int(v) for v in roi)
+        if min(y0, x0) < 0 or (y0 | x0) & 1 or rh < 16 or rw < 16 or y0 + rh > h or x0 + rw > w:
+            raise ValueError("noise_stats: the window (y0, x0, h, w) = %r must start on even coordinates, hold 16 x 16 samples "
+                             "and lie inside the %d x %d frame" % ((y0, x0, rh, rw), h, w))
+        src = self._strided("noise_stats", "the mosaic", mos, h, w)
+        want = (NOISE_RECORD_BYTES,) if single else (n, NOISE_RECORD_BYTES)
+        if out is None and accumulate:
+            raise ValueError("noise_stats: accumulate=True needs the records to add to (out=)")
+        out = self._out_arg(torch, dev, "noise_stats", out, want, torch.uint8, contiguous=True)
+        res = NoiseStats(out, shift)
+        if n == 0:
+            return res
+        s = Noise()
+        s.shift, s.x0, s.y0, s.w, s.h = int(shift), x0, y0, rw, rh
+        for i in range(4):
+            s.sat[i], s.lo[i] = sat[i], lo[i]
+        s.flags, s.reserved = (NOISE_ACCUMULATE if accumulate else 0), 0
+        self._call(torch, dev, "mcraw_noise_batch", (mos, out), C.byref(s), *src, w, h, n, C.c_void_p(out.data_ptr()),
+                   n * NOISE_RECORD_BYTES)
+        return res
+
+    def decode_noise_stats(self, inputs, width, height, type, *, shift=None, sat=65535, lo=0, roi=None, out=None,
+                           accumulate=False, check=True):
+        """Decode frames of one geometry that are resident in HBM and measure their noise (noise_stats()): the plain uint16
+        mosaics go to a scratch tensor of torch's caching allocator, both steps are queued on torch.cuda.current_stream().
+        inputs, check and the context's stage: as decode_stats.  Returns the NoiseStats of the (N, H, W) batch."""
+        scratch = self._decode_scratch(inputs, width, height, type, check, "decode_noise_stats")
+        return self.noise_stats(scratch, shift=shift, sat=sat, lo=lo, roi=roi, out=out, accumulate=accumulate)
+
+    def estimate_noise(self, mosaic, black, white, *, sat=None, roi=None, quantile=0.15):
+        """The noise profile (S, O) of uint16 mosaics resident on the context's device, each (4,) float64 by CFA position, pooled
+        over the batch: noise_stats() with sat (white unless given) and lo = 1, so that blocks clipped at either end do not
+        count, one copy of the records to the host (which synchronises), and noise_fit(black, white, quantile).
+        `S, O = ctx.estimate_noise(m, black, white); lut, shift = noise_lut(S, O, black, white)` is the whole recipe for
+        denoise() and merge().  It belongs in front of shade() and denoise(): a gain map scales the noise with the position in
+        the frame, and a denoised frame has none left to measure.  One static frame of a flat wall is enough -- every level
+        bin that is to count needs 200 blocks --, and a scene with texture is fine as long as a sixth of each level's blocks
+        are smooth.  A clip whose ISO changes has no one profile: take noise_stats() and noise_fit(pool=False) per frame."""
+        white_i = int(white)
+        st = self.noise_stats(mosaic, sat=white_i if sat is None else sat, lo=1, roi=roi)
+        return noise_fit(st.cpu(), black, white, quantile=quantile)
 
     def decode_merge(self, inputs, width, height, type, *, lut, shift, check=True, align=None, **merge_kw):
         """Decode frames of one geometry that are resident in HBM and merge them along time (merge()): the plain uint16

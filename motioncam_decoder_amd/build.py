@@ -40,15 +40,15 @@ def _run(cmd):
     subprocess.run(cmd, check=True)
 
 
-# The gfx950 library: kernels (mcraw_type7 / mcraw_type6, the encoder mcraw_encode7, the demosaic mcraw_rgb, the lens-shading stage mcraw_shade, the statistics mcraw_stats, the defective-pixel stage mcraw_fixpix, the denoiser mcraw_denoise, the temporal merge mcraw_merge, the shift estimate mcraw_align and its cell-wise form mcraw_cells, the area-average demosaic mcraw_area, the resampling demosaic mcraw_resample, the affine warp mcraw_warp and the mesh warp mcraw_mesh, the edge-directed demosaic mcraw_ha, the highlight stage mcraw_highlights), the host side of the C ABI in its units (csrc/mcraw_host.h) and the device pool.
+# The gfx950 library: kernels (mcraw_type7 / mcraw_type6, the encoder mcraw_encode7, the demosaic mcraw_rgb, the lens-shading stage mcraw_shade, the statistics mcraw_stats, the defective-pixel stage mcraw_fixpix, the denoiser mcraw_denoise, the temporal merge mcraw_merge, the shift estimate mcraw_align and its cell-wise form mcraw_cells, the area-average demosaic mcraw_area, the resampling demosaic mcraw_resample, the affine warp mcraw_warp and the mesh warp mcraw_mesh, the edge-directed demosaic mcraw_ha, the highlight stage mcraw_highlights, the noise measurement mcraw_noise), the host side of the C ABI in its units (csrc/mcraw_host.h) and the device pool.
 HIP_SOURCES = ("mcraw_abi.hip", "mcraw_submit.hip", "mcraw_tune.hip", "mcraw_device.hip", "mcraw_hostmem.hip", "mcraw_pool.hip",
                "mcraw_type7.hip", "mcraw_type6.hip", "mcraw_encode7.hip", "mcraw_rgb.hip", "mcraw_shade.hip", "mcraw_stats.hip",
                "mcraw_fixpix.hip", "mcraw_denoise.hip", "mcraw_merge.hip", "mcraw_align.hip", "mcraw_area.hip", "mcraw_resample.hip", "mcraw_cells.hip", "mcraw_warp.hip", "mcraw_ha.hip",
-               "mcraw_highlights.hip", "mcraw_mesh.hip")
+               "mcraw_highlights.hip", "mcraw_mesh.hip", "mcraw_noise.hip")
 HIP_HEADERS = ("mcraw_plan.h", "mcraw_dev.h", "mcraw_host.h", "mcraw_race.h", "mcraw_mosaic.h", "mcraw_mosaic_args.h",
                "mcraw_rgb_args.h", "mcraw_align_args.h", "mcraw_area_args.h", "mcraw_rgb_dev.h", "mcraw_rgb_launch.h",
                "mcraw_resample_args.h", "mcraw_rgb_paths.h", "mcraw_align_pyr.h", "mcraw_cells_args.h", "mcraw_warp_args.h", "mcraw_ha_args.h",
-               "mcraw_highlights_args.h", "mcraw_warp_dev.h", "mcraw_mesh_args.h", "mcraw_mosaic_paths.h")
+               "mcraw_highlights_args.h", "mcraw_warp_dev.h", "mcraw_mesh_args.h", "mcraw_mosaic_paths.h", "mcraw_noise_args.h")
 HIP_FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc"]
 
 
@@ -195,6 +195,10 @@ MOSAIC_PATH_VARIANTS = {
     "th16": ["-DMCRAW_PATHSM", "-DMCRAW_MERGE_TH=16", "-DMCRAW_DENOISE_TH=16", "-DMCRAW_FIXPIX_TH=16"],
 }
 
+# knoise with at most one strip per workgroup (tests/test_gpu_noise.py): as many workgroups as strips flush into a frame's record,
+# and half of every workgroup idles.  The name occurs in mcraw_noise.hip alone, so the variant compiles that one source.
+NOISE_STRIP_FLAGS = ["-DMCRAW_NOISE_MAXSTRIPS=1"]
+
 # The merge with tiles of 16 rows instead of 32 (tools/bench_merge.py --alt-lib, tests/test_gpu_merge_cells.py): the name occurs in
 # mcraw_merge.hip alone.
 MERGE_ALT_FLAGS = ["-DMCRAW_MERGE_TH=16"]
@@ -215,9 +219,9 @@ def build_merge_alt():
 
 # The -D builds that tests/ links on the GPU box (tests/test_gpu_split.py, test_gpu_segw.py, test_gpu_lookback_fault.py,
 # test_gpu_k6_paths.py, test_gpu_k7_paths.py, test_gpu_enc7_paths.py, test_gpu_k7t_paths.py, test_gpu_rgb_paths.py,
-# test_gpu_mosaic_paths.py).
+# test_gpu_mosaic_paths.py, test_gpu_noise.py).
 TEST_VARIANTS = ((["-DMCRAW_FORCE_SEGW"], ["-DMCRAW_INJECT_MUTE7"], ["-DMCRAW_INJECT_LOST"]) + tuple(K6_PATH_VARIANTS.values())
-                 + tuple(K7_PATH_VARIANTS.values()) + tuple(ENC7_PATH_VARIANTS.values()) + tuple(K7T_PATH_VARIANTS.values()) + tuple(RGB_PATH_VARIANTS.values()) + tuple(MOSAIC_PATH_VARIANTS.values()) + (MERGE_ALT_FLAGS,))
+                 + tuple(K7_PATH_VARIANTS.values()) + tuple(ENC7_PATH_VARIANTS.values()) + tuple(K7T_PATH_VARIANTS.values()) + tuple(RGB_PATH_VARIANTS.values()) + tuple(MOSAIC_PATH_VARIANTS.values()) + (MERGE_ALT_FLAGS, NOISE_STRIP_FLAGS))
 
 
 def prebuild_test_variants():

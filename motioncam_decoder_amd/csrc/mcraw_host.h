@@ -14,6 +14,8 @@
 //   mcraw_align.hip    mcraw_align_batch: likewise (its geometry and scratch layout, free of HIP: mcraw_align_args.h)
 //   mcraw_highlights.hip  mcraw_highlights_batch, mcraw_highlights_measure_batch: likewise (the struct's checks and what the host
 //                      derives from it, free of HIP: mcraw_highlights_args.h)
+//   mcraw_noise.hip    mcraw_noise_batch: likewise (the struct's checks, the bins, the launch plan and the lane mapping, free of HIP:
+//                      mcraw_noise_args.h)
 //   mcraw_rgb.hip      the demosaic entry points of mhc and bin2 (their checks and plan, free of HIP: mcraw_rgb_args.h, which also
 //                      holds the window layer that the checks of the two scaled entry points below share)
 //   mcraw_area.hip     mcraw_demosaic_area_batch (its checks, plan and weights, free of HIP: mcraw_area_args.h)

@@ -6,10 +6,10 @@ one line per instance in the format of profiles/rgb_resources.txt / display_reso
 shade_resources.txt / stats_resources.txt / fixpix_resources.txt / denoise_resources.txt / merge_resources.txt / align_resources.txt /
 cells_resources.txt (kcells_* and kmerge<..., field>) / area_resources.txt (csrc/mcraw_area.hip: krgb_area and karea_tab) /
 resample_resources.txt (csrc/mcraw_resample.hip: krgb_resample and kres_tab) / warp_resources.txt (csrc/mcraw_warp.hip: krgb_warp) /
-mesh_resources.txt (csrc/mcraw_mesh.hip: krgb_mesh) / ha_resources.txt (csrc/mcraw_ha.hip: krgb_ha) / highlights_resources.txt (csrc/mcraw_highlights.hip: khl_apply, khl_clip, khl_measure, khl_init).
+mesh_resources.txt (csrc/mcraw_mesh.hip: krgb_mesh) / ha_resources.txt (csrc/mcraw_ha.hip: krgb_ha) / highlights_resources.txt (csrc/mcraw_highlights.hip: khl_apply, khl_clip, khl_measure, khl_init) / noise_resources.txt (csrc/mcraw_noise.hip: knoise, knoise_init).
 
     python tools/rgb_resources.py            # every instance
-    python tools/rgb_resources.py --check    # the figures in the sixteen committed files must equal the compiler's; exit 1 if not
+    python tools/rgb_resources.py --check    # the figures in the seventeen committed files must equal the compiler's; exit 1 if not
 """
 import os
 import re
@@ -49,6 +49,8 @@ HA_FILE = "ha_resources.txt"
 HA_NAME = r"Function Name: _ZN5mcraw\d+(krgb_ha)ILi(\d+)ELi(\d)EEEv"  # krgb_ha<kind, CFA shift>
 HL_FILE = "highlights_resources.txt"
 HL_NAME = r"Function Name: _ZN5mcraw\d+(khl_init|khl_measure|khl_apply|khl_clip)(?:ILb([01])EEEv|E)"  # khl_apply<NT>, khl_clip<NT>, the measure kernel, the records' init
+NOISE_FILE = "noise_resources.txt"
+NOISE_NAME = r"Function Name: _ZN5mcraw\d+(knoise_init|knoise)E"  # the measuring kernel, the records' init
 SHADE_NAME = r"Function Name: _ZN5mcraw\d+(kshade)ILb([01])EEEv"  # kshade<NT>: `sc1 nt` streaming stores or plain ones
 
 
@@ -75,7 +77,7 @@ def _label(m):
         return m.group(1)
     if m.group(1) in ("karea_tab", "kres_tab"):
         return m.group(1)
-    if m.group(1) in ("khl_init", "khl_measure"):
+    if m.group(1) in ("khl_init", "khl_measure", "knoise", "knoise_init"):
         return m.group(1)
     if m.group(1) in ("khl_apply", "khl_clip"):
         return "%s<%s>" % (m.group(1), "stream" if m.group(2) == "1" else "plain")
@@ -135,9 +137,10 @@ def main():
     ha = report("mcraw_ha.hip", HA_NAME)
     mesh = report("mcraw_mesh.hip", MESH_NAME)
     hl = report("mcraw_highlights.hip", HL_NAME)
+    noise = report("mcraw_noise.hip", NOISE_NAME)
     if "--check" not in sys.argv:
         for line in list(rep.values()) + list(shade.values()) + list(stats.values()) + list(fixpix.values()) + list(denoise.values()) + \
-                list(merge.values()) + list(align.values()) + list(area.values()) + list(resample.values()) + list(cells.values()) + list(warp.values()) + list(ha.values()) + list(hl.values()) + list(mesh.values()):
+                list(merge.values()) + list(align.values()) + list(area.values()) + list(resample.values()) + list(cells.values()) + list(warp.values()) + list(ha.values()) + list(hl.values()) + list(mesh.values()) + list(noise.values()):
             print(line)
         return 0
     return _check(FILES, rep, "krgb_") | _check((SHADE_FILE,), shade, "kshade") | _check((STATS_FILE,), stats, "kstats") | \
@@ -145,7 +148,7 @@ def main():
         _check((ALIGN_FILE,), align, "kalign") | _check((AREA_FILE,), area, ("krgb_area", "karea_tab")) | \
         _check((RESAMPLE_FILE,), resample, ("krgb_resample", "kres_tab")) | _check((CELLS_FILE,), cells, ("kcells_", "kmerge<")) | \
         _check((WARP_FILE,), warp, "krgb_warp") | _check((HA_FILE,), ha, "krgb_ha") | \
-        _check((HL_FILE,), hl, "khl_") | _check((MESH_FILE,), mesh, "krgb_mesh")
+        _check((HL_FILE,), hl, "khl_") | _check((MESH_FILE,), mesh, "krgb_mesh") | _check((NOISE_FILE,), noise, "knoise")
 
 
 if __name__ == "__main__":
