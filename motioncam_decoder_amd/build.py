@@ -48,7 +48,7 @@ HIP_SOURCES = ("mcraw_abi.hip", "mcraw_submit.hip", "mcraw_tune.hip", "mcraw_dev
 HIP_HEADERS = ("mcraw_plan.h", "mcraw_dev.h", "mcraw_host.h", "mcraw_race.h", "mcraw_mosaic.h", "mcraw_mosaic_args.h",
                "mcraw_rgb_args.h", "mcraw_align_args.h", "mcraw_area_args.h", "mcraw_rgb_dev.h", "mcraw_rgb_launch.h",
                "mcraw_resample_args.h", "mcraw_rgb_paths.h", "mcraw_align_pyr.h", "mcraw_cells_args.h", "mcraw_warp_args.h", "mcraw_ha_args.h",
-               "mcraw_highlights_args.h", "mcraw_warp_dev.h", "mcraw_mesh_args.h", "mcraw_mosaic_paths.h", "mcraw_noise_args.h")
+               "mcraw_highlights_args.h", "mcraw_warp_dev.h", "mcraw_mesh_args.h", "mcraw_mosaic_paths.h", "mcraw_noise_args.h", "mcraw_est_paths.h")
 HIP_FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc"]
 
 
@@ -194,6 +194,28 @@ MOSAIC_PATH_VARIANTS = {
     "pieces": ["-DMCRAW_PATHSM", "-DMCRAW_MERGE_PIECE=3", "-DMCRAW_STATS_MAXTILES=2"],
     "th16": ["-DMCRAW_PATHSM", "-DMCRAW_MERGE_TH=16", "-DMCRAW_DENOISE_TH=16", "-DMCRAW_FIXPIX_TH=16"],
 }
+# ... and with 2 frames per launch instead of up to 65535 in every stage but kmerge (which `pieces` cuts): the second and later
+# iterations of the stages' launch loops (test_gpu_mosaic_paths.py::test_mosaic_paths_frames2).  The name occurs in mcraw_shade.hip,
+# mcraw_stats.hip, mcraw_fixpix.hip, mcraw_denoise.hip and mcraw_highlights.hip alone.
+MOSAIC_FRAMES2_FLAGS = ["-DMCRAW_PATHSM", "-DMCRAW_STAGE_FRAMES=2"]
+
+# The estimators (kalign_pyr, kalign_down, kalign_zero, kalign_sad<0|1>, kalign_pick, kalign_final; kcells_zero, kcells_sad<0|1>,
+# kcells_pick, kcells_final; knoise) with every path counted, the launch loops split and the guarded paths forced
+# (tests/test_gpu_est_paths.py; the switches and why each is valid for every input: the head of csrc/mcraw_est_paths.h).  Every name
+# below occurs in mcraw_align.hip, mcraw_cells.hip and mcraw_noise.hip alone -- the shared headers count and cut the launch loops
+# through hooks that only those sources define --, so a variant compiles those three sources and nothing else.
+#   frames2  2 frames per launch instead of up to 65535: the second and later iterations of every launch loop
+#   slow     al_refine<false> for every wave; kcells_sad adds with atomics onto kcells_zero's zeros
+#   poison   0xFFFF in the SAD kernels' LDS tiles in front of staging
+#   strips1  knoise with one strip per workgroup
+EST_PATH_VARIANTS = {
+    "census": ["-DMCRAW_PATHSA"],
+    "frames2": ["-DMCRAW_PATHSA", "-DMCRAW_EST_FRAMES=2"],
+    "slow": ["-DMCRAW_PATHSA", "-DMCRAW_FORCE_SLOWA"],
+    "poison": ["-DMCRAW_PATHSA", "-DMCRAW_POISON_A"],
+    "poisonslow": ["-DMCRAW_PATHSA", "-DMCRAW_POISON_A", "-DMCRAW_FORCE_SLOWA"],
+    "strips1": ["-DMCRAW_PATHSA", "-DMCRAW_NOISE_MAXSTRIPS=1"],
+}
 
 # knoise with at most one strip per workgroup (tests/test_gpu_noise.py): as many workgroups as strips flush into a frame's record,
 # and half of every workgroup idles.  The name occurs in mcraw_noise.hip alone, so the variant compiles that one source.
@@ -219,9 +241,10 @@ def build_merge_alt():
 
 # The -D builds that tests/ links on the GPU box (tests/test_gpu_split.py, test_gpu_segw.py, test_gpu_lookback_fault.py,
 # test_gpu_k6_paths.py, test_gpu_k7_paths.py, test_gpu_enc7_paths.py, test_gpu_k7t_paths.py, test_gpu_rgb_paths.py,
-# test_gpu_mosaic_paths.py, test_gpu_noise.py).
+# test_gpu_mosaic_paths.py, test_gpu_noise.py, test_gpu_est_paths.py).
 TEST_VARIANTS = ((["-DMCRAW_FORCE_SEGW"], ["-DMCRAW_INJECT_MUTE7"], ["-DMCRAW_INJECT_LOST"]) + tuple(K6_PATH_VARIANTS.values())
-                 + tuple(K7_PATH_VARIANTS.values()) + tuple(ENC7_PATH_VARIANTS.values()) + tuple(K7T_PATH_VARIANTS.values()) + tuple(RGB_PATH_VARIANTS.values()) + tuple(MOSAIC_PATH_VARIANTS.values()) + (MERGE_ALT_FLAGS, NOISE_STRIP_FLAGS))
+                 + tuple(K7_PATH_VARIANTS.values()) + tuple(ENC7_PATH_VARIANTS.values()) + tuple(K7T_PATH_VARIANTS.values()) + tuple(RGB_PATH_VARIANTS.values()) + tuple(MOSAIC_PATH_VARIANTS.values()) + (MERGE_ALT_FLAGS, NOISE_STRIP_FLAGS, MOSAIC_FRAMES2_FLAGS)
+                 + tuple(EST_PATH_VARIANTS.values()))
 
 
 def prebuild_test_variants():

@@ -19,6 +19,19 @@
 //   kalign_final    the chain's prefix sum over n in int32 (or the anchor form), the clamp, pos and sad.
 // The pyramid's launches (align_pyramid), the pair rule and the nine-candidate refinement (al_refine) are shared with the cell-wise
 // estimate, mcraw_cells.hip, through mcraw_align_pyr.h.
+//
+// Test builds (tests/test_gpu_est_paths.py, build.EST_PATH_VARIANTS; why each is valid: the head of mcraw_est_paths.h):
+//   MCRAW_PATHSA        the path census; mcraw_diag_est_paths below adds up the three estimator sources' counters
+//   MCRAW_EST_FRAMES=N  the launch loops take N frames at a time
+//   MCRAW_FORCE_SLOWA   every wave of kalign_sad<1> takes al_refine<false>
+//   MCRAW_POISON_A      s_m and s_b of kalign_sad hold 0xFFFF samples in front of staging
+#ifdef MCRAW_PATHSA
+#include "mcraw_est_paths.h"
+#define EST_LD_BASE ::mcraw::EP_PY_LD
+#endif
+#ifdef MCRAW_EST_FRAMES
+#define LAUNCH_PIECE MCRAW_EST_FRAMES
+#endif
 #include "mcraw_align_pyr.h"
 
 namespace mcraw {
@@ -31,6 +44,11 @@ constexpr uint32_t AL_PH = 64u;  //   8 lanes down with 8 rows each (kalign_sad'
 constexpr uint32_t AL_STOP = MCRAW_ALIGN_STOP;
 #else
 constexpr uint32_t AL_STOP = 0u;
+#endif
+#ifdef MCRAW_FORCE_SLOWA
+constexpr bool AL_SLOW = true;
+#else
+constexpr bool AL_SLOW = false;
 #endif
 
 struct AlLevels { // a frame's pyramid
@@ -62,6 +80,8 @@ __global__ void __launch_bounds__(AL_T) kalign_pyr(const AlPyrArgs A)
     const uint32_t f = blockIdx.y, ty = blockIdx.x / A.tilesX, tx = blockIdx.x - ty * A.tilesX;
     const uint32_t lx = threadIdx.x % 32u, ly = threadIdx.x / 32u;
     const uint32_t x = tx * AL_PW + 8u * lx, y = ty * AL_PH + 8u * ly; // the lane's 8 x 8 samples
+    EST_ONE(EP_PY_WG, true);
+    EST_PATH(EP_PY_RET, x >= A.W || y >= A.H);
     if (x >= A.W || y >= A.H)
         return;
     const uint16_t *src = A.in + static_cast<size_t>(f) * A.ifstride + static_cast<size_t>(y) * A.ipitch + x;
@@ -69,6 +89,7 @@ __global__ void __launch_bounds__(AL_T) kalign_pyr(const AlPyrArgs A)
     uint32_t p[8][4];
 #pragma unroll
     for (uint32_t r = 0; r < 8u; r++) {
+        EST_PATH(EP_PY_ZERO_ROW, y + r >= A.H);
         if (y + r < A.H)
             load8(src + static_cast<size_t>(r) * A.ipitch, nc, A.vec != 0u, p[r]);
         else
@@ -88,8 +109,11 @@ __global__ void __launch_bounds__(AL_T) kalign_pyr(const AlPyrArgs A)
         uint16_t *dst = pyr + A.L.off[0] + static_cast<size_t>(gy) * A.L.pitch[0] + gx; // 8-byte aligned: gx % 4 == 0, rows of 16 bytes
 #pragma unroll
         for (uint32_t r = 0; r < 4u; r++) {
+            EST_ADDN(EP_PY_G0_LEFT, gy + r >= h0, 4u - r);
             if (gy + r >= h0)
                 break;
+            EST_PATH(EP_PY_G0_VEC, gx + 4u <= w0);
+            EST_PATH(EP_PY_G0_ELEM, gx + 4u > w0);
             uint16_t *d = dst + static_cast<size_t>(r) * A.L.pitch[0];
             if (gx + 4u <= w0) {
                 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
@@ -102,6 +126,7 @@ __global__ void __launch_bounds__(AL_T) kalign_pyr(const AlPyrArgs A)
             }
         }
     }
+    EST_PATH(EP_PY_RET_L2, A.levels < 2u);
     if (A.levels < 2u)
         return;
     uint32_t g1[2][2];
@@ -115,8 +140,12 @@ __global__ void __launch_bounds__(AL_T) kalign_pyr(const AlPyrArgs A)
         uint16_t *dst = pyr + A.L.off[1] + static_cast<size_t>(gy) * A.L.pitch[1] + gx; // 4-byte aligned: gx % 2 == 0
 #pragma unroll
         for (uint32_t r = 0; r < 2u; r++) {
+            EST_ADDN(EP_PY_G1_LEFT, gy + r >= h1, 2u - r);
             if (gy + r >= h1)
                 break;
+            EST_PATH(EP_PY_G1_DWORD, gx + 2u <= w1);
+            EST_PATH(EP_PY_G1_ELEM, gx + 2u > w1 && gx < w1);
+            EST_PATH(EP_PY_G1_NONE, gx >= w1);
             uint16_t *d = dst + static_cast<size_t>(r) * A.L.pitch[1];
             if (gx + 2u <= w1)
                 *gptr<uint32_t>(d) = g1[r][0] | (g1[r][1] << 16);
@@ -124,9 +153,12 @@ __global__ void __launch_bounds__(AL_T) kalign_pyr(const AlPyrArgs A)
                 *gptr<uint16_t>(d) = static_cast<uint16_t>(g1[r][0]);
         }
     }
+    EST_PATH(EP_PY_RET_L3, A.levels < 3u);
     if (A.levels < 3u)
         return;
     const uint32_t gx = x >> 3, gy = y >> 3;
+    EST_PATH(EP_PY_G2_STORE, gx < A.L.w[2] && gy < A.L.h[2]);
+    EST_PATH(EP_PY_G2_NONE, !(gx < A.L.w[2] && gy < A.L.h[2]));
     if (gx < A.L.w[2] && gy < A.L.h[2])
         gptr<uint16_t>(pyr + A.L.off[2] + static_cast<size_t>(gy) * A.L.pitch[2])[gx] =
             static_cast<uint16_t>((g1[0][0] + g1[0][1] + g1[1][0] + g1[1][1] + 2u) >> 2);
@@ -137,6 +169,8 @@ __global__ void __launch_bounds__(AL_T) kalign_down(uint16_t *pyr, size_t pstrid
                                                     uint32_t dh, uint32_t dw)
 {
     const uint32_t i = blockIdx.x * AL_T + threadIdx.x;
+    EST_ONE(EP_DN_LAUNCH, blockIdx.x == 0u && blockIdx.y == 0u);
+    EST_PATH(EP_DN_PAST, i >= dh * dw);
     if (i >= dh * dw)
         return;
     const uint32_t y = i / dw, x = i - y * dw;
@@ -148,6 +182,7 @@ __global__ void __launch_bounds__(AL_T) kalign_down(uint16_t *pyr, size_t pstrid
 
 __global__ void __launch_bounds__(AL_T) kalign_zero(unsigned long long *p, size_t words)
 {
+    EST_ONE(EP_AZ_LAUNCH, blockIdx.x == 0u);
     const size_t step = static_cast<size_t>(gridDim.x) * AL_T;
     for (size_t i = static_cast<size_t>(blockIdx.x) * AL_T + threadIdx.x; i < words; i += step)
         p[i] = 0ull;
@@ -168,11 +203,17 @@ struct AlSadArgs {
 
 // rows x ndw dwords of the plane from row ys, even column xs on into s (LW elements per row); 0 below the plane.  The columns
 // between w and pitch hold whatever the scratch held: no pixel of the window reads them.
-__device__ __forceinline__ void al_stage(uint32_t *s, uint32_t LW, const uint16_t *plane, uint32_t pitch, uint32_t h, uint32_t ys,
+// (SLOT, w: the census's, test builds only)
+template <uint32_t SLOT>
+__device__ __forceinline__ void al_stage(uint32_t *s, uint32_t LW, const uint16_t *plane, uint32_t pitch, uint32_t h, uint32_t w, uint32_t ys,
                                          uint32_t xs, uint32_t rows, uint32_t ndw)
 {
     for (uint32_t i = threadIdx.x; i < rows * ndw; i += AL_T) {
         const uint32_t r = i / ndw, j = i - r * ndw, yy = ys + r, col = xs + 2u * j;
+        EST_PATH(SLOT + SK_STG_LOAD, yy < h && col < pitch);
+        EST_PATH(SLOT + SK_STG_ZERO_Y, yy >= h);
+        EST_PATH(SLOT + SK_STG_ZERO_COL, yy < h && col >= pitch);
+        EST_PATH(SLOT + SK_STG_PAD, yy < h && col < pitch && col + 1u >= w);
         uint32_t v = 0u;
         if (yy < h && col < pitch)
             v = *gptr<const uint32_t>(plane + static_cast<size_t>(yy) * pitch + col);
@@ -191,8 +232,23 @@ __global__ void __launch_bounds__(AL_T) kalign_sad(const AlSadArgs A)
     __shared__ __attribute__((aligned(16))) uint32_t s_b[AL_TH * LW / 2u];
     __shared__ uint32_t s_acc[NC];
     const int t = A.t0 + static_cast<int>(blockIdx.y), b = al_base(t, A.ref);
+#ifdef MCRAW_PATHSA
+    constexpr uint32_t SLOT = EP_AS + RT * SK_N; // this instance's counters
+#else
+    constexpr uint32_t SLOT = 0u;
+#endif
+    EST_ONE(SLOT + SK_LAUNCH, blockIdx.x == 0u && blockIdx.y == 0u);
+    EST_ONE(SLOT + SK_WG, true);
+    EST_ONE(SLOT + SK_NOPAIR, b < 0);
     if (b < 0) // (uniform over the workgroup)
         return;
+#ifdef MCRAW_POISON_A
+    for (uint32_t i = threadIdx.x; i < sizeof(s_m) / 4u; i += AL_T)
+        s_m[i] = 0xFFFFFFFFu;
+    for (uint32_t i = threadIdx.x; i < sizeof(s_b) / 4u; i += AL_T)
+        s_b[i] = 0xFFFFFFFFu;
+    __syncthreads();
+#endif
     const uint32_t R = RT ? 1u : A.R, ncand = (2u * R + 1u) * (2u * R + 1u);
     int cy = 0, cx = 0;
     if (!A.top) {
@@ -206,15 +262,19 @@ __global__ void __launch_bounds__(AL_T) kalign_sad(const AlSadArgs A)
     const uint16_t *pb = A.pyr + static_cast<size_t>(b) * A.pstride + A.loff, *pm = A.pyr + static_cast<size_t>(t) * A.pstride + A.loff;
     for (uint32_t i = threadIdx.x; i < ncand; i += AL_T)
         s_acc[i] = 0u;
-    al_stage(s_b, LW, pb, A.pitch, A.h, y0, x0 & ~1u, AL_TH, AL_TW / 2u + 1u);
-    al_stage(s_m, LW, pm, A.pitch, A.h, ym, xm & ~1u, AL_TH + 2u * R, AL_TW / 2u + R + 1u);
+    EST_ONE(SLOT + SK_OM0 + 2u * ob + om, true);
+    al_stage<SLOT>(s_b, LW, pb, A.pitch, A.h, A.w, y0, x0 & ~1u, AL_TH, AL_TW / 2u + 1u);
+    al_stage<SLOT>(s_m, LW, pm, A.pitch, A.h, A.w, ym, xm & ~1u, AL_TH + 2u * R, AL_TW / 2u + R + 1u);
     __syncthreads();
     const uint32_t lx = threadIdx.x % 32u, ly = threadIdx.x / 32u;
     const uint32_t px = x0 + 4u * lx, py = y0 + 4u * ly; // the lane's 4 x 4 pixels
     const uint32_t nx = px < x1 ? min(4u, x1 - px) : 0u, ny = py < y1 ? min(4u, y1 - py) : 0u;
+    EST_PATH(SLOT + SK_LANE_EMPTY, nx == 0u || ny == 0u);
     if (RT) {
         uint32_t acc[9];
-        if (__all(nx == 4u && ny == 4u)) // the window's interior: no masks
+        EST_PATH(SLOT + SK_REF_FULL, __all(nx == 4u && ny == 4u) && !AL_SLOW && __lane_id() == 0u); // (every lane takes part in __all)
+        EST_PATH(SLOT + SK_REF_MASK, !(__all(nx == 4u && ny == 4u) && !AL_SLOW) && __lane_id() == 0u);
+        if (!AL_SLOW && __all(nx == 4u && ny == 4u)) // the window's interior: no masks
             al_refine<true>(s_b, s_m, LW / 2u, lx, ly, ob, om, nx, ny, acc);
         else
             al_refine<false>(s_b, s_m, LW / 2u, lx, ly, ob, om, nx, ny, acc);
@@ -224,6 +284,8 @@ __global__ void __launch_bounds__(AL_T) kalign_sad(const AlSadArgs A)
 #pragma unroll
             for (int d = 32; d >= 1; d >>= 1)
                 v += __shfl_xor(v, d);
+            EST_PATH(SLOT + SK_WAVE_ADD, __lane_id() == 0u && v != 0u);
+            EST_PATH(SLOT + SK_WAVE_SKIP, __lane_id() == 0u && v == 0u);
             if (__lane_id() == 0u && v)
                 atomicAdd(&s_acc[c], v);
         }
@@ -251,12 +313,20 @@ __global__ void __launch_bounds__(AL_T) kalign_sad(const AlSadArgs A)
 #pragma unroll
             for (int d = 32; d >= 1; d >>= 1)
                 v += __shfl_xor(v, d);
+            EST_PATH(SLOT + SK_WAVE_ADD, __lane_id() == 0u && v != 0u);
+            EST_PATH(SLOT + SK_WAVE_SKIP, __lane_id() == 0u && v == 0u);
             if (__lane_id() == 0u && v)
                 atomicAdd(&s_acc[c], v);
         }
     }
     __syncthreads();
     unsigned long long *acc = A.acc + static_cast<size_t>(t) * A.nacc + A.acc0;
+#ifdef MCRAW_PATHSA
+    for (uint32_t i = threadIdx.x; i < ncand; i += AL_T) {
+        EST_PATH(SLOT + SK_GLOB_ADD, s_acc[i] != 0u);
+        EST_PATH(SLOT + SK_GLOB_SKIP, s_acc[i] == 0u);
+    }
+#endif
     for (uint32_t i = threadIdx.x; i < ncand; i += AL_T)
         if (s_acc[i])
             atomicAdd(acc + i, static_cast<unsigned long long>(s_acc[i]));
@@ -268,6 +338,7 @@ __global__ void __launch_bounds__(AL_T) kalign_pick(const unsigned long long *ac
                                                     uint32_t level, uint32_t top, int n, int ref)
 {
     const int t = static_cast<int>(blockIdx.x * AL_T + threadIdx.x);
+    EST_PATH(EP_AP_NOPAIR, t >= n || al_base(t, ref) < 0);
     if (t >= n || al_base(t, ref) < 0)
         return;
     AlignWin *wv = win + static_cast<size_t>(t) * AL_MAXLEVELS;
@@ -305,6 +376,7 @@ __global__ void __launch_bounds__(AL_T) kalign_final(const AlignWin *win, int16_
             const AlignWin wv = win[static_cast<size_t>(t) * AL_MAXLEVELS];
             dy = 2 * wv.dy, dx = 2 * wv.dx, sv = wv.sad;
         }
+        EST_ONE(EP_AF_PIECE, ref < 0);
         if (ref < 0) { // inclusive scan of the piece (uniform: every thread takes part)
             s_y[threadIdx.x] = dy, s_x[threadIdx.x] = dx;
             __syncthreads();
@@ -318,6 +390,8 @@ __global__ void __launch_bounds__(AL_T) kalign_final(const AlignWin *win, int16_
             carry_y += s_y[AL_T - 1], carry_x += s_x[AL_T - 1];
             __syncthreads();
         }
+        EST_PATH(EP_AF_CLAMP, t < n && (dy < -32768 || dy > 32767));
+        EST_PATH(EP_AF_CLAMP, t < n && (dx < -32768 || dx > 32767));
         if (t < n) {
             pos[2 * static_cast<size_t>(t)] = static_cast<int16_t>(max(-32768, min(32767, dy)));
             pos[2 * static_cast<size_t>(t) + 1u] = static_cast<int16_t>(max(-32768, min(32767, dx)));
@@ -339,6 +413,29 @@ extern "C" size_t mcraw_align_work_bytes(int width, int height, int n, uint32_t 
     return P.total;
 }
 
+#ifdef MCRAW_PATHSA
+void est_paths_read_cells(uint64_t *out, int n, int reset); // mcraw_cells.hip
+void est_paths_read_noise(uint64_t *out, int n, int reset); // mcraw_noise.hip
+#endif
+
+// The census of the three estimator sources added up into out[0 .. n), and started over when `reset`; returns the number of
+// counters, 0 in a build without the census (mcraw_est_paths.h).
+extern "C" int mcraw_diag_est_paths(uint64_t *out, int n, int reset)
+{
+#ifdef MCRAW_PATHSA
+    uint64_t none[1];
+    for (int i = 0; out && i < n; i++)
+        out[i] = 0u;
+    est_paths_read(out ? out : none, out ? n : 0, reset);
+    est_paths_read_cells(out ? out : none, out ? n : 0, reset);
+    est_paths_read_noise(out ? out : none, out ? n : 0, reset);
+    return static_cast<int>(EP_N);
+#else
+    (void)out, (void)n, (void)reset;
+    return 0;
+#endif
+}
+
 // The pyramids of the n frames (mcraw_align_pyr.h): the launch loop of the mosaic stages, grid.y frames at a time.
 int mcraw::align_pyramid(hipStream_t st, const MosaicBatch &I, const uint16_t *in, int n, const uint16_t black[4], const AlPyramid &G, uint16_t *pyr)
 {
@@ -351,8 +448,8 @@ int mcraw::align_pyramid(hipStream_t st, const MosaicBatch &I, const uint16_t *i
     Y.blk[1] = black[2] | (static_cast<uint32_t>(black[3]) << 16);
     for (uint32_t l = 0; l < G.levels; l++)
         Y.L.h[l] = G.h[l], Y.L.w[l] = G.w[l], Y.L.pitch[l] = G.pitch[l], Y.L.off[l] = G.off[l];
-    for (int f0 = 0; f0 < n; f0 += LAUNCH_FRAMES) {
-        const uint32_t nf = static_cast<uint32_t>(std::min(LAUNCH_FRAMES, n - f0));
+    for (int f0 = 0; f0 < n; f0 += LAUNCH_PIECE) {
+        const uint32_t nf = static_cast<uint32_t>(std::min<int>(LAUNCH_PIECE, n - f0));
         Y.in = in + static_cast<size_t>(f0) * I.fstride;
         Y.pyr = pyr + static_cast<size_t>(f0) * G.frame_elems;
         hipLaunchKernelGGL(kalign_pyr, dim3(Y.tilesX * ((Y.H + AL_PH - 1u) / AL_PH), nf), dim3(AL_T), 0, st, Y);
@@ -398,9 +495,9 @@ static int mcraw_align_launch(mcraw_ctx *c, const mcraw_align *a, const MosaicBa
             S.tilesX = (S.w - 2u * S.B + AL_TW - 1u) / AL_TW;
             S.ref = a->ref;
             const uint32_t tiles = S.tilesX * ((S.h - 2u * S.B + AL_TH - 1u) / AL_TH);
-            for (int f0 = 0; f0 < n; f0 += LAUNCH_FRAMES) {
+            for (int f0 = 0; f0 < n; f0 += LAUNCH_PIECE) {
                 S.t0 = f0;
-                const dim3 grid(tiles, static_cast<uint32_t>(std::min(LAUNCH_FRAMES, n - f0)));
+                const dim3 grid(tiles, static_cast<uint32_t>(std::min<int>(LAUNCH_PIECE, n - f0)));
                 if (S.R == 1u)
                     hipLaunchKernelGGL(kalign_sad<1>, grid, dim3(AL_T), 0, st, S);
                 else

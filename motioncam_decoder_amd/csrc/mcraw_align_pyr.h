@@ -6,6 +6,18 @@
 #include "mcraw_mosaic.h"
 #include "mcraw_align_args.h"
 
+// The hooks of the path census of the estimators (mcraw_est_paths.h, test builds only): empty unless a source defined them in
+// front of this header.
+#ifndef EST_PATH
+#define EST_PATH(slot, cond)
+#endif
+#ifndef EST_ADDN
+#define EST_ADDN(slot, cond, n)
+#endif
+#ifndef EST_ONE
+#define EST_ONE(slot, cond)
+#endif
+
 namespace mcraw {
 
 constexpr int AL_T = 256;        // threads per workgroup

@@ -16,10 +16,29 @@
 //                     adds each with one 64-bit atomic.
 //   kcells_pick       a thread per (pair, cell): the winner at the level by the contract's key.
 //   kcells_final      a thread per cell: the chain's running sum over n in int32 (or the anchor form), the clamp, pos and sad.
+//
+// Test builds (tests/test_gpu_est_paths.py, build.EST_PATH_VARIANTS; why each is valid: the head of mcraw_est_paths.h):
+//   MCRAW_PATHSA        the path census (mcraw_diag_est_paths: mcraw_align.hip)
+//   MCRAW_EST_FRAMES=N  the launch loop takes N frames at a time
+//   MCRAW_FORCE_SLOWA   every wave of kcells_sad<1> takes al_refine<false>; every cell adds its sums with atomics, onto kcells_zero's zeros
+//   MCRAW_POISON_A      s_m and s_b of kcells_sad hold 0xFFFF samples in front of staging
+#ifdef MCRAW_PATHSA
+#include "mcraw_est_paths.h"
+#define EST_LD_BASE ::mcraw::EP_PY_LD // (load8 is not called in here)
+#endif
+#ifdef MCRAW_EST_FRAMES
+#define LAUNCH_PIECE MCRAW_EST_FRAMES
+#endif
 #include "mcraw_align_pyr.h"
 #include "mcraw_cells_args.h"
 
 namespace mcraw {
+
+#ifdef MCRAW_FORCE_SLOWA
+constexpr bool CL_SLOW = true;
+#else
+constexpr bool CL_SLOW = false;
+#endif
 
 struct ClSadArgs {
     const uint16_t *pyr;     // frame 0's pyramid
@@ -49,12 +68,19 @@ __device__ __forceinline__ void cl_centre(const int16_t *gpos, int t, int b, uin
 
 // rows x ndw dwords into s (LW elements per row): dword j of row r holds the plane's pixels (ys + r, xs + 2 j) and (ys + r,
 // xs + 2 j + 1), each coordinate clamped into the plane (h, w >= 1).  xs is even, so a dword inside the plane is one aligned load.
+// (SLOT: the census's, test builds only)
+template <uint32_t SLOT>
 __device__ __forceinline__ void cl_stage(uint32_t *s, uint32_t LW, const uint16_t *plane, uint32_t pitch, int h, int w, int ys, int xs,
                                          uint32_t rows, uint32_t ndw)
 {
     for (uint32_t i = threadIdx.x; i < rows * ndw; i += AL_T) {
         const uint32_t r = i / ndw, j = i - r * ndw;
         const int yy = min(max(ys + static_cast<int>(r), 0), h - 1), col = xs + 2 * static_cast<int>(j);
+        EST_PATH(SLOT + SK_STG_LOAD, col >= 0 && col + 1 < w);
+        EST_PATH(SLOT + SK_STG_LEFT, col < 0);
+        EST_PATH(SLOT + SK_STG_RIGHT, col >= 0 && col + 1 >= w);
+        EST_PATH(SLOT + SK_ROW_ABOVE, j == 0u && ys + static_cast<int>(r) < 0);
+        EST_PATH(SLOT + SK_ROW_BELOW, j == 0u && ys + static_cast<int>(r) > h - 1);
         const uint16_t *row = plane + static_cast<size_t>(yy) * pitch;
         uint32_t v;
         if (col >= 0 && col + 1 < w) {
@@ -78,8 +104,23 @@ __global__ void __launch_bounds__(AL_T) kcells_sad(const ClSadArgs A)
     __shared__ __attribute__((aligned(16))) uint32_t s_b[AL_TH * LW / 2u];
     __shared__ uint32_t s_acc[NC];
     const int t = A.t0 + static_cast<int>(blockIdx.y), b = al_base(t, A.ref);
+#ifdef MCRAW_PATHSA
+    constexpr uint32_t SLOT = EP_CS + RT * SK_N; // this instance's counters
+#else
+    constexpr uint32_t SLOT = 0u;
+#endif
+    EST_ONE(SLOT + SK_LAUNCH, blockIdx.x == 0u && blockIdx.y == 0u);
+    EST_ONE(SLOT + SK_WG, true);
+    EST_ONE(SLOT + SK_NOPAIR, b < 0);
     if (b < 0) // (uniform over the workgroup)
         return;
+#ifdef MCRAW_POISON_A
+    for (uint32_t i = threadIdx.x; i < sizeof(s_m) / 4u; i += AL_T)
+        s_m[i] = 0xFFFFFFFFu;
+    for (uint32_t i = threadIdx.x; i < sizeof(s_b) / 4u; i += AL_T)
+        s_b[i] = 0xFFFFFFFFu;
+    __syncthreads();
+#endif
     const uint32_t R = RT ? 1u : A.R, ncand = (2u * R + 1u) * (2u * R + 1u);
     const uint32_t cell = blockIdx.x / A.pieces, piece = blockIdx.x - cell * A.pieces;
     const uint32_t ci = cell / A.cells_x, cj = cell - ci * A.cells_x;
@@ -90,6 +131,7 @@ __global__ void __launch_bounds__(AL_T) kcells_sad(const ClSadArgs A)
     const size_t slot = static_cast<size_t>(t) * A.cells + cell;
     for (uint32_t i = threadIdx.x; i < ncand; i += AL_T)
         s_acc[i] = 0u;
+    EST_ONE(SLOT + SK_EMPTY, !(x0 < x1 && y0 < y1));
     if (x0 < x1 && y0 < y1) { // (uniform) the piece has pixels: the plane is not empty
         int cy, cx;
         if (A.top) {
@@ -104,16 +146,24 @@ __global__ void __launch_bounds__(AL_T) kcells_sad(const ClSadArgs A)
         // only what the piece's pixels read is staged: a cell at a coarse level is a fraction of a piece.  The lanes without pixels
         // read LDS that nobody wrote, and mask it.
         const uint32_t nyp = min(AL_TH, y1 - y0), nxp = min(AL_TW, x1 - x0);
-        cl_stage(s_b, LW, pb, A.pitch, static_cast<int>(A.h), static_cast<int>(A.w), static_cast<int>(y0), static_cast<int>(x0), nyp,
+        EST_ONE(SLOT + SK_OM0 + om, true);
+        cl_stage<SLOT>(s_b, LW, pb, A.pitch, static_cast<int>(A.h), static_cast<int>(A.w), static_cast<int>(y0), static_cast<int>(x0), nyp,
                  (nxp + 1u) / 2u);
-        cl_stage(s_m, LW, pm, A.pitch, static_cast<int>(A.h), static_cast<int>(A.w), ym, xm & ~1, nyp + 2u * R, (nxp + 2u * R) / 2u + 1u);
+        cl_stage<SLOT>(s_m, LW, pm, A.pitch, static_cast<int>(A.h), static_cast<int>(A.w), ym, xm & ~1, nyp + 2u * R, (nxp + 2u * R) / 2u + 1u);
         __syncthreads();
         const uint32_t lx = threadIdx.x % 32u, ly = threadIdx.x / 32u;
         const uint32_t px = x0 + 4u * lx, py4 = y0 + 4u * ly; // the lane's 4 x 4 pixels
         const uint32_t nx = px < x1 ? min(4u, x1 - px) : 0u, ny = py4 < y1 ? min(4u, y1 - py4) : 0u;
+        EST_PATH(SLOT + SK_LANE_EMPTY, nx == 0u || ny == 0u);
+        // a lane's reads against what was staged: s_b rows 4 ly .. 4 ly + 3, s_m rows .. 4 ly + 3 + 2 R; al_refine reads dwords
+        // 2 lx .. 2 lx + 2 of s_b and .. 2 lx + 3 of s_m, the loop the elements 4 lx .. 4 lx + 3 of s_b and .. 4 lx + 3 + 2 R + om of s_m
+        EST_PATH(SLOT + SK_UNSTAGED, 4u * ly + 3u >= nyp || (RT ? 2u * lx + 2u : 2u * lx + 1u) >= (nxp + 1u) / 2u ||
+                                         (RT ? 2u * lx + 3u : (4u * lx + 3u + 2u * R + om) / 2u) >= (nxp + 2u * R) / 2u + 1u);
         if (RT) {
             uint32_t acc[9];
-            if (__all(nx == 4u && ny == 4u)) // the cell's interior: no masks
+            EST_PATH(SLOT + SK_REF_FULL, __all(nx == 4u && ny == 4u) && !CL_SLOW && __lane_id() == 0u); // (every lane takes part in __all)
+            EST_PATH(SLOT + SK_REF_MASK, !(__all(nx == 4u && ny == 4u) && !CL_SLOW) && __lane_id() == 0u);
+            if (!CL_SLOW && __all(nx == 4u && ny == 4u)) // the cell's interior: no masks
                 al_refine<true>(s_b, s_m, LW / 2u, lx, ly, 0u, om, nx, ny, acc);
             else
                 al_refine<false>(s_b, s_m, LW / 2u, lx, ly, 0u, om, nx, ny, acc);
@@ -123,6 +173,8 @@ __global__ void __launch_bounds__(AL_T) kcells_sad(const ClSadArgs A)
 #pragma unroll
                 for (int d = 32; d >= 1; d >>= 1)
                     v += __shfl_xor(v, d);
+                EST_PATH(SLOT + SK_WAVE_ADD, __lane_id() == 0u && v != 0u);
+                EST_PATH(SLOT + SK_WAVE_SKIP, __lane_id() == 0u && v == 0u);
                 if (__lane_id() == 0u && v)
                     atomicAdd(&s_acc[c], v);
             }
@@ -150,6 +202,8 @@ __global__ void __launch_bounds__(AL_T) kcells_sad(const ClSadArgs A)
 #pragma unroll
                 for (int d = 32; d >= 1; d >>= 1)
                     v += __shfl_xor(v, d);
+                EST_PATH(SLOT + SK_WAVE_ADD, __lane_id() == 0u && v != 0u);
+                EST_PATH(SLOT + SK_WAVE_SKIP, __lane_id() == 0u && v == 0u);
                 if (__lane_id() == 0u && v)
                     atomicAdd(&s_acc[c], v);
             }
@@ -157,7 +211,14 @@ __global__ void __launch_bounds__(AL_T) kcells_sad(const ClSadArgs A)
     }
     __syncthreads();
     unsigned long long *acc = A.acc + slot * A.nacc + A.acc0;
-    if (A.pieces == 1u) { // the cell is this workgroup's alone: a cell without pixels stores its zeros
+#ifdef MCRAW_PATHSA
+    for (uint32_t i = threadIdx.x; i < ncand; i += AL_T) {
+        EST_PATH(SLOT + SK_STORE, A.pieces == 1u && !CL_SLOW);
+        EST_PATH(SLOT + SK_GLOB_ADD, !(A.pieces == 1u && !CL_SLOW) && s_acc[i] != 0u);
+        EST_PATH(SLOT + SK_GLOB_SKIP, !(A.pieces == 1u && !CL_SLOW) && s_acc[i] == 0u);
+    }
+#endif
+    if (A.pieces == 1u && !CL_SLOW) { // the cell is this workgroup's alone: a cell without pixels stores its zeros
         for (uint32_t i = threadIdx.x; i < ncand; i += AL_T)
             acc[i] = s_acc[i];
     } else {
@@ -169,6 +230,7 @@ __global__ void __launch_bounds__(AL_T) kcells_sad(const ClSadArgs A)
 
 __global__ void __launch_bounds__(AL_T) kcells_zero(unsigned long long *p, size_t words)
 {
+    EST_ONE(EP_CZ_LAUNCH, blockIdx.x == 0u);
     const size_t step = static_cast<size_t>(gridDim.x) * AL_T;
     for (size_t i = static_cast<size_t>(blockIdx.x) * AL_T + threadIdx.x; i < words; i += step)
         p[i] = 0ull;
@@ -181,6 +243,7 @@ __global__ void __launch_bounds__(AL_T) kcells_pick(const unsigned long long *ac
 {
     const uint32_t cell = blockIdx.x * AL_T + threadIdx.x;
     const int t = t0 + static_cast<int>(blockIdx.y), b = al_base(t, ref);
+    EST_PATH(EP_CP_NOPAIR, cell >= cells || b < 0);
     if (cell >= cells || b < 0)
         return;
     const size_t slot = static_cast<size_t>(t) * cells + cell;
@@ -211,6 +274,7 @@ __global__ void __launch_bounds__(AL_T) kcells_pick(const unsigned long long *ac
 __global__ void __launch_bounds__(AL_T) kcells_final(const CellWin *win, int16_t *pos, unsigned long long *sad, uint32_t cells, int n, int ref)
 {
     const uint32_t cell = blockIdx.x * AL_T + threadIdx.x;
+    EST_PATH(EP_CF_PAST, cell >= cells);
     if (cell >= cells)
         return;
     int sy = 0, sx = 0;
@@ -224,6 +288,9 @@ __global__ void __launch_bounds__(AL_T) kcells_final(const CellWin *win, int16_t
         }
         if (ref < 0)
             dy = sy += dy, dx = sx += dx;
+        EST_PATH(EP_CF_NOPAIR, !(n > 1 && al_base(t, ref) >= 0));
+        EST_PATH(EP_CF_CLAMP, dy < -32768 || dy > 32767);
+        EST_PATH(EP_CF_CLAMP, dx < -32768 || dx > 32767);
         pos[2u * slot] = static_cast<int16_t>(max(-32768, min(32767, dy)));
         pos[2u * slot + 1u] = static_cast<int16_t>(max(-32768, min(32767, dx)));
         if (sad)
@@ -232,6 +299,10 @@ __global__ void __launch_bounds__(AL_T) kcells_final(const CellWin *win, int16_t
 }
 
 } // namespace mcraw
+
+#ifdef MCRAW_PATHSA
+void est_paths_read_cells(uint64_t *out, int n, int reset) { mcraw::est_paths_read(out, n, reset); } // (mcraw_diag_est_paths: mcraw_align.hip)
+#endif
 
 using namespace mcraw;
 
@@ -256,7 +327,7 @@ static int mcraw_cells_launch(const mcraw_align_cells *a, const MosaicBatch &I, 
         for (uint32_t l = 0; l < P.levels; l++) {
             px[l] = ((P.G.cell_w >> (l + 1u)) + AL_TW - 1u) / AL_TW;
             pieces[l] = px[l] * (((P.G.cell_h >> (l + 1u)) + AL_TH - 1u) / AL_TH);
-            shared = shared || pieces[l] != 1u;
+            shared = shared || pieces[l] != 1u || CL_SLOW;
         }
         if (shared) {
             const size_t words = static_cast<size_t>(n) * cells * P.nacc;
@@ -281,9 +352,9 @@ static int mcraw_cells_launch(const mcraw_align_cells *a, const MosaicBatch &I, 
             S.cells_x = P.G.cells_x, S.cells = cells;
             S.px = px[l], S.pieces = pieces[l];
             S.ref = a->ref;
-            for (int f0 = 0; f0 < n; f0 += LAUNCH_FRAMES) {
+            for (int f0 = 0; f0 < n; f0 += LAUNCH_PIECE) {
                 S.t0 = f0;
-                const uint32_t nf = static_cast<uint32_t>(std::min(LAUNCH_FRAMES, n - f0));
+                const uint32_t nf = static_cast<uint32_t>(std::min<int>(LAUNCH_PIECE, n - f0));
                 const dim3 grid(cells * pieces[l], nf);
                 if (S.top) // (the coarsest level takes the loop whatever its radius: one instance per role)
                     hipLaunchKernelGGL(kcells_sad<0>, grid, dim3(AL_T), 0, st, S);

@@ -14,6 +14,10 @@
 // Test builds (build.MOSAIC_PATH_VARIANTS, tests/test_gpu_mosaic_paths.py; why each is valid: the head of mcraw_mosaic_paths.h):
 //   MCRAW_PATHSM      the path census, and the sweep of div_round at the end of this file
 //   MCRAW_POISON_M    s_t filled with 0xFFFF in front of staging
+//   MCRAW_STAGE_FRAMES=N  the launch loop takes N frames at a time (mcraw_mosaic_paths.h: `frames2`)
+#ifdef MCRAW_STAGE_FRAMES
+#define LAUNCH_PIECE MCRAW_STAGE_FRAMES
+#endif
 #include "mcraw_host.h"
 #ifdef MCRAW_PATHSM
 #include "mcraw_mosaic_paths.h"
@@ -381,8 +385,8 @@ extern "C" int mcraw_denoise_batch(mcraw_ctx *c, const mcraw_denoise *d, const u
     A.perframe = d->nluts != 1u ? 1u : 0u;
     A.invec = I.on_grid();
     A.outvec = O.on_grid();
-    for (int f0 = 0; f0 < n; f0 += LAUNCH_FRAMES) {
-        const int nf = std::min(LAUNCH_FRAMES, n - f0);
+    for (int f0 = 0; f0 < n; f0 += LAUNCH_PIECE) {
+        const int nf = std::min<int>(LAUNCH_PIECE, n - f0);
         A.in = in + static_cast<size_t>(f0) * in_frame_stride;
         A.out = out + static_cast<size_t>(f0) * out_frame_stride;
         A.lut = d->lut + (A.perframe ? static_cast<size_t>(f0) * 4u * A.L : 0u);

@@ -17,6 +17,10 @@
 //   MCRAW_PATHSM       the path census
 //   MCRAW_FORCE_SLOWM  `cand` is true for every lane
 //   MCRAW_POISON_M     s_t filled with 0xFFFF in front of staging
+//   MCRAW_STAGE_FRAMES=N  the launch loop takes N frames at a time (mcraw_mosaic_paths.h: `frames2`)
+#ifdef MCRAW_STAGE_FRAMES
+#define LAUNCH_PIECE MCRAW_STAGE_FRAMES
+#endif
 #include "mcraw_host.h"
 #ifdef MCRAW_PATHSM
 #include "mcraw_mosaic_paths.h"
@@ -387,8 +391,8 @@ extern "C" int mcraw_fixpix_batch(mcraw_ctx *c, const mcraw_fixpix *p, const uin
         hipLaunchKernelGGL(kfixpix_init, dim3(blocks), dim3(256), 0, st, p->counts, words);
         HIP_TRY(hipGetLastError());
     }
-    for (int f0 = 0; f0 < n; f0 += LAUNCH_FRAMES) {
-        const int nf = std::min(LAUNCH_FRAMES, n - f0);
+    for (int f0 = 0; f0 < n; f0 += LAUNCH_PIECE) {
+        const int nf = std::min<int>(LAUNCH_PIECE, n - f0);
         A.in = in + static_cast<size_t>(f0) * in_frame_stride;
         A.out = out + static_cast<size_t>(f0) * out_frame_stride;
         A.counts = p->counts ? p->counts + static_cast<size_t>(f0) * 8u : nullptr;

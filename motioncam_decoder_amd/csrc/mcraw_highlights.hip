@@ -17,6 +17,10 @@
 //   MCRAW_PATHSM       the path census
 //   MCRAW_FORCE_SLOWM  khl_apply's `clipped` is true for every lane
 //   MCRAW_POISON_M     s_t filled with 0xFFFF in front of staging
+//   MCRAW_STAGE_FRAMES=N  the launch loop takes N frames at a time (mcraw_mosaic_paths.h: `frames2`)
+#ifdef MCRAW_STAGE_FRAMES
+#define LAUNCH_PIECE MCRAW_STAGE_FRAMES
+#endif
 #include "mcraw_host.h"
 #include "mcraw_highlights_args.h"
 #ifdef MCRAW_PATHSM
@@ -407,8 +411,8 @@ extern "C" int mcraw_highlights_measure_batch(mcraw_ctx *c, const mcraw_highligh
         hipLaunchKernelGGL(khl_init, dim3(blocks), dim3(256), 0, st, static_cast<uint32_t *>(h->rec), words);
         HIP_TRY(hipGetLastError());
     }
-    for (int f0 = 0; f0 < n; f0 += LAUNCH_FRAMES) {
-        const int nf = std::min(LAUNCH_FRAMES, n - f0);
+    for (int f0 = 0; f0 < n; f0 += LAUNCH_PIECE) {
+        const int nf = std::min<int>(LAUNCH_PIECE, n - f0);
         A.in = in + static_cast<size_t>(f0) * in_frame_stride;
         A.rec = static_cast<char *>(h->rec) + (A.perframe ? static_cast<size_t>(f0) * HL_REC_BYTES : 0u);
         hipLaunchKernelGGL(khl_measure, dim3(A.tilesX * tilesY, static_cast<uint32_t>(nf)), dim3(HL_T), 0, st, A);
@@ -444,8 +448,8 @@ extern "C" int mcraw_highlights_batch(mcraw_ctx *c, const mcraw_highlights *h, c
     HlArgs A = hl_args(*h, I, &O);
     const bool clip = h->mode == MCRAW_HL_CLIP;
     const uint32_t tilesY = (A.H + (clip ? HL_CTH : HL_TH) - 1u) / (clip ? HL_CTH : HL_TH);
-    for (int f0 = 0; f0 < n; f0 += LAUNCH_FRAMES) {
-        const int nf = std::min(LAUNCH_FRAMES, n - f0);
+    for (int f0 = 0; f0 < n; f0 += LAUNCH_PIECE) {
+        const int nf = std::min<int>(LAUNCH_PIECE, n - f0);
         A.in = in + static_cast<size_t>(f0) * in_frame_stride;
         A.out = out + static_cast<size_t>(f0) * out_frame_stride;
         A.rec = h->nrec ? static_cast<char *>(h->rec) + (A.perframe ? static_cast<size_t>(f0) * HL_REC_BYTES : 0u) : nullptr;

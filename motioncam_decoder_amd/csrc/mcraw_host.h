@@ -281,6 +281,11 @@ namespace mcraw {
 // The stream a stage's launches go to: the caller's, or the context's own.
 inline hipStream_t stream_of(const mcraw_ctx *c, void *stream) { return stream ? static_cast<hipStream_t>(stream) : c->stream; }
 constexpr int LAUNCH_FRAMES = 65535; // frames per launch of a stage (grid.y)
+// The piece of a stage's launch loop: LAUNCH_FRAMES unless a source defined another one in front of this header (test builds:
+// the loops are written for any piece >= 1).
+#ifndef LAUNCH_PIECE
+#define LAUNCH_PIECE ::mcraw::LAUNCH_FRAMES
+#endif
 
 int ensure(Buf &b, size_t bytes, bool pinned);
 hipEvent_t get_event(mcraw_ctx *c);

@@ -35,6 +35,10 @@
 //               how much a lane's 32-bit sums collect (8192 * 4 * 65535 < 2^32: fewer tiles collect less, the static_assert
 //               allows 1 .. 8192); the host's floor of B / 64 tiles per workgroup is a cost heuristic that the cap may undercut:
 //               every tile is still taken once, by grid = ceil(tiles / tpc) workgroups.
+//   frames2     (build.MOSAIC_FRAMES2_FLAGS) the launch loops of kshade, kstats, kfixpix (+ kfixpix_list), kdenoise, khl_apply, khl_clip and khl_measure take 2
+//               frames per launch instead of up to 65535 (LAUNCH_PIECE of mcraw_host.h): launches of 2 + 1 for the corpus' 3
+//               frames.  The loops are written for any piece >= 1: every launch gets its first frame's input, output, record,
+//               counts, table and map; kstats makes tiles per workgroup from the launch's frame count.
 //   th16        the tile heights of 16 rows that kfixpix, kdenoise and kmerge already support
 //               (their static_asserts allow 16 and 32; the
 //               benchmarks build them): another split of the same rows into workgroups, lanes and passes.

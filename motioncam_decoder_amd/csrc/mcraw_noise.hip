@@ -14,6 +14,22 @@
 //
 // Test build (tests/test_gpu_noise.py):
 //   MCRAW_NOISE_MAXSTRIPS=N  at most N strips per workgroup: many workgroups flush into one record at small sizes
+// Test builds (tests/test_gpu_est_paths.py, build.EST_PATH_VARIANTS; why each is valid: the head of mcraw_est_paths.h):
+//   MCRAW_PATHSA             the path census (mcraw_diag_est_paths: mcraw_align.hip)
+//   MCRAW_EST_FRAMES=N       the launch loop takes N frames at a time, each launch with a plan for its own frame count
+#ifdef MCRAW_PATHSA
+#include "mcraw_est_paths.h"
+#define EST_LD_BASE ::mcraw::EP_NS_LD
+#endif
+#ifdef MCRAW_EST_FRAMES
+#define LAUNCH_PIECE MCRAW_EST_FRAMES
+#endif
+#ifndef EST_PATH
+#define EST_PATH(slot, cond)
+#endif
+#ifndef EST_ONE
+#define EST_ONE(slot, cond)
+#endif
 #include "mcraw_host.h"
 #include "mcraw_mosaic.h"
 #include "mcraw_noise_args.h"
@@ -78,6 +94,7 @@ __global__ void __launch_bounds__(NS_T) knoise(const NoiseArgs A)
     const uint32_t f = blockIdx.y, t0 = blockIdx.x * A.spw, t1 = min(t0 + A.spw, A.strips);
     const uint32_t half = threadIdx.x / NS_SL, lane = threadIdx.x % NS_SL;
     const uint16_t *fin = A.in + static_cast<size_t>(f) * A.ifstride + static_cast<size_t>(A.y0) * A.ipitch + A.x0;
+    EST_ONE(EP_NS_WG, true);
     for (uint32_t i = threadIdx.x; i < NS_HIST; i += NS_T)
         s_h[i] = 0u;
     __syncthreads();
@@ -86,8 +103,11 @@ __global__ void __launch_bounds__(NS_T) knoise(const NoiseArgs A)
     for (uint32_t i = 0; noise_strip(blockIdx.x, A.spw, i, 0u) < t1; i++) {
         const uint32_t t = noise_strip(blockIdx.x, A.spw, i, half);
         const NoiseLane L = noise_lane(A.bx, A.stripsX, t, lane);
+        EST_PATH(EP_NS_SKIP_T1, t >= t1);
+        EST_PATH(EP_NS_SKIP_INACTIVE, t < t1 && !L.active);
         if (t >= t1 || !L.active)
             continue;
+        EST_PATH(EP_NS_BLOCK, true);
         const uint16_t *src = fin + static_cast<size_t>(L.y) * A.ipitch + L.x;
         uint32_t w[8][8];
 #pragma unroll
@@ -110,6 +130,9 @@ __global__ void __launch_bounds__(NS_T) knoise(const NoiseArgs A)
 #pragma unroll
         for (uint32_t par = 0; par < 2u; par++) {
             const uint32_t pos = 2u * rp + par;
+            EST_PATH(EP_NS_REJ_SAT, half16(mx, par) >= A.sat[pos]);
+            EST_PATH(EP_NS_REJ_LO, half16(mx, par) < A.sat[pos] && half16(mn, par) < A.lo[pos]);
+            EST_PATH(EP_NS_ACCEPT, half16(mx, par) < A.sat[pos] && half16(mn, par) >= A.lo[pos]);
             if (half16(mx, par) >= A.sat[pos] || half16(mn, par) < A.lo[pos]) {
                 nrej[par]++;
             } else {
@@ -128,6 +151,8 @@ __global__ void __launch_bounds__(NS_T) knoise(const NoiseArgs A)
             nb += __shfl_xor(nb, d);
             nr += __shfl_xor(nr, d);
         }
+        EST_PATH(EP_NS_REG_FLUSH, __lane_id() == 0u && nb != 0u);
+        EST_PATH(EP_NS_REG_FLUSH, __lane_id() == 0u && nr != 0u);
         if (__lane_id() == 0u) {
             if (nb)
                 atomicAdd(rec + NS_HIST + 2u * rp + par, nb);
@@ -139,6 +164,7 @@ __global__ void __launch_bounds__(NS_T) knoise(const NoiseArgs A)
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < NS_HIST; i += NS_T) {
         const uint32_t c = s_h[i];
+        EST_PATH(EP_NS_HIST_FLUSH, c != 0u);
         if (c)
             atomicAdd(rec + i, c);
     }
@@ -153,6 +179,10 @@ __global__ void __launch_bounds__(256) knoise_init(uint32_t *out, size_t words)
 }
 
 } // namespace mcraw
+
+#ifdef MCRAW_PATHSA
+void est_paths_read_noise(uint64_t *out, int n, int reset) { mcraw::est_paths_read(out, n, reset); } // (mcraw_diag_est_paths: mcraw_align.hip)
+#endif
 
 using namespace mcraw;
 
@@ -201,8 +231,8 @@ extern "C" int mcraw_noise_batch(mcraw_ctx *c, const mcraw_noise *s, const uint1
         hipLaunchKernelGGL(knoise_init, dim3(blocks), dim3(256), 0, st, static_cast<uint32_t *>(out), words);
         HIP_TRY(hipGetLastError());
     }
-    for (int f0 = 0; f0 < n; f0 += LAUNCH_FRAMES) {
-        const int nf = std::min(LAUNCH_FRAMES, n - f0);
+    for (int f0 = 0; f0 < n; f0 += LAUNCH_PIECE) {
+        const int nf = std::min<int>(LAUNCH_PIECE, n - f0);
         const NoisePlan P = noise_plan(s->w, s->h, static_cast<uint32_t>(nf), NS_MAXSTRIPS);
         A.bx = P.bx, A.stripsX = P.stripsX, A.strips = P.strips, A.spw = P.spw;
         A.in = in + static_cast<size_t>(f0) * in_frame_stride;

@@ -10,6 +10,10 @@
 //
 // Test builds (build.MOSAIC_PATH_VARIANTS, tests/test_gpu_mosaic_paths.py; why each is valid: the head of mcraw_mosaic_paths.h):
 //   MCRAW_PATHSM  the path census; mcraw_diag_mosaic_paths below adds up the stage sources' counters
+//   MCRAW_STAGE_FRAMES=N  the launch loop takes N frames at a time (mcraw_mosaic_paths.h: `frames2`)
+#ifdef MCRAW_STAGE_FRAMES
+#define LAUNCH_PIECE MCRAW_STAGE_FRAMES
+#endif
 #include "mcraw_host.h"
 #ifdef MCRAW_PATHSM
 #include "mcraw_mosaic_paths.h"
@@ -212,8 +216,8 @@ extern "C" int mcraw_shade_batch(mcraw_ctx *c, const mcraw_shade *s, const uint1
     A.invec = I.on_grid();
     A.outvec = O.on_grid();
     const bool nt = inplace ? SH_NT_INPLACE : SH_NT_OUT;
-    for (int f0 = 0; f0 < n; f0 += LAUNCH_FRAMES) {
-        const int nf = std::min(LAUNCH_FRAMES, n - f0);
+    for (int f0 = 0; f0 < n; f0 += LAUNCH_PIECE) {
+        const int nf = std::min<int>(LAUNCH_PIECE, n - f0);
         A.in = in + static_cast<size_t>(f0) * in_frame_stride;
         A.out = out + static_cast<size_t>(f0) * out_frame_stride;
         A.f0 = static_cast<uint32_t>(f0);

@@ -15,6 +15,10 @@
 //   MCRAW_PATHSM            the path census
 //   MCRAW_FORCE_SLOWM       no wave takes stats_tile<BL, true>, and with it none the one-bin shortcut
 //   MCRAW_STATS_MAXTILES=N  at most N tiles per workgroup
+//   MCRAW_STAGE_FRAMES=N  the launch loop takes N frames at a time (mcraw_mosaic_paths.h: `frames2`)
+#ifdef MCRAW_STAGE_FRAMES
+#define LAUNCH_PIECE MCRAW_STAGE_FRAMES
+#endif
 #include "mcraw_host.h"
 #ifdef MCRAW_PATHSM
 #include "mcraw_mosaic_paths.h"
@@ -329,8 +333,8 @@ extern "C" int mcraw_stats_batch(mcraw_ctx *c, const mcraw_stats *s, const uint1
         hipLaunchKernelGGL(kstats_init, dim3(blocks), dim3(256), 0, st, static_cast<uint32_t *>(out), words, A.recwords, B);
         HIP_TRY(hipGetLastError());
     }
-    for (int f0 = 0; f0 < n; f0 += LAUNCH_FRAMES) {
-        const int nf = std::min(LAUNCH_FRAMES, n - f0);
+    for (int f0 = 0; f0 < n; f0 += LAUNCH_PIECE) {
+        const int nf = std::min<int>(LAUNCH_PIECE, n - f0);
         // a workgroup's merge costs a pass over its LDS histogram: at least B / 64 tiles each, and ST_WGS workgroups if that leaves enough
         const uint32_t want = std::max(1u, ST_WGS / static_cast<uint32_t>(nf));
         A.tpc = std::min(ST_MAXTILES, std::max(std::max(1u, B / 64u), (A.tiles + want - 1u) / want));

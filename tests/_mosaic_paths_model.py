@@ -33,7 +33,8 @@ PATHS = ["wg", "idle_lane", "row_break", "row_cont",
          "mg_short", "mg_launch", "mg_zero", "mg_cut", "mg_self", "mg_zerow", "mg_staged", "mg_m_aligned", "mg_m_sx", "mg_m_invec",
          "div_calls", "div_down", "div_up"]
 UNMODELLED = ("div_down", "div_up")
-VARIANTS = ("census", "slow", "poison", "poisonslow", "pieces", "th16")
+VARIANTS = ("census", "slow", "poison", "poisonslow", "pieces", "th16")  # build.MOSAIC_PATH_VARIANTS
+EXTRA_VARIANTS = ("frames2",)                                             # build.MOSAIC_FRAMES2_FLAGS
 FRAMES = 3
 MG_FRAMES = 7  # frames of a merge call
 MG_WINDOWS = ((0, 0), (2, 2), (5, 0))  # (before, after)
@@ -409,7 +410,7 @@ def tile_heights(variant):
 
 # ---------------------------------------------------------------------------------------------------------------- the model
 def model(name, variant="census"):
-    assert variant in VARIANTS
+    assert variant in VARIANTS + EXTRA_VARIANTS
     S = SETTINGS[name]
     c = dict.fromkeys(PATHS, 0)
     c["_unstaged"] = {}
@@ -459,8 +460,14 @@ def stats_plan(S, variant="census"):
     xa, ya = x0 & ~(7 if vec else 1), y0 & ~1
     tilesx = (x0 + w - xa + 255) // 256
     tiles = tilesx * ((y0 + h - ya + 15) // 16)
-    want = max(1, ST_WGS // FRAMES)
-    tpc = min(2 if variant == "pieces" else ST_MAXTILES, max(max(1, S["bins"] // 64), (tiles + want - 1) // want))
+    # the plan takes the launch's frame count: 3 in one launch, 2 and 1 in the `frames2` build.  It is the only place where that
+    # build's census could differ from `census`'s, and with the corpus' few tiles it does not: every launch gets the same tpc.
+    tpcs = set()
+    for nf in ((2, 1) if variant == "frames2" else (FRAMES,)):
+        want = max(1, ST_WGS // nf)
+        tpcs.add(min(2 if variant == "pieces" else ST_MAXTILES, max(max(1, S["bins"] // 64), (tiles + want - 1) // want)))
+    assert len(tpcs) == 1
+    tpc = tpcs.pop()
     return dict(vec=vec, xa=xa, ya=ya, tilesx=tilesx, tiles=tiles, tpc=tpc, wgs=(tiles + tpc - 1) // tpc)
 
 

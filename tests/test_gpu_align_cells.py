@@ -99,6 +99,18 @@ def test_local_motion_is_found(gpu_ctx):
         assert np.array_equal(pos.cpu().numpy()[:, :, [0, 3]].astype(np.int64), want[:, :, [0, 3]])
 
 
+def test_cell_sums_beyond_32_bits(gpu_ctx):
+    """One cell of 8 x 4 pieces whose candidates each sum to 256 * 512 * 65535 > 2^32: the 32 pieces' 64-bit atomics carry (a piece
+    alone adds 4096 * 65535 < 2^32).  The cell counterpart of test_gpu_align.py's test_sums_beyond_32_bits."""
+    H, W, cell = 512, 1024, (512, 1024)
+    imgs = np.stack([np.zeros((H, W), np.uint16), np.full((H, W), 65535, np.uint16)])
+    want = CR.align_cells(imgs, (0, 0, 0, 0), cell, 1, 1)
+    assert int(want[1][1, 0, 0]) == 256 * 512 * 65535 > 1 << 32 and not want[0].any()
+    got = gpu_ctx.align_cells(_dev16(imgs), black=(0, 0, 0, 0), cell=cell, levels=1, radius=1, sad=True)
+    torch.cuda.synchronize()
+    _check(got, want, True, "beyond 32 bits")
+
+
 # (W, H, pitch, frame slack, offset in samples): an odd base off the dword grid, the 16-byte path, an odd pitch
 VIEWS = ((600, 100, 613, 29, 1), (600, 100, 608, 8, 8), (601, 101, 601, 0, 3))
 

@@ -5,8 +5,8 @@ kshade, kstats, kfixpix + kfixpix_list, kdenoise<1|2>, kmerge<0|1> (global posit
 khl_clip sit in front of every demosaic call of
 a real pipeline.  Their own suites compare outputs bit for bit; nothing there shows which branch a test entered: the per-wave fast paths
 (`__any(cand)`, `clipped`, kstats' stats_tile<BL, true> and its one-bin shortcut), the three forms of load8 / store8 / the staging pieces, the chunks that staging leaves as "whatever LDS
-held" and that kfixpix then reads into `cand`, the distance-4 swaps of kdenoise<2> at frames of 5 .. 7 rows or columns.  Here six
-builds of the stage sources (build.MOSAIC_PATH_VARIANTS; why each is valid: the head of csrc/mcraw_mosaic_paths.h) run the corpus of
+held" and that kfixpix then reads into `cand`, the distance-4 swaps of kdenoise<2> at frames of 5 .. 7 rows or columns.  Here seven
+builds of the stage sources (build.MOSAIC_PATH_VARIANTS and build.MOSAIC_FRAMES2_FLAGS; why each is valid: the head of csrc/mcraw_mosaic_paths.h) run the corpus of
 tests/_mosaic_paths_model.py in a child process each (tests/_mosaic_paths_child.py): 12 sizes from 1 x 1 to 35 x 520, each as three
 views (on the 16-byte grid, a base 2 bytes off it, a pitch of W + 3) of input and output, contents that drive both sides of every
 data-dependent branch, 3 frames per call (7 for the merge: windows (0, 0), (2, 2), (5, 0), positions none, multiples of 8, even,
@@ -25,6 +25,8 @@ statements; this module compares the census of every call with the model, EVERY 
   pieces             kstats with at most 2 tiles per workgroup: more workgroups than the product's, prefetches in all of them;
                      kmerge with 3 outputs per launch: ceil(count / 3) > 1 launches in every call, windows across them
   th16               kfixpix, kdenoise and kmerge with tiles of 16 rows
+  frames2            the launch loops of every stage but kmerge with 2 frames per launch (2 + 1 for the 3 frames of a call): outputs
+                     as the statements, every counter as `census`'s
   sweep              div_round(n, den) == n / den for den 1 .. 6400, quotients 0 .. 65536, n = k * den + {-1, 0, 1, den / 2,
                      den - 1}: as many evaluations as the enumeration in Python counts, no mismatch, and both correction steps taken
 
@@ -37,6 +39,7 @@ build; start of the child with its imports, child, the 407 models; the numpy sta
 in 0.6 s, in front of `census`):
   census 0.85 / 3.09   slow 0.65 / 2.84   poison 0.65 / 3.26   poisonslow 0.65 / 3.14   pieces 0.67 / 2.95   th16 0.66 / 3.06
   sweep 0.05 / 2.59
+`frames2` (test_mosaic_paths_frames2) was added later: its whole test 5.78 s in a run of this module.
 CHILD_TIMEOUT is ten times the slowest whole test; it guards against a hang, not against performance.
 
 The sweep on that chip: 2 097 177 599 evaluations, no mismatch; the step down (q - 1) taken by 516 137 076 of them, the step up
@@ -130,7 +133,7 @@ def _child(variant, corpus_npz, tmp_path_factory):
 
 
 def _run_child(variant, npz, tmp_path_factory):
-    flags = B.MOSAIC_PATH_VARIANTS["census" if variant == "sweep" else variant]
+    flags = B.MOSAIC_FRAMES2_FLAGS if variant == "frames2" else B.MOSAIC_PATH_VARIANTS["census" if variant == "sweep" else variant]
     lib = str(tmp_path_factory.mktemp("lib_" + variant) / ("libmcraw_mosp_%s.so" % variant))
     B.build_variant(lib, flags)
     env = dict(os.environ, MCRAW_LIB_PATH=lib)
@@ -187,7 +190,7 @@ def check(variant, res):
         assert ranged > 0, "no lane row of the corpus reads unstaged LDS"
         assert total["div_down"] > 0 and total["div_up"] > 0, "a correction step of div_round never ran: %r" % (total,)
     else:
-        assert variant in ("th16", "pieces", "slow") or ranged == 0
+        assert variant in ("th16", "pieces", "slow", "frames2") or ranged == 0
     if variant == "pieces":  # more workgroups of kstats than the product's, each of two tiles at most; kmerge in launches of 3 outputs
         plain = _results.get("census")
         for name, row in res["census"].items():
@@ -199,6 +202,11 @@ def check(variant, res):
                 P, got = T.stats_plan(S, variant), dict(zip(T.PATHS, row))
                 assert P["tpc"] <= 2 and got["wg"] == T.FRAMES * P["wgs"] and got["wg"] + got["ss_prefetch"] == T.FRAMES * P["tiles"], name
         assert total["ss_prefetch"] > 0 and (not isinstance(plain, dict) or total["wg"] > sum(r[0] for r in plain["census"].values()))
+    if variant == "frames2" and isinstance(_results.get("census"), dict):
+        for name, row in res["census"].items():
+            free = T.model(name, "census")["_unstaged"]
+            for k, a, b in zip(T.PATHS, row, _results["census"]["census"][name]):
+                assert a == b or k in free or k in T.UNMODELLED, (variant, name, k, a, b)
     if variant in ("slow", "poisonslow"):
         assert total["mg_zerow"] == 0 and total["mg_staged"] > 0
         assert total["ss_full"] == 0 and total["ss_onebin"] == 0 and total["ss_partial"] > 0
@@ -210,6 +218,13 @@ def test_mosaic_paths(variant, corpus_npz, tmp_path_factory):
     import _mosaic_paths_model as T
     assert tuple(B.MOSAIC_PATH_VARIANTS) == T.VARIANTS
     check(variant, _child(variant, corpus_npz, tmp_path_factory))
+
+
+def test_mosaic_paths_frames2(corpus_npz, tmp_path_factory):
+    """build.MOSAIC_FRAMES2_FLAGS: the same check as every other variant's."""
+    import _mosaic_paths_model as T
+    assert T.EXTRA_VARIANTS == ("frames2",)
+    check("frames2", _child("frames2", corpus_npz, tmp_path_factory))
 
 
 def test_div_round_sweep(tmp_path_factory):

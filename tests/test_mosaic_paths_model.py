@@ -14,14 +14,14 @@ STAGED = {"fixpix": 2, "denoise": None, "hl_apply": 1, "hl_measure": 1}  # famil
 
 @pytest.fixture(scope="module")
 def models():
-    return {v: {name: T.model(name, v) for name in T.SETTINGS} for v in T.VARIANTS}
+    return {v: {name: T.model(name, v) for name in T.SETTINGS} for v in T.VARIANTS + T.EXTRA_VARIANTS}
 
 
 def _pieces(S):
     return T.FRAMES * S["H"] * ((S["W"] + 7) // 8)
 
 
-@pytest.mark.parametrize("variant", T.VARIANTS)
+@pytest.mark.parametrize("variant", T.VARIANTS + T.EXTRA_VARIANTS)
 def test_identities(models, variant):
     for name, S in T.SETTINGS.items():
         c, fam, H, W = models[variant][name], S["family"], S["H"], S["W"]
@@ -116,7 +116,7 @@ def test_identities(models, variant):
             assert not any(c[k] for k in T.PATHS if k.startswith("dn_")), name
         # the ranges: none where LDS is poisoned or the predicate is forced, and only on the predicates' own counters
         assert set(rng) <= {"fp_cand", "fp_wave_any", "fp_wave_none", "hl_clipped", "hl_unclipped"}, name
-        if variant not in ("census", "th16", "pieces"):
+        if variant not in ("census", "th16", "pieces", "frames2"):
             assert (not rng and c["_unstaged_rows"] == 0) or variant == "slow", name
         if variant in ("slow", "poisonslow"):
             assert not rng and c["fp_wave_none"] == 0 and c["hl_unclipped"] == 0, name
@@ -156,6 +156,13 @@ def test_variants_differ_where_they_should(models):
     assert models["census"][flat]["fp_cand"] == 0 < models["slow"][flat]["fp_cand"] == 3 * 35 * 65
 
 
+def test_frames2_counts_what_census_counts(models):
+    """Two frames a launch change no counter: no stage counts its launches, and kstats' plan gives every launch the same tiles per
+    workgroup (stats_plan asserts it)."""
+    for name in T.SETTINGS:
+        assert models["frames2"][name] == models["census"][name], name
+
+
 def test_views():
     grid = {n: T.on_grid(S) for n, S in T.SETTINGS.items()}
     assert not any(g for n, g in grid.items() if T.SETTINGS[n]["view"] != "grid")
@@ -173,7 +180,8 @@ def test_counters_and_switches_of_the_sources():
     assert [m.lower() for m in re.findall(r"MP_([A-Z0-9_]+)", enum)] == T.PATHS
     assert tuple(B.MOSAIC_PATH_VARIANTS) == T.VARIANTS and all(v in B.TEST_VARIANTS for v in B.MOSAIC_PATH_VARIANTS.values())
     stage = {"mcraw_shade.hip", "mcraw_stats.hip", "mcraw_fixpix.hip", "mcraw_denoise.hip", "mcraw_merge.hip", "mcraw_highlights.hip"}
-    names = {re.sub(r"^-D([A-Za-z0-9_]+).*$", r"\1", f) for flags in B.MOSAIC_PATH_VARIANTS.values() for f in flags}
+    assert T.EXTRA_VARIANTS == ("frames2",) and B.MOSAIC_FRAMES2_FLAGS in B.TEST_VARIANTS and B.MOSAIC_FRAMES2_FLAGS[0] == "-DMCRAW_PATHSM"
+    names = {re.sub(r"^-D([A-Za-z0-9_]+).*$", r"\1", f) for flags in list(B.MOSAIC_PATH_VARIANTS.values()) + [B.MOSAIC_FRAMES2_FLAGS] for f in flags}
     for n in sorted(names):
         for f in B.HIP_HEADERS + B.HIP_SOURCES:
             if re.search(r"\b%s\b" % n, open(os.path.join(B.CSRC, f)).read()):
