@@ -48,7 +48,7 @@ HIP_SOURCES = ("mcraw_abi.hip", "mcraw_submit.hip", "mcraw_tune.hip", "mcraw_dev
 HIP_HEADERS = ("mcraw_plan.h", "mcraw_dev.h", "mcraw_host.h", "mcraw_race.h", "mcraw_mosaic.h", "mcraw_mosaic_args.h",
                "mcraw_rgb_args.h", "mcraw_align_args.h", "mcraw_area_args.h", "mcraw_rgb_dev.h", "mcraw_rgb_launch.h",
                "mcraw_resample_args.h", "mcraw_rgb_paths.h", "mcraw_align_pyr.h", "mcraw_cells_args.h", "mcraw_warp_args.h", "mcraw_ha_args.h",
-               "mcraw_highlights_args.h", "mcraw_warp_dev.h", "mcraw_mesh_args.h", "mcraw_mosaic_paths.h", "mcraw_noise_args.h", "mcraw_est_paths.h")
+               "mcraw_highlights_args.h", "mcraw_warp_dev.h", "mcraw_mesh_args.h", "mcraw_mosaic_paths.h", "mcraw_noise_args.h", "mcraw_est_paths.h", "mcraw_census.h")
 HIP_FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc"]
 
 
@@ -242,9 +242,10 @@ def build_merge_alt():
 # The -D builds that tests/ links on the GPU box (tests/test_gpu_split.py, test_gpu_segw.py, test_gpu_lookback_fault.py,
 # test_gpu_k6_paths.py, test_gpu_k7_paths.py, test_gpu_enc7_paths.py, test_gpu_k7t_paths.py, test_gpu_rgb_paths.py,
 # test_gpu_mosaic_paths.py, test_gpu_noise.py, test_gpu_est_paths.py).
-TEST_VARIANTS = ((["-DMCRAW_FORCE_SEGW"], ["-DMCRAW_INJECT_MUTE7"], ["-DMCRAW_INJECT_LOST"]) + tuple(K6_PATH_VARIANTS.values())
-                 + tuple(K7_PATH_VARIANTS.values()) + tuple(ENC7_PATH_VARIANTS.values()) + tuple(K7T_PATH_VARIANTS.values()) + tuple(RGB_PATH_VARIANTS.values()) + tuple(MOSAIC_PATH_VARIANTS.values()) + (MERGE_ALT_FLAGS, NOISE_STRIP_FLAGS, MOSAIC_FRAMES2_FLAGS)
-                 + tuple(EST_PATH_VARIANTS.values()))
+PATH_VARIANTS = (K6_PATH_VARIANTS, K7_PATH_VARIANTS, ENC7_PATH_VARIANTS, K7T_PATH_VARIANTS, RGB_PATH_VARIANTS, MOSAIC_PATH_VARIANTS,
+                 EST_PATH_VARIANTS)
+TEST_VARIANTS = ((["-DMCRAW_FORCE_SEGW"], ["-DMCRAW_INJECT_MUTE7"], ["-DMCRAW_INJECT_LOST"], MERGE_ALT_FLAGS, NOISE_STRIP_FLAGS, MOSAIC_FRAMES2_FLAGS)
+                 + tuple(flags for table in PATH_VARIANTS for flags in table.values()))
 
 
 def prebuild_test_variants():

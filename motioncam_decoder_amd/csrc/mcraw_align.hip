@@ -21,7 +21,7 @@
 // estimate, mcraw_cells.hip, through mcraw_align_pyr.h.
 //
 // Test builds (tests/test_gpu_est_paths.py, build.EST_PATH_VARIANTS; why each is valid: the head of mcraw_est_paths.h):
-//   MCRAW_PATHSA        the path census; mcraw_diag_est_paths below adds up the three estimator sources' counters
+//   MCRAW_PATHSA        the path census; mcraw_diag_est_paths below adds up the sources that include mcraw_est_paths.h
 //   MCRAW_EST_FRAMES=N  the launch loops take N frames at a time
 //   MCRAW_FORCE_SLOWA   every wave of kalign_sad<1> takes al_refine<false>
 //   MCRAW_POISON_A      s_m and s_b of kalign_sad hold 0xFFFF samples in front of staging
@@ -413,23 +413,12 @@ extern "C" size_t mcraw_align_work_bytes(int width, int height, int n, uint32_t 
     return P.total;
 }
 
-#ifdef MCRAW_PATHSA
-void est_paths_read_cells(uint64_t *out, int n, int reset); // mcraw_cells.hip
-void est_paths_read_noise(uint64_t *out, int n, int reset); // mcraw_noise.hip
-#endif
-
-// The census of the three estimator sources added up into out[0 .. n), and started over when `reset`; returns the number of
+// The census of the estimator sources that include mcraw_est_paths.h added up into out[0 .. n), and started over when `reset`; returns the number of
 // counters, 0 in a build without the census (mcraw_est_paths.h).
 extern "C" int mcraw_diag_est_paths(uint64_t *out, int n, int reset)
 {
 #ifdef MCRAW_PATHSA
-    uint64_t none[1];
-    for (int i = 0; out && i < n; i++)
-        out[i] = 0u;
-    est_paths_read(out ? out : none, out ? n : 0, reset);
-    est_paths_read_cells(out ? out : none, out ? n : 0, reset);
-    est_paths_read_noise(out ? out : none, out ? n : 0, reset);
-    return static_cast<int>(EP_N);
+    return census_sum<EstPath, EP_N>(out, n, reset);
 #else
     (void)out, (void)n, (void)reset;
     return 0;

@@ -300,10 +300,6 @@ __global__ void __launch_bounds__(AL_T) kcells_final(const CellWin *win, int16_t
 
 } // namespace mcraw
 
-#ifdef MCRAW_PATHSA
-void est_paths_read_cells(uint64_t *out, int n, int reset) { mcraw::est_paths_read(out, n, reset); } // (mcraw_diag_est_paths: mcraw_align.hip)
-#endif
-
 using namespace mcraw;
 
 extern "C" size_t mcraw_align_cells_work_bytes(int width, int height, int n, uint32_t levels, uint32_t radius, uint32_t cell_h, uint32_t cell_w)

@@ -269,8 +269,6 @@ static void denoise_launch(const DnArgs &A, uint32_t tilesY, uint32_t nf, hipStr
 }
 
 #ifdef MCRAW_PATHSM
-void mos_paths_read_denoise(uint64_t *out, int n, int reset) { mos_paths_read(out, n, reset); } // (mcraw_diag_mosaic_paths: mcraw_shade.hip)
-
 // The sweep of div_round over the edges of its proven domain: workgroup b takes den = b + 1, its threads the quotients k =
 // 0 .. 65536, each with n = k * den + {-1, 0, 1, den / 2, den - 1}; an n below 0 or from 2^30 on, or one whose quotient exceeds
 // 65536, is passed over.  The device's own integer division is the reference.
@@ -317,8 +315,7 @@ extern "C" int mcraw_diag_div_sweep(uint64_t *out)
 {
     if (!out)
         return -1;
-    uint64_t none[MP_N] = {};
-    mos_paths_read(none, 0, 1);
+    mos_paths_read(nullptr, 0, 1);
     DivSweep *R = nullptr, h{};
     if (hipMalloc(&R, sizeof(DivSweep)) != hipSuccess || hipMemset(R, 0, sizeof(DivSweep)) != hipSuccess)
         return -1;

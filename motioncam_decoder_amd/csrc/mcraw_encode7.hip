@@ -12,6 +12,9 @@
 //                and the frame's byte count.
 #include "mcraw_dev.h"
 #include "mcraw_host.h"
+#ifdef MCRAW_PATHSE
+#include "mcraw_census.h"
+#endif
 
 namespace mcraw {
 
@@ -918,20 +921,7 @@ using namespace mcraw;
 
 #ifdef MCRAW_PATHSE
 // The census, in the order of PathE (up to n counters; returns how many there are); `reset`: and start it over.
-extern "C" int mcraw_diag_k7e_paths(uint64_t *out, int n, int reset)
-{
-    (void)hipDeviceSynchronize();
-    n = n < 0 ? 0 : n < static_cast<int>(PE_N) ? n : static_cast<int>(PE_N);
-    if (out && n)
-        (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_k7e_paths), sizeof(uint64_t) * static_cast<size_t>(n));
-    if (reset) {
-        void *p = nullptr;
-        (void)hipGetSymbolAddress(&p, HIP_SYMBOL(g_k7e_paths));
-        (void)hipMemset(p, 0, sizeof(g_k7e_paths));
-        (void)hipDeviceSynchronize(); // (the contexts' streams do not wait for the null stream)
-    }
-    return static_cast<int>(PE_N);
-}
+extern "C" int mcraw_diag_k7e_paths(uint64_t *out, int n, int reset) { return census_read<PE_N>(g_k7e_paths, out, n, reset); }
 #endif
 
 extern "C" {

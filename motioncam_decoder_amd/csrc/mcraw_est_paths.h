@@ -3,12 +3,11 @@
 // (csrc/mcraw_noise.hip), for test builds only (tests/test_gpu_est_paths.py, build.EST_PATH_VARIANTS).  A source that wants the
 // census includes this header IN FRONT of its other headers, under a -D switch that only those three sources mention: the hooks
 // (EST_PATH, EST_ADDN, EST_ONE of mcraw_align_pyr.h and mcraw_noise.hip; MOS_PATH of mcraw_mosaic.h, through which load8 counts its
-// three forms) are empty unless defined, and this header names no switch, so a variant compiles the three sources alone.  The
-// library is linked without relocatable device code: every source has a counter array of its own (g_est_paths, internal
-// linkage), and est_paths_read of each adds its counters to the caller's (mcraw_diag_est_paths, mcraw_align.hip).
+// three forms) are empty unless defined, and this header names no switch, so a variant compiles the three sources alone.
+// Including it is joining the family: mcraw_diag_est_paths (mcraw_align.hip) adds up the sources that did (mcraw_census.h, which
+// also has the ways to count; EST_ADDN, rows a lane leaves: an atomic per lane).
 //
-// A count is taken per wave: a ballot, and the first active lane adds the number of lanes (EST_ADDN, rows a lane leaves: an
-// atomic per lane).  Every counter is fixed by geometry, by the alignment of the caller's buffers, by the parameters and by the
+// Every counter is fixed by geometry, by the alignment of the caller's buffers, by the parameters and by the
 // samples -- none depends on LDS that nobody staged, every such read is masked --: tests/_est_paths_model.py predicts each exactly.
 //
 // The builds (build.EST_PATH_VARIANTS; the -D names are spelled out there and in the sources), and why each is valid for every
@@ -30,8 +29,7 @@
 //   strips1     knoise with at most one strip per workgroup (the static_assert allows any limit >= 1): as many workgroups as
 //               strips flush into a frame's record, and half of every workgroup idles.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "mcraw_census.h"
 
 namespace mcraw {
 
@@ -83,35 +81,14 @@ enum EstLd { MP_LD_VEC, MP_LD_UNAL, MP_LD_ELEM, MP_ST_VEC, MP_ST_UNAL, MP_ST_ELE
 static __device__ unsigned long long g_est_paths[EP_N];
 
 // the active lanes for which `cond` holds (all active lanes of the wave call this together)
-__device__ __forceinline__ void est_add(uint32_t index, bool cond)
-{
-    const unsigned long long m = __ballot(cond), act = __ballot(true);
-    if (m != 0ull && (threadIdx.x & 63u) == static_cast<uint32_t>(__builtin_ctzll(act)))
-        atomicAdd(&g_est_paths[index], static_cast<unsigned long long>(__popcll(m)));
-}
+__device__ __forceinline__ void est_add(uint32_t index, bool cond) { census_count(&g_est_paths[index], cond); }
 
 // n for every lane for which `cond` holds
-__device__ __forceinline__ void est_addn(uint32_t index, bool cond, uint32_t n)
-{
-    if (cond && n)
-        atomicAdd(&g_est_paths[index], static_cast<unsigned long long>(n));
-}
+__device__ __forceinline__ void est_addn(uint32_t index, bool cond, uint32_t n) { census_addn(&g_est_paths[index], cond, n); }
 
-// This source's counters added to out[0 .. n) (n <= EP_N); `reset`: and start them over.  Defined once per source (internal).
-static void est_paths_read(uint64_t *out, int n, int reset)
-{
-    uint64_t h[EP_N];
-    (void)hipDeviceSynchronize();
-    (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_est_paths), sizeof(h));
-    for (int i = 0; i < n && i < static_cast<int>(EP_N); i++)
-        out[i] += h[i];
-    if (reset) {
-        void *p = nullptr;
-        (void)hipGetSymbolAddress(&p, HIP_SYMBOL(g_est_paths));
-        (void)hipMemset(p, 0, sizeof(g_est_paths));
-        (void)hipDeviceSynchronize(); // (the contexts' streams do not wait for the null stream)
-    }
-}
+// This source's counters added to out[0 .. n); `reset`: and start them over.  Defined, and joined, once per source (internal).
+static void est_paths_read(uint64_t *out, int n, int reset) { census_read<EP_N>(g_est_paths, out, n, reset, true); }
+static CensusJoin<EstPath> est_paths_join(est_paths_read);
 
 } // namespace mcraw
 

@@ -317,10 +317,6 @@ __global__ void __launch_bounds__(256) kfixpix_list(const FixArgs A)
             static_cast<uint16_t>(val);
 }
 
-#ifdef MCRAW_PATHSM
-void mos_paths_read_fixpix(uint64_t *out, int n, int reset) { mos_paths_read(out, n, reset); } // (mcraw_diag_mosaic_paths: mcraw_shade.hip)
-#endif
-
 } // namespace mcraw
 
 using namespace mcraw;

@@ -375,10 +375,6 @@ static HlArgs hl_args(const mcraw_highlights &h, const MosaicBatch &I, const Mos
     return A;
 }
 
-#ifdef MCRAW_PATHSM
-void mos_paths_read_highlights(uint64_t *out, int n, int reset) { mos_paths_read(out, n, reset); } // (mcraw_diag_mosaic_paths: mcraw_shade.hip)
-#endif
-
 } // namespace mcraw
 
 using namespace mcraw;

@@ -318,10 +318,6 @@ __global__ void __launch_bounds__(MG_T) kmerge(const ARGS A)
     }
 }
 
-#ifdef MCRAW_PATHSM
-void mos_paths_read_merge(uint64_t *out, int n, int reset) { mos_paths_read(out, n, reset); } // (mcraw_diag_mosaic_paths: mcraw_shade.hip)
-#endif
-
 static void merge_launch(const MgCellArgs &A, uint32_t support, hipStream_t st)
 {
     const dim3 grid(A.per * MG_XCDS), block(MG_T);

@@ -4,12 +4,11 @@
 // for test builds only (tests/test_gpu_mosaic_paths.py, build.MOSAIC_PATH_VARIANTS).  A source that wants the census includes this
 // header IN FRONT of mcraw_mosaic.h, under a -D switch that only the stage sources mention: the hooks of mcraw_mosaic.h (MOS_PATH,
 // MOS_WAVE, MOS_STAGE, MOS_DIV) are empty unless defined, as RGB_PATH is in mcraw_rgb_dev.h, and this header names no switch, so a
-// variant compiles the stage sources alone.  The library is linked without relocatable device code: every source has a counter
-// array of its own (g_mos_paths, internal linkage), and mos_paths_read of each adds its counters to the caller's.
+// variant compiles the stage sources alone.  Including it is joining the family: mcraw_diag_mosaic_paths (mcraw_shade.hip) adds
+// up the sources that did (mcraw_census.h, which also has the ways to count).
 //
-// A count is taken per wave: a ballot, and the first active lane adds the number of lanes.  Every counter but the two correction
-// steps of div_round is fixed by geometry, by the alignment of the caller's buffers, by the parameters and by the samples:
-// tests/_mosaic_paths_model.py predicts each one exactly.
+// Every counter but the two correction steps of div_round is fixed by geometry, by the alignment of the caller's buffers, by the
+// parameters and by the samples: tests/_mosaic_paths_model.py predicts each one exactly.
 //
 // The builds (build.MOSAIC_PATH_VARIANTS; the -D names are spelled out there and in the sources), and why each is valid for every
 // input:
@@ -43,8 +42,7 @@
 //               (their static_asserts allow 16 and 32; the
 //               benchmarks build them): another split of the same rows into workgroups, lanes and passes.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "mcraw_census.h"
 
 namespace mcraw {
 
@@ -91,63 +89,41 @@ enum MosPath {
 constexpr uint32_t MOS_STRIPES = 64u;
 static __device__ unsigned long long g_mos_paths[MP_N + 3u * (MOS_STRIPES - 1u)];
 
-__device__ __forceinline__ void mos_add(uint32_t index, bool cond)
-{
-    const unsigned long long m = __ballot(cond), act = __ballot(true);
-    if (m != 0ull && (threadIdx.x & 63u) == static_cast<uint32_t>(__builtin_ctzll(act)))
-        atomicAdd(&g_mos_paths[index], static_cast<unsigned long long>(__popcll(m)));
-}
-
 // the active lanes for which `cond` holds (all active lanes of the wave call this together)
-__device__ __forceinline__ void mos_path(uint32_t slot, bool cond)
-{
-    mos_add(slot, cond);
-}
+__device__ __forceinline__ void mos_path(uint32_t slot, bool cond) { census_count(&g_mos_paths[slot], cond); }
 
 // one for the wave when `cond` (uniform over the active lanes) holds
-__device__ __forceinline__ void mos_wave(uint32_t slot, bool cond)
-{
-    const unsigned long long act = __ballot(true);
-    if (cond && (threadIdx.x & 63u) == static_cast<uint32_t>(__builtin_ctzll(act)))
-        atomicAdd(&g_mos_paths[slot], 1ull);
-}
+__device__ __forceinline__ void mos_wave(uint32_t slot, bool cond) { census_wave(&g_mos_paths[slot], cond); }
 
 // a staged chunk: `inner`: not the first or last chunk of the LDS row; `whole`: all 8 columns inside the row
 __device__ __forceinline__ void mos_stage(bool inner, bool whole, bool vec)
 {
-    mos_add(MP_STG_VEC, inner && whole && vec);
-    mos_add(MP_STG_UNAL, inner && whole && !vec);
-    mos_add(MP_STG_HALO, !inner);
-    mos_add(MP_STG_CROP, inner && !whole);
+    mos_path(MP_STG_VEC, inner && whole && vec);
+    mos_path(MP_STG_UNAL, inner && whole && !vec);
+    mos_path(MP_STG_HALO, !inner);
+    mos_path(MP_STG_CROP, inner && !whole);
 }
 
 __device__ __forceinline__ void mos_div(int32_t r, uint32_t den)
 {
     const uint32_t s = blockIdx.x & (MOS_STRIPES - 1u);
     const uint32_t base = s ? MP_N + 3u * (s - 1u) : MP_DIV_CALLS; // calls, down, up
-    mos_add(base, true);
-    mos_add(base + 1u, r < 0);
-    mos_add(base + 2u, r >= static_cast<int32_t>(den));
+    mos_path(base, true);
+    mos_path(base + 1u, r < 0);
+    mos_path(base + 2u, r >= static_cast<int32_t>(den));
 }
 
-// This source's counters added to out[0 .. n) (n <= MP_N); `reset`: and start them over.  Defined once per source (internal).
-static void mos_paths_read(uint64_t *out, int n, int reset)
+// (div_round's stripes into MP_DIV_CALLS, MP_DIV_DOWN and MP_DIV_UP)
+static void mos_fold_stripes(uint64_t *h)
 {
-    uint64_t h[MP_N + 3u * (MOS_STRIPES - 1u)];
-    (void)hipDeviceSynchronize();
-    (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_mos_paths), sizeof(h));
     for (uint32_t s = 1; s < MOS_STRIPES; s++)
         for (uint32_t i = 0; i < 3u; i++)
             h[MP_DIV_CALLS + i] += h[MP_N + 3u * (s - 1u) + i];
-    for (int i = 0; i < n; i++)
-        out[i] += h[i];
-    if (reset) {
-        void *p = nullptr;
-        (void)hipGetSymbolAddress(&p, HIP_SYMBOL(g_mos_paths));
-        (void)hipMemset(p, 0, sizeof(g_mos_paths));
-        (void)hipDeviceSynchronize(); // (the contexts' streams do not wait for the null stream)
-    }
 }
+
+// This source's counters added to out[0 .. n); `reset`: and start them over.  Defined, and joined, once per source (internal).
+static void mos_paths_read(uint64_t *out, int n, int reset) { census_read<MP_N>(g_mos_paths, out, n, reset, true, mos_fold_stripes); }
+static CensusJoin<MosPath> mos_paths_join(mos_paths_read);
 
 } // namespace mcraw
 

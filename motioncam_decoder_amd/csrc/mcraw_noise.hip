@@ -180,10 +180,6 @@ __global__ void __launch_bounds__(256) knoise_init(uint32_t *out, size_t words)
 
 } // namespace mcraw
 
-#ifdef MCRAW_PATHSA
-void est_paths_read_noise(uint64_t *out, int n, int reset) { mcraw::est_paths_read(out, n, reset); } // (mcraw_diag_est_paths: mcraw_align.hip)
-#endif
-
 using namespace mcraw;
 
 extern "C" size_t mcraw_noise_record_bytes(void) { return NS_REC_BYTES; }

@@ -290,10 +290,6 @@ static int resample_launch(mcraw_ctx *c, const mcraw_rgb *p, const mcraw_resampl
     return rgb_launch(c, rgb_pick<ResK>(P.rgb), A, P.rgb, rgb_cols(p, colors, ncolors, 0.0625f), in, n, out, -1, st, G);
 }
 
-#ifdef MCRAW_PATHSR
-void rgb_paths_read_resample(uint64_t *out, int n, int reset) { rgb_paths_read(out, n, reset); } // (mcraw_diag_rgb_paths: mcraw_rgb.hip)
-#endif
-
 } // namespace mcraw
 
 using namespace mcraw;

@@ -23,7 +23,7 @@
 // Test builds of the demosaic kernels (tests/test_gpu_rgb_paths.py, build.RGB_PATH_VARIANTS; none of this is in the product
 // library).  The three switches are read by this file, mcraw_area.hip and mcraw_resample.hip alone; the shared headers only have
 // hooks that are empty unless defined in front of them.  Each switch chooses among ways that are right for EVERY input:
-//   MCRAW_PATHSR            the path census (mcraw_rgb_paths.h; mcraw_diag_rgb_paths below adds up the three sources' counters).
+//   MCRAW_PATHSR            the path census (mcraw_rgb_paths.h; mcraw_diag_rgb_paths below adds up the sources that include it).
 //   MCRAW_RGB_GRID_CAP=N    a persistent launch uses min(units x frames, N) workgroups, not min(units x frames, resident): the
 //                           loop's condition makes any grid of 1 .. units x frames workgroups walk every unit exactly once.  The
 //                           float kinds have no loop and are untouched.
@@ -344,12 +344,6 @@ static int demosaic_launch(const char *fn, mcraw_ctx *c, const mcraw_rgb *p, con
 // RGB_GRID_LIMIT, so that a build with a capped grid caps that unit's grid as well.
 uint32_t rgb_grid_limit(uint32_t resident) { return RGB_GRID_LIMIT(resident); }
 
-#ifdef MCRAW_PATHSR
-void rgb_paths_read_rgb(uint64_t *out, int n, int reset) { rgb_paths_read(out, n, reset); }
-void rgb_paths_read_area(uint64_t *out, int n, int reset);     // mcraw_area.hip
-void rgb_paths_read_resample(uint64_t *out, int n, int reset); // mcraw_resample.hip
-#endif
-
 } // namespace mcraw
 
 using namespace mcraw;
@@ -359,19 +353,7 @@ extern "C" {
 #ifdef MCRAW_PATHSR
 // The census of the demosaic kernels, in the order of RgbPath, summed over the three sources (up to n counters; returns how many
 // there are); `reset`: and start it over.
-int mcraw_diag_rgb_paths(uint64_t *out, int n, int reset)
-{
-    n = n < 0 ? 0 : n < static_cast<int>(RP_N) ? n : static_cast<int>(RP_N);
-    for (int i = 0; out && i < n; i++)
-        out[i] = 0u;
-    if (out || reset) {
-        uint64_t none[RP_N];
-        rgb_paths_read_rgb(out ? out : none, out ? n : 0, reset);
-        rgb_paths_read_area(out ? out : none, out ? n : 0, reset);
-        rgb_paths_read_resample(out ? out : none, out ? n : 0, reset);
-    }
-    return static_cast<int>(RP_N);
-}
+int mcraw_diag_rgb_paths(uint64_t *out, int n, int reset) { return census_sum<RgbPath, RP_N>(out, n, reset); }
 #endif
 
 int mcraw_demosaic_batch(mcraw_ctx *c, const mcraw_rgb *p, const mcraw_rgb_color *colors, int ncolors, const uint16_t *in,

@@ -3,14 +3,12 @@
 // build.RGB_PATH_VARIANTS).  A source that wants the census includes this header IN FRONT of mcraw_rgb_dev.h and mcraw_rgb_launch.h,
 // under a -D switch of its own: the hooks of those headers (RGB_PATH, RGB_PATH_YUV, RGB_WALK, RGB_WALK_DECL) are empty unless
 // defined, as MCRAW_STORE_PATH is in mcraw_dev.h, and this header names no switch, so a variant compiles the three sources alone.
-// The library is linked without relocatable device code: every source has a counter array of its own (g_rgb_paths, internal
-// linkage), and rgb_paths_read of each adds its counters to the caller's.
+// Including it is joining the family: mcraw_diag_rgb_paths (mcraw_rgb.hip) adds up the sources that did (mcraw_census.h).
 //
 // Every counter is fixed by geometry, by the alignment of the caller's buffers and by the grid size: tests/_rgb_paths_model.py
 // predicts each one exactly.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "mcraw_census.h"
 
 namespace mcraw {
 
@@ -47,12 +45,7 @@ enum RgbPath {
 static __device__ unsigned long long g_rgb_paths[RP_N];
 
 // the active lanes for which `cond` holds (all active lanes of the wave call this together)
-__device__ __forceinline__ void rgb_path(uint32_t slot, bool cond)
-{
-    const unsigned long long m = __ballot(cond), act = __ballot(true);
-    if (m != 0ull && (threadIdx.x & 63u) == static_cast<uint32_t>(__builtin_ctzll(act)))
-        atomicAdd(&g_rgb_paths[slot], static_cast<unsigned long long>(__popcll(m)));
-}
+__device__ __forceinline__ void rgb_path(uint32_t slot, bool cond) { census_count(&g_rgb_paths[slot], cond); }
 
 // 8 samples of a YUV row at dst: slot (whole, on the grid of 8 es bytes), slot + 1 (n < 8), slot + 2 (whole, off the grid)
 __device__ __forceinline__ void rgb_path_yuv(uint32_t slot, const void *dst, uint32_t n, uint32_t es)
@@ -82,21 +75,9 @@ __device__ __forceinline__ void rgb_walk(uint32_t family, uint32_t f, bool lut, 
     prev = f;
 }
 
-// This source's counters added to out[0 .. n) (n <= RP_N); `reset`: and start them over.  Defined once per source (internal).
-static void rgb_paths_read(uint64_t *out, int n, int reset)
-{
-    uint64_t h[RP_N];
-    (void)hipDeviceSynchronize();
-    (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_rgb_paths), sizeof(h));
-    for (int i = 0; i < n; i++)
-        out[i] += h[i];
-    if (reset) {
-        void *p = nullptr;
-        (void)hipGetSymbolAddress(&p, HIP_SYMBOL(g_rgb_paths));
-        (void)hipMemset(p, 0, sizeof(g_rgb_paths));
-        (void)hipDeviceSynchronize(); // (the contexts' streams do not wait for the null stream)
-    }
-}
+// This source's counters added to out[0 .. n); `reset`: and start them over.  Defined, and joined, once per source (internal).
+static void rgb_paths_read(uint64_t *out, int n, int reset) { census_read<RP_N>(g_rgb_paths, out, n, reset, true); }
+static CensusJoin<RgbPath> rgb_paths_join(rgb_paths_read);
 
 } // namespace mcraw
 

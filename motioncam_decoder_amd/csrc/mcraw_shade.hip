@@ -9,7 +9,7 @@
 // Every pixel reads only itself, so out == in (in place) is fine.
 //
 // Test builds (build.MOSAIC_PATH_VARIANTS, tests/test_gpu_mosaic_paths.py; why each is valid: the head of mcraw_mosaic_paths.h):
-//   MCRAW_PATHSM  the path census; mcraw_diag_mosaic_paths below adds up the stage sources' counters
+//   MCRAW_PATHSM  the path census; mcraw_diag_mosaic_paths below adds up the sources that include mcraw_mosaic_paths.h
 //   MCRAW_STAGE_FRAMES=N  the launch loop takes N frames at a time (mcraw_mosaic_paths.h: `frames2`)
 #ifdef MCRAW_STAGE_FRAMES
 #define LAUNCH_PIECE MCRAW_STAGE_FRAMES
@@ -131,14 +131,6 @@ __global__ void __launch_bounds__(SH_T) kshade(const ShadeArgs A)
     }
 }
 
-#ifdef MCRAW_PATHSM
-void mos_paths_read_fixpix(uint64_t *out, int n, int reset);     // mcraw_fixpix.hip
-void mos_paths_read_denoise(uint64_t *out, int n, int reset);    // mcraw_denoise.hip
-void mos_paths_read_highlights(uint64_t *out, int n, int reset); // mcraw_highlights.hip
-void mos_paths_read_stats(uint64_t *out, int n, int reset);      // mcraw_stats.hip
-void mos_paths_read_merge(uint64_t *out, int n, int reset);      // mcraw_merge.hip
-#endif
-
 } // namespace mcraw
 
 using namespace mcraw;
@@ -146,22 +138,7 @@ using namespace mcraw;
 #ifdef MCRAW_PATHSM
 // The census of the mosaic stages, in the order of MosPath, summed over the sources that have one (up to n counters; returns how
 // many there are); `reset`: and start it over.
-extern "C" int mcraw_diag_mosaic_paths(uint64_t *out, int n, int reset)
-{
-    n = n < 0 ? 0 : n < static_cast<int>(MP_N) ? n : static_cast<int>(MP_N);
-    for (int i = 0; out && i < n; i++)
-        out[i] = 0u;
-    if (out || reset) {
-        uint64_t none[MP_N];
-        mos_paths_read(out ? out : none, out ? n : 0, reset);
-        mos_paths_read_fixpix(out ? out : none, out ? n : 0, reset);
-        mos_paths_read_denoise(out ? out : none, out ? n : 0, reset);
-        mos_paths_read_highlights(out ? out : none, out ? n : 0, reset);
-        mos_paths_read_stats(out ? out : none, out ? n : 0, reset);
-        mos_paths_read_merge(out ? out : none, out ? n : 0, reset);
-    }
-    return static_cast<int>(MP_N);
-}
+extern "C" int mcraw_diag_mosaic_paths(uint64_t *out, int n, int reset) { return census_sum<MosPath, MP_N>(out, n, reset); }
 #endif
 
 extern "C" int mcraw_shade_batch(mcraw_ctx *c, const mcraw_shade *s, const uint16_t *in, size_t in_pitch, size_t in_frame_stride,

@@ -260,10 +260,6 @@ static uint32_t stats_parity(uint32_t lo, uint32_t hi, uint32_t par)
     return ((hi + 1u - par) >> 1) - ((lo + 1u - par) >> 1);
 }
 
-#ifdef MCRAW_PATHSM
-void mos_paths_read_stats(uint64_t *out, int n, int reset) { mos_paths_read(out, n, reset); } // (mcraw_diag_mosaic_paths: mcraw_shade.hip)
-#endif
-
 } // namespace mcraw
 
 using namespace mcraw;

@@ -16,6 +16,9 @@
 // and unpacks them (MSB-first bitstreams, RawData_Legacy.cpp:38-370), adds the references, interleaves even/odd
 // columns (:483-486) and crops the padded row (:490).
 #include "mcraw_dev.h"
+#ifdef MCRAW_PATHS6
+#include "mcraw_census.h"
+#endif
 
 #include <cstdlib>
 
@@ -270,7 +273,7 @@ __device__ unsigned long long g_k6_paths[P6_N];
 #define K6_PATH(cond, slot)                                                                                            \
     do {                                                                                                               \
         if (cond)                                                                                                      \
-            atomicAdd(&g_k6_paths[slot], 1ull);                                                                        \
+            census_one(&g_k6_paths[slot]);                                                                             \
     } while (0)
 #else
 #define K6_PATH(cond, slot)
@@ -1262,20 +1265,7 @@ extern "C" void mcraw_diag_k6_prof(uint32_t *out, int nwg, int reset)
 
 #ifdef MCRAW_PATHS6
 // The census, in the order of Path6 (up to n counters; returns how many there are); `reset`: and start it over.
-extern "C" int mcraw_diag_k6_paths(uint64_t *out, int n, int reset)
-{
-    (void)hipDeviceSynchronize();
-    n = n < 0 ? 0 : n < static_cast<int>(P6_N) ? n : static_cast<int>(P6_N);
-    if (out && n)
-        (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_k6_paths), sizeof(uint64_t) * static_cast<size_t>(n));
-    if (reset) {
-        void *p = nullptr;
-        (void)hipGetSymbolAddress(&p, HIP_SYMBOL(g_k6_paths));
-        (void)hipMemset(p, 0, sizeof(g_k6_paths));
-        (void)hipDeviceSynchronize(); // (the contexts' streams do not wait for the null stream)
-    }
-    return static_cast<int>(P6_N);
-}
+extern "C" int mcraw_diag_k6_paths(uint64_t *out, int n, int reset) { return census_read<P6_N>(g_k6_paths, out, n, reset); }
 #endif
 
 // wg_tab (3 * nframes + 1 words, see k6_decode): [0, nframes]: first workgroup of every stage; then the stages' first

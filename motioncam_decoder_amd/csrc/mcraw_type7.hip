@@ -34,12 +34,13 @@
 //                             the span among them) and rely on zero field masks to drop them; entries of no real block belong to
 //                             tiles that item_decode skips.  What was in the LDS before must not matter: a pixel that changes
 //                             proves a dependence on unstaged LDS.
+#if defined(MCRAW_PATHST) || defined(MCRAW_PATHS7)
+#include "mcraw_census.h"
+#endif
 #ifdef MCRAW_PATHST
-#include <hip/hip_runtime.h>
-#include <stdint.h>
 namespace mcraw {
-// What the waves of k7_tiles did, summed over the launches since the last reset.  Events are counted per wave (one lane adds 1) or
-// per lane through a ballot (the first active lane adds the population count).
+// What the waves of k7_tiles did, summed over the launches since the last reset.  Events are counted per wave (K7T_WAVE) or per
+// lane (K7T_COUNT), the ways of mcraw_census.h.
 enum PathT {
     PT_WAVES,                                       // waves with item < total
     PT_INVALID,                                     // ... whose group lies beyond their frame (a mixed size class), or whose frame failed
@@ -61,19 +62,9 @@ enum PathT {
 };
 __device__ unsigned long long g_k7t_paths[PT_N];
 // the active lanes for which `cond` holds (all active lanes of the wave must call this together)
-__device__ __forceinline__ void k7t_count(uint32_t slot, bool cond)
-{
-    const unsigned long long m = __ballot(cond), act = __ballot(true);
-    if (m != 0ull && (threadIdx.x & 63u) == static_cast<uint32_t>(__builtin_ctzll(act)))
-        atomicAdd(&g_k7t_paths[slot], static_cast<unsigned long long>(__popcll(m)));
-}
+__device__ __forceinline__ void k7t_count(uint32_t slot, bool cond) { census_count(&g_k7t_paths[slot], cond); }
 // one per wave (the lanes that are here) when `cond`, which is uniform over them, holds
-__device__ __forceinline__ void k7t_wave(uint32_t slot, bool cond)
-{
-    const unsigned long long act = __ballot(true);
-    if (cond && (threadIdx.x & 63u) == static_cast<uint32_t>(__builtin_ctzll(act)))
-        atomicAdd(&g_k7t_paths[slot], 1ull);
-}
+__device__ __forceinline__ void k7t_wave(uint32_t slot, bool cond) { census_wave(&g_k7t_paths[slot], cond); }
 } // namespace mcraw
 #define MCRAW_STORE_PATH(form, cond) ::mcraw::k7t_count(::mcraw::PT_ST_ALIGNED + static_cast<uint32_t>(form), (cond))
 #define K7T_COUNT(slot, cond) k7t_count(slot, (cond))
@@ -1629,38 +1620,12 @@ extern "C" void mcraw_diag_side_prof(unsigned long long *out, int reset)
 
 #ifdef MCRAW_PATHS7
 // The census, in the order of Path7 (up to n counters; returns how many there are); `reset`: and start it over.
-extern "C" int mcraw_diag_k7_paths(uint64_t *out, int n, int reset)
-{
-    (void)hipDeviceSynchronize();
-    n = n < 0 ? 0 : n < static_cast<int>(P7_N) ? n : static_cast<int>(P7_N);
-    if (out && n)
-        (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_k7_paths), sizeof(uint64_t) * static_cast<size_t>(n));
-    if (reset) {
-        void *p = nullptr;
-        (void)hipGetSymbolAddress(&p, HIP_SYMBOL(g_k7_paths));
-        (void)hipMemset(p, 0, sizeof(g_k7_paths));
-        (void)hipDeviceSynchronize(); // (the contexts' streams do not wait for the null stream)
-    }
-    return static_cast<int>(P7_N);
-}
+extern "C" int mcraw_diag_k7_paths(uint64_t *out, int n, int reset) { return census_read<P7_N>(g_k7_paths, out, n, reset); }
 #endif
 
 #ifdef MCRAW_PATHST
 // The census of k7_tiles, in the order of PathT (up to n counters; returns how many there are); `reset`: and start it over.
-extern "C" int mcraw_diag_k7t_paths(uint64_t *out, int n, int reset)
-{
-    (void)hipDeviceSynchronize();
-    n = n < 0 ? 0 : n < static_cast<int>(PT_N) ? n : static_cast<int>(PT_N);
-    if (out && n)
-        (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_k7t_paths), sizeof(uint64_t) * static_cast<size_t>(n));
-    if (reset) {
-        void *p = nullptr;
-        (void)hipGetSymbolAddress(&p, HIP_SYMBOL(g_k7t_paths));
-        (void)hipMemset(p, 0, sizeof(g_k7t_paths));
-        (void)hipDeviceSynchronize(); // (the contexts' streams do not wait for the null stream)
-    }
-    return static_cast<int>(PT_N);
-}
+extern "C" int mcraw_diag_k7t_paths(uint64_t *out, int n, int reset) { return census_read<PT_N>(g_k7t_paths, out, n, reset); }
 #endif
 
 // The order k7_tiles takes its workgroups' work in (block b of a grid of n -> logical workgroup), exported so that the rule

@@ -7,8 +7,6 @@ the frame still as it was filled -- and every good result is decoded back on the
 must leave its buffer untouched.  A frame whose look-back the `lost` build fails must come back with MCRAW_E_DEVICE and nothing
 counted, its buffer untouched outside the payload of the segments in front of the lost one (in host memory: untouched).  Prints
 the path census of each batch as one line  RESULT {json}.  Exit status 1 when a frame differs."""
-import ctypes as C
-import json
 import os
 import sys
 import time
@@ -21,6 +19,7 @@ sys.path[:0] = [os.path.dirname(HERE), HERE]
 import _enc7_model as E  # noqa: E402
 import _libs as L  # noqa: E402
 import motioncam_decoder_amd as M  # noqa: E402
+import _paths_harness as PH  # noqa: E402
 
 GUARD, FILL, UNSET = 64, 0xA5, 0x7777777777777777
 
@@ -29,15 +28,9 @@ def main(variant):
     t0 = time.time()
     dev = torch.device("cuda:0")
     lib = M.load()
-    lib.mcraw_diag_k7e_paths.restype = C.c_int
-    lib.mcraw_diag_k7e_paths.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.c_int]
     errors, want, tin = [], {}, {}
 
-    def census():
-        a = (C.c_uint64 * len(E.PATHS))()
-        got = lib.mcraw_diag_k7e_paths(a, len(E.PATHS), 1)
-        assert got == len(E.PATHS), "the census has %d counters, this script knows %d" % (got, len(E.PATHS))
-        return dict(zip(E.PATHS, (int(v) for v in a)))
+    census = PH.census_reader(lib, "mcraw_diag_k7e_paths", E.PATHS)
 
     def expect(f):
         if f["name"] not in want:
@@ -130,11 +123,8 @@ def main(variant):
             res["batches"].append(census())
     finally:
         ctx.close()
-    res["seconds"] = round(time.time() - t0, 2)
     res["nerrors"] = len(errors)
-    res["errors"] = errors[:20]
-    print("RESULT " + json.dumps(res))
-    return 1 if errors else 0
+    return PH.finish(res, errors, t0)
 
 
 if __name__ == "__main__":

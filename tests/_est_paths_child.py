@@ -9,7 +9,6 @@ the records are compared with what the parent worked out from the numpy statemen
 input must stay as it was.  The census is read, and started over, after every call of align and cells and after a setting of
 noise.  Prints one line  RESULT {json}.  Exit status 1 when something differs."""
 import ctypes as C
-import json
 import os
 import sys
 import time
@@ -20,6 +19,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 import motioncam_decoder_amd as M  # noqa: E402
+import _paths_harness as PH  # noqa: E402
 import _est_paths_model as T  # noqa: E402
 
 DEV = torch.device("cuda:0")
@@ -30,15 +30,9 @@ def main(npz, variant):
     t0 = time.time()
     lib = M.load()
     Z = np.load(npz)
-    lib.mcraw_diag_est_paths.restype = C.c_int
-    lib.mcraw_diag_est_paths.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.c_int]
     errors = []
 
-    def census():
-        a = (C.c_uint64 * len(T.PATHS))()
-        got = lib.mcraw_diag_est_paths(a, len(T.PATHS), 1)
-        assert got == len(T.PATHS), "the census has %d counters, this script knows %d" % (got, len(T.PATHS))
-        return [int(v) for v in a]
+    census = PH.census_reader(lib, "mcraw_diag_est_paths", T.PATHS, as_dict=False)
 
     def run(ctx, i, name, S):
         H, W, n, fam = S["H"], S["W"], S["n"], S["family"]
@@ -118,10 +112,7 @@ def main(npz, variant):
             res["census"][name] = run(ctx, i, name, S)
     finally:
         ctx.close()
-    res["seconds"] = round(time.time() - t0, 2)
-    res["errors"] = errors[:20]
-    print("RESULT " + json.dumps(res))
-    return 1 if errors else 0
+    return PH.finish(res, errors, t0)
 
 
 if __name__ == "__main__":

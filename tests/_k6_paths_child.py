@@ -5,8 +5,6 @@ batch, frame by frame and as one batch in reversed order, the frames of 16 and m
 and a few frames through the fused stages of k6_decode<POST> (12-bit strips, f16 planes); compares every frame with what the
 parent worked out (the oracle's pixels and return value, the fuzz suite's status rule) and prints the path census of each part
 as one line  RESULT {json}.  Exit status 1 when a frame differs."""
-import ctypes as C
-import json
 import os
 import sys
 import time
@@ -17,6 +15,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT]
 import motioncam_decoder_amd as M  # noqa: E402
+import _paths_harness as PH  # noqa: E402
 
 # the order of Path6 in csrc/mcraw_type6.hip
 PATHS = ["segments", "careful", "repaired", "front0", "latefront", "nofront", "maps", "lb_scalar", "lb_vector", "lb_handed",
@@ -32,17 +31,11 @@ def main(npz):
     want = [Z["out%d" % i] for i in range(n)]
     dev = torch.device("cuda:0")
     lib = M.load()
-    lib.mcraw_diag_k6_paths.restype = C.c_int
-    lib.mcraw_diag_k6_paths.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.c_int]
     ctx = M.Context(0)
     tin = [torch.from_numpy(b).to(dev) for b in bufs]
     errors = []
 
-    def census():
-        a = (C.c_uint64 * len(PATHS))()
-        got = lib.mcraw_diag_k6_paths(a, len(PATHS), 1)
-        assert got == len(PATHS), "the census has %d counters, this script knows %d" % (got, len(PATHS))
-        return dict(zip(PATHS, (int(v) for v in a)))
+    census = PH.census_reader(lib, "mcraw_diag_k6_paths", PATHS)
 
     def decode(order, how):
         outs = [torch.zeros(int(meta[i][0]) * int(meta[i][1]) * 2, dtype=torch.uint8, device=dev) for i in order]
@@ -108,10 +101,7 @@ def main(npz):
         ctx.set_post()
     res["post"] = census()
     ctx.close()
-    res["seconds"] = round(time.time() - t0, 2)
-    res["errors"] = errors[:20]
-    print("RESULT " + json.dumps(res))
-    return 1 if errors else 0
+    return PH.finish(res, errors, t0)
 
 
 if __name__ == "__main__":

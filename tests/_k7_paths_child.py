@@ -8,8 +8,6 @@ with a context of its own per setting (the environment is read when a context is
 compared with what the parent worked out (the oracle's pixels and return value, the fuzz suite's status rule); the rows below a
 frame coded shorter than asked and a guard band behind every output must stay as they were filled.  Prints the path census of
 each setting as one line  RESULT {json}.  Exit status 1 when a frame differs."""
-import ctypes as C
-import json
 import os
 import sys
 import time
@@ -20,6 +18,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT]
 import motioncam_decoder_amd as M  # noqa: E402
+import _paths_harness as PH  # noqa: E402
 
 # the order of Path7 in csrc/mcraw_type7.hip
 PATHS = ["streams", "rejected", "records", "units", "units_full", "piece_steps", "units_dead", "skipped_units", "dead", "run_passes",
@@ -40,8 +39,6 @@ def main(npz):
     n = len(meta)
     dev = torch.device("cuda:0")
     lib = M.load()
-    lib.mcraw_diag_k7_paths.restype = C.c_int
-    lib.mcraw_diag_k7_paths.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.c_int]
     tin = [torch.from_numpy(Z["buf%d" % i]).to(dev) for i in range(n)]
     want = []
     for i in range(n):
@@ -51,11 +48,7 @@ def main(npz):
         want.append(a.reshape(-1))
     errors = []
 
-    def census():
-        a = (C.c_uint64 * len(PATHS))()
-        got = lib.mcraw_diag_k7_paths(a, len(PATHS), 1)
-        assert got == len(PATHS), "the census has %d counters, this script knows %d" % (got, len(PATHS))
-        return dict(zip(PATHS, (int(v) for v in a)))
+    census = PH.census_reader(lib, "mcraw_diag_k7_paths", PATHS)
 
     def decode(ctx, order, how):
         outs = [torch.full((int(meta[i][0]) * int(meta[i][1]) * 2 + GUARD,), FILL, dtype=torch.uint8, device=dev) for i in order]
@@ -98,10 +91,7 @@ def main(npz):
             res[name] = census()
         finally:
             ctx.close()
-    res["seconds"] = round(time.time() - t0, 2)
-    res["errors"] = errors[:20]
-    print("RESULT " + json.dumps(res))
-    return 1 if errors else 0
+    return PH.finish(res, errors, t0)
 
 
 if __name__ == "__main__":

@@ -7,7 +7,6 @@ environment is read when a context is made; one context at a time): every frame 
 frame's output is compared byte for byte with what the parent worked out from the oracle; the bytes in front of an output that
 does not start on the allocation, the rows below a frame coded shorter than asked and a guard band behind every output must stay
 as they were filled.  Prints the census of each setting as one line  RESULT {json}.  Exit status 1 when a frame differs."""
-import ctypes as C
 import json
 import os
 import sys
@@ -19,6 +18,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT]
 import motioncam_decoder_amd as M  # noqa: E402
+import _paths_harness as PH  # noqa: E402
 
 # the order of PathT in csrc/mcraw_type7.hip
 PATHS = (["waves", "invalid", "short", "tiles_skipped", "span_empty", "span_full", "head", "wg_remap", "wg_chunked"]
@@ -37,16 +37,10 @@ def main(npz):
     meta = Z["meta"]  # per frame: w, h, ret
     dev = torch.device("cuda:0")
     lib = M.load()
-    lib.mcraw_diag_k7t_paths.restype = C.c_int
-    lib.mcraw_diag_k7t_paths.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.c_int]
     tin = [torch.from_numpy(Z["buf%d" % i]).to(dev) for i in range(len(meta))]
     errors = []
 
-    def census():
-        a = (C.c_uint64 * len(PATHS))()
-        got = lib.mcraw_diag_k7t_paths(a, len(PATHS), 1)
-        assert got == len(PATHS), "the census has %d counters, this script knows %d" % (got, len(PATHS))
-        return dict(zip(PATHS, (int(v) for v in a)))
+    census = PH.census_reader(lib, "mcraw_diag_k7t_paths", PATHS)
 
     def decode(ctx, s, S, order):
         off = int(S["off"])
@@ -88,10 +82,7 @@ def main(npz):
             res[S["name"]] = census()
         finally:
             ctx.close()
-    res["seconds"] = round(time.time() - t0, 2)
-    res["errors"] = errors[:20]
-    print("RESULT " + json.dumps(res))
-    return 1 if errors else 0
+    return PH.finish(res, errors, t0)
 
 
 if __name__ == "__main__":

@@ -16,6 +16,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 import motioncam_decoder_amd as M  # noqa: E402
+import _paths_harness as PH  # noqa: E402
 
 GUARD, FILL = 4096, 0xA5
 
@@ -53,8 +54,7 @@ def main(npz):
         if bad.size:
             errors.append("%s: %d bytes differ, the first at %d" % (S["name"], bad.size, int(bad[0])))
     ctx.close()
-    print("RESULT " + json.dumps({"errors": errors, "cases": len(plan), "seconds": round(time.time() - t0, 2)}))
-    return 1 if errors else 0
+    return PH.finish({"cases": len(plan)}, errors, t0)
 
 
 if __name__ == "__main__":

@@ -21,6 +21,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 import motioncam_decoder_amd as M  # noqa: E402
+import _paths_harness as PH  # noqa: E402
 import _mosaic_paths_model as T  # noqa: E402
 
 GUARD, SENT = 2048, 0xA5A5
@@ -54,15 +55,9 @@ def main(npz, variant):
         torch.zeros(1, device=DEV)
         return sweep(lib)
     Z = np.load(npz)
-    lib.mcraw_diag_mosaic_paths.restype = C.c_int
-    lib.mcraw_diag_mosaic_paths.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.c_int]
     errors = []
 
-    def census():
-        a = (C.c_uint64 * len(T.PATHS))()
-        got = lib.mcraw_diag_mosaic_paths(a, len(T.PATHS), 1)
-        assert got == len(T.PATHS), "the census has %d counters, this script knows %d" % (got, len(T.PATHS))
-        return [int(v) for v in a]
+    census = PH.census_reader(lib, "mcraw_diag_mosaic_paths", T.PATHS, as_dict=False)
 
     def run(ctx, i, name, S):
         H, W, fam = S["H"], S["W"], S["family"]
@@ -134,10 +129,7 @@ def main(npz, variant):
             res["census"][name] = census()
     finally:
         ctx.close()
-    res["seconds"] = round(time.time() - t0, 2)
-    res["errors"] = errors[:20]
-    print("RESULT " + json.dumps(res))
-    return 1 if errors else 0
+    return PH.finish(res, errors, t0)
 
 
 if __name__ == "__main__":

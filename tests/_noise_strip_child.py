@@ -4,9 +4,9 @@ Loads the build of the library that MCRAW_LIB_PATH names (build.NOISE_STRIP_FLAG
 three calls of Context.noise_stats whose frames have 6, 34 and 6 strips: that many workgroups add their LDS counters to one frame's
 record.  Every call's records, with the sentinels around them, are compared with the numpy statement (_noise_ref).  Prints one line
 RESULT {json}.  Exit status 1 when something differs."""
-import json
 import os
 import sys
+import time
 
 import numpy as np
 import torch
@@ -15,6 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 import motioncam_decoder_amd as M  # noqa: E402
 import _noise_ref as NR  # noqa: E402
+import _paths_harness as PH  # noqa: E402
 
 DEV = torch.device("cuda:0")
 GUARD, SENT = 4096, 0xA5
@@ -22,7 +23,7 @@ CALLS = ((2, 48, 1040), (1, 272, 1040), (3, 96, 272))  # frames, H, W
 
 
 def main():
-    errors, strips = [], []
+    t0, errors, strips = time.time(), [], []
     ctx = M.Context(0)
     try:
         for k, (n, H, W) in enumerate(CALLS):
@@ -44,8 +45,7 @@ def main():
                 errors.append("call %d: the records differ from the numpy statement" % k)
     finally:
         ctx.close()
-    print("RESULT " + json.dumps({"errors": errors, "calls": len(CALLS), "strips": strips}))
-    return 1 if errors else 0
+    return PH.finish({"calls": len(CALLS), "strips": strips}, errors, t0)
 
 
 if __name__ == "__main__":

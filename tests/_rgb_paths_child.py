@@ -19,6 +19,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 import motioncam_decoder_amd as M  # noqa: E402
+import _paths_harness as PH  # noqa: E402
 import _rgb_paths_model as T  # noqa: E402
 
 GUARD, FILL = 4096, 0xA5
@@ -72,16 +73,10 @@ def main(npz, variant):
     plan = json.loads(str(Z["plan"]))
     dev = torch.device("cuda:0")
     lib = M.load()
-    lib.mcraw_diag_rgb_paths.restype = C.c_int
-    lib.mcraw_diag_rgb_paths.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.c_int]
     luts = {n: torch.from_numpy(Z["lut_%d" % n].view(np.int16)).to(dev).view(torch.uint16) for n in (4096, 65536)}
     errors = []
 
-    def census():
-        a = (C.c_uint64 * len(T.PATHS))()
-        got = lib.mcraw_diag_rgb_paths(a, len(T.PATHS), 1)
-        assert got == len(T.PATHS), "the census has %d counters, this script knows %d" % (got, len(T.PATHS))
-        return dict(zip(T.PATHS, (int(v) for v in a)))
+    census = PH.census_reader(lib, "mcraw_diag_rgb_paths", T.PATHS)
 
     def run(ctx, S):
         n, H, W, kind = S["n"], S["H"], S["W"], S["kind"]
@@ -130,10 +125,7 @@ def main(npz, variant):
             res["census"][S["name"]] = census()
     finally:
         ctx.close()
-    res["seconds"] = round(time.time() - t0, 2)
-    res["errors"] = errors[:20]
-    print("RESULT " + json.dumps(res))
-    return 1 if errors else 0
+    return PH.finish(res, errors, t0)
 
 
 if __name__ == "__main__":

@@ -30,7 +30,7 @@ where `rmn > 4095` is evaluated (k7e_side only sees the clamped ref); and in a l
 those of the frames that do not fail plus the two look-backs in front of the lost segment -- one that gives up may have added
 none.
 
-A child that ends by a signal, at its time limit or without its result stops every further child: the remaining variants fail at
+A child that ends by a signal, at its time limit or without its result stops every further child, of this module and of every other (tests/_paths_harness.py): the remaining variants fail at
 once.  Nothing is tried twice.
 
 Wall times on an MI355X, one run of the module (the six tests: 16.0 s).  Per variant: the child's own `seconds` (from its first line
@@ -44,12 +44,11 @@ look-back gave up); in each of the three failing launches of `lost` 4 look-backs
 met LB_FAIL."""
 import json
 import os
-import subprocess
-import sys
 
 import pytest
 
 import _enc7_model as E
+import _paths_harness as PH
 from motioncam_decoder_amd import build as B
 
 pytestmark = pytest.mark.gpu
@@ -57,45 +56,19 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD = os.path.join(ROOT, "tests", "_enc7_paths_child.py")
 CHILD_TIMEOUT = 30  # seconds: ten times the slowest measured whole test (see above)
 
-_stop = []     # why no further child may be started (a child ended by signal or time limit)
-_results = {}  # variant -> what its child printed
+
+
+def _judge(variant, res, returncode):
+    print(variant, "errors", res["nerrors"])
+    for (name, _, _, _), c in zip(E.plan(variant), res["batches"]):
+        print(variant, name, json.dumps({k: v for k, v in c.items() if v}))
+    PH.no_errors("frames differ from the synthesiser")(variant, res, returncode)
 
 
 def _child(variant, tmp_path_factory):
-    """The census of `variant`'s child.  The child is run once, whatever becomes of it: a second caller gets the same answer."""
-    if variant not in _results:
-        if _stop:
-            pytest.fail("no GPU work after a child that did not end in order: " + _stop[0])
-        try:
-            _results[variant] = _run_child(variant, tmp_path_factory)
-        except BaseException as e:  # (pytest.fail's outcome is no Exception)
-            _results[variant] = e
-    if isinstance(_results[variant], BaseException):
-        raise _results[variant]
-    return _results[variant]
-
-
-def _run_child(variant, tmp_path_factory):
-    lib = str(tmp_path_factory.mktemp("lib_" + variant) / ("libmcraw_k7e_%s.so" % variant))
-    B.build_variant(lib, B.ENC7_PATH_VARIANTS[variant])
-    env = dict(os.environ, MCRAW_LIB_PATH=lib)
-    try:
-        r = subprocess.run([sys.executable, CHILD, variant], env=env, capture_output=True, text=True, timeout=CHILD_TIMEOUT)
-    except subprocess.TimeoutExpired:
-        _stop.append("%s ran into its time limit" % variant)
-        pytest.fail(_stop[0])
-    line = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")]
-    # A child that ends by a signal, or without its result line (an exception on the way: a HIP error is one), may have left the GPU
-    # faulted.  Only "compared everything, frames differ" (status 1 WITH the line) lets the other variants run.
-    if r.returncode < 0 or r.returncode in (124, 134, 137, 139) or not line:
-        _stop.append("%s ended with status %d%s" % (variant, r.returncode, "" if line else " and no result"))
-        pytest.fail(_stop[0] + "\n" + r.stdout[-2000:] + r.stderr[-3000:])
-    res = json.loads(line[-1][7:])
-    print(variant, "seconds", res["seconds"], "errors", res["nerrors"])
-    for (name, _, _, _), c in zip(E.plan(variant), res["batches"]):
-        print(variant, name, json.dumps({k: v for k, v in c.items() if v}))
-    assert r.returncode == 0 and not res["errors"], "%s: frames differ from the synthesiser:\n%s" % (variant, "\n".join(res["errors"]))
-    return res
+    """The census of `variant`'s child, which is run once whatever becomes of it (tests/_paths_harness.py)."""
+    return PH.run_child(__name__, variant, CHILD, [variant], B.ENC7_PATH_VARIANTS[variant], "libmcraw_k7e_%s.so" % variant, CHILD_TIMEOUT,
+                       tmp_path_factory, _judge)
 
 
 def check(variant, res):

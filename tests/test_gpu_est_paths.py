@@ -21,7 +21,7 @@ model, EVERY counter, EXACTLY.
                      knoise equals `census`'s; knoise's workgroups follow noise_plan per launch
   strips1            knoise with one strip per workgroup: as many workgroups as strips
 
-A child that ends by a signal, at its time limit or without its result stops every further child: the remaining tests fail at
+A child that ends by a signal, at its time limit or without its result stops every further child, of this module and of every other (tests/_paths_harness.py): the remaining tests fail at
 once.  Nothing is tried twice.
 
 Measured on an MI355X, one run of the module (7 passed in 34.28 s with the new test of test_gpu_align_cells.py).  Per variant: the
@@ -33,12 +33,11 @@ of `census`):
 CHILD_TIMEOUT is ten times the slowest whole test; it guards against a hang, not against performance."""
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+import _paths_harness as PH
 from motioncam_decoder_amd import build as B
 
 pytestmark = pytest.mark.gpu
@@ -46,8 +45,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD = os.path.join(ROOT, "tests", "_est_paths_child.py")
 CHILD_TIMEOUT = 115  # seconds: ten times the slowest measured whole test (see above)
 
-_stop = []     # why no further child may be started (a child ended by signal or time limit)
-_results = {}  # variant -> what its child printed
 
 
 def make_npz(path):
@@ -72,38 +69,14 @@ def corpus_npz(tmp_path_factory):
 
 
 def _child(variant, corpus_npz, tmp_path_factory):
-    """The result of `variant`'s child.  The child is run once, whatever becomes of it: a second caller gets the same answer."""
-    if variant not in _results:
-        if _stop:
-            pytest.fail("no GPU work after a child that did not end in order: " + _stop[0])
-        try:
-            _results[variant] = _run_child(variant, corpus_npz, tmp_path_factory)
-        except BaseException as e:  # (pytest.fail's outcome is no Exception)
-            _results[variant] = e
-    if isinstance(_results[variant], BaseException):
-        raise _results[variant]
-    return _results[variant]
+    """The result of `variant`'s child, which is run once whatever becomes of it (tests/_paths_harness.py)."""
+    return PH.run_child(__name__, variant, CHILD, [corpus_npz, variant], B.EST_PATH_VARIANTS[variant], "libmcraw_estp_%s.so" % variant,
+                       CHILD_TIMEOUT, tmp_path_factory, PH.no_errors("outputs differ from the numpy statements"))
 
 
-def _run_child(variant, npz, tmp_path_factory):
-    lib = str(tmp_path_factory.mktemp("lib_" + variant) / ("libmcraw_estp_%s.so" % variant))
-    B.build_variant(lib, B.EST_PATH_VARIANTS[variant])
-    env = dict(os.environ, MCRAW_LIB_PATH=lib)
-    try:
-        r = subprocess.run([sys.executable, CHILD, npz, variant], env=env, capture_output=True, text=True, timeout=CHILD_TIMEOUT)
-    except subprocess.TimeoutExpired:
-        _stop.append("%s ran into its time limit" % variant)
-        pytest.fail(_stop[0])
-    line = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")]
-    # A child that ends by a signal, or without its result line (an exception on the way: a HIP error is one), may have left the GPU
-    # faulted.  Only "compared everything, something differs" (status 1 WITH the line) lets the other variants run.
-    if r.returncode < 0 or r.returncode in (124, 134, 137, 139) or not line:
-        _stop.append("%s ended with status %d%s" % (variant, r.returncode, "" if line else " and no result"))
-        pytest.fail(_stop[0] + "\n" + r.stdout[-2000:] + r.stderr[-3000:])
-    res = json.loads(line[-1][7:])
-    print(variant, "child seconds", res["seconds"])
-    assert r.returncode == 0 and not res["errors"], "%s: outputs differ from the numpy statements:\n%s" % (variant, "\n".join(res["errors"]))
-    return res
+def _seen(variant):
+    """What `variant`'s child left, if it has run: its result or the failure."""
+    return PH.outcome(__name__, variant)
 
 
 def check(variant, res):
@@ -112,8 +85,8 @@ def check(variant, res):
     assert res["paths"] == T.PATHS, "the child's counters are not the model's"
     assert list(res["census"]) == list(T.SETTINGS)
     total = dict.fromkeys(T.PATHS, 0)
-    twin = _results.get({"poison": "census", "poisonslow": "slow"}.get(variant))
-    plain = _results.get("census") if variant == "frames2" else None
+    twin = _seen({"poison": "census", "poisonslow": "slow"}.get(variant))
+    plain = _seen("census") if variant == "frames2" else None
     bad = []
     for name, rows in res["census"].items():
         S, want = T.SETTINGS[name], T.model(name, variant)

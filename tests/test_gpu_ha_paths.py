@@ -11,16 +11,15 @@ LDS and in global memory.  With one workgroup every unit behind the first is a l
 another frame; with three a workgroup's successive units skip columns, rows and frames.  The child compares every call's output
 byte for byte with the numpy statement (_ha_ref), the guard bands around it included.
 
-A child that ends by a signal, at its time limit or without its result stops every further child: the remaining variants fail at
+A child that ends by a signal, at its time limit or without its result stops every further child, of this module and of every other (tests/_paths_harness.py): the remaining variants fail at
 once.  Nothing is tried twice."""
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+import _paths_harness as PH
 import motioncam_decoder_amd as M
 from motioncam_decoder_amd import build as B
 
@@ -31,8 +30,6 @@ CHILD_TIMEOUT = 60  # seconds: guards against a hang, not against performance (a
 VARIANTS = ("grid1", "grid3")
 H, WD, N = 40, 520, 3  # 2 x 3 tiles: the last tile row 8 rows high, the last tile column 8 columns wide
 WHITE, BLACK, IN_BITS = 3.5, (3, 1, 2, 3), 11
-
-_stop = []
 
 
 def make_npz(path):
@@ -91,23 +88,5 @@ def corpus_npz(tmp_path_factory):
 @pytest.mark.parametrize("variant", VARIANTS)
 def test_ha_persistent_loop(variant, corpus_npz, tmp_path_factory):
     assert (H + 31) // 32 * ((WD + 255) // 256) >= 6 and N >= 3  # at least 6 tiles x 3 frames
-    if _stop:
-        pytest.fail("no GPU work after a child that did not end in order: " + _stop[0])
-    lib = str(tmp_path_factory.mktemp("lib_" + variant) / ("libmcraw_hap_%s.so" % variant))
-    B.build_variant(lib, B.RGB_PATH_VARIANTS[variant])
-    env = dict(os.environ, MCRAW_LIB_PATH=lib)
-    try:
-        r = subprocess.run([sys.executable, CHILD, corpus_npz], env=env, capture_output=True, text=True, timeout=CHILD_TIMEOUT)
-    except subprocess.TimeoutExpired:
-        _stop.append("%s ran into its time limit" % variant)
-        pytest.fail(_stop[0])
-    line = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")]
-    # A child that ends by a signal, or without its result line (an exception on the way: a HIP error is one), may have left the GPU
-    # faulted.  Only "compared everything, bytes differ" (status 1 WITH the line) lets the other variants run.
-    if r.returncode < 0 or r.returncode in (124, 134, 137, 139) or not line:
-        _stop.append("%s ended with status %d%s" % (variant, r.returncode, "" if line else " and no result"))
-        pytest.fail(_stop[0] + "\n" + r.stdout[-2000:] + r.stderr[-3000:])
-    res = json.loads(line[-1][7:])
-    print(variant, "child seconds", res["seconds"])
-    assert r.returncode == 0 and not res["errors"] and res["cases"] == 8, "%s: outputs differ from the numpy statement:\n%s" % (
-        variant, "\n".join(res["errors"]))
+    PH.run_child(__name__, variant, CHILD, [corpus_npz], B.RGB_PATH_VARIANTS[variant], "libmcraw_hap_%s.so" % variant, CHILD_TIMEOUT, tmp_path_factory,
+                 PH.no_errors("outputs differ from the numpy statement", lambda res: res["cases"] == 8))

@@ -29,7 +29,7 @@ the switch decides, nothing where timing alone does:
               held at the next barrier; no barrier is added)
   every one   nothing lost, every segment counted once, the look-backs add up to the segments that have a predecessor
 
-A child that ends by a signal or runs into its time limit is followed by no more GPU work from this module: the remaining
+A child that ends by a signal or runs into its time limit is followed by no more GPU work from this module or any other (tests/_paths_harness.py): the remaining
 variants fail at once.  Nothing is tried twice.
 
 Wall times on an MI355X, one run of the module (11 passed in 26.0 s).  Per variant: the child's own `seconds` (from its first
@@ -40,12 +40,11 @@ The child process is what the time limit is on; it is no slower than the test ar
 ten times that."""
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+import _paths_harness as PH
 from motioncam_decoder_amd import build as B
 
 pytestmark = pytest.mark.gpu
@@ -54,8 +53,6 @@ CHILD = os.path.join(ROOT, "tests", "_k6_paths_child.py")
 CHILD_TIMEOUT = 25   # seconds: ten times the slowest measured child (see above)
 PASSES = 3           # one batch, frame by frame, reversed batch
 
-_stop = []     # why no further child may be started (a child ended by signal or time limit)
-_results = {}  # variant -> what its child printed
 
 POST_FRAMES = ("nat12 w200 1 segment", "nat12 8 segments, ends 3 bytes short", "mixed nibbles (1, 2, 3)", "late front")
 POST_BLACK, POST_WHITE = (60, 64, 68, 1000), 4095.0
@@ -95,37 +92,10 @@ def corpus_npz(tmp_path_factory):
 
 
 def _child(variant, corpus_npz, tmp_path_factory):
-    """The census of `variant`'s child.  The child is run once, whatever becomes of it: a second caller gets the same answer."""
-    if variant not in _results:
-        if _stop:
-            pytest.fail("no GPU work after a child that did not end in order: " + _stop[0])
-        try:
-            _results[variant] = _run_child(variant, corpus_npz[0], tmp_path_factory)
-        except BaseException as e:  # (pytest.fail's outcome is no Exception)
-            _results[variant] = e
-    if isinstance(_results[variant], BaseException):
-        raise _results[variant]
-    return _results[variant]
-
-
-def _run_child(variant, npz, tmp_path_factory):
-    lib = str(tmp_path_factory.mktemp("lib_" + variant) / ("libmcraw_k6_%s.so" % variant))
-    B.build_variant(lib, B.K6_PATH_VARIANTS[variant])
-    env = dict(os.environ, MCRAW_LIB_PATH=lib)
-    try:
-        r = subprocess.run([sys.executable, CHILD, npz], env=env, capture_output=True, text=True, timeout=CHILD_TIMEOUT)
-    except subprocess.TimeoutExpired:
-        _stop.append("%s ran into its time limit" % variant)
-        pytest.fail(_stop[0])
-    line = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")]
-    # A child that ends by a signal, or without its result line (an exception on the way: a HIP error is one), may have left the GPU
-    # faulted.  Only "compared everything, frames differ" (status 1 WITH the line) lets the other variants run.
-    if r.returncode < 0 or r.returncode in (124, 134, 137, 139) or not line:
-        _stop.append("%s ended with status %d%s" % (variant, r.returncode, "" if line else " and no result"))
-        pytest.fail(_stop[0] + "\n" + r.stdout[-2000:] + r.stderr[-3000:])
-    res = json.loads(line[-1][7:])
+    """The census of `variant`'s child, which is run once whatever becomes of it (tests/_paths_harness.py)."""
+    res = PH.run_child(__name__, variant, CHILD, [corpus_npz[0]], B.K6_PATH_VARIANTS[variant], "libmcraw_k6_%s.so" % variant, CHILD_TIMEOUT,
+                      tmp_path_factory, PH.no_errors("frames differ from the oracle"))
     print(variant, json.dumps(res))
-    assert r.returncode == 0 and not res["errors"], "%s: frames differ from the oracle:\n%s" % (variant, "\n".join(res["errors"]))
     return res
 
 

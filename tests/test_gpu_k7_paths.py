@@ -27,7 +27,7 @@ tests/_side7_corpus.py and the switch determine -- exact counts where content or
   smallpieces  the piece steps are the model's at 8 KiB
   poison       pixels, and the sums above
 
-A child that ends by a signal, at its time limit or without its result stops every further child: the remaining variants fail at
+A child that ends by a signal, at its time limit or without its result stops every further child, of this module and of every other (tests/_paths_harness.py): the remaining variants fail at
 once.  Nothing is tried twice.
 
 Wall times on an MI355X, one run of the module (10 passed in 26.5 s; the corpus and the oracle's answers, made once: 0.55 s).  Per
@@ -39,12 +39,11 @@ The child process is what the time limit is on; it is no slower than the test ar
 ten times that."""
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+import _paths_harness as PH
 from motioncam_decoder_amd import build as B
 
 pytestmark = pytest.mark.gpu
@@ -67,8 +66,6 @@ CENSUS_DRIVEN = ("streams", "rejected", "records", "units", "units_full", "piece
 # first piece), and no part of these batches gives up waiting: both are what the `mute` build is for
 NOT_DRIVEN = ("ho_mute", "ho_mute_work", "ho_mute_part1", "skipped_units")
 
-_stop = []     # why no further child may be started (a child ended by signal or time limit)
-_results = {}  # variant -> what its child printed
 _models = {}
 
 
@@ -121,37 +118,10 @@ def corpus_npz(tmp_path_factory):
 
 
 def _child(variant, corpus_npz, tmp_path_factory):
-    """The census of `variant`'s child.  The child is run once, whatever becomes of it: a second caller gets the same answer."""
-    if variant not in _results:
-        if _stop:
-            pytest.fail("no GPU work after a child that did not end in order: " + _stop[0])
-        try:
-            _results[variant] = _run_child(variant, corpus_npz, tmp_path_factory)
-        except BaseException as e:  # (pytest.fail's outcome is no Exception)
-            _results[variant] = e
-    if isinstance(_results[variant], BaseException):
-        raise _results[variant]
-    return _results[variant]
-
-
-def _run_child(variant, npz, tmp_path_factory):
-    lib = str(tmp_path_factory.mktemp("lib_" + variant) / ("libmcraw_k7_%s.so" % variant))
-    B.build_variant(lib, B.K7_PATH_VARIANTS[variant])
-    env = dict(os.environ, MCRAW_LIB_PATH=lib)
-    try:
-        r = subprocess.run([sys.executable, CHILD, npz], env=env, capture_output=True, text=True, timeout=CHILD_TIMEOUT)
-    except subprocess.TimeoutExpired:
-        _stop.append("%s ran into its time limit" % variant)
-        pytest.fail(_stop[0])
-    line = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")]
-    # A child that ends by a signal, or without its result line (an exception on the way: a HIP error is one), may have left the GPU
-    # faulted.  Only "compared everything, frames differ" (status 1 WITH the line) lets the other variants run.
-    if r.returncode < 0 or r.returncode in (124, 134, 137, 139) or not line:
-        _stop.append("%s ended with status %d%s" % (variant, r.returncode, "" if line else " and no result"))
-        pytest.fail(_stop[0] + "\n" + r.stdout[-2000:] + r.stderr[-3000:])
-    res = json.loads(line[-1][7:])
+    """The census of `variant`'s child, which is run once whatever becomes of it (tests/_paths_harness.py)."""
+    res = PH.run_child(__name__, variant, CHILD, [corpus_npz], B.K7_PATH_VARIANTS[variant], "libmcraw_k7_%s.so" % variant, CHILD_TIMEOUT,
+                      tmp_path_factory, PH.no_errors("frames differ from the oracle"))
     print(variant, json.dumps(res))
-    assert r.returncode == 0 and not res["errors"], "%s: frames differ from the oracle:\n%s" % (variant, "\n".join(res["errors"]))
     return res
 
 

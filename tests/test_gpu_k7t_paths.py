@@ -18,7 +18,7 @@ this module compares the census of every setting with the model, EVERY counter, 
   nomerge      no merged store and no decline; the plain 14-bit forms take the merged pieces
   poison       pixels, and every count as in `census` (a pixel that changes proves a dependence on LDS the item never staged)
 
-A child that ends by a signal, at its time limit or without its result stops every further child: the remaining variants fail at
+A child that ends by a signal, at its time limit or without its result stops every further child, of this module and of every other (tests/_paths_harness.py): the remaining variants fail at
 once.  Nothing is tried twice.
 
 Wall times on an MI355X, one run of the module (5 passed in 32.5 s).  Per variant: the child's own `seconds` (from its first line
@@ -29,12 +29,11 @@ answers and the file for the children):
 CHILD_TIMEOUT is ten times the slowest whole test; it guards against a hang, not against performance."""
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+import _paths_harness as PH
 from motioncam_decoder_amd import build as B
 
 pytestmark = pytest.mark.gpu
@@ -43,8 +42,6 @@ CHILD = os.path.join(ROOT, "tests", "_k7t_paths_child.py")
 CHILD_TIMEOUT = 110  # seconds: ten times the slowest measured whole test (see above)
 
 MERGED = ("st_merged_fwd", "st_merged_back")
-_stop = []     # why no further child may be started (a child ended by signal or time limit)
-_results = {}  # variant -> what its child printed
 
 
 def make_npz(path):
@@ -75,37 +72,10 @@ def corpus_npz(tmp_path_factory):
 
 
 def _child(variant, corpus_npz, tmp_path_factory):
-    """The census of `variant`'s child.  The child is run once, whatever becomes of it: a second caller gets the same answer."""
-    if variant not in _results:
-        if _stop:
-            pytest.fail("no GPU work after a child that did not end in order: " + _stop[0])
-        try:
-            _results[variant] = _run_child(variant, corpus_npz, tmp_path_factory)
-        except BaseException as e:  # (pytest.fail's outcome is no Exception)
-            _results[variant] = e
-    if isinstance(_results[variant], BaseException):
-        raise _results[variant]
-    return _results[variant]
-
-
-def _run_child(variant, npz, tmp_path_factory):
-    lib = str(tmp_path_factory.mktemp("lib_" + variant) / ("libmcraw_k7t_%s.so" % variant))
-    B.build_variant(lib, B.K7T_PATH_VARIANTS[variant])
-    env = dict(os.environ, MCRAW_LIB_PATH=lib)
-    try:
-        r = subprocess.run([sys.executable, CHILD, npz], env=env, capture_output=True, text=True, timeout=CHILD_TIMEOUT)
-    except subprocess.TimeoutExpired:
-        _stop.append("%s ran into its time limit" % variant)
-        pytest.fail(_stop[0])
-    line = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")]
-    # A child that ends by a signal, or without its result line (an exception on the way: a HIP error is one), may have left the GPU
-    # faulted.  Only "compared everything, frames differ" (status 1 WITH the line) lets the other variants run.
-    if r.returncode < 0 or r.returncode in (124, 134, 137, 139) or not line:
-        _stop.append("%s ended with status %d%s" % (variant, r.returncode, "" if line else " and no result"))
-        pytest.fail(_stop[0] + "\n" + r.stdout[-2000:] + r.stderr[-3000:])
-    res = json.loads(line[-1][7:])
+    """The census of `variant`'s child, which is run once whatever becomes of it (tests/_paths_harness.py)."""
+    res = PH.run_child(__name__, variant, CHILD, [corpus_npz], B.K7T_PATH_VARIANTS[variant], "libmcraw_k7t_%s.so" % variant, CHILD_TIMEOUT,
+                      tmp_path_factory, PH.no_errors("frames differ from the oracle"))
     print(variant, json.dumps(res))
-    assert r.returncode == 0 and not res["errors"], "%s: frames differ from the oracle:\n%s" % (variant, "\n".join(res["errors"]))
     return res
 
 

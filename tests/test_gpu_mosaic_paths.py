@@ -30,7 +30,7 @@ statements; this module compares the census of every call with the model, EVERY 
   sweep              div_round(n, den) == n / den for den 1 .. 6400, quotients 0 .. 65536, n = k * den + {-1, 0, 1, den / 2,
                      den - 1}: as many evaluations as the enumeration in Python counts, no mismatch, and both correction steps taken
 
-A child that ends by a signal, at its time limit or without its result stops every further child: the remaining tests fail at
+A child that ends by a signal, at its time limit or without its result stops every further child, of this module and of every other (tests/_paths_harness.py): the remaining tests fail at
 once.  Nothing is tried twice.
 
 Measured on an MI355X, one run of the module (7 passed in 22.25 s).  Per variant: the child's own `seconds` (from its first line to
@@ -49,12 +49,11 @@ are what LDS held: the steps differ by one or two from build to build) 495 steps
 content) only the step up occurs, at exact multiples of den: the `bright` settings are there for the other one."""
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+import _paths_harness as PH
 from motioncam_decoder_amd import build as B
 
 pytestmark = pytest.mark.gpu
@@ -62,8 +61,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD = os.path.join(ROOT, "tests", "_mosaic_paths_child.py")
 CHILD_TIMEOUT = 33  # seconds: ten times the slowest measured whole test (see above)
 
-_stop = []     # why no further child may be started (a child ended by signal or time limit)
-_results = {}  # variant -> what its child printed
 
 
 def make_npz(path):
@@ -119,40 +116,16 @@ def corpus_npz(tmp_path_factory):
 
 
 def _child(variant, corpus_npz, tmp_path_factory):
-    """The result of `variant`'s child.  The child is run once, whatever becomes of it: a second caller gets the same answer."""
-    if variant not in _results:
-        if _stop:
-            pytest.fail("no GPU work after a child that did not end in order: " + _stop[0])
-        try:
-            _results[variant] = _run_child(variant, corpus_npz, tmp_path_factory)
-        except BaseException as e:  # (pytest.fail's outcome is no Exception)
-            _results[variant] = e
-    if isinstance(_results[variant], BaseException):
-        raise _results[variant]
-    return _results[variant]
-
-
-def _run_child(variant, npz, tmp_path_factory):
+    """The result of `variant`'s child, which is run once whatever becomes of it (tests/_paths_harness.py)."""
     flags = B.MOSAIC_FRAMES2_FLAGS if variant == "frames2" else B.MOSAIC_PATH_VARIANTS["census" if variant == "sweep" else variant]
-    lib = str(tmp_path_factory.mktemp("lib_" + variant) / ("libmcraw_mosp_%s.so" % variant))
-    B.build_variant(lib, flags)
-    env = dict(os.environ, MCRAW_LIB_PATH=lib)
-    try:
-        r = subprocess.run([sys.executable, CHILD, npz, variant], env=env, capture_output=True, text=True, timeout=CHILD_TIMEOUT)
-    except subprocess.TimeoutExpired:
-        _stop.append("%s ran into its time limit" % variant)
-        pytest.fail(_stop[0])
-    line = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")]
-    # A child that ends by a signal, or without its result line (an exception on the way: a HIP error is one), may have left the GPU
-    # faulted.  Only "compared everything, something differs" (status 1 WITH the line) lets the other variants run.
-    if r.returncode < 0 or r.returncode in (124, 134, 137, 139) or not line:
-        _stop.append("%s ended with status %d%s" % (variant, r.returncode, "" if line else " and no result"))
-        pytest.fail(_stop[0] + "\n" + r.stdout[-2000:] + r.stderr[-3000:])
-    res = json.loads(line[-1][7:])
-    print(variant, "child seconds", res["seconds"])
-    if variant != "sweep":
-        assert r.returncode == 0 and not res["errors"], "%s: outputs differ from the numpy statements:\n%s" % (variant, "\n".join(res["errors"]))
-    return res
+    judge = (lambda *a: None) if variant == "sweep" else PH.no_errors("outputs differ from the numpy statements")
+    return PH.run_child(__name__, variant, CHILD, [corpus_npz, variant], flags, "libmcraw_mosp_%s.so" % variant, CHILD_TIMEOUT,
+                       tmp_path_factory, judge)
+
+
+def _seen(variant):
+    """What `variant`'s child left, if it has run: its result or the failure."""
+    return PH.outcome(__name__, variant)
 
 
 def check(variant, res):
@@ -180,7 +153,7 @@ def check(variant, res):
             for k, names in T.DRIVEN.items():
                 assert got[k] > 0 or name not in names, (variant, name, k)
         if variant in ("poison", "poisonslow"):
-            plain = _results.get({"poison": "census", "poisonslow": "slow"}[variant])
+            plain = _seen({"poison": "census", "poisonslow": "slow"}[variant])
             if isinstance(plain, dict):
                 free = T.model(name, "census")["_unstaged"]
                 for k, a, b in zip(T.PATHS, row, plain["census"][name]):
@@ -192,7 +165,7 @@ def check(variant, res):
     else:
         assert variant in ("th16", "pieces", "slow", "frames2") or ranged == 0
     if variant == "pieces":  # more workgroups of kstats than the product's, each of two tiles at most; kmerge in launches of 3 outputs
-        plain = _results.get("census")
+        plain = _seen("census")
         for name, row in res["census"].items():
             S = T.SETTINGS[name]
             if S["family"] in ("merge", "merge_cells"):
@@ -202,10 +175,10 @@ def check(variant, res):
                 P, got = T.stats_plan(S, variant), dict(zip(T.PATHS, row))
                 assert P["tpc"] <= 2 and got["wg"] == T.FRAMES * P["wgs"] and got["wg"] + got["ss_prefetch"] == T.FRAMES * P["tiles"], name
         assert total["ss_prefetch"] > 0 and (not isinstance(plain, dict) or total["wg"] > sum(r[0] for r in plain["census"].values()))
-    if variant == "frames2" and isinstance(_results.get("census"), dict):
+    if variant == "frames2" and isinstance(_seen("census"), dict):
         for name, row in res["census"].items():
             free = T.model(name, "census")["_unstaged"]
-            for k, a, b in zip(T.PATHS, row, _results["census"]["census"][name]):
+            for k, a, b in zip(T.PATHS, row, _seen("census")["census"][name]):
                 assert a == b or k in free or k in T.UNMODELLED, (variant, name, k, a, b)
     if variant in ("slow", "poisonslow"):
         assert total["mg_zerow"] == 0 and total["mg_staged"] > 0

@@ -2,10 +2,7 @@
 the numpy statement of the contract (_noise_ref) byte for byte -- everything is an integer, so there is no tolerance --, the call
 initialises its records itself and writes nothing around them, the input is left as it was, accumulation adds up, a repeated call
 gives the same bytes, and the profile that estimate_noise fits feeds noise_lut and denoise()."""
-import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -13,6 +10,7 @@ import torch
 
 import _libs as L
 import _noise_ref as NR
+import _paths_harness as PH
 import motioncam_decoder_amd as M
 from motioncam_decoder_amd import build as B
 
@@ -229,14 +227,9 @@ def test_estimate_noise_feeds_denoise(gpu_ctx):
     assert got.shape == imgs.shape and np.abs(got - clean).mean() < np.abs(imgs - clean).mean()
 
 
-def test_one_strip_per_workgroup(tmp_path):
+def test_one_strip_per_workgroup(tmp_path_factory):
     """A build that holds a workgroup to one strip (build.NOISE_STRIP_FLAGS), in a child process: as many workgroups as strips add
     their counters to a frame's record."""
-    lib = str(tmp_path / "libmcraw_noise_strip.so")
-    B.build_variant(lib, B.NOISE_STRIP_FLAGS)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_noise_strip_child.py")], env=dict(os.environ, MCRAW_LIB_PATH=lib),
-                       capture_output=True, text=True, timeout=120)
-    line = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")]
-    assert r.returncode == 0 and line, (r.returncode, r.stdout[-2000:], r.stderr[-3000:])
-    res = json.loads(line[-1][7:])
+    res = PH.run_child(__name__, "strips1", os.path.join(ROOT, "tests", "_noise_strip_child.py"), [], B.NOISE_STRIP_FLAGS,
+                       "libmcraw_noise_strip.so", 120, tmp_path_factory)
     assert res["errors"] == [] and res["calls"] == 3 and res["strips"] == [6, 34, 6]

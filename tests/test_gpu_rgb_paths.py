@@ -20,7 +20,7 @@ the guard bands around it included; this module compares the census of every cal
   grid3            the model's walk; with grid1: every instance with a LUT shows later units and frame crossings
   poison, poison1  pixels, and every count as in `census` / `grid1`
 
-A child that ends by a signal, at its time limit or without its result stops every further child: the remaining variants fail at
+A child that ends by a signal, at its time limit or without its result stops every further child, of this module and of every other (tests/_paths_harness.py): the remaining variants fail at
 once.  Nothing is tried twice.
 
 Wall times on an MI355X: one run of the module (5 passed in 13.87 s) for the whole tests, one run of the five children for their
@@ -32,12 +32,11 @@ the children are made once, in 0.5 s, in front of `census`):
 CHILD_TIMEOUT is ten times the slowest whole test; it guards against a hang, not against performance."""
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+import _paths_harness as PH
 import motioncam_decoder_amd as M
 from motioncam_decoder_amd import build as B
 
@@ -46,8 +45,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD = os.path.join(ROOT, "tests", "_rgb_paths_child.py")
 CHILD_TIMEOUT = 27  # seconds: ten times the slowest measured whole test (see above)
 
-_stop = []     # why no further child may be started (a child ended by signal or time limit)
-_results = {}  # variant -> what its child printed
 
 
 def make_npz(path):
@@ -103,38 +100,9 @@ def corpus_npz(tmp_path_factory):
 
 
 def _child(variant, corpus_npz, tmp_path_factory):
-    """The census of `variant`'s child.  The child is run once, whatever becomes of it: a second caller gets the same answer."""
-    if variant not in _results:
-        if _stop:
-            pytest.fail("no GPU work after a child that did not end in order: " + _stop[0])
-        try:
-            _results[variant] = _run_child(variant, corpus_npz, tmp_path_factory)
-        except BaseException as e:  # (pytest.fail's outcome is no Exception)
-            _results[variant] = e
-    if isinstance(_results[variant], BaseException):
-        raise _results[variant]
-    return _results[variant]
-
-
-def _run_child(variant, npz, tmp_path_factory):
-    lib = str(tmp_path_factory.mktemp("lib_" + variant) / ("libmcraw_rgbp_%s.so" % variant))
-    B.build_variant(lib, B.RGB_PATH_VARIANTS[variant])
-    env = dict(os.environ, MCRAW_LIB_PATH=lib)
-    try:
-        r = subprocess.run([sys.executable, CHILD, npz, variant], env=env, capture_output=True, text=True, timeout=CHILD_TIMEOUT)
-    except subprocess.TimeoutExpired:
-        _stop.append("%s ran into its time limit" % variant)
-        pytest.fail(_stop[0])
-    line = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")]
-    # A child that ends by a signal, or without its result line (an exception on the way: a HIP error is one), may have left the GPU
-    # faulted.  Only "compared everything, bytes differ" (status 1 WITH the line) lets the other variants run.
-    if r.returncode < 0 or r.returncode in (124, 134, 137, 139) or not line:
-        _stop.append("%s ended with status %d%s" % (variant, r.returncode, "" if line else " and no result"))
-        pytest.fail(_stop[0] + "\n" + r.stdout[-2000:] + r.stderr[-3000:])
-    res = json.loads(line[-1][7:])
-    print(variant, "child seconds", res["seconds"])
-    assert r.returncode == 0 and not res["errors"], "%s: outputs differ from the numpy statements:\n%s" % (variant, "\n".join(res["errors"]))
-    return res
+    """The census of `variant`'s child, which is run once whatever becomes of it (tests/_paths_harness.py)."""
+    return PH.run_child(__name__, variant, CHILD, [corpus_npz, variant], B.RGB_PATH_VARIANTS[variant], "libmcraw_rgbp_%s.so" % variant,
+                       CHILD_TIMEOUT, tmp_path_factory, PH.no_errors("outputs differ from the numpy statements"))
 
 
 def check(variant, res):
@@ -179,8 +147,8 @@ def check(variant, res):
     kinds_of = {"bin2": ("u8", "u16"), "bin2y": ("nv12", "p010")}
     instances = {(f, k, c) for f in T.FAMILIES for k in kinds_of.get(f, ("u8", "u16", "nv12", "p010")) for c in T.CFAS}
     assert instances <= seen, sorted(instances - seen)
-    if variant in T.PRODUCT_OF and T.PRODUCT_OF[variant] in _results and isinstance(_results[T.PRODUCT_OF[variant]], dict):
-        assert res["census"] == _results[T.PRODUCT_OF[variant]]["census"], "the poisoned build's counts are not the plain build's"
+    if variant in T.PRODUCT_OF and isinstance(PH.outcome(__name__, T.PRODUCT_OF[variant]), dict):
+        assert res["census"] == PH.outcome(__name__, T.PRODUCT_OF[variant])["census"], "the poisoned build's counts are not the plain build's"
 
 
 @pytest.mark.parametrize("variant", list(B.RGB_PATH_VARIANTS))
