@@ -165,12 +165,13 @@ K7T_PATH_VARIANTS = {
     "poison": ["-DMCRAW_PATHST", "-DMCRAW_POISON_PAYT"],
 }
 
-# The demosaic kernels (krgb_mhc, krgb_bin2, krgb_bin2y, krgb_area, krgb_resample) with every path counted and the persistent loop
-# forced (tests/test_gpu_rgb_paths.py; the switches and why each is valid for every input: the head of csrc/mcraw_rgb.hip).  Every
-# name below occurs in mcraw_rgb.hip, mcraw_area.hip and mcraw_resample.hip alone -- the shared headers count, cap and poison
-# through hooks that only those sources define --, so a variant compiles those three sources; mcraw_warp.hip, mcraw_mesh.hip and
-# mcraw_ha.hip name none of them and take their grids' limit from mcraw_rgb.hip (krgb_warp: tests/test_gpu_warp_paths.py; krgb_mesh:
-# tests/test_gpu_mesh_paths.py; krgb_ha: tests/test_gpu_ha_paths.py).
+# The demosaic kernels (krgb_mhc, krgb_bin2, krgb_bin2y, krgb_area, krgb_resample, krgb_warp, krgb_mesh, krgb_ha) with every path
+# counted and the persistent loop forced (tests/test_gpu_rgb_paths.py; krgb_warp: tests/test_gpu_warp_paths.py; krgb_mesh:
+# tests/test_gpu_mesh_paths.py; krgb_ha: tests/test_gpu_ha_paths.py; the switches and why each is valid for every input: the head of
+# csrc/mcraw_rgb.hip).  MCRAW_PATHSR and MCRAW_POISON_RGB occur in mcraw_rgb.hip, mcraw_area.hip, mcraw_resample.hip, mcraw_warp.hip,
+# mcraw_mesh.hip and mcraw_ha.hip alone -- the shared headers count, cap and poison through hooks that only those sources define --,
+# so a variant compiles those six sources; MCRAW_RGB_GRID_CAP occurs in the first three, and the other three take their grids'
+# limit from mcraw_rgb.hip.
 #   grid1  one workgroup walks every unit of every frame in order
 #   grid3  successive units of a workgroup skip columns, rows and frames
 RGB_PATH_VARIANTS = {

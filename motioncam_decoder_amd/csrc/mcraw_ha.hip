@@ -18,11 +18,14 @@
 //              and of g (4 x 5) from LDS, E[3][8] per row, and the family's row store
 // Every three-way choice is a pair of selects: the lanes of a wave disagree on every edge.
 // Float kinds: one tile per workgroup; display and YUV kinds: a persistent grid that stages the LUT once, as krgb_mhc.
+#ifdef MCRAW_PATHSR // (the test builds' switches: the head of mcraw_rgb.hip; the grid's cap comes from that source, below)
+#include "mcraw_rgb_paths.h"
+#endif
 #include "mcraw_dev.h"
 #include "mcraw_host.h"
 #include "mcraw_rgb_args.h"
 #include "mcraw_rgb_dev.h"
-// The persistent grid's limit is mcraw_rgb.hip's: this unit names no switch of a test build, and a build of that source with a
+// The persistent grid's limit is mcraw_rgb.hip's: this unit does not name the cap's switch, and a build of that source with a
 // capped grid (build.RGB_PATH_VARIANTS) caps this unit's grid too (tests/test_gpu_ha_paths.py).
 namespace mcraw {
 uint32_t rgb_grid_limit(uint32_t resident);
@@ -41,12 +44,15 @@ __device__ __forceinline__ int ha_pick(int a, int Da, int b, int Db)
     return lo + hi;
 }
 
-// g at an R / B site from d there (C), its axial neighbours at distance 1 (w1, e1, n1, s1) and 2 (w2, e2, n2, s2)
+// g at an R / B site from d there (C), its axial neighbours at distance 1 (w1, e1, n1, s1) and 2 (w2, e2, n2, s2); SITE: the call
+// site for the census (0 a main item, 1 an edge item)
+template <int SITE>
 __device__ __forceinline__ int ha_green(int C, int w1, int e1, int w2, int e2, int n1, int s1, int n2, int s2)
 {
     const int ch = 2 * C - w2 - e2, cv = 2 * C - n2 - s2;
     const int gh = 2 * (w1 + e1) + ch, gv = 2 * (n1 + s1) + cv;
     const int DH = abs(w1 - e1) + abs(ch), DV = abs(n1 - s1) + abs(cv);
+    HA_PICKS(SITE, DH, DV, true);
     return ha_pick(gh, DH, gv, DV);
 }
 
@@ -58,6 +64,7 @@ __global__ void __launch_bounds__(RGB_T) krgb_ha(const RgbArgs A)
     __shared__ __attribute__((aligned(16))) int32_t s_g[HA_GH * HA_GW];
     __shared__ __attribute__((aligned(16))) uint16_t s_lut[LUT ? DISP_LDS_MAX : 8u];
     uint32_t t = blockIdx.x;
+    RGB_WALK_DECL;
     if constexpr (LUT)
         stage_lut(A, s_lut);
     const int W = static_cast<int>(A.W), H = static_cast<int>(A.H);
@@ -65,7 +72,15 @@ __global__ void __launch_bounds__(RGB_T) krgb_ha(const RgbArgs A)
     do {
         if constexpr (LUT)
             __syncthreads(); // the LUT is staged; the previous tile's LDS reads are done
+#ifdef MCRAW_POISON_RGB
+        // the raw window as the siblings'; a green value of 0x05a5a5a5 lies far above every value of ha_green (< 2^21), and the
+        // estimates' sums over it (at most 8 of them) stay inside an int: a stray read changes bytes and overflows nothing
+        rgb_poison(s_raw, sizeof(s_raw), 0x5a5a5a5bu);
+        rgb_poison(s_g, sizeof(s_g), 0x05a5a5a5u);
+        __syncthreads();
+#endif
         const uint32_t f = LUT ? t / A.units : blockIdx.y, u = LUT ? t % A.units : blockIdx.x;
+        RGB_WALK(RF_HA, f, LUT, A.lutg);
         const uint32_t tx = u % A.tilesX, ty = u / A.tilesX;
         const int x0 = static_cast<int>(tx * MHC_TW), y0 = static_cast<int>(ty * MHC_TH);
         const uint16_t *in = A.in + static_cast<size_t>(f) * A.fstride;
@@ -76,8 +91,10 @@ __global__ void __launch_bounds__(RGB_T) krgb_ha(const RgbArgs A)
             const int xs = x0 - 8 + 8 * static_cast<int>(q);
             mcraw_u32x4 v;
             if (A.invec && xs >= 0 && xs + 8 <= W) {
+                RGB_PATH(RP_HA_LD_VEC, true);
                 v = *gptr<const mcraw_u32x4>(row + xs);
             } else {
+                RGB_PATH(RP_HA_LD_ELEM, true);
                 uint32_t e[8];
 #pragma unroll
                 for (int k = 0; k < 8; k++)
@@ -110,7 +127,7 @@ __global__ void __launch_bounds__(RGB_T) krgb_ha(const RgbArgs A)
 #pragma unroll
                 for (int k = 0; k < 4; k++) {
                     const int J = 2 * k + xp + 2;
-                    g[k] = static_cast<uint32_t>(ha_green(d[R][J], d[R][J - 1], d[R][J + 1], d[R][J - 2], d[R][J + 2], d[R - 1][J],
+                    g[k] = static_cast<uint32_t>(ha_green<0>(d[R][J], d[R][J - 1], d[R][J + 1], d[R][J - 2], d[R][J + 2], d[R - 1][J],
                                                           d[R + 1][J], d[R - 2][J], d[R + 2][J]));
                 }
                 *reinterpret_cast<mcraw_u32x4 *>(&s_g[ha_g_idx(2u * rp + static_cast<uint32_t>(a), 4u * q + 4u)]) =
@@ -125,13 +142,14 @@ __global__ void __launch_bounds__(RGB_T) krgb_ha(const RgbArgs A)
             const int b_h = yp ? (xp ? bk[2] : bk[3]) : (xp ? bk[0] : bk[1]);   // left and right
             const int b_v = yp ? (xp ? bk[1] : bk[0]) : (xp ? bk[3] : bk[2]);   // above and below
             const auto at = [&](uint32_t dr, int dc) { return static_cast<int>(s_raw[ha_raw_idx(Q + dr, static_cast<uint32_t>(static_cast<int>(C) + dc))]); };
-            s_g[ha_g_idx(Q, C >> 1)] = ha_green(at(2, 0) - b_c, at(2, -1) - b_h, at(2, 1) - b_h, at(2, -2) - b_c, at(2, 2) - b_c,
+            s_g[ha_g_idx(Q, C >> 1)] = ha_green<1>(at(2, 0) - b_c, at(2, -1) - b_h, at(2, 1) - b_h, at(2, -2) - b_c, at(2, 2) - b_c,
                                                 at(1, 0) - b_v, at(3, 0) - b_v, at(0, 0) - b_c, at(4, 0) - b_c);
         }
         __syncthreads();
         // ---- estimates
         const uint32_t lx = threadIdx.x & 31u, ly = threadIdx.x >> 5;
         const uint32_t x = static_cast<uint32_t>(x0) + 8u * lx;
+        RGB_PATH(RP_HA_CONTINUE, x >= A.W);
         if (x >= A.W)
             continue;
         const uint32_t n = min(8u, A.W - x);
@@ -140,6 +158,7 @@ __global__ void __launch_bounds__(RGB_T) krgb_ha(const RgbArgs A)
 #pragma unroll 1
         for (uint32_t pass = 0; pass < MHC_TH / 16u; pass++) {
             const uint32_t tr = 2u * (ly + 8u * pass), y = static_cast<uint32_t>(y0) + tr;
+            RGB_PATH(RP_HA_BREAK, y >= A.H);
             if (y >= A.H)
                 break;
             // d[r][j], G[r][j] at frame (y - 1 + r, x - 1 + j): frame parities (r + 1) & 1 and (j + 1) & 1
@@ -184,6 +203,7 @@ __global__ void __launch_bounds__(RGB_T) krgb_ha(const RgbArgs A)
                         const int DN = 8 * abs(d[R - 1][J - 1] - d[R + 1][J + 1]) + abs(cN);
                         const int DP = 8 * abs(d[R - 1][J + 1] - d[R + 1][J - 1]) + abs(cP);
                         const int o = ha_pick(nN, DN, nP, DP);
+                        HA_PICKS(2, DN, DP, static_cast<uint32_t>(b) < n);
                         E[0][b] = role == 0 ? nat : o;
                         E[1][b] = 4 * g;
                         E[2][b] = role == 0 ? o : nat;

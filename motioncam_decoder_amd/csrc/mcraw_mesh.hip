@@ -16,11 +16,15 @@
 //           otherwise -- both equal the contract's 64-bit statement (tests/cpp/mesh_args_check.cpp) --, then the per-pixel
 //           clamp to the frame and the clamp of the tap origin into the window
 // No node content can make a read leave the LDS arrays or the frame's reflection: the kernel depends on no validation.
+#ifdef MCRAW_PATHSR // (the test builds' switches: the head of mcraw_rgb.hip; the grid's cap comes from that source, below)
+#define RGB_GATHER_FAMILY 1u
+#include "mcraw_rgb_paths.h"
+#endif
 #include "mcraw_dev.h"
 #include "mcraw_host.h"
 #include "mcraw_rgb_args.h"
 #include "mcraw_rgb_dev.h"
-// The persistent grid's limit is mcraw_rgb.hip's, as for krgb_warp: this unit names no switch of a test build
+// The persistent grid's limit is mcraw_rgb.hip's, as for krgb_warp: this unit does not name the cap's switch
 // (tests/test_gpu_mesh_paths.py).
 namespace mcraw {
 uint32_t rgb_grid_limit(uint32_t resident);
@@ -52,6 +56,7 @@ __global__ void __launch_bounds__(RGB_T) krgb_mesh(const RgbArgs A, const MeshGe
     __shared__ __attribute__((aligned(16))) int16_t s_w[256u * 4u];
     __shared__ __attribute__((aligned(16))) uint16_t s_lut[LUT ? DISP_LDS_MAX : 8u];
     uint32_t t = blockIdx.x;
+    RGB_WALK_DECL;
     if constexpr (LUT)
         stage_lut(A, s_lut);
     for (uint32_t i = threadIdx.x; i < 256u; i += RGB_T) { // the phase table in use: four int16 per phase
@@ -65,6 +70,7 @@ __global__ void __launch_bounds__(RGB_T) krgb_mesh(const RgbArgs A, const MeshGe
     const int W = static_cast<int>(A.W), H = static_cast<int>(A.H);
     do {
         const uint32_t f = LUT ? t / A.units : blockIdx.y, u = LUT ? t % A.units : blockIdx.x;
+        RGB_WALK(RF_MESH, f, LUT, A.lutg);
         const uint32_t tx = u % G.tilesX, ty = u / G.tilesX;
         const uint32_t k0 = tx * WARP_TW, k1 = min(k0 + WARP_TW, A.Wo) - 1u; // the tile's first and last column
         const uint32_t i0 = ty * WARP_TH, i1 = min(i0 + WARP_TH, A.Ho) - 1u; // ... and row
@@ -81,17 +87,32 @@ __global__ void __launch_bounds__(RGB_T) krgb_mesh(const RgbArgs A, const MeshGe
         const uint32_t np = min(win.np, MESH_NP), ne = min(win.ne, MESH_NE);
         const int32_t rmax = mesh_tap_max_row(win.np), cmax = mesh_tap_max_col(win.ne);
         const bool narrow = mesh_narrow(cy) && mesh_narrow(cx);
+        RGB_PATH_UNIT(RP_MESH_NARROW, narrow);
+        RGB_PATH_UNIT(RP_MESH_WIDE, !narrow);
         const uint16_t *in = A.in + static_cast<size_t>(f) * A.fstride;
         __syncthreads(); // the LUT and the table are staged; the previous tile's LDS reads are done
+#ifdef MCRAW_POISON_RGB
+        // the raw window as the siblings'; an estimate of 0x5a5a5b lies above every value of phase A (< 2^22) and inside the taps'
+        // bounds (|v >> 8| < 2^15): a stray read changes bytes and overflows nothing
+        rgb_poison(s_raw, sizeof(s_raw), 0x5a5a5a5bu);
+        rgb_poison(s_e, sizeof(s_e), 0x005a5a5bu);
+        __syncthreads();
+#endif
+        WARP_UNIT(RPG_CUT_ROWS, np < win.np);
+        WARP_UNIT(RPG_CUT_COLS, ne < win.ne);
         warp_stage(A, in, s_raw, pb, eb, np, ne, W, H); // raw rows pb - 2 .. pb + 2 np + 1, columns eb - 8 .. eb + 8 ne + 7
         __syncthreads();
         // A: rows of parity 0 in the first half of the workgroup, of parity 1 in the second (uniform in a wave)
         if (threadIdx.x < RGB_T / 2u) {
-            for (uint32_t it = threadIdx.x; it < np * ne; it += RGB_T / 2u)
+            for (uint32_t it = threadIdx.x; it < np * ne; it += RGB_T / 2u) {
+                WARP_PATH(RPG_A_EVEN, true);
                 warp_mhc_row<S, 0>(A, s_raw, s_e, it / ne, it % ne);
+            }
         } else {
-            for (uint32_t it = threadIdx.x - RGB_T / 2u; it < np * ne; it += RGB_T / 2u)
+            for (uint32_t it = threadIdx.x - RGB_T / 2u; it < np * ne; it += RGB_T / 2u) {
+                WARP_PATH(RPG_A_ODD, true);
                 warp_mhc_row<S, 1>(A, s_raw, s_e, it / ne, it % ne);
+            }
         }
         __syncthreads();
         // gather: a lane takes 4 output columns of one output row: every lane of the workgroup has its pixels
@@ -99,6 +120,8 @@ __global__ void __launch_bounds__(RGB_T) krgb_mesh(const RgbArgs A, const MeshGe
             const uint32_t gr = threadIdx.x / (WARP_TW / 4u), gc = 4u * (threadIdx.x % (WARP_TW / 4u));
             const uint32_t j = i0 + gr, x = k0 + gc;
             int32_t E4[3][4] = {};
+            WARP_PATH(RPG_PIX, j <= i1 && x <= k1);
+            WARP_PATH(RPG_NOPIX, !(j <= i1 && x <= k1));
             if (j <= i1 && x <= k1) {
                 int32_t Ys[4], Xs[4]; // the lane's four positions: a uniform choice between the two forms of the same sum
                 if (narrow) {
@@ -109,12 +132,20 @@ __global__ void __launch_bounds__(RGB_T) krgb_mesh(const RgbArgs A, const MeshGe
                     for (uint32_t i = 0; i < 4u; i++) {
                         Ys[i] = mesh_clamp32(mesh_lerp32(cy[0], ly, ry, gc + i), H);
                         Xs[i] = mesh_clamp32(mesh_lerp32(cx[0], lx, rx, gc + i), W);
+                        RGB_PATH(RP_MESH_Y_LO, mesh_lerp32(cy[0], ly, ry, gc + i) < 0);
+                        RGB_PATH(RP_MESH_Y_HI, mesh_lerp32(cy[0], ly, ry, gc + i) > 256 * (H - 1));
+                        RGB_PATH(RP_MESH_X_LO, mesh_lerp32(cx[0], lx, rx, gc + i) < 0);
+                        RGB_PATH(RP_MESH_X_HI, mesh_lerp32(cx[0], lx, rx, gc + i) > 256 * (W - 1));
                     }
                 } else {
 #pragma unroll
                     for (uint32_t i = 0; i < 4u; i++) {
                         Ys[i] = static_cast<int32_t>(mesh_clamp(mesh_lerp64(cy, gr, gc + i), H));
                         Xs[i] = static_cast<int32_t>(mesh_clamp(mesh_lerp64(cx, gr, gc + i), W));
+                        RGB_PATH(RP_MESH_Y_LO, mesh_lerp64(cy, gr, gc + i) < 0);
+                        RGB_PATH(RP_MESH_Y_HI, mesh_lerp64(cy, gr, gc + i) > 256 * (static_cast<int64_t>(H) - 1));
+                        RGB_PATH(RP_MESH_X_LO, mesh_lerp64(cx, gr, gc + i) < 0);
+                        RGB_PATH(RP_MESH_X_HI, mesh_lerp64(cx, gr, gc + i) > 256 * (static_cast<int64_t>(W) - 1));
                     }
                 }
 #pragma unroll
@@ -124,6 +155,10 @@ __global__ void __launch_bounds__(RGB_T) krgb_mesh(const RgbArgs A, const MeshGe
                     warp_weights(s_w, static_cast<uint32_t>(Y) & 255u, wy);
                     warp_weights(s_w, static_cast<uint32_t>(X) & 255u, wx);
                     warp_taps(s_e, wy, wx, min(max((Y >> 8) - 1 - pb, 0), rmax), min(max((X >> 8) - 1 - eb, 0), cmax), e3);
+                    WARP_PATH(RPG_TAP_ROW_LO, (Y >> 8) - 1 - pb < 0);
+                    WARP_PATH(RPG_TAP_ROW_HI, (Y >> 8) - 1 - pb > rmax);
+                    WARP_PATH(RPG_TAP_COL_LO, (X >> 8) - 1 - eb < 0);
+                    WARP_PATH(RPG_TAP_COL_HI, (X >> 8) - 1 - eb > cmax);
                     E4[0][i] = e3[0], E4[1][i] = e3[1], E4[2][i] = e3[2];
                 }
             }

@@ -21,15 +21,18 @@
 // mcraw_rgb_dev.h and the host side of the launch through mcraw_rgb_launch.h.
 //
 // Test builds of the demosaic kernels (tests/test_gpu_rgb_paths.py, build.RGB_PATH_VARIANTS; none of this is in the product
-// library).  The three switches are read by this file, mcraw_area.hip and mcraw_resample.hip alone; the shared headers only have
-// hooks that are empty unless defined in front of them.  Each switch chooses among ways that are right for EVERY input:
+// library).  MCRAW_PATHSR and MCRAW_POISON_RGB are read by this file, mcraw_area.hip, mcraw_resample.hip, mcraw_warp.hip,
+// mcraw_mesh.hip and mcraw_ha.hip alone, MCRAW_RGB_GRID_CAP by the first three (the other three take rgb_grid_limit() below); the
+// shared headers only have hooks that are empty unless defined in front of them.  Each switch chooses among ways that are right
+// for EVERY input:
 //   MCRAW_PATHSR            the path census (mcraw_rgb_paths.h; mcraw_diag_rgb_paths below adds up the sources that include it).
 //   MCRAW_RGB_GRID_CAP=N    a persistent launch uses min(units x frames, N) workgroups, not min(units x frames, resident): the
 //                           loop's condition makes any grid of 1 .. units x frames workgroups walk every unit exactly once.  The
 //                           float kinds have no loop and are untouched.
 //   MCRAW_POISON_RGB        a workgroup fills every LDS array it stages per unit with a non-zero pattern at the start of every
 //                           unit, the first included, and syncs: a unit may read only what it staged itself, so a byte that
-//                           changes proves a dependence on stale LDS.  s_lut, staged once per workgroup, is left alone.
+//                           changes proves a dependence on stale LDS.  s_lut, staged once per workgroup, is left alone (and
+//                           s_w of krgb_warp and krgb_mesh).  The patterns: beside each rgb_poison().
 #ifdef MCRAW_PATHSR
 #include "mcraw_rgb_paths.h"
 #endif

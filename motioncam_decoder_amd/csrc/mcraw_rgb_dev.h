@@ -13,8 +13,12 @@
 //   RGB_PATH(slot, cond)            the active lanes for which `cond` holds take path `slot`
 //   RGB_PATH_YUV(slot, dst, n, es)  8 samples of a YUV row at dst: the form yuv_store8 takes
 //   RGB_WALK_DECL, RGB_WALK(family, f, lut, lutg)   a workgroup takes a unit of frame f
+//   RGB_PATH_UNIT(slot, cond)       the workgroup's unit takes path `slot` (`cond` is uniform over the workgroup)
+//   HA_PICKS(site, Da, Db, on)      the active lanes for which `on` holds call ha_pick(.., Da, .., Db) at call site `site`
 #ifndef RGB_PATH
 #define RGB_PATH(slot, cond)
+#define RGB_PATH_UNIT(slot, cond)
+#define HA_PICKS(site, Da, Db, on)
 #define RGB_PATH_YUV(slot, dst, n, es)
 #define RGB_WALK_DECL
 #define RGB_WALK(family, f, lut, lutg)

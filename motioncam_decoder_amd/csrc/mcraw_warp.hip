@@ -21,11 +21,15 @@
 // Every sum of taps is exact in two int32 accumulators: v = 256 vh + vl, A = sum w vh, B = sum w vl (the header's bounds),
 // 24-bit multiplies (|w| < 2^13, |vh| < 2^15).  The phase table in use sits in LDS; the maps travel in the kernel arguments,
 // beside the colours, in pieces of RGB_MAXF frames.
+#ifdef MCRAW_PATHSR // (the test builds' switches: the head of mcraw_rgb.hip; the grid's cap comes from that source, below)
+#define RGB_GATHER_FAMILY 0u
+#include "mcraw_rgb_paths.h"
+#endif
 #include "mcraw_dev.h"
 #include "mcraw_host.h"
 #include "mcraw_rgb_args.h"
 #include "mcraw_rgb_dev.h"
-// The persistent grid's limit is mcraw_rgb.hip's: this unit names no switch of a test build, and a build of that source with a
+// The persistent grid's limit is mcraw_rgb.hip's: this unit does not name the cap's switch, and a build of that source with a
 // capped grid (build.RGB_PATH_VARIANTS) caps this unit's grid too (tests/test_gpu_warp_paths.py).
 namespace mcraw {
 uint32_t rgb_grid_limit(uint32_t resident);
@@ -56,6 +60,10 @@ __device__ __forceinline__ void warp_pixel(const int32_t *s_e, const int16_t *s_
     warp_weights(s_w, static_cast<uint32_t>(X) & 255u, wx);
     const int32_t r0 = min(max(static_cast<int32_t>(Y >> 8) - 1 - pb, 0), static_cast<int32_t>(WARP_EROWS) - 4);
     const int32_t c0 = min(max(static_cast<int32_t>(X >> 8) - 1 - eb, 0), static_cast<int32_t>(WARP_ECOLS) - 4);
+    WARP_PATH(RPG_TAP_ROW_LO, static_cast<int32_t>(Y >> 8) - 1 - pb < 0);
+    WARP_PATH(RPG_TAP_ROW_HI, static_cast<int32_t>(Y >> 8) - 1 - pb > static_cast<int32_t>(WARP_EROWS) - 4);
+    WARP_PATH(RPG_TAP_COL_LO, static_cast<int32_t>(X >> 8) - 1 - eb < 0);
+    WARP_PATH(RPG_TAP_COL_HI, static_cast<int32_t>(X >> 8) - 1 - eb > static_cast<int32_t>(WARP_ECOLS) - 4);
     warp_taps(s_e, wy, wx, r0, c0, E);
 }
 
@@ -68,6 +76,7 @@ __global__ void __launch_bounds__(RGB_T) krgb_warp(const RgbArgs A, const WarpGe
     __shared__ __attribute__((aligned(16))) int16_t s_w[256u * 4u];
     __shared__ __attribute__((aligned(16))) uint16_t s_lut[LUT ? DISP_LDS_MAX : 8u];
     uint32_t t = blockIdx.x;
+    RGB_WALK_DECL;
     if constexpr (LUT)
         stage_lut(A, s_lut);
     for (uint32_t i = threadIdx.x; i < 256u; i += RGB_T) { // the phase table in use: four int16 per phase
@@ -81,6 +90,7 @@ __global__ void __launch_bounds__(RGB_T) krgb_warp(const RgbArgs A, const WarpGe
     const int W = static_cast<int>(A.W), H = static_cast<int>(A.H);
     do {
         const uint32_t f = LUT ? t / A.units : blockIdx.y, u = LUT ? t % A.units : blockIdx.x;
+        RGB_WALK(RF_WARP, f, LUT, A.lutg);
         const uint32_t tx = u % G.tilesX, ty = u / G.tilesX;
         const uint32_t k0 = tx * WARP_TW, k1 = min(k0 + WARP_TW, A.Wo) - 1u; // the tile's first and last column
         const uint32_t i0 = ty * WARP_TH, i1 = min(i0 + WARP_TH, A.Ho) - 1u; // ... and row
@@ -93,15 +103,28 @@ __global__ void __launch_bounds__(RGB_T) krgb_warp(const RgbArgs A, const WarpGe
         const uint32_t np = min(win.np, WARP_EROWS / 2u), ne = min(win.ne, WARP_ECOLS / 8u);
         const uint16_t *in = A.in + static_cast<size_t>(f) * A.fstride;
         __syncthreads(); // the LUT and the table are staged; the previous tile's LDS reads are done
+#ifdef MCRAW_POISON_RGB
+        // the raw window as the siblings'; an estimate of 0x5a5a5b lies above every value of phase A (< 2^22) and inside the taps'
+        // bounds (|v >> 8| < 2^15): a stray read changes bytes and overflows nothing
+        rgb_poison(s_raw, sizeof(s_raw), 0x5a5a5a5bu);
+        rgb_poison(s_e, sizeof(s_e), 0x005a5a5bu);
+        __syncthreads();
+#endif
+        WARP_UNIT(RPG_CUT_ROWS, np < win.np);
+        WARP_UNIT(RPG_CUT_COLS, ne < win.ne);
         warp_stage(A, in, s_raw, pb, eb, np, ne, W, H); // raw rows pb - 2 .. pb + 2 np + 1, columns eb - 8 .. eb + 8 ne + 7
         __syncthreads();
         // A: rows of parity 0 in the first half of the workgroup, of parity 1 in the second (uniform in a wave)
         if (threadIdx.x < RGB_T / 2u) {
-            for (uint32_t it = threadIdx.x; it < np * ne; it += RGB_T / 2u)
+            for (uint32_t it = threadIdx.x; it < np * ne; it += RGB_T / 2u) {
+                WARP_PATH(RPG_A_EVEN, true);
                 warp_mhc_row<S, 0>(A, s_raw, s_e, it / ne, it % ne);
+            }
         } else {
-            for (uint32_t it = threadIdx.x - RGB_T / 2u; it < np * ne; it += RGB_T / 2u)
+            for (uint32_t it = threadIdx.x - RGB_T / 2u; it < np * ne; it += RGB_T / 2u) {
+                WARP_PATH(RPG_A_ODD, true);
                 warp_mhc_row<S, 1>(A, s_raw, s_e, it / ne, it % ne);
+            }
         }
         __syncthreads();
         // gather: a lane takes 4 output columns of one output row: every lane of the workgroup has its pixels
@@ -109,6 +132,8 @@ __global__ void __launch_bounds__(RGB_T) krgb_warp(const RgbArgs A, const WarpGe
             const uint32_t gr = threadIdx.x / (WARP_TW / 4u), gc = 4u * (threadIdx.x % (WARP_TW / 4u));
             const uint32_t j = i0 + gr, x = k0 + gc;
             int32_t E4[3][4] = {};
+            WARP_PATH(RPG_PIX, j <= i1 && x <= k1);
+            WARP_PATH(RPG_NOPIX, !(j <= i1 && x <= k1));
             if (j <= i1 && x <= k1) {
                 const int64_t by = static_cast<int64_t>(map[0]) * j + static_cast<int64_t>(map[1]) * x + 128;
                 const int64_t bx = static_cast<int64_t>(map[3]) * j + static_cast<int64_t>(map[4]) * x + 128;

@@ -1,7 +1,16 @@
 // mcraw_warp_dev.h -- the device code that the kernels sampling the MHC image through a 4 x 4 gather share (krgb_warp:
 // csrc/mcraw_warp.hip; krgb_mesh: csrc/mcraw_mesh.hip): staging of a tile's raw window, phase A of one lane, the weights of a phase,
 // the taps of one pixel from a tap origin inside the window's estimates, and the store phase.  The LDS arrays' sizes are mcraw_warp_args.h's.
+//
+// Hooks of a test build's path census, empty unless defined in front of this header (mcraw_rgb_paths.h does, for the source that
+// includes it under its switch; this header names none), as RGB_PATH of mcraw_rgb_dev.h:
+//   WARP_PATH(slot, cond)   the active lanes for which `cond` holds take path `slot` of the including kernel's family
+//   WARP_UNIT(slot, cond)   the workgroup's unit takes it (`cond` is uniform over the workgroup)
 #pragma once
+#ifndef WARP_PATH
+#define WARP_PATH(slot, cond)
+#define WARP_UNIT(slot, cond)
+#endif
 #include "mcraw_dev.h"
 #include "mcraw_rgb_args.h"
 #include "mcraw_rgb_dev.h"
@@ -84,8 +93,10 @@ __device__ __forceinline__ void warp_stage(const RgbArgs &A, const uint16_t *in,
         const int xs = eb - 8 + 8 * static_cast<int>(q);
         mcraw_u32x4 v;
         if (A.invec && xs >= 0 && xs + 8 <= W) {
+            WARP_PATH(RPG_LD_VEC, true);
             v = *gptr<const mcraw_u32x4>(row + xs);
         } else {
+            WARP_PATH(RPG_LD_ELEM, true);
             uint32_t e[8];
 #pragma unroll
             for (int k = 0; k < 8; k++)
@@ -105,6 +116,9 @@ __device__ __forceinline__ void warp_store(const RgbArgs &A, const int32_t *s_e,
     constexpr uint32_t ROWS = is_yuv(PK) ? 2u : 1u; // output rows of a lane
     const uint32_t lxid = threadIdx.x & (WARP_TW / 8u - 1u), lyid = threadIdx.x / (WARP_TW / 8u);
     const uint32_t xo = k0 + 8u * lxid, j0 = i0 + ROWS * lyid;
+    WARP_PATH(RPG_ST_IDLE_LY, lyid >= WARP_TH / ROWS);
+    WARP_PATH(RPG_ST_IDLE_X, lyid < WARP_TH / ROWS && xo >= A.Wo);
+    WARP_PATH(RPG_ST_IDLE_ROW, lyid < WARP_TH / ROWS && xo < A.Wo && j0 > i1);
     if (lyid < WARP_TH / ROWS && xo < A.Wo && j0 <= i1) {
         const uint32_t n = min(8u, A.Wo - xo);
         const RgbCol &col = A.col[A.percol ? f : 0u];

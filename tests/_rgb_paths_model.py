@@ -26,14 +26,21 @@ RES_TW, RES_LYMAX, RES_TROWS, RES_ECOLS, RES_TAPS = 64, 16, 32, 144, 9
 
 # the order of RgbPath in csrc/mcraw_rgb_paths.h
 FAMILIES = ("mhc", "bin2", "bin2y", "area", "res")
+GATHER_FAMILIES = ("warp", "mesh")  # krgb_warp, krgb_mesh and krgb_ha: their corpus and model are tests/_gather_paths_model.py's
+WALK_FAMILIES = FAMILIES + GATHER_FAMILIES + ("ha",)
 WALK = ("wg", "first", "later", "cross")
-PATHS = (["%s_%s" % (w, f) for f in FAMILIES for w in WALK]
+GATHER = ("ld_vec", "ld_elem", "a_even", "a_odd", "pix", "nopix", "cut_rows", "cut_cols", "tap_row_lo", "tap_row_hi", "tap_col_lo", "tap_col_hi",
+          "st_idle_ly", "st_idle_x", "st_idle_row")
+PATHS = (["%s_%s" % (w, f) for f in WALK_FAMILIES for w in WALK]
          + ["lut_lds", "lut_global", "idle_mhc_lane", "idle_mhc_rows", "idle_bin2", "idle_area", "idle_res",
             "ld_mhc_vec", "ld_mhc_elem", "ld_res_vec", "ld_res_elem", "ld_bin2_vec", "ld_bin2_elem", "ld_bin2y_vec", "ld_bin2y_elem",
             "ld_area_m2", "ld_area_m1", "ld_area_m0", "ld_area_tail", "ld_area_skip",
             "st_f_fast", "st_f_crop", "st_f_off", "st_c8_fast", "st_c8_crop", "st_c8_off", "st_c16_fast", "st_c16_crop", "st_c16_off",
             "st_h8_16_8", "st_h8_8_16", "st_h8_elem", "st_h16_fast", "st_h16_elem",
-            "st_yl_fast", "st_yl_crop", "st_yl_off", "st_yc_fast", "st_yc_crop", "st_yc_off"])
+            "st_yl_fast", "st_yl_crop", "st_yl_off", "st_yc_fast", "st_yc_crop", "st_yc_off"]
+         + ["%s_%s" % (f, g) for f in GATHER_FAMILIES for g in GATHER]
+         + ["mesh_narrow", "mesh_wide", "mesh_y_lo", "mesh_y_hi", "mesh_x_lo", "mesh_x_hi", "ha_ld_vec", "ha_ld_elem", "ha_continue", "ha_break"]
+         + ["ha_%s_%s" % (s, o) for s in ("main", "edge", "diag") for o in ("a", "b", "eq")])
 
 VARIANT_CAP = {"census": None, "grid1": 1, "grid3": 3, "poison": None, "poison1": 1}
 PRODUCT_OF = {"poison": "census", "poison1": "grid1"}  # the variants whose counts are another's
@@ -351,13 +358,18 @@ def _forms(c, keys, addr, n, align):
 def stores(S, c):
     """Every 8-sample piece of every output row is stored once, whichever kernel and walk: the form follows from its address (the
     output starts out_off bytes behind a 16-byte boundary) and from n, the samples of the 8 that exist."""
-    P, kind, es = plan(S), S["kind"], ES[S["kind"]]
-    Wo, Ho = P["Wo"], P["Ho"]
+    P = plan(S)
+    stores_of(c, S["kind"], P["Wo"], P["Ho"], S["n"], S["out_off"], out_frame_bytes(S))
+
+
+def stores_of(c, kind, Wo, Ho, nframes, out_off, frame_bytes):
+    """stores() for any kernel: nframes frames of Ho x Wo of `kind`, frame_bytes apart, from out_off bytes behind a 16-byte boundary."""
+    es, yuv, flt = ES[kind], kind in ("nv12", "p010"), kind in FLOAT_KINDS
     y, x = np.meshgrid(np.arange(Ho, dtype=np.int64), np.arange(0, Wo, 8, dtype=np.int64), indexing="ij")
     n = np.minimum(8, Wo - x)
-    for f in range(S["n"]):
-        base = S["out_off"] + f * out_frame_bytes(S)
-        if is_yuv(S):
+    for f in range(nframes):
+        base = out_off + f * frame_bytes
+        if yuv:
             _forms(c, ("st_yl_fast", "st_yl_crop", "st_yl_off"), base + (y * Wo + x) * es, n, 8 * es)
             odd = (y & 1) == 1
             _forms(c, ("st_yc_fast", "st_yc_crop", "st_yc_off"), (base + ((Ho + (y >> 1)) * Wo + x) * es)[odd], n[odd], 8 * es)
@@ -372,8 +384,8 @@ def stores(S, c):
                 c["st_h16_fast"] += int(fast.sum())
                 c["st_h16_elem"] += int((~fast).sum())
         else:
-            pre = "st_f" if is_float(S) else "st_c8" if es == 1 else "st_c16"
-            align = 16 if is_float(S) else 8 * es
+            pre = "st_f" if flt else "st_c8" if es == 1 else "st_c16"
+            align = 16 if flt else 8 * es
             for r in range(3):
                 _forms(c, (pre + "_fast", pre + "_crop", pre + "_off"), base + (r * Ho * Wo + y * Wo + x) * es, n, align)
 

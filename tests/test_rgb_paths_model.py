@@ -8,8 +8,10 @@ against).
   * the walk: any grid of 1 .. units x frames workgroups takes every unit exactly once; one workgroup crosses frames - 1 times;
   * the corpus holds what it was made for: per kernel two unit columns and rows, a unit count that 3 divides and one that it does
     not, every instance with a LUT, both LUT homes, the three input alignments, outputs on and off their grid;
-  * the five builds of build.RGB_PATH_VARIANTS compile and link (cross-compiled: no GPU needed), only the three demosaic sources
-    are compiled for them, and the switches' names occur in those three sources alone."""
+  * the five builds of build.RGB_PATH_VARIANTS compile and link (cross-compiled: no GPU needed), only the six demosaic sources
+    are compiled for them, and the switches' names occur in those sources alone: the census and the poison in all six, the grid's
+    cap in the three older ones (krgb_warp, krgb_mesh and krgb_ha take their limit from mcraw_rgb.hip).
+The counters of krgb_warp, krgb_mesh and krgb_ha, the tail of PATHS: tests/test_gather_paths_model.py."""
 import os
 import re
 import subprocess
@@ -22,6 +24,8 @@ from motioncam_decoder_amd import build as B
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "motioncam_decoder_amd", "csrc")
 THREE = ("mcraw_rgb.hip", "mcraw_area.hip", "mcraw_resample.hip")
+SIX = THREE + ("mcraw_warp.hip", "mcraw_mesh.hip", "mcraw_ha.hip")
+WHERE = {"MCRAW_PATHSR": SIX, "MCRAW_POISON_RGB": SIX, "MCRAW_RGB_GRID_CAP": THREE}
 
 
 def test_plans_are_the_headers(tmp_path):
@@ -51,9 +55,11 @@ def test_plans_are_the_headers(tmp_path):
 
 
 def test_every_counter_is_driven():
+    import _gather_paths_model as G
     assert set(T.DRIVEN) == set(T.PATHS) and set(T.DRIVEN_CAPPED) <= set(T.PATHS)
-    for k in T.PATHS:
-        assert T.DRIVEN[k] or T.DRIVEN_CAPPED.get(k), "no setting drives " + k
+    for k in T.PATHS:  # (krgb_warp's, krgb_mesh's and krgb_ha's counters: their own corpus, or the argued-zero list)
+        assert T.DRIVEN[k] or T.DRIVEN_CAPPED.get(k) or G.DRIVEN.get(k) or G.DRIVEN_CAPPED.get(k) or k in G.ARGUED_ZERO, "no setting drives " + k
+        assert not (T.DRIVEN[k] or T.DRIVEN_CAPPED.get(k)) or k not in G.NEW
     for name in T.SETTINGS:
         m = T.model(name)
         for k, names in T.DRIVEN.items():
@@ -115,13 +121,13 @@ def test_corpus_holds_what_it_was_made_for():
     assert sum(S["n"] * S["H"] * S["W"] for S in {(S["n"], S["H"], S["W"]): S for S in T.SETTINGS.values()}.values()) < 8000000
 
 
-def test_switch_names_stay_in_the_three_sources():
+def test_switch_names_stay_in_the_six_sources():
     names = sorted({re.sub(r"^-D([A-Za-z0-9_]+).*$", r"\1", f) for flags in B.RGB_PATH_VARIANTS.values() for f in flags})
     assert names == ["MCRAW_PATHSR", "MCRAW_POISON_RGB", "MCRAW_RGB_GRID_CAP"]
     for f in sorted(os.listdir(CSRC)):
         text = open(os.path.join(CSRC, f)).read()
         for n in names:
-            assert bool(re.search(r"\b%s\b" % n, text)) == (f in THREE), (f, n)
+            assert bool(re.search(r"\b%s\b" % n, text)) == (f in WHERE[n]), (f, n)
 
 
 @pytest.mark.parametrize("variant", list(B.RGB_PATH_VARIANTS))
@@ -130,8 +136,8 @@ def test_variant_compiles_and_links(variant, tmp_path, capfd):
     assert flags in list(B.TEST_VARIANTS)
     out = B.build_variant(str(tmp_path / ("libmcraw_rgbp_%s.so" % variant)), flags)
     assert os.path.getsize(out) > 0
-    # the switches are known to the three demosaic sources alone: nothing else is compiled for a variant
+    # the switches are known to the six demosaic sources alone: nothing else is compiled for a variant
     compiled = [ln for ln in capfd.readouterr().out.splitlines() if " -c " in ln]
-    assert all(ln.endswith(THREE) for ln in compiled), compiled
+    assert all(ln.endswith(SIX) for ln in compiled), compiled
     syms = subprocess.run(["nm", "-D", "--defined-only", out], capture_output=True, text=True, check=True).stdout
     assert "mcraw_diag_rgb_paths" in syms
